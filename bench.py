@@ -14,13 +14,19 @@ REINFORCE loss + backward through all 20 steps + ONE flat-gradient all-reduce (N
 clip_grad_value_ + AdamW.  `--mode rollout` times the forward-only (eval) rollout instead.
 Inputs are resident in HBM before timing.
 
-Prints ONE JSON line on rank 0 (schema in the task contract) with `roofline` for the nano
-PAFPN conv stack (HIP events around the conv section of every glimpse step, on the stream
-the kernels run on) and `cpu_baseline` (the CPU oracle timed on the host cores).
+Prints ONE JSON line on rank 0 (schema in the task contract).  A plain run sets up, warms up,
+times the K steps and prints the headline line; nothing else.  `--full` adds what takes extra
+work: `roofline` for the nano PAFPN conv stack (HIP events around the conv section of every
+glimpse step, on the stream the kernels run on), `roofline_backward` / `roofline_iteration`,
+the per-rank `multi_rank` diagnostics (N > 1) and `cpu_baseline` (the CPU oracle timed on the
+host cores).  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
+Inputs are seeded, and every training step (warm-up and timed) starts from the seeded weights and
+a fresh AdamW (TrainingStart): two builds given the same arguments compare output for output.
 """
 import argparse
 import json
 import os
+import random
 import sys
 import time
 from pathlib import Path
@@ -49,6 +55,80 @@ PMC_TRAFFIC_BYTES_B64_448 = {"train": 5.651e9, "rollout": 4.399e9}       # round
 # re-read is NOT algorithmic (36 of the 77 layers already avoid it) and is only reported as a labelled second figure.
 NANO_448_BWD_ELEMS_PER_PATCH = 2 * 17.44e6
 NANO_448_BWD_REREAD_ELEMS_PER_PATCH = 2 * 7.35e6
+# --dump-outputs: at most 64 MB in all; an array above DUMP_SAMPLE_ELEMS elements is replaced by a fixed, seeded sample of
+# that many of its elements (flattened, ascending index order, the same indices on every run)
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_ELEMS = 4 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor | number} as out_dir/<name>.npy: floating data as float32 (float64 stays float64), integer and
+    boolean data as float64 (exact).  Entries that are not tensors or numbers (None, ragged lists) are skipped."""
+    import numpy as np
+    conv = {}
+    for name, v in arrays.items():
+        if torch.is_tensor(v):
+            v = v.detach().cpu()
+            if v.dtype not in (torch.float32, torch.float64):
+                v = v.to(torch.float32 if v.is_floating_point() else torch.float64)
+            a = v.numpy()
+        elif isinstance(v, (bool, int, float)):
+            a = np.asarray(v, dtype=np.float64)
+        else:
+            continue
+        if a.size > DUMP_SAMPLE_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        conv[name] = a
+    total = sum(a.nbytes for a in conv.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes over the {DUMP_LIMIT_BYTES} byte limit"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+class TrainingStart:
+    """Every step of a training benchmark (warm-up and timed) starts from the same engine state: the parameters as set up
+    from the seed and a fresh AdamW (zero moments, step 0).  Each step does the same work as a step of a continuing run,
+    and what it computes is a function of the arguments alone.  Steps that continued from one another would compound the
+    run-to-run rounding of the backward's atomic gradient sums: AdamW turns the sign of a near-zero gradient into a
+    full lr step, and after a few steps two runs no longer train the same weights.  The restore is three device-side
+    arena copies per step."""
+
+    def __init__(self, model):
+        from jolineedle_amd import _lib
+        self.lib, self.eng, self.dev = _lib, model.engine(), model.device
+        model.grad_arena()                             # uploads the weights, sizes the arena
+        self.n = model._arena_numel
+        self.params = torch.zeros(self.n, device=self.dev)
+        self.zeros = torch.zeros(self.n, device=self.dev)
+        self.lib.check(self.eng.lib.jn_export_arena(self.eng.handle, 0, self.lib.ptr(self.params), self.n, 0,
+                                                    self.lib.current_stream(self.dev)), "jn_export_arena")
+
+    def restore(self):
+        import ctypes as C
+        lib, eng, stream = self.lib, self.eng, self.lib.current_stream(self.dev)
+        for what, src in ((0, self.params), (2, self.zeros), (3, self.zeros)):
+            lib.check(eng.lib.jn_import_arena(eng.handle, what, lib.ptr(src), self.n, stream), "jn_import_arena")
+        for group in (0, 1):
+            lib.check(eng.lib.jn_optimizer_steps(eng.handle, group, C.byref(C.c_int(0)), 1), "jn_optimizer_steps")
+
+    def trained_state(self, model):
+        """The state a caller holds after the step, in the reference layout: the AdamW first / second moments (after one
+        step from a fresh optimiser: 0.1 g and 0.001 g^2 of the step's clipped gradient g) and the BatchNorm running
+        statistics.  With the seeded starting parameters the moments fix the updated parameters, which are not written
+        themselves: AdamW's first update lr * g / (|g| + eps) turns the rounding of a gradient near zero into a
+        difference of up to lr."""
+        lib, eng, stream = self.lib, self.eng, self.lib.current_stream(self.dev)
+        out = {}
+        for what, name in ((2, "adam_exp_avg"), (3, "adam_exp_avg_sq")):
+            out[name] = torch.zeros(self.n, device=self.dev)
+            lib.check(eng.lib.jn_export_arena(eng.handle, what, lib.ptr(out[name]), self.n, 0, stream), "jn_export_arena")
+        model.pull_bn_statistics()
+        stats = [b.detach().reshape(-1) for n, b in model.named_buffers() if n.endswith(("running_mean", "running_var"))]
+        if stats:
+            out["bn_running_stats"] = torch.cat(stats)
+        return out
 
 
 def pmc_traffic(mode):
@@ -102,7 +182,10 @@ def bench_detector(args, ja, model_config, dev, rank, world, dist):
     tg = tg.to(dev)
     eng = model.engine()
 
+    initial = TrainingStart(model)
+
     def step():
+        initial.restore()
         model.engine_zero_grad()
         losses = model.yolox.loss_and_backward(patches, tg)
         _lib.check(eng.lib.jn_optimizer_step_group(eng.handle, 1, 1e-4, 0.01, 1.0, 1.0, _lib.current_stream(dev)), "opt")
@@ -113,9 +196,11 @@ def bench_detector(args, ja, model_config, dev, rank, world, dist):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        losses = step()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(losses, **initial.trained_state(model)))
     if rank == 0:
         # yolox-s PAFPN + head @448: 3.976 + 2.521 GMAC forward per patch; training ~ 3x forward
         tflops = 3.0 * 2.0 * (3.976e9 + 2.521e9) * (P / 448.0) ** 2 * B * args.steps / dt / 1e12
@@ -146,7 +231,9 @@ def bench_supervised(args, ja, model_config, dev, rank, world, dist):
     cfg = ja.CfgNode(patch_size=P, max_seq_len=T, min_keypoints=0, max_keypoints=2, binomial_keypoints=False,
                      stop_enabled=False, learning_rate=1e-4, yolo_lr=1e-4, gradient_accumulation=1, detection_enabled=True)
     trainer = ja.SupervisedTrainer(cfg, model)
+    initial = TrainingStart(model)
     for i in range(args.warmup):
+        initial.restore()
         trainer.train_iteration(batch, seed=i)
     if dist is not None:
         dist.barrier()
@@ -161,12 +248,16 @@ def bench_supervised(args, ja, model_config, dev, rank, world, dist):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
+        initial.restore()
         m = trainer.train_iteration(batch, seed=1000 + i)
         det_patches += int(m["trajectories"]["patches_yolox"].shape[0])
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict({k: v for k, v in m.items() if k != "trajectories"},
+                                            **initial.trained_state(model)))
     if rank == 0:
         print(json.dumps({
             "metric": f"glimpse-patches/sec ({P}px, seq-len {T}) supervised step",
@@ -289,7 +380,13 @@ def main():
     ap.add_argument("--seq-len", type=int, default=20)
     ap.add_argument("--patch-size", type=int, default=448)
     ap.add_argument("--grid", type=int, default=10, help="image side in patches")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also report what a plain run leaves out: conv-section HIP events and the roofline entries, "
+                         "per-rank diagnostics (N > 1), the CPU oracle baseline (1 GPU)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all)")
     ap.add_argument("--mode", choices=["train", "rollout", "detector", "supervised"], default="train",
                     help="train (default, the headline): full REINFORCE iteration; rollout: inference rollout; detector: "
                          "secondary, one detector training step (yolox-s, SimOTA loss, backward, AdamW) on --batch patches")
@@ -339,6 +436,7 @@ def main():
 
     B, T, P, G = args.batch, args.seq_len, args.patch_size, args.grid
     torch.manual_seed(12345)
+    random.seed(12345 + rank)                # ties of the supervised mode's teacher walks (jolineedle_amd/trajectory.py)
     if args.mode == "detector":
         return bench_detector(args, ja, model_config, dev, rank, world, dist)
     if args.mode == "supervised":
@@ -355,30 +453,37 @@ def main():
     cfg = ja.CfgNode(max_seq_len=T, entropy_weight=0.01, stop_enabled=True, reward_norm=True, seed=12345 + rank,
                      learning_rate=1e-4, gradient_accumulation=1)
     trainer = ja.ReinforceTrainer(cfg, model)
+    train = args.mode == "train"
+    initial = TrainingStart(model) if train else None      # the rollout modes leave the engine's state as it is
     images, bboxes, start = synth_inputs(B, G, P, 12345 + rank, dev)
     forced = None if args.sample else torch.randint(0, 8, (B, T), generator=torch.Generator().manual_seed(777 + rank)).to(dev)
     eng = model.engine()
-    eng.lib.jn_set_profiling(eng.handle, 1)
-
-    train = args.mode == "train"
+    if args.full:
+        eng.lib.jn_set_profiling(eng.handle, 1)
 
     def one_step():
+        """(executed glimpse steps, what the step computed: its metrics and the trajectory's buffers)"""
         env = ja.NeedleGeneralEnv(images, bboxes, P, T, 1, True, engine=eng)
         if train:
+            initial.restore()
             m = trainer.train_iteration(env, forced_actions=forced, start_positions=start, sample_actions=True,
                                         stop_early=not os.environ.get("JN_BENCH_NO_STOP_EARLY"))   # (measuring aid: no skip flags)
-            return m["steps"], m["loss"]
-        ro = trainer.rollout(env, forced_actions=forced, start_positions=start, keep_patches=False,
-                             do_detection=args.detect, sample_actions=True)
-        m = trainer.compute_metrics(ro)
-        return ro["rewards"].shape[1], m["loss"]
+            S = m["steps"]
+            ro = {k: v[:, :S + 1] if k in ("masks", "positions", "final_emb") else v[:, :S]
+                  for k, v in trainer._last_train_buffers.items()}
+        else:
+            ro = trainer.rollout(env, forced_actions=forced, start_positions=start, keep_patches=False,
+                                 do_detection=args.detect, sample_actions=True)
+            m = trainer.compute_metrics(ro)
+            S = ro["rewards"].shape[1]
+        return S, dict({"rollout_" + k: v for k, v in ro.items()}, **m)
 
     def sync():
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
 
-    if dist is not None and train:
+    if dist is not None and train and args.full:
         trainer.allreduce_timing = []        # (start, end) CUDA events around the iteration's ONE gradient all-reduce
 
     import ctypes as C
@@ -388,19 +493,22 @@ def main():
     t0 = time.perf_counter()
     patches, conv_ms, bwd_ms, glimpse_steps = 0, 0.0, 0.0, 0
     for _ in range(args.steps):
-        S, loss = one_step()
+        S, outputs = one_step()
         patches += B * S
         glimpse_steps += S
-        ms = C.c_float()
-        eng.lib.jn_last_timing(eng.handle, 1, C.byref(ms))
-        conv_ms += ms.value
-        if train:
-            eng.lib.jn_last_timing(eng.handle, 2, C.byref(ms))
-            bwd_ms += ms.value
+        if args.full:
+            ms = C.c_float()
+            eng.lib.jn_last_timing(eng.handle, 1, C.byref(ms))
+            conv_ms += ms.value
+            if train:
+                eng.lib.jn_last_timing(eng.handle, 2, C.byref(ms))
+                bwd_ms += ms.value
     torch.cuda.synchronize()
     own = time.perf_counter() - t0           # this rank's own K steps (before it waits for the others)
     sync()
     elapsed = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(outputs, **(initial.trained_state(model) if train else {})))
     t = torch.tensor([elapsed, float(patches)], device=dev, dtype=torch.float64)
     multi = None
     if dist is not None:
@@ -409,6 +517,9 @@ def main():
         tsum = t.clone()
         dist.all_reduce(tsum, op=dist.ReduceOp.SUM)
         elapsed, total_patches = float(tmax[0]), float(tsum[1])
+    else:
+        total_patches = float(patches)
+    if dist is not None and args.full:
         # diagnostics of the multi-rank run: every rank's own time per step and its all-reduce time per step (CUDA events
         # on the launch stream: the time the stream spends in / waiting for the collective, i.e. RCCL itself plus the
         # wait for the slowest rank's backward); the timed steps only
@@ -428,15 +539,8 @@ def main():
                                           "iteration (collective + wait for the slowest rank); mean over the timed steps"},
                  "forward_ms_per_pass_per_rank": r3(cols[:, 2]), "backward_ms_per_step_per_rank": r3(cols[:, 3]),
                  "backend": os.environ.get("JN_BENCH_BACKEND", "nccl")}
-    else:
-        total_patches = float(patches)
 
     if rank == 0:
-        conv_ms_per_launch = conv_ms / max(glimpse_steps, 1)  # one PAFPN pass over B patches
-        headline_shape = (B, P, args.dtype) == (64, 448, "f32")
-        esz = 2.0 if args.dtype == "bf16" else 4.0
-        algo_bytes = NANO_448_ELEMS_PER_PATCH * (P / 448.0) ** 2 * esz * B
-        achieved = algo_bytes / (conv_ms_per_launch * 1e-3) / 1e9
         actions = (f"sampled actions, early STOP (free-running: {glimpse_steps / args.steps:.2f} of {T} steps executed per "
                    f"trajectory batch)") if args.sample else "forced non-STOP actions (S=T)"
         out = {
@@ -454,66 +558,80 @@ def main():
                                 "env build + whole-batch rollout (forward, eval-mode BN) + REINFORCE loss",
                        "parallelism": f"dp{world} (independent agents per rank; one RCCL all-reduce of the flat "
                                       f"gradient per iteration)"},
-            "roofline": {"bound": "hbm", "kernel": "yolox-nano PAFPN forward conv stack (stem/dw3x3/pw_mfma/spp/upsample"
-                                                   + ("/bn_finalize, train-mode BN" if train else "") +
-                                                   "), one pass over the batch per glimpse step",
-                         "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "traffic": headline_shape and pmc_traffic(args.mode)[0] or None,
-                         "traffic_source": headline_shape and pmc_traffic(args.mode)[1] or None,
-                         "ms_per_launch": round(conv_ms_per_launch, 4),
-                         "algorithmic_bytes_per_launch": int(algo_bytes),
-                         "timing": "HIP events around the conv section of every glimpse step, on the launch stream "
-                                   "(jn_set_profiling / jn_last_timing); rocprofv3 kernel stats of the same command: "
-                                   "profiles/r04_*_train_iteration_kernel_stats.csv"},
         }
-        if train and args.config == "c3":
-            # second entry: the step-batched conv-stack backward (embed_fpn + PAFPN), priced at its ALGORITHMIC traffic:
-            # per conv layer read g_out and z_out, read x_in, write g_in = 2 (in + out) elements (139.5 MB / patch)
-            bwd_bytes = NANO_448_BWD_ELEMS_PER_PATCH * (P / 448.0) ** 2 * 4.0 * B
-            bwd_reread = NANO_448_BWD_REREAD_ELEMS_PER_PATCH * (P / 448.0) ** 2 * 4.0 * B
-            bwd_ms_per_pass = bwd_ms / max(glimpse_steps, 1)
-            bwd_ach = bwd_bytes / (bwd_ms_per_pass * 1e-3) / 1e9
-            bwd_traffic, bwd_src = pmc_traffic("backward") if headline_shape else (None, None)
-            out["roofline_backward"] = {
-                "bound": "hbm", "kernel": "yolox-nano PAFPN conv-stack backward (step-batched: fused 1x1 / depthwise data + "
-                                          "weight gradients, BN-backward reductions, stem weight gradient), per glimpse step",
-                "achieved": round(bwd_ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(bwd_ach / HBM_PEAK_GBS, 4),
-                "traffic": bwd_traffic, "traffic_source": bwd_src,
-                "ms_per_launch": round(bwd_ms_per_pass, 4), "algorithmic_bytes_per_launch": int(bwd_bytes),
-                "achieved_incl_one_bn_reduce_reread": round((bwd_bytes + bwd_reread) / (bwd_ms_per_pass * 1e-3) / 1e9, 1),
-                "note": "algorithmic = 2 (in + out) elements per layer; the labelled second figure adds one re-read of g_out and "
-                        "z_out per layer (what a separate BatchNorm-backward reduction pass costs) and is not a roofline claim",
-                "timing": "HIP events around the conv-stack backward of the iteration (jn_last_timing(2)); per-op table: "
-                          "profiles/r04_*_backward_table_f32.txt"}
-            # third entry: the whole iteration against the same roof — forward + backward algorithmic bytes of every
-            # executed glimpse step over the wall time of the iteration (everything else included in the time)
-            it_bytes = (algo_bytes + bwd_bytes) * glimpse_steps
-            it_ach = it_bytes / elapsed / 1e9
-            out["roofline_iteration"] = {
-                "bound": "hbm", "kernel": "whole REINFORCE iteration (conv-stack forward + backward algorithmic bytes of all "
-                                          "glimpse steps over the iteration's wall time)",
-                "achieved": round(it_ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(it_ach / HBM_PEAK_GBS, 4),
-                "algorithmic_bytes_per_iteration": int(it_bytes / max(args.steps, 1))}
-        if multi is not None:
-            out["multi_rank"] = multi
         if args.detect:
             out["metric"] += " + yolox-s detection on every visited patch"
             out["config"]["phase"] += "; do_detection=True (yolox-s PAFPN + head + NMS per glimpse)"
-            out["roofline"]["note"] = ("the encoder's conv stack is timed while the detector pass of the previous glimpse runs "
-                                       "beside it on the engine's second stream: not comparable with the headline figure")
         if args.config == "c5":
-            tflops = 2.0 * S_640_GMAC_PER_PATCH * (P / 640.0) ** 2 * B / (conv_ms_per_launch * 1e-3) / 1e12
             out["metric"] = f"glimpse-patches/sec ({P}px, seq-len {T}) REINFORCE step, gpt-mini + yolox-s encoder"
             out["config"]["workload"] = (f"configs[4] topology on {world} GPU: gpt-mini + yolox-s (dense 3x3) encoder, {P}px, "
                                          f"seq-len {T}, {B} agents/GPU, {actions}")
-            out["roofline"] = {"bound": "mfma", "kernel": "yolox-s PAFPN forward conv stack (dense 3x3 + 1x1 on "
-                                                          "v_mfma_f32_16x16x4_f32), one pass over the batch per glimpse step",
-                               "achieved": round(tflops, 2), "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                               "frac": round(tflops / MFMA_F32_PEAK_TFLOPS, 4), "traffic": None,
-                               "ms_per_launch": round(conv_ms_per_launch, 4)}
-        elif world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(P, T, 12345, train)
+        if args.full:
+            conv_ms_per_launch = conv_ms / max(glimpse_steps, 1)  # one PAFPN pass over B patches
+            headline_shape = (B, P, args.dtype) == (64, 448, "f32")
+            esz = 2.0 if args.dtype == "bf16" else 4.0
+            algo_bytes = NANO_448_ELEMS_PER_PATCH * (P / 448.0) ** 2 * esz * B
+            achieved = algo_bytes / (conv_ms_per_launch * 1e-3) / 1e9
+            out["roofline"] = {
+                "bound": "hbm", "kernel": "yolox-nano PAFPN forward conv stack (stem/dw3x3/pw_mfma/spp/upsample"
+                                          + ("/bn_finalize, train-mode BN" if train else "") +
+                                          "), one pass over the batch per glimpse step",
+                "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 4),
+                "traffic": headline_shape and pmc_traffic(args.mode)[0] or None,
+                "traffic_source": headline_shape and pmc_traffic(args.mode)[1] or None,
+                "ms_per_launch": round(conv_ms_per_launch, 4),
+                "algorithmic_bytes_per_launch": int(algo_bytes),
+                "timing": "HIP events around the conv section of every glimpse step, on the launch stream "
+                          "(jn_set_profiling / jn_last_timing); rocprofv3 kernel stats of the same command: "
+                          "profiles/r04_*_train_iteration_kernel_stats.csv"}
+            if train and args.config == "c3":
+                # second entry: the step-batched conv-stack backward (embed_fpn + PAFPN), priced at its ALGORITHMIC traffic:
+                # per conv layer read g_out and z_out, read x_in, write g_in = 2 (in + out) elements (139.5 MB / patch)
+                bwd_bytes = NANO_448_BWD_ELEMS_PER_PATCH * (P / 448.0) ** 2 * 4.0 * B
+                bwd_reread = NANO_448_BWD_REREAD_ELEMS_PER_PATCH * (P / 448.0) ** 2 * 4.0 * B
+                bwd_ms_per_pass = bwd_ms / max(glimpse_steps, 1)
+                bwd_ach = bwd_bytes / (bwd_ms_per_pass * 1e-3) / 1e9
+                bwd_traffic, bwd_src = pmc_traffic("backward") if headline_shape else (None, None)
+                out["roofline_backward"] = {
+                    "bound": "hbm", "kernel": "yolox-nano PAFPN conv-stack backward (step-batched: fused 1x1 / depthwise "
+                                              "data + weight gradients, BN-backward reductions, stem weight gradient), per "
+                                              "glimpse step",
+                    "achieved": round(bwd_ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(bwd_ach / HBM_PEAK_GBS, 4), "traffic": bwd_traffic, "traffic_source": bwd_src,
+                    "ms_per_launch": round(bwd_ms_per_pass, 4), "algorithmic_bytes_per_launch": int(bwd_bytes),
+                    "achieved_incl_one_bn_reduce_reread": round((bwd_bytes + bwd_reread) / (bwd_ms_per_pass * 1e-3) / 1e9, 1),
+                    "note": "algorithmic = 2 (in + out) elements per layer; the labelled second figure adds one re-read of "
+                            "g_out and z_out per layer (what a separate BatchNorm-backward reduction pass costs) and is not "
+                            "a roofline claim",
+                    "timing": "HIP events around the conv-stack backward of the iteration (jn_last_timing(2)); per-op table: "
+                              "profiles/r04_*_backward_table_f32.txt"}
+                # third entry: the whole iteration against the same roof — forward + backward algorithmic bytes of every
+                # executed glimpse step over the wall time of the iteration (everything else included in the time)
+                it_bytes = (algo_bytes + bwd_bytes) * glimpse_steps
+                it_ach = it_bytes / elapsed / 1e9
+                out["roofline_iteration"] = {
+                    "bound": "hbm", "kernel": "whole REINFORCE iteration (conv-stack forward + backward algorithmic bytes of "
+                                              "all glimpse steps over the iteration's wall time)",
+                    "achieved": round(it_ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(it_ach / HBM_PEAK_GBS, 4),
+                    "algorithmic_bytes_per_iteration": int(it_bytes / max(args.steps, 1))}
+            if multi is not None:
+                out["multi_rank"] = multi
+            if args.detect:
+                out["roofline"]["note"] = ("the encoder's conv stack is timed while the detector pass of the previous glimpse "
+                                           "runs beside it on the engine's second stream: not comparable with the headline "
+                                           "figure")
+            if args.config == "c5":
+                tflops = 2.0 * S_640_GMAC_PER_PATCH * (P / 640.0) ** 2 * B / (conv_ms_per_launch * 1e-3) / 1e12
+                out["roofline"] = {"bound": "mfma", "kernel": "yolox-s PAFPN forward conv stack (dense 3x3 + 1x1 on "
+                                                              "v_mfma_f32_16x16x4_f32), one pass over the batch per glimpse "
+                                                              "step",
+                                   "achieved": round(tflops, 2), "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                   "frac": round(tflops / MFMA_F32_PEAK_TFLOPS, 4), "traffic": None,
+                                   "ms_per_launch": round(conv_ms_per_launch, 4)}
+            elif world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(P, T, 12345, train)
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

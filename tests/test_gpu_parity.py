@@ -2248,7 +2248,8 @@ def test_bench_multi_rank_launch_reports_every_rank(ranks):
     root = Path(__file__).resolve().parent.parent
     per_rank = 16 // ranks
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--batch",
-                        str(per_rank), "--grid", "3", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        str(per_rank), "--grid", "3", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
+                       timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -2263,6 +2264,40 @@ def test_bench_multi_rank_launch_reports_every_rank(ranks):
     assert all(0 < v < out["ms_per_step"] for v in mr["allreduce_ms"]["per_rank"])
     assert 5_000_000 < mr["allreduce_ms"]["bytes"] < 6_500_000      # the 1.37 M floats of SURVEY §8e (padded arena)
     assert all(v > 0 for v in mr["forward_ms_per_pass_per_rank"] + mr["backward_ms_per_step_per_rank"])
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain `bench.py` run (fresh child process) prints the headline line only — no roofline, no CPU baseline — with
+    `--steps` timed steps, and `--dump-outputs` writes the last timed step's metrics, trajectory and optimiser state.
+    Every step trains from the same seeded start, so a second run computes the same outputs up to the rounding of the
+    backward's atomic gradient sums."""
+    import json
+    import subprocess
+    root = Path(__file__).resolve().parent.parent
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch",
+                            "4", "--grid", "3", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["unit"] == "glimpse-patches/s" and out["dtype"] == "f32"
+        assert abs(out["value"] - 4 * 20 / (out["ms_per_step"] * 1e-3)) < 0.02 * out["value"]
+        assert not {"roofline", "roofline_backward", "roofline_iteration", "cpu_baseline"} & set(out)
+        arrays = {f.stem: np.load(f) for f in d.glob("*.npy")}
+        assert {"loss", "rollout_logits", "rollout_positions", "adam_exp_avg", "adam_exp_avg_sq"} <= set(arrays)
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["rollout_logits"].shape == (4, 20, 9) and np.isfinite(arrays["adam_exp_avg"]).all()
+        runs.append(arrays)
+    assert set(runs[0]) == set(runs[1])
+    for k in ("rollout_actions", "rollout_positions", "rollout_rewards", "rollout_returns", "steps"):
+        assert np.array_equal(runs[0][k], runs[1][k]), k
+    for k, a in runs[0].items():
+        scale = max(float(np.abs(a).max()), 1e-30)
+        assert np.abs(a - runs[1][k]).max() <= 1e-4 * scale, k
 
 
 # --------------------------------------------------------------------------------------

@@ -318,3 +318,25 @@ def test_every_library_switch_is_documented():
     design = (root / "DESIGN.md").read_text()
     assert len(names) > 20
     assert not sorted(n for n in names if n not in design)
+
+
+def test_bench_dump_outputs_writes_float_arrays_under_the_limit(tmp_path):
+    """bench.py --dump-outputs: floating data as float32 (float64 kept), integers / booleans as float64, non-array entries
+    skipped, an array above the sample size replaced by the same seeded sample on every call, 64 MB at most in all."""
+    import bench
+    big = torch.arange(bench.DUMP_SAMPLE_ELEMS + 1000, dtype=torch.float32)
+    arrays = {"loss": torch.tensor(1.5), "logits": torch.randn(2, 3, 9), "positions": torch.arange(6).view(3, 2),
+              "masks": torch.ones(2, 3, dtype=torch.bool), "half": torch.ones(4, dtype=torch.float16),
+              "wide": torch.ones(3, dtype=torch.float64), "steps": 20, "bboxes": [[None]], "patches": None, "big": big}
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(d), arrays)
+    got = {f.stem: np.load(f) for f in (tmp_path / "a").glob("*.npy")}
+    assert set(got) == {"loss", "logits", "positions", "masks", "half", "wide", "steps", "big"}
+    assert got["loss"].dtype == np.float32 and got["loss"].shape == () and float(got["loss"]) == 1.5
+    assert got["positions"].dtype == np.float64 and np.array_equal(got["positions"], np.arange(6).reshape(3, 2))
+    assert got["masks"].dtype == np.float64 and got["half"].dtype == np.float32 and got["wide"].dtype == np.float64
+    assert float(got["steps"]) == 20.0
+    assert got["big"].shape == (bench.DUMP_SAMPLE_ELEMS,) and np.all(np.diff(got["big"]) > 0)
+    assert np.array_equal(got["big"], np.load(tmp_path / "b" / "big.npy"))
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "c"), {f"x{i}": big for i in range(5)})

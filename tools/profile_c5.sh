@@ -6,7 +6,7 @@ TAG=${1:-r02}
 OUT=$PWD/gpurun_out
 export TMPDIR=/tmp
 for mode in train rollout; do
-  timeout -k 10 200 python3 bench.py --config c5 --mode $mode --steps 3 --warmup 1 --no-cpu-baseline > $OUT/${TAG}_bench_c5_$mode.json 2>/dev/null
+  timeout -k 10 200 python3 bench.py --config c5 --mode $mode --steps 3 --warmup 1 --full --no-cpu-baseline > $OUT/${TAG}_bench_c5_$mode.json 2>/dev/null
   rm -rf $OUT/prof_c5_$mode
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c5_$mode -- python3 bench.py --config c5 --mode $mode --steps 2 --warmup 1 --no-cpu-baseline > $OUT/${TAG}_c5_$mode.log 2>&1
   find $OUT/prof_c5_$mode -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/${TAG}_c5_${mode}_kernel_stats.csv

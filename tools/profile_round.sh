@@ -25,7 +25,7 @@ python3 tools/pmc_traffic.py $OUT/${TAG}_pmc_fetch.csv $OUT/${TAG}_pmc_write.csv
 rm -rf $OUT/prof_fetch $OUT/prof_write
 for m in "rollout" "train --sample" "rollout --sample"; do
   n=$(echo $m | tr -d ' -')
-  timeout -k 10 200 python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --mode $m > $OUT/${TAG}_bench_$n.json 2>/dev/null
+  timeout -k 10 200 python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --mode $m > $OUT/${TAG}_bench_$n.json 2>/dev/null
 done
-timeout -k 10 200 python3 bench.py --steps 5 --warmup 2 > $OUT/${TAG}_bench_train.json 2>/dev/null
+timeout -k 10 200 python3 bench.py --steps 5 --warmup 2 --full > $OUT/${TAG}_bench_train.json 2>/dev/null
 tail -c 300 $OUT/${TAG}_bench_train.json
