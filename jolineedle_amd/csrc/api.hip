@@ -680,8 +680,7 @@ static inline int det_slot_base(const jn_ctx* ctx);   // first workspace slot of
 static int ensure_defer_tables(jn_ctx* ctx, Net& net) {
   if (net.defer_built) return JN_OK;
   net.defer_built = true;
-  static const bool off = std::getenv("JN_NO_DEFER_BN") != nullptr;
-  bool ok = !off && net.depthwise && net.act_dtype == JN_F32 && ctx->params;
+  bool ok = net.depthwise && net.act_dtype == JN_F32 && ctx->params;
   const int n_ops = net.n_backbone_ops < 0 ? (int)net.ops.size() : net.n_backbone_ops;
   for (int oi = 0; ok && oi < n_ops; ++oi) {
     const Op& op = net.ops[oi];
@@ -782,32 +781,32 @@ static int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int 
   // consumers read the batch sums (ChanTab in jn_kernels.h), one finalize launch closes the pass
   if (train && !with_head && (rc = ensure_defer_tables(ctx, net))) return rc;
   const bool defer = train && !with_head && net.defer_ok;
-  auto deferred = [&](const Op& op) { return defer && (long long)N * op.out.H * op.out.W <= jn_defer_max_m(); };
+  auto deferred = [&](const Op& op) { return defer && (long long)N * op.out.H * op.out.W <= JN_DEFER_MAX_M; };
   auto ptr = [&](const View& v) { return view_ptr(net, slot, MB, v); };
   auto tab = [&](const View& v) {
     ChanTab t = view_tab(net, slot, v);
     bool any = false;                       // does the view hold a channel whose table is deferred in this pass?
     if (defer) {
       const int off = net.tab_off[v.buf] + v.coff;
-      for (int c = 0; c < v.C && !any; ++c) any = net.h_td_hw[off + c] > 0.0f && (double)N * net.h_td_hw[off + c] <= (double)jn_defer_max_m();
+      for (int c = 0; c < v.C && !any; ++c) any = net.h_td_hw[off + c] > 0.0f && (double)N * net.h_td_hw[off + c] <= (double)JN_DEFER_MAX_M;
     }
     if (any) {
       const int off = net.tab_off[v.buf] + v.coff;
       t.dsrc = net.td_src + off; t.dhw = net.td_hw + off; t.dgoff = net.td_goff + off; t.dboff = net.td_boff + off;
-      t.dparams = ctx->params; t.dstats = stats; t.drep_stride = rep_stride; t.dN = N; t.dmax = jn_defer_max_m();
+      t.dparams = ctx->params; t.dstats = stats; t.drep_stride = rep_stride; t.dN = N; t.dmax = JN_DEFER_MAX_M;
       // channel runs for the kernel arguments (at most four: a concat of a few producers); more: the arrays above
       int ns = 0;
       bool fits = true;
       for (int c = 0; c < v.C && fits;) {
         const int tc = off + c;
-        const bool d = net.h_td_hw[tc] > 0.0f && (double)N * net.h_td_hw[tc] <= (double)jn_defer_max_m();
+        const bool d = net.h_td_hw[tc] > 0.0f && (double)N * net.h_td_hw[tc] <= (double)JN_DEFER_MAX_M;
         int e = c + 1;
         if (d) {
           while (e < v.C && net.h_td_src[off + e] == net.h_td_src[tc] + (e - c) && net.h_td_goff[off + e] == net.h_td_goff[tc] + (e - c) &&
                  net.h_td_boff[off + e] == net.h_td_boff[tc] + (e - c) && net.h_td_hw[off + e] == net.h_td_hw[tc])
             ++e;
         } else {
-          while (e < v.C && !(net.h_td_hw[off + e] > 0.0f && (double)N * net.h_td_hw[off + e] <= (double)jn_defer_max_m())) ++e;
+          while (e < v.C && !(net.h_td_hw[off + e] > 0.0f && (double)N * net.h_td_hw[off + e] <= (double)JN_DEFER_MAX_M)) ++e;
         }
         if (ns == 4) { fits = false; break; }
         const ChanTab::Run run{c, e, d ? net.h_td_src[tc] : -1, net.h_td_goff[tc], net.h_td_boff[tc], net.h_td_hw[tc]};
@@ -854,8 +853,7 @@ static int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int 
       case OP_CONV3:
       case OP_DW: {
         const ConvW& cw = net.convs[op.wslot];
-        static const bool no_fused_eval = std::getenv("JN_NO_FUSED_EVAL") != nullptr;
-        if (!train && !no_fused_eval && net.act_dtype == JN_F32 && op.kind == OP_DW && oi + 1 < n_ops) {
+        if (!train && net.act_dtype == JN_F32 && op.kind == OP_DW && oi + 1 < n_ops) {
           // eval: DWConv = depthwise + pointwise in one kernel, the depthwise output stays on chip
           const Op& nx = net.ops[oi + 1];
           if (nx.kind == OP_PW && nx.in.buf == op.out.buf && nx.in.coff == op.out.coff && nx.in.C == op.out.C &&
@@ -958,7 +956,7 @@ static int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int 
     fa.goff = net.fd_goff; fa.boff = net.fd_boff; fa.params = ctx->params; fa.t0 = net.fd_t0; fa.t1 = net.fd_t1;
     fa.tab = net.tab + (size_t)slot * 3 * net.tab_channels; fa.tab_channels = net.tab_channels; fa.save = save;
     fa.run_mean = net.fd_rm; fa.run_var = net.fd_rv; fa.eps = kBnEps; fa.momentum = kBnMomentum;
-    fa.skip_flag = skip_flag; fa.skip_when = skip_when; fa.defer_max_m = jn_defer_max_m();
+    fa.skip_flag = skip_flag; fa.skip_when = skip_when; fa.defer_max_m = JN_DEFER_MAX_M;
     launch_bn_finalize_all(fa, s);
   }
   JN_HIP(hipGetLastError());
@@ -1154,7 +1152,6 @@ static int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int s
   static const bool no_aux = std::getenv("JN_NO_AUX_STREAM") != nullptr;
   bool aux_used = false;
   if (!no_aux) { int ra = ensure_aux_stream(ctx); if (ra) return ra; }
-  static const bool no_red_fusion = std::getenv("JN_NO_FUSED_REDUCE") != nullptr;
   const int n_ops_b = (with_head || net.n_backbone_ops < 0) ? (int)net.ops.size() : net.n_backbone_ops;
   // JN_BWD_PROFILE=1: HIP events around the launches of every op, table on stderr (a measuring aid; use it together with
   // JN_NO_AUX_STREAM=1 so that the wide weight-gradient GEMMs are inside the brackets)
@@ -1216,11 +1213,10 @@ static int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int s
                              grad_of(ctx, cw.gamma_dev), grad_of(ctx, cw.beta_dev), cw.cout, s, sb, red_done.count(op.wslot) ? 1 : 0);
       }
       float* gw = grad_of(ctx, cw.w_dev);
-      static const bool no_fused = std::getenv("JN_NO_FUSED_BWD") != nullptr;
       // a merged pair too wide for the fused kernel is differentiated as its two halves (independent output rows)
       const bool whole = pw_bwd_fused_supported(cw.cout, cw.cin);
       const bool halves = !whole && !cw.prefix2.empty() && 2 * cw.cout_first == cw.cout && pw_bwd_fused_supported(cw.cout_first, cw.cin);
-      if (op.kind == OP_PW && net.act_dtype == JN_F32 && !no_fused && (whole || halves)) {
+      if (op.kind == OP_PW && net.act_dtype == JN_F32 && (whole || halves)) {
         const int parts = whole ? 1 : 2, pc = cw.cout / parts;
         for (int part = 0; part < parts; ++part) {
           const int c0 = part * pc;
@@ -1239,8 +1235,7 @@ static int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int s
           }
           // BN-backward sums of the input's producer(s) in this kernel's epilogue: it must write the FINAL gradient of
           // the view (sole reader, or the shortcut folded in) — one run, or the two halves of a CSP conv3's input
-          if (parts == 1 && (!op.acc_in || folded) && !no_red_fusion && pw_bwd_fused_reduces_input(pc, cw.cin)) {
-            static const bool no_half = std::getenv("JN_NO_HALF_REDUCE") != nullptr;
+          if (parts == 1 && (!op.acc_in || folded) && pw_bwd_fused_reduces_input(pc, cw.cin)) {
             const int fa_idx = folded ? shortcut_addact[obi] : -1;
             auto base_of = [&](const RedRun& r) {
               const ConvW& pcw = net.convs[r.wslot];
@@ -1251,10 +1246,8 @@ static int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int s
               if (r.half < 0) red_done.insert(r.wslot); else red_half[r.wslot] |= 1 << r.half;
             };
             RedRun r0, r1;
-            static const bool no_red2 = std::getenv("JN_NO_RED2") != nullptr;
             // RED2: a run that is a shortcut sum -> sums of the conv behind it (its raw output and table instead of the input's)
             auto red2 = [&](int coff, int C, int fidx) {
-              if (no_red2) return false;
               int add = -1;
               const int conv = shortcut_sum_conv(net, obi, op.in.buf, coff, C, fidx, &add);
               if (conv < 0) return false;
@@ -1266,11 +1259,11 @@ static int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int s
               red_done.insert(co.wslot);
               return true;
             };
-            if (red_segment(net, obi, op.in.buf, op.in.coff, op.in.C, fa_idx, r0) && (r0.half < 0 || !no_half)) {
+            if (red_segment(net, obi, op.in.buf, op.in.coff, op.in.C, fa_idx, r0)) {
               fa.red_in = base_of(r0); fa.red_rep_stride = rep_stride; mark(r0);
             } else if (red2(op.in.coff, op.in.C, fa_idx)) {
               fa.red_split = op.in.C;
-            } else if (!no_half && op.in.C % 32 == 0 && !folded) {
+            } else if (op.in.C % 32 == 0 && !folded) {
               const int hC = op.in.C / 2;
               bool ok0 = red_segment(net, obi, op.in.buf, op.in.coff, hC, -1, r0);
               const bool ok1 = red_segment(net, obi, op.in.buf, op.in.coff + hC, hC, -1, r1);
@@ -1292,8 +1285,7 @@ static int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int s
         }
         continue;
       }
-      static const bool no_fused_dw = std::getenv("JN_NO_FUSED_DW") != nullptr;
-      if (op.kind == OP_DW && net.act_dtype == JN_F32 && !no_fused && !no_fused_dw &&
+      if (op.kind == OP_DW && net.act_dtype == JN_F32 &&
           dw_bwd_fused_supported(cw.cout, op.in.H, op.in.W, op.out.H, op.out.W, op.stride)) {
         DwBwdFusedArgs fa{};
         fa.g = gp_out; fa.g_ld = gld_out; fa.z = (const float*)ptr(op.out); fa.z_ld = ld(op.out); fa.ot = tab(op.out);
@@ -1307,24 +1299,21 @@ static int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int s
         // more than the separate pass costs.  A view that only the network's outside could also write (an FPN output) and
         // that gets no outside gradient in this backward (fpn_zero) is an ordinary single-consumer output: this kernel
         // then WRITES its gradient (the buffer holds zeros) and forms the producer's sums like for any other.
-        static const bool no_s2_red = std::getenv("JN_NO_S2_RED") != nullptr;
-        if (!no_red_fusion && (op.stride == 1 || !no_s2_red)) {
-          bool ext_zero = false;
-          for (int i = 0; i < 3; ++i) ext_zero = ext_zero || (((fpn_zero >> i) & 1) && views_overlap(op.in, net.fpn[i]));
-          if (!op.acc_in || ext_zero) {
-            const int prod = sole_producer(net, obi, fpn_zero);
-            if (prod >= 0) {
-              const ConvW& pcw = net.convs[net.ops[prod].wslot];
-              fa.red_in = net.bred + 2 * pcw.stat_off; fa.red_rep_stride = rep_stride;
-              fa.accumulate = 0;                      // sole reader: nothing but the (zero) outside seed was there before
-              red_done.insert(net.ops[prod].wslot);
-            }
+        bool ext_zero = false;
+        for (int i = 0; i < 3; ++i) ext_zero = ext_zero || (((fpn_zero >> i) & 1) && views_overlap(op.in, net.fpn[i]));
+        if (!op.acc_in || ext_zero) {
+          const int prod = sole_producer(net, obi, fpn_zero);
+          if (prod >= 0) {
+            const ConvW& pcw = net.convs[net.ops[prod].wslot];
+            fa.red_in = net.bred + 2 * pcw.stat_off; fa.red_rep_stride = rep_stride;
+            fa.accumulate = 0;                      // sole reader: nothing but the (zero) outside seed was there before
+            red_done.insert(net.ops[prod].wslot);
           }
         }
         launch_dw_bwd_fused(fa, s);
         continue;
       }
-      if (op.kind == OP_STEM && net.act_dtype == JN_F32 && !no_fused) {
+      if (op.kind == OP_STEM && net.act_dtype == JN_F32) {
         StemArgs a{ss.src, ss.positions, ss.pos_stride, ss.sample_stride, ss.chan_stride, ss.row_stride, net.P, N, cw.cout,
                    cw.w_dev, nullptr, 0, JN_F32, nullptr, 0, nullptr, 0};
         launch_stem_bwd_weight(a, gp_out, gld_out, gw, ctx->wpart, s, sb, (const float*)ptr(op.out), ld(op.out),
@@ -1410,8 +1399,6 @@ static int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int s
         // and that layer takes the fused backward kernel, the kernel adds g[sum] while it writes its data gradient (one
         // read of g[sum] instead of a copy pass — read, read-modify-write — over the largest 16 / 32-channel maps)
         {
-          static const bool no_fold = std::getenv("JN_NO_SHORTCUT_FOLD") != nullptr;
-          static const bool no_fused2 = std::getenv("JN_NO_FUSED_BWD") != nullptr;
           int conv1 = -1, readers = 0;
           for (int j = 0; j < n_ops_b; ++j) {
             const Op& o = net.ops[j];
@@ -1420,7 +1407,7 @@ static int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int s
               if (o.kind == OP_PW && o.in.buf == op.res.buf && o.in.coff == op.res.coff && o.in.C == op.res.C && j < obi) conv1 = j;
             }
           }
-          bool fold = !no_fold && !no_fused2 && !op.acc_res && readers == 1 && conv1 >= 0 && net.act_dtype == JN_F32;
+          bool fold = !op.acc_res && readers == 1 && conv1 >= 0 && net.act_dtype == JN_F32;
           if (fold) {
             const Op& c1 = net.ops[conv1];
             const ConvW& cw1 = net.convs[c1.wslot];
@@ -2241,8 +2228,8 @@ static int build_grad_layer_table(jn_ctx* ctx) {
   return JN_OK;
 }
 
-// GPT backward over a trajectory: scratch (sized for either kernel) + launch.  The batched kernels are the default;
-// JN_GPT_BWD_V1=1 keeps the one-workgroup-per-agent kernel (diagnostic), which also takes the shapes the batched one refuses.
+// GPT backward over a trajectory: scratch (sized for either kernel) + launch.  The batched kernels are the default; the
+// one-workgroup-per-agent kernel takes the shapes the batched one refuses.
 static int launch_gpt_bwd(jn_ctx* ctx, GptBwdArgs& ba, hipStream_t s) {
   const jn_config& c = ctx->cfg;
   const int L = ba.T + 1, nL = c.n_layer, nh = c.n_head, C = c.n_embd;
@@ -2256,24 +2243,20 @@ static int launch_gpt_bwd(jn_ctx* ctx, GptBwdArgs& ba, hipStream_t s) {
     ctx->gpt_bwd_scratch_floats = need;
   }
   ba.scratch = ctx->gpt_bwd_scratch; ba.scratch_per_agent = per_agent;
-  static const bool v1 = std::getenv("JN_GPT_BWD_V1") != nullptr;
-  if (!v1) {
-    std::vector<GptLayerPtrs> W(nL), G(nL);
-    for (int l = 0; l < nL; ++l) {
-      const GptW::Layer& y = ctx->gpt.layers[l];
-      W[l] = GptLayerPtrs{y.ln1_w, y.ln1_b, y.qkv_wt, y.qkv_b, y.proj_wt, y.proj_b, y.ln2_w, y.ln2_b, y.fc_wt, y.fc_b, y.fc2_wt, y.fc2_b};
-      G[l] = GptLayerPtrs{grad_of(ctx, y.ln1_w), grad_of(ctx, y.ln1_b), grad_of(ctx, y.qkv_wt), grad_of(ctx, y.qkv_b),
-                          grad_of(ctx, y.proj_wt), grad_of(ctx, y.proj_b), grad_of(ctx, y.ln2_w), grad_of(ctx, y.ln2_b),
-                          grad_of(ctx, y.fc_wt), grad_of(ctx, y.fc_b), grad_of(ctx, y.fc2_wt), grad_of(ctx, y.fc2_b)};
-    }
-    if (launch_gpt_backward_batched(ba, W.data(), G.data(), s) == 0) return JN_OK;
+  std::vector<GptLayerPtrs> W(nL), G(nL);
+  for (int l = 0; l < nL; ++l) {
+    const GptW::Layer& y = ctx->gpt.layers[l];
+    W[l] = GptLayerPtrs{y.ln1_w, y.ln1_b, y.qkv_wt, y.qkv_b, y.proj_wt, y.proj_b, y.ln2_w, y.ln2_b, y.fc_wt, y.fc_b, y.fc2_wt, y.fc2_b};
+    G[l] = GptLayerPtrs{grad_of(ctx, y.ln1_w), grad_of(ctx, y.ln1_b), grad_of(ctx, y.qkv_wt), grad_of(ctx, y.qkv_b),
+                        grad_of(ctx, y.proj_wt), grad_of(ctx, y.proj_b), grad_of(ctx, y.ln2_w), grad_of(ctx, y.ln2_b),
+                        grad_of(ctx, y.fc_wt), grad_of(ctx, y.fc_b), grad_of(ctx, y.fc2_wt), grad_of(ctx, y.fc2_b)};
   }
+  if (launch_gpt_backward_batched(ba, W.data(), G.data(), s) == 0) return JN_OK;
   launch_gpt_backward(ba, s);
   return JN_OK;
 }
 
 }  // extern "C"
-static bool bf16_train_allowed() { static const bool on = std::getenv("JN_ALLOW_BF16_TRAIN") != nullptr; return on; }
 static int reinforce_backward_impl(jn_ctx* ctx, const jn_rollout_out* out, int S, int stop_early, hipStream_t s);
 static int check_train_outputs(jn_ctx* ctx, const jn_rollout_out* out) {
   JN_CHECK(out->logits_dev && out->actions_dev && out->returns_dev && out->logit_masks_dev && out->positions_dev &&
@@ -2281,9 +2264,9 @@ static int check_train_outputs(jn_ctx* ctx, const jn_rollout_out* out) {
            JN_EINVAL, "training needs logits/actions/returns/logit_masks/positions/final_emb/rewards/masks outputs");
   JN_CHECK(!ctx->cfg.no_patch_emb, JN_ESTATE, "training without a patch encoder is not supported");
   JN_CHECK(ctx->cfg.block_size <= 62, JN_EINVAL, "training supports block_size <= 62");
-  // batch-statistics BatchNorm on bf16-rounded pre-activations is ill-conditioned (JN_ALLOW_BF16_TRAIN=1
-  // lifts the refusal for the measurement behind that statement, tools/bf16_train_probe.py)
-  JN_CHECK(ctx->cfg.act_dtype == JN_F32 || bf16_train_allowed(), JN_ESTATE, "training needs act_dtype = fp32 (bf16 is the inference mode)");
+  // batch-statistics BatchNorm on bf16-rounded pre-activations is ill-conditioned (the measurement behind
+  // that statement: profiles/r03_bf16_train_probe.txt)
+  JN_CHECK(ctx->cfg.act_dtype == JN_F32, JN_ESTATE, "training needs act_dtype = fp32 (bf16 is the inference mode)");
   return JN_OK;
 }
 extern "C" {
@@ -2435,7 +2418,7 @@ static int supervised_forward_impl(jn_ctx* ctx, const float* patches_dev, const 
   JN_CHECK(ctx->weights_loaded, JN_ESTATE, "jn_load_weights has not been called");
   const jn_config& c = ctx->cfg;
   JN_CHECK(!c.no_patch_emb, JN_ESTATE, "training without a patch encoder is not supported");
-  JN_CHECK(c.act_dtype == JN_F32 || bf16_train_allowed(), JN_ESTATE, "training needs act_dtype = fp32 (bf16 is the inference mode)");
+  JN_CHECK(c.act_dtype == JN_F32, JN_ESTATE, "training needs act_dtype = fp32 (bf16 is the inference mode)");
   JN_CHECK(T >= 1 && T <= c.block_size && c.block_size <= 62, JN_EINVAL, "sequence length %d out of range", T);
   JN_CHECK(B >= 1 && B * T <= c.max_batch, JN_EINVAL, "B*T = %d patches exceed max_batch = %d", B * T, c.max_batch);
   JN_CHECK(!c.use_pos_emb || positions_dev, JN_EINVAL, "positions are required when use_pos_emb is set");

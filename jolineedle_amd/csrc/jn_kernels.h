@@ -35,7 +35,7 @@ struct ChanTab {
   const double* dstats;    // [JN_NREP_DEFER used][drep_stride] batch sums of the workspace slot
   long long drep_stride;
   int dN;                  // patches in this pass
-  long long dmax;          // deferral limit in pixels (dN * dhw <= dmax: deferred), jn_defer_max_m()
+  long long dmax;          // deferral limit in pixels (dN * dhw <= dmax: deferred), JN_DEFER_MAX_M
   // The same information as up to four channel runs in the kernel arguments (scalar registers, no memory round trip
   // before the sums can be requested): channels [c0, c1) of the view are BatchNorm channels stat0 + (c - c0) with affine
   // at g0 / b0 + (c - c0) and pixel count dN * hw — or, with stat0 < 0, plain table entries.  nseg == 0: use the arrays.
@@ -45,8 +45,7 @@ struct ChanTab {
   int nseg;
   Run r0, r1, r2, r3;
 };
-constexpr long long JN_DEFER_MAX_M = 65536;   // default of jn_defer_max_m(): output pixels (N * H * W) up to which a layer's table is deferred
-long long jn_defer_max_m();                   // the limit in force (env JN_DEFER_MAX_M overrides the default; read once)
+constexpr long long JN_DEFER_MAX_M = 65536;   // output pixels (N * H * W) up to which a layer's table is deferred
 constexpr int JN_NREP_DEFER = 8;              // statistics replicas such a layer accumulates into (its consumers sum them)
 
 // Step batching of the backward: ONE launch covers `n` workspace slots (glimpse steps of a trajectory, each
@@ -110,7 +109,7 @@ int launch_dw(const ConvArgs& a, hipStream_t s);
 int launch_pw(const ConvArgs& a, hipStream_t s);
 bool pw_fused_upsample_supported(const ConvArgs& a);   // launch_pw(a) with a.up_out set will take a route that writes the upsampled copy
 bool pw_res_supported(const ConvArgs& a);              // kernels_pwres.hip: shapes the resident-weight 1x1 kernels take (K, N >= 64)
-int launch_pw_dir(const ConvArgs& a, int ctw, int split, hipStream_t s);
+int launch_pw_dir(const ConvArgs& a, int ctw, hipStream_t s);
 int launch_pw_wide(const ConvArgs& a, hipStream_t s);   // production route: 0 when taken
 bool pw_xs_supported(const ConvArgs& a);               // kernels_pwxs.hip: pixel-stationary kernel for the small maps of a forward pass
 int launch_pw_xs(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu = 0);   // pt: pixel tiles per workgroup (0 = default)
@@ -325,9 +324,6 @@ struct GptStepArgs {
   const int* skip_flag; int skip_when;
 };
 int launch_gpt_step(const GptStepArgs& a, hipStream_t s);
-// kernels_gptmfma.hip: the same step for n_embd % 64 == 0, 4 or 16 agents per workgroup, Linears on fp32 MFMA; opt-in
-// (JN_GPT_MFMA=1: measured slower, see its header); false = not taken
-bool launch_gpt_step_mfma(const GptStepArgs& a, hipStream_t s);
 
 // ---- training of the decision side (kernels_train.hip) ------------------------------------
 struct LossArgs {

@@ -812,18 +812,14 @@ __global__ __launch_bounds__(256) void pw_mfma_kernel(
     }
   }
   if (stats) {
-#ifndef JN_DBG_NO_LDS_STATS
     wave_stats_to_lds<CTW>(s1, s2, red + wm * 32 * CT + 2 * (wn * CTW * 16), lane, Nc - n0 - wn * CTW * 16);
-#endif
     __syncthreads();
-#ifndef JN_DBG_NO_GLOBAL_STATS
     if (tid < 32 * CT && n0 + (tid >> 1) < Nc) {
       float v = 0.0f;
 #pragma unroll
       for (int q = 0; q < WM; ++q) v += red[q * 32 * CT + tid];
       atomicAdd(&stats[(blockIdx.x % nrep) * rep_stride + 2 * n0 + tid], (double)v);
     }
-#endif
   }
 }
 
@@ -979,8 +975,7 @@ static void launch_pw_narrow_t(const ConvArgs& a, long long M, hipStream_t s) {
 
 // true when the persistent narrow kernel took the launch
 static bool launch_pw_narrow(const ConvArgs& a, hipStream_t s) {
-  static const bool off = std::getenv("JN_NO_PW_NARROW") != nullptr;
-  if (off || a.bf16_mfma || a.in_dtype != JN_F32 || a.out_dtype != JN_F32 || a.w_transposed || a.accumulate || a.bias ||
+  if (a.bf16_mfma || a.in_dtype != JN_F32 || a.out_dtype != JN_F32 || a.w_transposed || a.accumulate || a.bias ||
       a.act != ACT_NONE || a.n_slots > 1)
     return false;
   const long long M = (long long)a.N * a.H * a.W;
@@ -1057,11 +1052,10 @@ static void launch_pw_types(const ConvArgs& a, hipStream_t s) {
 // embed_fpn.0 (bf16 -> f32) and gradients (f32 -> f32), all on the bf16 MFMA.
 // Pixel-stationary kernel (kernels_pwxs.hip) for the forward 1x1 layers with K, N >= 64 on at most JN_XS_MAX_M pixels per
 // launch (the 56x56 / 28x28 / 14x14 maps of the headline batch: 10 - 30 % under the weight-stationary kernel on every one
-// of them, profiles/r03_pwxsbench.txt); JN_NO_PW_XS=1 keeps them on the weight-stationary kernel.
+// of them, profiles/r03_pwxsbench.txt).
+constexpr long long JN_XS_MAX_M = 262144;
 static int launch_pw_small_maps(const ConvArgs& a, hipStream_t s) {
-  static const bool off = std::getenv("JN_NO_PW_XS") != nullptr;
-  static const long long max_m = std::getenv("JN_XS_MAX_M") ? std::atoll(std::getenv("JN_XS_MAX_M")) : 262144;
-  if (off || (long long)a.N * a.H * a.W > max_m) return -1;
+  if ((long long)a.N * a.H * a.W > JN_XS_MAX_M) return -1;
   if (pw_x1_supported(a)) return launch_pw_x1(a, s);      // bf16 inference mode
   if (!pw_xs_supported(a)) return -1;
   // fp32 operands as three bf16 planes on the bf16 matrix pipe where that is the faster kernel (a.w_x3 is null under
@@ -1074,9 +1068,7 @@ static int launch_pw_small_maps(const ConvArgs& a, hipStream_t s) {
 // small-map routes of the headline batch: their kernel can store the upsampled copy itself (a.up_out).  Mirrors the
 // route choice of launch_pw_small_maps; any other shape / route keeps the separate upsample launch.
 bool pw_fused_upsample_supported(const ConvArgs& a) {
-  static const bool off = std::getenv("JN_NO_PW_XS") != nullptr || std::getenv("JN_NO_FUSED_UPSAMPLE") != nullptr;
-  static const long long max_m = std::getenv("JN_XS_MAX_M") ? std::atoll(std::getenv("JN_XS_MAX_M")) : 262144;
-  if (off || (long long)a.N * a.H * a.W > max_m || !pw_xs_supported(a)) return false;
+  if ((long long)a.N * a.H * a.W > JN_XS_MAX_M || !pw_xs_supported(a)) return false;
   if (a.cin == 128 && a.cout == 64) return pw_x3_preferred(a);          // pw_x3_kernel<128, 1, 2, 4>
   return a.cin == 256 && a.cout == 128;                                  // pw_xs_kernel<256, 2, 2, 4>
 }
@@ -1224,8 +1216,7 @@ __global__ __launch_bounds__(256) void spp4_kernel(float* __restrict__ cat, int 
 
 int launch_spp(void* cat, int dtype, int ld, int h, int H, int W, int N, ChanTab it, const int* skip_flag,
                int skip_when, hipStream_t s) {
-  static const bool no_v4 = std::getenv("JN_NO_SPP_V4") != nullptr;
-  if (dtype == JN_F32 && !no_v4 && h % 16 == 0 && ld % 4 == 0 && H * W * 4 <= 2048) {
+  if (dtype == JN_F32 && h % 16 == 0 && ld % 4 == 0 && H * W * 4 <= 2048) {
     hipLaunchKernelGGL(spp4_kernel<4>, dim3(h / 16, N), dim3(256), (size_t)H * W * 4 * 2 * sizeof(f32x4), s, (float*)cat, ld, h, H, W, it,
                        skip_flag, skip_when);
     return 0;
@@ -1389,11 +1380,6 @@ __global__ __launch_bounds__(256) void bn_finalize_all_kernel(BnAllArgs a) {
   float* rm = a.run_mean[i]; float* rv = a.run_var[i];
   *rm = (1.0f - a.momentum) * *rm + a.momentum * mean;
   *rv = (1.0f - a.momentum) * *rv + a.momentum * (float)unbiased;
-}
-
-long long jn_defer_max_m() {
-  static const long long v = std::getenv("JN_DEFER_MAX_M") ? std::atoll(std::getenv("JN_DEFER_MAX_M")) : JN_DEFER_MAX_M;
-  return v;
 }
 
 int launch_bn_finalize_all(const BnAllArgs& a, hipStream_t s) {

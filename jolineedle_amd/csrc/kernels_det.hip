@@ -674,7 +674,7 @@ static void launch_conv3_x3s2(const ConvArgs& a, hipStream_t s) {
 // launch): fp32 matrix pipe.  Stride 2 stays on the fp32 kernel: its halo tile leaves room for one row per wave only, the
 // operand reads of the three planes then need more than the LDS delivers (measured: 5 % slower).
 // The x3 workgroup is 16 x 16 pixels on a whole CU (124 KB of LDS), the fp32 one 8 x 16 with two per CU; per 16 rows of
-// pixels the x3 kernel takes ~0.65 of the fp32 kernel's time (tools/c5_layers.sh: 80x80 64 -> 64: 91 -> 62 us; 20x20
+// pixels the x3 kernel takes ~0.65 of the fp32 kernel's time (per-layer profile of configs[4]: 80x80 64 -> 64: 91 -> 62 us; 20x20
 // 256 -> 256: 159 -> 107), but a launch is whole rounds of workgroups and a 40 x 40 map is 2.5 tiles high — pick per launch:
 // rounds x time per round (forward of 16 patches at 40 x 40: 480 fp32 workgroups = one round, 288 x3 workgroups = two).
 static bool conv3_x3_ok(const ConvArgs& a) {
@@ -688,9 +688,9 @@ static bool conv3_x3_ok(const ConvArgs& a) {
 }
 
 // stride 2 forward on the parity-class kernel: whole rounds again (16 x 16 output tiles on a CU of their own against 4 x 16 fp32
-// tiles, two workgroups per CU); JN_NO_CONV3_X3S2=1 / JN_NO_CONV3_X3=1: fp32 matrix pipe
+// tiles, two workgroups per CU); JN_NO_CONV3_X3=1: fp32 matrix pipe
 static bool conv3_x3s2_ok(const ConvArgs& a) {
-  if (std::getenv("JN_NO_CONV3_X3") || std::getenv("JN_NO_CONV3_X3S2") || a.stride != 2 || a.in_dtype != JN_F32 || a.out_dtype != JN_F32 ||
+  if (std::getenv("JN_NO_CONV3_X3") || a.stride != 2 || a.in_dtype != JN_F32 || a.out_dtype != JN_F32 ||
       a.cin % 32 || a.cout % 4 || a.in_ld % 4 || a.out_ld % 4 || a.bias || a.act != ACT_NONE || a.accumulate || a.n_slots > 1 ||
       a.w_transposed)
     return false;
@@ -730,8 +730,7 @@ int launch_conv3(const ConvArgs& a, hipStream_t s) {
     if (conv3_x3_ok(a)) launch_conv3_x3<1, true, 2, 8>(a, s); else launch_conv3_t<1, float, true>(a, s);
     return 0;
   }
-  static const bool no_bf16_conv3 = std::getenv("JN_NO_BF16_CONV3") != nullptr;
-  if (!no_bf16_conv3 && a.w_bf16 && a.in_dtype == JN_BF16 && a.out_dtype == JN_BF16 && !a.stats && !a.accumulate && a.cin % 8 == 0) {
+  if (a.w_bf16 && a.in_dtype == JN_BF16 && a.out_dtype == JN_BF16 && !a.stats && !a.accumulate && a.cin % 8 == 0) {
     if (a.stride == 1) launch_conv3_bf16<1>(a, s); else launch_conv3_bf16<2>(a, s);
     return 0;
   }
@@ -967,7 +966,7 @@ int launch_conv3_bwd_data_s2(const float* gz, int g_ld, const float* w, float* g
   if (Co % 4 || Ci % 4) return -1;
   // bf16 matrix pipe (three-way split operands): whole 16 x 16 class tiles on a CU of their own against the fp32 kernel's
   // 8 x 16 tiles, two per CU — chosen like the forward routes, by rounds of workgroups x time per round
-  if (!std::getenv("JN_NO_CONV3_X3") && !std::getenv("JN_NO_CONV3_X3S2") && !std::getenv("JN_NO_CONV3_X3S2_BWD") && Co % 32 == 0 && g_ld % 4 == 0 &&
+  if (!std::getenv("JN_NO_CONV3_X3") && Co % 32 == 0 && g_ld % 4 == 0 &&
       gin_ld % 4 == 0) {
     constexpr int PR = 2, NW = 8, TH = PR * NW;
     const int txs = (OW + C3_TW - 1) / C3_TW, tys = (OH + TH - 1) / TH;
@@ -1281,8 +1280,7 @@ int launch_conv3_bwd_weight(const float* gz, int g_ld, const void* x, int x_dtyp
   if (gx > n_tiles) gx = n_tiles;
   dim3 grid((unsigned)gx, nbo, nbk * sb.n);
   static const bool exact = std::getenv("JN_WW_EXACT") != nullptr;
-  static const bool no_tr = std::getenv("JN_NO_CONV3_WTR") != nullptr;
-  if (!exact && !no_tr && x_dtype == JN_F32 && Co % 16 == 0 && Ci % 4 == 0 && g_ld % 4 == 0 && x_ld % 4 == 0) {
+  if (!exact && x_dtype == JN_F32 && Co % 16 == 0 && Ci % 4 == 0 && g_ld % 4 == 0 && x_ld % 4 == 0) {
     // split planes + transposed LDS reads (conv3_bwd_weight_tr_kernel)
 #define JN_CWT(S_)                                                                                                      \
     {                                                                                                                   \

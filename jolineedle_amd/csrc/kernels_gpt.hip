@@ -321,7 +321,6 @@ __global__ __launch_bounds__(NT) void gpt_step_kernel(GptStepArgs a) {
 }
 
 int launch_gpt_step(const GptStepArgs& a, hipStream_t s) {
-  if (launch_gpt_step_mfma(a, s)) return 0;             // wide models: 16 agents per workgroup on the matrix pipe
   const int nt = a.C <= 64 ? 256 : 1024;
   const size_t smem = (size_t)(9 * a.C + a.n_head * a.Tmax + nt / 64 + 16 + 4 + 4 * nt) * sizeof(float);
   if (nt == 256) hipLaunchKernelGGL(gpt_step_kernel<256>, dim3(a.B), dim3(256), smem, s, a);

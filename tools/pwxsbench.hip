@@ -92,7 +92,7 @@ int main(int argc, char** argv) {
       printf(" | %s:", dt ? "deferred" : "plain");
       const float t_old = time_it([&] { launch_pw_types<float, float, false>(a, s); });
       printf(" mfma %5.1f", t_old);
-      if (launch_pw_dir(a, 0, 0, s) == 0 && hipDeviceSynchronize() == hipSuccess) printf(" dir %5.1f", time_it([&] { launch_pw_dir(a, 0, 0, s); }));
+      if (launch_pw_dir(a, 0, s) == 0 && hipDeviceSynchronize() == hipSuccess) printf(" dir %5.1f", time_it([&] { launch_pw_dir(a, 0, s); }));
       for (int pt : {2, 4})
         for (int wg : {1, 2, 3}) {
           if (dt == 0 && wg != 2) continue;
