@@ -190,8 +190,10 @@ int jn_embed_patches(jn_ctx* ctx, const float* patches_dev, int N, float* out_de
 /* optimizer.zero_grad(): clears the flat gradient arena. */
 int jn_zero_grad(jn_ctx* ctx, void* stream);
 /* Backward of the most recent train-mode jn_backbone_forward(net, patches, N, train=1): g*_dev are
- * dL/d(fpn outputs), NCHW f32 (NULL = zero); parameter gradients (conv weights, BN weight/bias)
- * are ACCUMULATED into the gradient arena (read with jn_read_grad). */
+ * dL/d(fpn outputs), NCHW f32.  NULL = no gradient arrives in that output from outside the network
+ * (numerically a zero gradient; the backward then takes the routes of the training backward, which
+ * feeds fpn[2] only).  Parameter gradients (conv weights, BN weight/bias) are ACCUMULATED into the
+ * gradient arena (read with jn_read_grad). */
 int jn_backbone_backward(jn_ctx* ctx, int net, const float* patches_dev, int N, const float* g0_dev,
                          const float* g1_dev, const float* g2_dev, void* stream);
 /* Options of one REINFORCE iteration (src/reinforce.py:217-265, 341). */

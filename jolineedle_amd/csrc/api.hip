@@ -1667,6 +1667,7 @@ int jn_backbone_backward(jn_ctx* ctx, int net, const float* patches_dev, int N, 
   Net& n = ctx->nets[net];
   const int P = ctx->cfg.patch_size, MB = ctx->cfg.max_batch;
   const float* gs[3] = {g0_dev, g1_dev, g2_dev};
+  int fpn_zero = 0;                 // bit i: no gradient arrives in fpn[i] from outside (the training backward's routes)
   for (int i = 0; i < 3; ++i) {
     const View& f = n.fpn[i];
     float* gp = n.gact + n.buf_off[f.buf] * (size_t)MB + f.coff;
@@ -1675,10 +1676,11 @@ int jn_backbone_backward(jn_ctx* ctx, int net, const float* patches_dev, int N, 
     } else {
       JN_CHECK(n.bufs[f.buf].C == f.C, JN_ESTATE, "fpn output is a slice");
       JN_HIP(hipMemsetAsync(gp, 0, (size_t)N * f.H * f.W * f.C * sizeof(float), s));
+      fpn_zero |= 1 << i;
     }
   }
   StemSrc ss{patches_dev, nullptr, 3LL * P * P, (long long)P * P, P};
-  return run_net_backward(ctx, net, N, ss, 0, s);
+  return run_net_backward(ctx, net, N, ss, 0, s, 1, 0, false, fpn_zero);
 }
 
 int jn_read_grad(jn_ctx* ctx, const char* name, float* host_out, size_t numel) {

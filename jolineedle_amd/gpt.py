@@ -309,7 +309,8 @@ class GPT(nn.Module):
 
     def backbone_backward(self, patches, grads, net=None):
         """Backward of the last ``backbone_features(patches, train=True)``: `grads` = dL/d(fpn_outs)
-        (NCHW, entries may be None).  Parameter gradients accumulate inside the engine."""
+        (NCHW).  An entry may be None: no gradient arrives in that output, which selects the kernel routes of the
+        training backward (it feeds only the last FPN output).  Parameter gradients accumulate inside the engine."""
         cfg = self._engine.cfg
         if net is None:
             net = _lib.JN_NET_GPT_BACKBONE if cfg.gpt_bb_width > 0 else _lib.JN_NET_DETECTOR

@@ -11,6 +11,7 @@ import torch
 import jolineedle_amd as ja
 from jolineedle_amd import _lib
 from jolineedle_amd._lib import check, ptr
+from tests.fp64_bars import _UlpSiLU, _with_noisy_silu  # noqa: F401  (the conditioning probe's SiLU noise)
 from tests.helpers import make_pair, model_config, randomize_bn, synth_batch, synth_tokens
 
 pytestmark = pytest.mark.gpu
@@ -642,32 +643,6 @@ def grad_bar(name, full_size=False):
     return bar
 
 
-class _UlpSiLU(torch.nn.Module):
-    def __init__(self, gen, eps=1e-7):
-        super().__init__()
-        self.gen, self.eps = gen, eps
-
-    def forward(self, x):
-        y = torch.nn.functional.silu(x)
-        return y * (1.0 + self.eps * torch.randn(y.shape, generator=self.gen, dtype=y.dtype))
-
-
-def _with_noisy_silu(oracle, seed, eps):
-    """A copy of the oracle whose every SiLU output carries relative Gaussian noise `eps`."""
-    import copy
-    o = copy.deepcopy(oracle)
-    gen = torch.Generator().manual_seed(seed)
-
-    def swap(mod):
-        for n, c in list(mod.named_children()):
-            if isinstance(c, torch.nn.SiLU):
-                setattr(mod, n, _UlpSiLU(gen, eps))
-            else:
-                swap(c)
-    swap(o)
-    return o
-
-
 def _measured_probe_eps(product, oracle, patches, eps0=2e-6):
     """The noise level of the conditioning probe, MEASURED instead of picked: the eps at which the
     noisy fp32 oracle's FORWARD error equals the engine's.  Train-mode FPN maps (batch statistics) of `patches`, relative L2
@@ -854,7 +829,8 @@ def test_reinforce_iteration_at_the_headline_kernel_mix_vs_oracle():
     has deferred entries and whose dark3 half has not, bu_conv2.dconv crosses the boundary, etc.; the narrow persistent
     1x1 kernel, the weight-stationary wide one and the fused backward kernels run with the grids of thousands of
     pixel tiles.  B = 24, 448 px, T = 2: train-mode maps of the first glimpse step, losses and every gradient of the
-    REINFORCE iteration against torch autograd on the CPU oracle (src/reinforce.py:302-353, src/models/gpt.py:356-384)."""
+    REINFORCE iteration against torch autograd on the CPU oracle (src/reinforce.py:302-353, src/models/gpt.py:356-384).
+    Its kernel routes are now pinned with fixed fp64 bars, no draws, by tests/test_gpu_encoder_fp64.py."""
     P, Tn, B = 448, 2, 24
     product, oracle = make_pair(5, patch_size=P, block_size=Tn, with_detector=False, image_processor=None, max_batch=B)
     images, bboxes, start = synth_batch(B, 2, 2, P, seed=43)
@@ -941,15 +917,17 @@ def test_three_way_split_1x1_kernels_are_as_accurate_as_the_fp32_matrix_pipe(mon
 def test_headline_shape_backward_does_not_depend_on_the_step_batching(monkeypatch):
     """BASELINE configs[2] shape (64 agents, 448 px, T = 20): the step-batched backward (ONE set of launches over all 20
     glimpse steps: grid.z = 20, the 'whole resident rounds' grid rules) against the same iteration differentiated in chunks
-    of 5 steps (JN_GRAD_SLOTS; grids of the sizes the oracle tests cover).  A size-independent property: the loss and every
-    gradient agree to the order of the atomics (relative L2 <= 2e-5, max-norm <= 2e-4)."""
+    of 5 steps and of ONE step (JN_GRAD_SLOTS; grids of the sizes the oracle tests cover; one slot is the launch shape of
+    jn_backbone_backward, whose routes tests/test_gpu_encoder_fp64.py pins against fp64 — this carries them over to the
+    20-slot backward).  A size-independent property: the loss and every gradient agree, pair by pair, to the order of the
+    atomics (relative L2 <= 2e-5, max-norm <= 2e-4)."""
     P, Tn, B, G = 448, 20, 64, 3
     images = torch.rand((B, 3, G * P, G * P), device=DEV, generator=torch.Generator(device=DEV).manual_seed(5))
     _, bboxes, start = synth_batch(B, G, G, 64, seed=41)
     bboxes = bboxes * (P // 64)
     forced = torch.randint(0, 8, (B, Tn), generator=torch.Generator().manual_seed(3))
     grads, losses = [], []
-    for slots in (None, 5):
+    for slots in (None, 5, 1):
         if slots:
             monkeypatch.setenv("JN_GRAD_SLOTS", str(slots))
         product, _ = make_pair(5, bn_seed=None, patch_size=P, block_size=Tn, with_detector=False, image_processor=None, max_batch=B)
@@ -961,16 +939,17 @@ def test_headline_shape_backward_does_not_depend_on_the_step_batching(monkeypatc
         grads.append(product.engine_grads())
         del product, tr, env
         torch.cuda.empty_cache()
-    assert abs(losses[0] - losses[1]) < 1e-5
-    checked = 0
-    for k, a in grads[0].items():
-        b = grads[1][k]
-        if float(a.abs().max()) < 1e-12:
-            continue
-        assert float((a - b).norm() / a.norm()) < 2e-5, (k, float((a - b).norm() / a.norm()))
-        assert float((a - b).abs().max() / a.abs().max()) < 2e-4, k
-        checked += 1
-    assert checked > 150
+    for i, j in ((0, 1), (0, 2), (1, 2)):
+        assert abs(losses[i] - losses[j]) < 1e-5, (i, j, losses)
+        checked = 0
+        for k, a in grads[i].items():
+            b = grads[j][k]
+            if float(a.abs().max()) < 1e-12:
+                continue
+            assert float((a - b).norm() / a.norm()) < 2e-5, (i, j, k, float((a - b).norm() / a.norm()))
+            assert float((a - b).abs().max() / a.abs().max()) < 2e-4, (i, j, k)
+            checked += 1
+        assert checked > 150
 
 
 def test_config5_training_at_its_sequence_length_does_not_depend_on_the_step_batching(monkeypatch):
