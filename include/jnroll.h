@@ -134,6 +134,11 @@ int jn_load_weights(jn_ctx* ctx, const jn_tensor* tensors, size_t n);
  * by the caller and must outlive the env; bboxes [B,nb,4] int64 xyxy (zero rows = pad). */
 int jn_env_init(jn_ctx* ctx, const float* images_dev, const int64_t* bboxes_dev,
                 int B, int H, int W, int nb, int max_ep_len, int stop_enabled, void* stream);
+/* The same env over 8-bit images [B,3,H,W] u8 (what the reference's ToTensor gets from PIL), read in place: byte b
+ * stands for b / 255 correctly rounded, so every result equals that of jn_env_init on u8.float().div(255).  The
+ * gathers, the rollout's encoders and the training backward read the bytes (a quarter of the fp32 image's traffic). */
+int jn_env_init_u8(jn_ctx* ctx, const uint8_t* images_dev, const int64_t* bboxes_dev,
+                   int B, int H, int W, int nb, int max_ep_len, int stop_enabled, void* stream);
 /* reset :144-170.  positions [B,2] (y,x) int64 or NULL = uniform draw from `seed`. */
 int jn_env_reset(jn_ctx* ctx, const int64_t* positions_dev, uint64_t seed, void* stream);
 /* step :172-233 + rewards :321-358 + terminated :235-246.  Outputs may be NULL. */
@@ -149,6 +154,9 @@ int jn_env_patches(jn_ctx* ctx, float* out_dev, void* stream);
 /* Stand-alone gather (no context state): out[b] = images[b,:,y*P:(y+1)*P, x*P:(x+1)*P]. */
 int jn_gather_patches(const float* images_dev, const int64_t* positions_dev, float* out_dev,
                       int B, int C, int H, int W, int P, void* stream);
+/* ... of u8 images: out (f32) = byte / 255 correctly rounded. */
+int jn_gather_patches_u8(const uint8_t* images_dev, const int64_t* positions_dev, float* out_dev,
+                         int B, int C, int H, int W, int P, void* stream);
 /* Trajectory form of the gather: out[n] = images[image_index[n], :, y_n*P:(y_n+1)*P, x_n*P:(x_n+1)*P] for N
  * (image, position) pairs — the patches NeedleSimpleEnv.generate_sample stacks one `get_patch` at a time
  * (src/env/simple_env.py:55-81, 472) and init_sample's detector patches (:417-419).  image_index[n] < 0 writes
@@ -157,6 +165,10 @@ int jn_gather_patches(const float* images_dev, const int64_t* positions_dev, flo
 int jn_gather_patches_indexed(const float* images_dev, const int64_t* image_index_dev,
                               const int64_t* positions_dev, float* out_dev, int N, int n_images,
                               int C, int H, int W, int P, void* stream);
+/* ... of u8 images: out (f32) = byte / 255 correctly rounded. */
+int jn_gather_patches_indexed_u8(const uint8_t* images_dev, const int64_t* image_index_dev,
+                                 const int64_t* positions_dev, float* out_dev, int N, int n_images,
+                                 int C, int H, int W, int P, void* stream);
 
 /* ---- detection augmentation ------------------------------------- */
 /* Trainer.init_detection's on-device chain (src/trainer.py:176-186, applied at src/reinforce.py:332-333 and

@@ -668,8 +668,9 @@ static View net_full_view(const Net& net, int buf) {
 }
 
 struct StemSrc {
-  const float* src; const int64_t* positions; long long sample_stride, chan_stride; int row_stride;
+  const void* src; const int64_t* positions; long long sample_stride, chan_stride; int row_stride;
   int pos_stride = 2;
+  int src_u8 = 0;     // src holds uint8 (the env's byte images): StemArgs::src_u8
 };
 static inline int det_slot_base(const jn_ctx* ctx);   // first workspace slot of the detector's training passes (below)
 
@@ -844,7 +845,7 @@ static int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int 
         const ConvW& cw = net.convs[op.wslot];
         StemArgs a{ss.src, ss.positions, ss.pos_stride, ss.sample_stride, ss.chan_stride, ss.row_stride, net.P, N, cw.cout,
                    cw.w_dev, ptr(op.out), ld(op.out), net.act_dtype, train ? stats + 2 * cw.stat_off : nullptr, rep_stride,
-                   skip_flag, skip_when, deferred(op) ? JN_NREP_DEFER : JN_NREP};
+                   skip_flag, skip_when, deferred(op) ? JN_NREP_DEFER : JN_NREP, ss.src_u8};
         launch_stem(a, s);
         finalize(op, cw);
         break;
@@ -1315,7 +1316,7 @@ static int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int s
       }
       if (op.kind == OP_STEM && net.act_dtype == JN_F32) {
         StemArgs a{ss.src, ss.positions, ss.pos_stride, ss.sample_stride, ss.chan_stride, ss.row_stride, net.P, N, cw.cout,
-                   cw.w_dev, nullptr, 0, JN_F32, nullptr, 0, nullptr, 0};
+                   cw.w_dev, nullptr, 0, JN_F32, nullptr, 0, nullptr, 0, 0, ss.src_u8};
         launch_stem_bwd_weight(a, gp_out, gld_out, gw, ctx->wpart, s, sb, (const float*)ptr(op.out), ld(op.out),
                                tab(op.out), save + 2 * cw.stat_off, consts);
         continue;
@@ -1355,7 +1356,7 @@ static int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int s
                              op.in.W, op.out.H, op.out.W, N, op.stride, s, sb);
       } else if (op.kind == OP_STEM) {
         StemArgs a{ss.src, ss.positions, ss.pos_stride, ss.sample_stride, ss.chan_stride, ss.row_stride, net.P, N, cw.cout,
-                   cw.w_dev, nullptr, 0, JN_F32, nullptr, 0, nullptr, 0};
+                   cw.w_dev, nullptr, 0, JN_F32, nullptr, 0, nullptr, 0, 0, ss.src_u8};
         launch_stem_bwd_weight(a, gp_out, gld_out, gw, ctx->wpart, s, sb);
       } else if (op.kind == OP_CONV3) {
         // dense 3x3 (non-depthwise patch encoders, e.g. yolox-s): stride 1 = the forward kernel over g_z with
@@ -1905,9 +1906,23 @@ static EnvPtrs env_ptrs(jn_ctx* ctx) {
   return p;
 }
 
-int jn_env_init(jn_ctx* ctx, const float* images_dev, const int64_t* bboxes_dev, int B, int H, int W, int nb,
-                int max_ep_len, int stop_enabled, void* stream) {
-  JN_CHECK(ctx && images_dev && (bboxes_dev || nb == 0), JN_EINVAL, "jn_env_init: null argument");
+// the env's images are read in place by the gathers and the stems; images_u8 selects the byte instantiations
+static void env_gather(const EnvState& e, float* out, long long out_sample_stride, int P, const int* skip_flag, int skip_when,
+                       hipStream_t s) {
+  if (e.images_u8)
+    launch_gather((const uint8_t*)e.images, e.positions, out, out_sample_stride, e.B, 3, e.H, e.W, P, skip_flag, skip_when, s);
+  else
+    launch_gather((const float*)e.images, e.positions, out, out_sample_stride, e.B, 3, e.H, e.W, P, skip_flag, skip_when, s);
+}
+
+static StemSrc env_stem_src(const EnvState& e, const int64_t* positions) {
+  StemSrc ss{e.images, positions, 3LL * e.H * e.W, (long long)e.H * e.W, e.W};
+  ss.src_u8 = e.images_u8;
+  return ss;
+}
+
+static int env_init_impl(jn_ctx* ctx, const void* images_dev, int images_u8, const int64_t* bboxes_dev, int B, int H, int W,
+                         int nb, int max_ep_len, int stop_enabled, void* stream) {
   const int P = ctx->cfg.patch_size;
   JN_CHECK(B >= 1 && B <= ctx->cfg.max_batch, JN_EINVAL, "B=%d exceeds max_batch=%d", B, ctx->cfg.max_batch);
   // general_env.py:50-51
@@ -1929,7 +1944,8 @@ int jn_env_init(jn_ctx* ctx, const float* images_dev, const int64_t* bboxes_dev,
     if ((rc = dev_alloc(ctx, &e.n_bbox_tiles, (size_t)MB))) return rc;
     if ((rc = dev_alloc(ctx, &ctx->found, (size_t)MB))) return rc;
   }
-  e.images = images_dev; e.B = B; e.H = H; e.W = W; e.nb = nb; e.Gh = Gh; e.Gw = Gw; e.T = max_ep_len;
+  e.images = images_dev; e.images_u8 = images_u8;
+  e.B = B; e.H = H; e.W = W; e.nb = nb; e.Gh = Gh; e.Gw = Gw; e.T = max_ep_len;
   e.stop = stop_enabled ? 1 : 0;
   hipStream_t s = (hipStream_t)stream;
   launch_bbox_masks(bboxes_dev, e.bbox_masks, e.n_bbox_tiles, B, nb, H, W, P, s);
@@ -1937,6 +1953,18 @@ int jn_env_init(jn_ctx* ctx, const float* images_dev, const int64_t* bboxes_dev,
   JN_HIP(hipGetLastError());
   e.ready = true;
   return JN_OK;
+}
+
+int jn_env_init(jn_ctx* ctx, const float* images_dev, const int64_t* bboxes_dev, int B, int H, int W, int nb,
+                int max_ep_len, int stop_enabled, void* stream) {
+  JN_CHECK(ctx && images_dev && (bboxes_dev || nb == 0), JN_EINVAL, "jn_env_init: null argument");
+  return env_init_impl(ctx, images_dev, 0, bboxes_dev, B, H, W, nb, max_ep_len, stop_enabled, stream);
+}
+
+int jn_env_init_u8(jn_ctx* ctx, const uint8_t* images_dev, const int64_t* bboxes_dev, int B, int H, int W, int nb,
+                   int max_ep_len, int stop_enabled, void* stream) {
+  JN_CHECK(ctx && images_dev && (bboxes_dev || nb == 0), JN_EINVAL, "jn_env_init_u8: null argument");
+  return env_init_impl(ctx, images_dev, 1, bboxes_dev, B, H, W, nb, max_ep_len, stop_enabled, stream);
 }
 
 int jn_env_reset(jn_ctx* ctx, const int64_t* positions_dev, uint64_t seed, void* stream) {
@@ -1980,6 +2008,16 @@ int jn_gather_patches(const float* images_dev, const int64_t* positions_dev, flo
   return JN_OK;
 }
 
+int jn_gather_patches_u8(const uint8_t* images_dev, const int64_t* positions_dev, float* out_dev, int B, int C, int H,
+                         int W, int P, void* stream) {
+  JN_CHECK(images_dev && positions_dev && out_dev, JN_EINVAL, "jn_gather_patches_u8: null argument");
+  JN_CHECK(B >= 0 && C >= 1 && P >= 1 && H % P == 0 && W % P == 0, JN_EINVAL, "jn_gather_patches_u8: bad shape");
+  if (B == 0) return JN_OK;
+  launch_gather(images_dev, positions_dev, out_dev, (long long)C * P * P, B, C, H, W, P, nullptr, 0, (hipStream_t)stream);
+  JN_HIP(hipGetLastError());
+  return JN_OK;
+}
+
 int jn_augment_patches(const float* in_dev, float* out_dev, const float* params_dev, const float* noise_dev, uint64_t seed,
                        int N, int P, void* stream) {
   JN_CHECK(in_dev && out_dev && params_dev, JN_EINVAL, "jn_augment_patches: null argument");
@@ -2003,10 +2041,25 @@ int jn_gather_patches_indexed(const float* images_dev, const int64_t* image_inde
   return JN_OK;
 }
 
+int jn_gather_patches_indexed_u8(const uint8_t* images_dev, const int64_t* image_index_dev, const int64_t* positions_dev,
+                                 float* out_dev, int N, int n_images, int C, int H, int W, int P, void* stream) {
+  JN_CHECK(images_dev && image_index_dev && positions_dev && out_dev, JN_EINVAL,
+           "jn_gather_patches_indexed_u8: null argument");
+  JN_CHECK(N >= 0 && n_images >= 1 && C >= 1 && P >= 1 && H % P == 0 && W % P == 0, JN_EINVAL,
+           "jn_gather_patches_indexed_u8: bad shape");
+  if (N == 0) return JN_OK;
+  launch_gather(images_dev, positions_dev, out_dev, (long long)C * P * P, N, C, H, W, P, nullptr, 0, (hipStream_t)stream,
+                image_index_dev);
+  JN_HIP(hipGetLastError());
+  return JN_OK;
+}
+
 int jn_env_patches(jn_ctx* ctx, float* out_dev, void* stream) {
   JN_CHECK(ctx && ctx->env.ready && out_dev, JN_ESTATE, "jn_env_init has not been called");
   const EnvState& e = ctx->env;
-  return jn_gather_patches(e.images, e.positions, out_dev, e.B, 3, e.H, e.W, ctx->cfg.patch_size, stream);
+  if (e.images_u8)
+    return jn_gather_patches_u8((const uint8_t*)e.images, e.positions, out_dev, e.B, 3, e.H, e.W, ctx->cfg.patch_size, stream);
+  return jn_gather_patches((const float*)e.images, e.positions, out_dev, e.B, 3, e.H, e.W, ctx->cfg.patch_size, stream);
 }
 
 // ---- the hot loop ----------------------------------------------------------------------
@@ -2055,7 +2108,7 @@ static int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev
   launch_rollout_begin(ep, r, ctx->prev_action, ctx->cache_len, ctx->n_done, s);
   const long long patch_stride = (long long)(T + 1) * 3 * P * P;
   if (out->patches_dev)
-    launch_gather(e.images, e.positions, out->patches_dev, patch_stride, B, 3, e.H, e.W, P, nullptr, 0, s);
+    env_gather(e, out->patches_dev, patch_stride, P, nullptr, 0, s);
 
   const int Kd = c.max_det_per_patch;
   if (do_detection) {
@@ -2092,7 +2145,7 @@ static int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev
       JN_HIP(hipStreamWaitEvent(ds_stream, ctx->aux_fork, 0));
       pos = snap;
     }
-    StemSrc ds{e.images, pos, 3LL * e.H * e.W, (long long)e.H * e.W, e.W};
+    const StemSrc ds = env_stem_src(e, pos);
     int r = detect_impl(ctx, ds, B, ctx->det_tmp_boxes, ctx->det_tmp_counts, nullptr, flag, B, ds_stream);
     if (r) return r;
     launch_det_scatter(ctx->det_tmp_boxes, ctx->det_tmp_counts, out->det_boxes_dev, out->det_counts_dev, B, T + 1, col, Kd,
@@ -2108,7 +2161,7 @@ static int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev
     }
   }
   ctx->conv_ev_used = 0;
-  StemSrc ss{e.images, e.positions, 3LL * e.H * e.W, (long long)e.H * e.W, e.W};
+  const StemSrc ss = env_stem_src(e, e.positions);
   int rc;
   if (train) {
     Net& tn = ctx->nets[ctx->enc_net];
@@ -2170,8 +2223,7 @@ static int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev
     a.pdrop = train ? ctx->pdrop : 0.0f; a.drop_seed = ctx->drop_seed_used;
     launch_gpt_step(a, s);
     if (out->patches_dev)
-      launch_gather(e.images, e.positions, out->patches_dev + (long long)(t + 1) * 3 * P * P, patch_stride, B, 3, e.H, e.W,
-                    P, flag, B, s);
+      env_gather(e, out->patches_dev + (long long)(t + 1) * 3 * P * P, patch_stride, P, flag, B, s);
     if (do_detection && (rc = detect_step(t + 1, flag))) return rc;     // src/reinforce.py:162-167
   }
   if (ds_stream != s) {
@@ -2399,7 +2451,7 @@ static int reinforce_backward_impl(jn_ctx* ctx, const jn_rollout_out* out, int S
         JN_HIP(hipMemsetAsync(net.gact + (size_t)j * g_slot + net.buf_off[f.buf] * (size_t)MB + f.coff, 0,
                               (size_t)B * f.H * f.W * f.C * sizeof(float), s));
     }
-    StemSrc ss{e.images, out->positions_dev + 2 * t0, 3LL * e.H * e.W, (long long)e.H * e.W, e.W};
+    StemSrc ss = env_stem_src(e, out->positions_dev + 2 * t0);
     ss.pos_stride = 2 * (T + 1);
     // (only fpn[2] carries a gradient from outside the encoder: embed_fpn; the other two FPN views were zeroed above)
     if ((rc = run_net_backward(ctx, ctx->enc_net, B, ss, t0 + 1, s, g_n, 2, false, 0x3))) return rc;

@@ -158,7 +158,8 @@ struct GptW {   // device, packed
 
 struct EnvState {
   bool ready = false;
-  const float* images = nullptr;
+  const void* images = nullptr;   // [B,3,H,W] fp32, or uint8 when images_u8 (byte b = b / 255): not copied
+  int images_u8 = 0;
   int B = 0, H = 0, W = 0, nb = 0, Gh = 0, Gw = 0, T = 0, stop = 0;
   int64_t* positions = nullptr;   // [B,2]
   uint8_t* bbox_masks = nullptr;  // [B,Gh,Gw]

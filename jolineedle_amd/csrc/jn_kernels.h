@@ -63,7 +63,7 @@ struct SlotBatch {
 };
 
 struct StemArgs {
-  const float* src; const int64_t* positions; int pos_stride;   // positions[pos_stride * n + {0,1}] = (y, x)
+  const void* src; const int64_t* positions; int pos_stride;    // positions[pos_stride * n + {0,1}] = (y, x)
   long long sample_stride, chan_stride; int row_stride;
   int P, N, cout;
   const float* w; void* out; int out_ld; int out_dtype;
@@ -71,6 +71,7 @@ struct StemArgs {
   long long stats_rep_stride;
   const int* skip_flag; int skip_when;
   int stats_nrep;                   // replicas in use (0 -> JN_NREP)
+  int src_u8;                       // src holds uint8 (byte b = b / 255) instead of fp32; strides count elements
 };
 
 struct ConvArgs {
@@ -104,7 +105,7 @@ struct DwPwArgs {
 bool dwpw_supported(int C, int cout, int stride);
 int launch_dwpw(const DwPwArgs& a, hipStream_t s);
 int launch_stem(const StemArgs& a, hipStream_t s);
-bool stem_rows_aligned(const StemArgs& a);        // the stem kernels may fetch the image tile with 16-byte loads
+bool stem_rows_aligned(const StemArgs& a);        // the stem kernels may fetch the image tile with 4-element loads
 int launch_dw(const ConvArgs& a, hipStream_t s);
 int launch_pw(const ConvArgs& a, hipStream_t s);
 bool pw_fused_upsample_supported(const ConvArgs& a);   // launch_pw(a) with a.up_out set will take a route that writes the upsampled copy
@@ -259,6 +260,9 @@ constexpr int AUG_NPARAM = 20;   // ... + shade intensity, shade quantity, rough
 int launch_augment(const float* in, float* out, const float* params, const float* noise, unsigned long long seed, int N, int P,
                    hipStream_t s);
 int launch_gather(const float* images, const int64_t* positions, float* out, long long out_sample_stride,
+                  int B, int C, int H, int W, int P, const int* skip_flag, int skip_when, hipStream_t s,
+                  const int64_t* image_index = nullptr);
+int launch_gather(const uint8_t* images, const int64_t* positions, float* out, long long out_sample_stride,   // b -> b / 255
                   int B, int C, int H, int W, int P, const int* skip_flag, int skip_when, hipStream_t s,
                   const int64_t* image_index = nullptr);
 int launch_bbox_masks(const int64_t* bboxes, uint8_t* masks, int32_t* n_tiles, int B, int nb, int H, int W, int P,

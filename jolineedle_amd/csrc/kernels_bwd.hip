@@ -1259,9 +1259,10 @@ constexpr int SB_TY = 8, SB_TX = 32, SB_IH = 2 * SB_TY + 4, SB_IW = 2 * SB_TX + 
 constexpr int SB_IWP = 70, SB_GZG = 8 * 16 + 16, SB_GZROW = 4 * SB_GZG;
 
 constexpr int SB_W4 = SB_IW / 4 + 1;     // float4 groups per row of the aligned window (see stem_mfma_kernel, VEC)
-template <bool VEC>
+// ST = uint8_t: the image is kept as bytes (4-byte groups on VEC), converted to b / 255 when staged in LDS
+template <bool VEC, typename ST>
 __global__ __launch_bounds__(256) void stem_bwd_weight_kernel(
-    const float* __restrict__ src, const long long* __restrict__ pos, int pos_stride, long long sample_stride,
+    const ST* __restrict__ src, const long long* __restrict__ pos, int pos_stride, long long sample_stride,
     long long chan_stride, int row_stride, int P, const float* __restrict__ gz, int g_ld, int cout, int ocg,
     int tiles_x, int tiles_y, int n_tiles, float* __restrict__ gw, long long pos_slot, long long g_slot,
     const float* __restrict__ z, int z_ld, ChanTab ot, const float* __restrict__ save,
@@ -1304,13 +1305,15 @@ __global__ __launch_bounds__(256) void stem_bwd_weight_kernel(
   // tile's image values and gradients are fetched into registers while the MFMAs of the current one run
   constexpr int NI = (3 * SB_IH * SB_IW + 255) / 256, NG = SB_TY * SB_TX * 4 / 256;
   constexpr int NI4 = (3 * SB_IH * SB_W4 + 255) / 256;
-  float pim[VEC ? 1 : NI];
-  f32x4 pim4[VEC ? NI4 : 1];
+  using R1 = typename SrcRegs<ST>::one;
+  using R4 = typename SrcRegs<ST>::four;
+  R1 pim[VEC ? 1 : NI];
+  R4 pim4[VEC ? NI4 : 1];
   f32x4 pg[NG], pz[NG];
   auto fetch = [&](int tl) {
     const int n = tl / (tiles_x * tiles_y), tr = tl % (tiles_x * tiles_y);
     const int oy0 = (tr / tiles_x) * SB_TY, ox0 = (tr % tiles_x) * SB_TX;
-    const float* base = src + (long long)n * sample_stride;
+    const ST* base = src + (long long)n * sample_stride;
     if (pos) base += pos[(long long)pos_stride * n] * (long long)P * row_stride + pos[(long long)pos_stride * n + 1] * (long long)P;
     if constexpr (VEC) {
 #pragma unroll
@@ -1318,9 +1321,9 @@ __global__ __launch_bounds__(256) void stem_bwd_weight_kernel(
         const int i = tid + 256 * j;
         const int c = i / (SB_IH * SB_W4), r = (i / SB_W4) % SB_IH, q4 = i % SB_W4;
         const int iy = 2 * oy0 - 2 + r, ix = 2 * ox0 - 4 + 4 * q4;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        R4 v = {};
         if (i < 3 * SB_IH * SB_W4 && iy >= 0 && iy < P && ix >= 0 && ix < P)
-          v = *reinterpret_cast<const f32x4*>(base + c * chan_stride + (long long)iy * row_stride + ix);
+          v = *reinterpret_cast<const R4*>(base + c * chan_stride + (long long)iy * row_stride + ix);
         pim4[j] = v;
       }
     } else {
@@ -1329,7 +1332,7 @@ __global__ __launch_bounds__(256) void stem_bwd_weight_kernel(
         const int i = tid + 256 * j;
         const int c = i / (SB_IH * SB_IW), r = (i / SB_IW) % SB_IH, q = i % SB_IW;
         const int iy = 2 * oy0 - 2 + r, ix = 2 * ox0 - 2 + q;
-        float v = 0.0f;
+        R1 v = 0;
         if (i < 3 * SB_IH * SB_IW && iy >= 0 && iy < P && ix >= 0 && ix < P) v = base[c * chan_stride + (long long)iy * row_stride + ix];
         pim[j] = v;
       }
@@ -1357,15 +1360,16 @@ __global__ __launch_bounds__(256) void stem_bwd_weight_kernel(
         if (i < 3 * SB_IH * SB_W4) {
           const int q4 = i % SB_W4;
           float* d = tile + (i / SB_W4) * SB_IWP + 4 * q4 - 2;               // 8-byte aligned (row = 280 bytes)
-          if (q4 > 0) *reinterpret_cast<float2*>(d) = float2{pim4[j].x, pim4[j].y};
-          if (q4 < SB_W4 - 1) *reinterpret_cast<float2*>(d + 2) = float2{pim4[j].z, pim4[j].w};
+          const f32x4 v = src_unit4(pim4[j]);
+          if (q4 > 0) *reinterpret_cast<float2*>(d) = float2{v.x, v.y};
+          if (q4 < SB_W4 - 1) *reinterpret_cast<float2*>(d + 2) = float2{v.z, v.w};
         }
       }
     } else {
 #pragma unroll
       for (int j = 0; j < NI; ++j) {
         const int i = tid + 256 * j;
-        if (i < 3 * SB_IH * SB_IW) tile[(i / SB_IW) * SB_IWP + i % SB_IW] = pim[j];
+        if (i < 3 * SB_IH * SB_IW) tile[(i / SB_IW) * SB_IWP + i % SB_IW] = src_unit(pim[j]);
       }
     }
 #pragma unroll
@@ -1441,11 +1445,13 @@ int launch_stem_bwd_weight(const StemArgs& a, const float* gz, int g_ld, float* 
   const int n_tiles = tiles_x * tiles_y * a.N;
   const int cap = sb.n >= 4 ? 256 : 1024 / sb.n;
   dim3 grid(n_tiles < cap ? n_tiles : cap, ocg, sb.n);
-#define JN_STEMB(V_)                                                                                                      \
-  hipLaunchKernelGGL(stem_bwd_weight_kernel<V_>, grid, dim3(256), 0, s, a.src, (const long long*)a.positions, a.pos_stride, \
-                     a.sample_stride, a.chan_stride, a.row_stride, a.P, gz, g_ld, a.cout, ocg, tiles_x, tiles_y, n_tiles,  \
-                     wpart, sb.pos, sb.grad, z, z_ld, ot, save, consts, sb)
-  if (stem_rows_aligned(a)) JN_STEMB(true); else JN_STEMB(false);
+#define JN_STEMB(V_, ST_)                                                                                                 \
+  hipLaunchKernelGGL((stem_bwd_weight_kernel<V_, ST_>), grid, dim3(256), 0, s, (const ST_*)a.src, (const long long*)a.positions, \
+                     a.pos_stride, a.sample_stride, a.chan_stride, a.row_stride, a.P, gz, g_ld, a.cout, ocg, tiles_x, tiles_y, \
+                     n_tiles, wpart, sb.pos, sb.grad, z, z_ld, ot, save, consts, sb)
+  const bool vec = stem_rows_aligned(a);
+  if (a.src_u8) { if (vec) JN_STEMB(true, uint8_t); else JN_STEMB(false, uint8_t); }
+  else { if (vec) JN_STEMB(true, float); else JN_STEMB(false, float); }
 #undef JN_STEMB
   launch_wpart_reduce(gw, wpart, 108 * a.cout, s);
   return 0;

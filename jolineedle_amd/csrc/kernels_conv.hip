@@ -70,12 +70,14 @@ constexpr int ST_NL = (3 * ST_IH * ST_IW + 255) / 256;        // image values pe
 // bound by the number of load instructions, not by bytes: 2.3 - 2.5 TB/s whatever the segment length, against 4.1 - 6.2
 // TB/s for the same tiles with 16-byte loads (tools/imgreadbench.hip, profiles/r04_imgreadbench.txt).  Needs 16-byte
 // aligned rows (base pointer, strides and the patch size multiples of four floats: checked by the launcher).
+// ST = uint8_t (images kept as bytes): the same window in 4-byte groups, byte b -> b / 255 when the tile is written to
+// LDS; the LDS tile and the MFMA sequence are those of the fp32 image.  VEC needs 4-byte aligned rows.
 constexpr int ST_W4 = ST_IW / 4 + 1;                            // float4 groups per row of the aligned window
 constexpr int ST_NL4 = (3 * ST_IH * ST_W4 + 255) / 256;
 
-template <typename OT, bool VEC>
+template <typename OT, bool VEC, typename ST>
 __global__ __launch_bounds__(256) void stem_mfma_kernel(
-    const float* __restrict__ src, const long long* __restrict__ pos, int pos_stride, long long sample_stride,
+    const ST* __restrict__ src, const long long* __restrict__ pos, int pos_stride, long long sample_stride,
     long long chan_stride, int row_stride, int P, const float* __restrict__ w, OT* __restrict__ out,
     int out_ld, int cout, int tiles_x, int tiles_y, int n_tiles, double* __restrict__ stats, long long rep_stride,
     const int* __restrict__ skip_flag, int skip_when, int nrep) {
@@ -96,12 +98,14 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(
     const int c = k / 36, dy = (k % 36) / 6, dx = k % 6;
     koff[s] = (c * ST_IH + dy) * ST_IW + dx;
   }
-  float pre[VEC ? 1 : ST_NL];
-  f32x4 pre4[VEC ? ST_NL4 : 1];
+  using R1 = typename SrcRegs<ST>::one;
+  using R4 = typename SrcRegs<ST>::four;
+  R1 pre[VEC ? 1 : ST_NL];
+  R4 pre4[VEC ? ST_NL4 : 1];
   auto fetch = [&](int tl) {
     const int n = tl / (tiles_x * tiles_y), tr = tl - n * (tiles_x * tiles_y);
     const int oy0 = (tr / tiles_x) * ST_TY, ox0 = (tr % tiles_x) * ST_TX;
-    const float* base = src + (long long)n * sample_stride;
+    const ST* base = src + (long long)n * sample_stride;
     if (pos) base += pos[(long long)pos_stride * n] * (long long)P * row_stride + pos[(long long)pos_stride * n + 1] * (long long)P;
     if constexpr (VEC) {
 #pragma unroll
@@ -109,9 +113,9 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(
         const int i = tid + 256 * j;
         const int c = i / (ST_IH * ST_W4), r = (i / ST_W4) % ST_IH, q4 = i % ST_W4;
         const int iy = 2 * oy0 - 2 + r, ix = 2 * ox0 - 4 + 4 * q4;          // P % 4 == 0: a group is inside the patch or outside
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        R4 v = {};
         if (i < 3 * ST_IH * ST_W4 && iy >= 0 && iy < P && ix >= 0 && ix < P)
-          v = *reinterpret_cast<const f32x4*>(base + c * chan_stride + (long long)iy * row_stride + ix);
+          v = *reinterpret_cast<const R4*>(base + c * chan_stride + (long long)iy * row_stride + ix);
         pre4[j] = v;
       }
     } else {
@@ -120,7 +124,7 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(
         const int i = tid + 256 * j;
         const int c = i / (ST_IH * ST_IW), r = (i / ST_IW) % ST_IH, q = i % ST_IW;
         const int iy = 2 * oy0 - 2 + r, ix = 2 * ox0 - 2 + q;
-        float v = 0.0f;
+        R1 v = 0;
         if (i < 3 * ST_IH * ST_IW && iy >= 0 && iy < P && ix >= 0 && ix < P) v = base[c * chan_stride + (long long)iy * row_stride + ix];
         pre[j] = v;
       }
@@ -140,15 +144,16 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(
         if (i < 3 * ST_IH * ST_W4) {
           const int q4 = i % ST_W4;
           float* d = tile + (i / ST_W4) * ST_IW + 4 * q4 - 2;                // 8-byte aligned (row = 272 bytes)
-          if (q4 > 0) *reinterpret_cast<float2*>(d) = float2{pre4[j].x, pre4[j].y};
-          if (q4 < ST_W4 - 1) *reinterpret_cast<float2*>(d + 2) = float2{pre4[j].z, pre4[j].w};
+          const f32x4 v = src_unit4(pre4[j]);
+          if (q4 > 0) *reinterpret_cast<float2*>(d) = float2{v.x, v.y};
+          if (q4 < ST_W4 - 1) *reinterpret_cast<float2*>(d + 2) = float2{v.z, v.w};
         }
       }
     } else {
 #pragma unroll
       for (int j = 0; j < ST_NL; ++j) {
         const int i = tid + 256 * j;
-        if (i < 3 * ST_IH * ST_IW) tile[i] = pre[j];
+        if (i < 3 * ST_IH * ST_IW) tile[i] = src_unit(pre[j]);
       }
     }
     __syncthreads();
@@ -182,10 +187,11 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(
   }
 }
 
-// 16-byte loads of image rows: base pointer, every stride and the patch size must be multiples of four floats
+// 4-element loads of image rows (16 bytes of fp32, 4 of uint8): base pointer, every stride and the patch size must be
+// multiples of four elements
 bool stem_rows_aligned(const StemArgs& a) {
-  return (reinterpret_cast<uintptr_t>(a.src) & 15) == 0 && a.sample_stride % 4 == 0 && a.chan_stride % 4 == 0 &&
-         a.row_stride % 4 == 0 && a.P % 4 == 0;
+  return (reinterpret_cast<uintptr_t>(a.src) & (a.src_u8 ? 3 : 15)) == 0 && a.sample_stride % 4 == 0 &&
+         a.chan_stride % 4 == 0 && a.row_stride % 4 == 0 && a.P % 4 == 0;
 }
 
 int launch_stem(const StemArgs& a, hipStream_t s) {
@@ -198,12 +204,14 @@ int launch_stem(const StemArgs& a, hipStream_t s) {
   dim3 grid(nwg, ocg);
   const int nrep = a.stats_nrep > 0 ? a.stats_nrep : JN_NREP;
   const bool vec = stem_rows_aligned(a);
-#define JN_STEM(OT_, V_)                                                                                                       \
-  hipLaunchKernelGGL((stem_mfma_kernel<OT_, V_>), grid, dim3(256), 0, s, a.src, (const long long*)a.positions, a.pos_stride, \
-                     a.sample_stride, a.chan_stride, a.row_stride, a.P, a.w, (OT_*)a.out, a.out_ld, a.cout, tiles_x,         \
-                     tiles_y, n_tiles, a.stats, a.stats_rep_stride, a.skip_flag, a.skip_when, nrep)
-  if (a.out_dtype == JN_BF16) { if (vec) JN_STEM(bf16_t, true); else JN_STEM(bf16_t, false); }
-  else { if (vec) JN_STEM(float, true); else JN_STEM(float, false); }
+#define JN_STEM(OT_, V_, ST_)                                                                                                \
+  hipLaunchKernelGGL((stem_mfma_kernel<OT_, V_, ST_>), grid, dim3(256), 0, s, (const ST_*)a.src, (const long long*)a.positions, \
+                     a.pos_stride, a.sample_stride, a.chan_stride, a.row_stride, a.P, a.w, (OT_*)a.out, a.out_ld, a.cout,    \
+                     tiles_x, tiles_y, n_tiles, a.stats, a.stats_rep_stride, a.skip_flag, a.skip_when, nrep)
+#define JN_STEM_V(OT_, ST_) do { if (vec) JN_STEM(OT_, true, ST_); else JN_STEM(OT_, false, ST_); } while (0)
+  if (a.src_u8) { if (a.out_dtype == JN_BF16) JN_STEM_V(bf16_t, uint8_t); else JN_STEM_V(float, uint8_t); }
+  else { if (a.out_dtype == JN_BF16) JN_STEM_V(bf16_t, float); else JN_STEM_V(float, float); }
+#undef JN_STEM_V
 #undef JN_STEM
   return 0;
 }

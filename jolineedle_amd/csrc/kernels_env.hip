@@ -3,15 +3,17 @@
 // Integer / bool work is exact; see jn_device.h for the per-agent step.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "jn_device.h"
+#include "jn_types.h"
 
 namespace jnr {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
 // out[b, c, r, :] = images[b, c, y*P + r, x*P : x*P + P]   (src/env/general_env.py:285-306)
-template <bool VEC>
-__global__ __launch_bounds__(256) void gather_kernel(const float* __restrict__ images,
+// ST = float: a copy; ST = uint8_t: byte b -> b / 255 (u8_unit), VEC reads 4 bytes per 16-byte store
+template <bool VEC, typename ST>
+__global__ __launch_bounds__(256) void gather_kernel(const ST* __restrict__ images,
                                                      const long long* __restrict__ pos, float* __restrict__ out,
                                                      long long out_sample_stride, int C, int H, int W, int P,
                                                      long long total, const int* __restrict__ skip_flag,
@@ -32,26 +34,45 @@ __global__ __launch_bounds__(256) void gather_kernel(const float* __restrict__ i
       else *dp = 0.f;
       continue;
     }
-    const float* sp = images + ((im * C + c) * H + y * P + r) * W + x * P + q * V;
-    if (VEC) *reinterpret_cast<f32x4*>(dp) = *reinterpret_cast<const f32x4*>(sp);
-    else *dp = *sp;
+    const ST* sp = images + ((im * C + c) * H + y * P + r) * W + x * P + q * V;
+    if constexpr (std::is_same<ST, uint8_t>::value) {
+      if (VEC) *reinterpret_cast<f32x4*>(dp) = u8x4_unit(*reinterpret_cast<const uint32_t*>(sp));
+      else *dp = u8_unit(*sp);
+    } else {
+      if (VEC) *reinterpret_cast<f32x4*>(dp) = *reinterpret_cast<const f32x4*>(sp);
+      else *dp = *sp;
+    }
   }
+}
+
+// VEC: four values per thread; the source rows must be aligned to four elements (16 bytes of fp32, 4 of uint8)
+template <typename ST>
+static int launch_gather_t(const ST* images, const int64_t* positions, float* out, long long out_sample_stride, int B,
+                           int C, int H, int W, int P, const int* skip_flag, int skip_when, hipStream_t s,
+                           const int64_t* image_index) {
+  const bool vec = (P % 4 == 0) && (W % 4 == 0) && (out_sample_stride % 4 == 0) &&
+                   ((uintptr_t)images % (4 * sizeof(ST)) == 0) && ((uintptr_t)out % 16 == 0);
+  const long long total = (long long)B * C * P * (P / (vec ? 4 : 1));
+  const unsigned blocks = (unsigned)std::min<long long>((total + 255) / 256, 256 * 32);
+  if (vec)
+    hipLaunchKernelGGL((gather_kernel<true, ST>), dim3(blocks), dim3(256), 0, s, images, (const long long*)positions, out,
+                       out_sample_stride, C, H, W, P, total, skip_flag, skip_when, (const long long*)image_index);
+  else
+    hipLaunchKernelGGL((gather_kernel<false, ST>), dim3(blocks), dim3(256), 0, s, images, (const long long*)positions, out,
+                       out_sample_stride, C, H, W, P, total, skip_flag, skip_when, (const long long*)image_index);
+  return 0;
 }
 
 int launch_gather(const float* images, const int64_t* positions, float* out, long long out_sample_stride, int B,
                   int C, int H, int W, int P, const int* skip_flag, int skip_when, hipStream_t s,
                   const int64_t* image_index) {
-  const bool vec = (P % 4 == 0) && (W % 4 == 0) && (out_sample_stride % 4 == 0) &&
-                   (((uintptr_t)images | (uintptr_t)out) % 16 == 0);
-  const long long total = (long long)B * C * P * (P / (vec ? 4 : 1));
-  const unsigned blocks = (unsigned)std::min<long long>((total + 255) / 256, 256 * 32);
-  if (vec)
-    hipLaunchKernelGGL(gather_kernel<true>, dim3(blocks), dim3(256), 0, s, images, (const long long*)positions, out,
-                       out_sample_stride, C, H, W, P, total, skip_flag, skip_when, (const long long*)image_index);
-  else
-    hipLaunchKernelGGL(gather_kernel<false>, dim3(blocks), dim3(256), 0, s, images, (const long long*)positions, out,
-                       out_sample_stride, C, H, W, P, total, skip_flag, skip_when, (const long long*)image_index);
-  return 0;
+  return launch_gather_t(images, positions, out, out_sample_stride, B, C, H, W, P, skip_flag, skip_when, s, image_index);
+}
+
+int launch_gather(const uint8_t* images, const int64_t* positions, float* out, long long out_sample_stride, int B,
+                  int C, int H, int W, int P, const int* skip_flag, int skip_when, hipStream_t s,
+                  const int64_t* image_index) {
+  return launch_gather_t(images, positions, out, out_sample_stride, B, C, H, W, P, skip_flag, skip_when, s, image_index);
 }
 
 // convert_bboxes_to_masks (src/env/general_env.py:360-379) on the patch grid: a box covers

@@ -29,13 +29,18 @@ def padded_collate(images: Sequence[Tensor], bboxes: Sequence[Tensor], patch_siz
     return res
 
 
-def synthetic_batch(batch_size: int, grid: int, patch_size: int, seed: int, device="cuda", max_boxes: int = 3) -> Dict[str, Tensor]:
+def synthetic_batch(batch_size: int, grid: int, patch_size: int, seed: int, device="cuda", max_boxes: int = 3,
+                    dtype=torch.float32) -> Dict[str, Tensor]:
     """SURVEY.md §8(d) synthetic inputs, generated ON the device: images uniform in [0, 1) of (grid * patch_size)^2
     pixels, 1..max_boxes boxes per image with sides in [32, patch_size) fully inside the image (int64 xyxy, zero-row
-    padded), start positions uniform over the grid.  Deterministic in `seed`."""
+    padded), start positions uniform over the grid.  Deterministic in `seed`.  dtype=torch.uint8: bytes uniform over
+    0..255 instead (8-bit images, for envs with uint8_images=True); the boxes and starts are those of the fp32 form."""
     side = grid * patch_size
     gen = torch.Generator(device=device).manual_seed(seed)
-    images = torch.rand((batch_size, 3, side, side), device=device, generator=gen)
+    if dtype == torch.uint8:
+        images = torch.randint(0, 256, (batch_size, 3, side, side), device=device, generator=gen, dtype=torch.uint8)
+    else:
+        images = torch.rand((batch_size, 3, side, side), device=device, generator=gen)
     g = torch.Generator().manual_seed(seed)
     boxes = torch.zeros((batch_size, max_boxes, 4), dtype=torch.long)
     for b in range(batch_size):

@@ -1,6 +1,10 @@
 """``NeedleGeneralEnv`` — batched needle environment of the reference
 (src/env/general_env.py:14-573) with all state on the device, stepped by
-libjnroll.so (``jn_env_*``).  n_glimps_levels must be 1 (src/reinforce.py:58)."""
+libjnroll.so (``jn_env_*``).  n_glimps_levels must be 1 (src/reinforce.py:58).
+
+The images stay where the caller put them: fp32 values in [0, 1], or, with
+``uint8_images=True``, the 8-bit pixels themselves (a quarter of the upload and of
+the HBM), which every kernel reads as byte / 255 exactly as ToTensor computes it."""
 from typing import Tuple
 
 import torch
@@ -13,7 +17,8 @@ from .engine import Engine, bare_env_config
 
 class NeedleGeneralEnv:
     def __init__(self, images: Tensor, bboxes: Tensor, patch_size: int, max_ep_len: int,
-                 n_glimps_levels: int = 1, stop_enabled: bool = False, engine: Engine = None):
+                 n_glimps_levels: int = 1, stop_enabled: bool = False, engine: Engine = None, *,
+                 uint8_images: bool = False):
         assert images.shape[0] == bboxes.shape[0]          # general_env.py:37-39
         assert len(images.shape) == 4
         assert n_glimps_levels > 0
@@ -30,7 +35,12 @@ class NeedleGeneralEnv:
         self.n_vertical_patches = self.height // patch_size
         self.n_horizontal_patches = self.width // patch_size
         self.device = images.device
-        self._images = images.to(torch.float32).contiguous()
+        # uint8_images: a uint8 tensor is used in place (jn_env_init_u8); otherwise (or for float images) it becomes fp32
+        self.uint8_images = bool(uint8_images) and images.dtype == torch.uint8
+        if self.uint8_images:
+            self._images = images.contiguous()
+        else:
+            self._images = images.to(torch.float32).contiguous()
         self.bboxes = bboxes
         self._bboxes_dev = bboxes.to(self.device, torch.int64).contiguous()
         self._engine = None
@@ -46,9 +56,10 @@ class NeedleGeneralEnv:
             return
         self._engine = engine
         nb = self._bboxes_dev.shape[1] if self._bboxes_dev.dim() == 3 else 0
-        check(engine.lib.jn_env_init(engine.handle, ptr(self._images), ptr(self._bboxes_dev), self.batch_size,
-                                     self.height, self.width, nb, self.max_ep_len, int(self.stop_enabled),
-                                     self._stream()), "jn_env_init")
+        init = engine.lib.jn_env_init_u8 if self.uint8_images else engine.lib.jn_env_init
+        check(init(engine.handle, ptr(self._images), ptr(self._bboxes_dev), self.batch_size,
+                   self.height, self.width, nb, self.max_ep_len, int(self.stop_enabled),
+                   self._stream()), "jn_env_init")
 
     def _stream(self):
         return _lib.current_stream(self.device)
@@ -69,7 +80,7 @@ class NeedleGeneralEnv:
     # ---- reference surface -------------------------------------------------------------
     @property
     def images(self) -> Tensor:
-        return self._images.unsqueeze(1)                   # [B, 1, C, H, W] (general_env.py:115)
+        return self._images.unsqueeze(1)                   # [B, 1, C, H, W] (general_env.py:115); uint8 env: the bytes
 
     @property
     def positions(self) -> Tensor:
@@ -150,13 +161,22 @@ class NeedleGeneralEnv:
         any_box = masks.any(-1).cpu()
         P = self.patch_size
         patches, all_boxes = [], []
+        cells = []                                         # uint8 env: (image, y, x) of each patch, one gather below
         for i in range(self.batch_size):
             pos = torch.nonzero(any_box[i])
             neg = torch.nonzero(~any_box[i])
             neg = neg[torch.randperm(len(neg), generator=generator)[:sample_neg]]
             for y, x in torch.cat((pos, neg)).tolist():
-                patches.append(self._images[i, :, y * P:(y + 1) * P, x * P:(x + 1) * P])
+                if self.uint8_images:
+                    cells.append((i, y, x))
+                else:
+                    patches.append(self._images[i, :, y * P:(y + 1) * P, x * P:(x + 1) * P])
                 all_boxes.append(torch.nn.functional.pad(boxes[i, y, x], (1, 0)))
+        if self.uint8_images:
+            from .trajectory import gather_indexed
+            cells = torch.tensor(cells, dtype=torch.int64).reshape(-1, 3)
+            return (gather_indexed(self._images, cells[:, 0], cells[:, 1:], P),
+                    torch.stack(all_boxes).to(self.device))
         return torch.stack(patches), torch.stack(all_boxes).to(self.device)
 
     @property

@@ -174,7 +174,7 @@ class ReinforceTrainer:
         model.train()
         images, bboxes = batch["image"].to(self.device), batch["bboxes"]
         env = NeedleGeneralEnv(images, bboxes, self.patch_size, self.max_ep_len, self.n_glimps_levels, self.stop_enabled,
-                               engine=model.engine())
+                               engine=model.engine(), uint8_images=bool(getattr(config, "uint8_images", False)))
         rollout = self.rollout(env, keep_patches=False, **rollout_kw)
         metrics = self.compute_metrics(rollout)
         loss = metrics["loss"]

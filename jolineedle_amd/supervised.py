@@ -49,7 +49,10 @@ class SupervisedTrainer:
         images = batch["image"]
         if not isinstance(images, torch.Tensor):
             images = torch.stack(list(images))
-        images = images.to(self.device, torch.float32).contiguous()
+        if getattr(cfg, "uint8_images", False) and images.dtype == torch.uint8:
+            images = images.to(self.device).contiguous()          # the bytes, gathered as byte / 255
+        else:
+            images = images.to(self.device, torch.float32).contiguous()
         P = int(cfg.patch_size)
         idx = []
         for i in range(images.shape[0]):

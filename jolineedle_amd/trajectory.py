@@ -254,10 +254,12 @@ class NeedleSimpleEnv:
 
 
 def gather_indexed(images: torch.Tensor, image_index: torch.Tensor, positions: torch.Tensor, patch_size: int) -> torch.Tensor:
-    """out[n] = images[image_index[n], :, y*P:(y+1)*P, x*P:(x+1)*P]; a negative image index gives a zero patch."""
+    """out[n] = images[image_index[n], :, y*P:(y+1)*P, x*P:(x+1)*P]; a negative image index gives a zero patch.
+    uint8 images are read in place and give byte / 255 (fp32, as ToTensor computes it)."""
     from . import _lib
     from ._lib import check, ptr
-    assert images.is_cuda and images.dtype == torch.float32 and images.is_contiguous(), "images must be a contiguous f32 device tensor"
+    assert images.is_cuda and images.dtype in (torch.float32, torch.uint8) and images.is_contiguous(), \
+        "images must be a contiguous f32 or uint8 device tensor"
     nimg, Cc, H, W = images.shape
     P = int(patch_size)
     assert H % P == 0 and W % P == 0
@@ -273,8 +275,9 @@ def gather_indexed(images: torch.Tensor, image_index: torch.Tensor, positions: t
     lib = _lib.load_library()
     if N == 0:                                # empty tensors have no storage to point at
         return out
-    check(lib.jn_gather_patches_indexed(ptr(images), ptr(ii), ptr(pos), ptr(out), N, nimg, Cc, H, W, P,
-                                        _lib.current_stream(images.device)), "jn_gather_patches_indexed")
+    fn = lib.jn_gather_patches_indexed_u8 if images.dtype == torch.uint8 else lib.jn_gather_patches_indexed
+    check(fn(ptr(images), ptr(ii), ptr(pos), ptr(out), N, nimg, Cc, H, W, P,
+             _lib.current_stream(images.device)), "jn_gather_patches_indexed")
     return out
 
 
