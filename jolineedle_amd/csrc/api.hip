@@ -363,6 +363,11 @@ int jn_create(const jn_config* cfg, jn_ctx** out) {
   } else {
     ctx->enc_net = JN_NET_DETECTOR;
   }
+  // the plans of the training backwards, checked here so that a broken one fails now (each backward plans again): the
+  // patch encoder fed through fpn[2] alone, unless it is the detached detector, and the detector with its head
+  std::vector<BwdStep> plan;
+  if (ctx->enc_net != JN_NET_DETECTOR && (rc = plan_backward(ctx->nets[ctx->enc_net], false, 0x3, plan))) return rc;
+  if (cfg->with_detector && (rc = plan_backward(ctx->nets[JN_NET_DETECTOR], true, 0, plan))) return rc;
   if (!cfg->no_patch_emb) {
     const Net& enc = ctx->nets[ctx->enc_net];
     ctx->efpn_cin = enc.fpn[2].C; ctx->efpn_h = enc.fpn[2].H; ctx->efpn_w = enc.fpn[2].W;
@@ -1007,125 +1012,20 @@ static int ensure_aux_stream(jn_ctx* ctx) {
   return JN_OK;
 }
 
-static inline bool views_overlap(const View& a, const View& b) {
-  return a.buf >= 0 && a.buf == b.buf && a.coff < b.coff + b.C && b.coff < a.coff + a.C;
-}
-
-// Backward fusion of a producer's BN reduce into its consumer: returns the index of the ONE BatchNorm conv whose
-// output view is exactly ops[obi].in, provided ops[obi] is the only reader of that view, nothing else writes into it
-// and no gradient arrives from outside the network (FPN outputs); -1 otherwise.
-// fpn_zero: bit i set = NO gradient arrives in net.fpn[i] from outside the network in this backward (the REINFORCE /
-// supervised backward only feeds fpn[2]); such a view is an ordinary single-consumer output.
-static int sole_producer(const Net& net, int obi, int fpn_zero = 0) {
-  const View& v = net.ops[obi].in;
-  for (int i = 0; i < 3; ++i)
-    if (!((fpn_zero >> i) & 1) && views_overlap(v, net.fpn[i])) return -1;
-  int prod = -1;
-  for (int j = 0; j < (int)net.ops.size(); ++j) {
-    const Op& o = net.ops[j];
-    if (j != obi && (views_overlap(o.in, v) || views_overlap(o.res, v))) return -1;
-    if (o.kind == OP_SPP && o.out.buf == v.buf) return -1;            // works on the whole concat buffer
-    if (views_overlap(o.out, v) || views_overlap(o.alias, v)) {
-      if (prod >= 0 || j >= obi) return -1;
-      prod = j;
-    }
-  }
-  if (prod < 0) return -1;
-  const Op& po = net.ops[prod];
-  if (po.wslot < 0 || po.out.coff != v.coff || po.out.C != v.C || po.out.buf != v.buf) return -1;
-  const ConvW& pw = net.convs[po.wslot];
-  if (!pw.has_bn || !pw.prefix2.empty() || pw.cout != v.C) return -1;
-  return prod;
-}
-
-// Generalisation for the fused 1x1 kernels (round 3): the producer of channel segment [coff, coff + C) of buffer `buf` as
-// ONE BatchNorm conv — its whole output, or one half of a merged conv2|conv1 pair (half 0 = conv2 rows, 1 = conv1 rows) —
-// whose only reader is op `reader` (plus, optionally, the shortcut add `folded_addact` whose gradient copy the reader's
-// kernel has absorbed).  The reader then holds the FINAL gradient of the segment and can form that layer's BN-backward
-// sums in its epilogue.
-struct RedRun { int wslot = -1; int half = -1; };     // half -1: whole conv
-static bool red_segment(const Net& net, int reader, int buf, int coff, int C, int folded_addact, RedRun& out, int fpn_zero = 0) {
-  View seg; seg.buf = buf; seg.coff = coff; seg.C = C;
-  for (int i = 0; i < 3; ++i)
-    if (!((fpn_zero >> i) & 1) && views_overlap(seg, net.fpn[i])) return false;
-  int prod = -1;
-  for (int j = 0; j < (int)net.ops.size(); ++j) {
-    const Op& o = net.ops[j];
-    if (j != reader && views_overlap(o.in, seg)) return false;
-    if (j != reader && j != folded_addact && views_overlap(o.res, seg)) return false;
-    if (o.kind == OP_SPP && o.out.buf == buf) return false;
-    if (views_overlap(o.out, seg) || views_overlap(o.alias, seg)) {
-      if (prod >= 0 || j >= reader) return false;
-      prod = j;
-    }
-  }
-  if (prod < 0) return false;
-  const Op& po = net.ops[prod];
-  if (po.wslot < 0 || po.out.buf != buf || views_overlap(po.alias, seg)) return false;
-  const ConvW& pw = net.convs[po.wslot];
-  if (!pw.has_bn) return false;
-  if (pw.prefix2.empty()) {
-    if (po.out.coff != coff || po.out.C != C || pw.cout != C) return false;
-    out.wslot = po.wslot; out.half = -1;
-    return true;
-  }
-  if (pw.cout != 2 * C || 2 * pw.cout_first != pw.cout || po.out.C != 2 * C) return false;
-  if (coff == po.out.coff) out.half = 0; else if (coff == po.out.coff + C) out.half = 1; else return false;
-  out.wslot = po.wslot;
-  return true;
-}
-
-// RED2 (round 3): segment [coff, coff + C) of `buf` is a materialised shortcut sum (the output of an OP_ADDACT) read only by
-// op `reader` (and, as residual, by the shortcut add `folded_addact` whose gradient copy the reader's kernel absorbs): the
-// reader writes the FINAL gradient of the sum, which is also the gradient of the activation of the add's `in` operand —
-// the bottleneck's last pointwise conv.  Returns that conv's op index (BatchNorm, whole output == the add's `in`, no other
-// reader) and the add's index, or -1.
-static int shortcut_sum_conv(const Net& net, int reader, int buf, int coff, int C, int folded_addact, int* addact_out) {
-  View seg; seg.buf = buf; seg.coff = coff; seg.C = C;
-  for (int i = 0; i < 3; ++i)
-    if (views_overlap(seg, net.fpn[i])) return -1;
-  int add = -1;
-  for (int j = 0; j < (int)net.ops.size(); ++j) {
-    const Op& o = net.ops[j];
-    if (j != reader && views_overlap(o.in, seg)) return -1;
-    if (j != reader && j != folded_addact && views_overlap(o.res, seg)) return -1;
-    if (o.kind == OP_SPP && o.out.buf == buf) return -1;
-    if (views_overlap(o.out, seg) || views_overlap(o.alias, seg)) {
-      if (add >= 0 || j >= reader) return -1;
-      add = j;
-    }
-  }
-  if (add < 0 || net.ops[add].kind != OP_ADDACT) return -1;
-  const Op& ao = net.ops[add];
-  if (ao.out.coff != coff || ao.out.C != C || ao.in.C != C) return -1;
-  int conv = -1;
-  for (int j = 0; j < (int)net.ops.size(); ++j) {
-    const Op& o = net.ops[j];
-    if (j != add && (views_overlap(o.in, ao.in) || views_overlap(o.res, ao.in))) return -1;
-    if (j == add && views_overlap(o.res, ao.in)) return -1;
-    if (views_overlap(o.out, ao.in) || views_overlap(o.alias, ao.in)) {
-      if (conv >= 0 || j >= add) return -1;
-      conv = j;
-    }
-  }
-  if (conv < 0) return -1;
-  const Op& co = net.ops[conv];
-  if (co.wslot < 0 || co.kind != OP_PW || views_overlap(co.alias, ao.in)) return -1;
-  const ConvW& cw = net.convs[co.wslot];
-  if (!cw.has_bn || !cw.prefix2.empty() || co.out.buf != ao.in.buf || co.out.coff != ao.in.coff || co.out.C != C || cw.cout != C) return -1;
-  *addact_out = add;
-  return conv;
-}
-
 // Backward of `nsl` train-mode PAFPN passes (workspace slots slot .. slot + nsl - 1, N patches each; gradient
 // slots 0 .. nsl - 1): every kernel is launched ONCE for all the passes (SlotBatch), so a 20-step trajectory
 // costs the launches of one pass.  g[fpn views] must hold the incoming gradients; parameter gradients are
 // accumulated into ctx->grads.  ss.positions belongs to the first pass, pos_slot_stride int64s separate passes.
+// fpn_zero: bit i set = NO gradient arrives in net.fpn[i] from outside the network (the REINFORCE / supervised backward
+// only feeds fpn[2]).  The routes come from plan_backward (plan.cpp); what depends on launch-time state stays here.
 static int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, hipStream_t s, int nsl = 1,
                             long long pos_slot_stride = 0, bool with_head = false, int fpn_zero = 0) {
   Net& net = ctx->nets[ni];
   const int MB = ctx->cfg.max_batch;
   JN_CHECK(nsl >= 1 && nsl <= net.g_slots && slot + nsl <= net.n_slots, JN_ESTATE, "backward over %d slots from %d: not allocated", nsl, slot);
+  std::vector<BwdStep> plan;
+  int rc = plan_backward(net, with_head, fpn_zero, plan);
+  if (rc) return rc;
   JN_HIP(hipMemsetAsync(net.bred, 0, (size_t)nsl * JN_NREP * 2 * net.stat_channels * sizeof(double), s));
   const long long rep_stride = 2LL * net.stat_channels;
   SlotBatch sb;
@@ -1142,18 +1042,18 @@ static int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int s
   auto gptr = [&](const View& v) { return net.gact + net.buf_off[v.buf] * (size_t)MB + v.coff; };
   auto tab = [&](const View& v) { return view_tab(net, slot, v); };
   auto ld = [&](const View& v) { return net.bufs[v.buf].C; };
+  auto sums = [&](int p, int half) {      // BN-backward sums of op p (half -1: the whole conv)
+    const ConvW& pcw = net.convs[net.ops[p].wslot];
+    return net.bred + 2 * (pcw.stat_off + (half > 0 ? pcw.cout / 2 : 0));
+  };
   const ChanTab ident{ctx->ident, ctx->ident + 2048, ctx->ident + 4096};
-  std::map<int, std::pair<int, View>> g_alias;      // conv output buffer -> (coff, gradient view to read instead)
-  std::set<int> red_done;                           // conv slots whose BN-backward sums a consumer's kernel already formed
-  std::map<int, int> red_half;                      // merged pairs: bit h set = half h's sums were formed by its consumer
-  std::map<int, View> shortcut_grad;                // op index of a bottleneck's conv1 -> gradient view of its shortcut sum
-  std::map<int, int> shortcut_addact;               // ... -> index of the shortcut add whose copy the conv1 kernel absorbs
   // Wide 1x1 layers (unfused path): the weight-gradient GEMM only feeds the optimiser, so it runs on a second stream
   // beside the data-gradient GEMM of the same layer and whatever follows; joined before this function returns.
   static const bool no_aux = std::getenv("JN_NO_AUX_STREAM") != nullptr;
+  static const bool dbg_plan = std::getenv("JN_DBG_BWD_PLAN") != nullptr;
   bool aux_used = false;
   if (!no_aux) { int ra = ensure_aux_stream(ctx); if (ra) return ra; }
-  const int n_ops_b = (with_head || net.n_backbone_ops < 0) ? (int)net.ops.size() : net.n_backbone_ops;
+  const int n_ops_b = (int)plan.size();
   // JN_BWD_PROFILE=1: HIP events around the launches of every op, table on stderr (a measuring aid; use it together with
   // JN_NO_AUX_STREAM=1 so that the wide weight-gradient GEMMs are inside the brackets)
   static const bool bwd_profile = std::getenv("JN_BWD_PROFILE") != nullptr;
@@ -1161,38 +1061,28 @@ static int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int s
   if (bwd_profile) {
     bev.resize(n_ops_b + 1);
     for (auto& e : bev) (void)hipEventCreate(&e);
+    (void)hipEventRecord(bev[n_ops_b], s);
   }
-  struct BwdProfileMark {        // records the event of op `i` when the loop body is left (continue / break / fall through)
-    std::vector<hipEvent_t>& ev; int i; hipStream_t s;
-    ~BwdProfileMark() { if (!ev.empty()) (void)hipEventRecord(ev[i], s); }
-  };
-  if (bwd_profile) (void)hipEventRecord(bev[n_ops_b], s);
   for (int obi = n_ops_b - 1; obi >= 0; --obi) {
     const Op& op = net.ops[obi];
-    BwdProfileMark mark{bev, obi, s};
+    const BwdStep& st = plan[obi];
     if (op.wslot >= 0) {
       const ConvW& cw = net.convs[op.wslot];
-      JN_CHECK(cw.has_bn, JN_ESTATE, "backward of BN-free conv %s inside a PAFPN", op.name.c_str());
-      // the gradient of a conv that feeds a shortcut add IS the gradient of the sum: read it in place
-      const auto al = g_alias.find(op.out.buf);
-      const View gview = (al != g_alias.end() && al->second.first == op.out.coff) ? al->second.second : op.out;
-      float* const gp_out = gptr(gview);
-      const int gld_out = ld(gview);
+      float* const gp_out = gptr(st.g);
+      const int gld_out = ld(st.g);
       const long long M = (long long)N * op.out.H * op.out.W;
       double* red = net.bred + 2 * cw.stat_off;
       float* consts = net.bconsts + 3 * cw.stat_off;
-      static const bool dbg_plan = std::getenv("JN_DBG_BWD_PLAN") != nullptr;
-      const int hmask = red_half.count(op.wslot) ? red_half[op.wslot] : 0;
+      const bool pair_halves = st.red_by && !cw.prefix2.empty();
       if (dbg_plan) {
         // elements per patch that a separate bn_bwd_reduce pass re-reads (g and z: 8 bytes each); merged pairs per half
-        const bool pair_halves = hmask && !cw.prefix2.empty() && net.act_dtype == JN_F32;
-        const long long sep = red_done.count(op.wslot) ? 0 : pair_halves ? (M / N) * (cw.cout / 2) * (2 - ((hmask & 1) + ((hmask >> 1) & 1)))
-                                                                         : (M / N) * cw.cout;
+        const int hm = st.red_by;
+        const long long sep = pair_halves ? (M / N) * (cw.cout / 2) * (2 - ((hm & 1) + ((hm >> 1) & 1))) : hm ? 0 : (M / N) * cw.cout;
         std::fprintf(stderr, "[bwd-plan] %-34s kind %d cout %4d cin %4d M/patch %6lld stride %d acc_in %d separate-reduce elements/patch %8lld%s\n",
                      op.name.c_str(), (int)op.kind, cw.cout, cw.cin, M / N, op.stride, (int)op.acc_in, sep,
-                     pair_halves ? (hmask == 3 ? " (both halves by their consumers)" : " (one half by its consumer)") : "");
+                     pair_halves ? (hm == 3 ? " (both halves by their consumers)" : " (one half by its consumer)") : "");
       }
-      if (hmask && !cw.prefix2.empty() && net.act_dtype == JN_F32) {
+      if (pair_halves) {
         // merged pair with at least one half reduced by its consumer: the other half (if any) gets its own pass, and the
         // constants are formed per half (consumer-made sums carry the moment against y, see bn_bwd_consts)
         const int h = cw.cout / 2;
@@ -1200,25 +1090,22 @@ static int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int s
           const int c0 = half * h;
           ChanTab ot = tab(op.out);
           ot.sc += c0; ot.sh += c0; ot.fl += c0;
-          if (!(hmask & (1 << half)))
+          if (!(st.red_by & (1 << half)))
             launch_bn_bwd_reduce(gp_out + c0, gld_out, (const float*)ptr(op.out) + c0, net.act_dtype, ld(op.out), ot,
                                  save + 2 * (cw.stat_off + c0), h, M, red + 2 * c0, rep_stride, s, sb);
           launch_bn_bwd_consts(red + 2 * c0, rep_stride, (double)M, cw.gamma_dev + c0, cw.beta_dev + c0, save + 2 * (cw.stat_off + c0), consts + 3 * c0,
-                               grad_of(ctx, cw.gamma_dev) + c0, grad_of(ctx, cw.beta_dev) + c0, h, s, sb, (hmask >> half) & 1);
+                               grad_of(ctx, cw.gamma_dev) + c0, grad_of(ctx, cw.beta_dev) + c0, h, s, sb, (st.red_by >> half) & 1);
         }
       } else {
-        if (!red_done.count(op.wslot))
+        if (!st.red_by)
           launch_bn_bwd_reduce(gp_out, gld_out, ptr(op.out), net.act_dtype, ld(op.out), tab(op.out), save + 2 * cw.stat_off, cw.cout,
                                M, red, rep_stride, s, sb);
         launch_bn_bwd_consts(red, rep_stride, (double)M, cw.gamma_dev, cw.beta_dev, save + 2 * cw.stat_off, consts,
-                             grad_of(ctx, cw.gamma_dev), grad_of(ctx, cw.beta_dev), cw.cout, s, sb, red_done.count(op.wslot) ? 1 : 0);
+                             grad_of(ctx, cw.gamma_dev), grad_of(ctx, cw.beta_dev), cw.cout, s, sb, st.red_by & 1);
       }
       float* gw = grad_of(ctx, cw.w_dev);
-      // a merged pair too wide for the fused kernel is differentiated as its two halves (independent output rows)
-      const bool whole = pw_bwd_fused_supported(cw.cout, cw.cin);
-      const bool halves = !whole && !cw.prefix2.empty() && 2 * cw.cout_first == cw.cout && pw_bwd_fused_supported(cw.cout_first, cw.cin);
-      if (op.kind == OP_PW && net.act_dtype == JN_F32 && (whole || halves)) {
-        const int parts = whole ? 1 : 2, pc = cw.cout / parts;
+      if (st.route == BR_PW_FUSED || st.route == BR_PW_FUSED_HALVES) {
+        const int parts = st.route == BR_PW_FUSED ? 1 : 2, pc = cw.cout / parts;
         for (int part = 0; part < parts; ++part) {
           const int c0 = part * pc;
           ChanTab ot = tab(op.out);
@@ -1229,65 +1116,25 @@ static int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int s
           fa.x = (const float*)ptr(op.in); fa.x_ld = ld(op.in); fa.it = tab(op.in); fa.w = cw.w_dev + (size_t)c0 * cw.cin;
           fa.gx = gptr(op.in); fa.gx_ld = ld(op.in); fa.accumulate = (op.acc_in || part > 0) ? 1 : 0;
           fa.gw = gw + (size_t)c0 * cw.cin; fa.wpart = ctx->wpart; fa.M = M; fa.cout = pc; fa.cin = cw.cin; fa.sb = sb;
-          const auto sg = shortcut_grad.find(obi);
-          const bool folded = sg != shortcut_grad.end();
-          if (folded) {                         // the shortcut add's backward left its copy to this kernel (OP_ADDACT below)
-            fa.gadd = gptr(sg->second); fa.gadd_ld = ld(sg->second); fa.accumulate = 0;
+          if (st.fold >= 0) {                   // the shortcut add's backward left its copy to this kernel
+            const View& sum = net.ops[st.fold].out;
+            fa.gadd = gptr(sum); fa.gadd_ld = ld(sum); fa.accumulate = 0;
           }
-          // BN-backward sums of the input's producer(s) in this kernel's epilogue: it must write the FINAL gradient of
-          // the view (sole reader, or the shortcut folded in) — one run, or the two halves of a CSP conv3's input
-          if (parts == 1 && (!op.acc_in || folded) && pw_bwd_fused_reduces_input(pc, cw.cin)) {
-            const int fa_idx = folded ? shortcut_addact[obi] : -1;
-            auto base_of = [&](const RedRun& r) {
-              const ConvW& pcw = net.convs[r.wslot];
-              const int c0 = r.half > 0 ? pcw.cout / 2 : 0;
-              return net.bred + 2 * (pcw.stat_off + c0);
-            };
-            auto mark = [&](const RedRun& r) {
-              if (r.half < 0) red_done.insert(r.wslot); else red_half[r.wslot] |= 1 << r.half;
-            };
-            RedRun r0, r1;
-            // RED2: a run that is a shortcut sum -> sums of the conv behind it (its raw output and table instead of the input's)
-            auto red2 = [&](int coff, int C, int fidx) {
-              int add = -1;
-              const int conv = shortcut_sum_conv(net, obi, op.in.buf, coff, C, fidx, &add);
-              if (conv < 0) return false;
-              const Op& co = net.ops[conv];
-              const ConvW& pcw = net.convs[co.wslot];
-              const ChanTab zt = tab(co.out);
-              fa.red2_z = (const float*)ptr(co.out); fa.red2_ld = ld(co.out); fa.red2_sc = zt.sc; fa.red2_sh = zt.sh;
-              fa.red_in = net.bred + 2 * pcw.stat_off; fa.red_rep_stride = rep_stride;
-              red_done.insert(co.wslot);
-              return true;
-            };
-            if (red_segment(net, obi, op.in.buf, op.in.coff, op.in.C, fa_idx, r0)) {
-              fa.red_in = base_of(r0); fa.red_rep_stride = rep_stride; mark(r0);
-            } else if (red2(op.in.coff, op.in.C, fa_idx)) {
-              fa.red_split = op.in.C;
-            } else if (op.in.C % 32 == 0 && !folded) {
-              const int hC = op.in.C / 2;
-              bool ok0 = red_segment(net, obi, op.in.buf, op.in.coff, hC, -1, r0);
-              const bool ok1 = red_segment(net, obi, op.in.buf, op.in.coff + hC, hC, -1, r1);
-              if (!ok0 && red2(op.in.coff, hC, -1)) {        // [shortcut sum | conv2 half]: the input of a CSP's conv3
-                fa.red_split = hC;
-                if (ok1) { fa.red_in2 = base_of(r1); mark(r1); }
-              } else
-              if (ok0 || ok1) {
-                fa.red_rep_stride = rep_stride; fa.red_split = hC;
-                if (ok0) { fa.red_in = base_of(r0); mark(r0); }
-                if (ok1) { fa.red_in2 = base_of(r1); mark(r1); }
-                if (!ok1) fa.red_in2 = nullptr;
-                // (a lone second run still needs the split: red_in stays null, red_in2 set)
-                if (!ok0 && ok1) fa.red_in = nullptr;
-              }
-            }
+          if (st.red_in >= 0 || st.red_in2 >= 0) fa.red_rep_stride = rep_stride;
+          if (st.red_in >= 0) fa.red_in = sums(st.red_in, st.red_half);
+          if (st.red_in2 >= 0) fa.red_in2 = sums(st.red_in2, st.red_half2);
+          fa.red_split = st.red_split;
+          if (st.red2) {                        // the sums of the conv behind the shortcut sum: its raw output and table
+            const Op& co = net.ops[st.red_in];
+            const ChanTab zt = tab(co.out);
+            fa.red2_z = (const float*)ptr(co.out); fa.red2_ld = ld(co.out); fa.red2_sc = zt.sc; fa.red2_sh = zt.sh;
           }
           launch_pw_bwd_fused(fa, s);
         }
-        continue;
-      }
-      if (op.kind == OP_DW && net.act_dtype == JN_F32 &&
-          dw_bwd_fused_supported(cw.cout, op.in.H, op.in.W, op.out.H, op.out.W, op.stride)) {
+      } else if (st.route == BR_DW_FUSED) {
+        // stride 2 (round 4): the owner-staged variant of the kernel (every thread stages the 2 x 2 input block it
+        // differentiates and keeps the raw values); round 3's variant re-read the input inside the gradient loop and lost
+        // more than the separate pass costs
         DwBwdFusedArgs fa{};
         fa.g = gp_out; fa.g_ld = gld_out; fa.z = (const float*)ptr(op.out); fa.z_ld = ld(op.out); fa.ot = tab(op.out);
         fa.save = save + 2 * cw.stat_off; fa.consts = consts;
@@ -1295,155 +1142,97 @@ static int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int s
         fa.gin = gptr(op.in); fa.gin_ld = ld(op.in); fa.accumulate = op.acc_in ? 1 : 0; fa.gw = gw; fa.wpart = ctx->wpart;
         fa.C = cw.cout; fa.H = op.in.H; fa.W = op.in.W; fa.OH = op.out.H; fa.OW = op.out.W; fa.N = N; fa.stride = op.stride;
         fa.sb = sb;
-        // stride 2 (round 4): the owner-staged variant of the kernel (every thread stages the 2 x 2 input block it
-        // differentiates and keeps the raw values); round 3's variant re-read the input inside the gradient loop and lost
-        // more than the separate pass costs.  A view that only the network's outside could also write (an FPN output) and
-        // that gets no outside gradient in this backward (fpn_zero) is an ordinary single-consumer output: this kernel
-        // then WRITES its gradient (the buffer holds zeros) and forms the producer's sums like for any other.
-        bool ext_zero = false;
-        for (int i = 0; i < 3; ++i) ext_zero = ext_zero || (((fpn_zero >> i) & 1) && views_overlap(op.in, net.fpn[i]));
-        if (!op.acc_in || ext_zero) {
-          const int prod = sole_producer(net, obi, fpn_zero);
-          if (prod >= 0) {
-            const ConvW& pcw = net.convs[net.ops[prod].wslot];
-            fa.red_in = net.bred + 2 * pcw.stat_off; fa.red_rep_stride = rep_stride;
-            fa.accumulate = 0;                      // sole reader: nothing but the (zero) outside seed was there before
-            red_done.insert(net.ops[prod].wslot);
-          }
+        if (st.red_in >= 0) {
+          fa.red_in = sums(st.red_in, st.red_half); fa.red_rep_stride = rep_stride;
+          fa.accumulate = 0;                      // sole reader: nothing but the (zero) outside seed was there before
         }
         launch_dw_bwd_fused(fa, s);
-        continue;
-      }
-      if (op.kind == OP_STEM && net.act_dtype == JN_F32) {
+      } else if (st.route == BR_STEM_FUSED) {
         StemArgs a{ss.src, ss.positions, ss.pos_stride, ss.sample_stride, ss.chan_stride, ss.row_stride, net.P, N, cw.cout,
                    cw.w_dev, nullptr, 0, JN_F32, nullptr, 0, nullptr, 0, 0, ss.src_u8};
         launch_stem_bwd_weight(a, gp_out, gld_out, gw, ctx->wpart, s, sb, (const float*)ptr(op.out), ld(op.out),
                                tab(op.out), save + 2 * cw.stat_off, consts);
-        continue;
-      }
-      launch_bn_bwd_gz(gp_out, gld_out, ptr(op.out), net.act_dtype, ld(op.out), tab(op.out), save + 2 * cw.stat_off, consts,
-                       cw.cout, M, s, sb);
-      if (op.kind == OP_PW) {
-        ConvArgs a{};
-        a.in = gp_out; a.in_ld = gld_out; a.in_dtype = JN_F32; a.itab = ident; a.w = cw.w_dev; a.bias = nullptr;
-        a.out = gptr(op.in); a.out_ld = ld(op.in); a.out_dtype = JN_F32; a.bf16_mfma = net.act_dtype == JN_BF16;
-        a.N = N; a.H = op.out.H; a.W = op.out.W; a.OH = op.out.H; a.OW = op.out.W;
-        a.cin = cw.cout; a.cout = cw.cin; a.stride = 1; a.act = ACT_NONE;
-        a.accumulate = op.acc_in ? 1 : 0; a.w_transposed = 1; a.in_identity = 1;
-        a.n_slots = nsl; a.in_slot_stride = sb.grad; a.out_slot_stride = sb.grad; a.tab_slot_stride = 0;
-        hipStream_t ws = s;
-        if (!no_aux && cw.cout >= 128 && cw.cin >= 128) {      // the wide kernel: plain atomics on gw, no shared scratch
-          JN_HIP(hipEventRecord(ctx->aux_fork, s));           // g_z is complete
-          JN_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->aux_fork, 0));
-          ws = ctx->aux_stream;
-          aux_used = true;
-        }
-        // wide layers, fp32: the data gradient on the bf16 pipe at fp32 accuracy (pw_x3_kernel over the slots, transposed
-        // weight split on the way: kernels_pwxs.hip); JN_NO_PW_X3_BWD=1 keeps pw_dir_kernel<WT> on the fp32 pipe
-        const bool no_x3_bwd = std::getenv("JN_NO_PW_X3_BWD") != nullptr;     // read per launch: a test flips it
-        bool x3_done = false;
-        if (!no_x3_bwd && net.act_dtype == JN_F32 && !op.acc_in && ctx->params_x3t && pw_x3_bwd_data_supported(cw.cout, cw.cin) &&
-            (cw.w_dev - ctx->params) % 8 == 0) {
-          x3_done = launch_pw_x3_bwd_data(a, cw.w_dev, ctx->params_x3t + 3 * (cw.w_dev - ctx->params), s) == 0;
-        }
-        if (!x3_done) launch_pw(a, s);
-        launch_pw_bwd_weight(gp_out, gld_out, ptr(op.in), net.act_dtype, ld(op.in), tab(op.in), gw, ctx->wpart, M, cw.cout,
-                             cw.cin, ws, sb);
-      } else if (op.kind == OP_DW) {
-        launch_dw_bwd_data(gp_out, gld_out, cw.w_dev, gptr(op.in), ld(op.in), cw.cout, op.in.H, op.in.W, op.out.H,
-                           op.out.W, N, op.stride, op.acc_in ? 1 : 0, s, sb);
-        launch_dw_bwd_weight(gp_out, gld_out, ptr(op.in), net.act_dtype, ld(op.in), tab(op.in), gw, ctx->wpart, cw.cout, op.in.H,
-                             op.in.W, op.out.H, op.out.W, N, op.stride, s, sb);
-      } else if (op.kind == OP_STEM) {
-        StemArgs a{ss.src, ss.positions, ss.pos_stride, ss.sample_stride, ss.chan_stride, ss.row_stride, net.P, N, cw.cout,
-                   cw.w_dev, nullptr, 0, JN_F32, nullptr, 0, nullptr, 0, 0, ss.src_u8};
-        launch_stem_bwd_weight(a, gp_out, gld_out, gw, ctx->wpart, s, sb);
-      } else if (op.kind == OP_CONV3) {
-        // dense 3x3 (non-depthwise patch encoders, e.g. yolox-s): stride 1 = the forward kernel over g_z with
-        // mirrored taps and the transposed weight; stride 2 = one MFMA tile loop per input-pixel parity class
-        int rc3 = 0;
-        hipStream_t ws3 = s;
-        if (!no_aux) {                     // the 9-tap weight gradient (plain atomics on gw) beside the data gradient
-          JN_HIP(hipEventRecord(ctx->aux_fork, s));
-          JN_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->aux_fork, 0));
-          ws3 = ctx->aux_stream;
-          aux_used = true;
-        }
-        if (op.stride == 1) {
+      } else {
+        launch_bn_bwd_gz(gp_out, gld_out, ptr(op.out), net.act_dtype, ld(op.out), tab(op.out), save + 2 * cw.stat_off, consts,
+                         cw.cout, M, s, sb);
+        if (st.route == BR_PW) {
           ConvArgs a{};
           a.in = gp_out; a.in_ld = gld_out; a.in_dtype = JN_F32; a.itab = ident; a.w = cw.w_dev; a.bias = nullptr;
-          a.out = gptr(op.in); a.out_ld = ld(op.in); a.out_dtype = JN_F32;
-          a.N = N; a.H = op.out.H; a.W = op.out.W; a.OH = op.in.H; a.OW = op.in.W;
+          a.out = gptr(op.in); a.out_ld = ld(op.in); a.out_dtype = JN_F32; a.bf16_mfma = net.act_dtype == JN_BF16;
+          a.N = N; a.H = op.out.H; a.W = op.out.W; a.OH = op.out.H; a.OW = op.out.W;
           a.cin = cw.cout; a.cout = cw.cin; a.stride = 1; a.act = ACT_NONE;
           a.accumulate = op.acc_in ? 1 : 0; a.w_transposed = 1; a.in_identity = 1;
-          a.n_slots = nsl; a.in_slot_stride = sb.grad; a.out_slot_stride = sb.grad;
-          rc3 = launch_conv3(a, s);
+          a.n_slots = nsl; a.in_slot_stride = sb.grad; a.out_slot_stride = sb.grad; a.tab_slot_stride = 0;
+          hipStream_t ws = s;
+          if (!no_aux && cw.cout >= 128 && cw.cin >= 128) {      // the wide kernel: plain atomics on gw, no shared scratch
+            JN_HIP(hipEventRecord(ctx->aux_fork, s));           // g_z is complete
+            JN_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->aux_fork, 0));
+            ws = ctx->aux_stream;
+            aux_used = true;
+          }
+          // wide layers, fp32: the data gradient on the bf16 pipe at fp32 accuracy (pw_x3_kernel over the slots, transposed
+          // weight split on the way: kernels_pwxs.hip); JN_NO_PW_X3_BWD=1 keeps pw_dir_kernel<WT> on the fp32 pipe
+          const bool no_x3_bwd = std::getenv("JN_NO_PW_X3_BWD") != nullptr;     // read per launch: a test flips it
+          bool x3_done = false;
+          if (!no_x3_bwd && net.act_dtype == JN_F32 && !op.acc_in && ctx->params_x3t && pw_x3_bwd_data_supported(cw.cout, cw.cin) &&
+              (cw.w_dev - ctx->params) % 8 == 0) {
+            x3_done = launch_pw_x3_bwd_data(a, cw.w_dev, ctx->params_x3t + 3 * (cw.w_dev - ctx->params), s) == 0;
+          }
+          if (!x3_done) launch_pw(a, s);
+          launch_pw_bwd_weight(gp_out, gld_out, ptr(op.in), net.act_dtype, ld(op.in), tab(op.in), gw, ctx->wpart, M, cw.cout,
+                               cw.cin, ws, sb);
+        } else if (st.route == BR_DW) {
+          launch_dw_bwd_data(gp_out, gld_out, cw.w_dev, gptr(op.in), ld(op.in), cw.cout, op.in.H, op.in.W, op.out.H,
+                             op.out.W, N, op.stride, op.acc_in ? 1 : 0, s, sb);
+          launch_dw_bwd_weight(gp_out, gld_out, ptr(op.in), net.act_dtype, ld(op.in), tab(op.in), gw, ctx->wpart, cw.cout, op.in.H,
+                               op.in.W, op.out.H, op.out.W, N, op.stride, s, sb);
+        } else if (st.route == BR_STEM) {
+          StemArgs a{ss.src, ss.positions, ss.pos_stride, ss.sample_stride, ss.chan_stride, ss.row_stride, net.P, N, cw.cout,
+                     cw.w_dev, nullptr, 0, JN_F32, nullptr, 0, nullptr, 0, 0, ss.src_u8};
+          launch_stem_bwd_weight(a, gp_out, gld_out, gw, ctx->wpart, s, sb);
         } else {
-          rc3 = launch_conv3_bwd_data_s2(gp_out, gld_out, cw.w_dev, gptr(op.in), ld(op.in), op.in.H, op.in.W, op.out.H,
-                                         op.out.W, cw.cout, cw.cin, N, op.acc_in ? 1 : 0, s, sb);
+          // dense 3x3 (non-depthwise patch encoders, e.g. yolox-s): stride 1 = the forward kernel over g_z with
+          // mirrored taps and the transposed weight; stride 2 = one MFMA tile loop per input-pixel parity class
+          int rc3 = 0;
+          hipStream_t ws3 = s;
+          if (!no_aux) {                     // the 9-tap weight gradient (plain atomics on gw) beside the data gradient
+            JN_HIP(hipEventRecord(ctx->aux_fork, s));
+            JN_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->aux_fork, 0));
+            ws3 = ctx->aux_stream;
+            aux_used = true;
+          }
+          if (st.route == BR_CONV3_S1) {
+            ConvArgs a{};
+            a.in = gp_out; a.in_ld = gld_out; a.in_dtype = JN_F32; a.itab = ident; a.w = cw.w_dev; a.bias = nullptr;
+            a.out = gptr(op.in); a.out_ld = ld(op.in); a.out_dtype = JN_F32;
+            a.N = N; a.H = op.out.H; a.W = op.out.W; a.OH = op.in.H; a.OW = op.in.W;
+            a.cin = cw.cout; a.cout = cw.cin; a.stride = 1; a.act = ACT_NONE;
+            a.accumulate = op.acc_in ? 1 : 0; a.w_transposed = 1; a.in_identity = 1;
+            a.n_slots = nsl; a.in_slot_stride = sb.grad; a.out_slot_stride = sb.grad;
+            rc3 = launch_conv3(a, s);
+          } else {
+            rc3 = launch_conv3_bwd_data_s2(gp_out, gld_out, cw.w_dev, gptr(op.in), ld(op.in), op.in.H, op.in.W, op.out.H,
+                                           op.out.W, cw.cout, cw.cin, N, op.acc_in ? 1 : 0, s, sb);
+          }
+          JN_CHECK(rc3 == 0, JN_ESTATE, "backward of dense 3x3 conv %s: unsupported shape", op.name.c_str());
+          launch_conv3_bwd_weight(gp_out, gld_out, ptr(op.in), net.act_dtype, ld(op.in), tab(op.in), gw, op.in.H, op.in.W,
+                                  op.out.H, op.out.W, cw.cout, cw.cin, N, op.stride, ws3, sb);
         }
-        JN_CHECK(rc3 == 0, JN_ESTATE, "backward of dense 3x3 conv %s: unsupported shape", op.name.c_str());
-        launch_conv3_bwd_weight(gp_out, gld_out, ptr(op.in), net.act_dtype, ld(op.in), tab(op.in), gw, op.in.H, op.in.W,
-                                op.out.H, op.out.W, cw.cout, cw.cin, N, op.stride, ws3, sb);
-      } else {
-        set_error("backward of op %s is not implemented", op.name.c_str());
-        return JN_ESTATE;
       }
-      continue;
+    } else if (st.route == BR_ADDACT_COPY || st.route == BR_ADDACT_FOLD) {
+      const long long M = (long long)N * op.out.H * op.out.W;
+      // (without acc_in the conv that feeds the add reads g[sum] in place, BwdStep::g; folded: that conv's kernel adds it)
+      if (op.acc_in) launch_grad_copy(gptr(op.out), ld(op.out), gptr(op.in), ld(op.in), op.out.C, M, 1, s, sb);
+      if (st.route == BR_ADDACT_COPY)
+        launch_grad_copy(gptr(op.out), ld(op.out), gptr(op.res), ld(op.res), op.out.C, M, op.acc_res ? 1 : 0, s, sb);
+    } else if (st.route == BR_SPP) {
+      const View full = net_full_view(net, op.out.buf);
+      launch_spp_bwd(ptr(full), net.act_dtype, gptr(full), ld(op.out), op.in.C, op.in.H, op.in.W, N, tab(op.in), s, sb);
+    } else if (st.route == BR_UPSAMPLE) {
+      launch_upsample_bwd(gptr(op.out), ld(op.out), gptr(op.in), ld(op.in), op.in.C, op.in.H, op.in.W, N,
+                          op.acc_in ? 1 : 0, s, sb);
     }
-    switch (op.kind) {
-      case OP_ADDACT: {
-        const long long M = (long long)N * op.out.H * op.out.W;
-        if (op.acc_in) launch_grad_copy(gptr(op.out), ld(op.out), gptr(op.in), ld(op.in), op.out.C, M, 1, s, sb);
-        else g_alias[op.in.buf] = std::make_pair(op.in.coff, op.out);       // sole consumer: no copy, see above
-        // The shortcut branch: g[res] += g[sum].  When the only other reader of `res` is the bottleneck's first 1x1 conv
-        // and that layer takes the fused backward kernel, the kernel adds g[sum] while it writes its data gradient (one
-        // read of g[sum] instead of a copy pass — read, read-modify-write — over the largest 16 / 32-channel maps)
-        {
-          int conv1 = -1, readers = 0;
-          for (int j = 0; j < n_ops_b; ++j) {
-            const Op& o = net.ops[j];
-            if (j != obi && (views_overlap(o.in, op.res) || views_overlap(o.res, op.res))) {
-              ++readers;
-              if (o.kind == OP_PW && o.in.buf == op.res.buf && o.in.coff == op.res.coff && o.in.C == op.res.C && j < obi) conv1 = j;
-            }
-          }
-          bool fold = !op.acc_res && readers == 1 && conv1 >= 0 && net.act_dtype == JN_F32;
-          if (fold) {
-            const Op& c1 = net.ops[conv1];
-            const ConvW& cw1 = net.convs[c1.wslot];
-            fold = c1.acc_in && cw1.prefix2.empty() && pw_bwd_fused_supported(cw1.cout, cw1.cin);
-          }
-          if (fold) {
-            // g[sum] must still hold the gradient when that kernel runs: the conv that feeds the add reads it in place
-            // (g_alias above) before — fine for the fused 1x1 kernel, which leaves it alone, not for the unfused paths,
-            // whose bn_bwd_gz turns it into g_z IN PLACE (dense 3x3 bottlenecks of the non-depthwise encoders)
-            bool intact = false;
-            for (int j = 0; j < obi; ++j) {
-              const Op& o = net.ops[j];
-              if (o.wslot >= 0 && o.out.buf == op.in.buf && o.out.coff == op.in.coff && o.out.C == op.in.C) {
-                const ConvW& cwp = net.convs[o.wslot];
-                intact = o.kind == OP_PW && cwp.prefix2.empty() && pw_bwd_fused_supported(cwp.cout, cwp.cin);
-              }
-            }
-            fold = intact;
-          }
-          if (fold) { shortcut_grad[conv1] = op.out; shortcut_addact[conv1] = obi; }
-          else launch_grad_copy(gptr(op.out), ld(op.out), gptr(op.res), ld(op.res), op.out.C, M, op.acc_res ? 1 : 0, s, sb);
-        }
-        break;
-      }
-      case OP_SPP: {
-        const View full = net_full_view(net, op.out.buf);
-        launch_spp_bwd(ptr(full), net.act_dtype, gptr(full), ld(op.out), op.in.C, op.in.H, op.in.W, N, tab(op.in), s, sb);
-        break;
-      }
-      case OP_UPSAMPLE:
-        launch_upsample_bwd(gptr(op.out), ld(op.out), gptr(op.in), ld(op.in), op.in.C, op.in.H, op.in.W, N,
-                            op.acc_in ? 1 : 0, s, sb);
-        break;
-      default: break;
-    }
+    if (bwd_profile) (void)hipEventRecord(bev[obi], s);
   }
   if (aux_used) {
     JN_HIP(hipEventRecord(ctx->aux_join, ctx->aux_stream));
@@ -2310,6 +2099,71 @@ static int launch_gpt_bwd(jn_ctx* ctx, GptBwdArgs& ba, hipStream_t s) {
   return JN_OK;
 }
 
+// The GptBwdArgs fields that the REINFORCE and the supervised backward share: shapes, flags, weights and their
+// gradients, the dropout of the forward, the patch embeddings of the training pass and their gradient buffer.
+static void fill_gpt_bwd_common(jn_ctx* ctx, GptBwdArgs& ba) {
+  const jn_config& c = ctx->cfg;
+  const GptW& g = ctx->gpt;
+  ba.C = c.n_embd; ba.n_head = c.n_head; ba.n_layer = c.n_layer; ba.nA = c.n_actions;
+  ba.use_pos_emb = c.use_pos_emb; ba.no_patch_emb = c.no_patch_emb; ba.concat_emb = c.concat_emb;
+  ba.dec_pos_enc = c.decoder_pos_encoding; ba.pe2_ch = (int)std::ceil(c.n_embd / 4.0) * 2;
+  ba.n_done = ctx->n_done; ba.dlogits = ctx->dlogits; ba.tok_emb = ctx->tok_emb_train; ba.d_tok_emb = ctx->d_tok_emb;
+  ba.wte = g.wte; ba.wpe = g.wpe; ba.proj_wt = g.proj_wt; ba.pos1d = g.pos1d; ba.pe2 = g.pos2d_col; ba.head_wt = g.head_wt;
+  ba.lnf_w = g.lnf_w; ba.lnf_b = g.lnf_b; ba.layers = ctx->layers_dev; ba.g_layers = ctx->g_layers_dev;
+  ba.g_wte = grad_of(ctx, g.wte); ba.g_wpe = g.wpe ? grad_of(ctx, g.wpe) : nullptr;
+  ba.g_embed_class = grad_of(ctx, g.embed_class);
+  ba.g_proj_wt = g.proj_wt ? grad_of(ctx, g.proj_wt) : nullptr; ba.g_proj_b = g.proj_b ? grad_of(ctx, g.proj_b) : nullptr;
+  ba.g_head_wt = grad_of(ctx, g.head_wt); ba.g_lnf_w = grad_of(ctx, g.lnf_w); ba.g_lnf_b = grad_of(ctx, g.lnf_b);
+  ba.pdrop = ctx->pdrop; ba.drop_seed = ctx->drop_seed_used; ba.Tmax = c.block_size + 1;
+}
+
+// The patch-encoder side of a training backward over g_n workspace slots of `rows` patches from slot `slot` (gradient
+// slots 0 .. g_n - 1), given e (embed_fpn.0 activations) and dpe (d loss / d patch embedding) of those g_n * rows
+// patches: embed_fpn's backward, then the conv stack's.  In training only fpn[2] gets a gradient from outside the
+// encoder (embed_fpn): fpn[0] and fpn[1] are zeroed and the conv stack takes the routes of fpn_zero = 0x3.
+static int encoder_backward(jn_ctx* ctx, int g_n, int rows, int slot, const float* e, const float* dpe, const StemSrc& ss,
+                            long long pos_slot_stride, hipStream_t s) {
+  const int C = ctx->cfg.n_embd, MB = ctx->cfg.max_batch, HW = ctx->efpn_h * ctx->efpn_w, K = HW * C;
+  const GptW& g = ctx->gpt;
+  Net& net = ctx->nets[ctx->enc_net];
+  const View& f2 = net.fpn[2];
+  const ChanTab ident{ctx->ident, ctx->ident + 2048, ctx->ident + 4096};
+  const long long g_slot = (long long)net.per_image_floats * MB, Mr = (long long)g_n * rows;
+  // Linear backward as two GEMMs on the 1x1-conv kernels: de = dpe . W^T (then the ReLU mask), dW = e^T . dpe
+  ConvArgs la2{};
+  la2.in = dpe; la2.in_ld = C; la2.in_dtype = JN_F32; la2.itab = ident; la2.w = g.efpn_lin_wt; la2.bias = nullptr;
+  la2.out = ctx->de_ws; la2.out_ld = K; la2.out_dtype = JN_F32; la2.bf16_mfma = 0;
+  la2.N = (int)Mr; la2.H = 1; la2.W = 1; la2.OH = 1; la2.OW = 1; la2.cin = C; la2.cout = K; la2.stride = 1; la2.act = ACT_NONE;
+  launch_pw(la2, s);
+  launch_relu_mask(ctx->de_ws, e, Mr * K, s);
+  launch_pw_bwd_weight(e, K, dpe, JN_F32, C, ident, grad_of(ctx, g.efpn_lin_wt), nullptr, Mr, K, C, s);
+  launch_colsum_add(dpe, Mr, C, grad_of(ctx, g.efpn_lin_b), s);
+  // embed_fpn.0 (1x1 conv) backward into the f2 gradient view of every slot (fp32 operands: the training entry points
+  // refuse bf16 activations)
+  SlotBatch sb;
+  sb.n = g_n; sb.act = g_slot; sb.grad = g_slot; sb.tab = 3LL * net.tab_channels;
+  ConvArgs a{};
+  a.in = ctx->de_ws; a.in_ld = C; a.in_dtype = JN_F32; a.itab = ident; a.w = g.efpn_w; a.bias = nullptr;
+  a.out = net.gact + net.buf_off[f2.buf] * (size_t)MB + f2.coff; a.out_ld = net.bufs[f2.buf].C; a.out_dtype = JN_F32; a.bf16_mfma = 0;
+  a.N = rows; a.H = f2.H; a.W = f2.W; a.OH = f2.H; a.OW = f2.W; a.cin = C; a.cout = f2.C; a.stride = 1; a.act = ACT_NONE;
+  a.accumulate = 0; a.w_transposed = 1; a.in_identity = 1;
+  a.n_slots = g_n; a.in_slot_stride = (long long)rows * K; a.out_slot_stride = g_slot; a.tab_slot_stride = 0;
+  // the detector's PAFPN as patch encoder is detached (src/models/gpt.py:376-380 "Do not backpropagate through
+  // yolox"): the policy gradient stops at embed_fpn.0's weight
+  const bool detached = ctx->enc_net == JN_NET_DETECTOR;
+  if (!detached) launch_pw(a, s);
+  launch_pw_bwd_weight(ctx->de_ws, C, view_ptr(net, slot, MB, f2), net.act_dtype, net.bufs[f2.buf].C, view_tab(net, slot, f2),
+                       grad_of(ctx, g.efpn_w), ctx->wpart, (long long)rows * HW, C, f2.C, s, sb, (long long)rows * K);
+  if (detached) return JN_OK;
+  for (int i = 0; i < 2; ++i) {
+    const View& f = net.fpn[i];
+    for (int j = 0; j < g_n; ++j)
+      JN_HIP(hipMemsetAsync(net.gact + (size_t)j * g_slot + net.buf_off[f.buf] * (size_t)MB + f.coff, 0,
+                            (size_t)rows * f.H * f.W * f.C * sizeof(float), s));
+  }
+  return run_net_backward(ctx, ctx->enc_net, rows, ss, slot, s, g_n, pos_slot_stride, false, 0x3);
+}
+
 }  // extern "C"
 static int reinforce_backward_impl(jn_ctx* ctx, const jn_rollout_out* out, int S, int stop_early, hipStream_t s);
 static int check_train_outputs(jn_ctx* ctx, const jn_rollout_out* out) {
@@ -2384,80 +2238,27 @@ static int reinforce_backward_impl(jn_ctx* ctx, const jn_rollout_out* out, int S
   if ((rc = build_grad_layer_table(ctx))) return rc;
   const jn_config& c = ctx->cfg;
   const EnvState& e = ctx->env;
-  const int B = e.B, T = e.T, C = c.n_embd, nA = c.n_actions, P = c.patch_size;
-  const int nL = c.n_layer, nh = c.n_head;
-  const GptW& g = ctx->gpt;
+  const int B = e.B, T = e.T, C = c.n_embd, K = ctx->efpn_h * ctx->efpn_w * C;
   GptBwdArgs ba{};
-  ba.C = C; ba.n_head = nh; ba.n_layer = nL; ba.nA = nA; ba.B = B; ba.T = T; ba.stop_early = stop_early ? 1 : 0;
-  ba.use_pos_emb = c.use_pos_emb; ba.no_patch_emb = c.no_patch_emb; ba.concat_emb = c.concat_emb;
-  ba.dec_pos_enc = c.decoder_pos_encoding; ba.pe2_ch = (int)std::ceil(C / 4.0) * 2;
-  ba.n_done = ctx->n_done; ba.final_emb = out->final_emb_dev; ba.dlogits = ctx->dlogits; ba.actions = out->actions_dev;
+  fill_gpt_bwd_common(ctx, ba);
+  ba.B = B; ba.T = T; ba.stop_early = stop_early ? 1 : 0;
+  ba.final_emb = out->final_emb_dev; ba.actions = out->actions_dev;
   ba.positions = out->positions_dev; ba.pos_tokens = T + 1; ba.pos1d_by_token = 0; ba.tok_actions = nullptr;
-  ba.tok_emb = ctx->tok_emb_train; ba.d_tok_emb = ctx->d_tok_emb;
   ba.dte_stride_b = 1; ba.dte_stride_t = B;          // [T][B][C]: the rows of one glimpse step are contiguous
-  ba.wte = g.wte; ba.wpe = g.wpe; ba.proj_wt = g.proj_wt; ba.pos1d = g.pos1d; ba.pe2 = g.pos2d_col; ba.head_wt = g.head_wt;
-  ba.lnf_w = g.lnf_w; ba.lnf_b = g.lnf_b; ba.layers = ctx->layers_dev; ba.g_layers = ctx->g_layers_dev;
-  ba.g_wte = grad_of(ctx, g.wte); ba.g_wpe = g.wpe ? grad_of(ctx, g.wpe) : nullptr;
-  ba.g_embed_class = grad_of(ctx, g.embed_class);
-  ba.g_proj_wt = g.proj_wt ? grad_of(ctx, g.proj_wt) : nullptr; ba.g_proj_b = g.proj_b ? grad_of(ctx, g.proj_b) : nullptr;
-  ba.g_head_wt = grad_of(ctx, g.head_wt); ba.g_lnf_w = grad_of(ctx, g.lnf_w); ba.g_lnf_b = grad_of(ctx, g.lnf_b);
-  ba.pdrop = ctx->pdrop; ba.drop_seed = ctx->drop_seed_used; ba.Tmax = c.block_size + 1;
   if ((rc = launch_gpt_bwd(ctx, ba, s))) return rc;
 
   // patch-encoder side: all executed glimpse steps in ONE set of launches (chunks of net.g_slots steps
   // when the gradient buffers of a whole trajectory do not fit): embed_fpn backward, then the PAFPN.
-  Net& net = ctx->nets[ctx->enc_net];
-  const int MB = c.max_batch, HW = ctx->efpn_h * ctx->efpn_w, K = HW * C;
-  const View& f2 = net.fpn[2];
-  const ChanTab ident{ctx->ident, ctx->ident + 2048, ctx->ident + 4096};
-  const long long g_slot = (long long)net.per_image_floats * MB;
   if (ctx->profiling && ctx->ev[2]) JN_HIP(hipEventRecord(ctx->ev[2], s));     // conv-stack backward section (bench.py)
   // (a detached encoder needs no gradient slots: all steps in one chunk)
-  const int chunk = ctx->enc_net == JN_NET_DETECTOR ? std::max(S, 1) : net.g_slots;
+  const int chunk = ctx->enc_net == JN_NET_DETECTOR ? std::max(S, 1) : ctx->nets[ctx->enc_net].g_slots;
   for (int t0 = 0; t0 < S; t0 += chunk) {
-    const int g_n = std::min(chunk, S - t0);
-    const long long Mr = (long long)g_n * B;                       // (step, agent) rows of this chunk
-    const float* e_c = ctx->efpn_train + (size_t)t0 * B * K;       // [g_n*B][K] embed_fpn.0 activations
-    const float* dpe = ctx->d_tok_emb + (size_t)t0 * B * C;        // [g_n*B][C]  d loss / d patch embedding
-    // Linear backward as two GEMMs on the 1x1-conv kernels: de = dpe . W^T (then the ReLU mask), dW = e^T . dpe
-    ConvArgs la2{};
-    la2.in = dpe; la2.in_ld = C; la2.in_dtype = JN_F32; la2.itab = ident; la2.w = g.efpn_lin_wt; la2.bias = nullptr;
-    la2.out = ctx->de_ws; la2.out_ld = K; la2.out_dtype = JN_F32; la2.bf16_mfma = 0;
-    la2.N = (int)Mr; la2.H = 1; la2.W = 1; la2.OH = 1; la2.OW = 1; la2.cin = C; la2.cout = K; la2.stride = 1; la2.act = ACT_NONE;
-    launch_pw(la2, s);
-    launch_relu_mask(ctx->de_ws, e_c, Mr * K, s);
-    launch_pw_bwd_weight(e_c, K, dpe, JN_F32, C, ident, grad_of(ctx, g.efpn_lin_wt), nullptr, Mr, K, C, s);
-    launch_colsum_add(dpe, Mr, C, grad_of(ctx, g.efpn_lin_b), s);
-    // embed_fpn.0 (1x1 conv) backward into the f2 gradient view of every slot
-    SlotBatch sb;
-    sb.n = g_n; sb.act = g_slot; sb.grad = g_slot; sb.tab = 3LL * net.tab_channels;
-    float* g_f2 = net.gact + net.buf_off[f2.buf] * (size_t)MB + f2.coff;
-    ConvArgs a{};
-    a.in = ctx->de_ws; a.in_ld = C; a.in_dtype = JN_F32; a.itab = ident; a.w = g.efpn_w; a.bias = nullptr;
-    a.out = g_f2; a.out_ld = net.bufs[f2.buf].C; a.out_dtype = JN_F32; a.bf16_mfma = 0;
-    a.N = B; a.H = f2.H; a.W = f2.W; a.OH = f2.H; a.OW = f2.W; a.cin = C; a.cout = f2.C; a.stride = 1; a.act = ACT_NONE;
-    a.accumulate = 0; a.w_transposed = 1; a.in_identity = 1;
-    a.n_slots = g_n; a.in_slot_stride = (long long)B * K; a.out_slot_stride = g_slot; a.tab_slot_stride = 0;
-    // the detector's PAFPN as patch encoder is detached (src/models/gpt.py:376-380 "Do not backpropagate through
-    // yolox"): the policy gradient stops at embed_fpn.0's weight
-    const bool detached = ctx->enc_net == JN_NET_DETECTOR;
-    if (!detached) launch_pw(a, s);
-    launch_pw_bwd_weight(ctx->de_ws, C, view_ptr(net, t0 + 1, MB, f2), net.act_dtype, net.bufs[f2.buf].C, view_tab(net, t0 + 1, f2),
-                         grad_of(ctx, g.efpn_w), ctx->wpart, (long long)B * HW, C, f2.C, s, sb, (long long)B * K);
-    if (detached) continue;
-    for (int i = 0; i < 2; ++i) {
-      const View& f = net.fpn[i];
-      for (int j = 0; j < g_n; ++j)
-        JN_HIP(hipMemsetAsync(net.gact + (size_t)j * g_slot + net.buf_off[f.buf] * (size_t)MB + f.coff, 0,
-                              (size_t)B * f.H * f.W * f.C * sizeof(float), s));
-    }
     StemSrc ss = env_stem_src(e, out->positions_dev + 2 * t0);
     ss.pos_stride = 2 * (T + 1);
-    // (only fpn[2] carries a gradient from outside the encoder: embed_fpn; the other two FPN views were zeroed above)
-    if ((rc = run_net_backward(ctx, ctx->enc_net, B, ss, t0 + 1, s, g_n, 2, false, 0x3))) return rc;
+    if ((rc = encoder_backward(ctx, std::min(chunk, S - t0), B, t0 + 1, ctx->efpn_train + (size_t)t0 * B * K,
+                               ctx->d_tok_emb + (size_t)t0 * B * C, ss, 2, s))) return rc;
   }
   if (ctx->profiling && ctx->ev[3]) { JN_HIP(hipEventRecord(ctx->ev[3], s)); ctx->bwd_timed = true; }
-  (void)P;
   JN_HIP(hipGetLastError());
   return JN_OK;
 }
@@ -2535,61 +2336,19 @@ static int supervised_forward_impl(jn_ctx* ctx, const float* patches_dev, const 
 static int supervised_backward_impl(jn_ctx* ctx, hipStream_t s) {
   JN_CHECK(ctx->sup_valid, JN_ESTATE,
            "the activations of the supervised forward were overwritten (another pass used the encoder's workspace) or no forward ran");
-  const jn_config& c = ctx->cfg;
-  const int B = ctx->sup.B, T = ctx->sup.T;
-  const int64_t* current_actions_dev = ctx->sup.actions; const int64_t* positions_dev = ctx->sup.positions;
-  const int C = c.n_embd, nA = c.n_actions, P = c.patch_size, N = B * T;
-  const int HW = ctx->efpn_h * ctx->efpn_w, K = HW * C;
+  const int B = ctx->sup.B, T = ctx->sup.T, P = ctx->cfg.patch_size;
   int rc;
-  Net& net = ctx->nets[ctx->enc_net];
-  StemSrc ss{ctx->sup.patches, nullptr, 3LL * P * P, (long long)P * P, P};
-  const int nL = c.n_layer, nh = c.n_head;
-  const GptW& g = ctx->gpt;
   GptBwdArgs ba{};
-  ba.C = C; ba.n_head = nh; ba.n_layer = nL; ba.nA = nA; ba.B = B; ba.T = T; ba.stop_early = 0;
-  ba.use_pos_emb = c.use_pos_emb; ba.no_patch_emb = c.no_patch_emb; ba.concat_emb = c.concat_emb;
-  ba.dec_pos_enc = c.decoder_pos_encoding; ba.pe2_ch = (int)std::ceil(C / 4.0) * 2;
-  ba.n_done = ctx->n_done; ba.final_emb = ctx->sup_final_emb; ba.dlogits = ctx->dlogits; ba.actions = current_actions_dev;
-  ba.tok_actions = current_actions_dev; ba.positions = positions_dev; ba.pos_tokens = T; ba.pos1d_by_token = 1;
+  fill_gpt_bwd_common(ctx, ba);
+  ba.B = B; ba.T = T; ba.stop_early = 0;
+  ba.final_emb = ctx->sup_final_emb; ba.actions = ctx->sup.actions;
+  ba.tok_actions = ctx->sup.actions; ba.positions = ctx->sup.positions; ba.pos_tokens = T; ba.pos1d_by_token = 1;
   ba.classes = ctx->sup.classes;
-  ba.tok_emb = ctx->tok_emb_train; ba.d_tok_emb = ctx->d_tok_emb; ba.dte_stride_b = T; ba.dte_stride_t = 1;
-  ba.wte = g.wte; ba.wpe = g.wpe; ba.proj_wt = g.proj_wt; ba.pos1d = g.pos1d; ba.pe2 = g.pos2d_col; ba.head_wt = g.head_wt;
-  ba.lnf_w = g.lnf_w; ba.lnf_b = g.lnf_b; ba.layers = ctx->layers_dev; ba.g_layers = ctx->g_layers_dev;
-  ba.g_wte = grad_of(ctx, g.wte); ba.g_wpe = g.wpe ? grad_of(ctx, g.wpe) : nullptr;
-  ba.g_embed_class = grad_of(ctx, g.embed_class);
-  ba.g_proj_wt = g.proj_wt ? grad_of(ctx, g.proj_wt) : nullptr; ba.g_proj_b = g.proj_b ? grad_of(ctx, g.proj_b) : nullptr;
-  ba.g_head_wt = grad_of(ctx, g.head_wt); ba.g_lnf_w = grad_of(ctx, g.lnf_w); ba.g_lnf_b = grad_of(ctx, g.lnf_b);
-  ba.pdrop = ctx->pdrop; ba.drop_seed = ctx->drop_seed_used; ba.Tmax = c.block_size + 1;
+  ba.dte_stride_b = T; ba.dte_stride_t = 1;
   if ((rc = launch_gpt_bwd(ctx, ba, s))) return rc;
-  const int MB = c.max_batch;
-  const View& f2 = net.fpn[2];
-  const ChanTab ident{ctx->ident, ctx->ident + 2048, ctx->ident + 4096};
-  {   // Linear backward as two GEMMs (see jn_reinforce_step)
-    ConvArgs la2{};
-    la2.in = ctx->d_tok_emb; la2.in_ld = C; la2.in_dtype = JN_F32; la2.itab = ident; la2.w = g.efpn_lin_wt; la2.bias = nullptr;
-    la2.out = ctx->de_ws; la2.out_ld = K; la2.out_dtype = JN_F32; la2.bf16_mfma = 0;
-    la2.N = N; la2.H = 1; la2.W = 1; la2.OH = 1; la2.OW = 1; la2.cin = C; la2.cout = K; la2.stride = 1; la2.act = ACT_NONE;
-    launch_pw(la2, s);
-    launch_relu_mask(ctx->de_ws, ctx->efpn_train, (long long)N * K, s);
-    launch_pw_bwd_weight(ctx->efpn_train, K, ctx->d_tok_emb, JN_F32, C, ident, grad_of(ctx, g.efpn_lin_wt), nullptr, N, K, C, s);
-    launch_colsum_add(ctx->d_tok_emb, N, C, grad_of(ctx, g.efpn_lin_b), s);
-  }
-  float* g_f2 = net.gact + net.buf_off[f2.buf] * (size_t)MB + f2.coff;
-  ConvArgs ca{};
-  ca.in = ctx->de_ws; ca.in_ld = C; ca.in_dtype = JN_F32; ca.itab = ident; ca.w = g.efpn_w; ca.bias = nullptr;
-  ca.out = g_f2; ca.out_ld = net.bufs[f2.buf].C; ca.out_dtype = JN_F32; ca.bf16_mfma = net.act_dtype == JN_BF16;
-  ca.N = N; ca.H = f2.H; ca.W = f2.W; ca.OH = f2.H; ca.OW = f2.W; ca.cin = C; ca.cout = f2.C; ca.stride = 1; ca.act = ACT_NONE;
-  ca.accumulate = 0; ca.w_transposed = 1; ca.in_identity = 1;
-  const bool detached = ctx->enc_net == JN_NET_DETECTOR;        // src/models/gpt.py:376-380, see jn_reinforce_step
-  if (!detached) launch_pw(ca, s);
-  launch_pw_bwd_weight(ctx->de_ws, C, view_ptr(net, 0, MB, f2), net.act_dtype, net.bufs[f2.buf].C, view_tab(net, 0, f2),
-                       grad_of(ctx, g.efpn_w), ctx->wpart, (long long)N * HW, C, f2.C, s);
-  if (detached) { JN_HIP(hipGetLastError()); return JN_OK; }
-  for (int i = 0; i < 2; ++i) {
-    const View& f = net.fpn[i];
-    JN_HIP(hipMemsetAsync(net.gact + net.buf_off[f.buf] * (size_t)MB + f.coff, 0, (size_t)N * f.H * f.W * f.C * sizeof(float), s));
-  }
-  if ((rc = run_net_backward(ctx, ctx->enc_net, N, ss, 0, s, 1, 0, false, 0x3))) return rc;
+  // the encoder's B*T patches as one slot
+  const StemSrc ss{ctx->sup.patches, nullptr, 3LL * P * P, (long long)P * P, P};
+  if ((rc = encoder_backward(ctx, 1, B * T, 0, ctx->efpn_train, ctx->d_tok_emb, ss, 0, s))) return rc;
   JN_HIP(hipGetLastError());
   return JN_OK;
 }

@@ -130,6 +130,28 @@ struct Net {
   std::vector<int> h_td_src, h_td_goff, h_td_boff;
 };
 
+// ---- backward plan (plan.cpp: plan_backward): the route of every op of the conv-stack backward --------------
+enum BwdRoute {
+  BR_NONE = 0,
+  BR_PW_FUSED, BR_PW_FUSED_HALVES,        // pw_bwd_fused_kernel over the whole 1x1 conv / the two halves of a merged pair
+  BR_DW_FUSED, BR_STEM_FUSED,             // dw_bwd_fused_kernel, the stem's weight gradient with bn_bwd_gz inside
+  BR_PW, BR_DW, BR_STEM, BR_CONV3_S1, BR_CONV3_S2,   // bn_bwd_gz, then separate data / weight gradients
+  BR_ADDACT_COPY, BR_ADDACT_FOLD,         // shortcut add: g[res] (+)= g[sum] by a copy / inside the fold conv's kernel
+  BR_SPP, BR_UPSAMPLE,
+};
+struct BwdStep {           // op indices only: the launcher turns them into pointers
+  BwdRoute route = BR_NONE;
+  View g;                  // conv: the gradient view it reads (a shortcut sum's, in place, when the conv feeds the add)
+  int red_by = 0;          // BN conv: bit h = a consumer forms the sums of half h of a merged pair (bit 0: of the conv)
+  // fused consumer: its epilogue forms the BN sums of input channels [0, red_split or cin) for op red_in and of the
+  // rest for op red_in2 (-1: none); half -1 = the whole conv, 0 / 1 = a half of a merged pair.  red2: the run of red_in
+  // is a shortcut sum and red_in the conv behind it (whose z and table replace the input's)
+  int red_in = -1, red_half = -1, red_in2 = -1, red_half2 = -1, red_split = 0;
+  bool red2 = false;
+  int fold = -1;           // 1x1 conv: the shortcut add whose copy of g[sum] into g[in] its kernel absorbs
+};
+int plan_backward(const Net& net, bool with_head, int fpn_zero, std::vector<BwdStep>& plan);
+
 struct ParamEntry {
   jn_param_info info;
 };

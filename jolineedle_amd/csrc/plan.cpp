@@ -321,4 +321,189 @@ int build_head(Net& net, std::vector<ParamEntry>& params, const std::string& pre
   return JN_OK;
 }
 
+// ---- backward plan ---------------------------------------------------------------------------------------------------
+namespace {
+
+bool views_overlap(const View& a, const View& b) {
+  return a.buf >= 0 && a.buf == b.buf && a.coff < b.coff + b.C && b.coff < a.coff + a.C;
+}
+
+// The one op that writes segment `seg` (as output or upsampled alias), provided it comes before op `before` and every
+// op that reads the segment passes may_read(op, as_residual); -1 otherwise, and also when an SPP works on the buffer
+// (it reads and writes the whole concat) or when seg is an FPN output that gets a gradient from outside the network
+// (fpn_zero bit clear).  All ops are scanned, the head's too when it is not differentiated: a view it reads is not a
+// single-consumer output.
+template <class MayRead>
+int sole_writer(const Net& net, const View& seg, int before, int fpn_zero, MayRead may_read) {
+  for (int i = 0; i < 3; ++i)
+    if (!((fpn_zero >> i) & 1) && views_overlap(seg, net.fpn[i])) return -1;
+  int w = -1;
+  for (int j = 0; j < (int)net.ops.size(); ++j) {
+    const Op& o = net.ops[j];
+    if ((views_overlap(o.in, seg) && !may_read(j, false)) || (views_overlap(o.res, seg) && !may_read(j, true))) return -1;
+    if (o.kind == OP_SPP && o.out.buf == seg.buf) return -1;
+    if (views_overlap(o.out, seg) || views_overlap(o.alias, seg)) {
+      if (w >= 0 || j >= before) return -1;
+      w = j;
+    }
+  }
+  return w;
+}
+
+// The conv whose whole output is the `in` operand of shortcut add `add`, read by that add alone; -1 otherwise.
+int shortcut_conv(const Net& net, int add, int fpn_zero) {
+  const View& z = net.ops[add].in;
+  const int w = sole_writer(net, z, add, fpn_zero, [&](int j, bool res) { return j == add && !res; });
+  if (w < 0) return -1;
+  const Op& o = net.ops[w];
+  return o.wslot >= 0 && o.out.buf == z.buf && o.out.coff == z.coff && o.out.C == z.C ? w : -1;
+}
+
+// The BatchNorm conv that alone writes segment `seg` of op `reader`'s input: its whole output (*half = -1) or one half
+// of a merged conv2|conv1 pair (*half = 0: conv2 rows, 1: conv1 rows), read by nothing but the reader and, as residual,
+// `also` (the shortcut add whose copy the reader's kernel absorbs).  The reader then holds the FINAL gradient of the
+// segment and can form that layer's BN-backward sums in its epilogue.  -1 otherwise.
+int bn_producer(const Net& net, const View& seg, int reader, int also, int fpn_zero, int* half) {
+  *half = -1;
+  const int p = sole_writer(net, seg, reader, fpn_zero, [&](int j, bool res) { return j == reader || (res && j == also); });
+  if (p < 0) return -1;
+  const Op& po = net.ops[p];
+  if (po.wslot < 0 || po.out.buf != seg.buf || views_overlap(po.alias, seg)) return -1;
+  const ConvW& pw = net.convs[po.wslot];
+  if (!pw.has_bn) return -1;
+  if (pw.prefix2.empty()) return po.out.coff == seg.coff && po.out.C == seg.C && pw.cout == seg.C ? p : -1;
+  if (pw.cout != 2 * seg.C || 2 * pw.cout_first != pw.cout || po.out.C != 2 * seg.C) return -1;
+  *half = seg.coff == po.out.coff ? 0 : seg.coff == po.out.coff + seg.C ? 1 : -1;
+  return *half >= 0 ? p : -1;
+}
+
+// RED2: segment `seg` of op `reader`'s input is a materialised shortcut sum (an OP_ADDACT's whole output) read by
+// nothing but the reader and, as residual, `also`: the reader writes the FINAL gradient of the sum, which is also the
+// gradient of the activation of the add's `in` operand.  Returns the conv behind that operand — the bottleneck's last
+// 1x1 conv, BatchNorm, a single conv — or -1.
+int shortcut_sum_conv(const Net& net, const View& seg, int reader, int also, int fpn_zero) {
+  const int add = sole_writer(net, seg, reader, fpn_zero, [&](int j, bool res) { return j == reader || (res && j == also); });
+  if (add < 0 || net.ops[add].kind != OP_ADDACT) return -1;
+  const Op& ao = net.ops[add];
+  if (ao.out.coff != seg.coff || ao.out.C != seg.C || ao.in.C != seg.C) return -1;
+  const int conv = shortcut_conv(net, add, fpn_zero);
+  if (conv < 0) return -1;
+  const Op& co = net.ops[conv];
+  const ConvW& cw = net.convs[co.wslot];
+  return co.kind == OP_PW && !views_overlap(co.alias, ao.in) && cw.has_bn && cw.prefix2.empty() && cw.cout == seg.C ? conv : -1;
+}
+
+}  // namespace
+
+// The backward of `net` as a pure function of its topology, activation dtype, the head (with_head) and the FPN outputs
+// that get no outside gradient (fpn_zero bit i: none arrives in fpn[i], the training backward's case): one record per
+// op of the backward range, filled walking it in reverse like the launcher (run_net_backward, api.hip).
+int plan_backward(const Net& net, bool with_head, int fpn_zero, std::vector<BwdStep>& plan) {
+  const int n = (with_head || net.n_backbone_ops < 0) ? (int)net.ops.size() : net.n_backbone_ops;
+  const bool f32 = net.act_dtype == JN_F32;
+  plan.assign(n, BwdStep{});
+  auto fused_whole = [&](int j) {       // a 1x1 conv that takes pw_bwd_fused_kernel in one piece
+    const Op& o = net.ops[j];
+    const ConvW& cw = net.convs[o.wslot];
+    return o.kind == OP_PW && f32 && cw.prefix2.empty() && pw_bwd_fused_supported(cw.cout, cw.cin);
+  };
+  for (int i = n - 1; i >= 0; --i) {
+    const Op& op = net.ops[i];
+    BwdStep& st = plan[i];
+    if (op.wslot >= 0) {
+      const ConvW& cw = net.convs[op.wslot];
+      JN_CHECK(cw.has_bn, JN_ESTATE, "backward of BN-free conv %s inside a PAFPN", op.name.c_str());
+      if (st.g.buf < 0) st.g = op.out;
+      // a merged pair too wide for the fused kernel is differentiated as its two halves (independent output rows)
+      const bool whole = pw_bwd_fused_supported(cw.cout, cw.cin);
+      const bool halves = !whole && !cw.prefix2.empty() && 2 * cw.cout_first == cw.cout && pw_bwd_fused_supported(cw.cout_first, cw.cin);
+      if (op.kind == OP_PW && f32 && (whole || halves)) {
+        st.route = whole ? BR_PW_FUSED : BR_PW_FUSED_HALVES;
+        // BN-backward sums of the input's producer(s) in the kernel's epilogue: it must write the FINAL gradient of the
+        // view (sole reader, or the shortcut folded in) — one run, or the two halves of a CSP conv3's input
+        if (!whole || (op.acc_in && st.fold < 0) || !pw_bwd_fused_reduces_input(cw.cout, cw.cin)) continue;
+        auto seg = [&](int c0, int C) { View v = op.in; v.coff += c0; v.C = C; return v; };
+        int r2 = -1;
+        st.red_in = bn_producer(net, op.in, i, st.fold, fpn_zero, &st.red_half);
+        if (st.red_in < 0 && (r2 = shortcut_sum_conv(net, op.in, i, st.fold, fpn_zero)) >= 0) {
+          st.red_in = r2; st.red2 = true; st.red_split = op.in.C;
+        } else if (st.red_in < 0 && op.in.C % 32 == 0 && st.fold < 0) {
+          const int hC = op.in.C / 2;
+          st.red_in = bn_producer(net, seg(0, hC), i, -1, fpn_zero, &st.red_half);
+          st.red_in2 = bn_producer(net, seg(hC, hC), i, -1, fpn_zero, &st.red_half2);
+          if (st.red_in < 0 && (r2 = shortcut_sum_conv(net, seg(0, hC), i, -1, fpn_zero)) >= 0) {
+            st.red_in = r2; st.red2 = true;       // [shortcut sum | conv2 half]: the input of a CSP's conv3
+          }
+          if (st.red_in >= 0 || st.red_in2 >= 0) st.red_split = hC;   // (a lone second run still needs the split)
+        }
+      } else if (op.kind == OP_DW && f32 && dw_bwd_fused_supported(cw.cout, op.in.H, op.in.W, op.out.H, op.out.W, op.stride)) {
+        st.route = BR_DW_FUSED;
+        // A view that only the network's outside could also write (an FPN output) and that gets no outside gradient in
+        // this backward (fpn_zero) is an ordinary single-consumer output: the kernel then WRITES its gradient (the
+        // buffer holds zeros) and forms the producer's sums like for any other.
+        bool ext_zero = false;
+        for (int k = 0; k < 3; ++k) ext_zero = ext_zero || (((fpn_zero >> k) & 1) && views_overlap(op.in, net.fpn[k]));
+        if (!op.acc_in || ext_zero) st.red_in = bn_producer(net, op.in, i, -1, fpn_zero, &st.red_half);
+      } else if (op.kind == OP_STEM) {
+        st.route = f32 ? BR_STEM_FUSED : BR_STEM;
+      } else if (op.kind == OP_PW) {
+        st.route = BR_PW;
+      } else if (op.kind == OP_DW) {
+        st.route = BR_DW;
+      } else {
+        JN_CHECK(op.kind == OP_CONV3, JN_ESTATE, "backward of op %s is not implemented", op.name.c_str());
+        st.route = op.stride == 1 ? BR_CONV3_S1 : BR_CONV3_S2;
+      }
+      continue;
+    }
+    if (op.kind == OP_ADDACT) {
+      // the gradient of the conv that feeds the add IS the gradient of the sum: as the sum's sole consumer it reads it
+      // in place (no copy)
+      const int z = shortcut_conv(net, i, fpn_zero);
+      JN_CHECK(op.acc_in || z >= 0, JN_ESTATE, "backward plan: shortcut %s has no single conv behind its input", op.name.c_str());
+      if (!op.acc_in) plan[z].g = op.out;
+      // The shortcut branch, g[res] += g[sum]: when the only other reader of `res` is the bottleneck's first 1x1 conv
+      // and that layer takes the fused kernel, the kernel adds g[sum] while it writes its data gradient (one read of
+      // g[sum] instead of a copy pass over the largest 16 / 32-channel maps).  g[sum] must still hold the gradient
+      // then: fine when the conv that feeds the add is a fused 1x1 too, not for the unfused paths, whose bn_bwd_gz
+      // turns it into g_z IN PLACE (dense 3x3 bottlenecks of the non-depthwise encoders).
+      int conv1 = -1;
+      const bool one_reader = sole_writer(net, op.res, i, fpn_zero, [&](int j, bool res) {
+        if (j == i) return res;
+        const Op& o = net.ops[j];
+        if (conv1 >= 0 || res || j > i || o.kind != OP_PW || o.in.buf != op.res.buf || o.in.coff != op.res.coff || o.in.C != op.res.C)
+          return false;
+        conv1 = j;
+        return true;
+      }) >= 0;
+      const bool fold = f32 && !op.acc_res && one_reader && conv1 >= 0 && net.ops[conv1].acc_in && fused_whole(conv1) &&
+                        z >= 0 && fused_whole(z);
+      if (fold) plan[conv1].fold = i;
+      st.route = fold ? BR_ADDACT_FOLD : BR_ADDACT_COPY;
+    } else if (op.kind == OP_SPP) {
+      st.route = BR_SPP;
+    } else if (op.kind == OP_UPSAMPLE) {
+      st.route = BR_UPSAMPLE;
+    }
+  }
+  // every BN conv gets its sums formed exactly once: by one consumer that runs before it in the backward (per half for
+  // merged pairs), else by its own reduce; every folded shortcut goes to a whole-route fused 1x1 conv
+  for (int c = n - 1; c >= 0; --c) {
+    const BwdStep& st = plan[c];
+    const int runs[2][2] = {{st.red_in, st.red_half}, {st.red_in2, st.red_half2}};
+    for (const auto& r : runs) {
+      if (r[0] < 0) continue;
+      const Op& po = net.ops[r[0]];
+      const int bit = r[1] < 0 ? 1 : 1 << r[1];
+      JN_CHECK((st.route == BR_PW_FUSED || st.route == BR_DW_FUSED) && r[0] < c && po.wslot >= 0 &&
+               (r[1] >= 0) == !net.convs[po.wslot].prefix2.empty() && !(plan[r[0]].red_by & bit),
+               JN_ESTATE, "backward plan: %s cannot form the BatchNorm sums of %s", net.ops[c].name.c_str(), po.name.c_str());
+      plan[r[0]].red_by |= bit;
+    }
+    JN_CHECK(st.fold < 0 || st.route == BR_PW_FUSED, JN_ESTATE, "backward plan: shortcut %s folded into %s, not a fused 1x1 conv",
+             st.fold < 0 ? "" : net.ops[st.fold].name.c_str(), net.ops[c].name.c_str());
+  }
+  return JN_OK;
+}
+
 }  // namespace jnr
