@@ -170,6 +170,36 @@ int jn_gather_patches_indexed_u8(const uint8_t* images_dev, const int64_t* image
                                  const int64_t* positions_dev, float* out_dev, int N, int n_images,
                                  int C, int H, int W, int P, void* stream);
 
+/* ---- image views: NeedleDataset.rotate / translate and padded_collate_fn, applied in the read ------------------
+ * (src/dataset.py:95-226 rotate / translate, :274-278 their order, :308-347 bottom / right padding to one canvas.)
+ * A view describes one stored image [3,Hs,Ws] (contiguous, f32 or u8) as an image on the batch's logical canvas
+ * Hc x Wc: with (Hr,Wr) = (Hs,Ws) for rot 0 / 180 and (Ws,Hs) for rot 90 / 270, canvas pixel (c,Y,X) is
+ *   0 when Y >= Hr or X >= Wr (padding); else with (y1,x1) = (Y - ty, X - tx): 0 outside [0,Hr) x [0,Wr) (the
+ *   whole-pixel shift's zero fill); else rot 0: src[y1,x1]; 90: src[Hs-1-x1,y1]; 180: src[Hs-1-y1,Ws-1-x1];
+ *   270: src[x1,Ws-1-y1] (the transpose / flip pairs of rotate); a byte b stands for b / 255 correctly rounded.
+ * The augmented image is never written: the kernels that cut patches apply the mapping. */
+typedef struct jn_image_view {
+  const void* src;     /* device address of the stored image; stays the caller's */
+  int32_t src_u8;      /* 0: f32 values, 1: u8 bytes */
+  int32_t Hs, Ws;      /* stored height and width */
+  int32_t rot;         /* 0, 90, 180 or 270 */
+  int32_t ty, tx;      /* translation in pixels, down / right positive (bbox + translate, :212-226) */
+} jn_image_view;
+/* jn_env_init over B views on one canvas Hc x Wc (multiples of patch_size): views_host[B] is read from HOST
+ * memory, validated (JN_EINVAL: rot outside the four values, a rotated image larger than the canvas, a canvas that
+ * is no multiple of patch_size, a null source, mixed element types) and copied to the device; the context owns the
+ * copy, the stored images must outlive the env.  bboxes [B,nb,4] are the boxes already transformed to the canvas.
+ * Every glimpse step then gathers its B patches through the views into a staging stack the context owns (element
+ * type of the sources) and the encoders read that.  jn_env_init / jn_env_init_u8 put the env back into plain mode. */
+int jn_env_init_views(jn_ctx* ctx, const jn_image_view* views_host, const int64_t* bboxes_dev, int B, int Hc, int Wc,
+                      int nb, int max_ep_len, int stop_enabled, void* stream);
+/* Context-free indexed gather through a DEVICE table of n_views views (all of one element type, already valid):
+ * out[n] = canvas[image_index[n]][:, y*P:(y+1)*P, x*P:(x+1)*P], image_index[n] < 0 = zero patch.  out_u8 = 0:
+ * out is f32 (bytes as b / 255); out_u8 = 1: u8 sources only, out is the transformed byte copy. */
+int jn_gather_patches_views(const jn_image_view* views_dev, int n_views, const int64_t* image_index_dev,
+                            const int64_t* positions_dev, void* out_dev, int out_u8, int N, int Hc, int Wc, int P,
+                            void* stream);
+
 /* ---- detection augmentation ------------------------------------- */
 /* Trainer.init_detection's on-device chain (src/trainer.py:176-186, applied at src/reinforce.py:332-333 and
  * src/supervised.py:855-861, 884-885) fused into one pass: RandomPlanckianJitter (per-patch red / blue gains,

@@ -57,6 +57,11 @@ class JnRolloutOut(C.Structure):
         "det_counts_dev")]
 
 
+class JnImageView(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("src_u8", C.c_int32), ("Hs", C.c_int32), ("Ws", C.c_int32), ("rot", C.c_int32),
+                ("ty", C.c_int32), ("tx", C.c_int32)]
+
+
 ABI_VERSION = 2      # JN_ABI_VERSION of include/jnroll.h
 
 # name -> (restype, argtypes); every symbol include/jnroll.h declares
@@ -85,6 +90,10 @@ SIGNATURES = {
                                             C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "jn_gather_patches_indexed_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "jn_env_init_views": (C.c_int, [C.c_void_p, C.POINTER(JnImageView), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_void_p]),
+    "jn_gather_patches_views": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_void_p]),
     "jn_backbone_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
     "jn_read_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t]),

@@ -117,6 +117,9 @@ def args_to_config(args):
     """-> (train_config, model_config), field names of main.py:310-388."""
     t = CfgNode()
     t.training_mode = args.training_mode
+    t.rotations, t.translations = args.augment_rotate, args.augment_translate      # main.py:314-315
+    t.min_keypoints, t.max_keypoints = args.min_keypoints, args.max_keypoints      # main.py:335-339
+    t.binomial_keypoints, t.loss_mode = args.binomial_keypoints, args.loss
     t.learning_rate, t.yolo_lr, t.weight_decay = args.lr, args.yolo_lr, args.weight_decay
     t.max_iters, t.batch_size = args.max_iters, args.batch_size
     t.detection_enabled = args.detection_enabled

@@ -408,6 +408,7 @@ int jn_destroy(jn_ctx* ctx) {
   (void)hipSetDevice(ctx->cfg.device);
   (void)hipDeviceSynchronize();
   for (void* p : ctx->owned) (void)hipFree(p);
+  if (ctx->env.stage) (void)hipFree(ctx->env.stage);
   for (auto& e : ctx->ev) if (e) (void)hipEventDestroy(e);
   for (auto& e : ctx->conv_ev) (void)hipEventDestroy(e);
   if (ctx->aux_fork) (void)hipEventDestroy(ctx->aux_fork);
@@ -1698,7 +1699,9 @@ static EnvPtrs env_ptrs(jn_ctx* ctx) {
 // the env's images are read in place by the gathers and the stems; images_u8 selects the byte instantiations
 static void env_gather(const EnvState& e, float* out, long long out_sample_stride, int P, const int* skip_flag, int skip_when,
                        hipStream_t s) {
-  if (e.images_u8)
+  if (e.view_mode)
+    launch_view_gather(e.views, e.images_u8, nullptr, e.positions, out, 0, out_sample_stride, e.B, P, skip_flag, skip_when, s);
+  else if (e.images_u8)
     launch_gather((const uint8_t*)e.images, e.positions, out, out_sample_stride, e.B, 3, e.H, e.W, P, skip_flag, skip_when, s);
   else
     launch_gather((const float*)e.images, e.positions, out, out_sample_stride, e.B, 3, e.H, e.W, P, skip_flag, skip_when, s);
@@ -1710,8 +1713,41 @@ static StemSrc env_stem_src(const EnvState& e, const int64_t* positions) {
   return ss;
 }
 
+// ---- view mode: the staging stack [cols][B][3][P][P] (element type of the sources) ----
+static size_t stage_col_bytes(const EnvState& e, int P) { return (size_t)e.B * 3 * P * P * (e.images_u8 ? 1 : sizeof(float)); }
+// cols = 1: every step overwrites the one column (stream order keeps its reader ahead of the next writer);
+// cols = T + 1: column t holds the patches at positions[:, t] until the next rollout (the training backward and the
+// detector's second stream read them later).  Sized for this env, not for max_batch: it is the one large view-mode buffer.
+static int ensure_stage(jn_ctx* ctx, int cols) {
+  EnvState& e = ctx->env;
+  // (whole 2 MiB granules, which is what the driver hands out for a buffer of this size anyway: the tail of the last
+  // granule is then not shared with the context's small allocations, whose packing stays what it is in plain mode)
+  const size_t granule = (size_t)2 << 20;
+  const size_t need = ((size_t)cols * stage_col_bytes(e, ctx->cfg.patch_size) + granule - 1) / granule * granule;
+  e.stage_cols = cols;
+  if (e.stage && e.stage_bytes >= need) return JN_OK;
+  if (e.stage) { JN_HIP(hipDeviceSynchronize()); JN_HIP(hipFree(e.stage)); e.stage = nullptr; e.stage_bytes = 0; }
+  hipError_t er = hipMalloc(&e.stage, need);
+  if (er != hipSuccess) { e.stage = nullptr; set_error("hipMalloc(%zu bytes) for the view staging stack failed: %s", need, hipGetErrorString(er)); return JN_ENOMEM; }
+  e.stage_bytes = need;
+  return JN_OK;
+}
+static void* stage_col(const EnvState& e, int P, int t) {
+  return (char*)e.stage + (e.stage_cols == 1 ? 0 : (size_t)t) * stage_col_bytes(e, P);
+}
+static void stage_fill(const EnvState& e, int P, int t, const int* skip_flag, int skip_when, hipStream_t s) {
+  launch_view_gather(e.views, e.images_u8, nullptr, e.positions, stage_col(e, P, t), e.images_u8, 3LL * P * P, e.B, P, skip_flag,
+                     skip_when, s);
+}
+// column t as the plain patch stack the supervised step already feeds the stems (positions = NULL)
+static StemSrc stage_stem_src(const EnvState& e, int P, int t) {
+  StemSrc ss{stage_col(e, P, t), nullptr, 3LL * P * P, (long long)P * P, P};
+  ss.src_u8 = e.images_u8;
+  return ss;
+}
+
 static int env_init_impl(jn_ctx* ctx, const void* images_dev, int images_u8, const int64_t* bboxes_dev, int B, int H, int W,
-                         int nb, int max_ep_len, int stop_enabled, void* stream) {
+                         int nb, int max_ep_len, int stop_enabled, void* stream, const jn_image_view* views_host = nullptr) {
   const int P = ctx->cfg.patch_size;
   JN_CHECK(B >= 1 && B <= ctx->cfg.max_batch, JN_EINVAL, "B=%d exceeds max_batch=%d", B, ctx->cfg.max_batch);
   // general_env.py:50-51
@@ -1732,11 +1768,29 @@ static int env_init_impl(jn_ctx* ctx, const void* images_dev, int images_u8, con
     if ((rc = dev_alloc(ctx, &e.has_stopped, (size_t)MB))) return rc;
     if ((rc = dev_alloc(ctx, &e.n_bbox_tiles, (size_t)MB))) return rc;
     if ((rc = dev_alloc(ctx, &ctx->found, (size_t)MB))) return rc;
+    // the two small tables of view mode come with the env state (24 KB at the headline sizes), so that switching to
+    // views later allocates nothing but the staging stack
+    if ((rc = dev_alloc(ctx, &e.views, (size_t)MB))) return rc;
+    if ((rc = dev_alloc(ctx, &e.stage_pos, (size_t)(ctx->cfg.block_size + 1) * MB * 2))) return rc;
   }
+  hipStream_t s = (hipStream_t)stream;
+  if (views_host) {
+    // the previous table may still be read by work in flight; the new one is in place before anything launched below
+    JN_HIP(hipStreamSynchronize(s));
+    JN_HIP(hipMemcpy(e.views, views_host, (size_t)B * sizeof(jn_image_view), hipMemcpyHostToDevice));
+    if (e.stage_pos_B != B) {
+      std::vector<int64_t> sp((size_t)(ctx->cfg.block_size + 1) * B * 2, 0);
+      for (int t = 0; t <= ctx->cfg.block_size; ++t)
+        for (int b = 0; b < B; ++b) sp[((size_t)t * B + b) * 2] = 3LL * B * t;
+      JN_HIP(hipMemcpy(e.stage_pos, sp.data(), sp.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+      e.stage_pos_B = B;
+    }
+    ctx->train_out_valid = false;     // the staged patches of an earlier rollout belong to the earlier views
+  }
+  e.view_mode = views_host != nullptr;
   e.images = images_dev; e.images_u8 = images_u8;
   e.B = B; e.H = H; e.W = W; e.nb = nb; e.Gh = Gh; e.Gw = Gw; e.T = max_ep_len;
   e.stop = stop_enabled ? 1 : 0;
-  hipStream_t s = (hipStream_t)stream;
   launch_bbox_masks(bboxes_dev, e.bbox_masks, e.n_bbox_tiles, B, nb, H, W, P, s);
   launch_env_reset(env_ptrs(ctx), nullptr, 0, s);   // zeroed state at (0,0)-independent start; reset() follows
   JN_HIP(hipGetLastError());
@@ -1754,6 +1808,26 @@ int jn_env_init_u8(jn_ctx* ctx, const uint8_t* images_dev, const int64_t* bboxes
                    int max_ep_len, int stop_enabled, void* stream) {
   JN_CHECK(ctx && images_dev && (bboxes_dev || nb == 0), JN_EINVAL, "jn_env_init_u8: null argument");
   return env_init_impl(ctx, images_dev, 1, bboxes_dev, B, H, W, nb, max_ep_len, stop_enabled, stream);
+}
+
+int jn_env_init_views(jn_ctx* ctx, const jn_image_view* views_host, const int64_t* bboxes_dev, int B, int Hc, int Wc, int nb,
+                      int max_ep_len, int stop_enabled, void* stream) {
+  JN_CHECK(ctx && views_host && (bboxes_dev || nb == 0), JN_EINVAL, "jn_env_init_views: null argument");
+  JN_CHECK(B >= 1 && B <= ctx->cfg.max_batch, JN_EINVAL, "B=%d exceeds max_batch=%d", B, ctx->cfg.max_batch);
+  const int P = ctx->cfg.patch_size;
+  JN_CHECK(Hc >= P && Wc >= P && Hc % P == 0 && Wc % P == 0, JN_EINVAL, "canvas %dx%d is not a multiple of patch_size %d", Hc, Wc, P);
+  for (int b = 0; b < B; ++b) {
+    const jn_image_view& v = views_host[b];
+    JN_CHECK(v.src, JN_EINVAL, "view %d: null source", b);
+    JN_CHECK(v.rot == 0 || v.rot == 90 || v.rot == 180 || v.rot == 270, JN_EINVAL, "view %d: rot %d is not 0, 90, 180 or 270", b, v.rot);
+    JN_CHECK(v.Hs >= 1 && v.Ws >= 1, JN_EINVAL, "view %d: stored size %dx%d", b, v.Hs, v.Ws);
+    const bool turned = v.rot == 90 || v.rot == 270;
+    JN_CHECK((turned ? v.Ws : v.Hs) <= Hc && (turned ? v.Hs : v.Ws) <= Wc, JN_EINVAL,
+             "view %d: the rotated image %dx%d does not fit the canvas %dx%d", b, turned ? v.Ws : v.Hs, turned ? v.Hs : v.Ws, Hc, Wc);
+    JN_CHECK((v.src_u8 == 0 || v.src_u8 == 1) && v.src_u8 == views_host[0].src_u8, JN_EINVAL,
+             "view %d: mixed element types within one env", b);
+  }
+  return env_init_impl(ctx, nullptr, views_host[0].src_u8, bboxes_dev, B, Hc, Wc, nb, max_ep_len, stop_enabled, stream, views_host);
 }
 
 int jn_env_reset(jn_ctx* ctx, const int64_t* positions_dev, uint64_t seed, void* stream) {
@@ -1843,9 +1917,33 @@ int jn_gather_patches_indexed_u8(const uint8_t* images_dev, const int64_t* image
   return JN_OK;
 }
 
+// (the table was validated by whoever uploaded it; its element type selects the kernel, so the first entry is read back:
+// one small copy and a stream sync per call, on a path that assembles samples and is not the rollout's)
+int jn_gather_patches_views(const jn_image_view* views_dev, int n_views, const int64_t* image_index_dev,
+                            const int64_t* positions_dev, void* out_dev, int out_u8, int N, int Hc, int Wc, int P, void* stream) {
+  JN_CHECK(views_dev && image_index_dev && positions_dev && out_dev, JN_EINVAL, "jn_gather_patches_views: null argument");
+  JN_CHECK(N >= 0 && n_views >= 1 && P >= 1 && Hc >= P && Wc >= P && Hc % P == 0 && Wc % P == 0, JN_EINVAL,
+           "jn_gather_patches_views: bad shape");
+  if (N == 0) return JN_OK;
+  jn_image_view v0;
+  JN_HIP(hipMemcpyAsync(&v0, views_dev, sizeof(v0), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  JN_HIP(hipStreamSynchronize((hipStream_t)stream));
+  JN_CHECK((v0.src_u8 == 0 || v0.src_u8 == 1) && (v0.src_u8 || !out_u8), JN_EINVAL, "jn_gather_patches_views: a byte output needs byte sources");
+  launch_view_gather(views_dev, v0.src_u8, image_index_dev, positions_dev, out_dev, out_u8, 3LL * P * P, N, P, nullptr, 0,
+                     (hipStream_t)stream);
+  JN_HIP(hipGetLastError());
+  return JN_OK;
+}
+
 int jn_env_patches(jn_ctx* ctx, float* out_dev, void* stream) {
   JN_CHECK(ctx && ctx->env.ready && out_dev, JN_ESTATE, "jn_env_init has not been called");
   const EnvState& e = ctx->env;
+  if (e.view_mode) {
+    const int P = ctx->cfg.patch_size;
+    env_gather(e, out_dev, 3LL * P * P, P, nullptr, 0, (hipStream_t)stream);
+    JN_HIP(hipGetLastError());
+    return JN_OK;
+  }
   if (e.images_u8)
     return jn_gather_patches_u8((const uint8_t*)e.images, e.positions, out_dev, e.B, 3, e.H, e.W, ctx->cfg.patch_size, stream);
   return jn_gather_patches((const float*)e.images, e.positions, out_dev, e.B, 3, e.H, e.W, ctx->cfg.patch_size, stream);
@@ -1925,16 +2023,27 @@ static int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev
     }
     ds_stream = ctx->aux_stream;
   }
+  // view mode: column t of the staging stack holds the patches at positions[:, t].  The training backward reads the
+  // columns again and the detector's second stream reads one while the decision path moves on, so both keep all of
+  // them (a column nobody overwrites replaces the position snapshot); otherwise one column is reused
+  const bool vm = e.view_mode;
+  if (vm) {
+    int rs = ensure_stage(ctx, (train || ds_stream != s) ? T + 1 : 1);
+    if (rs) return rs;
+    stage_fill(e, P, 0, nullptr, 0, s);
+  }
   auto detect_step = [&](int col, const int* flag) -> int {
     const int64_t* pos = e.positions;
     if (ds_stream != s) {
-      int64_t* snap = ctx->det_pos + (size_t)col * B * 2;
-      JN_HIP(hipMemcpyAsync(snap, e.positions, (size_t)B * 2 * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+      if (!vm) {
+        int64_t* snap = ctx->det_pos + (size_t)col * B * 2;
+        JN_HIP(hipMemcpyAsync(snap, e.positions, (size_t)B * 2 * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+        pos = snap;
+      }
       JN_HIP(hipEventRecord(ctx->aux_fork, s));
       JN_HIP(hipStreamWaitEvent(ds_stream, ctx->aux_fork, 0));
-      pos = snap;
     }
-    const StemSrc ds = env_stem_src(e, pos);
+    const StemSrc ds = vm ? stage_stem_src(e, P, col) : env_stem_src(e, pos);
     int r = detect_impl(ctx, ds, B, ctx->det_tmp_boxes, ctx->det_tmp_counts, nullptr, flag, B, ds_stream);
     if (r) return r;
     launch_det_scatter(ctx->det_tmp_boxes, ctx->det_tmp_counts, out->det_boxes_dev, out->det_counts_dev, B, T + 1, col, Kd,
@@ -1990,7 +2099,7 @@ static int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev
     const int* flag = stop_early ? ctx->n_done + t : nullptr;
     if (!c.no_patch_emb) {
       if (ctx->profiling) JN_HIP(hipEventRecord(ctx->conv_ev[2 * t], s));
-      if ((rc = run_net(ctx, ctx->enc_net, B, ss, train ? t + 1 : 0, train, flag, B, s))) return rc;
+      if ((rc = run_net(ctx, ctx->enc_net, B, vm ? stage_stem_src(e, P, t) : ss, train ? t + 1 : 0, train, flag, B, s))) return rc;
       if (ctx->profiling) { JN_HIP(hipEventRecord(ctx->conv_ev[2 * t + 1], s)); ctx->conv_ev_used = 2 * (t + 1); }
       if ((rc = run_embed_fpn(ctx, B, train ? t + 1 : 0, train ? ctx->efpn_train + (size_t)t * B * ctx->efpn_h * ctx->efpn_w * C : nullptr, flag, B, s))) return rc;
     }
@@ -2013,6 +2122,7 @@ static int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev
     launch_gpt_step(a, s);
     if (out->patches_dev)
       env_gather(e, out->patches_dev + (long long)(t + 1) * 3 * P * P, patch_stride, P, flag, B, s);
+    if (vm && (t + 1 < T || do_detection)) stage_fill(e, P, t + 1, flag, B, s);    // read by the next step and the detector
     if (do_detection && (rc = detect_step(t + 1, flag))) return rc;     // src/reinforce.py:162-167
   }
   if (ds_stream != s) {
@@ -2255,8 +2365,17 @@ static int reinforce_backward_impl(jn_ctx* ctx, const jn_rollout_out* out, int S
   for (int t0 = 0; t0 < S; t0 += chunk) {
     StemSrc ss = env_stem_src(e, out->positions_dev + 2 * t0);
     ss.pos_stride = 2 * (T + 1);
+    long long pos_slot = 2;
+    if (e.view_mode) {
+      // the staged columns t0 ... are one contiguous run of plain patches [step][agent]; the stem's weight gradient
+      // steps from pass to pass through its position operand, so the table stage_pos names column t as "P-row 3 B t"
+      JN_CHECK(e.stage && e.stage_cols == T + 1, JN_ESTATE, "the staged patches of the rollout are gone");
+      ss = stage_stem_src(e, c.patch_size, 0);
+      ss.positions = e.stage_pos + (size_t)t0 * B * 2;
+      pos_slot = 2LL * B;
+    }
     if ((rc = encoder_backward(ctx, std::min(chunk, S - t0), B, t0 + 1, ctx->efpn_train + (size_t)t0 * B * K,
-                               ctx->d_tok_emb + (size_t)t0 * B * C, ss, 2, s))) return rc;
+                               ctx->d_tok_emb + (size_t)t0 * B * C, ss, pos_slot, s))) return rc;
   }
   if (ctx->profiling && ctx->ev[3]) { JN_HIP(hipEventRecord(ctx->ev[3], s)); ctx->bwd_timed = true; }
   JN_HIP(hipGetLastError());

@@ -189,6 +189,15 @@ struct EnvState {
   int32_t* steps = nullptr;       // [B]
   uint8_t* has_stopped = nullptr; // [B]
   int32_t* n_bbox_tiles = nullptr;// [B] sum(bbox_masks)
+  // view mode (jn_env_init_views): `images` is null and H x W is the logical canvas; the patches of a glimpse step are
+  // gathered through the views into column `col` of the staging stack, which the encoders then read as plain patches
+  bool view_mode = false;
+  jn_image_view* views = nullptr; // [B] device copy of the table (capacity max_batch)
+  void* stage = nullptr;          // [stage_cols][B][3][P][P] in the sources' element type (images_u8); hipMalloc / hipFree
+  size_t stage_bytes = 0;
+  int stage_cols = 0;             // columns in use: T + 1 when a later pass reads them again, else 1
+  int64_t* stage_pos = nullptr;   // [block_size + 1][B][2] = (3 B t, 0): "position" of column t's first patch in units of P rows
+  int stage_pos_B = 0;            // the B that table was written for
 };
 
 }  // namespace jnr

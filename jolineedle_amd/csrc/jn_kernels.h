@@ -267,6 +267,11 @@ int launch_gather(const uint8_t* images, const int64_t* positions, float* out, l
                   const int64_t* image_index = nullptr);
 int launch_bbox_masks(const int64_t* bboxes, uint8_t* masks, int32_t* n_tiles, int B, int nb, int H, int W, int P,
                       hipStream_t s);
+// kernels_view.hip: the indexed gather through image views (jnroll.h: jn_image_view); all views of one element type.
+// out is float, or uint8 when out_u8 (byte sources only); image_index = null: patch n reads view n
+int launch_view_gather(const jn_image_view* views, int src_u8, const int64_t* image_index, const int64_t* positions,
+                       void* out, int out_u8, long long out_sample_stride, int N, int P, const int* skip_flag,
+                       int skip_when, hipStream_t s);
 
 struct EnvPtrs {
   int64_t* positions; uint8_t* bbox_masks; uint8_t* visited; int32_t* steps; uint8_t* has_stopped;

@@ -18,7 +18,14 @@ from .engine import Engine, bare_env_config
 class NeedleGeneralEnv:
     def __init__(self, images: Tensor, bboxes: Tensor, patch_size: int, max_ep_len: int,
                  n_glimps_levels: int = 1, stop_enabled: bool = False, engine: Engine = None, *,
-                 uint8_images: bool = False):
+                 uint8_images: bool = False, views=None):
+        """views: an ``ImageViews`` (views.py) — the env then sees the augmented images on the views' canvas without
+        their ever being written; `images` may be None, `bboxes` are the boxes already on the canvas
+        (``views.transform_bboxes``) and ``height`` / ``width`` are the canvas."""
+        self.views = views
+        if views is not None:
+            self._init_views(views, bboxes, patch_size, max_ep_len, n_glimps_levels, stop_enabled, engine)
+            return
         assert images.shape[0] == bboxes.shape[0]          # general_env.py:37-39
         assert len(images.shape) == 4
         assert n_glimps_levels > 0
@@ -46,6 +53,28 @@ class NeedleGeneralEnv:
         self._engine = None
         self.bind(engine)
 
+    def _init_views(self, views, bboxes, patch_size, max_ep_len, n_glimps_levels, stop_enabled, engine):
+        assert len(views) == bboxes.shape[0]
+        assert n_glimps_levels > 0
+        if n_glimps_levels != 1:
+            raise NotImplementedError("only n_glimps_levels == 1 is on the rollout path (src/reinforce.py:58)")
+        if views.device.type != "cuda":
+            raise RuntimeError("NeedleGeneralEnv of the HIP engine needs images on the GPU (no CPU fallback)")
+        self.patch_size, self.max_ep_len = patch_size, max_ep_len
+        self.n_glimps_levels, self.stop_enabled = n_glimps_levels, stop_enabled
+        self.batch_size, self.n_channels = len(views), 3
+        self.height, self.width = views.canvas
+        assert self.height % patch_size == 0 and self.width % patch_size == 0
+        self.n_vertical_patches = self.height // patch_size
+        self.n_horizontal_patches = self.width // patch_size
+        self.device = views.device
+        self.uint8_images = views.uint8
+        self._images = None
+        self.bboxes = bboxes
+        self._bboxes_dev = bboxes.to(self.device, torch.int64).contiguous()
+        self._engine = None
+        self.bind(engine)
+
     # ---- engine binding ----------------------------------------------------------------
     def bind(self, engine: Engine = None):
         """(Re-)create the device state inside `engine` (the model's context for rollouts)."""
@@ -56,6 +85,11 @@ class NeedleGeneralEnv:
             return
         self._engine = engine
         nb = self._bboxes_dev.shape[1] if self._bboxes_dev.dim() == 3 else 0
+        if self.views is not None:
+            check(engine.lib.jn_env_init_views(engine.handle, self.views.table_host(), ptr(self._bboxes_dev), self.batch_size,
+                                               self.height, self.width, nb, self.max_ep_len, int(self.stop_enabled),
+                                               self._stream()), "jn_env_init_views")
+            return
         init = engine.lib.jn_env_init_u8 if self.uint8_images else engine.lib.jn_env_init
         check(init(engine.handle, ptr(self._images), ptr(self._bboxes_dev), self.batch_size,
                    self.height, self.width, nb, self.max_ep_len, int(self.stop_enabled),
@@ -80,6 +114,8 @@ class NeedleGeneralEnv:
     # ---- reference surface -------------------------------------------------------------
     @property
     def images(self) -> Tensor:
+        if self.views is not None:                         # on demand only: the engine never needs the canvas
+            return self.views.materialize().unsqueeze(1)
         return self._images.unsqueeze(1)                   # [B, 1, C, H, W] (general_env.py:115); uint8 env: the bytes
 
     @property
@@ -167,15 +203,15 @@ class NeedleGeneralEnv:
             neg = torch.nonzero(~any_box[i])
             neg = neg[torch.randperm(len(neg), generator=generator)[:sample_neg]]
             for y, x in torch.cat((pos, neg)).tolist():
-                if self.uint8_images:
+                if self.uint8_images or self.views is not None:
                     cells.append((i, y, x))
                 else:
                     patches.append(self._images[i, :, y * P:(y + 1) * P, x * P:(x + 1) * P])
                 all_boxes.append(torch.nn.functional.pad(boxes[i, y, x], (1, 0)))
-        if self.uint8_images:
+        if self.uint8_images or self.views is not None:
             from .trajectory import gather_indexed
             cells = torch.tensor(cells, dtype=torch.int64).reshape(-1, 3)
-            return (gather_indexed(self._images, cells[:, 0], cells[:, 1:], P),
+            return (gather_indexed(self._images, cells[:, 0], cells[:, 1:], P, views=self.views),
                     torch.stack(all_boxes).to(self.device))
         return torch.stack(patches), torch.stack(all_boxes).to(self.device)
 

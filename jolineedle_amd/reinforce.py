@@ -173,8 +173,21 @@ class ReinforceTrainer:
         self.iter_num = getattr(self, "iter_num", 0) + 1
         model.train()
         images, bboxes = batch["image"].to(self.device), batch["bboxes"]
-        env = NeedleGeneralEnv(images, bboxes, self.patch_size, self.max_ep_len, self.n_glimps_levels, self.stop_enabled,
-                               engine=model.engine(), uint8_images=bool(getattr(config, "uint8_images", False)))
+        u8 = bool(getattr(config, "uint8_images", False))
+        # --augment-rotate / --augment-translate (src/dataset.py:274-278): drawn per image, applied inside the patch reads
+        views = None
+        if getattr(config, "rotations", False) or getattr(config, "translations", False):
+            from .views import trainer_views
+            src = images if (u8 and images.dtype == torch.uint8) else images.to(torch.float32)
+            views = trainer_views(self, src.contiguous(), bboxes, self.patch_size)
+        self.last_views = views
+        if views is not None:
+            env = NeedleGeneralEnv(None, views.transform_bboxes(bboxes), self.patch_size, self.max_ep_len, self.n_glimps_levels,
+                                   self.stop_enabled, engine=model.engine(), views=views)
+        else:
+            env = NeedleGeneralEnv(images, bboxes, self.patch_size, self.max_ep_len, self.n_glimps_levels, self.stop_enabled,
+                                   engine=model.engine(), uint8_images=u8)
+        self.last_env = env
         rollout = self.rollout(env, keep_patches=False, **rollout_kw)
         metrics = self.compute_metrics(rollout)
         loss = metrics["loss"]

@@ -54,16 +54,25 @@ class SupervisedTrainer:
         else:
             images = images.to(self.device, torch.float32).contiguous()
         P = int(cfg.patch_size)
+        # --augment-rotate / --augment-translate (src/dataset.py:274-278): the teacher walks the transformed boxes on the
+        # views' canvas and both patch tensors are cut through the views; the augmented images are never written
+        views, boxes = None, batch["bboxes"]
+        if getattr(cfg, "rotations", False) or getattr(cfg, "translations", False):
+            from .views import stack_bboxes, trainer_views
+            views = trainer_views(self, images, boxes, P)
+            boxes = views.transform_bboxes(stack_bboxes(boxes, images.shape[0]))
+        self.last_views = views
+        height, width = views.canvas if views is not None else images.shape[2:]
         idx = []
         for i in range(images.shape[0]):
-            bb = batch["bboxes"][i]
+            bb = boxes[i]
             if isinstance(bb, torch.Tensor):
                 bb = bb[(bb != 0).any(dim=-1)] if bb.numel() else bb.reshape(0, 4)      # drop the collate's zero rows
-            env = NeedleSimpleEnv(None, P, bb, seed=None if seed is None else seed + i, height=images.shape[2], width=images.shape[3])
+            env = NeedleSimpleEnv(None, P, bb, seed=None if seed is None else seed + i, height=height, width=width)
             idx.append(env.generate_sample_indices(int(cfg.max_seq_len), int(getattr(cfg, "min_keypoints", 0)),
                                                    int(getattr(cfg, "max_keypoints", 0)),
                                                    bool(getattr(cfg, "binomial_keypoints", False)), position))
-        out = assemble_samples(images, list(range(images.shape[0])), idx, P)
+        out = assemble_samples(images, list(range(images.shape[0])), idx, P, views=views)
         cid = batch.get("class_id")
         out["class_id"] = (torch.as_tensor(cid) if cid is not None else torch.zeros(images.shape[0], dtype=torch.long)).to(self.device, torch.long)
         return out

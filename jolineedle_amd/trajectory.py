@@ -253,9 +253,13 @@ class NeedleSimpleEnv:
         return assemble_samples(self.image, [self.image_index], [idx], self.patch_size, stacked=False)
 
 
-def gather_indexed(images: torch.Tensor, image_index: torch.Tensor, positions: torch.Tensor, patch_size: int) -> torch.Tensor:
+def gather_indexed(images: torch.Tensor, image_index: torch.Tensor, positions: torch.Tensor, patch_size: int,
+                   views=None) -> torch.Tensor:
     """out[n] = images[image_index[n], :, y*P:(y+1)*P, x*P:(x+1)*P]; a negative image index gives a zero patch.
-    uint8 images are read in place and give byte / 255 (fp32, as ToTensor computes it)."""
+    uint8 images are read in place and give byte / 255 (fp32, as ToTensor computes it).
+    views: an ``ImageViews`` — the patches are cut from its augmented canvas instead (`images` is not used)."""
+    if views is not None:
+        return views.gather(image_index, positions, patch_size)
     from . import _lib
     from ._lib import check, ptr
     assert images.is_cuda and images.dtype in (torch.float32, torch.uint8) and images.is_contiguous(), \
@@ -282,11 +286,11 @@ def gather_indexed(images: torch.Tensor, image_index: torch.Tensor, positions: t
 
 
 def assemble_samples(images: torch.Tensor, image_ids: Sequence[int], indices: Sequence[Dict[str, np.ndarray]],
-                     patch_size: int, stacked: bool = True) -> Dict[str, torch.Tensor]:
+                     patch_size: int, stacked: bool = True, views=None) -> Dict[str, torch.Tensor]:
     """Turn per-image index dicts into the reference's (collated) tensors with two device gathers: trajectory patches
     [B, T, C, P, P] and detector patches [sum M_i, C, P, P]; boxes are zero-row padded to the longest list
     (NeedleSimpleEnv.collate_fn, src/env/simple_env.py:720-763)."""
-    dev = images.device
+    dev = images.device if views is None else views.device
     B, T = len(indices), indices[0]["masks"].shape[0]
     nb = max(int(d["local_bboxes"].shape[1]) for d in indices)
 
@@ -295,11 +299,11 @@ def assemble_samples(images: torch.Tensor, image_ids: Sequence[int], indices: Se
 
     ii = np.concatenate([np.where(d["masks"] > 0, i, -1) for i, d in zip(image_ids, indices)]).astype(np.int64)
     pos = np.concatenate([d["positions"] for d in indices])
-    patches = gather_indexed(images, torch.from_numpy(ii), torch.from_numpy(pos), patch_size)
+    patches = gather_indexed(images, torch.from_numpy(ii), torch.from_numpy(pos), patch_size, views=views)
     iy = np.concatenate([np.full(d["positions_yolox"].shape[0], i, np.int64) for i, d in zip(image_ids, indices)])
     py = np.concatenate([d["positions_yolox"] for d in indices])
     out = {"patches": patches.view(B, T, *patches.shape[1:]),
-           "patches_yolox": gather_indexed(images, torch.from_numpy(iy), torch.from_numpy(py), patch_size),
+           "patches_yolox": gather_indexed(images, torch.from_numpy(iy), torch.from_numpy(py), patch_size, views=views),
            "bboxes_yolox": torch.from_numpy(np.concatenate([pad(d["bboxes_yolox"]) for d in indices])).to(dev)}
     for k in ("current_actions", "next_actions", "positions", "masks", "labels"):
         out[k] = torch.from_numpy(np.stack([d[k] for d in indices])).to(dev)
