@@ -146,7 +146,8 @@ int jn_env_step(jn_ctx* ctx, const int64_t* actions_dev, float* rewards_dev,
                 uint8_t* terminated_dev, uint8_t* truncated_dev, void* stream);
 /* State views (device pointers into the context, valid until jn_env_init/jn_destroy):
  * what = 0 positions int64 [B,2]; 1 bbox_masks u8 [B,Gh,Gw]; 2 visited u8 [B,Gh,Gw];
- * 3 steps int32 [B]; 4 has_stopped u8 [B]. */
+ * 3 steps int32 [B]; 4 has_stopped u8 [B]; 5 the grid extents int32 [B,2] of ragged mode (jn_env_init_ragged
+ * below; a null pointer in every other mode). */
 int jn_env_state(jn_ctx* ctx, int what, void** ptr_dev);
 /* `patches` property :285-306 — bit-exact strided copy of the current patches
  * -> out [B,3,P,P] f32. */
@@ -193,6 +194,28 @@ typedef struct jn_image_view {
  * type of the sources) and the encoders read that.  jn_env_init / jn_env_init_u8 put the env back into plain mode. */
 int jn_env_init_views(jn_ctx* ctx, const jn_image_view* views_host, const int64_t* bboxes_dev, int B, int Hc, int Wc,
                       int nb, int max_ep_len, int stop_enabled, void* stream);
+/* jn_env_init_views for batched inference over images of unequal size: extents_host [B][2] = (gh, gw) int32, read
+ * from HOST memory, gives every agent its own patch grid inside the canvas grid.  The reference pads an image it
+ * infers on to ITS OWN multiple of patch_size and the agent cannot leave that image (infer.py:138-146; the B = 1 envs
+ * of test(), src/reinforce.py:383-386), whereas on the canvas of padded_collate_fn every agent walks the whole canvas
+ * (the training semantics, which jn_env_init_views keeps).  With extents: the step clamps to gh - 1 / gw - 1, the
+ * random reset draws modulo (gh, gw), the boxes are clipped to gh*P x gw*P; the state arrays stay [B,Gh,Gw] on the
+ * canvas grid, cells outside an extent are never visited and never marked.  Agent b then behaves exactly as a B = 1
+ * env on image b padded on its own.  JN_EINVAL beyond jn_env_init_views' checks: an extent outside 1..Hc/P x
+ * 1..Wc/P, a view with ty or tx != 0, a rotated image larger than gh*P x gw*P.  Every other jn_env_init* call clears
+ * ragged mode. */
+int jn_env_init_ragged(jn_ctx* ctx, const jn_image_view* views_host, const int32_t* extents_host,
+                       const int64_t* bboxes_dev, int B, int Hc, int Wc, int nb, int max_ep_len, int stop_enabled,
+                       void* stream);
+/* Trainer.patch_bboxes2full_image (src/trainer.py:250-280) for a whole batch, context-free: the detections of a
+ * rollout (jn_rollout_out: det_boxes [B,T+1,K,7], det_counts [B,T+1], positions [B,T+1,2] (y,x), masks u8 [B,T+1])
+ * become one list per image in full-image pixels.  Image b walks t = 0..S (S <= T steps were executed), skips the
+ * steps with masks[b,t] == 0 and appends the step's boxes in their stored order: columns 0..3 + (x*P, y*P, x*P,
+ * y*P) as one f32 add each, columns 4..6 copied.  out_boxes [B,(S+1)*K,7]: rows 0..out_totals[b]-1 of image b are
+ * written, the rest is left alone; out_totals int32 [B] is all the host needs to read back. */
+int jn_rollout_boxes_to_image(const float* det_boxes_dev, const int32_t* det_counts_dev, const int64_t* positions_dev,
+                              const uint8_t* masks_dev, int B, int T, int S, int K, int P, float* out_boxes_dev,
+                              int32_t* out_totals_dev, void* stream);
 /* Context-free indexed gather through a DEVICE table of n_views views (all of one element type, already valid):
  * out[n] = canvas[image_index[n]][:, y*P:(y+1)*P, x*P:(x+1)*P], image_index[n] < 0 = zero patch.  out_u8 = 0:
  * out is f32 (bytes as b / 255); out_u8 = 1: u8 sources only, out is the transformed byte copy. */

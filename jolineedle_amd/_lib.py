@@ -92,6 +92,10 @@ SIGNATURES = {
                                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "jn_env_init_views": (C.c_int, [C.c_void_p, C.POINTER(JnImageView), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_void_p]),
+    "jn_env_init_ragged": (C.c_int, [C.c_void_p, C.POINTER(JnImageView), C.POINTER(C.c_int32), C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                     C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "jn_rollout_boxes_to_image": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "jn_gather_patches_views": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                           C.c_int, C.c_int, C.c_void_p]),
     "jn_backbone_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

@@ -1692,7 +1692,7 @@ int jn_detector_backward(jn_ctx* ctx, int pass, const float* dloss_dev, float sc
 static EnvPtrs env_ptrs(jn_ctx* ctx) {
   const EnvState& e = ctx->env;
   EnvPtrs p{e.positions, e.bbox_masks, e.visited, e.steps, e.has_stopped, e.n_bbox_tiles, ctx->found,
-            e.B, e.Gh, e.Gw, e.T, e.stop};
+            e.B, e.Gh, e.Gw, e.T, e.stop, e.ragged ? e.extent : nullptr};
   return p;
 }
 
@@ -1747,7 +1747,8 @@ static StemSrc stage_stem_src(const EnvState& e, int P, int t) {
 }
 
 static int env_init_impl(jn_ctx* ctx, const void* images_dev, int images_u8, const int64_t* bboxes_dev, int B, int H, int W,
-                         int nb, int max_ep_len, int stop_enabled, void* stream, const jn_image_view* views_host = nullptr) {
+                         int nb, int max_ep_len, int stop_enabled, void* stream, const jn_image_view* views_host = nullptr,
+                         const int32_t* extents_host = nullptr) {
   const int P = ctx->cfg.patch_size;
   JN_CHECK(B >= 1 && B <= ctx->cfg.max_batch, JN_EINVAL, "B=%d exceeds max_batch=%d", B, ctx->cfg.max_batch);
   // general_env.py:50-51
@@ -1787,11 +1788,17 @@ static int env_init_impl(jn_ctx* ctx, const void* images_dev, int images_u8, con
     }
     ctx->train_out_valid = false;     // the staged patches of an earlier rollout belong to the earlier views
   }
+  if (extents_host) {
+    if (!e.extent && (rc = dev_alloc(ctx, &e.extent, (size_t)ctx->cfg.max_batch * 2))) return rc;
+    // (ragged mode comes with views: the stream was drained for their table above)
+    JN_HIP(hipMemcpy(e.extent, extents_host, (size_t)B * 2 * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  e.ragged = extents_host != nullptr;
   e.view_mode = views_host != nullptr;
   e.images = images_dev; e.images_u8 = images_u8;
   e.B = B; e.H = H; e.W = W; e.nb = nb; e.Gh = Gh; e.Gw = Gw; e.T = max_ep_len;
   e.stop = stop_enabled ? 1 : 0;
-  launch_bbox_masks(bboxes_dev, e.bbox_masks, e.n_bbox_tiles, B, nb, H, W, P, s);
+  launch_bbox_masks(bboxes_dev, e.bbox_masks, e.n_bbox_tiles, B, nb, H, W, P, s, e.ragged ? e.extent : nullptr);
   launch_env_reset(env_ptrs(ctx), nullptr, 0, s);   // zeroed state at (0,0)-independent start; reset() follows
   JN_HIP(hipGetLastError());
   e.ready = true;
@@ -1810,9 +1817,9 @@ int jn_env_init_u8(jn_ctx* ctx, const uint8_t* images_dev, const int64_t* bboxes
   return env_init_impl(ctx, images_dev, 1, bboxes_dev, B, H, W, nb, max_ep_len, stop_enabled, stream);
 }
 
-int jn_env_init_views(jn_ctx* ctx, const jn_image_view* views_host, const int64_t* bboxes_dev, int B, int Hc, int Wc, int nb,
-                      int max_ep_len, int stop_enabled, void* stream) {
-  JN_CHECK(ctx && views_host && (bboxes_dev || nb == 0), JN_EINVAL, "jn_env_init_views: null argument");
+// the checks jn_env_init_views and jn_env_init_ragged share; extents_host = null: plain view mode
+static int env_init_views_impl(jn_ctx* ctx, const jn_image_view* views_host, const int32_t* extents_host, const int64_t* bboxes_dev,
+                               int B, int Hc, int Wc, int nb, int max_ep_len, int stop_enabled, void* stream) {
   JN_CHECK(B >= 1 && B <= ctx->cfg.max_batch, JN_EINVAL, "B=%d exceeds max_batch=%d", B, ctx->cfg.max_batch);
   const int P = ctx->cfg.patch_size;
   JN_CHECK(Hc >= P && Wc >= P && Hc % P == 0 && Wc % P == 0, JN_EINVAL, "canvas %dx%d is not a multiple of patch_size %d", Hc, Wc, P);
@@ -1826,8 +1833,30 @@ int jn_env_init_views(jn_ctx* ctx, const jn_image_view* views_host, const int64_
              "view %d: the rotated image %dx%d does not fit the canvas %dx%d", b, turned ? v.Ws : v.Hs, turned ? v.Hs : v.Ws, Hc, Wc);
     JN_CHECK((v.src_u8 == 0 || v.src_u8 == 1) && v.src_u8 == views_host[0].src_u8, JN_EINVAL,
              "view %d: mixed element types within one env", b);
+    if (extents_host) {
+      const int gh = extents_host[2 * b], gw = extents_host[2 * b + 1];
+      JN_CHECK(gh >= 1 && gh <= Hc / P && gw >= 1 && gw <= Wc / P, JN_EINVAL,
+               "view %d: extent %dx%d is outside the canvas grid %dx%d", b, gh, gw, Hc / P, Wc / P);
+      JN_CHECK(v.ty == 0 && v.tx == 0, JN_EINVAL, "view %d: a ragged env takes no translation (ty %d, tx %d)", b, v.ty, v.tx);
+      JN_CHECK((turned ? v.Ws : v.Hs) <= gh * P && (turned ? v.Hs : v.Ws) <= gw * P, JN_EINVAL,
+               "view %d: the rotated image %dx%d does not fit its extent %dx%d patches", b, turned ? v.Ws : v.Hs,
+               turned ? v.Hs : v.Ws, gh, gw);
+    }
   }
-  return env_init_impl(ctx, nullptr, views_host[0].src_u8, bboxes_dev, B, Hc, Wc, nb, max_ep_len, stop_enabled, stream, views_host);
+  return env_init_impl(ctx, nullptr, views_host[0].src_u8, bboxes_dev, B, Hc, Wc, nb, max_ep_len, stop_enabled, stream, views_host,
+                       extents_host);
+}
+
+int jn_env_init_views(jn_ctx* ctx, const jn_image_view* views_host, const int64_t* bboxes_dev, int B, int Hc, int Wc, int nb,
+                      int max_ep_len, int stop_enabled, void* stream) {
+  JN_CHECK(ctx && views_host && (bboxes_dev || nb == 0), JN_EINVAL, "jn_env_init_views: null argument");
+  return env_init_views_impl(ctx, views_host, nullptr, bboxes_dev, B, Hc, Wc, nb, max_ep_len, stop_enabled, stream);
+}
+
+int jn_env_init_ragged(jn_ctx* ctx, const jn_image_view* views_host, const int32_t* extents_host, const int64_t* bboxes_dev, int B,
+                       int Hc, int Wc, int nb, int max_ep_len, int stop_enabled, void* stream) {
+  JN_CHECK(ctx && views_host && extents_host && (bboxes_dev || nb == 0), JN_EINVAL, "jn_env_init_ragged: null argument");
+  return env_init_views_impl(ctx, views_host, extents_host, bboxes_dev, B, Hc, Wc, nb, max_ep_len, stop_enabled, stream);
 }
 
 int jn_env_reset(jn_ctx* ctx, const int64_t* positions_dev, uint64_t seed, void* stream) {
@@ -1856,6 +1885,7 @@ int jn_env_state(jn_ctx* ctx, int what, void** ptr_dev) {
     case 2: *ptr_dev = ctx->env.visited; break;
     case 3: *ptr_dev = ctx->env.steps; break;
     case 4: *ptr_dev = ctx->env.has_stopped; break;
+    case 5: *ptr_dev = ctx->env.ragged ? ctx->env.extent : nullptr; break;   // null outside ragged mode
     default: set_error("jn_env_state: unknown selector %d", what); return JN_EINVAL;
   }
   return JN_OK;
@@ -1931,6 +1961,22 @@ int jn_gather_patches_views(const jn_image_view* views_dev, int n_views, const i
   JN_CHECK((v0.src_u8 == 0 || v0.src_u8 == 1) && (v0.src_u8 || !out_u8), JN_EINVAL, "jn_gather_patches_views: a byte output needs byte sources");
   launch_view_gather(views_dev, v0.src_u8, image_index_dev, positions_dev, out_dev, out_u8, 3LL * P * P, N, P, nullptr, 0,
                      (hipStream_t)stream);
+  JN_HIP(hipGetLastError());
+  return JN_OK;
+}
+
+int jn_rollout_boxes_to_image(const float* det_boxes_dev, const int32_t* det_counts_dev, const int64_t* positions_dev,
+                              const uint8_t* masks_dev, int B, int T, int S, int K, int P, float* out_boxes_dev,
+                              int32_t* out_totals_dev, void* stream) {
+  JN_CHECK(det_boxes_dev && det_counts_dev && positions_dev && masks_dev && out_boxes_dev && out_totals_dev, JN_EINVAL,
+           "jn_rollout_boxes_to_image: null argument");
+  JN_CHECK(B >= 0 && T >= 0 && S >= 0 && S <= T && K >= 1 && P >= 1, JN_EINVAL, "jn_rollout_boxes_to_image: bad shape");
+  // the kernel keeps four int32 per step in LDS (beside 2 KB of scan buffers); 48 KB of them is far beyond any block_size
+  JN_CHECK((size_t)(S + 1) * 4 * sizeof(int32_t) <= (size_t)48 * 1024, JN_EINVAL,
+           "jn_rollout_boxes_to_image: %d steps need more than 48 KB of LDS (at most 3071 steps)", S);
+  if (B == 0) return JN_OK;
+  launch_boxes_to_image(det_boxes_dev, det_counts_dev, positions_dev, masks_dev, B, T, S, K, P, out_boxes_dev, out_totals_dev,
+                        (hipStream_t)stream);
   JN_HIP(hipGetLastError());
   return JN_OK;
 }

@@ -43,8 +43,10 @@ struct EnvStepResult { float reward; bool terminated, truncated; int y, x; };
 __device__ inline EnvStepResult env_step_one(const EnvPtrs& e, int b, int action) {
   int y = (int)e.positions[2 * b] + kActionDy[action];
   int x = (int)e.positions[2 * b + 1] + kActionDx[action];
-  y = min(max(y, 0), e.Gh - 1);
-  x = min(max(x, 0), e.Gw - 1);
+  // ragged mode: the border is the agent's own image, not the canvas (infer.py:138-146 pads each image on its own)
+  const int gh = e.extent ? e.extent[2 * b] : e.Gh, gw = e.extent ? e.extent[2 * b + 1] : e.Gw;
+  y = min(max(y, 0), gh - 1);
+  x = min(max(x, 0), gw - 1);
   e.positions[2 * b] = y; e.positions[2 * b + 1] = x;
   bool stopped = e.has_stopped[b] | (action == 8);
   e.has_stopped[b] = stopped;

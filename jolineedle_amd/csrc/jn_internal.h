@@ -198,6 +198,10 @@ struct EnvState {
   int stage_cols = 0;             // columns in use: T + 1 when a later pass reads them again, else 1
   int64_t* stage_pos = nullptr;   // [block_size + 1][B][2] = (3 B t, 0): "position" of column t's first patch in units of P rows
   int stage_pos_B = 0;            // the B that table was written for
+  // ragged mode (jn_env_init_ragged): view mode plus a per-agent grid extent; the table is allocated by the first
+  // ragged init, so that an env that never uses it allocates what it always did
+  bool ragged = false;
+  int32_t* extent = nullptr;      // [max_batch][2] = (gh, gw)
 };
 
 }  // namespace jnr

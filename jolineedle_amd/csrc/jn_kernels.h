@@ -266,7 +266,7 @@ int launch_gather(const uint8_t* images, const int64_t* positions, float* out, l
                   int B, int C, int H, int W, int P, const int* skip_flag, int skip_when, hipStream_t s,
                   const int64_t* image_index = nullptr);
 int launch_bbox_masks(const int64_t* bboxes, uint8_t* masks, int32_t* n_tiles, int B, int nb, int H, int W, int P,
-                      hipStream_t s);
+                      hipStream_t s, const int32_t* extent = nullptr);
 // kernels_view.hip: the indexed gather through image views (jnroll.h: jn_image_view); all views of one element type.
 // out is float, or uint8 when out_u8 (byte sources only); image_index = null: patch n reads view n
 int launch_view_gather(const jn_image_view* views, int src_u8, const int64_t* image_index, const int64_t* positions,
@@ -277,6 +277,9 @@ struct EnvPtrs {
   int64_t* positions; uint8_t* bbox_masks; uint8_t* visited; int32_t* steps; uint8_t* has_stopped;
   int32_t* n_bbox_tiles; int32_t* found;
   int B, Gh, Gw, T, stop;
+  // ragged mode (jn_env_init_ragged): [B][2] = (gh, gw), the agent's own grid inside the [Gh, Gw] canvas grid it may not
+  // leave; null = every agent walks the whole canvas.  The state arrays stay canvas-strided either way.
+  const int32_t* extent;
 };
 int launch_env_reset(const EnvPtrs& e, const int64_t* start_positions, uint64_t seed, hipStream_t s);
 int launch_env_step(const EnvPtrs& e, const int64_t* actions, float* rewards, uint8_t* terminated,
@@ -295,6 +298,9 @@ int launch_rollout_begin(const EnvPtrs& e, const RolloutBuffers& r, int64_t* pre
                          int32_t* n_done, hipStream_t s);
 int launch_rollout_epilogue(const RolloutBuffers& r, const int32_t* n_done, int B, int T, int stop_early,
                             hipStream_t s);
+// kernels_ragged.hip: patch_bboxes2full_image for a whole batch (jnroll.h: jn_rollout_boxes_to_image)
+int launch_boxes_to_image(const float* det_boxes, const int32_t* det_counts, const int64_t* positions, const uint8_t* masks,
+                          int B, int T, int S, int K, int P, float* out_boxes, int32_t* out_totals, hipStream_t s);
 
 // ---- decision transformer step (kernels_gpt.hip) -------------------------------------
 struct GptLayerPtrs {

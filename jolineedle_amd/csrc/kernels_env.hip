@@ -77,12 +77,15 @@ int launch_gather(const uint8_t* images, const int64_t* positions, float* out, l
 
 // convert_bboxes_to_masks (src/env/general_env.py:360-379) on the patch grid: a box covers
 // pixels x1..x2, y1..y2 inclusive (kornia "xyxy_plus"), clipped to the image; a patch is
-// marked when it holds at least one covered pixel.  One thread per image.
+// marked when it holds at least one covered pixel.  One thread per image.  With `extent` ([B][2] = (gh, gw)) the
+// image a box is clipped to is the agent's own gh*P x gw*P; the mask rows keep the canvas stride.
 __global__ void bbox_masks_kernel(const long long* __restrict__ bboxes, uint8_t* __restrict__ masks,
-                                  int32_t* __restrict__ n_tiles, int B, int nb, int H, int W, int P) {
+                                  int32_t* __restrict__ n_tiles, int B, int nb, int H, int W, int P,
+                                  const int32_t* __restrict__ extent) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   const int Gh = H / P, Gw = W / P;
+  if (extent) { H = extent[2 * b] * P; W = extent[2 * b + 1] * P; }
   uint8_t* m = masks + (long long)b * Gh * Gw;
   for (int i = 0; i < Gh * Gw; ++i) m[i] = 0;
   for (int k = 0; k < nb; ++k) {
@@ -99,9 +102,9 @@ __global__ void bbox_masks_kernel(const long long* __restrict__ bboxes, uint8_t*
 }
 
 int launch_bbox_masks(const int64_t* bboxes, uint8_t* masks, int32_t* n_tiles, int B, int nb, int H, int W, int P,
-                      hipStream_t s) {
+                      hipStream_t s, const int32_t* extent) {
   hipLaunchKernelGGL(bbox_masks_kernel, dim3((B + 63) / 64), dim3(64), 0, s, (const long long*)bboxes, masks, n_tiles,
-                     B, nb, H, W, P);
+                     B, nb, H, W, P, extent);
   return 0;
 }
 
@@ -113,7 +116,8 @@ __global__ void env_reset_kernel(EnvPtrs e, const long long* __restrict__ start,
   if (start) { y = (int)start[2 * b]; x = (int)start[2 * b + 1]; }
   else {
     const uint4 r = philox4x32(seed, (uint32_t)b, 0u, 0x52455345u, 0u);
-    y = (int)(r.x % (uint32_t)e.Gh); x = (int)(r.y % (uint32_t)e.Gw);
+    const int gh = e.extent ? e.extent[2 * b] : e.Gh, gw = e.extent ? e.extent[2 * b + 1] : e.Gw;
+    y = (int)(r.x % (uint32_t)gh); x = (int)(r.y % (uint32_t)gw);
   }
   e.positions[2 * b] = y; e.positions[2 * b + 1] = x;
   uint8_t* v = e.visited + (long long)b * e.Gh * e.Gw;

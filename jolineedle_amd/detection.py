@@ -78,6 +78,37 @@ def patch_bboxes2full_image(outputs: List[List[Optional[Tensor]]], offsets: Tens
     return res
 
 
+def rollout_boxes_to_image(rollout: dict, patch_size: int) -> List[Optional[Tensor]]:
+    """``patch_bboxes2full_image(rollout["bboxes"], positions[:, :, [1, 0]] * P, rollout["masks"])`` for the whole
+    batch in one launch of the engine (``jn_rollout_boxes_to_image``), from the rollout's device outputs "det_boxes" /
+    "det_counts" / "positions" / "masks" — so it also serves ``rollout(..., bbox_lists=False)``.  Only the per-image totals
+    come back to the host; the returned tensors are slices of one device buffer (None where an image has no box)."""
+    from . import _lib
+    from ._lib import check, ptr
+    boxes, counts, pos, masks = rollout["det_boxes"], rollout["det_counts"], rollout["positions"], rollout["masks"]
+    if boxes is None or counts is None:
+        raise ValueError("rollout_boxes_to_image needs a rollout with do_detection=True")
+    dev = boxes.device
+    B, n, K = boxes.shape[0], boxes.shape[1], boxes.shape[2]
+    S = n - 1
+    # the rollout hands out [:, :S + 1] slices of its [B, T + 1, ...] buffers: read them in place where the strides say so
+    T1 = counts.stride(0) if B > 1 else n
+    in_place = (counts.dtype == torch.int32 and pos.dtype == torch.int64 and boxes.dtype == torch.float32
+                and counts.stride(1) == 1 and T1 >= n
+                and (B == 1 or (boxes.stride(0) == T1 * K * 7 and pos.stride(0) == T1 * 2))
+                and boxes[0].is_contiguous() and pos[0].is_contiguous())
+    if not in_place:
+        boxes, counts, pos, T1 = boxes.float().contiguous(), counts.to(torch.int32).contiguous(), pos.long().contiguous(), n
+    m = torch.zeros((B, T1), device=dev, dtype=torch.uint8)
+    m[:, :n] = masks
+    out = torch.empty((B, n * K, 7), device=dev, dtype=torch.float32)
+    totals = torch.empty((B,), device=dev, dtype=torch.int32)
+    check(_lib.load_library().jn_rollout_boxes_to_image(ptr(boxes), ptr(counts), ptr(pos), ptr(m), B, T1 - 1, S, K, int(patch_size),
+                                                        ptr(out), ptr(totals), _lib.current_stream(dev)),
+          "jn_rollout_boxes_to_image")
+    return [out[b, :k] if k > 0 else None for b, k in enumerate(totals.tolist())]
+
+
 def merge_boxes(boxes: Tensor, threshold: int = 2, target: bool = False) -> Tensor:
     """Union of boxes whose edges are within `threshold` px of each other (src/utils.py:198-255): box i opens a group
     (or keeps the one it already belongs to) and pulls in every later box j with min edge distance <= threshold.

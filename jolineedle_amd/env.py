@@ -18,11 +18,18 @@ from .engine import Engine, bare_env_config
 class NeedleGeneralEnv:
     def __init__(self, images: Tensor, bboxes: Tensor, patch_size: int, max_ep_len: int,
                  n_glimps_levels: int = 1, stop_enabled: bool = False, engine: Engine = None, *,
-                 uint8_images: bool = False, views=None):
+                 uint8_images: bool = False, views=None, clamp_to_image: bool = False):
         """views: an ``ImageViews`` (views.py) — the env then sees the augmented images on the views' canvas without
         their ever being written; `images` may be None, `bboxes` are the boxes already on the canvas
-        (``views.transform_bboxes``) and ``height`` / ``width`` are the canvas."""
+        (``views.transform_bboxes``) and ``height`` / ``width`` are the canvas.
+        clamp_to_image (views without translation only): every agent stays inside its own image's patch grid
+        (``views.grid_extents``) and its boxes are clipped to it, as if the image were padded on its own (infer.py:138-146)
+        — the inference semantics; the default lets every agent walk the canvas, the reference's padded collate."""
         self.views = views
+        self.grid_extents = None
+        if clamp_to_image:
+            assert views is not None, "clamp_to_image needs views"
+            self.grid_extents = views.grid_extents(patch_size)
         if views is not None:
             self._init_views(views, bboxes, patch_size, max_ep_len, n_glimps_levels, stop_enabled, engine)
             return
@@ -85,6 +92,14 @@ class NeedleGeneralEnv:
             return
         self._engine = engine
         nb = self._bboxes_dev.shape[1] if self._bboxes_dev.dim() == 3 else 0
+        if self.grid_extents is not None:
+            import ctypes as C
+            ext = self.grid_extents.contiguous()
+            check(engine.lib.jn_env_init_ragged(engine.handle, self.views.table_host(),
+                                                C.cast(ext.data_ptr(), C.POINTER(C.c_int32)), ptr(self._bboxes_dev),
+                                                self.batch_size, self.height, self.width, nb, self.max_ep_len,
+                                                int(self.stop_enabled), self._stream()), "jn_env_init_ragged")
+            return
         if self.views is not None:
             check(engine.lib.jn_env_init_views(engine.handle, self.views.table_host(), ptr(self._bboxes_dev), self.batch_size,
                                                self.height, self.width, nb, self.max_ep_len, int(self.stop_enabled),

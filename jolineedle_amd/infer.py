@@ -8,8 +8,10 @@ from typing import Dict, List, Optional, Sequence
 import torch
 import torch.nn.functional as F
 
-from .detection import compute_detection_metrics, patch_bboxes2full_image
+from .detection import compute_detection_metrics, detection_targets, patch_bboxes2full_image, rollout_boxes_to_image
 from .env import NeedleGeneralEnv
+from .ragged import (env_metrics, found_ratios, image_env, loop_start_positions, own_steps, plan_chunks,  # noqa: F401
+                     slice_rollout)
 
 
 def load_bboxes(bbox_fname) -> List[List[int]]:
@@ -33,14 +35,29 @@ def pad_to_patch_multiple(image: torch.Tensor, patch_size: int) -> torch.Tensor:
 
 @torch.no_grad()
 def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequence] = None, sample_actions: bool = True,
-                 do_detection: Optional[bool] = None) -> Dict:
+                 do_detection: Optional[bool] = None, batch_size: Optional[int] = None) -> Dict:
     """`images`: [C, H, W] tensors (uint8 0..255 or float 0..1) of any sizes; `targets`: per image an [n, 4] xyxy list /
     tensor or None.  Returns per-image boxes ([n, 7] in full-image pixels or None), positions, step counts, durations
-    and — where targets are given — the mean of the reference's metrics."""
+    and — where targets are given — the mean of the reference's metrics.
+
+    batch_size=None: one ``B = 1`` env and rollout per image, the reference's loop.  batch_size=k (at most the model's
+    ``max_batch``): the images in input order, k at a time, each chunk as one rollout (``ragged.plan_chunks``): uint8
+    images stay bytes and are read in place, the others are fp32, every agent stays inside its own image, the boxes
+    are assembled per image on the device.  Same keys, per image and in input order; ``steps[i]`` is what image i's own
+    rollout reports; ``duration_ms[i]`` is its chunk's time divided by the chunk's size — a share, not a measurement
+    of that image.  Every image starts where the loop's own random reset puts it
+    (``ragged.loop_start_positions``), so on floating-point images greedy results equal the loop's up to the engine's
+    rounding across batch sizes; sampled ones differ (an agent's action stream is keyed by its index in the batch).
+    On uint8 images the two do not see the same pixels: the loop scales on the device (``x.float() / 255``, which torch
+    computes as a multiply by the rounded reciprocal, one ulp off b / 255 for some bytes) while the batched path reads
+    the bytes as the correctly rounded b / 255 that ToTensor computes; measured on the test detector that moved a box
+    by up to 3e-3 px (positions and steps unchanged)."""
     cfg, dev = trainer.config, trainer.device
     P, T = int(cfg.patch_size), int(cfg.max_seq_len)
     if do_detection is None:
         do_detection = bool(getattr(cfg, "detection_enabled", False)) and trainer.yolox_model() is not None
+    if batch_size is not None:
+        return _infer_batched(trainer, images, targets, sample_actions, do_detection, int(batch_size))
     res = {"boxes": [], "positions": [], "steps": [], "duration_ms": []}
     all_metrics = defaultdict(list)
     for i, img in enumerate(images):
@@ -63,6 +80,54 @@ def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequ
             m = trainer.compute_metrics(ro, env)
             if do_detection:
                 m.update(compute_detection_metrics(full, env.get_detection_targets()))
+            for k, v in m.items():
+                all_metrics[k].append(float(v))
+    res["metrics"] = {k: sum(v) / len(v) for k, v in all_metrics.items()}
+    return res
+
+
+def _infer_batched(trainer, images, targets, sample_actions, do_detection, batch_size) -> Dict:
+    dev, P = trainer.device, int(trainer.config.patch_size)
+    n = len(images)
+    res = {"boxes": [None] * n, "positions": [None] * n, "steps": [0] * n, "duration_ms": [0.0] * n}
+    per_image = [None] * n
+    first = trainer._rollouts + 1                         # the loop's rollout of image i is this trainer's number first + i
+    for chunk in plan_chunks(images, batch_size, P, getattr(trainer.model, "max_batch", None)):
+        sel = chunk["indices"]
+        has_tg = [not (targets is None or i >= len(targets) or targets[i] is None) for i in sel]
+        rows = [torch.as_tensor(targets[i]).reshape(-1, 4).to(torch.long) if h else torch.zeros((1, 4), dtype=torch.long)
+                for i, h in zip(sel, has_tg)]
+        imgs = [images[i] if images[i].dtype == torch.uint8 else images[i].float() for i in sel]
+        env = image_env(trainer, imgs, rows, canvas=chunk["canvas"])
+        extents = env.grid_extents.tolist()
+        start = loop_start_positions(trainer, first, sel, extents)
+        t0 = time.perf_counter()
+        ro = trainer.rollout(env, do_detection=do_detection, sample_actions=sample_actions, start_positions=start,
+                             bbox_lists=False)
+        torch.cuda.synchronize(dev)
+        ms = (time.perf_counter() - t0) * 1e3 / len(sel)
+        full = rollout_boxes_to_image(ro, P) if do_detection else [None] * len(sel)
+        steps = own_steps(ro)
+        found = found_ratios(env, ro, steps) if any(has_tg) else None
+        pos_cpu, masks_cpu = ro["positions"].cpu(), ro["masks"].cpu()
+        for b, i in enumerate(sel):
+            res["boxes"][i] = full[b]
+            res["positions"][i] = pos_cpu[b, :steps[b] + 1][masks_cpu[b, :steps[b] + 1]]
+            res["steps"][i] = steps[b]
+            res["duration_ms"][i] = ms
+            if has_tg[b]:
+                ro_b = slice_rollout(ro, b, steps[b])
+                m = dict(env_metrics(trainer, found, ro_b, b))       # what follows compute_metrics' own entries
+                if do_detection:
+                    gh, gw = extents[b]
+                    m.update(compute_detection_metrics([full[b]], detection_targets(rows[b].unsqueeze(0), gh, gw, P)))
+                per_image[i] = (ro_b, m)
+    trainer._rollouts = first - 1 + n                     # where the loop leaves the counter
+    all_metrics = defaultdict(list)
+    for entry in per_image:                               # in input order, as the loop accumulates them (and as it
+        if entry is not None:                             # feeds the reward-norm window through compute_metrics)
+            m = trainer.compute_metrics(entry[0])
+            m.update(entry[1])
             for k, v in m.items():
                 all_metrics[k].append(float(v))
     res["metrics"] = {k: sum(v) / len(v) for k, v in all_metrics.items()}

@@ -1,0 +1,137 @@
+"""Batched rollouts over images of unequal size that reproduce the per-image loop of the reference's inference and
+test (infer.py:87-221, src/reinforce.py:383-392): the images of a chunk become one ``ImageViews`` on the smallest canvas
+that holds them, every agent is kept inside its own image (``NeedleGeneralEnv(..., clamp_to_image=True)``), and the one
+rollout of the chunk is cut back into what each image's own ``B = 1`` rollout would have returned.
+
+What makes the cut exact: agent b of a batch never reads another agent's state; a ``B = 1`` rollout stops at the first
+step after which its agent is terminated or truncated, and in a batch that step is the first t with masks[b, t] == 0
+(termination is sticky), or the chunk's own last step; the returns are a suffix sum over rewards * logit_masks, to which
+the masked steps after that point add exact zeros.  The env of the batch keeps stepping an agent after its own end (a
+stopped agent still moves), so the found-ratios are rebuilt from the positions up to the image's own last step and not
+read from the env's final state."""
+from typing import Dict, List, Optional, Sequence
+
+import torch
+from torch import Tensor
+
+from .env import NeedleGeneralEnv
+from .views import ImageViews
+
+# a padding row of a stacked box tensor that marks no patch and splits into no piece (x2 < x1); all-zero rows are not
+# padding here: the per-image loop gives an image without targets the box (0, 0, 0, 0), which marks patch (0, 0)
+INERT_BOX = (0, 0, -1, -1)
+
+_PER_STEP = ("rewards", "returns", "logprobs", "entropies", "logit_masks", "actions", "logits")
+_PER_TOKEN = ("masks", "positions", "final_emb", "det_counts", "det_boxes", "patches")
+
+
+def plan_chunks(images: Sequence[Tensor], batch_size: int, patch_size: int, max_batch: Optional[int] = None) -> List[Dict]:
+    """The chunks ``infer_images(batch_size=k)`` runs: the images in input order, `k` at a time; the uint8 and the
+    floating-point images of such a group go to separate chunks (one env reads one element type); every chunk gets the
+    smallest canvas (a multiple of `patch_size`) that holds its images.  Needs only shapes and dtypes (no device)."""
+    k, P = int(batch_size), int(patch_size)
+    assert k >= 1, "batch_size must be at least 1"
+    assert max_batch is None or k <= int(max_batch), f"batch_size {k} exceeds the model's max_batch {max_batch}"
+    plan = []
+    for start in range(0, len(images), k):
+        group = range(start, min(start + k, len(images)))
+        parts = [[i for i in group if (images[i].dtype == torch.uint8) == u8] for u8 in (True, False)]
+        for sel in sorted((p for p in parts if p), key=lambda p: p[0]):
+            canvas = tuple(max(-(-int(images[i].shape[d]) // P) for i in sel) * P for d in (-2, -1))
+            plan.append({"indices": sel, "uint8": images[sel[0]].dtype == torch.uint8, "canvas": canvas})
+    return plan
+
+
+def stack_inert(bbox_rows: Sequence[Tensor]) -> Tensor:
+    """[B, nb, 4] int64 from per-image [n_i, 4] rows, padded with ``INERT_BOX``."""
+    nb = max(1, max(int(r.shape[0]) for r in bbox_rows))
+    out = torch.tensor(INERT_BOX, dtype=torch.int64).repeat(len(bbox_rows), nb, 1)
+    for i, r in enumerate(bbox_rows):
+        out[i, :r.shape[0]] = r.to(torch.int64).reshape(-1, 4)
+    return out
+
+
+def image_env(trainer, images: Sequence[Tensor], bbox_rows: Sequence[Tensor], canvas=None) -> NeedleGeneralEnv:
+    """One ragged env over `images` ([3, Hi, Wi], all uint8 — read in place — or all floating point, 0..1) on the
+    model's engine; bbox_rows[i]: [n_i, 4] xyxy in image i's own pixels."""
+    dev, P = trainer.device, int(trainer.patch_size)
+    srcs = [im.to(dev) if im.dtype == torch.uint8 else im.to(dev, torch.float32) for im in images]
+    views = ImageViews(srcs, patch_size=P, canvas=canvas)
+    return NeedleGeneralEnv(None, stack_inert(bbox_rows), P, trainer.max_ep_len, 1, bool(trainer.stop_enabled),
+                            engine=trainer.model.engine(), views=views, clamp_to_image=True)
+
+
+def _philox4x32(seed: int, c0: int, c1: int, c2: int, c3: int):
+    """Philox4x32-10 as the engine computes it (csrc/jn_device.h), on Python integers."""
+    k0, k1, m = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & m, (p0 >> 32) ^ c3 ^ k1, p0 & m
+        k0, k1 = (k0 + 0x9E3779B9) & m, (k1 + 0xBB67AE85) & m
+    return c0, c1, c2, c3
+
+
+def loop_start_positions(trainer, first_rollout: int, indices: Sequence[int], extents: Sequence[Sequence[int]]) -> Tensor:
+    """[n, 2] the start position image indices[j] draws in the per-image loop: there it is agent 0 of rollout number
+    `first_rollout` + indices[j] of this trainer, whose reset draws (y, x) = Philox(rollout seed, agent 0) modulo the
+    image's own grid (env_reset_kernel).  Handing these to the batched rollout makes it start where the loop starts."""
+    out = []
+    for i, (gh, gw) in zip(indices, extents):
+        seed = (trainer.seed * 1000003 + first_rollout + i) & 0xFFFFFFFFFFFFFFFF
+        r = _philox4x32(seed, 0, 0, 0x52455345, 0)
+        out.append([r[0] % gh, r[1] % gw])
+    return torch.tensor(out, dtype=torch.int64)
+
+
+def own_steps(rollout: Dict) -> List[int]:
+    """Per image the step count its own ``B = 1`` rollout reports: the first t >= 1 with masks[b, t] == 0, else all S."""
+    masks = rollout["masks"]
+    S = masks.shape[1] - 1
+    ended = ~masks[:, 1:]
+    first = torch.where(ended.any(1), ended.to(torch.int64).argmax(1) + 1, torch.full((masks.shape[0],), S, device=masks.device))
+    return [int(v) for v in first.tolist()]
+
+
+def slice_rollout(rollout: Dict, b: int, steps: int) -> Dict:
+    """Image b's part of a batched rollout, cut to its own `steps`: the dict of its ``B = 1`` rollout."""
+    out = {}
+    for k, v in rollout.items():
+        if k in _PER_STEP:
+            out[k] = None if v is None else v[b:b + 1, :steps]
+        elif k in _PER_TOKEN:
+            out[k] = None if v is None else v[b:b + 1, :steps + 1]
+        elif k == "bboxes":
+            out[k] = [v[b][:steps + 1]] if v and v[b] else [[]]
+        else:
+            out[k] = v
+    return out
+
+
+@torch.no_grad()
+def found_ratios(env: NeedleGeneralEnv, rollout: Dict, steps: Sequence[int]) -> Tensor:
+    """``env.prop_patches_found`` [B] as it stands after each image's own last step: the patches marked by a box among
+    those visited at positions[b, 0..steps[b]] (same integer counts and the same division as the env's property)."""
+    pos = rollout["positions"]
+    B, n = pos.shape[0], pos.shape[1]
+    Gh, Gw = env.n_vertical_patches, env.n_horizontal_patches
+    st = torch.tensor(list(steps), device=pos.device).unsqueeze(1)
+    own = torch.arange(n, device=pos.device).unsqueeze(0) <= st                  # [B, S + 1]
+    cell = (torch.arange(B, device=pos.device).unsqueeze(1) * Gh + pos[..., 0]) * Gw + pos[..., 1]
+    visited = torch.zeros(B * Gh * Gw, dtype=torch.bool, device=pos.device)
+    visited[cell[own]] = True
+    m = env.bbox_masks
+    count = (m & visited.view(B, Gh, Gw)).sum(dim=(1, 2))
+    tot = m.sum(dim=(1, 2))
+    tot[tot == 0] = 1
+    return count / tot
+
+
+def env_metrics(trainer, found: Tensor, rollout_b: Dict, b: int) -> Dict[str, Tensor]:
+    """The entries ``compute_metrics(rollout, env)`` reads from a ``B = 1`` env (src/reinforce.py:254-263) for image b."""
+    f = found[b]
+    m = {"prop_patches_found": f, "prop_bbox_found": (found > 0).to(torch.float32)[b]}
+    if trainer.stop_enabled:
+        stopped = (rollout_b["actions"][0] == 8).any()       # STOP ends a B = 1 rollout, so it can only be its last action
+        m["stop_used"] = stopped.to(torch.float32)
+        m["stop_misused"] = (stopped & (f < 1)).to(torch.float32)
+    return m

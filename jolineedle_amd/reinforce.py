@@ -74,11 +74,13 @@ class ReinforceTrainer:
 
     def rollout(self, env: NeedleGeneralEnv, do_detection: bool = False, sample_actions: bool = True,
                 forced_actions: torch.Tensor = None, start_positions: torch.Tensor = None,
-                keep_patches: bool = True, stop_early: bool = True) -> Dict[str, torch.Tensor]:
+                keep_patches: bool = True, stop_early: bool = True, bbox_lists: bool = True) -> Dict[str, torch.Tensor]:
         """src/reinforce.py:108-215.  Extra keyword arguments (not in the reference):
         `forced_actions` [B,T] replays a trajectory, `start_positions` [B,2] injects reset
         positions (reference: env.reset(positions)), `keep_patches=False` skips the
-        [B,S+1,3,P,P] patch stack, `stop_early=False` always runs max_ep_len steps."""
+        [B,S+1,3,P,P] patch stack, `stop_early=False` always runs max_ep_len steps, `bbox_lists=False` leaves
+        "bboxes" empty (no B x (S+1) clones): the detections are then only "det_boxes" [B,S+1,K,7] / "det_counts"
+        [B,S+1] on the device, which ``detection.rollout_boxes_to_image`` assembles per image."""
         model, dev = self.model, self.device
         model.sync_weights()
         eng = model.engine()
@@ -140,11 +142,12 @@ class ReinforceTrainer:
             "masks": buf["masks"][:, :S + 1].bool(), "logit_masks": buf["logit_masks"][:, :S].bool(),
             "positions": buf["positions"][:, :S + 1], "bboxes": [[] for _ in range(B)],
             "det_counts": det_counts[:, :S + 1] if do_detection else None,
+            "det_boxes": det_boxes[:, :S + 1] if do_detection else None,
             "patches": patches[:, :S + 1] if patches is not None else None,
             "actions": buf["actions"][:, :S], "logits": buf["logits"][:, :S],
             "final_emb": buf["final_emb"][:, :S + 1],
         }
-        if do_detection:                      # ragged list-of-lists of [n,7] | None (src/reinforce.py:145-146, 166-167)
+        if do_detection and bbox_lists:       # ragged list-of-lists of [n,7] | None (src/reinforce.py:145-146, 166-167)
             cnt = det_counts[:, :S + 1].tolist()
             res["bboxes"] = [[det_boxes[b, t, :cnt[b][t]].clone() if cnt[b][t] > 0 else None for t in range(S + 1)]
                              for b in range(B)]
@@ -400,7 +403,7 @@ class ReinforceTrainer:
         trajectories (moved to full-image coordinates, optionally merged) plus the detector's mAP on every patch that
         holds a box (`yolo_map`).  The reference evaluates one image at a time; any batch size works here (the
         per-image metrics it reads from index 0 stay index 0)."""
-        from .detection import (compute_detection_metrics, merge_boxes_batched, patch_bboxes2full_image)
+        from .detection import patch_bboxes2full_image
         cfg = self.config
         if do_detection is None:
             do_detection = bool(getattr(cfg, "detection_enabled", False))
@@ -412,14 +415,78 @@ class ReinforceTrainer:
             targets = env.get_detection_targets()
             offsets = ro["positions"][:, :, [1, 0]] * self.patch_size        # (y, x) grid -> (x, y) pixels
             preds = patch_bboxes2full_image(ro["bboxes"], offsets, ro["masks"])
-            if merge_bboxes:
-                preds = merge_boxes_batched(preds, target=False)
-                targets = merge_boxes_batched(targets, target=True)
-            metrics.update(compute_detection_metrics(preds, targets))
             patches, patch_targets = env.get_detection_batch(sample_neg=0)
-            pred_bboxes, _, yolo_losses = self.yolox_model()(patches)
-            for k, v in compute_detection_metrics(pred_bboxes, list(patch_targets)).items():
-                metrics["yolo_" + k] = v
-            for k, v in yolo_losses.items():
-                metrics["yolo_" + k] = v
+            metrics.update(self._detection_eval_metrics(preds, targets, patches, patch_targets, merge_bboxes))
         return metrics
+
+    def _detection_eval_metrics(self, preds, targets, patches, patch_targets, merge_bboxes: bool) -> Dict[str, torch.Tensor]:
+        """The detection half of ``eval_on_sample`` (src/reinforce.py:455-497), shared by ``eval_on_batch`` and
+        ``eval_on_images``: mAP-50 of the full-image predictions (optionally merged) and the detector's own mAP and
+        losses on the patches that hold a box."""
+        from .detection import compute_detection_metrics, merge_boxes_batched
+        if merge_bboxes:
+            preds = merge_boxes_batched(preds, target=False)
+            targets = merge_boxes_batched(targets, target=True)
+        metrics = dict(compute_detection_metrics(preds, targets))
+        pred_bboxes, _, yolo_losses = self.yolox_model()(patches)
+        for k, v in compute_detection_metrics(pred_bboxes, list(patch_targets)).items():
+            metrics["yolo_" + k] = v
+        for k, v in yolo_losses.items():
+            metrics["yolo_" + k] = v
+        return metrics
+
+    @torch.no_grad()
+    def eval_on_images(self, images, bboxes, batch_size: int, do_detection: bool = None,
+                       merge_bboxes: bool = None) -> Dict[str, list]:
+        """The per-image ``all_metrics`` of the reference's ``test()`` (src/reinforce.py:383-392) without its loop of
+        ``B = 1`` envs: `images` ([3, Hi, Wi] tensors of any sizes, uint8 read in place or float 0..1) are evaluated
+        `batch_size` at a time (``ragged.plan_chunks``), every agent inside its own image.  Returns, for every key of
+        ``eval_on_batch``, one value per image in image order, each equal to ``eval_on_batch`` on that image alone (up
+        to the engine's rounding across batch sizes; every image starts where its own random reset would put it,
+        ``ragged.loop_start_positions``); ``last_return_values`` grows by one entry per image in image
+        order, as that loop leaves it.  bboxes[i]: [n_i, 4] xyxy in image i's own pixels."""
+        from .detection import detection_targets, rollout_boxes_to_image, split_bboxes_over_patches
+        from .ragged import (env_metrics, found_ratios, image_env, loop_start_positions, own_steps, plan_chunks,
+                             slice_rollout)
+        cfg, P = self.config, int(self.patch_size)
+        if do_detection is None:
+            do_detection = bool(getattr(cfg, "detection_enabled", False))
+        if merge_bboxes is None:
+            merge_bboxes = bool(getattr(cfg, "merge_bboxes", False))
+        rows = [torch.as_tensor(b).reshape(-1, 4).to(torch.long) for b in bboxes]
+        assert len(rows) == len(images)
+        per_image = [None] * len(images)
+        first = self._rollouts + 1                        # eval_on_batch on image i alone would be rollout first + i
+        for chunk in plan_chunks(images, batch_size, P, getattr(self.model, "max_batch", None)):
+            sel = chunk["indices"]
+            imgs = [images[i] if images[i].dtype == torch.uint8 else images[i].float() for i in sel]
+            env = image_env(self, imgs, [rows[i] for i in sel], canvas=chunk["canvas"])
+            extents = env.grid_extents.tolist()
+            ro = self.rollout(env, sample_actions=False, do_detection=do_detection, bbox_lists=False,
+                              start_positions=loop_start_positions(self, first, sel, extents))
+            steps = own_steps(ro)
+            found = found_ratios(env, ro, steps)
+            full = rollout_boxes_to_image(ro, P) if do_detection else None
+            for b, i in enumerate(sel):
+                ro_b = slice_rollout(ro, b, steps[b])
+                metrics = dict(env_metrics(self, found, ro_b, b))     # what follows compute_metrics' own entries
+                per_image[i] = (metrics, ro_b)
+                if not do_detection:
+                    continue
+                gh, gw = extents[b]
+                box = rows[i].unsqueeze(0)
+                # env.get_detection_batch(sample_neg=0) of the image's own env: every patch that holds a piece of a box
+                local, masks = split_bboxes_over_patches(box, gh, gw, P)
+                cells = torch.nonzero(masks.any(-1)[0].cpu())
+                patches = env.views.gather(torch.full((len(cells),), b, dtype=torch.int64), cells, P)
+                patch_targets = torch.stack([torch.nn.functional.pad(local[0, y, x], (1, 0)) for y, x in cells.tolist()]).to(self.device)
+                metrics.update(self._detection_eval_metrics([full[b]], detection_targets(box, gh, gw, P), patches, patch_targets,
+                                                            merge_bboxes))
+        self._rollouts = first - 1 + len(images)          # where that loop leaves the counter
+        out: Dict[str, list] = {}
+        for tail, ro_b in per_image:                      # compute_metrics in image order: the reward-norm window's order
+            m = self.compute_metrics(ro_b)
+            m.update(tail)
+            for k, v in m.items():
+                out.setdefault(k, []).append(float(v))
+        return out

@@ -104,6 +104,14 @@ class ImageViews:
     def uint8(self) -> bool:
         return self.dtype == torch.uint8
 
+    def grid_extents(self, patch_size: int) -> Tensor:
+        """int32 [B, 2] = (ceil(rotated_h / P), ceil(rotated_w / P)): the patch grid of every image padded on its own
+        (infer.py:138-146), which ``NeedleGeneralEnv(..., clamp_to_image=True)`` keeps its agent inside.  Translated
+        views have no such grid (the shift moves the image across it)."""
+        assert not self.ty.any() and not self.tx.any(), "grid extents are defined for views without translation"
+        P = int(patch_size)
+        return torch.tensor([[-(-h // P), -(-w // P)] for h, w in self.rotated_hw], dtype=torch.int32)
+
     # ---- the reference's draws ---------------------------------------------------------------------------
     @classmethod
     def sample(cls, images, bboxes: Tensor, rotations: bool, translations: bool, rng: np.random.Generator,
