@@ -216,6 +216,35 @@ int jn_env_init_ragged(jn_ctx* ctx, const jn_image_view* views_host, const int32
 int jn_rollout_boxes_to_image(const float* det_boxes_dev, const int32_t* det_counts_dev, const int64_t* positions_dev,
                               const uint8_t* masks_dev, int B, int T, int S, int K, int P, float* out_boxes_dev,
                               int32_t* out_totals_dev, void* stream);
+/* merge_boxes (src/utils.py:198-255) for a whole batch, context-free: boxes [B,Nmax,W] f32 with counts int32 [B]
+ * (what jn_rollout_boxes_to_image writes), W = 7 or 6 for predictions (x1,y1,x2,y2,obj,cls,...) -> rows of 6
+ * (x1,y1,x2,y2,max obj*cls,1); target != 0: W = 5 (cls,x1,y1,x2,y2) -> rows of 5 with a leading 0.  Box i joins the
+ * lowest-numbered group that contains it and pulls every later box within `threshold` px (min of the four edge
+ * distances, f32) into that group; groups come out in the order the reference opens them.  out_boxes
+ * [B,Nmax,Wout]: rows 0..out_counts[b]-1 of image b are written.  rounds_dev (int32 [B], may be NULL) receives the
+ * label-relaxation rounds each image took.  JN_EINVAL: Nmax > 4096 (no launch is made), another W.  Inputs are finite. */
+int jn_merge_boxes(const float* boxes_dev, const int32_t* counts_dev, int B, int Nmax, int W, int target, float threshold,
+                   float* out_boxes_dev, int32_t* out_counts_dev, int32_t* rounds_dev, void* stream);
+/* The per-image half of mAP-50 as Trainer.compute_detection_metrics reports it (src/trainer.py:188-248; COCO
+ * protocol, one class): preds [B,Nmax,W >= 5] f32 with score in column 4 and pred_counts int32 [B]; targets
+ * [B,Mmax,5] f32 (cls,x1,y1,x2,y2) with target_counts int32 [B] (Mmax = 0: no targets, both may be NULL).  Per image
+ * the max_det best predictions by score (ties to the lower index) are matched in that order to the untaken target of
+ * highest IoU >= 0.5 (f64, ties to the higher index).  Outputs [B,max_det]: scores f64, hits int32, sel int32 (the
+ * chosen row), valid up to n_pred[b] = min(count, max_det); n_gt[b] = the image's targets.  JN_EINVAL: Nmax or
+ * Mmax > 4096. */
+int jn_match_detections(const float* preds_dev, const int32_t* pred_counts_dev, int B, int Nmax, int W,
+                        const float* targets_dev, const int32_t* target_counts_dev, int Mmax, int max_det,
+                        double* scores_dev, int32_t* hits_dev, int32_t* sel_dev, int32_t* n_pred_dev, int32_t* n_gt_dev,
+                        void* stream);
+/* The average-precision half (same reference site): from jn_match_detections' outputs, out f64 [B] = the AP of every
+ * image on its own (pooled = 0), or out f64 [1] = the AP of all B images' lists concatenated in image order
+ * (pooled = 1).  Score order descending, ties in concatenation order; precision made monotone from the right and
+ * sampled at thresholds_dev (f64 [n_thresholds], the caller's linspace(0, 1, 101)), summed in threshold order.  No
+ * target or no prediction in a segment gives 0.  JN_EINVAL: a segment of more than 8192 slots (B * max_det when
+ * pooled, else max_det), n_thresholds outside 1..256. */
+int jn_average_precision(const double* scores_dev, const int32_t* hits_dev, const int32_t* n_pred_dev,
+                         const int32_t* n_gt_dev, int B, int max_det, int pooled, const double* thresholds_dev,
+                         int n_thresholds, double* out_dev, void* stream);
 /* Context-free indexed gather through a DEVICE table of n_views views (all of one element type, already valid):
  * out[n] = canvas[image_index[n]][:, y*P:(y+1)*P, x*P:(x+1)*P], image_index[n] < 0 = zero patch.  out_u8 = 0:
  * out is f32 (bytes as b / 255); out_u8 = 1: u8 sources only, out is the transformed byte copy. */

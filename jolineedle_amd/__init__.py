@@ -22,7 +22,9 @@ from .infer import infer_images, plan_chunks, pad_to_patch_multiple, load_bboxes
 from .trajectory import NeedleSimpleEnv  # noqa: F401
 from .views import ImageViews  # noqa: F401
 from .detection import (patch_bboxes2full_image, rollout_boxes_to_image, merge_boxes, merge_boxes_batched,  # noqa: F401
-                        compute_detection_metrics, detection_targets)
+                        compute_detection_metrics, detection_targets, rollout_boxes_packed, pack_boxes, unpack_boxes,
+                        merge_boxes_device, merge_boxes_batched_device, match_detections_device, average_precision_device,
+                        map_50_device, compute_detection_metrics_device)
 
 __all__ = ["GPT", "NeedleYOLOX", "NeedleGeneralEnv", "ReinforceTrainer", "SupervisedTrainer", "Action", "ACTION_DELTAS",
            "ActionInfo", "get_actions_info", "CfgNode", "get_args", "args_to_config", "load_library"]

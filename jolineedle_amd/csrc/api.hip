@@ -1981,6 +1981,57 @@ int jn_rollout_boxes_to_image(const float* det_boxes_dev, const int32_t* det_cou
   return JN_OK;
 }
 
+int jn_merge_boxes(const float* boxes_dev, const int32_t* counts_dev, int B, int Nmax, int W, int target, float threshold,
+                   float* out_boxes_dev, int32_t* out_counts_dev, int32_t* rounds_dev, void* stream) {
+  JN_CHECK(counts_dev && out_counts_dev && ((boxes_dev && out_boxes_dev) || Nmax == 0), JN_EINVAL, "jn_merge_boxes: null argument");
+  JN_CHECK(B >= 0 && Nmax >= 0, JN_EINVAL, "jn_merge_boxes: bad shape");
+  JN_CHECK(target ? W == 5 : (W == 6 || W == 7), JN_EINVAL,
+           "jn_merge_boxes: %d columns; predictions have 6 or 7, targets 5", W);
+  JN_CHECK(Nmax <= JN_EVAL_MAX_BOXES, JN_EINVAL, "jn_merge_boxes: %d boxes per image, the kernel holds at most %d in LDS", Nmax,
+           JN_EVAL_MAX_BOXES);
+  if (B == 0) return JN_OK;
+  JN_CHECK(launch_merge_boxes(boxes_dev, counts_dev, B, Nmax, W, target, threshold, out_boxes_dev, out_counts_dev, rounds_dev,
+                              (hipStream_t)stream) == 0,
+           JN_EHIP, "jn_merge_boxes: %d bytes of LDS refused", 24 * Nmax);
+  JN_HIP(hipGetLastError());
+  return JN_OK;
+}
+
+int jn_match_detections(const float* preds_dev, const int32_t* pred_counts_dev, int B, int Nmax, int W,
+                        const float* targets_dev, const int32_t* target_counts_dev, int Mmax, int max_det,
+                        double* scores_dev, int32_t* hits_dev, int32_t* sel_dev, int32_t* n_pred_dev, int32_t* n_gt_dev,
+                        void* stream) {
+  JN_CHECK(pred_counts_dev && (preds_dev || Nmax == 0) && ((targets_dev && target_counts_dev) || Mmax == 0) && scores_dev &&
+               hits_dev && sel_dev && n_pred_dev && n_gt_dev,
+           JN_EINVAL, "jn_match_detections: null argument");
+  JN_CHECK(B >= 0 && Nmax >= 0 && Mmax >= 0 && W >= 5 && max_det >= 1, JN_EINVAL, "jn_match_detections: bad shape");
+  JN_CHECK(Nmax <= JN_EVAL_MAX_BOXES && Mmax <= JN_EVAL_MAX_BOXES, JN_EINVAL,
+           "jn_match_detections: %d predictions / %d targets per image, at most %d of either", Nmax, Mmax, JN_EVAL_MAX_BOXES);
+  if (B == 0) return JN_OK;
+  launch_match_detections(preds_dev, pred_counts_dev, B, Nmax, W, targets_dev, target_counts_dev, Mmax, max_det, scores_dev,
+                          hits_dev, sel_dev, n_pred_dev, n_gt_dev, (hipStream_t)stream);
+  JN_HIP(hipGetLastError());
+  return JN_OK;
+}
+
+int jn_average_precision(const double* scores_dev, const int32_t* hits_dev, const int32_t* n_pred_dev,
+                         const int32_t* n_gt_dev, int B, int max_det, int pooled, const double* thresholds_dev,
+                         int n_thresholds, double* out_dev, void* stream) {
+  JN_CHECK(scores_dev && hits_dev && n_pred_dev && n_gt_dev && thresholds_dev && out_dev, JN_EINVAL,
+           "jn_average_precision: null argument");
+  JN_CHECK(B >= 1 && max_det >= 1, JN_EINVAL, "jn_average_precision: bad shape");
+  JN_CHECK(n_thresholds >= 1 && n_thresholds <= JN_EVAL_MAX_THRESHOLDS, JN_EINVAL,
+           "jn_average_precision: %d thresholds, at most %d", n_thresholds, JN_EVAL_MAX_THRESHOLDS);
+  const long long slots = (long long)(pooled ? B : 1) * max_det;
+  JN_CHECK(slots <= JN_EVAL_MAX_ENTRIES, JN_EINVAL, "jn_average_precision: a segment of %lld entries, at most %d", slots,
+           JN_EVAL_MAX_ENTRIES);
+  JN_CHECK(launch_average_precision(scores_dev, hits_dev, n_pred_dev, n_gt_dev, B, max_det, pooled, thresholds_dev, n_thresholds,
+                                    out_dev, (hipStream_t)stream) == 0,
+           JN_EHIP, "jn_average_precision: LDS for %lld entries refused", slots);
+  JN_HIP(hipGetLastError());
+  return JN_OK;
+}
+
 int jn_env_patches(jn_ctx* ctx, float* out_dev, void* stream) {
   JN_CHECK(ctx && ctx->env.ready && out_dev, JN_ESTATE, "jn_env_init has not been called");
   const EnvState& e = ctx->env;

@@ -301,6 +301,18 @@ int launch_rollout_epilogue(const RolloutBuffers& r, const int32_t* n_done, int 
 // kernels_ragged.hip: patch_bboxes2full_image for a whole batch (jnroll.h: jn_rollout_boxes_to_image)
 int launch_boxes_to_image(const float* det_boxes, const int32_t* det_counts, const int64_t* positions, const uint8_t* masks,
                           int B, int T, int S, int K, int P, float* out_boxes, int32_t* out_totals, hipStream_t s);
+// kernels_eval.hip: detection evaluation, one workgroup per image / segment (jnroll.h: jn_merge_boxes,
+// jn_match_detections, jn_average_precision).  Each returns nonzero when the LDS it needs cannot be had.
+constexpr int JN_EVAL_MAX_BOXES = 4096;        // boxes (and targets) per image
+constexpr int JN_EVAL_MAX_ENTRIES = 8192;      // (score, hit) slots per average-precision segment
+constexpr int JN_EVAL_MAX_THRESHOLDS = 256;
+int launch_merge_boxes(const float* boxes, const int32_t* counts, int B, int Nmax, int W, int target, float threshold,
+                       float* out_boxes, int32_t* out_counts, int32_t* out_rounds, hipStream_t s);
+int launch_match_detections(const float* preds, const int32_t* pred_counts, int B, int Nmax, int W, const float* targets,
+                            const int32_t* target_counts, int Mmax, int max_det, double* scores, int32_t* hits, int32_t* sel,
+                            int32_t* n_pred, int32_t* n_gt, hipStream_t s);
+int launch_average_precision(const double* scores, const int32_t* hits, const int32_t* n_pred, const int32_t* n_gt, int B,
+                             int max_det, int pooled, const double* thresholds, int n_thresholds, double* out, hipStream_t s);
 
 // ---- decision transformer step (kernels_gpt.hip) -------------------------------------
 struct GptLayerPtrs {

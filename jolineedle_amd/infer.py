@@ -8,7 +8,8 @@ from typing import Dict, List, Optional, Sequence
 import torch
 import torch.nn.functional as F
 
-from .detection import compute_detection_metrics, detection_targets, patch_bboxes2full_image, rollout_boxes_to_image
+from .detection import (compute_detection_metrics, detection_targets, map_50_device, pack_boxes, patch_bboxes2full_image,
+                        rollout_boxes_packed, rollout_boxes_to_image, unpack_boxes)  # noqa: F401
 from .env import NeedleGeneralEnv
 from .ragged import (env_metrics, found_ratios, image_env, loop_start_positions, own_steps, plan_chunks,  # noqa: F401
                      slice_rollout)
@@ -35,7 +36,7 @@ def pad_to_patch_multiple(image: torch.Tensor, patch_size: int) -> torch.Tensor:
 
 @torch.no_grad()
 def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequence] = None, sample_actions: bool = True,
-                 do_detection: Optional[bool] = None, batch_size: Optional[int] = None) -> Dict:
+                 do_detection: Optional[bool] = None, batch_size: Optional[int] = None, device_metrics: bool = False) -> Dict:
     """`images`: [C, H, W] tensors (uint8 0..255 or float 0..1) of any sizes; `targets`: per image an [n, 4] xyxy list /
     tensor or None.  Returns per-image boxes ([n, 7] in full-image pixels or None), positions, step counts, durations
     and — where targets are given — the mean of the reference's metrics.
@@ -51,13 +52,18 @@ def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequ
     On uint8 images the two do not see the same pixels: the loop scales on the device (``x.float() / 255``, which torch
     computes as a multiply by the rounded reciprocal, one ulp off b / 255 for some bytes) while the batched path reads
     the bytes as the correctly rounded b / 255 that ToTensor computes; measured on the test detector that moved a box
-    by up to 3e-3 px (positions and steps unchanged)."""
+    by up to 3e-3 px (positions and steps unchanged).
+
+    device_metrics=True (with batch_size): the `map` metric of a chunk's images comes from ``map_50_device`` on the
+    chunk's packed boxes, one readback per chunk, instead of one host ``map_50`` per image."""
     cfg, dev = trainer.config, trainer.device
     P, T = int(cfg.patch_size), int(cfg.max_seq_len)
     if do_detection is None:
         do_detection = bool(getattr(cfg, "detection_enabled", False)) and trainer.yolox_model() is not None
     if batch_size is not None:
-        return _infer_batched(trainer, images, targets, sample_actions, do_detection, int(batch_size))
+        return _infer_batched(trainer, images, targets, sample_actions, do_detection, int(batch_size), device_metrics)
+    if device_metrics:
+        raise ValueError("device_metrics needs batch_size: the per-image loop evaluates one image at a time")
     res = {"boxes": [], "positions": [], "steps": [], "duration_ms": []}
     all_metrics = defaultdict(list)
     for i, img in enumerate(images):
@@ -86,7 +92,7 @@ def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequ
     return res
 
 
-def _infer_batched(trainer, images, targets, sample_actions, do_detection, batch_size) -> Dict:
+def _infer_batched(trainer, images, targets, sample_actions, do_detection, batch_size, device_metrics=False) -> Dict:
     dev, P = trainer.device, int(trainer.config.patch_size)
     n = len(images)
     res = {"boxes": [None] * n, "positions": [None] * n, "steps": [0] * n, "duration_ms": [0.0] * n}
@@ -106,7 +112,13 @@ def _infer_batched(trainer, images, targets, sample_actions, do_detection, batch
                              bbox_lists=False)
         torch.cuda.synchronize(dev)
         ms = (time.perf_counter() - t0) * 1e3 / len(sel)
-        full = rollout_boxes_to_image(ro, P) if do_detection else [None] * len(sel)
+        packed = rollout_boxes_packed(ro, P) if do_detection else None
+        full = unpack_boxes(*packed) if do_detection else [None] * len(sel)
+        maps = None
+        if do_detection and device_metrics and any(has_tg):
+            tg = pack_boxes([detection_targets(rows[b].unsqueeze(0), *extents[b], P)[0] if has_tg[b] else None
+                             for b in range(len(sel))], 5, dev)
+            maps = map_50_device(packed, tg, per_image=True)
         steps = own_steps(ro)
         found = found_ratios(env, ro, steps) if any(has_tg) else None
         pos_cpu, masks_cpu = ro["positions"].cpu(), ro["masks"].cpu()
@@ -118,7 +130,9 @@ def _infer_batched(trainer, images, targets, sample_actions, do_detection, batch
             if has_tg[b]:
                 ro_b = slice_rollout(ro, b, steps[b])
                 m = dict(env_metrics(trainer, found, ro_b, b))       # what follows compute_metrics' own entries
-                if do_detection:
+                if maps is not None:
+                    m["map"] = torch.tensor([maps[b]], dtype=torch.float32)
+                elif do_detection:
                     gh, gw = extents[b]
                     m.update(compute_detection_metrics([full[b]], detection_targets(rows[b].unsqueeze(0), gh, gw, P)))
                 per_image[i] = (ro_b, m)

@@ -428,6 +428,13 @@ class ReinforceTrainer:
             preds = merge_boxes_batched(preds, target=False)
             targets = merge_boxes_batched(targets, target=True)
         metrics = dict(compute_detection_metrics(preds, targets))
+        metrics.update(self._detector_eval_metrics(patches, patch_targets))
+        return metrics
+
+    def _detector_eval_metrics(self, patches, patch_targets) -> Dict[str, torch.Tensor]:
+        """The `yolo_*` entries of ``_detection_eval_metrics``: the detector alone on the patches that hold a box."""
+        from .detection import compute_detection_metrics
+        metrics = {}
         pred_bboxes, _, yolo_losses = self.yolox_model()(patches)
         for k, v in compute_detection_metrics(pred_bboxes, list(patch_targets)).items():
             metrics["yolo_" + k] = v
@@ -437,15 +444,21 @@ class ReinforceTrainer:
 
     @torch.no_grad()
     def eval_on_images(self, images, bboxes, batch_size: int, do_detection: bool = None,
-                       merge_bboxes: bool = None) -> Dict[str, list]:
+                       merge_bboxes: bool = None, device_metrics: bool = False) -> Dict[str, list]:
         """The per-image ``all_metrics`` of the reference's ``test()`` (src/reinforce.py:383-392) without its loop of
         ``B = 1`` envs: `images` ([3, Hi, Wi] tensors of any sizes, uint8 read in place or float 0..1) are evaluated
         `batch_size` at a time (``ragged.plan_chunks``), every agent inside its own image.  Returns, for every key of
         ``eval_on_batch``, one value per image in image order, each equal to ``eval_on_batch`` on that image alone (up
         to the engine's rounding across batch sizes; every image starts where its own random reset would put it,
         ``ragged.loop_start_positions``); ``last_return_values`` grows by one entry per image in image
-        order, as that loop leaves it.  bboxes[i]: [n_i, 4] xyxy in image i's own pixels."""
-        from .detection import detection_targets, rollout_boxes_to_image, split_bboxes_over_patches
+        order, as that loop leaves it.  bboxes[i]: [n_i, 4] xyxy in image i's own pixels.
+
+        device_metrics=True: the `map` entry of a whole chunk comes from the device — the rollout's boxes go
+        ``rollout_boxes_packed`` -> (merge_bboxes) ``merge_boxes_device`` -> ``map_50_device(per_image=True)`` without
+        leaving it, the targets are merged there too; one readback per chunk.  Same keys; `map` equals the host
+        path's up to fp32 storage; the `yolo_*` entries are computed as without it."""
+        from .detection import (detection_targets, map_50_device, merge_boxes_device, pack_boxes, rollout_boxes_packed,
+                                split_bboxes_over_patches, unpack_boxes)
         from .ragged import (env_metrics, found_ratios, image_env, loop_start_positions, own_steps, plan_chunks,
                              slice_rollout)
         cfg, P = self.config, int(self.patch_size)
@@ -466,7 +479,16 @@ class ReinforceTrainer:
                               start_positions=loop_start_positions(self, first, sel, extents))
             steps = own_steps(ro)
             found = found_ratios(env, ro, steps)
-            full = rollout_boxes_to_image(ro, P) if do_detection else None
+            packed = rollout_boxes_packed(ro, P) if do_detection else None
+            if do_detection and device_metrics:
+                tg = pack_boxes([detection_targets(rows[i].unsqueeze(0), *extents[b], P)[0] for b, i in enumerate(sel)], 5,
+                                self.device)
+                pr = packed
+                if merge_bboxes:
+                    pr, tg = merge_boxes_device(*pr, target=False), merge_boxes_device(*tg, target=True)
+                maps = map_50_device(pr, tg, per_image=True)
+            elif do_detection:
+                full = unpack_boxes(*packed)
             for b, i in enumerate(sel):
                 ro_b = slice_rollout(ro, b, steps[b])
                 metrics = dict(env_metrics(self, found, ro_b, b))     # what follows compute_metrics' own entries
@@ -480,8 +502,12 @@ class ReinforceTrainer:
                 cells = torch.nonzero(masks.any(-1)[0].cpu())
                 patches = env.views.gather(torch.full((len(cells),), b, dtype=torch.int64), cells, P)
                 patch_targets = torch.stack([torch.nn.functional.pad(local[0, y, x], (1, 0)) for y, x in cells.tolist()]).to(self.device)
-                metrics.update(self._detection_eval_metrics([full[b]], detection_targets(box, gh, gw, P), patches, patch_targets,
-                                                            merge_bboxes))
+                if device_metrics:
+                    metrics["map"] = torch.tensor([maps[b]], dtype=torch.float32)
+                    metrics.update(self._detector_eval_metrics(patches, patch_targets))
+                else:
+                    metrics.update(self._detection_eval_metrics([full[b]], detection_targets(box, gh, gw, P), patches,
+                                                                patch_targets, merge_bboxes))
         self._rollouts = first - 1 + len(images)          # where that loop leaves the counter
         out: Dict[str, list] = {}
         for tail, ro_b in per_image:                      # compute_metrics in image order: the reward-norm window's order
