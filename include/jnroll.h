@@ -225,6 +225,19 @@ int jn_rollout_boxes_to_image(const float* det_boxes_dev, const int32_t* det_cou
  * label-relaxation rounds each image took.  JN_EINVAL: Nmax > 4096 (no launch is made), another W.  Inputs are finite. */
 int jn_merge_boxes(const float* boxes_dev, const int32_t* counts_dev, int B, int Nmax, int W, int target, float threshold,
                    float* out_boxes_dev, int32_t* out_counts_dev, int32_t* rounds_dev, void* stream);
+/* The detector's training loss on given predictor outputs, context-free: the published YOLOX head's get_losses for one
+ * class (called at src/models/yolox.py:58-73 with use_l1 = True; restated in oracle/yolox_ref.py::losses_from_raw) as
+ * jn_detector_step / jn_detector_forward run it after the head, without a network around it.  raw_dev [N,A,6] f32 (reg 4,
+ * obj logit, cls logit; anchors level by level, row-major), targets_dev [N,nb,5] f32 = (class, x1, y1, x2, y2) in patch
+ * pixels, zero rows = padding (converted to cxcywh on the device as the training pass does).  The patch is P x P with
+ * levels of stride0 < stride1 < stride2: level l holds (P / stride_l)^2 anchors, A is their sum.  Outputs: d_raw_dev
+ * [N,A,6] = d loss / d raw before the 1 / max(num_fg, 1) factor, metrics_dev f32[8] as for jn_detector_step, scale_dev
+ * f32[1] = loss_scale / max(num_fg, 1), the factor the predictor backward applies to d_raw.  At most 8 boxes per patch
+ * (see jn_detector_step).  Allocates its scratch and waits for `stream`: an entry for tests and diagnostics, not part of
+ * a training step.  JN_EINVAL: a null pointer, N < 1, nb < 1, P not a multiple of 32 or of a stride. */
+int jn_yolox_loss(const float* raw_dev, const float* targets_dev, int N, int nb, int P, int stride0, int stride1,
+                  int stride2, int use_l1, float loss_scale, float* d_raw_dev, float* metrics_dev, float* scale_dev,
+                  void* stream);
 /* The per-image half of mAP-50 as Trainer.compute_detection_metrics reports it (src/trainer.py:188-248; COCO
  * protocol, one class): preds [B,Nmax,W >= 5] f32 with score in column 4 and pred_counts int32 [B]; targets
  * [B,Mmax,5] f32 (cls,x1,y1,x2,y2) with target_counts int32 [B] (Mmax = 0: no targets, both may be NULL).  Per image
@@ -403,7 +416,12 @@ int jn_detect(jn_ctx* ctx, const float* patches_dev, int N, float* boxes_dev,
  * targets_dev: [N, nb, 5] float32 = (class id, x1, y1, x2, y2) in patch pixels, zero rows = padding
  * (NeedleGeneralEnv.get_detection_batch layout).  loss_scale multiplies the loss before backward
  * (1 / gradient_accumulation).  metrics_dev: float32[8] = total_loss, iou_loss (x5), conf_loss, cls_loss, l1_loss,
- * num_fg (foreground anchors per ground-truth box). */
+ * num_fg (foreground anchors per ground-truth box).
+ * Box cap: a patch's boxes are its first ng rows, ng = the number of rows with a positive sum (as published); the loss
+ * kernel holds 8 of them in LDS, and a patch with ng > 8 is cut to its first 8 rows WITHOUT an error (the reference uses
+ * them all; num_fg then counts 8).  nb > 8 is accepted and exact as long as no patch has more than 8 such rows.  The
+ * Python wrappers refuse such a batch (ValueError); a C caller checks its own targets.  Holds for jn_detector_forward
+ * and jn_yolox_loss too. */
 int jn_detector_step(jn_ctx* ctx, const float* patches_dev, int N, const float* targets_dev, int nb,
                      float loss_scale, float* metrics_dev, void* stream);
 /* Detector autograd bridge — NeedleYOLOX.forward(patches, targets) (src/models/yolox.py:24-91) as the two halves of

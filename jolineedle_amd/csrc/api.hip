@@ -1566,7 +1566,7 @@ static int detector_forward_impl(jn_ctx* ctx, const float* patches_dev, int N, c
   dp.valid = false;
   if (!dp.dlogits) {
     if ((rc = dev_alloc(ctx, &dp.dlogits, (size_t)MB * A * 6))) return rc;
-    if ((rc = dev_alloc(ctx, &dp.acc, (size_t)16))) return rc;
+    if ((rc = dev_alloc(ctx, &dp.acc, (size_t)8 + (size_t)8 * MB))) return rc;
   }
   if (!ctx->det_labels || ctx->det_labels_rows < (size_t)N * nb) {
     if ((rc = dev_alloc(ctx, &ctx->det_labels, (size_t)MB * nb * 5))) return rc;
@@ -1581,7 +1581,7 @@ static int detector_forward_impl(jn_ctx* ctx, const float* patches_dev, int N, c
     if (op.kind != OP_PRED) continue;
     geo.a0[op.level] = op.anchor0; geo.H[op.level] = op.in.H; geo.W[op.level] = op.in.W; geo.stride[op.level] = op.stride;
   }
-  launch_yolox_loss(ctx->det_logits, ctx->det_labels, N, nb, geo, dp.dlogits, dp.acc, 1, loss_scale, metrics_dev, dp.acc + 8, s);
+  launch_yolox_loss(ctx->det_logits, ctx->det_labels, N, nb, geo, dp.dlogits, dp.acc + 8, 1, loss_scale, metrics_dev, dp.acc, s);
   JN_HIP(hipGetLastError());
   dp.patches = patches_dev; dp.N = N; dp.valid = true;
   return JN_OK;
@@ -1618,7 +1618,7 @@ int jn_detector_step(jn_ctx* ctx, const float* patches_dev, int N, const float* 
   hipStream_t s = (hipStream_t)stream;
   int rc = detector_forward_impl(ctx, patches_dev, N, targets_dev, nb, 0, 1, loss_scale, metrics_dev, s);
   if (rc) return rc;
-  rc = detector_backward_impl(ctx, 0, ctx->det_pass[0].acc + 8, s);
+  rc = detector_backward_impl(ctx, 0, ctx->det_pass[0].acc, s);
   ctx->det_pass[0].valid = false;          // the gradient buffers of the head were consumed
   return rc;
 }
@@ -1682,7 +1682,7 @@ int jn_detector_backward(jn_ctx* ctx, int pass, const float* dloss_dev, float sc
            "jn_detector_backward: pass %d has no forward to differentiate (none ran, or a later pass overwrote its activations)", pass);
   JN_HIP(hipSetDevice(ctx->cfg.device));
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(det_scale_kernel, dim3(1), dim3(1), 0, s, ctx->det_pass[pass].acc + 8, dloss_dev, scale, ctx->det_bwd_scale);
+  hipLaunchKernelGGL(det_scale_kernel, dim3(1), dim3(1), 0, s, ctx->det_pass[pass].acc, dloss_dev, scale, ctx->det_bwd_scale);
   int rc = detector_backward_impl(ctx, pass, ctx->det_bwd_scale, s);
   ctx->det_pass[pass].valid = false;       // one backward per forward (retain_graph is not offered)
   return rc;
@@ -1994,6 +1994,35 @@ int jn_merge_boxes(const float* boxes_dev, const int32_t* counts_dev, int B, int
                               (hipStream_t)stream) == 0,
            JN_EHIP, "jn_merge_boxes: %d bytes of LDS refused", 24 * Nmax);
   JN_HIP(hipGetLastError());
+  return JN_OK;
+}
+
+int jn_yolox_loss(const float* raw_dev, const float* targets_dev, int N, int nb, int P, int stride0, int stride1,
+                  int stride2, int use_l1, float loss_scale, float* d_raw_dev, float* metrics_dev, float* scale_dev,
+                  void* stream) {
+  JN_CHECK(raw_dev && targets_dev && d_raw_dev && metrics_dev && scale_dev, JN_EINVAL, "jn_yolox_loss: null argument");
+  JN_CHECK(N >= 1, JN_EINVAL, "jn_yolox_loss: N=%d", N);
+  JN_CHECK(nb >= 1, JN_EINVAL, "jn_yolox_loss: targets need at least one (padding) row per patch");
+  JN_CHECK(P >= 32 && P % 32 == 0, JN_EINVAL, "jn_yolox_loss: patch size %d is not a multiple of 32", P);
+  const int strides[3] = {stride0, stride1, stride2};
+  // the geometry detector_forward_impl reads off the three predictor ops: level l is (P / stride)^2 anchors behind level l - 1
+  DetGeom geo{};
+  for (int l = 0; l < 3; ++l) {
+    JN_CHECK(strides[l] >= 1 && P % strides[l] == 0 && (l == 0 || strides[l] > strides[l - 1]), JN_EINVAL,
+             "jn_yolox_loss: strides %d, %d, %d do not ascend or do not divide patch size %d", stride0, stride1, stride2, P);
+    geo.a0[l] = geo.A; geo.H[l] = geo.W[l] = P / strides[l]; geo.stride[l] = strides[l];
+    geo.A += geo.H[l] * geo.W[l];
+  }
+  hipStream_t s = (hipStream_t)stream;
+  float* work = nullptr;                                         // cxcywh labels, then the per-patch sums
+  const size_t n_lab = (size_t)N * nb * 5;
+  JN_HIP(hipMalloc((void**)&work, (n_lab + (size_t)8 * N) * sizeof(float)));
+  hipLaunchKernelGGL(labels_to_cxcywh_kernel, dim3((N * nb + 255) / 256), dim3(256), 0, s, targets_dev, work, N * nb);
+  launch_yolox_loss(raw_dev, work, N, nb, geo, d_raw_dev, work + n_lab, use_l1, loss_scale, metrics_dev, scale_dev, s);
+  const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(s);
+  (void)hipFree(work);
+  JN_HIP(e1);
+  JN_HIP(e2);
   return JN_OK;
 }
 

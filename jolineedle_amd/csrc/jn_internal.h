@@ -250,7 +250,7 @@ struct jn_ctx {
   // one entry per resident detector training pass (jn_detector_forward ... jn_detector_backward, api.hip)
   struct DetPass {
     float* dlogits = nullptr;     // [B][A][6] d loss / d raw (before the 1 / num_fg factor)
-    float* acc = nullptr;         // [8] loss accumulators, [8] scale (scale[0] = loss_scale / max(num_fg, 1))
+    float* acc = nullptr;         // [8] scale (scale[0] = loss_scale / max(num_fg, 1)), then [max_batch][8] per-patch loss sums
     const float* patches = nullptr; int N = 0;   // caller-owned input of the pass (the stem's weight gradient reads it)
     bool valid = false;           // cleared by every pass over the same workspace slot and by the backward
   };

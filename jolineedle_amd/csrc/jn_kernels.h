@@ -170,7 +170,8 @@ int launch_postprocess(const float* raw, int A, int N, float conf, float nms_thr
 // ---- detector training (kernels_detloss.hip) ------------------------------------------------------------
 struct DetGeom { int A; int a0[3]; int H[3]; int W[3]; int stride[3]; };
 // raw: [N][A][6] predictor outputs; labels [N][nb][5] = (class, cx, cy, w, h) floats, zero rows = padding;
-// d_raw gets d loss / d raw before the 1 / max(num_fg, 1) factor, which `scale[0]` carries to the predictor backward
+// d_raw gets d loss / d raw before the 1 / max(num_fg, 1) factor, which `scale[0]` carries to the predictor backward;
+// acc: [N][8] floats of scratch, one row of sums per patch (written, not accumulated: nothing to clear)
 int launch_yolox_loss(const float* raw, const float* labels, int N, int nb, const DetGeom& geo, float* d_raw, float* acc,
                       int use_l1, float loss_scale, float* metrics, float* scale, hipStream_t s);
 int launch_head_pred_bwd(const float* d_raw, const float* scale, const void* reg, int reg_ld, ChanTab rt, const void* cls,

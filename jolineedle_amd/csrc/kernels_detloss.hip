@@ -21,8 +21,13 @@ __device__ __forceinline__ f32x4 tf4_d(f32x4 z, f32x4 sc, f32x4 sh, f32x4 fl) {
   return r;
 }
 
+// A patch with more boxes than DL_MAXG is cut to its first DL_MAXG rows (the reference uses them all): documented at
+// jn_detector_step in include/jnroll.h, refused by the Python wrappers (yolox.py::check_box_cap).
 constexpr int DL_MAXG = 8;          // ground-truth boxes per patch
-constexpr int DL_MAXC = 256;        // candidate anchors per patch (27 per box)
+// A box has at most 3 x 3 cells x 3 levels = 27 candidates, so DL_MAXG boxes give at most 216: the cap is never reached
+// and the `pos < DL_MAXC` / min(DL_MAXC, ...) guards below never drop a candidate.  Raise it with DL_MAXG (27 per box).
+constexpr int DL_MAXC = 256;        // candidate anchors per patch
+static_assert(27 * DL_MAXG <= DL_MAXC, "the candidate cap must stay unreachable");
 
 __device__ __forceinline__ float sigm(float v) { return 1.0f / (1.0f + expf(-v)); }
 __device__ __forceinline__ float softplus(float v) { return fmaxf(v, 0.0f) + log1pf(expf(-fabsf(v))); }
@@ -37,7 +42,9 @@ __device__ __forceinline__ float iou_cxcywh(const DlBox& a, const DlBox& b) {
   return inter / (a.w * a.h + b.w * b.h - inter);
 }
 
-// acc: per-launch accumulators [0] iou loss, [1] obj loss, [2] cls loss, [3] l1 loss, [4] num_fg, [5] num_gt (floats)
+// acc [N][8]: the sums of patch n in row n, [0] iou loss, [1] obj loss, [2] cls loss, [3] l1 loss, [4] num_fg, [5] num_gt
+// (floats).  No atomics: lanes, waves and (in the finalize kernel) patches are summed in a fixed order, so the metrics
+// of a launch are the same bits every time, whatever order the waves and workgroups ran in.
 __global__ __launch_bounds__(256) void yolox_loss_kernel(const float* __restrict__ raw, const float* __restrict__ labels,
                                                          int nb, DetGeom geo, float* __restrict__ d_raw,
                                                          float* __restrict__ acc, int use_l1) {
@@ -48,7 +55,7 @@ __global__ __launch_bounds__(256) void yolox_loss_kernel(const float* __restrict
   __shared__ unsigned char match[DL_MAXG][DL_MAXC];
   __shared__ int c_gt[DL_MAXC];                 // matched gt of a foreground candidate, -1 otherwise
   __shared__ int s_ng, s_nc, wave_cnt[4];
-  __shared__ float part[6];
+  __shared__ float part[4][5];                  // per-wave sums of the five accumulated terms
   const int n = blockIdx.x, tid = threadIdx.x, A = geo.A;
   const float* r = raw + (long long)n * A * 6;
   float* dr = d_raw + (long long)n * A * 6;
@@ -66,7 +73,6 @@ __global__ __launch_bounds__(256) void yolox_loss_kernel(const float* __restrict
     }
     s_ng = ng; s_nc = 0;
   }
-  if (tid < 6) part[tid] = 0.0f;
   __syncthreads();
   const int ng = s_ng;
   auto level_of = [&](int a, int& gx, int& gy, float& st) {
@@ -222,16 +228,29 @@ __global__ __launch_bounds__(256) void yolox_loss_kernel(const float* __restrict
       }
     }
   }
-  atomicAdd(&part[0], l_iou); atomicAdd(&part[1], l_obj); atomicAdd(&part[2], l_cls); atomicAdd(&part[3], l_l1);
-  atomicAdd(&part[4], n_fg);
+  float v[5] = {l_iou, l_obj, l_cls, l_l1, n_fg};
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    for (int off = 32; off > 0; off >>= 1) v[j] += __shfl_xor(v[j], off);
+    if ((tid & 63) == 0) part[tid >> 6][j] = v[j];
+  }
   __syncthreads();
-  if (tid < 5) atomicAdd(&acc[tid], part[tid]);
-  if (tid == 5) atomicAdd(&acc[5], (float)ng);
+  float* out = acc + (long long)n * 8;
+  if (tid < 5) out[tid] = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
+  if (tid == 5) out[5] = (float)ng;
 }
 
 // metrics[0..5] = total, 5 * iou, obj, cls, l1, num_fg / max(num_gts, 1); scale[0] = loss_scale / max(num_fg, 1)
-__global__ void yolox_loss_finalize_kernel(const float* __restrict__ acc, float loss_scale, float* __restrict__ metrics,
+__global__ void yolox_loss_finalize_kernel(const float* __restrict__ rows, int N, float loss_scale, float* __restrict__ metrics,
                                            float* __restrict__ scale) {
+  __shared__ float acc[6];
+  if (threadIdx.x < 6) {                        // one thread per term, patches in order
+    float t = 0.0f;
+    for (int n = 0; n < N; ++n) t += rows[(long long)n * 8 + threadIdx.x];
+    acc[threadIdx.x] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
   const float den = fmaxf(acc[4], 1.0f);
   const float iou = 5.0f * acc[0] / den, obj = acc[1] / den, cls = acc[2] / den, l1 = acc[3] / den;
   metrics[0] = iou + obj + cls + l1; metrics[1] = iou; metrics[2] = obj; metrics[3] = cls; metrics[4] = l1;
@@ -241,9 +260,8 @@ __global__ void yolox_loss_finalize_kernel(const float* __restrict__ acc, float 
 
 int launch_yolox_loss(const float* raw, const float* labels, int N, int nb, const DetGeom& geo, float* d_raw, float* acc,
                       int use_l1, float loss_scale, float* metrics, float* scale, hipStream_t s) {
-  (void)hipMemsetAsync(acc, 0, 8 * sizeof(float), s);
   hipLaunchKernelGGL(yolox_loss_kernel, dim3(N), dim3(256), 0, s, raw, labels, nb, geo, d_raw, acc, use_l1);
-  hipLaunchKernelGGL(yolox_loss_finalize_kernel, dim3(1), dim3(1), 0, s, acc, loss_scale, metrics, scale);
+  hipLaunchKernelGGL(yolox_loss_finalize_kernel, dim3(1), dim3(64), 0, s, acc, N, loss_scale, metrics, scale);
   return 0;
 }
 

@@ -9,6 +9,46 @@ from . import _lib
 from ._lib import check, ptr
 
 LOSS_NAMES = ("total_loss", "iou_loss", "conf_loss", "cls_loss", "l1_loss", "num_fg")
+MAX_BOXES_PER_PATCH = 8          # DL_MAXG of csrc/kernels_detloss.hip: boxes of one patch the loss kernel holds in LDS
+
+
+def check_box_cap(targets: torch.Tensor) -> None:
+    """Refuses targets [N, nb, 5] (class, x1, y1, x2, y2) with more boxes in one patch than the loss kernel holds: the kernel
+    would cut the patch to its first ``MAX_BOXES_PER_PATCH`` rows without a word, where the reference uses every row.  A
+    box is a row whose (class, cx, cy, w, h) sum is positive, as the kernel counts them.  With nb <= 8 nothing is launched
+    or read back; above, one reduction and one readback."""
+    if targets.shape[1] <= MAX_BOXES_PER_PATCH:
+        return
+    t = targets
+    rows = t[..., 0] + 0.5 * (t[..., 1] + t[..., 3]) + 0.5 * (t[..., 2] + t[..., 4]) + (t[..., 3] - t[..., 1]) + (t[..., 4] - t[..., 2])
+    worst, patch = (rows > 0).sum(dim=1).max(dim=0)
+    worst, patch = int(worst), int(patch)
+    if worst > MAX_BOXES_PER_PATCH:
+        raise ValueError(f"patch {patch} holds {worst} ground-truth boxes; the detector loss takes at most "
+                         f"{MAX_BOXES_PER_PATCH} per patch")
+
+
+def yolox_loss(raw: torch.Tensor, targets: torch.Tensor, patch_size: int, strides=(8, 16, 32), use_l1: bool = True,
+               loss_scale: float = 1.0):
+    """The detector's SimOTA loss on given predictor outputs (``jn_yolox_loss``, no engine): raw [N, A, 6] and targets
+    [N, nb, 5] = (class, x1, y1, x2, y2) on the device.  Returns (d_raw [N, A, 6] = d loss / d raw before the
+    1 / max(num_fg, 1) factor, metrics f32[8] in the order of ``LOSS_NAMES``, scale f32[1] = loss_scale / max(num_fg, 1))."""
+    assert raw.is_cuda and raw.dim() == 3 and raw.shape[2] == 6 and targets.dim() == 3 and targets.shape[2] == 5
+    assert targets.shape[0] == raw.shape[0]
+    dev = raw.device
+    raw = raw.to(torch.float32).contiguous()
+    t = targets.to(dev, torch.float32).contiguous()
+    N, A, nb = raw.shape[0], raw.shape[1], t.shape[1]
+    if all(int(s) > 0 and patch_size % int(s) == 0 for s in strides):
+        assert A == sum((patch_size // int(s)) ** 2 for s in strides), (A, patch_size, strides)
+    check_box_cap(t)
+    d_raw = torch.empty_like(raw)
+    metrics = torch.zeros(8, device=dev)
+    scale = torch.zeros(1, device=dev)
+    check(_lib.load_library().jn_yolox_loss(ptr(raw), ptr(t), N, nb, int(patch_size), *(int(s) for s in strides), int(bool(use_l1)),
+                                            float(loss_scale), ptr(d_raw), ptr(metrics), ptr(scale), _lib.current_stream(dev)),
+          "jn_yolox_loss")
+    return d_raw, metrics, scale
 
 
 class _DetectorGraph(torch.autograd.Function):
@@ -53,6 +93,9 @@ class NeedleYOLOX:
     as written, in either order with the policy loss's own backward.  The other entries of ``losses`` are values
     (the reference's loops only log them).  ``predict=False`` skips the eval head / maps (the loops discard them).
 
+    At most ``MAX_BOXES_PER_PATCH`` = 8 boxes per patch: ``targets`` may be wider (padding rows), but a patch with more
+    real rows raises ``ValueError`` (the loss kernel would drop the rest, the reference uses them all).
+
     A detection batch larger than ``max_batch`` is fed in chunks of ``max_batch``, each weighted by its share of the
     patches (deviation: BatchNorm statistics and the 1 / num_fg normalisation are per chunk); every chunk keeps its own
     workspace until the backward.
@@ -88,6 +131,7 @@ class NeedleYOLOX:
         # ---- loss branch + eval head (src/models/yolox.py:58-91) ----
         assert targets.shape[0] == N and targets.shape[-1] >= 5
         t = targets[..., :5].to(g.device, torch.float32).contiguous()
+        check_box_cap(t)
         graph = torch.is_grad_enabled()
         if graph:
             g.bind_flat()
@@ -133,6 +177,7 @@ class NeedleYOLOX:
         assert targets.shape[0] == N and targets.shape[-1] >= 5
         x = patches.to(g.device, torch.float32).contiguous()
         t = targets[..., :5].to(g.device, torch.float32).contiguous()
+        check_box_cap(t)
         tot = {k: torch.zeros((), device=g.device) for k in LOSS_NAMES}
         for i in range(0, N, g.max_batch):
             n = min(g.max_batch, N - i)

@@ -251,54 +251,63 @@ class YOLOXHead(nn.Module):
         (loss, 5 * iou_loss, obj_loss, cls_loss, l1_loss, num_fg / max(num_gts, 1))."""
         assert self.num_classes == 1
         raw, hw = self.raw_logits(feats)
-        B, A, _ = raw.shape
-        grids, svec = [], []
-        for (h, w), s in zip(hw, self.strides):
-            yv, xv = torch.meshgrid(torch.arange(h), torch.arange(w), indexing="ij")
-            grids.append(torch.stack((xv, yv), 2).view(-1, 2))
-            svec.append(torch.full((h * w,), float(s)))
-        grid = torch.cat(grids, 0).to(raw.dtype)
-        stride = torch.cat(svec, 0).to(raw.dtype)
-        xy = (raw[..., 0:2] + grid) * stride[:, None]
-        wh = torch.exp(raw[..., 2:4]) * stride[:, None]
-        boxes = torch.cat([xy, wh], -1)                       # decoded cxcywh predictions (with grad)
-        obj, cls = raw[..., 4], raw[..., 5]
-        nlabel = (labels.sum(dim=2) > 0).sum(dim=1)            # rows with a positive sum count as objects
-        loss_iou = raw.new_zeros(())
-        loss_cls = raw.new_zeros(())
-        loss_l1 = raw.new_zeros(())
-        obj_target = torch.zeros((B, A), dtype=raw.dtype)
-        num_fg, num_gts = 0.0, 0.0
-        assign = []
-        for b in range(B):
-            ng = int(nlabel[b])
-            num_gts += ng
-            if ng == 0:
-                assign.append(None)
-                continue
-            gt = labels[b, :ng, 1:5].to(raw.dtype)            # the FIRST ng rows (as published, even if a zero row precedes)
-            with torch.no_grad():
-                fg, matched, ious = simota_assign(gt, boxes[b].detach(), obj[b].detach(), cls[b].detach(), grid, stride)
-            assign.append((fg, matched, ious))
-            nf = int(fg.sum())
-            num_fg += nf
-            if nf == 0:
-                continue
-            obj_target[b, fg] = 1.0
-            tgt = gt[matched]
-            pb = boxes[b][fg]
-            loss_iou = loss_iou + iou_loss(pb, tgt).sum()
-            loss_cls = loss_cls + F.binary_cross_entropy_with_logits(cls[b][fg], ious, reduction="sum")
-            if use_l1:
-                l1t = torch.stack([tgt[:, 0] / stride[fg] - grid[fg, 0], tgt[:, 1] / stride[fg] - grid[fg, 1],
-                                   torch.log(tgt[:, 2] / stride[fg] + 1e-8), torch.log(tgt[:, 3] / stride[fg] + 1e-8)], 1)
-                loss_l1 = loss_l1 + (raw[b][fg][:, :4] - l1t).abs().sum()
-        den = max(num_fg, 1.0)
-        loss_obj = F.binary_cross_entropy_with_logits(obj, obj_target, reduction="sum") / den
-        loss_iou, loss_cls, loss_l1 = loss_iou / den, loss_cls / den, loss_l1 / den
-        total = 5.0 * loss_iou + loss_obj + loss_cls + loss_l1
-        self.last_assignment = assign
-        return total, 5.0 * loss_iou, loss_obj, loss_cls, loss_l1, num_fg / max(num_gts, 1.0)
+        out, self.last_assignment = losses_from_raw(raw, hw, labels, use_l1, self.strides)
+        return out
+
+
+def losses_from_raw(raw: torch.Tensor, hw, labels: torch.Tensor, use_l1: bool = True, strides=(8, 16, 32)):
+    """get_losses of the published head from the raw predictor outputs: raw [B, A, 6] (reg 4, obj logit, cls logit; anchors
+    level by level, row-major), hw = the (h, w) of every level, labels [B, nb, 5] = (class, cx, cy, w, h), zero rows =
+    padding.  Works in the dtype of `raw`.  Returns (the reference's tuple (loss, 5 * iou_loss, obj_loss, cls_loss, l1_loss,
+    num_fg / max(num_gts, 1)), assignment): per patch None (no box) or (foreground mask [A], matched box of every
+    foreground anchor, its IoU with that box)."""
+    B, A, _ = raw.shape
+    grids, svec = [], []
+    for (h, w), s in zip(hw, strides):
+        yv, xv = torch.meshgrid(torch.arange(h), torch.arange(w), indexing="ij")
+        grids.append(torch.stack((xv, yv), 2).view(-1, 2))
+        svec.append(torch.full((h * w,), float(s)))
+    grid = torch.cat(grids, 0).to(raw.dtype)
+    stride = torch.cat(svec, 0).to(raw.dtype)
+    xy = (raw[..., 0:2] + grid) * stride[:, None]
+    wh = torch.exp(raw[..., 2:4]) * stride[:, None]
+    boxes = torch.cat([xy, wh], -1)                       # decoded cxcywh predictions (with grad)
+    obj, cls = raw[..., 4], raw[..., 5]
+    nlabel = (labels.sum(dim=2) > 0).sum(dim=1)            # rows with a positive sum count as objects
+    loss_iou = raw.new_zeros(())
+    loss_cls = raw.new_zeros(())
+    loss_l1 = raw.new_zeros(())
+    obj_target = torch.zeros((B, A), dtype=raw.dtype)
+    num_fg, num_gts = 0.0, 0.0
+    assign = []
+    for b in range(B):
+        ng = int(nlabel[b])
+        num_gts += ng
+        if ng == 0:
+            assign.append(None)
+            continue
+        gt = labels[b, :ng, 1:5].to(raw.dtype)            # the FIRST ng rows (as published, even if a zero row precedes)
+        with torch.no_grad():
+            fg, matched, ious = simota_assign(gt, boxes[b].detach(), obj[b].detach(), cls[b].detach(), grid, stride)
+        assign.append((fg, matched, ious))
+        nf = int(fg.sum())
+        num_fg += nf
+        if nf == 0:
+            continue
+        obj_target[b, fg] = 1.0
+        tgt = gt[matched]
+        pb = boxes[b][fg]
+        loss_iou = loss_iou + iou_loss(pb, tgt).sum()
+        loss_cls = loss_cls + F.binary_cross_entropy_with_logits(cls[b][fg], ious, reduction="sum")
+        if use_l1:
+            l1t = torch.stack([tgt[:, 0] / stride[fg] - grid[fg, 0], tgt[:, 1] / stride[fg] - grid[fg, 1],
+                               torch.log(tgt[:, 2] / stride[fg] + 1e-8), torch.log(tgt[:, 3] / stride[fg] + 1e-8)], 1)
+            loss_l1 = loss_l1 + (raw[b][fg][:, :4] - l1t).abs().sum()
+    den = max(num_fg, 1.0)
+    loss_obj = F.binary_cross_entropy_with_logits(obj, obj_target, reduction="sum") / den
+    loss_iou, loss_cls, loss_l1 = loss_iou / den, loss_cls / den, loss_l1 / den
+    total = 5.0 * loss_iou + loss_obj + loss_cls + loss_l1
+    return (total, 5.0 * loss_iou, loss_obj, loss_cls, loss_l1, num_fg / max(num_gts, 1.0)), assign
 
 
 def pairwise_iou_cxcywh(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
