@@ -238,6 +238,20 @@ int jn_merge_boxes(const float* boxes_dev, const int32_t* counts_dev, int B, int
 int jn_yolox_loss(const float* raw_dev, const float* targets_dev, int N, int nb, int P, int stride0, int stride1,
                   int stride2, int use_l1, float loss_scale, float* d_raw_dev, float* metrics_dev, float* scale_dev,
                   void* stream);
+/* The detector's threshold / sort / NMS stage on given decoded predictions, context-free: what jn_detect runs behind
+ * the head (the published postprocess with class_agnostic = True and one class, then clamp_(0, P - 1);
+ * src/models/yolox.py:80-113, restated in oracle/yolox_ref.py::postprocess).  raw_dev [N,A,6] f32 = decoded rows
+ * (cx, cy, w, h, obj, cls), which is what jn_detect hands back as raw_dev; A is free.  Per patch: keep the anchors with
+ * obj * cls >= conf_threshold, order them by score descending (ties to the lower anchor index), greedy NMS (a box is
+ * suppressed when its IoU with a kept box is > nms_threshold), clamp the edges to [0, clamp_max] AFTER the NMS.  Two
+ * silent caps: only the first 2048 passing anchors in index order enter the sort, and only the first max_out survivors
+ * in score order are written.  boxes_dev [N,max_out,7] = (x1, y1, x2, y2, obj, cls, 0) and counts_dev int32 [N] exactly
+ * as jn_detect writes them; rows at or beyond counts[n] are left alone.  stats_dev (int32 [N,2], may be NULL): column 0
+ * = the anchors with score >= conf_threshold before the 2048 cap, column 1 = the NMS survivors before max_out; a caller
+ * sees a cap was reached from stats[n][0] > 2048 or stats[n][1] > max_out.  Launches on `stream` and does not wait.
+ * Inputs are finite with w, h >= 0.  JN_EINVAL: a null raw / boxes / counts, N < 1, A < 1, max_out < 1. */
+int jn_postprocess(const float* raw_dev, int N, int A, float conf_threshold, float nms_threshold, float clamp_max,
+                   int max_out, float* boxes_dev, int32_t* counts_dev, int32_t* stats_dev, void* stream);
 /* The per-image half of mAP-50 as Trainer.compute_detection_metrics reports it (src/trainer.py:188-248; COCO
  * protocol, one class): preds [B,Nmax,W >= 5] f32 with score in column 4 and pred_counts int32 [B]; targets
  * [B,Mmax,5] f32 (cls,x1,y1,x2,y2) with target_counts int32 [B] (Mmax = 0: no targets, both may be NULL).  Per image

@@ -1501,7 +1501,7 @@ static int detect_impl(jn_ctx* ctx, const StemSrc& ss, int N, float* boxes_dev, 
     JN_HIP(hipMemcpyAsync(raw_dev, ctx->det_raw, (size_t)N * net.n_anchors * 6 * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (boxes_dev && counts_dev)
     launch_postprocess(ctx->det_raw, net.n_anchors, N, ctx->cfg.det_conf_threshold, ctx->cfg.det_nms_threshold,
-                       (float)(ctx->cfg.patch_size - 1), boxes_dev, counts_dev, ctx->cfg.max_det_per_patch, s);
+                       (float)(ctx->cfg.patch_size - 1), boxes_dev, counts_dev, ctx->cfg.max_det_per_patch, nullptr, s);
   JN_HIP(hipGetLastError());
   return JN_OK;
 }
@@ -1651,7 +1651,7 @@ static int detector_eval_head(jn_ctx* ctx, int pass, float* boxes_dev, int32_t* 
   net.eval_tab_dirty = true;               // slot 0's FPN entries hold batch statistics now: rebuilt before the next eval pass
   if (rc) return rc;
   launch_postprocess(ctx->det_raw, net.n_anchors, N, ctx->cfg.det_conf_threshold, ctx->cfg.det_nms_threshold,
-                     (float)(ctx->cfg.patch_size - 1), boxes_dev, counts_dev, ctx->cfg.max_det_per_patch, s);
+                     (float)(ctx->cfg.patch_size - 1), boxes_dev, counts_dev, ctx->cfg.max_det_per_patch, nullptr, s);
   JN_HIP(hipGetLastError());
   return JN_OK;
 }
@@ -2023,6 +2023,17 @@ int jn_yolox_loss(const float* raw_dev, const float* targets_dev, int N, int nb,
   (void)hipFree(work);
   JN_HIP(e1);
   JN_HIP(e2);
+  return JN_OK;
+}
+
+int jn_postprocess(const float* raw_dev, int N, int A, float conf_threshold, float nms_threshold, float clamp_max,
+                   int max_out, float* boxes_dev, int32_t* counts_dev, int32_t* stats_dev, void* stream) {
+  JN_CHECK(raw_dev && boxes_dev && counts_dev, JN_EINVAL, "jn_postprocess: null argument");
+  JN_CHECK(N >= 1 && A >= 1, JN_EINVAL, "jn_postprocess: N=%d A=%d", N, A);
+  JN_CHECK(max_out >= 1, JN_EINVAL, "jn_postprocess: max_out=%d", max_out);
+  launch_postprocess(raw_dev, A, N, conf_threshold, nms_threshold, clamp_max, boxes_dev, counts_dev, max_out, stats_dev,
+                     (hipStream_t)stream);
+  JN_HIP(hipGetLastError());
   return JN_OK;
 }
 

@@ -164,8 +164,9 @@ int launch_head_pred(const void* reg, int reg_ld, ChanTab rt, const void* cls, i
                      int N, hipStream_t s, int logits_only = 0);
 int launch_det_scatter(const float* boxes, const int* counts, float* out_boxes, int* out_counts, int B, int cols, int col,
                        int K, const int* skip_flag, int skip_when, hipStream_t s);
+// stats: nullable int [N][2] = (anchors with score >= conf before the 2048-candidate cap, NMS survivors before max_out)
 int launch_postprocess(const float* raw, int A, int N, float conf, float nms_thr, float clamp_max, float* boxes,
-                       int* counts, int max_out, hipStream_t s);
+                       int* counts, int max_out, int* stats, hipStream_t s);
 
 // ---- detector training (kernels_detloss.hip) ------------------------------------------------------------
 struct DetGeom { int A; int a0[3]; int H[3]; int W[3]; int stride[3]; };

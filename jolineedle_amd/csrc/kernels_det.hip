@@ -1387,19 +1387,21 @@ int launch_head_pred(const void* reg, int reg_ld, ChanTab rt, const void* cls, i
 // postprocess (class-agnostic, one class): cxcywh -> xyxy, keep obj*cls >= conf, sort by score
 // (descending, ties by anchor index), greedy NMS (IoU > thr suppressed), clamp to [0, P-1].
 // One workgroup per patch; candidates live in LDS (cap DET_CAP, lowest anchor indices kept).
+// stats (nullable) [N][2]: anchors with score >= conf before the DET_CAP cut, NMS survivors before the max_out cut.
 // ------------------------------------------------------------------------------------
 constexpr int DET_CAP = 2048;
 
 __global__ __launch_bounds__(256) void postprocess_kernel(const float* __restrict__ raw, int A, float conf, float nms_thr,
                                                           float clamp_max, float* __restrict__ boxes,
-                                                          int* __restrict__ counts, int max_out) {
+                                                          int* __restrict__ counts, int max_out,
+                                                          int* __restrict__ stats) {
   __shared__ float sc[DET_CAP];
   __shared__ int id[DET_CAP];
   __shared__ unsigned char dead[DET_CAP];
-  __shared__ int s_n, s_keep;
+  __shared__ int s_n, s_keep, s_pass;
   const int n = blockIdx.x, tid = threadIdx.x;
   const float* r = raw + (long long)n * A * 6;
-  if (tid == 0) { s_n = 0; s_keep = 0; }
+  if (tid == 0) { s_n = 0; s_keep = 0; s_pass = 0; }
   __syncthreads();
   // ordered compaction, chunk by chunk so that lower anchor indices win the cap
   for (int base = 0; base < A; base += 256) {
@@ -1417,7 +1419,11 @@ __global__ __launch_bounds__(256) void postprocess_kernel(const float* __restric
     off += __popcll(m & ((1ull << lane) - 1ull));
     if (ok && off < DET_CAP) { sc[off] = score; id[off] = a; }
     __syncthreads();
-    if (tid == 0) s_n = min(DET_CAP, s_n + wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3]);
+    if (tid == 0) {
+      const int passed = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+      s_n = min(DET_CAP, s_n + passed);
+      s_pass += passed;
+    }
     __syncthreads();
   }
   const int cnt = s_n;
@@ -1469,13 +1475,16 @@ __global__ __launch_bounds__(256) void postprocess_kernel(const float* __restric
     }
     __syncthreads();
   }
-  if (tid == 0) counts[n] = min(s_keep, max_out);
+  if (tid == 0) {
+    counts[n] = min(s_keep, max_out);
+    if (stats) { stats[n * 2] = s_pass; stats[n * 2 + 1] = s_keep; }
+  }
 }
 
 int launch_postprocess(const float* raw, int A, int N, float conf, float nms_thr, float clamp_max, float* boxes,
-                       int* counts, int max_out, hipStream_t s) {
+                       int* counts, int max_out, int* stats, hipStream_t s) {
   hipLaunchKernelGGL(postprocess_kernel, dim3(N), dim3(256), 0, s, raw, A, conf, nms_thr, clamp_max, boxes, counts,
-                     max_out);
+                     max_out, stats);
   return 0;
 }
 
