@@ -473,6 +473,33 @@ int jn_optimizer_step_group(jn_ctx* ctx, int group, float lr, float weight_decay
 int jn_rollout(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev,
                const int64_t* start_positions_dev, uint64_t seed, int do_detection,
                int stop_early, const jn_rollout_out* out, void* stream);
+/* 1-D token positions of the following rollouts.  by_token = 0 (the default): every new token sits at position 0, the
+ * recurrent forward of src/models/gpt.py:431-449 that a REINFORCE-trained policy saw.  by_token != 0: the token of
+ * step t sits at position t (row t of the sinusoid table with decoder_pos_encoding, else wpe[t]) — the last row of
+ * the full-prefix forward (gpt.py:331-354) that --no-recurrent-embedding selects in ReinforceTrainer.rollout
+ * (gpt.py:427-428) and that SupervisedTrainer.test_model_on_env runs at every step (src/supervised.py:279-405); exact
+ * in eval mode (running BatchNorm statistics, causal attention), everything else in the step unchanged.  Sticky until
+ * set again.  While it is set: a rollout with a learned table and max_ep_len > pos_emb_size fails with JN_EINVAL (the
+ * reference's nn.Embedding raises there), and jn_reinforce_forward / jn_reinforce_step fail with JN_ESTATE (train mode
+ * re-encodes the whole prefix with BatchNorm statistics over B * (t + 1) patches, which one step cannot reproduce). */
+int jn_set_rollout_positions(jn_ctx* ctx, int by_token);
+/* The teacher's action set of B states, context-free (NeedleSimpleEnv.build_keypoints_trajectory and move_towards,
+ * src/env/simple_env.py:590-629, 84-125).  positions_dev int64 [B,2] (y, x); visited_dev, targets_dev uint8
+ * [B,Gh,Gw] (non-zero = set).  Per agent: the remaining targets are targets & ~visited, N = those at the minimum
+ * Manhattan distance |dy| + |dx|, and sets_dev[b] (uint8 [B]) gets bit a for every action a = move_towards(position,
+ * q), q in N, actions 0..7 in the Action order — the set the reference draws one member of with random.choice.  STOP
+ * (a remaining target under the agent) sets no bit; no remaining target gives 0.  Launches on `stream`, does not wait.
+ * JN_EINVAL: a null pointer, B, Gh or Gw < 1. */
+int jn_teacher_actions(const int64_t* positions_dev, const uint8_t* visited_dev, const uint8_t* targets_dev, int B, int Gh,
+                       int Gw, uint8_t* sets_dev, void* stream);
+/* Arms the following rollouts of `ctx` with that teacher (the per-step `best_action` that test_model_on_env compares
+ * each chosen action with, src/supervised.py:279-405): before the decision of step t, the set of the state that
+ * decision sees (position and visited patches before the step) goes to sets_dev[b * T + t] (uint8 [B,T], T =
+ * max_ep_len), on the rollout's stream and under the step's own early-stop flag; columns past the executed steps are
+ * 0.  targets_dev: NULL = the env's own bbox masks, else a uint8 [B,Gh,Gw] grid on the env's canvas (cells outside a
+ * ragged extent must be 0).  Both buffers are the caller's and must outlive the rollouts.  sets_dev = NULL disarms.
+ * Independent of jn_set_rollout_positions. */
+int jn_set_rollout_teacher(jn_ctx* ctx, const uint8_t* targets_dev, uint8_t* sets_dev);
 /* Number of steps S the last rollout executed (reference tensor width).  Synchronises
  * on `stream`. */
 int jn_rollout_steps(jn_ctx* ctx, int* n_steps, void* stream);

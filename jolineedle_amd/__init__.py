@@ -19,7 +19,7 @@ from .augment import DetectionAugment  # noqa: F401
 from .checkpoint import (save_config, config_from_file, save_checkpoint, load_checkpoint,  # noqa: F401
                          load_detection_checkpoint)
 from .infer import infer_images, plan_chunks, pad_to_patch_multiple, load_bboxes  # noqa: F401
-from .trajectory import NeedleSimpleEnv  # noqa: F401
+from .trajectory import NeedleSimpleEnv, teacher_action_sets, teacher_action_sets_device  # noqa: F401
 from .views import ImageViews  # noqa: F401
 from .detection import (patch_bboxes2full_image, rollout_boxes_to_image, merge_boxes, merge_boxes_batched,  # noqa: F401
                         compute_detection_metrics, detection_targets, rollout_boxes_packed, pack_boxes, unpack_boxes,

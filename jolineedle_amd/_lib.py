@@ -132,6 +132,9 @@ SIGNATURES = {
     "jn_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "jn_rollout": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int,
                              C.POINTER(JnRolloutOut), C.c_void_p]),
+    "jn_set_rollout_positions": (C.c_int, [C.c_void_p, C.c_int]),
+    "jn_teacher_actions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "jn_set_rollout_teacher": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "jn_rollout_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "jn_last_timing": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "jn_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),

@@ -2110,6 +2110,17 @@ static int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev
   const jn_config& c = ctx->cfg;
   const EnvState& e = ctx->env;
   const int B = e.B, T = e.T, C = c.n_embd, P = c.patch_size, nA = c.n_actions;
+  const bool by_token = ctx->pos_by_token;
+  // gpt.py:427-428 in train mode re-encodes the whole prefix, BatchNorm statistics over B * (t + 1) patches: not what the
+  // per-step workspace holds
+  JN_CHECK(!(by_token && train), JN_ESTATE,
+           "sequence token positions (jn_set_rollout_positions) are for eval rollouts: in train mode the reference "
+           "re-encodes the whole prefix at every step with BatchNorm statistics over B*(t+1) patches");
+  JN_CHECK(!by_token || c.decoder_pos_encoding || T <= c.pos_emb_size, JN_EINVAL,
+           "sequence token positions: max_ep_len %d exceeds the %d rows of the learned position table (pos_emb_size)", T,
+           c.pos_emb_size);
+  uint8_t* const tsets = ctx->teacher_sets;
+  const uint8_t* const ttargets = ctx->teacher_targets ? ctx->teacher_targets : e.bbox_masks;
   ctx->train_out_valid = false;       // every rollout restarts n_done / the env state the REINFORCE backward reads
   if (train) ctx->sup_valid = false;  // ... and a train-mode one the per-token buffers the supervised backward reads
   RolloutBuffers r{out->rewards_dev, out->returns_dev, out->logprobs_dev, out->entropies_dev, out->masks_dev,
@@ -2125,6 +2136,7 @@ static int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev
   if (r.actions) JN_HIP(hipMemsetAsync(r.actions, 0, (size_t)B * T * sizeof(int64_t), s));
   if (r.logits) JN_HIP(hipMemsetAsync(r.logits, 0, (size_t)B * T * nA * sizeof(float), s));
   if (r.final_emb) JN_HIP(hipMemsetAsync(r.final_emb, 0, (size_t)B * (T + 1) * C * sizeof(float), s));
+  if (tsets) JN_HIP(hipMemsetAsync(tsets, 0, (size_t)B * T, s));
 
   if (ctx->ev[0]) JN_HIP(hipEventRecord(ctx->ev[0], s));
   EnvPtrs ep = env_ptrs(ctx);
@@ -2234,6 +2246,8 @@ static int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev
   }
   for (int t = 0; t < T; ++t) {
     const int* flag = stop_early ? ctx->n_done + t : nullptr;
+    // the teacher's opinion of the state this step's decision sees (src/supervised.py:279-405 compares against it)
+    if (tsets) launch_teacher_sets(e.positions, e.visited, ttargets, tsets + t, T, B, e.Gh, e.Gw, flag, B, s);
     if (!c.no_patch_emb) {
       if (ctx->profiling) JN_HIP(hipEventRecord(ctx->conv_ev[2 * t], s));
       if ((rc = run_net(ctx, ctx->enc_net, B, vm ? stage_stem_src(e, P, t) : ss, train ? t + 1 : 0, train, flag, B, s))) return rc;
@@ -2251,7 +2265,9 @@ static int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev
     a.layers = x.layers_dev; a.emb_part = x.emb_part; a.KS = x.KS; a.efpn_lin_b = g.efpn_lin_b;
     a.kcache = ctx->kcache; a.vcache = ctx->vcache; a.prev_action = ctx->prev_action; a.cache_len = ctx->cache_len;
     a.step = t; a.mode = mode; a.forced = forced_actions_dev; a.seed = seed;
-    a.src_mode = GPT_SRC_ENV; a.pos_index = 0; a.emb_stride = T + 1;
+    // recurrent: every new token at 1-D position 0 (gpt.py:431-449); by token: position t, the last row of the
+    // reference's full-prefix forward (gpt.py:331-354, 427-428)
+    a.src_mode = GPT_SRC_ENV; a.pos_index = by_token ? t : 0; a.emb_stride = T + 1;
     a.env = ep; a.out = r; a.n_done = ctx->n_done;
     a.skip_flag = flag; a.skip_when = B;
     a.tok_emb_out = train ? ctx->tok_emb_train : nullptr;
@@ -2277,6 +2293,29 @@ static int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev
 int jn_rollout(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const int64_t* start_positions_dev,
                uint64_t seed, int do_detection, int stop_early, const jn_rollout_out* out, void* stream) {
   return rollout_impl(ctx, mode, forced_actions_dev, start_positions_dev, seed, do_detection, stop_early, out, 0, stream);
+}
+
+int jn_set_rollout_positions(jn_ctx* ctx, int by_token) {
+  JN_CHECK(ctx, JN_EINVAL, "null ctx");
+  ctx->pos_by_token = by_token != 0;
+  return JN_OK;
+}
+
+int jn_set_rollout_teacher(jn_ctx* ctx, const uint8_t* targets_dev, uint8_t* sets_dev) {
+  JN_CHECK(ctx, JN_EINVAL, "null ctx");
+  ctx->teacher_sets = sets_dev;
+  ctx->teacher_targets = sets_dev ? targets_dev : nullptr;
+  return JN_OK;
+}
+
+int jn_teacher_actions(const int64_t* positions_dev, const uint8_t* visited_dev, const uint8_t* targets_dev, int B, int Gh,
+                       int Gw, uint8_t* sets_dev, void* stream) {
+  JN_CHECK(positions_dev && visited_dev && targets_dev && sets_dev, JN_EINVAL, "jn_teacher_actions: null argument");
+  JN_CHECK(B >= 1 && Gh >= 1 && Gw >= 1 && (long long)Gh * Gw <= INT32_MAX, JN_EINVAL, "jn_teacher_actions: B=%d grid %dx%d", B,
+           Gh, Gw);
+  launch_teacher_sets(positions_dev, visited_dev, targets_dev, sets_dev, 1, B, Gh, Gw, nullptr, 0, (hipStream_t)stream);
+  JN_HIP(hipGetLastError());
+  return JN_OK;
 }
 
 int jn_rollout_steps(jn_ctx* ctx, int* n_steps, void* stream);

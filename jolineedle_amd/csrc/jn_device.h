@@ -9,6 +9,8 @@ namespace jnr {
 // src/env/common.py:17-27 — (dy, dx) per action id LEFT..STOP.
 __device__ __constant__ const int8_t kActionDy[9] = {0, 0, -1, 1, -1, -1, 1, 1, 0};
 __device__ __constant__ const int8_t kActionDx[9] = {-1, 1, 0, 0, -1, 1, -1, 1, 0};
+// The inverse (move_towards, src/env/simple_env.py:84-125): action id at [(sign dy + 1) * 3 + sign dx + 1].
+__device__ __constant__ const int8_t kTowards[9] = {4, 2, 5, 0, 8, 1, 6, 3, 7};
 
 // Philox4x32-10 keyed by seed, counter (a, b, c, d) -> 4 x u32.
 __device__ inline uint4 philox4x32(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {

@@ -300,6 +300,9 @@ int launch_rollout_begin(const EnvPtrs& e, const RolloutBuffers& r, int64_t* pre
                          int32_t* n_done, hipStream_t s);
 int launch_rollout_epilogue(const RolloutBuffers& r, const int32_t* n_done, int B, int T, int stop_early,
                             hipStream_t s);
+// the teacher's action set of every agent's state (jnroll.h: jn_teacher_actions); sets[b * set_stride], one wave per agent
+int launch_teacher_sets(const int64_t* positions, const uint8_t* visited, const uint8_t* targets, uint8_t* sets,
+                        long long set_stride, int B, int Gh, int Gw, const int* skip_flag, int skip_when, hipStream_t s);
 // kernels_ragged.hip: patch_bboxes2full_image for a whole batch (jnroll.h: jn_rollout_boxes_to_image)
 int launch_boxes_to_image(const float* det_boxes, const int32_t* det_counts, const int64_t* positions, const uint8_t* masks,
                           int B, int T, int S, int K, int P, float* out_boxes, int32_t* out_totals, hipStream_t s);

@@ -3,6 +3,7 @@
 // Integer / bool work is exact; see jn_device.h for the per-agent step.
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <type_traits>
 
 #include "jn_device.h"
@@ -199,6 +200,53 @@ __global__ void rollout_epilogue_kernel(RolloutBuffers r, const int32_t* __restr
 int launch_rollout_epilogue(const RolloutBuffers& r, const int32_t* n_done, int B, int T, int stop_early,
                             hipStream_t s) {
   hipLaunchKernelGGL(rollout_epilogue_kernel, dim3((B + 63) / 64), dim3(64), 0, s, r, n_done, B, T, stop_early);
+  return 0;
+}
+
+// The teacher's opinion of a state (NeedleSimpleEnv.build_keypoints_trajectory + move_towards, src/env/simple_env.py:
+// 590-629, 84-125): the remaining targets are targets & ~visited, N = those at the minimum Manhattan distance from the
+// agent, and the byte holds bit a for every action a = move_towards(agent, q), q in N — the deterministic object behind
+// the reference's random.choice among N.  STOP (a target under the agent) sets no bit; no remaining target gives 0.
+// One wave per agent: each lane keeps (min distance, directions at it) over its cells i = lane, lane + 64, ..., then the
+// wave takes the minimum of the distances and ORs the bits of the lanes that hold it.  set_stride: bytes between agents
+// in `sets` (1 for a [B] vector, T for column t of the rollout's [B,T]).
+constexpr int kTeacherWaves = 4;   // agents per 256-thread block
+__global__ __launch_bounds__(64 * kTeacherWaves) void teacher_sets_kernel(
+    const long long* __restrict__ pos, const uint8_t* __restrict__ visited, const uint8_t* __restrict__ targets,
+    uint8_t* __restrict__ sets, long long set_stride, int B, int Gh, int Gw, const int* __restrict__ skip_flag,
+    int skip_when) {
+  if (skip_flag && *skip_flag >= skip_when) return;
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * kTeacherWaves + (threadIdx.x >> 6);
+  if (b >= B) return;                                    // whole waves leave: the shuffles below stay wave-uniform
+  const int y = (int)pos[2 * b], x = (int)pos[2 * b + 1];
+  const int cells = Gh * Gw;
+  const uint8_t* tg = targets + (long long)b * cells;
+  const uint8_t* vs = visited + (long long)b * cells;
+  int best = INT_MAX;
+  uint32_t bits = 0;
+  for (int i = lane; i < cells; i += 64) {
+    if (!tg[i] || vs[i]) continue;
+    const int dy = i / Gw - y, dx = i % Gw - x;
+    const int d = abs(dy) + abs(dx);
+    const int a = kTowards[((dy > 0) - (dy < 0) + 1) * 3 + (dx > 0) - (dx < 0) + 1];
+    const uint32_t bit = a < 8 ? 1u << a : 0u;
+    if (d < best) { best = d; bits = bit; }
+    else if (d == best) bits |= bit;
+  }
+  int wmin = best;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) wmin = min(wmin, __shfl_xor(wmin, o, 64));
+  bits = (best == wmin && best != INT_MAX) ? bits : 0u;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) bits |= (uint32_t)__shfl_xor((int)bits, o, 64);
+  if (lane == 0) sets[b * set_stride] = (uint8_t)bits;
+}
+
+int launch_teacher_sets(const int64_t* positions, const uint8_t* visited, const uint8_t* targets, uint8_t* sets,
+                        long long set_stride, int B, int Gh, int Gw, const int* skip_flag, int skip_when, hipStream_t s) {
+  hipLaunchKernelGGL(teacher_sets_kernel, dim3((B + kTeacherWaves - 1) / kTeacherWaves), dim3(64 * kTeacherWaves), 0, s,
+                     (const long long*)positions, visited, targets, sets, set_stride, B, Gh, Gw, skip_flag, skip_when);
   return 0;
 }
 

@@ -36,7 +36,8 @@ def pad_to_patch_multiple(image: torch.Tensor, patch_size: int) -> torch.Tensor:
 
 @torch.no_grad()
 def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequence] = None, sample_actions: bool = True,
-                 do_detection: Optional[bool] = None, batch_size: Optional[int] = None, device_metrics: bool = False) -> Dict:
+                 do_detection: Optional[bool] = None, batch_size: Optional[int] = None, device_metrics: bool = False,
+                 token_positions: Optional[str] = None) -> Dict:
     """`images`: [C, H, W] tensors (uint8 0..255 or float 0..1) of any sizes; `targets`: per image an [n, 4] xyxy list /
     tensor or None.  Returns per-image boxes ([n, 7] in full-image pixels or None), positions, step counts, durations
     and — where targets are given — the mean of the reference's metrics.
@@ -55,13 +56,17 @@ def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequ
     by up to 3e-3 px (positions and steps unchanged).
 
     device_metrics=True (with batch_size): the `map` metric of a chunk's images comes from ``map_50_device`` on the
-    chunk's packed boxes, one readback per chunk, instead of one host ``map_50`` per image."""
+    chunk's packed boxes, one readback per chunk, instead of one host ``map_50`` per image.
+
+    token_positions: "sequence" / "recurrent" / None, handed to every rollout (``ReinforceTrainer.rollout``): a policy
+    trained in supervised mode needs "sequence"."""
     cfg, dev = trainer.config, trainer.device
     P, T = int(cfg.patch_size), int(cfg.max_seq_len)
     if do_detection is None:
         do_detection = bool(getattr(cfg, "detection_enabled", False)) and trainer.yolox_model() is not None
     if batch_size is not None:
-        return _infer_batched(trainer, images, targets, sample_actions, do_detection, int(batch_size), device_metrics)
+        return _infer_batched(trainer, images, targets, sample_actions, do_detection, int(batch_size), device_metrics,
+                              token_positions)
     if device_metrics:
         raise ValueError("device_metrics needs batch_size: the per-image loop evaluates one image at a time")
     res = {"boxes": [], "positions": [], "steps": [], "duration_ms": []}
@@ -74,7 +79,7 @@ def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequ
         bboxes = tg.to(torch.long) if tg is not None else torch.zeros((1, 1, 4), dtype=torch.long)
         env = NeedleGeneralEnv(x, bboxes, P, T, 1, bool(getattr(cfg, "stop_enabled", False)))
         t0 = time.perf_counter()
-        ro = trainer.rollout(env, do_detection=do_detection, sample_actions=sample_actions)
+        ro = trainer.rollout(env, do_detection=do_detection, sample_actions=sample_actions, token_positions=token_positions)
         torch.cuda.synchronize(dev)
         res["duration_ms"].append((time.perf_counter() - t0) * 1e3)
         offsets = ro["positions"][:, :, [1, 0]] * P                       # (y, x) grid -> (x, y) pixels
@@ -92,7 +97,8 @@ def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequ
     return res
 
 
-def _infer_batched(trainer, images, targets, sample_actions, do_detection, batch_size, device_metrics=False) -> Dict:
+def _infer_batched(trainer, images, targets, sample_actions, do_detection, batch_size, device_metrics=False,
+                   token_positions=None) -> Dict:
     dev, P = trainer.device, int(trainer.config.patch_size)
     n = len(images)
     res = {"boxes": [None] * n, "positions": [None] * n, "steps": [0] * n, "duration_ms": [0.0] * n}
@@ -109,7 +115,7 @@ def _infer_batched(trainer, images, targets, sample_actions, do_detection, batch
         start = loop_start_positions(trainer, first, sel, extents)
         t0 = time.perf_counter()
         ro = trainer.rollout(env, do_detection=do_detection, sample_actions=sample_actions, start_positions=start,
-                             bbox_lists=False)
+                             bbox_lists=False, token_positions=token_positions)
         torch.cuda.synchronize(dev)
         ms = (time.perf_counter() - t0) * 1e3 / len(sel)
         packed = rollout_boxes_packed(ro, P) if do_detection else None

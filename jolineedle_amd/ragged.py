@@ -21,7 +21,7 @@ from .views import ImageViews
 # padding here: the per-image loop gives an image without targets the box (0, 0, 0, 0), which marks patch (0, 0)
 INERT_BOX = (0, 0, -1, -1)
 
-_PER_STEP = ("rewards", "returns", "logprobs", "entropies", "logit_masks", "actions", "logits")
+_PER_STEP = ("rewards", "returns", "logprobs", "entropies", "logit_masks", "actions", "logits", "teacher_sets")
 _PER_TOKEN = ("masks", "positions", "final_emb", "det_counts", "det_boxes", "patches")
 
 
@@ -108,9 +108,10 @@ def slice_rollout(rollout: Dict, b: int, steps: int) -> Dict:
 
 
 @torch.no_grad()
-def found_ratios(env: NeedleGeneralEnv, rollout: Dict, steps: Sequence[int]) -> Tensor:
+def found_ratios(env: NeedleGeneralEnv, rollout: Dict, steps: Sequence[int], masks: Optional[Tensor] = None) -> Tensor:
     """``env.prop_patches_found`` [B] as it stands after each image's own last step: the patches marked by a box among
-    those visited at positions[b, 0..steps[b]] (same integer counts and the same division as the env's property)."""
+    those visited at positions[b, 0..steps[b]] (same integer counts and the same division as the env's property).
+    masks: bool [B, Gh, Gw] to count instead of the env's bbox masks."""
     pos = rollout["positions"]
     B, n = pos.shape[0], pos.shape[1]
     Gh, Gw = env.n_vertical_patches, env.n_horizontal_patches
@@ -119,7 +120,7 @@ def found_ratios(env: NeedleGeneralEnv, rollout: Dict, steps: Sequence[int]) -> 
     cell = (torch.arange(B, device=pos.device).unsqueeze(1) * Gh + pos[..., 0]) * Gw + pos[..., 1]
     visited = torch.zeros(B * Gh * Gw, dtype=torch.bool, device=pos.device)
     visited[cell[own]] = True
-    m = env.bbox_masks
+    m = env.bbox_masks if masks is None else masks
     count = (m & visited.view(B, Gh, Gw)).sum(dim=(1, 2))
     tot = m.sum(dim=(1, 2))
     tot[tot == 0] = 1

@@ -74,14 +74,35 @@ class ReinforceTrainer:
 
     def rollout(self, env: NeedleGeneralEnv, do_detection: bool = False, sample_actions: bool = True,
                 forced_actions: torch.Tensor = None, start_positions: torch.Tensor = None,
-                keep_patches: bool = True, stop_early: bool = True, bbox_lists: bool = True) -> Dict[str, torch.Tensor]:
+                keep_patches: bool = True, stop_early: bool = True, bbox_lists: bool = True,
+                token_positions: str = None, teacher: bool = False,
+                teacher_targets: torch.Tensor = None) -> Dict[str, torch.Tensor]:
         """src/reinforce.py:108-215.  Extra keyword arguments (not in the reference):
         `forced_actions` [B,T] replays a trajectory, `start_positions` [B,2] injects reset
         positions (reference: env.reset(positions)), `keep_patches=False` skips the
         [B,S+1,3,P,P] patch stack, `stop_early=False` always runs max_ep_len steps, `bbox_lists=False` leaves
         "bboxes" empty (no B x (S+1) clones): the detections are then only "det_boxes" [B,S+1,K,7] / "det_counts"
-        [B,S+1] on the device, which ``detection.rollout_boxes_to_image`` assembles per image."""
+        [B,S+1] on the device, which ``detection.rollout_boxes_to_image`` assembles per image.
+
+        `token_positions`: "recurrent" gives every new token the 1-D position 0 (gpt.py:431-449, what a REINFORCE-trained
+        policy saw), "sequence" gives the token of step t position t — the last row of the full-prefix forward
+        (gpt.py:331-354) that a supervised policy was trained on and that ``--no-recurrent-embedding`` selects
+        (gpt.py:427-428); None = "sequence" when ``model.config.no_recurrent_embedding``, else "recurrent".  "sequence"
+        is an eval-mode feature (see the NotImplementedError below).
+        `teacher=True` adds "teacher_sets" [B,S] uint8: per step the teacher's action set
+        (``trajectory.teacher_action_sets``) of the state the decision saw, computed inside the rollout;
+        `teacher_targets` [B,Gh,Gw] replaces the env's bbox masks as the cells the teacher walks to."""
         model, dev = self.model, self.device
+        if token_positions is None:
+            token_positions = "sequence" if getattr(model.config, "no_recurrent_embedding", False) else "recurrent"
+        if token_positions not in ("sequence", "recurrent"):
+            raise ValueError(f"token_positions must be 'sequence', 'recurrent' or None, got {token_positions!r}")
+        by_token = token_positions == "sequence"
+        if by_token and model.training and torch.is_grad_enabled():
+            raise NotImplementedError(
+                "token_positions='sequence' is for eval-mode rollouts: in train mode the reference re-encodes the whole "
+                "prefix at every step with BatchNorm statistics over B*(t+1) patches, which the per-step rollout cannot "
+                "reproduce (call model.eval() or torch.no_grad())")
         model.sync_weights()
         eng = model.engine()
         env.bind(eng)
@@ -121,18 +142,37 @@ class ReinforceTrainer:
         # model.train() + grad mode (the reference's training loop, src/reinforce.py:304, 326): batch-statistics BatchNorm,
         # activations of every step kept resident, logprobs / entropies leave with a graph (autograd bridge)
         graph = bool(model.training) and torch.is_grad_enabled() and not do_detection
-        if graph:
-            model.bind_flat()
-            model._rollout_gen += 1
-            check(eng.lib.jn_reinforce_forward(eng.handle, mode, ptr(forced_actions), ptr(start_positions), seed,
-                                               int(stop_early), C.byref(out), stream), "jn_reinforce_forward")
-            anchor = next(p for p in model.parameters() if p.requires_grad)
-            keep = dict(buf, forced_actions=forced_actions, start_positions=start_positions)
-            buf["logprobs"], buf["entropies"] = _RolloutGraph.apply(anchor, model, model._rollout_gen, buf["logprobs"],
-                                                                    buf["entropies"], keep)
-        else:
-            check(eng.lib.jn_rollout(eng.handle, mode, ptr(forced_actions), ptr(start_positions), seed,
-                                     int(do_detection), int(stop_early), C.byref(out), stream), "jn_rollout")
+        sets = None
+        if teacher:
+            sets = torch.empty((B, T), device=dev, dtype=torch.uint8)
+            if teacher_targets is not None:
+                teacher_targets = teacher_targets.to(dev, torch.uint8).contiguous()
+                grid = (B, env.n_vertical_patches, env.n_horizontal_patches)
+                assert tuple(teacher_targets.shape) == grid, f"teacher_targets must be {grid}, got {tuple(teacher_targets.shape)}"
+        try:
+            # both switches are sticky in the engine: set for this rollout only, so that every other caller of the
+            # engine (and the default path, which makes neither call) finds it as it always was
+            if by_token:
+                check(eng.lib.jn_set_rollout_positions(eng.handle, 1), "jn_set_rollout_positions")
+            if teacher:
+                check(eng.lib.jn_set_rollout_teacher(eng.handle, ptr(teacher_targets), ptr(sets)), "jn_set_rollout_teacher")
+            if graph:
+                model.bind_flat()
+                model._rollout_gen += 1
+                check(eng.lib.jn_reinforce_forward(eng.handle, mode, ptr(forced_actions), ptr(start_positions), seed,
+                                                   int(stop_early), C.byref(out), stream), "jn_reinforce_forward")
+                anchor = next(p for p in model.parameters() if p.requires_grad)
+                keep = dict(buf, forced_actions=forced_actions, start_positions=start_positions)
+                buf["logprobs"], buf["entropies"] = _RolloutGraph.apply(anchor, model, model._rollout_gen, buf["logprobs"],
+                                                                        buf["entropies"], keep)
+            else:
+                check(eng.lib.jn_rollout(eng.handle, mode, ptr(forced_actions), ptr(start_positions), seed,
+                                         int(do_detection), int(stop_early), C.byref(out), stream), "jn_rollout")
+        finally:
+            if by_token:
+                eng.lib.jn_set_rollout_positions(eng.handle, 0)
+            if teacher:
+                eng.lib.jn_set_rollout_teacher(eng.handle, None, None)
         S = C.c_int()
         check(eng.lib.jn_rollout_steps(eng.handle, C.byref(S), stream), "jn_rollout_steps")
         S = S.value
@@ -147,6 +187,8 @@ class ReinforceTrainer:
             "actions": buf["actions"][:, :S], "logits": buf["logits"][:, :S],
             "final_emb": buf["final_emb"][:, :S + 1],
         }
+        if teacher:
+            res["teacher_sets"] = sets[:, :S]
         if do_detection and bbox_lists:       # ragged list-of-lists of [n,7] | None (src/reinforce.py:145-146, 166-167)
             cnt = det_counts[:, :S + 1].tolist()
             res["bboxes"] = [[det_boxes[b, t, :cnt[b][t]].clone() if cnt[b][t] > 0 else None for t in range(S + 1)]
@@ -397,19 +439,20 @@ class ReinforceTrainer:
         return metrics
 
     @torch.no_grad()
-    def eval_on_batch(self, env: NeedleGeneralEnv, do_detection: bool = None, merge_bboxes: bool = None) -> Dict[str, torch.Tensor]:
+    def eval_on_batch(self, env: NeedleGeneralEnv, do_detection: bool = None, merge_bboxes: bool = None,
+                      token_positions: str = None) -> Dict[str, torch.Tensor]:
         """``eval_on_sample`` of the reference (src/reinforce.py:424-497) without the plotting: greedy rollout,
         rollout metrics incl. the env's found-ratios, and — with detection — mAP-50 of the boxes found along the
         trajectories (moved to full-image coordinates, optionally merged) plus the detector's mAP on every patch that
         holds a box (`yolo_map`).  The reference evaluates one image at a time; any batch size works here (the
-        per-image metrics it reads from index 0 stay index 0)."""
+        per-image metrics it reads from index 0 stay index 0).  `token_positions`: see ``rollout``."""
         from .detection import patch_bboxes2full_image
         cfg = self.config
         if do_detection is None:
             do_detection = bool(getattr(cfg, "detection_enabled", False))
         if merge_bboxes is None:
             merge_bboxes = bool(getattr(cfg, "merge_bboxes", False))
-        ro = self.rollout(env, sample_actions=False, do_detection=do_detection)
+        ro = self.rollout(env, sample_actions=False, do_detection=do_detection, token_positions=token_positions)
         metrics = self.compute_metrics(ro, env)
         if do_detection:
             targets = env.get_detection_targets()
@@ -444,7 +487,7 @@ class ReinforceTrainer:
 
     @torch.no_grad()
     def eval_on_images(self, images, bboxes, batch_size: int, do_detection: bool = None,
-                       merge_bboxes: bool = None, device_metrics: bool = False) -> Dict[str, list]:
+                       merge_bboxes: bool = None, device_metrics: bool = False, token_positions: str = None) -> Dict[str, list]:
         """The per-image ``all_metrics`` of the reference's ``test()`` (src/reinforce.py:383-392) without its loop of
         ``B = 1`` envs: `images` ([3, Hi, Wi] tensors of any sizes, uint8 read in place or float 0..1) are evaluated
         `batch_size` at a time (``ragged.plan_chunks``), every agent inside its own image.  Returns, for every key of
@@ -456,7 +499,26 @@ class ReinforceTrainer:
         device_metrics=True: the `map` entry of a whole chunk comes from the device — the rollout's boxes go
         ``rollout_boxes_packed`` -> (merge_bboxes) ``merge_boxes_device`` -> ``map_50_device(per_image=True)`` without
         leaving it, the targets are merged there too; one readback per chunk.  Same keys; `map` equals the host
-        path's up to fp32 storage; the `yolo_*` entries are computed as without it."""
+        path's up to fp32 storage; the `yolo_*` entries are computed as without it.  `token_positions`: see ``rollout``."""
+        per_image = self._eval_image_chunks(images, bboxes, batch_size, do_detection, merge_bboxes, device_metrics,
+                                            token_positions=token_positions)
+        out: Dict[str, list] = {}
+        for tail, ro_b in per_image:                      # compute_metrics in image order: the reward-norm window's order
+            m = self.compute_metrics(ro_b)
+            m.update(tail)
+            for k, v in m.items():
+                out.setdefault(k, []).append(float(v))
+        return out
+
+    @torch.no_grad()
+    def _eval_image_chunks(self, images, bboxes, batch_size: int, do_detection: bool = None, merge_bboxes: bool = None,
+                           device_metrics: bool = False, sample_actions: bool = False, token_positions: str = None,
+                           teacher_targets=None) -> list:
+        """The chunked rollouts behind ``eval_on_images`` (and ``SupervisedTrainer.eval_on_images``): per image, in image
+        order, (the metrics that do not come from ``compute_metrics``, the image's own ``B = 1`` rollout).
+        teacher_targets: a callable (box rows of the chunk's images, their grid extents, the canvas grid) -> uint8
+        [n, Gh, Gw]; the rollouts then carry "teacher_sets" and "teacher_targets", and the found-ratios count these
+        cells instead of the env's bbox masks."""
         from .detection import (detection_targets, map_50_device, merge_boxes_device, pack_boxes, rollout_boxes_packed,
                                 split_bboxes_over_patches, unpack_boxes)
         from .ragged import (env_metrics, found_ratios, image_env, loop_start_positions, own_steps, plan_chunks,
@@ -475,10 +537,16 @@ class ReinforceTrainer:
             imgs = [images[i] if images[i].dtype == torch.uint8 else images[i].float() for i in sel]
             env = image_env(self, imgs, [rows[i] for i in sel], canvas=chunk["canvas"])
             extents = env.grid_extents.tolist()
-            ro = self.rollout(env, sample_actions=False, do_detection=do_detection, bbox_lists=False,
-                              start_positions=loop_start_positions(self, first, sel, extents))
+            kw, tg_grid = {}, None
+            if teacher_targets is not None:
+                tg_grid = teacher_targets([rows[i] for i in sel], extents, (env.n_vertical_patches, env.n_horizontal_patches))
+                tg_grid = tg_grid.to(self.device)                 # uploaded once per chunk
+                kw = dict(teacher=True, teacher_targets=tg_grid)
+            ro = self.rollout(env, sample_actions=sample_actions, do_detection=do_detection, bbox_lists=False,
+                              start_positions=loop_start_positions(self, first, sel, extents),
+                              token_positions=token_positions, **kw)
             steps = own_steps(ro)
-            found = found_ratios(env, ro, steps)
+            found = found_ratios(env, ro, steps, masks=None if tg_grid is None else tg_grid.bool())
             packed = rollout_boxes_packed(ro, P) if do_detection else None
             if do_detection and device_metrics:
                 tg = pack_boxes([detection_targets(rows[i].unsqueeze(0), *extents[b], P)[0] for b, i in enumerate(sel)], 5,
@@ -491,6 +559,8 @@ class ReinforceTrainer:
                 full = unpack_boxes(*packed)
             for b, i in enumerate(sel):
                 ro_b = slice_rollout(ro, b, steps[b])
+                if tg_grid is not None:
+                    ro_b["teacher_targets"] = tg_grid[b:b + 1]
                 metrics = dict(env_metrics(self, found, ro_b, b))     # what follows compute_metrics' own entries
                 per_image[i] = (metrics, ro_b)
                 if not do_detection:
@@ -509,10 +579,4 @@ class ReinforceTrainer:
                     metrics.update(self._detection_eval_metrics([full[b]], detection_targets(box, gh, gw, P), patches,
                                                                 patch_targets, merge_bboxes))
         self._rollouts = first - 1 + len(images)          # where that loop leaves the counter
-        out: Dict[str, list] = {}
-        for tail, ro_b in per_image:                      # compute_metrics in image order: the reward-norm window's order
-            m = self.compute_metrics(ro_b)
-            m.update(tail)
-            for k, v in m.items():
-                out.setdefault(k, []).append(float(v))
-        return out
+        return per_image

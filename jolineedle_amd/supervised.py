@@ -2,7 +2,8 @@
 (src/supervised.py:138-177 loss, :863-902 step) over ``jn_supervised_step``, fed by teacher trajectories
 (``generate_trajectories``, src/supervised.py:95-136, over trajectory.NeedleSimpleEnv) whose patches are gathered on
 the device, and followed by the detector step on the trajectories' detector patches (src/supervised.py:881-902).
-The evaluation suite is out of scope; augmentation is opt-in (``init_detection``)."""
+``eval_on_images`` is the free-running half of ``test()`` (src/supervised.py:279-405) on the engine's rollout; the rest of
+the evaluation suite is out of scope; augmentation is opt-in (``init_detection``)."""
 import ctypes as C
 from typing import Dict, Optional, Tuple
 
@@ -233,6 +234,75 @@ class SupervisedTrainer:
             dist.destroy_process_group()                 # src/reinforce.py:362 / src/supervised.py:911
             self._owns_process_group = False
         return metrics
+
+    # ---- evaluation: the free-running half of test() (src/supervised.py:279-405, 407-470) ------------------------------
+    def _eval_runner(self):
+        """The rollout machinery of ``ReinforceTrainer`` over this trainer's model, walking ``test_max_seq_len`` steps.
+        Kept between calls so that its rollout counter (start positions, sampling seeds) moves on like a loop's."""
+        if getattr(self, "_eval_trainer", None) is None:
+            from types import SimpleNamespace
+            from .reinforce import ReinforceTrainer
+            cfg = self.config
+            view = SimpleNamespace(
+                max_seq_len=int(getattr(cfg, "test_max_seq_len", None) or cfg.max_seq_len), entropy_weight=0.0,
+                stop_enabled=bool(getattr(cfg, "stop_enabled", False)), reward_norm=False, seed=int(getattr(cfg, "seed", 0)),
+                patch_size=int(cfg.patch_size), detection_enabled=bool(getattr(cfg, "detection_enabled", True)),
+                merge_bboxes=bool(getattr(cfg, "merge_bboxes", False)))
+            self._eval_trainer = ReinforceTrainer(view, self.model, rank=self.rank)
+        return self._eval_trainer
+
+    @torch.no_grad()
+    def eval_on_images(self, images, bboxes, batch_size: int, sample_actions: bool = False, do_detection: bool = None,
+                       merge_bboxes: bool = None, device_metrics: bool = False) -> Dict[str, list]:
+        """The free-running half of the reference's ``test()``: ``test_model_on_env`` (src/supervised.py:279-405) lets the
+        policy walk one image, calling the full-sequence forward again at every step, and compares every chosen action
+        with the teacher's ``best_action``.  Here the walks are the engine's rollouts with the token of step t at 1-D
+        position t (``token_positions="sequence"``: the KV-cached step computes the last row of that full forward),
+        `batch_size` images at a time with the chunking, start positions and detection metrics of
+        ``ReinforceTrainer.eval_on_images``, for ``config.test_max_seq_len`` steps; the teacher's opinion of every
+        visited state is computed inside the rollout (``jn_set_rollout_teacher``) on the simple env's target cells
+        (``trajectory.simple_env_targets``, built on the host per image, uploaded once per chunk).
+
+        Returns per-image lists: `prop_patches_found` (target cells visited / target cells, 0 without targets),
+        `episode_length` (the image's own executed steps), with detection `map` and the `yolo_*` entries,
+        `teacher_agreement` (share of the own steps with a non-empty teacher set whose action is a member of it; 0 when
+        there is none) and `stopped_inside_bbox` (the final cell is a target cell).  No REINFORCE losses;
+        ``last_return_values`` of no trainer is touched.  ``self.last_eval_rollouts`` keeps, per image, the small
+        part of its walk on the host (actions, positions, logits, teacher_sets, teacher_targets).  Deviations from the
+        reference: DESIGN.md §6."""
+        from .trajectory import simple_env_targets, teacher_agreement
+        runner = self._eval_runner()
+        P = int(self.config.patch_size)
+        if do_detection is None:
+            do_detection = bool(getattr(self.config, "detection_enabled", True)) and self.yolox_model() is not None
+
+        def target_grids(rows, extents, canvas):
+            grid = torch.zeros((len(rows), *canvas), dtype=torch.uint8)
+            for b, (r, (gh, gw)) in enumerate(zip(rows, extents)):
+                grid[b, :gh, :gw] = simple_env_targets(r, gh * P, gw * P, P)
+            return grid
+
+        was_training = self.model.training
+        self.model.eval()                                  # src/supervised.py:294
+        try:
+            per_image = runner._eval_image_chunks(images, bboxes, batch_size, do_detection, merge_bboxes, device_metrics,
+                                                  sample_actions=sample_actions, token_positions="sequence",
+                                                  teacher_targets=target_grids)
+        finally:
+            self.model.train(was_training)
+        out: Dict[str, list] = {}
+        self.last_eval_rollouts = []
+        for tail, ro_b in per_image:
+            walk = {k: ro_b[k][0].cpu() for k in ("actions", "positions", "logits", "teacher_sets", "teacher_targets")}
+            self.last_eval_rollouts.append(walk)
+            y, x = walk["positions"][-1].tolist()
+            m = {"prop_patches_found": tail["prop_patches_found"], "episode_length": walk["actions"].numel(),
+                 "teacher_agreement": teacher_agreement(walk["teacher_sets"], walk["actions"]),
+                 "stopped_inside_bbox": bool(walk["teacher_targets"][y, x])}
+            m.update({k: v for k, v in tail.items() if k == "map" or k.startswith("yolo_")})
+            for k, v in m.items():
+                out.setdefault(k, []).append(float(v))
+        return out
 
     def train_step(self, patches, current_actions, next_actions, positions, masks, optimizer_step: bool = True,
                    process_group=None, classes=None) -> Dict[str, torch.Tensor]:

@@ -253,6 +253,71 @@ class NeedleSimpleEnv:
         return assemble_samples(self.image, [self.image_index], [idx], self.patch_size, stacked=False)
 
 
+def teacher_action_sets(positions: torch.Tensor, visited: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
+    """The teacher's opinion of B states as action sets, uint8 [B] (host, torch CPU): the deterministic object behind the
+    first ``random.choice`` of ``build_keypoints_trajectory``.  positions [B, 2] (y, x); visited, targets [B, Gh, Gw]
+    (non-zero = set).  The remaining targets of agent b are ``targets[b] & ~visited[b]``, N those at the minimum L1
+    distance, and bit a of the byte is set when action a = ``move_towards(position, q)`` for some q in N (actions 0..7;
+    STOP, which ``remove_stop_action`` replaces by a random move, is never a member).  0: nothing left to visit (the
+    reference then walks to a random cell and no action is "right")."""
+    pos = positions.to("cpu", torch.int64).reshape(-1, 2)
+    left = (targets.to("cpu") != 0) & ~(visited.to("cpu") != 0)
+    B, Gh, Gw = left.shape
+    assert pos.shape[0] == B
+    dy = torch.arange(Gh).view(1, Gh, 1) - pos[:, 0].view(B, 1, 1)
+    dx = torch.arange(Gw).view(1, 1, Gw) - pos[:, 1].view(B, 1, 1)
+    dist = dy.abs() + dx.abs()                                          # [B, Gh, Gw]
+    far = Gh + Gw
+    dist = torch.where(left, dist, torch.full_like(dist, far))
+    nearest = left & (dist == dist.amin(dim=(1, 2), keepdim=True))
+    sets = torch.zeros(B, dtype=torch.int64)
+    for (sy, sx), action in _BY_SIGN.items():
+        if action is Action.STOP:
+            continue
+        hit = nearest & (dy.sign() == sy) & (dx.sign() == sx)
+        sets |= hit.any(dim=2).any(dim=1).to(torch.int64) << action.value
+    return sets.to(torch.uint8)
+
+
+def teacher_action_sets_device(positions: torch.Tensor, visited: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
+    """``teacher_action_sets`` in one launch (``jn_teacher_actions``, one wave per agent) on device tensors: positions
+    [B, 2] int64, visited / targets [B, Gh, Gw] bool or uint8; returns uint8 [B] on the device without a readback."""
+    from . import _lib
+    from ._lib import check, ptr
+    assert positions.is_cuda and visited.is_cuda and targets.is_cuda, "device tensors required (host: teacher_action_sets)"
+    dev = positions.device
+    pos = positions.to(torch.int64).reshape(-1, 2).contiguous()
+    vis, tg = visited.to(torch.uint8).contiguous(), targets.to(torch.uint8).contiguous()
+    B, Gh, Gw = tg.shape
+    assert pos.shape[0] == B and vis.shape == tg.shape
+    out = torch.empty((B,), device=dev, dtype=torch.uint8)
+    if B:
+        check(_lib.load_library().jn_teacher_actions(ptr(pos), ptr(vis), ptr(tg), B, Gh, Gw, ptr(out),
+                                                     _lib.current_stream(dev)), "jn_teacher_actions")
+    return out
+
+
+def teacher_agreement(sets: torch.Tensor, actions: torch.Tensor) -> float:
+    """Share of the steps with a non-empty teacher set whose action is a member of it (sets uint8 [S], actions [S]);
+    0.0 when there is no such step (the reference zeroes the NaN of an empty mean, src/supervised.py:390-396)."""
+    sets, actions = sets.to("cpu", torch.int64).flatten(), actions.to("cpu", torch.int64).flatten()
+    judged = sets != 0
+    if not bool(judged.any()):
+        return 0.0
+    member = ((sets >> actions.clamp(max=62)) & 1).bool()
+    return float((member & judged).sum()) / float(judged.sum())
+
+
+def simple_env_targets(bboxes, height: int, width: int, patch_size: int) -> torch.Tensor:
+    """uint8 [height // P, width // P]: the cells ``NeedleSimpleEnv`` counts as targets (``bbox_positions`` with its
+    area threshold, plus each box's centre cell), for xyxy boxes of an image of height x width pixels."""
+    env = NeedleSimpleEnv(None, patch_size, bboxes, height=height, width=width)
+    grid = torch.zeros((env.patch_height, env.patch_width), dtype=torch.uint8)
+    for y, x in env.bbox_patches:
+        grid[y, x] = 1
+    return grid
+
+
 def gather_indexed(images: torch.Tensor, image_index: torch.Tensor, positions: torch.Tensor, patch_size: int,
                    views=None) -> torch.Tensor:
     """out[n] = images[image_index[n], :, y*P:(y+1)*P, x*P:(x+1)*P]; a negative image index gives a zero patch.
