@@ -272,6 +272,35 @@ int jn_match_detections(const float* preds_dev, const int32_t* pred_counts_dev, 
 int jn_average_precision(const double* scores_dev, const int32_t* hits_dev, const int32_t* n_pred_dev,
                          const int32_t* n_gt_dev, int B, int max_det, int pooled, const double* thresholds_dev,
                          int n_thresholds, double* out_dev, void* stream);
+/* jn_average_precision over arbitrary runs of units: jn_match_detections' outputs over U units and seg_offsets int32
+ * [NS+1] (device); segment s is the units seg_offsets[s] .. seg_offsets[s+1]-1 concatenated in unit order, out f64 [NS].
+ * Same arithmetic as jn_average_precision (one segment over all units equals pooled = 1 bit for bit); n_gt of a segment
+ * is the sum over its units; no target or no prediction gives 0.  max_units is the caller's bound on the units of a
+ * segment (the offsets stay on the device): JN_EINVAL when max_units * max_det > 8192, and a longer segment is cut to
+ * max_units.  The reference's per-image value of the multistart evaluation is one MeanAveragePrecision over that
+ * image's patches (src/supervised.py:203-277). */
+int jn_average_precision_segments(const double* scores_dev, const int32_t* hits_dev, const int32_t* n_pred_dev,
+                                  const int32_t* n_gt_dev, int U, int max_det, const int32_t* seg_offsets_dev, int NS,
+                                  int max_units, const double* thresholds_dev, int n_thresholds, double* out_dev, void* stream);
+/* The pooling of the multistart evaluation (metrics_from_multiple_samples / eval_missing_patches,
+ * src/supervised.py:573-625), context-free, on what a rollout of A walks leaves on the device: det_boxes f32
+ * [A,T+1,K_det,7] (patch-local pixels), det_counts int32 [A,T+1], positions int64 [A,T+1,2] (y,x); tokens 0..S of a
+ * walk are read (S <= T), of which walk a owns the first walk_tokens[a] (int32 [A], its own steps + 1).  Image i uses
+ * the walks walk_first[i] .. walk_first[i]+walk_count[i]-1 (int32 [NI] each; one launch per n_starts prefix needs no
+ * repacking).  Cell c = y*Gw + x of image i is visited when a token of a used walk stands on it (visited u8
+ * [NI,Gh*Gw]); its pool is the boxes of every such token in (walk, token, stored) order, a walk that returns to a cell
+ * contributing again.  Greedy NMS in (column 4 descending, pool index ascending) order: a box is suppressed when its
+ * IoU with a kept box is > 0.5, the IoU in f32 with every operation rounded once (w = max(min(x2) - max(x1), 0),
+ * likewise h, inter = w*h, iou = inter / ((area_a + area_b) - inter)); a NaN IoU suppresses nothing.  The survivors go
+ * in that order to cell_boxes f32 [NI,Gh*Gw,max_per_cell,7], cell_counts int32 = min(survivors, max_per_cell) (0 on
+ * an unvisited cell), rows beyond the count are left alone; cell_stats (int32 [NI,Gh*Gw,2], may be NULL) = pool size
+ * and survivors before that cut.  max_walks is the caller's bound on walk_count.  JN_EINVAL, before any launch:
+ * max_walks*(S+1)*K_det > 4096, max_per_cell < 1, NI < 1, a null pointer. */
+int jn_pool_walk_detections(const float* det_boxes_dev, const int32_t* det_counts_dev, const int64_t* positions_dev,
+                            const int32_t* walk_tokens_dev, const int32_t* walk_first_dev, const int32_t* walk_count_dev, int A,
+                            int T, int S, int K_det, int NI, int max_walks, int Gh, int Gw, int max_per_cell,
+                            float* cell_boxes_dev, int32_t* cell_counts_dev, int32_t* cell_stats_dev, uint8_t* visited_dev,
+                            void* stream);
 /* Context-free indexed gather through a DEVICE table of n_views views (all of one element type, already valid):
  * out[n] = canvas[image_index[n]][:, y*P:(y+1)*P, x*P:(x+1)*P], image_index[n] < 0 = zero patch.  out_u8 = 0:
  * out is f32 (bytes as b / 255); out_u8 = 1: u8 sources only, out is the transformed byte copy. */

@@ -110,6 +110,8 @@ def get_args(args=None):
     p.add_argument("--filter-classes", nargs="+", default=None)
     p.add_argument("--measure-flops", action="store_true")
     p.add_argument("--no-recurrent-embedding", action="store_true")
+    p.add_argument("--eval-max-per-cell", type=int, default=64,
+                   help="multistart evaluation: survivors of the per-patch NMS that are scored, per patch (not a reference flag)")
     return p.parse_args(args)
 
 
@@ -126,6 +128,7 @@ def args_to_config(args):
     t.gradient_accumulation = args.gradient_accumulation
     t.env_name, t.work_dir, t.seed = args.env_name, args.work_dir, args.seed
     t.test_every, t.test_samples = args.test_every, args.test_samples
+    t.eval_max_per_cell = args.eval_max_per_cell       # SupervisedTrainer.eval_envs_on_images (ours)
     t.stop_weight, t.entropy_weight, t.reward_norm = args.stop_weight, args.entropy_weight, args.reward_norm
     t.merge_bboxes, t.failure_select_rate = args.merge_bboxes, args.failure_select_rate
     t.port_ddp = args.port_ddp

@@ -2072,6 +2072,49 @@ int jn_average_precision(const double* scores_dev, const int32_t* hits_dev, cons
   return JN_OK;
 }
 
+int jn_average_precision_segments(const double* scores_dev, const int32_t* hits_dev, const int32_t* n_pred_dev,
+                                  const int32_t* n_gt_dev, int U, int max_det, const int32_t* seg_offsets_dev, int NS,
+                                  int max_units, const double* thresholds_dev, int n_thresholds, double* out_dev, void* stream) {
+  JN_CHECK(scores_dev && hits_dev && n_pred_dev && n_gt_dev && seg_offsets_dev && thresholds_dev && out_dev, JN_EINVAL,
+           "jn_average_precision_segments: null argument");
+  JN_CHECK(U >= 1 && max_det >= 1 && NS >= 1 && max_units >= 1, JN_EINVAL, "jn_average_precision_segments: bad shape");
+  JN_CHECK(n_thresholds >= 1 && n_thresholds <= JN_EVAL_MAX_THRESHOLDS, JN_EINVAL,
+           "jn_average_precision_segments: %d thresholds, at most %d", n_thresholds, JN_EVAL_MAX_THRESHOLDS);
+  const long long slots = (long long)max_units * max_det;
+  JN_CHECK(slots <= JN_EVAL_MAX_ENTRIES, JN_EINVAL,
+           "jn_average_precision_segments: a segment of %lld entries (%d units of %d), at most %d", slots, max_units, max_det,
+           JN_EVAL_MAX_ENTRIES);
+  JN_CHECK(launch_average_precision_segments(scores_dev, hits_dev, n_pred_dev, n_gt_dev, U, max_det, seg_offsets_dev, NS, max_units,
+                                             thresholds_dev, n_thresholds, out_dev, (hipStream_t)stream) == 0,
+           JN_EHIP, "jn_average_precision_segments: LDS for %lld entries refused", slots);
+  JN_HIP(hipGetLastError());
+  return JN_OK;
+}
+
+int jn_pool_walk_detections(const float* det_boxes_dev, const int32_t* det_counts_dev, const int64_t* positions_dev,
+                            const int32_t* walk_tokens_dev, const int32_t* walk_first_dev, const int32_t* walk_count_dev, int A,
+                            int T, int S, int K_det, int NI, int max_walks, int Gh, int Gw, int max_per_cell,
+                            float* cell_boxes_dev, int32_t* cell_counts_dev, int32_t* cell_stats_dev, uint8_t* visited_dev,
+                            void* stream) {
+  JN_CHECK(det_boxes_dev && det_counts_dev && positions_dev && walk_tokens_dev && walk_first_dev && walk_count_dev &&
+               cell_boxes_dev && cell_counts_dev && visited_dev,
+           JN_EINVAL, "jn_pool_walk_detections: null argument");
+  JN_CHECK(NI >= 1 && max_per_cell >= 1, JN_EINVAL, "jn_pool_walk_detections: NI=%d max_per_cell=%d, both must be at least 1", NI,
+           max_per_cell);
+  JN_CHECK(A >= 1 && S >= 0 && S <= T && K_det >= 1 && max_walks >= 1 && Gh >= 1 && Gw >= 1 && NI <= 65535, JN_EINVAL,
+           "jn_pool_walk_detections: bad shape");
+  const long long pool = (long long)max_walks * (S + 1) * K_det;
+  JN_CHECK(pool <= JN_EVAL_MAX_BOXES, JN_EINVAL,
+           "jn_pool_walk_detections: a pool of up to %lld boxes per cell (%d walks x %d tokens x %d), the kernel holds at most %d "
+           "in LDS", pool, max_walks, S + 1, K_det, JN_EVAL_MAX_BOXES);
+  JN_CHECK(launch_pool_walk_detections(det_boxes_dev, det_counts_dev, positions_dev, walk_tokens_dev, walk_first_dev,
+                                       walk_count_dev, A, T, S, K_det, NI, max_walks, Gh, Gw, max_per_cell, cell_boxes_dev,
+                                       cell_counts_dev, cell_stats_dev, visited_dev, (hipStream_t)stream) == 0,
+           JN_EHIP, "jn_pool_walk_detections: LDS for %lld boxes refused", pool);
+  JN_HIP(hipGetLastError());
+  return JN_OK;
+}
+
 int jn_env_patches(jn_ctx* ctx, float* out_dev, void* stream) {
   JN_CHECK(ctx && ctx->env.ready && out_dev, JN_ESTATE, "jn_env_init has not been called");
   const EnvState& e = ctx->env;

@@ -318,6 +318,14 @@ int launch_match_detections(const float* preds, const int32_t* pred_counts, int 
                             int32_t* n_pred, int32_t* n_gt, hipStream_t s);
 int launch_average_precision(const double* scores, const int32_t* hits, const int32_t* n_pred, const int32_t* n_gt, int B,
                              int max_det, int pooled, const double* thresholds, int n_thresholds, double* out, hipStream_t s);
+int launch_average_precision_segments(const double* scores, const int32_t* hits, const int32_t* n_pred, const int32_t* n_gt,
+                                      int U, int max_det, const int32_t* seg_offsets, int NS, int max_units,
+                                      const double* thresholds, int n_thresholds, double* out, hipStream_t s);
+// the multistart evaluation's per-cell pool + NMS (jnroll.h: jn_pool_walk_detections), one workgroup per (cell, image)
+int launch_pool_walk_detections(const float* det_boxes, const int32_t* det_counts, const int64_t* positions,
+                                const int32_t* walk_tokens, const int32_t* walk_first, const int32_t* walk_count, int A, int T,
+                                int S, int K, int NI, int max_walks, int Gh, int Gw, int M, float* cell_boxes,
+                                int32_t* cell_counts, int32_t* cell_stats, uint8_t* visited, hipStream_t s);
 
 // ---- decision transformer step (kernels_gpt.hip) -------------------------------------
 struct GptLayerPtrs {

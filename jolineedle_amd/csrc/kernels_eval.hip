@@ -277,17 +277,18 @@ __global__ __launch_bounds__(EV_NT) void match_detections_kernel(const float* __
   }
 }
 
-// Average precision of one segment of the concatenated (score, hit) lists per workgroup: segment s is image s
-// (pooled = 0) or all B images (pooled = 1), entry e of a segment is (image e / max_det, rank e % max_det), present
-// where rank < n_pred.  Order by score descending, ties in concatenation order (Python's stable sorted); cumulative
+// Average precision of one segment of the concatenated (score, hit) lists per workgroup: a segment is `nimg` consecutive
+// images (units) from img0, entry e of a segment is (image img0 + e / max_det, rank e % max_det), present where
+// rank < n_pred.  Order by score descending, ties in concatenation order (Python's stable sorted); cumulative
 // tp, precision = tp / (tp + fp), monotone envelope from the right; at every threshold the precision at the first
 // index with recall >= threshold (0 past the end), summed sequentially in threshold order and divided by their number.
-// Dynamic LDS: double [Npow2] (score, then precision envelope) + int32 [Npow2] (entry, then cumulative tp).
-__global__ __launch_bounds__(EV_NT) void average_precision_kernel(const double* __restrict__ scores, const int32_t* __restrict__ hits,
-                                                                  const int32_t* __restrict__ n_pred,
-                                                                  const int32_t* __restrict__ n_gt, int B, int max_det,
-                                                                  int pooled, int Npow2, const double* __restrict__ thresholds,
-                                                                  int n_thr, double* __restrict__ out) {
+// Dynamic LDS: double [Npow2] (score, then precision envelope) + int32 [Npow2] (entry, then cumulative tp).  Shared by
+// average_precision_kernel (one image or all of them) and average_precision_segments_kernel (a range of units).
+__device__ __forceinline__ void average_precision_segment(const double* __restrict__ scores, const int32_t* __restrict__ hits,
+                                                          const int32_t* __restrict__ n_pred, const int32_t* __restrict__ n_gt,
+                                                          int img0, int nimg, int max_det, int Npow2,
+                                                          const double* __restrict__ thresholds, int n_thr,
+                                                          double* __restrict__ out) {
   extern __shared__ double ap_sm[];
   __shared__ int32_t iscan[2][EV_NT];
   __shared__ double dscan[2][EV_NT];
@@ -297,7 +298,6 @@ __global__ __launch_bounds__(EV_NT) void average_precision_kernel(const double* 
   double* val = ap_sm;
   int32_t* ent = (int32_t*)(ap_sm + Npow2);
   const int tid = threadIdx.x;
-  const int img0 = pooled ? 0 : blockIdx.x, nimg = pooled ? B : 1;
   const int slots = nimg * max_det;
   const long long base = (long long)img0 * max_det;
   if (tid == 0) n_valid = 0, gt_total = 0, icarry = 0;
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(EV_NT) void average_precision_kernel(const double* 
   __syncthreads();
   const int n = n_valid, ngt = gt_total;
   if (n == 0 || ngt <= 0) {                               // map_50: no target / no prediction -> 0
-    if (tid == 0) out[blockIdx.x] = 0.0;
+    if (tid == 0) *out = 0.0;
     return;
   }
   for (int k = 2; k <= Npow2; k <<= 1) {                  // bitonic sort: (score descending, entry ascending)
@@ -391,7 +391,167 @@ __global__ __launch_bounds__(EV_NT) void average_precision_kernel(const double* 
   if (tid == 0) {
     double ap = 0.0;
     for (int t = 0; t < n_thr; ++t) ap += terms[t];
-    out[blockIdx.x] = ap / (double)n_thr;
+    *out = ap / (double)n_thr;
+  }
+}
+
+// segment s is image s (pooled = 0) or all B images (pooled = 1)
+__global__ __launch_bounds__(EV_NT) void average_precision_kernel(const double* __restrict__ scores, const int32_t* __restrict__ hits,
+                                                                  const int32_t* __restrict__ n_pred,
+                                                                  const int32_t* __restrict__ n_gt, int B, int max_det,
+                                                                  int pooled, int Npow2, const double* __restrict__ thresholds,
+                                                                  int n_thr, double* __restrict__ out) {
+  average_precision_segment(scores, hits, n_pred, n_gt, pooled ? 0 : (int)blockIdx.x, pooled ? B : 1, max_det, Npow2, thresholds,
+                            n_thr, out + blockIdx.x);
+}
+
+// segment s is the units seg_offsets[s] .. seg_offsets[s + 1] - 1 (kept inside 0..U and at most max_units long: the LDS
+// was sized for that many)
+__global__ __launch_bounds__(EV_NT) void average_precision_segments_kernel(const double* __restrict__ scores,
+                                                                           const int32_t* __restrict__ hits,
+                                                                           const int32_t* __restrict__ n_pred,
+                                                                           const int32_t* __restrict__ n_gt, int U, int max_det,
+                                                                           const int32_t* __restrict__ seg_offsets, int max_units,
+                                                                           int Npow2, const double* __restrict__ thresholds,
+                                                                           int n_thr, double* __restrict__ out) {
+  const int u0 = min(max(seg_offsets[blockIdx.x], 0), U);
+  const int u1 = min(max(seg_offsets[blockIdx.x + 1], u0), U);
+  average_precision_segment(scores, hits, n_pred, n_gt, u0, min(u1 - u0, max_units), max_det, Npow2, thresholds, n_thr,
+                            out + blockIdx.x);
+}
+
+// Inclusive sum of one int per thread over the workgroup (Hillis-Steele in LDS, as the compactions above); every thread
+// calls it, and the buffer is free again when it returns.
+__device__ __forceinline__ int block_scan_inclusive(int v, int32_t (*scan)[EV_NT], int tid) {
+  int cur = 0;
+  scan[0][tid] = v;
+  __syncthreads();
+  for (int d = 1; d < EV_NT; d <<= 1) {
+    const int s = scan[cur][tid] + (tid >= d ? scan[cur][tid - d] : 0);
+    scan[cur ^ 1][tid] = s;
+    cur ^= 1;
+    __syncthreads();
+  }
+  const int r = scan[cur][tid];
+  __syncthreads();
+  return r;
+}
+
+// The multistart evaluation's pool + NMS (src/supervised.py:573-625) for one (cell, image) per workgroup: the boxes of
+// every token of the image's used walks that stands on the cell, in (walk, token, stored) order, de-duplicated greedily
+// in (score descending, pool index ascending) order at IoU > 0.5 in fp32.  A token slot of the image is
+// e = walk * (S + 1) + t, a box slot r = e * K + k < cap <= JN_EVAL_MAX_BOXES, so both the pool index and r fit 16 bits
+// of the sort key: key = (inverted ordered score) << 32 | pool << 16 | r.  Dynamic LDS: uint64 [cap2] keys, then
+// float [4][cap] x1, y1, x2, y2 at the POOL index (24 B per box where cap is a power of two).
+__global__ __launch_bounds__(EV_NT) void pool_walk_detections_kernel(
+    const float* __restrict__ det_boxes, const int32_t* __restrict__ det_counts, const int64_t* __restrict__ positions,
+    const int32_t* __restrict__ walk_tokens, const int32_t* __restrict__ walk_first, const int32_t* __restrict__ walk_count,
+    int A, int T, int S, int K, int max_walks, int Gw, int M, int cap, int cap2, float* __restrict__ cell_boxes,
+    int32_t* __restrict__ cell_counts, int32_t* __restrict__ cell_stats, uint8_t* __restrict__ visited) {
+  extern __shared__ unsigned long long pw_keys[];
+  __shared__ int32_t scan[2][EV_NT];
+  __shared__ uint32_t dead[JN_EVAL_MAX_BOXES / 32];
+  __shared__ int32_t carry, seen;
+  float* x1 = (float*)(pw_keys + cap2);
+  float* y1 = x1 + cap;
+  float* x2 = y1 + cap;
+  float* y2 = x2 + cap;
+  const int tid = threadIdx.x, c = blockIdx.x, img = blockIdx.y;
+  const int cells = gridDim.x;
+  const long long cy = c / Gw, cx = c % Gw;
+  const int w0 = walk_first[img];
+  const int nw = min(max(walk_count[img], 0), max_walks);
+  const int slots = nw * (S + 1);
+  const long long unit = (long long)img * cells + c;
+  if (tid == 0) carry = 0, seen = 0;
+  for (int i = tid; i < JN_EVAL_MAX_BOXES / 32; i += EV_NT) dead[i] = 0;
+  __syncthreads();
+  // ---- the tokens on this cell and their boxes: pool offsets by a scan over the token slots
+  for (int e0 = 0; e0 < slots; e0 += EV_NT) {
+    const int e = e0 + tid;
+    int cnt = 0;
+    long long tok = 0;
+    if (e < slots) {
+      const int a = w0 + e / (S + 1), t = e % (S + 1);
+      if (a >= 0 && a < A && t < walk_tokens[a]) {
+        tok = (long long)a * (T + 1) + t;
+        if (positions[tok * 2] == cy && positions[tok * 2 + 1] == cx) {
+          seen = 1;
+          cnt = min(max(det_counts[tok], 0), K);
+        }
+      }
+    }
+    const int before = carry;                              // stable since the barrier that ended the last chunk
+    const int incl = block_scan_inclusive(cnt, scan, tid);
+    const int base = before + incl - cnt;
+    for (int k = 0; k < cnt; ++k) {
+      const float* row = det_boxes + (tok * K + k) * 7;
+      const int p = base + k;
+      x1[p] = row[0], y1[p] = row[1], x2[p] = row[2], y2[p] = row[3];
+      // ord_enc orders bit patterns: -0.0 ranks below +0.0 and a NaN by its bits, where the host's stable argsort holds
+      // +-0 equal and puts NaN first.  Scores are sigmoid products in (0, 1], so neither occurs (as in match_detections).
+      pw_keys[p] = ((unsigned long long)(~ord_enc(row[4])) << 32) | ((unsigned)p << 16) | (unsigned)(e * K + k);
+    }
+    if (tid == EV_NT - 1) carry = before + incl;
+    __syncthreads();
+  }
+  const int n = carry;
+  if (n == 0) {                                            // an unvisited cell, or a visited one whose tokens hold no box
+    if (tid == 0) {
+      cell_counts[unit] = 0;
+      visited[unit] = seen ? 1 : 0;
+      if (cell_stats) cell_stats[unit * 2] = 0, cell_stats[unit * 2 + 1] = 0;
+    }
+    return;
+  }
+  int np2 = 1;
+  while (np2 < n) np2 <<= 1;
+  for (int i = n + tid; i < np2; i += EV_NT) pw_keys[i] = ~0ull;
+  __syncthreads();
+  bitonic_sort_u64(pw_keys, np2, tid);
+  // ---- greedy NMS: the kept box of rank p against every later live box, one round per kept box
+  for (int p = 0; p + 1 < n; ++p) {
+    if ((dead[p >> 5] >> (p & 31)) & 1u) continue;          // uniform: written before the last barrier
+    const int pi = (int)((pw_keys[p] >> 16) & 0xFFFFu);
+    const float ax1 = x1[pi], ay1 = y1[pi], ax2 = x2[pi], ay2 = y2[pi];
+    const float area_a = (ax2 - ax1) * (ay2 - ay1);
+    for (int q = p + 1 + tid; q < n; q += EV_NT) {
+      if ((dead[q >> 5] >> (q & 31)) & 1u) continue;
+      const int qi = (int)((pw_keys[q] >> 16) & 0xFFFFu);
+      const float bx1 = x1[qi], by1 = y1[qi], bx2 = x2[qi], by2 = y2[qi];
+      const float w = fmaxf(fminf(ax2, bx2) - fmaxf(ax1, bx1), 0.0f);
+      const float h = fmaxf(fminf(ay2, by2) - fmaxf(ay1, by1), 0.0f);
+      const float inter = w * h;
+      const float area_b = (bx2 - bx1) * (by2 - by1);
+      const float iou = __fdiv_rn(inter, (area_a + area_b) - inter);
+      if (iou > 0.5f) atomicOr(&dead[q >> 5], 1u << (q & 31));      // (a NaN compares false)
+    }
+    __syncthreads();
+  }
+  // ---- the survivors in score order: rows 0 .. min(survivors, M) - 1
+  if (tid == 0) carry = 0;
+  __syncthreads();
+  for (int p0 = 0; p0 < n; p0 += EV_NT) {
+    const int p = p0 + tid;
+    const int live = (p < n && !((dead[p >> 5] >> (p & 31)) & 1u)) ? 1 : 0;
+    const int before = carry;
+    const int incl = block_scan_inclusive(live, scan, tid);
+    const int rank = before + incl - 1;
+    if (live && rank < M) {
+      const int r = (int)(pw_keys[p] & 0xFFFFu);
+      const int e = r / K, k = r % K;
+      const long long tok = (long long)(w0 + e / (S + 1)) * (T + 1) + e % (S + 1);
+      const float* row = det_boxes + (tok * K + k) * 7;
+      float* dst = cell_boxes + (unit * M + rank) * 7;
+      for (int j = 0; j < 7; ++j) dst[j] = row[j];
+    }
+    if (tid == EV_NT - 1) carry = before + incl;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    cell_counts[unit] = min(carry, M);
+    visited[unit] = 1;
+    if (cell_stats) cell_stats[unit * 2] = n, cell_stats[unit * 2 + 1] = carry;
   }
 }
 
@@ -431,6 +591,34 @@ int launch_average_precision(const double* scores, const int32_t* hits, const in
   if (allow_lds(average_precision_kernel, smem)) return 1;
   hipLaunchKernelGGL(average_precision_kernel, dim3(pooled ? 1 : B), dim3(EV_NT), smem, s, scores, hits, n_pred, n_gt, B, max_det,
                      pooled, np2, thresholds, n_thresholds, out);
+  return 0;
+}
+
+int launch_pool_walk_detections(const float* det_boxes, const int32_t* det_counts, const int64_t* positions,
+                                const int32_t* walk_tokens, const int32_t* walk_first, const int32_t* walk_count, int A, int T,
+                                int S, int K, int NI, int max_walks, int Gh, int Gw, int M, float* cell_boxes,
+                                int32_t* cell_counts, int32_t* cell_stats, uint8_t* visited, hipStream_t s) {
+  const int cap = max_walks * (S + 1) * K;
+  int cap2 = 1;
+  while (cap2 < cap) cap2 <<= 1;
+  const size_t smem = (size_t)cap2 * sizeof(unsigned long long) + (size_t)4 * cap * sizeof(float);
+  if (allow_lds(pool_walk_detections_kernel, smem)) return 1;
+  hipLaunchKernelGGL(pool_walk_detections_kernel, dim3(Gh * Gw, NI), dim3(EV_NT), smem, s, det_boxes, det_counts, positions,
+                     walk_tokens, walk_first, walk_count, A, T, S, K, max_walks, Gw, M, cap, cap2, cell_boxes, cell_counts,
+                     cell_stats, visited);
+  return 0;
+}
+
+int launch_average_precision_segments(const double* scores, const int32_t* hits, const int32_t* n_pred, const int32_t* n_gt,
+                                      int U, int max_det, const int32_t* seg_offsets, int NS, int max_units,
+                                      const double* thresholds, int n_thresholds, double* out, hipStream_t s) {
+  const int slots = max_units * max_det;
+  int np2 = 2;
+  while (np2 < slots) np2 <<= 1;
+  const size_t smem = (size_t)np2 * (sizeof(double) + sizeof(int32_t));
+  if (allow_lds(average_precision_segments_kernel, smem)) return 1;
+  hipLaunchKernelGGL(average_precision_segments_kernel, dim3(NS), dim3(EV_NT), smem, s, scores, hits, n_pred, n_gt, U, max_det,
+                     seg_offsets, max_units, np2, thresholds, n_thresholds, out);
   return 0;
 }
 

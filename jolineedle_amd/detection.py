@@ -9,7 +9,7 @@ Reference: ``NeedleGeneralEnv.parse_bboxes / get_detection_targets`` (src/env/ge
 ``Trainer.compute_detection_metrics`` (src/trainer.py:188-248; the reference calls torchmetrics' COCO
 MeanAveragePrecision, which is not vendored — map_50 is restated here from the published COCO protocol and pinned by
 the known answers of the reference's tests/test_map.py: 0, 1 and 0.8)."""
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
@@ -371,3 +371,240 @@ def compute_detection_metrics_device(outputs, targets) -> dict:
     """``compute_detection_metrics`` through ``map_50_device``."""
     dev = targets[1].device if isinstance(targets, tuple) else (targets[0].device if len(targets) else torch.device("cpu"))
     return {"map": torch.tensor([map_50_device(outputs, targets)], dtype=torch.float32, device=dev)}
+
+
+# ---- the multistart evaluation (src/supervised.py:485-636): pool the walks' detections per cell, NMS, mAP per image ------
+def nms_pool(boxes: Tensor) -> List[int]:
+    """Greedy NMS at IoU 0.5 over one pool [n, >= 5] (``nms(bboxes[:, :4], score, 0.5)``, src/supervised.py:552, 624):
+    the rows in (column 4 descending, index ascending) order, a row suppressed when its IoU with a kept row is > 0.5.
+    The IoU is fp32, every operation rounded once: w = max(min(x2) - max(x1), 0), likewise h, inter = w * h,
+    iou = inter / ((area_a + area_b) - inter); a NaN (two zero-area boxes) suppresses nothing.  Returns the kept row
+    indices in that order."""
+    n = len(boxes)
+    if n == 0:
+        return []
+    b = boxes.detach().to("cpu", torch.float32)
+    order = torch.argsort(b[:, 4], descending=True, stable=True)
+    b = b[order]
+    area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    dead = torch.zeros(n, dtype=torch.bool)
+    keep = []
+    for p in range(n):
+        if dead[p]:
+            continue
+        keep.append(int(order[p]))
+        if p + 1 < n:
+            w = (torch.minimum(b[p, 2], b[p + 1:, 2]) - torch.maximum(b[p, 0], b[p + 1:, 0])).clamp(min=0)
+            h = (torch.minimum(b[p, 3], b[p + 1:, 3]) - torch.maximum(b[p, 1], b[p + 1:, 1])).clamp(min=0)
+            inter = w * h
+            dead[p + 1:] |= inter / ((area[p] + area[p + 1:]) - inter) > 0.5
+    return keep
+
+
+def pool_walk_detections(det_boxes: Tensor, det_counts: Tensor, positions: Tensor, walk_tokens: Sequence[int],
+                         walk_first: Sequence[int], walk_count: Sequence[int], grid: Tuple[int, int],
+                         max_per_cell: int) -> dict:
+    """The pooling of ``metrics_from_multiple_samples`` / ``eval_missing_patches`` (src/supervised.py:573-625) on the
+    host, and the statement of the rule ``jn_pool_walk_detections`` computes.  det_boxes [A, S + 1, K, 7], det_counts
+    [A, S + 1], positions [A, S + 1, 2] (y, x) of A walks; walk a owns its first walk_tokens[a] tokens; image i uses the
+    walks walk_first[i] .. walk_first[i] + walk_count[i] - 1.  A cell of the `grid` = (Gh, Gw) is visited when such a
+    token stands on it; its pool is the boxes of all those tokens in (walk, token, stored) order — a walk that returns
+    to a cell contributes its boxes again — de-duplicated by ``nms_pool`` (score = column 4; DESIGN.md §6 on the
+    reference's column) and cut to the first `max_per_cell` survivors.
+
+    Returns {"boxes": per image a list over the Gh * Gw cells of None (not visited) or the survivors [n, 7] fp32 on
+    the CPU, "visited": bool [NI, Gh * Gw], "stats": int32 [NI, Gh * Gw, 2] = (pool size, survivors before the cut)}."""
+    Gh, Gw = int(grid[0]), int(grid[1])
+    boxes, counts, pos = det_boxes.detach().cpu().float(), det_counts.detach().cpu().tolist(), positions.detach().cpu().tolist()
+    tokens = [int(v) for v in (walk_tokens.tolist() if isinstance(walk_tokens, Tensor) else walk_tokens)]
+    first = [int(v) for v in (walk_first.tolist() if isinstance(walk_first, Tensor) else walk_first)]
+    count = [int(v) for v in (walk_count.tolist() if isinstance(walk_count, Tensor) else walk_count)]
+    A, n_tok, M = boxes.shape[0], boxes.shape[1], int(max_per_cell)
+    assert M >= 1 and len(first) == len(count) >= 1
+    out = {"boxes": [], "visited": torch.zeros((len(first), Gh * Gw), dtype=torch.bool),
+           "stats": torch.zeros((len(first), Gh * Gw, 2), dtype=torch.int32)}
+    for i, (w0, nw) in enumerate(zip(first, count)):
+        pools: dict = {}
+        for a in range(max(w0, 0), min(w0 + nw, A)):
+            for t in range(min(tokens[a], n_tok)):
+                y, x = pos[a][t]
+                if 0 <= y < Gh and 0 <= x < Gw:
+                    pools.setdefault(y * Gw + x, []).append(boxes[a, t, :max(0, min(counts[a][t], boxes.shape[2]))])
+        cells: List[Optional[Tensor]] = [None] * (Gh * Gw)
+        for c, parts in pools.items():
+            pool = torch.cat(parts)
+            kept = pool[nms_pool(pool)] if len(pool) else pool
+            out["visited"][i, c] = True
+            out["stats"][i, c] = torch.tensor([len(pool), len(kept)], dtype=torch.int32)
+            cells[c] = kept[:M]
+        out["boxes"].append(cells)
+    return out
+
+
+def pool_walk_detections_device(det_boxes: Tensor, det_counts: Tensor, positions: Tensor, walk_tokens: Tensor,
+                                walk_first: Tensor, walk_count: Tensor, max_walks: int, grid: Tuple[int, int],
+                                max_per_cell: int, stats: bool = True) -> dict:
+    """``pool_walk_detections`` of every (image, cell) in one launch (``jn_pool_walk_detections``), without a readback.
+    The first three arguments are a rollout's "det_boxes" / "det_counts" / "positions" (read in place where they are
+    [:, :S + 1] slices of [A, T + 1, ...] buffers); walk_tokens / walk_first / walk_count int32 on the device; `max_walks`
+    is the host's bound on walk_count.  Returns device tensors {"boxes": fp32 [NI, Gh * Gw, M, 7] (rows beyond a count
+    are not written), "counts": int32 [NI, Gh * Gw], "stats": int32 [NI, Gh * Gw, 2] or None, "visited": bool
+    [NI, Gh * Gw]}.  Beyond ``MAX_EVAL_BOXES`` boxes per pool (max_walks * (S + 1) * K) the kernel does not apply and
+    the host function pools."""
+    from . import _lib
+    from ._lib import check, ptr
+    dev = det_boxes.device
+    A, n, K = det_boxes.shape[0], det_boxes.shape[1], det_boxes.shape[2]
+    S, Gh, Gw, M = n - 1, int(grid[0]), int(grid[1]), int(max_per_cell)
+    NI = int(walk_first.numel())
+    if int(max_walks) * n * K > MAX_EVAL_BOXES:
+        host = pool_walk_detections(det_boxes, det_counts, positions, walk_tokens, walk_first, walk_count, grid, M)
+        boxes = torch.zeros((NI, Gh * Gw, M, 7), dtype=torch.float32)
+        cnt = torch.zeros((NI, Gh * Gw), dtype=torch.int32)
+        for i, cells in enumerate(host["boxes"]):
+            for c, rows in enumerate(cells):
+                if rows is not None and len(rows):
+                    boxes[i, c, :len(rows)], cnt[i, c] = rows, len(rows)
+        return {"boxes": boxes.to(dev), "counts": cnt.to(dev), "stats": host["stats"].to(dev) if stats else None,
+                "visited": host["visited"].to(dev)}
+    T1 = det_counts.stride(0) if A > 1 else n
+    in_place = (det_counts.dtype == torch.int32 and positions.dtype == torch.int64 and det_boxes.dtype == torch.float32
+                and det_counts.stride(1) == 1 and T1 >= n
+                and (A == 1 or (det_boxes.stride(0) == T1 * K * 7 and positions.stride(0) == T1 * 2))
+                and det_boxes[0].is_contiguous() and positions[0].is_contiguous())
+    if not in_place:
+        det_boxes, det_counts, positions, T1 = (det_boxes.float().contiguous(), det_counts.to(torch.int32).contiguous(),
+                                                positions.long().contiguous(), n)
+    i32 = lambda t: t.to(dev, torch.int32).contiguous()
+    walk_tokens, walk_first, walk_count = i32(walk_tokens), i32(walk_first), i32(walk_count)
+    assert walk_tokens.numel() == A and walk_count.numel() == NI
+    out = {"boxes": torch.empty((NI, Gh * Gw, M, 7), device=dev, dtype=torch.float32),
+           "counts": torch.empty((NI, Gh * Gw), device=dev, dtype=torch.int32),
+           "stats": torch.empty((NI, Gh * Gw, 2), device=dev, dtype=torch.int32) if stats else None}
+    vis = torch.empty((NI, Gh * Gw), device=dev, dtype=torch.uint8)
+    check(_lib.load_library().jn_pool_walk_detections(ptr(det_boxes), ptr(det_counts), ptr(positions), ptr(walk_tokens),
+                                                      ptr(walk_first), ptr(walk_count), A, T1 - 1, S, K, NI, int(max_walks), Gh, Gw,
+                                                      M, ptr(out["boxes"]), ptr(out["counts"]), ptr(out["stats"]), ptr(vis),
+                                                      _lib.current_stream(dev)), "jn_pool_walk_detections")
+    out["visited"] = vis.bool()
+    return out
+
+
+def cell_targets(bbox_rows: Sequence[Tensor], extents: Sequence[Sequence[int]], canvas_grid: Tuple[int, int],
+                 patch_size: int, device=None) -> Tuple[Tensor, Tensor]:
+    """Per image and per cell of the canvas grid the targets a patch-level mAP scores against: the rows
+    (0, x1, y1, x2, y2) of ``NeedleSimpleEnv.local_bboxes`` (trajectory.py; the part of every box inside the cell,
+    patch-local, kept where it is more than a line: strict <) with the objectness-0 rows dropped, in box order.
+    bbox_rows[i]: [n_i, 4] xyxy in image i's pixels; extents[i] = (gh, gw), cells outside hold nothing.  Returns fp32
+    [NI, Gh * Gw, nb, 5] and int32 counts [NI, Gh * Gw] (torch ops on `device`, once per chunk, without a readback)."""
+    Gh, Gw, P = int(canvas_grid[0]), int(canvas_grid[1]), int(patch_size)
+    NI = len(bbox_rows)
+    nb = max([1] + [int(r.shape[0]) for r in bbox_rows])
+    rows = torch.zeros((NI, nb, 4), dtype=torch.int64)
+    real = torch.zeros((NI, nb), dtype=torch.bool)
+    for i, r in enumerate(bbox_rows):
+        rows[i, :r.shape[0]], real[i, :r.shape[0]] = r.to(torch.int64).reshape(-1, 4), True
+    ext = torch.as_tensor([[int(e[0]), int(e[1])] for e in extents], dtype=torch.int64).reshape(NI, 2)
+    # every coordinate kept below lies in 0 .. P (the part of a box inside its cell), so P bounds what fp32 must hold
+    assert P < (1 << 24), "integer boxes beyond 2**24 are not exact in fp32"
+    rows, real, ext = rows.to(device), real.to(device), ext.to(device)
+    ys = torch.arange(Gh, device=rows.device).repeat_interleave(Gw)                     # cell c = y * Gw + x
+    xs = torch.arange(Gw, device=rows.device).repeat(Gh)
+    px, py = (xs * P)[None, :, None], (ys * P)[None, :, None]                           # [1, cells, 1]
+    x1, y1, x2, y2 = (rows[:, None, :, k] for k in range(4))                             # [NI, 1, nb]
+    cx1, cy1 = torch.maximum(px, x1), torch.maximum(py, y1)
+    cx2, cy2 = torch.minimum(px + P, x2), torch.minimum(py + P, y2)
+    inside = (ys[None, :] < ext[:, None, 0]) & (xs[None, :] < ext[:, None, 1])          # [NI, cells]
+    valid = (cx1 < cx2) & (cy1 < cy2) & real[:, None, :] & inside[:, :, None]
+    local = torch.stack((torch.zeros_like(cx1), cx1 - px, cy1 - py, cx2 - px, cy2 - py), -1)      # [NI, cells, nb, 5]
+    order = torch.argsort((~valid).to(torch.int8), dim=-1, stable=True)                 # the valid rows first, in box order
+    local = torch.gather(local, 2, order[..., None].expand(-1, -1, -1, 5))
+    counts = valid.sum(-1).to(torch.int32)
+    local = local * (torch.arange(nb, device=rows.device)[None, None, :] < counts[..., None])[..., None]
+    return local.to(torch.float32).contiguous(), counts.contiguous()
+
+
+def average_precision_segments_device(match: dict, seg_offsets: Tensor, max_units: int) -> Tensor:
+    """``jn_average_precision_segments`` over ``match_detections_device``'s result: f64 [NS], segment s = the units
+    seg_offsets[s] .. seg_offsets[s + 1] - 1 (int32 on the device); `max_units` is the host's bound on their number."""
+    from . import _lib
+    from ._lib import check, ptr
+    U, max_det = match["scores"].shape
+    dev = match["scores"].device
+    thr = _recall_thresholds(dev)
+    seg = seg_offsets.to(dev, torch.int32).contiguous()
+    NS = seg.numel() - 1
+    out = torch.zeros((NS,), device=dev, dtype=torch.float64)
+    check(_lib.load_library().jn_average_precision_segments(ptr(match["scores"]), ptr(match["hits"]), ptr(match["n_pred"]),
+                                                            ptr(match["n_gt"]), U, max_det, ptr(seg), NS, int(max_units), ptr(thr),
+                                                            thr.numel(), ptr(out), _lib.current_stream(dev)),
+          "jn_average_precision_segments")
+    return out
+
+
+def map_50_segments(outputs: List[Optional[Tensor]], targets: List[Tensor], seg_offsets: Sequence[int],
+                    max_det: int = 100) -> List[float]:
+    """Per segment ``map_50`` over the units seg_offsets[s] .. seg_offsets[s + 1] - 1 of the two lists (host)."""
+    return [map_50(outputs[a:b], targets[a:b], max_det) for a, b in zip(seg_offsets[:-1], seg_offsets[1:])]
+
+
+def map_50_segments_device(outputs, targets, seg_offsets: Sequence[int], max_det: int = 100, readback: bool = True):
+    """``map_50_segments`` on the device: ``jn_match_detections`` over all units, then ``jn_average_precision_segments``;
+    `outputs` / `targets` in list form or packed (fp32 rows [U, N, W] / [U, Mmax, 5] with int32 counts [U]);
+    `seg_offsets` host integers.  One readback (none with readback=False: the f64 [NS] device tensor is returned).
+    A unit never offers more than its N rows, so min(max_det, N) slots per unit hold every selected prediction; beyond
+    ``MAX_EVAL_ENTRIES`` slots per segment or ``MAX_EVAL_BOXES`` rows per unit the host function evaluates."""
+    seg = [int(v) for v in seg_offsets]
+    n_rows = outputs[0].shape[1] if isinstance(outputs, tuple) else max([0] + [len(o) for o in outputs if o is not None])
+    n_tgts = targets[0].shape[1] if isinstance(targets, tuple) else max([0] + [len(t) for t in targets])
+    U = outputs[0].shape[0] if isinstance(outputs, tuple) else len(outputs)
+    max_units = max([1] + [b - a for a, b in zip(seg[:-1], seg[1:])])
+    det = max(1, min(int(max_det), n_rows))
+    if len(seg) < 2:
+        return [] if readback else torch.zeros((0,), dtype=torch.float64)
+    if U == 0 or n_rows > MAX_EVAL_BOXES or n_tgts > MAX_EVAL_BOXES or max_units * det > MAX_EVAL_ENTRIES:
+        outs = unpack_boxes(*outputs) if isinstance(outputs, tuple) else list(outputs)
+        tgts = ([t if t is not None else targets[0][:0, 0] for t in unpack_boxes(*targets)] if isinstance(targets, tuple)
+                else list(targets))
+        res = map_50_segments(outs, [t.reshape(-1, 5) for t in tgts], seg, max_det)
+        return res if readback else torch.tensor(res, dtype=torch.float64)
+    ap = average_precision_segments_device(match_detections_device(outputs, targets, det), torch.tensor(seg, dtype=torch.int32),
+                                           max_units)
+    return ap.tolist() if readback else ap
+
+
+def walk_cell_maps(pool: dict, targets: Tensor, target_counts: Tensor, target_cells: Tensor, max_det: int = 100) -> List[List[float]]:
+    """The two per-image mAP-50 values of the multistart evaluation from ``pool_walk_detections``' result, on the host:
+    [map_traj, map], each a list over the images.  map_traj (``metrics_from_multiple_samples``): one ``map_50`` over the
+    image's visited cells, each a unit with its survivors as predictions and its ``cell_targets`` as targets.  map
+    (``eval_missing_patches``): the target cells (`target_cells` bool [NI, cells]) that were not visited come first as
+    units without predictions.  Cells in row-major order."""
+    tg, tc = targets.detach().cpu(), target_counts.detach().cpu().tolist()
+    vis, tcell = pool["visited"].cpu().tolist(), target_cells.cpu().tolist()
+    traj, full = [], []
+    for i, cells in enumerate(pool["boxes"]):
+        seen = [c for c in range(len(cells)) if vis[i][c]]
+        missed = [c for c in range(len(cells)) if tcell[i][c] and not vis[i][c]]
+        outs = [cells[c] if cells[c] is not None and len(cells[c]) else None for c in seen]
+        tgts = [tg[i, c, :tc[i][c]] for c in seen]
+        traj.append(map_50(outs, tgts, max_det))
+        full.append(map_50([None] * len(missed) + outs, [tg[i, c, :tc[i][c]] for c in missed] + tgts, max_det))
+    return [traj, full]
+
+
+def walk_cell_maps_device(pool: dict, targets: Tensor, target_counts: Tensor, target_cells: Tensor, max_det: int = 100) -> Tensor:
+    """``walk_cell_maps`` on the device from ``pool_walk_detections_device``'s result: f64 [2, NI] without a readback.
+    Per variant one ``jn_match_detections`` over all NI * cells units and one ``jn_average_precision_segments`` with one
+    segment per image; a cell that is not counted has its target count zeroed (and, unvisited, holds no prediction), so
+    it adds nothing to either side."""
+    NI, cells, M, W = pool["boxes"].shape
+    dev = pool["boxes"].device
+    preds = (pool["boxes"].view(NI * cells, M, W), pool["counts"].view(NI * cells))
+    tg = targets.to(dev).view(NI * cells, -1, 5)
+    tcounts, vis = target_counts.to(dev), pool["visited"]
+    seg = [i * cells for i in range(NI + 1)]
+    res = []
+    for counted in (vis, vis | target_cells.to(dev)):
+        tc = (tcounts * counted.to(torch.int32)).view(NI * cells).contiguous()
+        res.append(map_50_segments_device(preds, (tg, tc), seg, max_det, readback=False).to(dev))
+    return torch.stack(res)

@@ -83,6 +83,30 @@ def loop_start_positions(trainer, first_rollout: int, indices: Sequence[int], ex
     return torch.tensor(out, dtype=torch.int64)
 
 
+EVAL_MODES = ("multistart", "corners", "rollouts")
+
+
+def walk_start_positions(trainer, first_rollout: int, indices: Sequence[int], extents: Sequence[Sequence[int]], n_walks: int,
+                         eval_mode: str = "multistart") -> Tensor:
+    """[n, K, 2] the starts of the K walks of every image in ``eval_envs`` (src/supervised.py:668-690), image
+    indices[j] with grid extents[j] = (gh, gw):
+    "multistart" — walk (i, k) is rollout number first_rollout + i * K + k of the per-image loop and starts where that
+    rollout's random reset would (``loop_start_positions``); "rollouts" — every walk of image i starts where its walk 0
+    does under "multistart"; "corners" — the corners of the image's own grid in ``iter_corners`` order
+    (src/env/simple_env.py:46-52): (0, 0), (gh - 1, 0), (gh - 1, gw - 1), (0, gw - 1), so K = 4."""
+    K = int(n_walks)
+    if eval_mode == "multistart":
+        walks = [i * K + k for i in indices for k in range(K)]
+        return loop_start_positions(trainer, first_rollout, walks, [e for e in extents for _ in range(K)]).reshape(-1, K, 2)
+    if eval_mode == "rollouts":
+        return loop_start_positions(trainer, first_rollout, [i * K for i in indices], extents).unsqueeze(1).repeat(1, K, 1)
+    if eval_mode == "corners":
+        assert K == 4, "the corners mode walks every image from its four corners"
+        return torch.tensor([[[0, 0], [gh - 1, 0], [gh - 1, gw - 1], [0, gw - 1]] for gh, gw in extents],
+                            dtype=torch.int64).reshape(-1, 4, 2)
+    raise ValueError(f"eval_mode must be one of {EVAL_MODES}, got {eval_mode!r}")
+
+
 def own_steps(rollout: Dict) -> List[int]:
     """Per image the step count its own ``B = 1`` rollout reports: the first t >= 1 with masks[b, t] == 0, else all S."""
     masks = rollout["masks"]

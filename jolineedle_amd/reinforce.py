@@ -513,12 +513,22 @@ class ReinforceTrainer:
     @torch.no_grad()
     def _eval_image_chunks(self, images, bboxes, batch_size: int, do_detection: bool = None, merge_bboxes: bool = None,
                            device_metrics: bool = False, sample_actions: bool = False, token_positions: str = None,
-                           teacher_targets=None) -> list:
+                           teacher_targets=None, walks: int = 1, walk_starts=None, chunk_metrics=None) -> list:
         """The chunked rollouts behind ``eval_on_images`` (and ``SupervisedTrainer.eval_on_images``): per image, in image
         order, (the metrics that do not come from ``compute_metrics``, the image's own ``B = 1`` rollout).
         teacher_targets: a callable (box rows of the chunk's images, their grid extents, the canvas grid) -> uint8
         [n, Gh, Gw]; the rollouts then carry "teacher_sets" and "teacher_targets", and the found-ratios count these
-        cells instead of the env's bbox masks."""
+        cells instead of the env's bbox masks.
+
+        walks = K > 1 (``SupervisedTrainer.eval_envs_on_images``): a chunk of n images runs as n * K agents, agents
+        i * K .. i * K + K - 1 walking image i — the same stored image, one view-table row per walk with the same source
+        pointer — and the result lists one entry per WALK, in image order then walk order; `batch_size` still counts
+        images and n * K stays within the model's max_batch.  Walk (i, j) starts where rollout first + i * K + j of the
+        per-image loop would (``ragged.loop_start_positions``), or at walk_starts(first, image indices, their extents)
+        -> [n, K, 2]; the rollout counter ends at first - 1 + len(images) * K.
+        chunk_metrics: a callable(chunk) called once per chunk with {"indices", "env", "rollout", "steps", "extents"
+        (per agent), "rows", "walks", "targets" (the teacher grid per agent or None)} in place of the per-image detection
+        metrics (`map`, `yolo_*`), which are then not computed."""
         from .detection import (detection_targets, map_50_device, merge_boxes_device, pack_boxes, rollout_boxes_packed,
                                 split_bboxes_over_patches, unpack_boxes)
         from .ragged import (env_metrics, found_ratios, image_env, loop_start_positions, own_steps, plan_chunks,
@@ -530,23 +540,49 @@ class ReinforceTrainer:
             merge_bboxes = bool(getattr(cfg, "merge_bboxes", False))
         rows = [torch.as_tensor(b).reshape(-1, 4).to(torch.long) for b in bboxes]
         assert len(rows) == len(images)
-        per_image = [None] * len(images)
+        K = int(walks)
+        assert K >= 1
+        per_image = [None] * (len(images) * K)
         first = self._rollouts + 1                        # eval_on_batch on image i alone would be rollout first + i
-        for chunk in plan_chunks(images, batch_size, P, getattr(self.model, "max_batch", None)):
-            sel = chunk["indices"]
-            imgs = [images[i] if images[i].dtype == torch.uint8 else images[i].float() for i in sel]
-            env = image_env(self, imgs, [rows[i] for i in sel], canvas=chunk["canvas"])
+        max_batch = getattr(self.model, "max_batch", None)
+        for chunk in plan_chunks(images, batch_size, P, max_batch if max_batch is None or K == 1 else int(max_batch) // K):
+            imgs_of = chunk["indices"]
+            if K == 1:
+                sel = imgs_of
+                imgs = [images[i] if images[i].dtype == torch.uint8 else images[i].float() for i in sel]
+            else:
+                # one upload per image; its K walks hand the SAME tensor to the env, so their views share one source
+                sel = [i * K + j for i in imgs_of for j in range(K)]
+                once = {i: images[i].to(self.device) if images[i].dtype == torch.uint8 else images[i].to(self.device, torch.float32)
+                        for i in imgs_of}
+                imgs = [once[a // K] for a in sel]
+            env = image_env(self, imgs, [rows[a // K] for a in sel], canvas=chunk["canvas"])
             extents = env.grid_extents.tolist()
             kw, tg_grid = {}, None
             if teacher_targets is not None:
-                tg_grid = teacher_targets([rows[i] for i in sel], extents, (env.n_vertical_patches, env.n_horizontal_patches))
+                tg_grid = teacher_targets([rows[i] for i in imgs_of], extents[::K], (env.n_vertical_patches, env.n_horizontal_patches))
                 tg_grid = tg_grid.to(self.device)                 # uploaded once per chunk
+                if K > 1:
+                    tg_grid = tg_grid.repeat_interleave(K, 0)
                 kw = dict(teacher=True, teacher_targets=tg_grid)
+            if walk_starts is not None:
+                starts = torch.as_tensor(walk_starts(first, imgs_of, extents[::K])).reshape(len(sel), 2).to(torch.int64)
+            else:
+                starts = loop_start_positions(self, first, sel, extents)
             ro = self.rollout(env, sample_actions=sample_actions, do_detection=do_detection, bbox_lists=False,
-                              start_positions=loop_start_positions(self, first, sel, extents),
-                              token_positions=token_positions, **kw)
+                              start_positions=starts, token_positions=token_positions, **kw)
             steps = own_steps(ro)
             found = found_ratios(env, ro, steps, masks=None if tg_grid is None else tg_grid.bool())
+            if chunk_metrics is not None:
+                chunk_metrics({"indices": imgs_of, "env": env, "rollout": ro, "steps": steps, "extents": extents, "rows": rows,
+                               "walks": K, "targets": tg_grid})
+                for b, i in enumerate(sel):
+                    ro_b = slice_rollout(ro, b, steps[b])
+                    if tg_grid is not None:
+                        ro_b["teacher_targets"] = tg_grid[b:b + 1]
+                    per_image[i] = (dict(env_metrics(self, found, ro_b, b)), ro_b)
+                continue
+            assert K == 1, "several walks per image are evaluated by a chunk_metrics callable"
             packed = rollout_boxes_packed(ro, P) if do_detection else None
             if do_detection and device_metrics:
                 tg = pack_boxes([detection_targets(rows[i].unsqueeze(0), *extents[b], P)[0] for b, i in enumerate(sel)], 5,
@@ -578,5 +614,5 @@ class ReinforceTrainer:
                 else:
                     metrics.update(self._detection_eval_metrics([full[b]], detection_targets(box, gh, gw, P), patches,
                                                                 patch_targets, merge_bboxes))
-        self._rollouts = first - 1 + len(images)          # where that loop leaves the counter
+        self._rollouts = first - 1 + len(images) * K      # where that loop leaves the counter
         return per_image

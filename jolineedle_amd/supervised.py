@@ -2,8 +2,9 @@
 (src/supervised.py:138-177 loss, :863-902 step) over ``jn_supervised_step``, fed by teacher trajectories
 (``generate_trajectories``, src/supervised.py:95-136, over trajectory.NeedleSimpleEnv) whose patches are gathered on
 the device, and followed by the detector step on the trajectories' detector patches (src/supervised.py:881-902).
-``eval_on_images`` is the free-running half of ``test()`` (src/supervised.py:279-405) on the engine's rollout; the rest of
-the evaluation suite is out of scope; augmentation is opt-in (``init_detection``)."""
+``eval_on_images`` is the free-running half of ``test()`` (src/supervised.py:279-405) on the engine's rollout and
+``eval_envs_on_images`` the multistart evaluation that selects the best checkpoint (``eval_envs``, :638-752); the
+teacher-forced ``eval_supervised`` is out of scope; augmentation is opt-in (``init_detection``)."""
 import ctypes as C
 from typing import Dict, Optional, Tuple
 
@@ -270,11 +271,17 @@ class SupervisedTrainer:
         ``last_return_values`` of no trainer is touched.  ``self.last_eval_rollouts`` keeps, per image, the small
         part of its walk on the host (actions, positions, logits, teacher_sets, teacher_targets).  Deviations from the
         reference: DESIGN.md §6."""
-        from .trajectory import simple_env_targets, teacher_agreement
-        runner = self._eval_runner()
-        P = int(self.config.patch_size)
         if do_detection is None:
             do_detection = bool(getattr(self.config, "detection_enabled", True)) and self.yolox_model() is not None
+        return self._walk_metrics(self._eval_walks(images, bboxes, batch_size, do_detection, merge_bboxes, device_metrics,
+                                                   sample_actions=sample_actions))
+
+    def _eval_walks(self, images, bboxes, batch_size, do_detection, merge_bboxes, device_metrics, **kw) -> list:
+        """The free-running walks of both evaluations: ``ReinforceTrainer._eval_image_chunks`` in sequence-position mode
+        with the teacher armed on the simple env's target cells, the model in eval mode (src/supervised.py:294)."""
+        from .trajectory import simple_env_targets
+        runner = self._eval_runner()
+        P = int(self.config.patch_size)
 
         def target_grids(rows, extents, canvas):
             grid = torch.zeros((len(rows), *canvas), dtype=torch.uint8)
@@ -283,16 +290,19 @@ class SupervisedTrainer:
             return grid
 
         was_training = self.model.training
-        self.model.eval()                                  # src/supervised.py:294
+        self.model.eval()
         try:
-            per_image = runner._eval_image_chunks(images, bboxes, batch_size, do_detection, merge_bboxes, device_metrics,
-                                                  sample_actions=sample_actions, token_positions="sequence",
-                                                  teacher_targets=target_grids)
+            return runner._eval_image_chunks(images, bboxes, batch_size, do_detection, merge_bboxes, device_metrics,
+                                             token_positions="sequence", teacher_targets=target_grids, **kw)
         finally:
             self.model.train(was_training)
+
+    def _walk_metrics(self, per_walk: list) -> Dict[str, list]:
+        """The per-walk entries of ``eval_on_images`` from ``_eval_walks``' result; fills ``last_eval_rollouts``."""
+        from .trajectory import teacher_agreement
         out: Dict[str, list] = {}
         self.last_eval_rollouts = []
-        for tail, ro_b in per_image:
+        for tail, ro_b in per_walk:
             walk = {k: ro_b[k][0].cpu() for k in ("actions", "positions", "logits", "teacher_sets", "teacher_targets")}
             self.last_eval_rollouts.append(walk)
             y, x = walk["positions"][-1].tolist()
@@ -302,6 +312,115 @@ class SupervisedTrainer:
             m.update({k: v for k, v in tail.items() if k == "map" or k.startswith("yolo_")})
             for k, v in m.items():
                 out.setdefault(k, []).append(float(v))
+        return out
+
+    @torch.no_grad()
+    def eval_envs_on_images(self, images, bboxes, batch_size: int, eval_mode: str = "multistart", n_starts: int = 2,
+                            sample_actions: bool = False, start_positions=None, device_metrics: bool = True) -> Dict[str, list]:
+        """``eval_envs`` of the reference (src/supervised.py:638-752) without its plots — the evaluation whose `map` at one
+        start selects ``checkpoint_best.pt`` (:81, :804): every image is walked from K starts and, for every prefix
+        k = 1..K of those walks, the detections of the walks are pooled per visited patch, de-duplicated by an NMS at
+        IoU 0.5 and scored per patch against the patch-local pieces of the boxes
+        (``metrics_from_multiple_samples``, :569-636, and ``eval_missing_patches``, :485-567).
+
+        The K walks of `batch_size` images run as ONE ragged rollout of batch_size * K agents (agents i * K .. i * K + K - 1
+        read image i's one stored copy), exactly as ``eval_on_images`` runs its walks (sequence positions, teacher armed).
+        eval_mode: "multistart" (K = n_starts random starts, each where the per-image loop's reset would put it),
+        "corners" (K = 4, the corners of the image's own grid) or "rollouts" (K = n_starts walks from walk 0's start;
+        meaningful with sample_actions); start_positions [n_images, K, 2] overrides the mode's starts (and its K).  The
+        tokens of a walk are t = 0 .. its own steps, the last patch reached included (:354-363).
+
+        Returns lists.  One entry per WALK, in image order then walk order (:694-695): `prop_patches_found`,
+        `episode_length`, `teacher_agreement`, `stopped_inside_bbox` as ``eval_on_images`` reports them.  One entry per
+        IMAGE for every k = 1..K, suffix "" for k = 1 and f"_{eval_mode}_{k}" otherwise (:697-710):
+          `map_traj{suffix}`                 mAP-50 over the cells the first k walks visited (targets: ``detection.cell_targets``)
+          `prop_patches_found_traj{suffix}`  |visited ∩ target cells| / |target cells| (0 without target cells)
+          `map{suffix}`                      the same mAP with every target cell no walk reached counted as well: its
+                                             targets, no predictions (false negatives)
+        An image whose counted cells hold no target gives 0 (:225-230).  All `map*` values are stored as fp32.
+        device_metrics=True: per k one ``jn_pool_walk_detections`` launch, per variant one ``jn_match_detections`` over all
+        cells of the chunk and one ``jn_average_precision_segments``; one readback per chunk (values and pool stats as one
+        tensor).  The buffers are read up to the chunk's longest walk, so a pool of k walks holds at most
+        k * (longest walk + 1) * max_det_per_patch boxes; beyond 4096 (at the defaults, 64 boxes per patch and 21 tokens:
+        k >= 4, i.e. the last prefix of "corners" unless every walk stops early) that prefix is pooled by the host
+        function, with readbacks of its own.  False: the same values from ``detection.pool_walk_detections`` and
+        ``detection.map_50`` on the host.  At most ``config.eval_max_per_cell`` (``--eval-max-per-cell``, 64) survivors
+        per cell are scored; ``last_eval_pool_stats`` keeps, per chunk, the [K, n, cells, 2] pool sizes and survivor
+        counts that show whether the cap was reached.  ``last_eval_rollouts`` keeps the walks, K per image.
+        Deviations from the reference: DESIGN.md §6."""
+        from . import detection, ragged
+        if eval_mode not in ragged.EVAL_MODES:
+            raise ValueError(f"eval_mode must be one of {ragged.EVAL_MODES}, got {eval_mode!r}")
+        if self.yolox_model() is None:
+            raise ValueError("eval_envs_on_images scores detections: the model has no detector")
+        runner = self._eval_runner()
+        P = int(self.config.patch_size)
+        M = int(getattr(self.config, "eval_max_per_cell", 64))
+        given = None
+        if start_positions is not None:
+            given = torch.as_tensor(start_positions).to(torch.int64).cpu()
+            assert given.dim() == 3 and given.shape[0] == len(images) and given.shape[2] == 2, "start_positions is [n_images, K, 2]"
+            K = int(given.shape[1])
+        else:
+            K = 4 if eval_mode == "corners" else int(n_starts)
+        assert K >= 1
+        names = ["" if k == 1 else f"_{eval_mode}_{k}" for k in range(1, K + 1)]
+        per_image: Dict[int, dict] = {}
+        self.last_eval_pool_stats = []
+
+        def starts(first, indices, extents):
+            if given is not None:
+                return given[list(indices)]
+            return ragged.walk_start_positions(runner, first, indices, extents, K, eval_mode)
+
+        def chunk_metrics(ch):
+            ro, env, sel = ch["rollout"], ch["env"], ch["indices"]
+            n, grid = len(sel), (env.n_vertical_patches, env.n_horizontal_patches)
+            dev = self.device
+            tokens = torch.tensor([s + 1 for s in ch["steps"]], dtype=torch.int32)
+            walk_first = torch.arange(n, dtype=torch.int32) * K
+            tg, tcounts = detection.cell_targets([ch["rows"][i] for i in sel], ch["extents"][::K], grid, P,
+                                                 device=dev if device_metrics else None)
+            target_cells = ch["targets"][::K].reshape(n, -1).bool()
+            n_tok = max(ch["steps"]) + 1                   # the kernel's LDS bound is k * n_tok * K_det: the longest walk, not T + 1
+            args = tuple(ro[name][:, :n_tok] for name in ("det_boxes", "det_counts", "positions"))        # read in place
+            tokens_d, first_d = (tokens.to(dev), walk_first.to(dev)) if device_metrics else (None, None)
+            stats, values = [], []
+            for k in range(1, K + 1):
+                walk_count = torch.full((n,), k, dtype=torch.int32)
+                if device_metrics:
+                    pool = detection.pool_walk_detections_device(*args, tokens_d, first_d, walk_count.to(dev), k, grid, M)
+                    maps = detection.walk_cell_maps_device(pool, tg, tcounts, target_cells)
+                    vis = pool["visited"]
+                    counts = torch.stack(((vis & target_cells).sum(1), target_cells.sum(1))).to(torch.float64)
+                    values.append(torch.cat((maps.to(dev), counts)))                     # [4, n] f64
+                else:
+                    pool = detection.pool_walk_detections(*args, tokens, walk_first, walk_count, grid, M)
+                    maps = torch.tensor(detection.walk_cell_maps(pool, tg, tcounts, target_cells.cpu()), dtype=torch.float64)
+                    tc = target_cells.cpu()
+                    counts = torch.stack(((pool["visited"] & tc).sum(1), tc.sum(1))).to(torch.float64)
+                    values.append(torch.cat((maps, counts)))
+                stats.append(pool["stats"])
+            values, stats = torch.stack(values), torch.stack(stats)
+            # the chunk's one readback: the values and the stats (int32, exact in f64) leave the device as one tensor
+            flat = torch.cat((values.flatten(), stats.flatten().to(torch.float64))).cpu()
+            self.last_eval_pool_stats.append(flat[values.numel():].to(torch.int32).reshape(stats.shape))
+            values = flat[:values.numel()].reshape(values.shape).tolist()
+            f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))
+            for b, i in enumerate(sel):
+                m = {}
+                for name, (map_traj, map_all, hit, tot) in zip(names, values):
+                    m["map_traj" + name] = f32(map_traj[b])
+                    m["prop_patches_found_traj" + name] = f32(int(hit[b]) / int(tot[b])) if int(tot[b]) > 0 else 0.0
+                    m["map" + name] = f32(map_all[b])
+                per_image[i] = m
+
+        out = self._walk_metrics(self._eval_walks(images, bboxes, batch_size, True, False, device_metrics,
+                                                  sample_actions=sample_actions, walks=K, walk_starts=starts,
+                                                  chunk_metrics=chunk_metrics))
+        for i in range(len(images)):
+            for k, v in per_image[i].items():
+                out.setdefault(k, []).append(v)
         return out
 
     def train_step(self, patches, current_actions, next_actions, positions, masks, optimizer_step: bool = True,
