@@ -125,6 +125,15 @@ int jn_destroy(jn_ctx* ctx);
 /* ---- weights: nn.Module.state_dict()/load_state_dict of GPT (main.py:532-584) ---- */
 int jn_param_count(const jn_ctx* ctx);
 int jn_param_info_at(const jn_ctx* ctx, int index, jn_param_info* out);
+/* Debugging aid, no device needed: the plan of one conv-stack forward pass of `net` over N patches (train / eval,
+ * with the detection head or not, from op `first_op` on), as the pass itself forms it.  Writes up to `cap` triples
+ * (route, link, deferred) to `out`, one per op, and returns the number of ops of the pass (or a negative error).
+ * route: 1 stem, 2 conv (1x1 / depthwise / dense 3x3 by the op), 3 fused DWConv, 4 fused DWConv + shortcut add,
+ * 5 absorbed by the fused kernel of op `link`, 6 spp, 7 upsample, 8 shortcut add, 9 predictors.  link (an op index, -1:
+ * none): of route 3 / 4 the pointwise op; of an fp32 1x1 conv the upsample whose copy its kernel may write.  deferred:
+ * the layer's BatchNorm table is left to its consumers in this pass. */
+int jn_debug_forward_plan(const jn_ctx* ctx, int net, int N, int train, int with_head, int first_op, int32_t* out,
+                          int cap);
 /* Uploads and pre-packs (BN folded for eval, Linear weights transposed).  Entries the
  * path does not use are ignored; a missing used entry -> JN_ENOTFOUND.  Synchronises. */
 int jn_load_weights(jn_ctx* ctx, const jn_tensor* tensors, size_t n);

@@ -72,6 +72,7 @@ SIGNATURES = {
     "jn_destroy": (C.c_int, [C.c_void_p]),
     "jn_param_count": (C.c_int, [C.c_void_p]),
     "jn_param_info_at": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(JnParamInfo)]),
+    "jn_debug_forward_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "jn_load_weights": (C.c_int, [C.c_void_p, C.POINTER(JnTensor), C.c_size_t]),
     "jn_env_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                               C.c_int, C.c_void_p]),

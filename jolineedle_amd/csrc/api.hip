@@ -5,7 +5,6 @@
 #include <cstdarg>
 #include <cstring>
 #include <memory>
-#include <set>
 
 #include "jn_internal.h"
 
@@ -26,20 +25,6 @@ int build_head(Net& net, std::vector<ParamEntry>& params, const std::string& pre
                int num_classes);
 
 namespace {
-
-void add_param(std::vector<ParamEntry>& params, const std::string& name, std::initializer_list<int64_t> shape,
-               int dtype, bool buffer, bool used) {
-  ParamEntry e;
-  std::memset(&e, 0, sizeof(e));
-  std::snprintf(e.info.name, sizeof(e.info.name), "%s", name.c_str());
-  e.info.dtype = dtype;
-  e.info.ndim = (int)shape.size();
-  int i = 0;
-  for (auto s : shape) e.info.shape[i++] = s;
-  e.info.is_buffer = buffer;
-  e.info.used = used;
-  params.push_back(e);
-}
 
 template <typename T>
 int dev_alloc(jn_ctx* ctx, T** out, size_t count) {
@@ -297,6 +282,37 @@ inline ChanTab view_tab(const Net& net, int slot, const View& v) {
   float* t = net.tab + (size_t)slot * 3 * net.tab_channels + net.tab_off[v.buf] + v.coff;
   return ChanTab{t, t + net.tab_channels, t + 2 * net.tab_channels};
 }
+// Train-mode pass over N patches that defers: the channel runs of view v for the kernel arguments (ChanTab::r0..r3; at
+// most four: a concat of a few producers; more: nseg = 0 and the kernels read the arrays).  False, t untouched: no
+// channel of the view has its table deferred at this N.  Needs the host descriptors of ensure_defer_tables.
+inline bool defer_tab_runs(const Net& net, const View& v, int N, ChanTab& t) {
+  const int off = net.tab_off[v.buf] + v.coff;
+  auto deferred = [&](int c) { return net.h_td_hw[off + c] > 0.0f && (double)N * net.h_td_hw[off + c] <= (double)JN_DEFER_MAX_M; };
+  bool any = false;
+  for (int c = 0; c < v.C && !any; ++c) any = deferred(c);
+  if (!any) return false;
+  int ns = 0;
+  bool fits = true;
+  for (int c = 0; c < v.C && fits;) {
+    const int tc = off + c;
+    const bool d = deferred(c);
+    int e = c + 1;
+    if (d) {
+      while (e < v.C && net.h_td_src[off + e] == net.h_td_src[tc] + (e - c) && net.h_td_goff[off + e] == net.h_td_goff[tc] + (e - c) &&
+             net.h_td_boff[off + e] == net.h_td_boff[tc] + (e - c) && net.h_td_hw[off + e] == net.h_td_hw[tc])
+        ++e;
+    } else {
+      while (e < v.C && !deferred(e)) ++e;
+    }
+    if (ns == 4) { fits = false; break; }
+    const ChanTab::Run run{c, e, d ? net.h_td_src[tc] : -1, net.h_td_goff[tc], net.h_td_boff[tc], net.h_td_hw[tc]};
+    (ns == 0 ? t.r0 : ns == 1 ? t.r1 : ns == 2 ? t.r2 : t.r3) = run;
+    ++ns;
+    c = e;
+  }
+  t.nseg = fits ? ns : 0;
+  return true;
+}
 inline double* slot_stats(const Net& net, int slot) { return net.stats + (size_t)slot * JN_NREP * 2 * net.stat_channels; }
 inline float* slot_save(const Net& net, int slot) { return net.save + (size_t)slot * 2 * net.stat_channels; }
 
@@ -368,6 +384,20 @@ int jn_create(const jn_config* cfg, jn_ctx** out) {
   std::vector<BwdStep> plan;
   if (ctx->enc_net != JN_NET_DETECTOR && (rc = plan_backward(ctx->nets[ctx->enc_net], false, 0x3, plan))) return rc;
   if (cfg->with_detector && (rc = plan_backward(ctx->nets[JN_NET_DETECTOR], true, 0, plan))) return rc;
+  // ... and the forward passes each net will run (run_net plans again per call), at both ends of the batch range: the
+  // PAFPN in eval and train mode, with a head also the whole detector and the head-only range of its training step
+  std::vector<FwdStep> fplan;
+  for (int ni = 0; ni < 2; ++ni) {
+    const Net& net = ctx->nets[ni];
+    const bool head = net.n_backbone_ops >= 0;
+    if (!ctx->has_net[ni]) continue;
+    for (int N : {1, cfg->max_batch})
+      for (int train = 0; train < 2; ++train) {
+        if ((rc = plan_forward(net, N, train, false, 0, train && defer_eligible(net), fplan))) return rc;
+        if (head && (rc = plan_forward(net, N, train, true, 0, false, fplan))) return rc;
+        if (head && !train && (rc = plan_forward(net, N, false, true, net.n_backbone_ops, false, fplan))) return rc;
+      }
+  }
   if (!cfg->no_patch_emb) {
     const Net& enc = ctx->nets[ctx->enc_net];
     ctx->efpn_cin = enc.fpn[2].C; ctx->efpn_h = enc.fpn[2].H; ctx->efpn_w = enc.fpn[2].W;
@@ -424,6 +454,20 @@ int jn_param_info_at(const jn_ctx* ctx, int index, jn_param_info* out) {
   JN_CHECK(ctx && out && index >= 0 && index < (int)ctx->params_tab.size(), JN_EINVAL, "jn_param_info_at: bad index %d", index);
   *out = ctx->params_tab[index].info;
   return JN_OK;
+}
+
+// The forward plan of one pass as run_net would form it (plan.cpp: plan_forward; needs no device): (route, link,
+// deferred) of each op from first_op on, at most `cap` triples.  Returns the number of ops of the pass, or an error.
+int jn_debug_forward_plan(const jn_ctx* ctx, int net, int N, int train, int with_head, int first_op, int32_t* out, int cap) {
+  JN_CHECK(ctx && net >= 0 && net < 2 && ctx->has_net[net] && (out || cap <= 0), JN_EINVAL, "jn_debug_forward_plan: bad argument");
+  const Net& n = ctx->nets[net];
+  std::vector<FwdStep> plan;
+  const int rc = plan_forward(n, N, train != 0, with_head != 0, first_op, train && !with_head && defer_eligible(n), plan);
+  if (rc) return rc;
+  for (int i = 0; i < (int)plan.size() && i < cap; ++i) {
+    out[3 * i] = plan[i].route; out[3 * i + 1] = plan[i].link; out[3 * i + 2] = plan[i].deferred;
+  }
+  return (int)plan.size();
 }
 
 // (scale, shift, flag) of BN channels from the running statistics (eval mode)
@@ -497,6 +541,33 @@ static int refresh_eval_table(jn_ctx* ctx, Net& net, hipStream_t s) {
   return JN_OK;
 }
 
+// fp32 passes: the 1x1 weights of `net` as three bf16 planes for pw_x3_kernel (bf16 inference mode uses the h plane
+// alone: pw_x1).  Split again only after something wrote the arena (mark_params_written): a rollout's T passes and
+// every eval pass in between reuse the planes (for yolox-s / -m detectors the split is tens of MB per pass).
+static void refresh_x3_planes(jn_ctx* ctx, Net& net, hipStream_t s) {
+  if (net.x3_hi == 0) {
+    size_t lo = ctx->arena_size, hi = 0;
+    for (const Op& op : net.ops) {
+      if (op.kind != OP_PW || op.wslot < 0) continue;
+      const ConvW& cw = net.convs[op.wslot];
+      if (!cw.w_dev) continue;
+      const size_t o = (size_t)(cw.w_dev - ctx->params);
+      lo = std::min(lo, o); hi = std::max(hi, o + (size_t)cw.cout * cw.cin);
+    }
+    net.x3_lo = lo / 8 * 8; net.x3_hi = hi > lo ? (hi + 7) / 8 * 8 : 0;
+  }
+  if (net.x3_hi > net.x3_lo && net.x3_dirty) {
+    launch_w_split3(ctx->params + net.x3_lo, ctx->params_x3 + 3 * net.x3_lo, (long long)(net.x3_hi - net.x3_lo), s);
+    net.x3_dirty = false;
+  }
+}
+
+// Something wrote the parameter arena (jn_load_weights, an optimiser step, jn_import_arena): BN affine and 1x1 weights
+// may have moved, so the slot-0 tables and the split-bf16 planes of both nets are stale.
+static void mark_params_written(jn_ctx* ctx) {
+  for (Net& net : ctx->nets) net.eval_tab_dirty = net.x3_dirty = true;
+}
+
 // Device-side workspaces; allocated on the first jn_load_weights (needs a GPU).
 static int alloc_workspaces(jn_ctx* ctx) {
   jn_ctx& x = *ctx;
@@ -555,22 +626,12 @@ int jn_load_weights(jn_ctx* ctx, const jn_tensor* tensors, size_t n) {
       int r = pack_conv(ctx, tm, net.convs[op.wslot], op.kind);
       if (r) return r;
     }
-    net.eval_tab_dirty = true;
-    net.x3_dirty = true;
     for (const Op& op : net.ops) {
       if (op.kind != OP_PRED) continue;
       const std::string k = std::to_string(op.level), hp = "yolox.head.";
       const int hid = net.head_hid;
-      const float* rw = tm.f32(hp + "reg_preds." + k + ".weight", (size_t)4 * hid);
-      const float* rb = tm.f32(hp + "reg_preds." + k + ".bias", 4);
-      const float* ow = tm.f32(hp + "obj_preds." + k + ".weight", hid);
-      const float* ob = tm.f32(hp + "obj_preds." + k + ".bias", 1);
-      const float* cw = tm.f32(hp + "cls_preds." + k + ".weight", hid);
-      const float* cb = tm.f32(hp + "cls_preds." + k + ".bias", 1);
-      if (!rw || !rb || !ow || !ob || !cw || !cb) return JN_ENOTFOUND;
       // arena-resident (trainable): reg (4 x hid) | obj (hid) | cls (hid) rows back to back = one [6][hid] matrix;
       // biases reg (4) | obj (1, padded to 4) | cls (1, padded to 4): entries 0..3, 4 and 8 of `pred_b`
-      (void)rw; (void)rb; (void)ow; (void)ob; (void)cw; (void)cb;
       int r;
       float *w_reg = nullptr, *w_obj = nullptr, *w_cls = nullptr, *b_reg = nullptr, *b_obj = nullptr, *b_cls = nullptr;
       if ((r = upload_raw(ctx, tm, hp + "reg_preds." + k + ".weight", (size_t)4 * hid, &w_reg))) return r;
@@ -586,6 +647,7 @@ int jn_load_weights(jn_ctx* ctx, const jn_tensor* tensors, size_t n) {
     }
     return JN_OK;
   };
+  mark_params_written(ctx);
   // arena order: [gpt_backbone | decision model] = what optim_gpt updates (gpt.py:552-557), then yolox.*
   if ((rc = pack_net(JN_NET_GPT_BACKBONE))) return rc;
   GptW& g = ctx->gpt;
@@ -682,20 +744,13 @@ static inline int det_slot_base(const jn_ctx* ctx);   // first workspace slot of
 
 
 // Descriptors of the deferred BatchNorm tables (ChanTab): which (sum, sumsq) pair, BatchNorm weight / bias and pixel
-// count stand behind every table channel, and the reverse map for the one finalize launch per pass.  Only the depthwise
-// fp32 PAFPN (the nano patch encoder) takes part: its consumers all read their table through jn_tab.h.
+// count stand behind every table channel, and the reverse map for the one finalize launch per pass.  Only a net that
+// is defer_eligible (plan.cpp) takes part.
 static int ensure_defer_tables(jn_ctx* ctx, Net& net) {
   if (net.defer_built) return JN_OK;
   net.defer_built = true;
-  bool ok = net.depthwise && net.act_dtype == JN_F32 && ctx->params;
+  if (!ctx->params || !defer_eligible(net)) return JN_OK;
   const int n_ops = net.n_backbone_ops < 0 ? (int)net.ops.size() : net.n_backbone_ops;
-  for (int oi = 0; ok && oi < n_ops; ++oi) {
-    const Op& op = net.ops[oi];
-    if (op.kind == OP_CONV3 || op.kind == OP_PRED) ok = false;
-    if (op.kind == OP_DW && op.in.C % 16 != 0) ok = false;
-    if (op.wslot >= 0 && !net.convs[op.wslot].has_bn) ok = false;
-  }
-  if (!ok) return JN_OK;
   const int TC = net.tab_channels, SC = net.stat_channels;
   std::vector<int> td_src(TC, -1), td_g(TC, 0), td_b(TC, 0), fd_g(SC, 0), fd_b(SC, 0), fd_t0(SC, 0), fd_t1(SC, -1);
   std::vector<float> td_hw(TC, 0.0f), fd_hw(SC, 0.0f);
@@ -738,47 +793,56 @@ static int ensure_defer_tables(jn_ctx* ctx, Net& net) {
   return JN_OK;
 }
 
-// One pass of a PAFPN over N patches in workspace slot `slot`.  train != 0: batch-statistics
-// BatchNorm (stats accumulated by every conv, finalised per layer, running stats updated).
-static int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int train, const int* skip_flag,
-                   int skip_when, hipStream_t s, bool with_head = false, int first_op = 0) {
-  Net& net = ctx->nets[ni];
-  const int n_ops = (with_head || net.n_backbone_ops < 0) ? (int)net.ops.size() : net.n_backbone_ops;
-  const int MB = ctx->cfg.max_batch;
-  int rc;
-  // the autograd bridges differentiate LATER what a forward left in the workspace: a pass over the same slots in
-  // between makes that state stale (the backward entry points then fail with JN_ESTATE instead of computing garbage)
-  // (slots: 0 = eval / supervised pass; 1 .. T = the glimpse steps of a train-mode rollout of the ENCODER net; from
-  // det_slot_base on = detector training passes)
+// JN_LAYER_PROFILE / JN_BWD_PROFILE: HIP events around every op of a pass and its table on stderr (a measuring aid, off
+// by default).  Event i closes op i - 1 of a forward pass; the backward walks in reverse, so event i + 1 opens its op i.
+struct OpProfile {
+  std::vector<hipEvent_t> ev;
+  hipStream_t s;
+  double tot_us = 0, tot_b = 0;
+  OpProfile(bool on, int n_events, hipStream_t s_) : s(s_) {
+    if (on) { ev.resize(n_events); for (auto& e : ev) (void)hipEventCreate(&e); }
+  }
+  ~OpProfile() { for (auto& e : ev) (void)hipEventDestroy(e); }
+  explicit operator bool() const { return !ev.empty(); }
+  void mark(int i) { if (!ev.empty()) (void)hipEventRecord(ev[i], s); }
+  void row(const Op& op, int from, int to, double bytes, bool bwd) {
+    static const char* kn[] = {"stem", "pw", "dw", "conv3", "spp", "upsample", "addact", "pred"};
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ev[from], ev[to]);
+    tot_us += ms * 1e3; tot_b += bytes;
+    fprintf(stderr, "%-8s %-44s in %3dx%3dx%3d out %3dx%3dx%3d s%d", kn[op.kind], op.name.c_str(), op.in.H, op.in.W, op.in.C,
+            op.out.H, op.out.W, op.out.C, op.stride);
+    if (bwd) fprintf(stderr, " acc %d  %8.1f us  %8.1f MB  %6.0f GB/s\n", (int)op.acc_in, ms * 1e3, bytes / 1e6, bytes / (ms * 1e-3) / 1e9);
+    else fprintf(stderr, "  %8.1f us  %7.1f MB  %7.0f GB/s\n", ms * 1e3, bytes / 1e6, bytes / (ms * 1e-3) / 1e9);
+  }
+  void total() { fprintf(stderr, "# total %.1f us, %.1f MB, %.0f GB/s\n", tot_us, tot_b / 1e6, tot_b / (tot_us * 1e-6) / 1e9); }
+};
+
+// The autograd bridges differentiate LATER what a forward left in the workspace: a pass over the same slots in between
+// makes that state stale (the backward entry points then fail with JN_ESTATE instead of computing garbage).  Slots: 0 =
+// eval / supervised pass; 1 .. T = the glimpse steps of a train-mode rollout of the ENCODER net; from det_slot_base on =
+// detector training passes.
+static void invalidate_slot_state(jn_ctx* ctx, int ni, int slot) {
   if (ni == ctx->enc_net) {
     if (slot == 0) ctx->sup_valid = false;
     else if (ni != JN_NET_DETECTOR || slot < det_slot_base(ctx)) ctx->train_out_valid = false;
   }
   if (ni == JN_NET_DETECTOR && slot >= det_slot_base(ctx) && slot - det_slot_base(ctx) < (int)ctx->det_pass.size())
     ctx->det_pass[slot - det_slot_base(ctx)].valid = false;
+}
+
+// One pass of a PAFPN over N patches in workspace slot `slot`.  train != 0: batch-statistics
+// BatchNorm (stats accumulated by every conv, finalised per layer, running stats updated).
+// The routes come from plan_forward (plan.cpp); what depends on launch-time state stays here.
+static int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int train, const int* skip_flag,
+                   int skip_when, hipStream_t s, bool with_head = false, int first_op = 0) {
+  Net& net = ctx->nets[ni];
+  const int MB = ctx->cfg.max_batch;
+  int rc;
+  invalidate_slot_state(ctx, ni, slot);
   if (!train && (rc = refresh_eval_table(ctx, net, s))) return rc;
-  // fp32 passes: the 1x1 weights of this net as three bf16 planes for pw_x3_kernel (bf16 inference mode uses the h plane
-  // alone: pw_x1).  Split again only after something wrote the arena (jn_load_weights, jn_import_arena, an optimiser
-  // step: mark_params_written) — a rollout's T passes and every eval pass in between reuse the planes (ADVICE round 3:
-  // for yolox-s / -m detectors the split is tens of MB per pass)
   const bool x3 = ctx->params_x3 && !std::getenv("JN_NO_PW_X3");   // read per pass: tests flip it
-  if (x3) {
-    if (net.x3_hi == 0) {
-      size_t lo = ctx->arena_size, hi = 0;
-      for (const Op& op : net.ops) {
-        if (op.kind != OP_PW || op.wslot < 0) continue;
-        const ConvW& cw = net.convs[op.wslot];
-        if (!cw.w_dev) continue;
-        const size_t o = (size_t)(cw.w_dev - ctx->params);
-        lo = std::min(lo, o); hi = std::max(hi, o + (size_t)cw.cout * cw.cin);
-      }
-      net.x3_lo = lo / 8 * 8; net.x3_hi = hi > lo ? (hi + 7) / 8 * 8 : 0;
-    }
-    if (net.x3_hi > net.x3_lo && net.x3_dirty) {
-      launch_w_split3(ctx->params + net.x3_lo, ctx->params_x3 + 3 * net.x3_lo, (long long)(net.x3_hi - net.x3_lo), s);
-      net.x3_dirty = false;
-    }
-  }
+  if (x3) refresh_x3_planes(ctx, net, s);
   double* stats = train ? slot_stats(net, slot) : nullptr;
   float* save = train ? slot_save(net, slot) : nullptr;
   // (a train-mode rollout zeroes the statistics of all its slots with ONE memset up front)
@@ -788,46 +852,22 @@ static int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int 
   // consumers read the batch sums (ChanTab in jn_kernels.h), one finalize launch closes the pass
   if (train && !with_head && (rc = ensure_defer_tables(ctx, net))) return rc;
   const bool defer = train && !with_head && net.defer_ok;
-  auto deferred = [&](const Op& op) { return defer && (long long)N * op.out.H * op.out.W <= JN_DEFER_MAX_M; };
+  std::vector<FwdStep> plan;
+  if ((rc = plan_forward(net, N, train != 0, with_head, first_op, defer, plan))) return rc;
+  const int n_ops = first_op + (int)plan.size();
   auto ptr = [&](const View& v) { return view_ptr(net, slot, MB, v); };
   auto tab = [&](const View& v) {
     ChanTab t = view_tab(net, slot, v);
-    bool any = false;                       // does the view hold a channel whose table is deferred in this pass?
-    if (defer) {
-      const int off = net.tab_off[v.buf] + v.coff;
-      for (int c = 0; c < v.C && !any; ++c) any = net.h_td_hw[off + c] > 0.0f && (double)N * net.h_td_hw[off + c] <= (double)JN_DEFER_MAX_M;
-    }
-    if (any) {
+    if (defer && defer_tab_runs(net, v, N, t)) {     // the view holds a channel whose table is deferred in this pass
       const int off = net.tab_off[v.buf] + v.coff;
       t.dsrc = net.td_src + off; t.dhw = net.td_hw + off; t.dgoff = net.td_goff + off; t.dboff = net.td_boff + off;
       t.dparams = ctx->params; t.dstats = stats; t.drep_stride = rep_stride; t.dN = N; t.dmax = JN_DEFER_MAX_M;
-      // channel runs for the kernel arguments (at most four: a concat of a few producers); more: the arrays above
-      int ns = 0;
-      bool fits = true;
-      for (int c = 0; c < v.C && fits;) {
-        const int tc = off + c;
-        const bool d = net.h_td_hw[tc] > 0.0f && (double)N * net.h_td_hw[tc] <= (double)JN_DEFER_MAX_M;
-        int e = c + 1;
-        if (d) {
-          while (e < v.C && net.h_td_src[off + e] == net.h_td_src[tc] + (e - c) && net.h_td_goff[off + e] == net.h_td_goff[tc] + (e - c) &&
-                 net.h_td_boff[off + e] == net.h_td_boff[tc] + (e - c) && net.h_td_hw[off + e] == net.h_td_hw[tc])
-            ++e;
-        } else {
-          while (e < v.C && !(net.h_td_hw[off + e] > 0.0f && (double)N * net.h_td_hw[off + e] <= (double)JN_DEFER_MAX_M)) ++e;
-        }
-        if (ns == 4) { fits = false; break; }
-        const ChanTab::Run run{c, e, d ? net.h_td_src[tc] : -1, net.h_td_goff[tc], net.h_td_boff[tc], net.h_td_hw[tc]};
-        (ns == 0 ? t.r0 : ns == 1 ? t.r1 : ns == 2 ? t.r2 : t.r3) = run;
-        ++ns;
-        c = e;
-      }
-      t.nseg = fits ? ns : 0;
     }
     return t;
   };
   auto ld = [&](const View& v) { return net.bufs[v.buf].C; };
-  auto finalize = [&](const Op& op, const ConvW& cw) {
-    if (!train || !cw.has_bn || deferred(op)) return;
+  auto finalize = [&](const Op& op, const ConvW& cw, bool deferred) {
+    if (!train || !cw.has_bn || deferred) return;
     ChanTab t1{nullptr, nullptr, nullptr};
     if (op.alias.buf >= 0) t1 = tab(op.alias);
     // with the end-of-pass finalize (defer): table only here, saved / running statistics there
@@ -835,57 +875,41 @@ static int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int 
                        defer ? nullptr : cw.rmean_dev, defer ? nullptr : cw.rvar_dev, defer ? nullptr : save + 2 * cw.stat_off,
                        tab(op.out), t1, cw.cout, kBnEps, kBnMomentum, skip_flag, skip_when, s);
   };
-  // JN_LAYER_PROFILE=1: HIP events around every op of the pass, table on stderr (a measuring aid, off by default)
   static const bool layer_profile = std::getenv("JN_LAYER_PROFILE") != nullptr;
-  std::vector<hipEvent_t> lev;
-  if (layer_profile) {
-    lev.resize(n_ops + 1);
-    for (auto& e : lev) (void)hipEventCreate(&e);
-    (void)hipEventRecord(lev[first_op], s);
-  }
-  std::set<int> fused_ups;                  // upsample ops whose copy the producing 1x1 kernel wrote
+  OpProfile prof(layer_profile, n_ops + 1, s);
+  prof.mark(first_op);
+  std::vector<char> up_done(n_ops, 0);      // upsample ops whose copy the producing 1x1 kernel wrote
   for (int oi = first_op; oi < n_ops; ++oi) {
     const Op& op = net.ops[oi];
-    switch (op.kind) {
-      case OP_STEM: {
+    const FwdStep& st = plan[oi - first_op];
+    switch (st.route) {
+      case FR_STEM: {
         const ConvW& cw = net.convs[op.wslot];
         StemArgs a{ss.src, ss.positions, ss.pos_stride, ss.sample_stride, ss.chan_stride, ss.row_stride, net.P, N, cw.cout,
                    cw.w_dev, ptr(op.out), ld(op.out), net.act_dtype, train ? stats + 2 * cw.stat_off : nullptr, rep_stride,
-                   skip_flag, skip_when, deferred(op) ? JN_NREP_DEFER : JN_NREP, ss.src_u8};
+                   skip_flag, skip_when, st.deferred ? JN_NREP_DEFER : JN_NREP, ss.src_u8};
         launch_stem(a, s);
-        finalize(op, cw);
+        finalize(op, cw, st.deferred);
         break;
       }
-      case OP_PW:
-      case OP_CONV3:
-      case OP_DW: {
-        const ConvW& cw = net.convs[op.wslot];
-        if (!train && net.act_dtype == JN_F32 && op.kind == OP_DW && oi + 1 < n_ops) {
-          // eval: DWConv = depthwise + pointwise in one kernel, the depthwise output stays on chip
-          const Op& nx = net.ops[oi + 1];
-          if (nx.kind == OP_PW && nx.in.buf == op.out.buf && nx.in.coff == op.out.coff && nx.in.C == op.out.C &&
-              dwpw_supported(op.out.C, nx.out.C, op.stride)) {
-            const ConvW& pw = net.convs[nx.wslot];
-            DwPwArgs f{};
-            f.in = ptr(op.in); f.in_ld = ld(op.in); f.itab = tab(op.in); f.w_dw = cw.w_dev; f.mtab = tab(op.out);
-            f.w_pw = pw.w_dev; f.out = ptr(nx.out); f.out_ld = ld(nx.out); f.dtype = net.act_dtype;
-            f.C = op.out.C; f.cout = nx.out.C; f.N = N; f.H = op.in.H; f.W = op.in.W; f.OH = op.out.H; f.OW = op.out.W;
-            f.stride = op.stride; f.skip_flag = skip_flag; f.skip_when = skip_when;
-            int skip_ops = 1;
-            if (oi + 2 < n_ops && net.ops[oi + 2].kind == OP_ADDACT && net.ops[oi + 2].in.buf == nx.out.buf &&
-                net.ops[oi + 2].in.coff == nx.out.coff) {
-              // bottleneck shortcut: the add + activation goes into the epilogue, the pconv's raw z is never stored
-              const Op& ad = net.ops[oi + 2];
-              f.res = ptr(ad.res); f.res_ld = ld(ad.res); f.rtab = tab(ad.res); f.ptab = tab(nx.out);
-              f.out = ptr(ad.out); f.out_ld = ld(ad.out);
-              skip_ops = 2;
-            }
-            launch_dwpw(f, s);
-            if (layer_profile) for (int k = 1; k <= skip_ops + 1; ++k) (void)hipEventRecord(lev[oi + k], s);
-            oi += skip_ops;
-            continue;
-          }
+      case FR_DWPW:
+      case FR_DWPW_ADD: {
+        const Op& nx = net.ops[st.link];
+        DwPwArgs f{};
+        f.in = ptr(op.in); f.in_ld = ld(op.in); f.itab = tab(op.in); f.w_dw = net.convs[op.wslot].w_dev; f.mtab = tab(op.out);
+        f.w_pw = net.convs[nx.wslot].w_dev; f.out = ptr(nx.out); f.out_ld = ld(nx.out); f.dtype = net.act_dtype;
+        f.C = op.out.C; f.cout = nx.out.C; f.N = N; f.H = op.in.H; f.W = op.in.W; f.OH = op.out.H; f.OW = op.out.W;
+        f.stride = op.stride; f.skip_flag = skip_flag; f.skip_when = skip_when;
+        if (st.route == FR_DWPW_ADD) {
+          const Op& ad = net.ops[st.add];
+          f.res = ptr(ad.res); f.res_ld = ld(ad.res); f.rtab = tab(ad.res); f.ptab = tab(nx.out);
+          f.out = ptr(ad.out); f.out_ld = ld(ad.out);
         }
+        launch_dwpw(f, s);
+        break;
+      }
+      case FR_CONV: {
+        const ConvW& cw = net.convs[op.wslot];
         ConvArgs a{};
         a.in = ptr(op.in); a.in_ld = ld(op.in); a.in_dtype = net.act_dtype; a.itab = tab(op.in); a.w = cw.w_dev;
         a.w_bf16 = cw.w_bf16;
@@ -896,66 +920,53 @@ static int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int 
         a.cin = op.in.C; a.cout = op.out.C; a.stride = op.stride; a.act = op.act;
         a.stats = (train && cw.has_bn) ? stats + 2 * cw.stat_off : nullptr;
         a.stats_rep_stride = rep_stride;
-        a.stats_nrep = deferred(op) ? JN_NREP_DEFER : JN_NREP;
+        a.stats_nrep = st.deferred ? JN_NREP_DEFER : JN_NREP;
         a.skip_flag = skip_flag; a.skip_when = skip_when;
-        if (op.kind == OP_PW && net.act_dtype == JN_F32) {
-          // the source of a nearest x2 upsample: the producing kernel writes the upsampled copy itself where its route can
-          for (int uj = oi + 1; uj < n_ops; ++uj) {
-            const Op& up = net.ops[uj];
-            if (up.kind == OP_UPSAMPLE && up.in.buf == op.out.buf && up.in.coff == op.out.coff && up.in.C == op.out.C) {
-              if (pw_fused_upsample_supported(a)) { a.up_out = ptr(up.out); a.up_ld = ld(up.out); fused_ups.insert(uj); }
-              break;
-            }
-          }
+        if (st.link >= 0 && pw_fused_upsample_supported(a)) {      // the planned candidate, where this launch's route can
+          const Op& up = net.ops[st.link];
+          a.up_out = ptr(up.out); a.up_ld = ld(up.out); up_done[st.link] = 1;
         }
         if (op.kind == OP_PW) { JN_CHECK(launch_pw(a, s) == 0, JN_ESTATE, "1x1 conv %s: no kernel for this shape", op.name.c_str()); }
         else if (op.kind == OP_DW) launch_dw(a, s); else launch_conv3(a, s);
-        finalize(op, cw);
+        finalize(op, cw, st.deferred);
         break;
       }
-      case OP_SPP:
+      case FR_SPP:
         launch_spp(view_ptr(net, slot, MB, net_full_view(net, op.out.buf)), net.act_dtype, ld(op.out), op.in.C, op.in.H, op.in.W, N,
                    tab(op.in), skip_flag, skip_when, s);
         break;
-      case OP_UPSAMPLE:
-        if (!fused_ups.count(oi))
+      case FR_UPSAMPLE:
+        if (!up_done[oi])
           launch_upsample(ptr(op.in), ld(op.in), ptr(op.out), ld(op.out), net.act_dtype, op.in.C, op.in.H, op.in.W, N, skip_flag,
                           skip_when, s);
         break;
-      case OP_ADDACT:
+      case FR_ADDACT:
         launch_addact(ptr(op.in), ld(op.in), tab(op.in), ptr(op.res), ld(op.res), tab(op.res), ptr(op.out), ld(op.out),
                       net.act_dtype, op.out.C, (long long)N * op.out.H * op.out.W, skip_flag, skip_when, s);
         break;
-      case OP_PRED:
+      case FR_PRED:
         launch_head_pred(ptr(op.in), ld(op.in), tab(op.in), ptr(op.res), ld(op.res), tab(op.res), net.act_dtype, net.pred_w[op.level],
                          net.pred_b[op.level], train ? ctx->det_logits : ctx->det_raw, net.head_hid, op.in.H, op.in.W, op.stride,
                          net.n_anchors, op.anchor0, N, s, train ? 1 : 0);
         break;
+      case FR_ABSORBED: case FR_NONE: break;   // covered by the kernel of op st.link
     }
-    if (layer_profile) (void)hipEventRecord(lev[oi + 1], s);
+    prof.mark(oi + 1);
   }
-  if (layer_profile) {
+  if (prof) {
     (void)hipStreamSynchronize(s);
-    static const char* kn[] = {"stem", "pw", "dw", "conv3", "spp", "upsample", "addact", "pred"};
     const double esz = (double)act_esz(net);
-    double tot_us = 0, tot_b = 0;
     fprintf(stderr, "# layer profile: net %d, N=%d, train=%d, slot=%d\n", ni, N, train, slot);
     for (int oi = first_op; oi < n_ops; ++oi) {
       const Op& op = net.ops[oi];
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, lev[oi], lev[oi + 1]);
       const double in_e = op.kind == OP_STEM ? 3.0 * net.P * net.P * 4.0 / esz : (double)op.in.H * op.in.W * op.in.C;
-      double out_e = (double)op.out.H * op.out.W * op.out.C;
+      const double out_e = (double)op.out.H * op.out.W * op.out.C;
       double elems = in_e + out_e;
       if (op.kind == OP_ADDACT) elems += out_e;
       if (op.kind == OP_SPP) elems = in_e * 4;
-      const double bytes = elems * esz * N;
-      tot_us += ms * 1e3; tot_b += bytes;
-      fprintf(stderr, "%-8s %-44s in %3dx%3dx%3d out %3dx%3dx%3d s%d  %8.1f us  %7.1f MB  %7.0f GB/s\n", kn[op.kind], op.name.c_str(),
-              op.in.H, op.in.W, op.in.C, op.out.H, op.out.W, op.out.C, op.stride, ms * 1e3, bytes / 1e6, bytes / (ms * 1e-3) / 1e9);
+      prof.row(op, oi, oi + 1, elems * esz * N, false);
     }
-    fprintf(stderr, "# total %.1f us, %.1f MB, %.0f GB/s\n", tot_us, tot_b / 1e6, tot_b / (tot_us * 1e-6) / 1e9);
-    for (auto& e : lev) (void)hipEventDestroy(e);
+    prof.total();
   }
   if (defer) {
     BnAllArgs fa{};
@@ -1058,12 +1069,8 @@ static int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int s
   // JN_BWD_PROFILE=1: HIP events around the launches of every op, table on stderr (a measuring aid; use it together with
   // JN_NO_AUX_STREAM=1 so that the wide weight-gradient GEMMs are inside the brackets)
   static const bool bwd_profile = std::getenv("JN_BWD_PROFILE") != nullptr;
-  std::vector<hipEvent_t> bev;
-  if (bwd_profile) {
-    bev.resize(n_ops_b + 1);
-    for (auto& e : bev) (void)hipEventCreate(&e);
-    (void)hipEventRecord(bev[n_ops_b], s);
-  }
+  OpProfile prof(bwd_profile, n_ops_b + 1, s);
+  prof.mark(n_ops_b);
   for (int obi = n_ops_b - 1; obi >= 0; --obi) {
     const Op& op = net.ops[obi];
     const BwdStep& st = plan[obi];
@@ -1233,34 +1240,26 @@ static int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int s
       launch_upsample_bwd(gptr(op.out), ld(op.out), gptr(op.in), ld(op.in), op.in.C, op.in.H, op.in.W, N,
                           op.acc_in ? 1 : 0, s, sb);
     }
-    if (bwd_profile) (void)hipEventRecord(bev[obi], s);
+    prof.mark(obi);
   }
   if (aux_used) {
     JN_HIP(hipEventRecord(ctx->aux_join, ctx->aux_stream));
     JN_HIP(hipStreamWaitEvent(s, ctx->aux_join, 0));
   }
-  if (bwd_profile) {
+  if (prof) {
     (void)hipStreamSynchronize(s);
-    static const char* kn[] = {"stem", "pw", "dw", "conv3", "spp", "upsample", "addact", "pred"};
-    double tot_us = 0, tot_b = 0;
     fprintf(stderr, "# backward profile: net %d, N=%d patches x %d steps; bytes = g_out + z_out + x read, g_in written (+ read when accumulated)\n", ni, N, nsl);
     for (int obi = n_ops_b - 1; obi >= 0; --obi) {
       const Op& op = net.ops[obi];
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, bev[obi + 1], bev[obi]);
       const double in_e = op.kind == OP_STEM ? 0.0 : (double)op.in.H * op.in.W * op.in.C, out_e = (double)op.out.H * op.out.W * op.out.C;
       double elems;
       if (op.wslot >= 0) elems = 2.0 * out_e + (op.kind == OP_STEM ? 3.0 * net.P * net.P : 2.0 * in_e + (op.acc_in ? in_e : 0.0));
       else if (op.kind == OP_ADDACT) elems = 3.0 * out_e;                 // g read, two destinations
       else if (op.kind == OP_SPP) elems = 8.0 * in_e;
       else elems = in_e + out_e;
-      const double bytes = elems * 4.0 * N * nsl;
-      tot_us += ms * 1e3; tot_b += bytes;
-      fprintf(stderr, "%-8s %-44s in %3dx%3dx%3d out %3dx%3dx%3d s%d acc %d  %8.1f us  %8.1f MB  %6.0f GB/s\n", kn[op.kind], op.name.c_str(),
-              op.in.H, op.in.W, op.in.C, op.out.H, op.out.W, op.out.C, op.stride, (int)op.acc_in, ms * 1e3, bytes / 1e6, bytes / (ms * 1e-3) / 1e9);
+      prof.row(op, obi + 1, obi, elems * 4.0 * N * nsl, true);
     }
-    fprintf(stderr, "# total %.1f us, %.1f MB, %.0f GB/s\n", tot_us, tot_b / 1e6, tot_b / (tot_us * 1e-6) / 1e9);
-    for (auto& e : bev) (void)hipEventDestroy(e);
+    prof.total();
   }
   JN_HIP(hipGetLastError());
   return JN_OK;
@@ -2149,7 +2148,6 @@ static int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev
            "do_detection needs a detector and det_boxes_dev / det_counts_dev outputs");
   JN_HIP(hipSetDevice(ctx->cfg.device));
   hipStream_t s = (hipStream_t)stream;
-  jn_ctx& x = *ctx;
   const jn_config& c = ctx->cfg;
   const EnvState& e = ctx->env;
   const int B = e.B, T = e.T, C = c.n_embd, P = c.patch_size, nA = c.n_actions;
@@ -2298,20 +2296,13 @@ static int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev
       if ((rc = run_embed_fpn(ctx, B, train ? t + 1 : 0, train ? ctx->efpn_train + (size_t)t * B * ctx->efpn_h * ctx->efpn_w * C : nullptr, flag, B, s))) return rc;
     }
     GptStepArgs a{};
-    a.C = C; a.n_head = c.n_head; a.n_layer = c.n_layer; a.nA = nA; a.Tmax = c.block_size + 1; a.B = B; a.T = T;
-    a.use_pos_emb = c.use_pos_emb; a.no_patch_emb = c.no_patch_emb; a.concat_emb = c.concat_emb;
-    a.dec_pos_enc = c.decoder_pos_encoding; a.n_parts = n_parts(c);
-    a.pe2_ch = (int)std::ceil(C / 4.0) * 2;
-    const GptW& g = ctx->gpt;
-    a.wte = g.wte; a.wpe = g.wpe; a.embed_class = g.embed_class; a.proj_wt = g.proj_wt; a.proj_b = g.proj_b;
-    a.pos1d = g.pos1d; a.pe2 = g.pos2d_col; a.head_wt = g.head_wt; a.lnf_w = g.lnf_w; a.lnf_b = g.lnf_b;
-    a.layers = x.layers_dev; a.emb_part = x.emb_part; a.KS = x.KS; a.efpn_lin_b = g.efpn_lin_b;
-    a.kcache = ctx->kcache; a.vcache = ctx->vcache; a.prev_action = ctx->prev_action; a.cache_len = ctx->cache_len;
+    fill_gpt_weights(ctx, a);
+    a.B = B; a.T = T;
     a.step = t; a.mode = mode; a.forced = forced_actions_dev; a.seed = seed;
     // recurrent: every new token at 1-D position 0 (gpt.py:431-449); by token: position t, the last row of the
     // reference's full-prefix forward (gpt.py:331-354, 427-428)
     a.src_mode = GPT_SRC_ENV; a.pos_index = by_token ? t : 0; a.emb_stride = T + 1;
-    a.env = ep; a.out = r; a.n_done = ctx->n_done;
+    a.env = ep; a.out = r;
     a.skip_flag = flag; a.skip_when = B;
     a.tok_emb_out = train ? ctx->tok_emb_train : nullptr;
     a.pdrop = train ? ctx->pdrop : 0.0f; a.drop_seed = ctx->drop_seed_used;
@@ -2747,7 +2738,7 @@ int jn_optimizer_step_group(jn_ctx* ctx, int group, float lr, float weight_decay
   step += 1;
   launch_adamw(ctx->params + lo, ctx->grads + lo, ctx->adam_m + lo, ctx->adam_v + lo, (long long)(hi - lo), lr, 0.9f, 0.999f, 1e-8f,
                weight_decay, step, clip_value, grad_scale, (hipStream_t)stream);
-  for (int ni = 0; ni < 2; ++ni) if (ctx->has_net[ni]) ctx->nets[ni].eval_tab_dirty = ctx->nets[ni].x3_dirty = true;   // BN affine, 1x1 weights moved
+  mark_params_written(ctx);
   JN_HIP(hipGetLastError());
   return JN_OK;
 }
@@ -2790,8 +2781,7 @@ static int arena_copy(jn_ctx* ctx, int what, float* ref_dev, size_t numel, int t
   launch_arena_copy(ctx->segs_dev, ctx->segs_dev_n, arena, ref_dev, (long long)ctx->arena_used, to_ref, accumulate,
                     (hipStream_t)stream);
   JN_HIP(hipGetLastError());
-  if (!to_ref && what == 0)
-    for (int ni = 0; ni < 2; ++ni) if (ctx->has_net[ni]) ctx->nets[ni].eval_tab_dirty = ctx->nets[ni].x3_dirty = true;   // parameters may have moved
+  if (!to_ref && what == 0) mark_params_written(ctx);
   return JN_OK;
 }
 

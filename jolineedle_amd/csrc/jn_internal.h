@@ -152,9 +152,32 @@ struct BwdStep {           // op indices only: the launcher turns them into poin
 };
 int plan_backward(const Net& net, bool with_head, int fpn_zero, std::vector<BwdStep>& plan);
 
+// ---- forward plan (plan.cpp: plan_forward): the route of every op of one conv-stack forward pass ---------------------
+enum FwdRoute {
+  FR_NONE = 0,
+  FR_STEM, FR_CONV,              // launch_stem; launch_pw / launch_dw / launch_conv3 by the op's kind
+  FR_DWPW, FR_DWPW_ADD,          // eval DWConv (depthwise + pointwise) in one kernel; with the bottleneck's shortcut add
+  FR_ABSORBED,                   // nothing to launch: the kernel of op `link` covers this op
+  FR_SPP, FR_UPSAMPLE, FR_ADDACT, FR_PRED,
+};
+struct FwdStep {           // op indices and flags only: the launcher turns them into pointers
+  FwdRoute route = FR_NONE;
+  // FR_ABSORBED: the op whose kernel covers this one.  FR_DWPW / FR_DWPW_ADD: the pointwise op.  FR_CONV of an fp32 1x1
+  // conv: the upsample whose copy its kernel MAY write (the launcher asks pw_fused_upsample_supported).  -1: none
+  int link = -1;
+  int add = -1;            // FR_DWPW_ADD: the shortcut add
+  bool deferred = false;   // BatchNorm conv: no finalize launch of its own, its consumers read the batch sums
+};
+bool defer_eligible(const Net& net);   // the net's train-mode passes without the head may defer BatchNorm tables
+// plan[i] belongs to op first_op + i; defer: this pass defers (train && !with_head && defer_eligible && its tables exist)
+int plan_forward(const Net& net, int N, bool train, bool with_head, int first_op, bool defer, std::vector<FwdStep>& plan);
+
 struct ParamEntry {
   jn_param_info info;
 };
+// one row of the state-dict table (plan.cpp)
+void add_param(std::vector<ParamEntry>& params, const std::string& name, std::initializer_list<int64_t> shape, int dtype,
+               bool buffer, bool used);
 
 // One trainable tensor inside the flat parameter arena.
 struct ParamSeg {

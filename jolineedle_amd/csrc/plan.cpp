@@ -12,6 +12,16 @@
 
 namespace jnr {
 
+void add_param(std::vector<ParamEntry>& params, const std::string& name, std::initializer_list<int64_t> shape, int dtype,
+               bool buffer, bool used) {
+  ParamEntry e; std::memset(&e, 0, sizeof(e));
+  std::snprintf(e.info.name, sizeof(e.info.name), "%s", name.c_str());
+  e.info.dtype = dtype; e.info.ndim = (int)shape.size();
+  int i = 0; for (auto s : shape) e.info.shape[i++] = s;
+  e.info.is_buffer = buffer; e.info.used = used;
+  params.push_back(e);
+}
+
 namespace {
 
 struct Builder {
@@ -33,12 +43,7 @@ struct Builder {
   View fresh(int H, int W, int C) { return full(new_buf(H, W, C)); }
 
   void add_param(const std::string& name, std::initializer_list<int64_t> shape, int dtype, bool buffer, bool used) {
-    ParamEntry e; std::memset(&e, 0, sizeof(e));
-    std::snprintf(e.info.name, sizeof(e.info.name), "%s", name.c_str());
-    e.info.dtype = dtype; e.info.ndim = (int)shape.size();
-    int i = 0; for (auto s : shape) e.info.shape[i++] = s;
-    e.info.is_buffer = buffer; e.info.used = used;
-    params.push_back(e);
+    jnr::add_param(params, name, shape, dtype, buffer, used);
   }
 
   int add_conv(const std::string& name, int cin, int cout, int k, int groups, bool bn, bool bias) {
@@ -151,6 +156,20 @@ struct Builder {
   }
 };
 
+// per-image buffer offsets (every buffer 256-B aligned), table channels and BatchNorm statistics channels of the net
+void layout_offsets(Net& net) {
+  net.buf_off.resize(net.bufs.size());
+  net.tab_off.resize(net.bufs.size());
+  size_t off = 0;
+  int toff = 0, soff = 0;
+  for (size_t i = 0; i < net.bufs.size(); ++i) {
+    net.buf_off[i] = off; off += (net.bufs[i].per_image() + 63) / 64 * 64;
+    net.tab_off[i] = toff; toff += net.bufs[i].C;
+  }
+  for (auto& cw : net.convs) { cw.stat_off = soff; soff += cw.cout; }
+  net.per_image_floats = off; net.tab_channels = (toff + 3) / 4 * 4; net.stat_channels = soff;
+}
+
 }  // namespace
 
 int build_pafpn(Net& net, std::vector<ParamEntry>& params, const std::string& prefix,
@@ -210,20 +229,7 @@ int build_pafpn(Net& net, std::vector<ParamEntry>& params, const std::string& pr
   View pan_out0 = b.csp("C3_n4", cat_n4, c2, n, false);
   net.fpn[0] = pan_out2; net.fpn[1] = pan_out1; net.fpn[2] = pan_out0;
 
-  net.buf_off.resize(net.bufs.size());
-  size_t off = 0;
-  for (size_t i = 0; i < net.bufs.size(); ++i) {
-    net.buf_off[i] = off;
-    off += (net.bufs[i].per_image() + 63) / 64 * 64;   // keep every buffer 256-B aligned
-  }
-  net.per_image_floats = off;
-  net.tab_off.resize(net.bufs.size());
-  int toff = 0;
-  for (size_t i = 0; i < net.bufs.size(); ++i) { net.tab_off[i] = toff; toff += net.bufs[i].C; }
-  net.tab_channels = (toff + 3) / 4 * 4;
-  int soff = 0;
-  for (auto& cw : net.convs) { cw.stat_off = soff; soff += cw.cout; }
-  net.stat_channels = soff;
+  layout_offsets(net);
 
   // Backward bookkeeping: walking the ops in reverse, the first contributor to a gradient view
   // writes it, later ones accumulate.  The three FPN outputs are seeded from outside first.
@@ -306,18 +312,7 @@ int build_head(Net& net, std::vector<ParamEntry>& params, const std::string& pre
       for (int c = 0; c < op.in.C; ++c) written[op.in.buf][op.in.coff + c] = 1;
     }
   }
-  // buffer / table / stats offsets grew with the head
-  net.buf_off.resize(net.bufs.size());
-  size_t off = 0;
-  for (size_t i = 0; i < net.bufs.size(); ++i) { net.buf_off[i] = off; off += (net.bufs[i].per_image() + 63) / 64 * 64; }
-  net.per_image_floats = off;
-  net.tab_off.resize(net.bufs.size());
-  int toff = 0;
-  for (size_t i = 0; i < net.bufs.size(); ++i) { net.tab_off[i] = toff; toff += net.bufs[i].C; }
-  net.tab_channels = (toff + 3) / 4 * 4;
-  int soff = 0;
-  for (auto& cw : net.convs) { cw.stat_off = soff; soff += cw.cout; }
-  net.stat_channels = soff;
+  layout_offsets(net);         // buffer / table / stats offsets grew with the head
   return JN_OK;
 }
 
@@ -502,6 +497,92 @@ int plan_backward(const Net& net, bool with_head, int fpn_zero, std::vector<BwdS
     }
     JN_CHECK(st.fold < 0 || st.route == BR_PW_FUSED, JN_ESTATE, "backward plan: shortcut %s folded into %s, not a fused 1x1 conv",
              st.fold < 0 ? "" : net.ops[st.fold].name.c_str(), net.ops[c].name.c_str());
+  }
+  return JN_OK;
+}
+
+// ---- forward plan ----------------------------------------------------------------------------------------------------
+// Deferred BatchNorm tables (ChanTab in jn_kernels.h) need every consumer to read its table through jn_tab.h: only the
+// depthwise fp32 PAFPN (the nano patch encoder) qualifies.
+bool defer_eligible(const Net& net) {
+  if (!net.depthwise || net.act_dtype != JN_F32) return false;
+  const int n = net.n_backbone_ops < 0 ? (int)net.ops.size() : net.n_backbone_ops;
+  for (int i = 0; i < n; ++i) {
+    const Op& op = net.ops[i];
+    if (op.kind == OP_CONV3 || op.kind == OP_PRED || (op.kind == OP_DW && op.in.C % 16 != 0)) return false;
+    if (op.wslot >= 0 && !net.convs[op.wslot].has_bn) return false;
+  }
+  return true;
+}
+
+// One forward pass of `net` over N patches as a pure function of its topology, activation dtype and the pass (train,
+// with_head, the first op, whether it defers): one record per op of [first_op, n_ops), in launch order.  What depends
+// on launch-time state (pw_fused_upsample_supported, JN_NO_PW_X3, the stream) stays with the launcher (run_net, api.hip).
+int plan_forward(const Net& net, int N, bool train, bool with_head, int first_op, bool defer, std::vector<FwdStep>& plan) {
+  const int n = (with_head || net.n_backbone_ops < 0) ? (int)net.ops.size() : net.n_backbone_ops;
+  const bool f32 = net.act_dtype == JN_F32;
+  JN_CHECK(first_op >= 0 && first_op <= n && N >= 1, JN_EINVAL, "forward plan: first op %d of %d, N = %d", first_op, n, N);
+  JN_CHECK(!defer || (train && !with_head), JN_ESTATE, "forward plan: only a train-mode pass without the head defers");
+  plan.assign(n - first_op, FwdStep{});
+  auto at = [&](int i) -> FwdStep& { return plan[i - first_op]; };
+  auto same = [](const View& a, const View& b) { return a.buf == b.buf && a.coff == b.coff && a.C == b.C; };
+  for (int i = first_op; i < n; ++i) {
+    const Op& op = net.ops[i];
+    FwdStep& st = at(i);
+    if (st.route == FR_ABSORBED) continue;
+    static const FwdRoute by_kind[] = {FR_STEM, FR_CONV, FR_CONV, FR_CONV, FR_SPP, FR_UPSAMPLE, FR_ADDACT, FR_PRED};   // OpKind order
+    st.route = by_kind[op.kind];
+    if (!train && f32 && op.kind == OP_DW && i + 1 < n) {
+      // eval: DWConv = depthwise + pointwise in one kernel, the depthwise output stays on chip
+      const Op& nx = net.ops[i + 1];
+      if (nx.kind == OP_PW && same(nx.in, op.out) && dwpw_supported(op.out.C, nx.out.C, op.stride)) {
+        st.route = FR_DWPW; st.link = i + 1;
+        at(i + 1).route = FR_ABSORBED; at(i + 1).link = i;
+        // bottleneck shortcut: the add + activation goes into the epilogue, the pconv's raw z is never stored
+        if (i + 2 < n && net.ops[i + 2].kind == OP_ADDACT && net.ops[i + 2].in.buf == nx.out.buf && net.ops[i + 2].in.coff == nx.out.coff) {
+          st.route = FR_DWPW_ADD; st.add = i + 2;
+          at(i + 2).route = FR_ABSORBED; at(i + 2).link = i;
+        }
+      }
+    }
+    // the source of a nearest x2 upsample: the producing fp32 1x1 kernel writes the upsampled copy where its route can
+    for (int u = i + 1; st.route == FR_CONV && op.kind == OP_PW && f32 && u < n; ++u)
+      if (net.ops[u].kind == OP_UPSAMPLE && same(net.ops[u].in, op.out)) { st.link = u; break; }
+    st.deferred = defer && op.wslot >= 0 && (long long)N * op.out.H * op.out.W <= JN_DEFER_MAX_M;
+  }
+  // every op is launched or absorbed by exactly one launched fusion that precedes it and matches its kind and views; an
+  // upsample is the candidate of at most one conv; fusions are eval fp32 only; a deferred layer has BatchNorm
+  std::vector<char> covered(n, 0), cand(n, 0);
+  for (int i = first_op; i < n; ++i) {
+    const Op& op = net.ops[i];
+    const FwdStep& st = at(i);
+    const char* name = op.name.c_str();
+    JN_CHECK(st.route != FR_NONE, JN_ESTATE, "forward plan: op %s has no route", name);
+    if (st.route == FR_ABSORBED) {
+      JN_CHECK(covered[i] == 1, JN_ESTATE, "forward plan: op %s is covered by %d kernels", name, (int)covered[i]);
+      continue;
+    }
+    JN_CHECK(covered[i] == 0, JN_ESTATE, "forward plan: op %s is launched and absorbed", name);
+    if (st.route == FR_DWPW || st.route == FR_DWPW_ADD) {
+      const bool add = st.route == FR_DWPW_ADD;
+      JN_CHECK(!train && f32 && op.kind == OP_DW && st.link == i + 1 && st.link < n && st.add == (add ? i + 2 : -1) && st.add < n,
+               JN_ESTATE, "forward plan: %s cannot run as a fused DWConv", name);
+      const Op& pw = net.ops[st.link];
+      JN_CHECK(pw.kind == OP_PW && same(pw.in, op.out) && at(st.link).route == FR_ABSORBED && at(st.link).link == i, JN_ESTATE,
+               "forward plan: %s does not absorb the 1x1 conv %s", name, pw.name.c_str());
+      ++covered[st.link];
+      if (add) {
+        const Op& ad = net.ops[st.add];
+        JN_CHECK(ad.kind == OP_ADDACT && same(ad.in, pw.out) && at(st.add).route == FR_ABSORBED && at(st.add).link == i, JN_ESTATE,
+                 "forward plan: %s does not absorb the shortcut %s", name, ad.name.c_str());
+        ++covered[st.add];
+      }
+    } else if (st.link >= 0) {
+      JN_CHECK(st.route == FR_CONV && op.kind == OP_PW && f32 && st.link > i && st.link < n && net.ops[st.link].kind == OP_UPSAMPLE &&
+               same(net.ops[st.link].in, op.out) && !cand[st.link]++, JN_ESTATE, "forward plan: %s cannot write upsample %d", name, st.link);
+    }
+    JN_CHECK(!st.deferred || (defer && op.wslot >= 0 && net.convs[op.wslot].has_bn), JN_ESTATE,
+             "forward plan: %s defers a BatchNorm table it does not have", name);
   }
   return JN_OK;
 }
