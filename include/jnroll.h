@@ -261,6 +261,21 @@ int jn_yolox_loss(const float* raw_dev, const float* targets_dev, int N, int nb,
  * Inputs are finite with w, h >= 0.  JN_EINVAL: a null raw / boxes / counts, N < 1, A < 1, max_out < 1. */
 int jn_postprocess(const float* raw_dev, int N, int A, float conf_threshold, float nms_threshold, float clamp_max,
                    int max_out, float* boxes_dev, int32_t* counts_dev, int32_t* stats_dev, void* stream);
+/* The metrics of one teacher-forced validation batch on given logits, context-free: SupervisedTrainer.compute_metrics
+ * (src/supervised.py:162-197) on the labels eval_supervised forms (:449-458).  logits_dev [B,T,nA] f32, current_actions /
+ * next_actions [B,T] int64, masks u8 [B,T] (1 = token, 0 = padding).  Labels: next_actions; with on_self_trajectory != 0
+ * (config.loss_mode == "on-self-trajectory") label(b,t) = next[b,t] at t = n_b - 1, n_b = the row's mask sum (n_b = 0
+ * addresses column T - 1, as Python's index -1 does); elsewhere current[b,t+1] for t < T - 1 and 0 in the last column
+ * (current_actions may be NULL otherwise).  Per token CrossEntropy(weight[STOP = 8] = stop_weight, reduction none);
+ * metrics_dev f32[4] = action_loss (plain mean over the tokens with mask == 1, not weight-normalised), action_accuracy
+ * over the same tokens (argmax, first maximum wins), episode_length (mean row sum of masks), the number of valid tokens.
+ * No valid token: action_loss NaN (torch's mean of nothing) and action_accuracy 0 (the reference replaces that NaN,
+ * :188-195).  Optional outputs: token_loss_out_dev f32 [B,T], predicted_out_dev u8 [B,T]; padding tokens get 0 / 0.
+ * One workgroup, sums in a fixed order without atomics: two calls give equal bits.  Launches on `stream`, does not wait.
+ * JN_EINVAL: a null logits / next_actions / masks / metrics, B, T or nA < 1, nA > 256. */
+int jn_supervised_metrics(const float* logits_dev, const int64_t* current_actions_dev, const int64_t* next_actions_dev,
+                          const uint8_t* masks_dev, int B, int T, int nA, float stop_weight, int on_self_trajectory,
+                          float* token_loss_out_dev, uint8_t* predicted_out_dev, float* metrics_dev, void* stream);
 /* The per-image half of mAP-50 as Trainer.compute_detection_metrics reports it (src/trainer.py:188-248; COCO
  * protocol, one class): preds [B,Nmax,W >= 5] f32 with score in column 4 and pred_counts int32 [B]; targets
  * [B,Mmax,5] f32 (cls,x1,y1,x2,y2) with target_counts int32 [B] (Mmax = 0: no targets, both may be NULL).  Per image
@@ -430,6 +445,21 @@ int jn_supervised_forward(jn_ctx* ctx, const float* patches_dev, const int64_t* 
                           const int64_t* classes_dev, const int64_t* positions_dev, int B, int T, float* logits_out_dev,
                           float* final_emb_out_dev, void* stream);
 int jn_supervised_backward(jn_ctx* ctx, const float* dlogits_dev, void* stream);
+/* The eval-mode twin of jn_supervised_step — one batch of SupervisedTrainer.eval_supervised (src/supervised.py:431-472,
+ * under model.eval() and no_grad): GPT.forward on the teacher's sequences with BatchNorm running statistics and no
+ * dropout, then jn_supervised_metrics on the logits.  Same tensors as jn_supervised_step; on_self_trajectory selects the
+ * labels of :449-456.  Touches no statistic, weight or gradient and needs no training state; works in both activation
+ * dtypes.  The encoder takes the B*T patches in flattened (b t) order in chunks of at most max_batch (ceil(B*T /
+ * max_batch) conv-stack passes, where jn_gpt_forward makes T of B patches each); then the full-sequence decode over
+ * T + 1 tokens (1-D positions 0..T-1, class token from `classes`).  B <= max_batch, T <= block_size; B*T is free.
+ * Optional outputs: logits_out_dev [B,T,n_actions], token_loss_out_dev f32 [B,T], predicted_out_dev u8 [B,T];
+ * metrics_dev f32[4] as jn_supervised_metrics.  All on `stream`, no synchronisation.  Like every eval pass it uses the
+ * encoder's workspace slot 0: a pending jn_supervised_backward then fails with JN_ESTATE. */
+int jn_supervised_eval(jn_ctx* ctx, const float* patches_dev, const int64_t* current_actions_dev,
+                       const int64_t* next_actions_dev, const int64_t* classes_dev, const int64_t* positions_dev,
+                       const uint8_t* masks_dev, int B, int T, float stop_weight, int on_self_trajectory,
+                       float* logits_out_dev, float* token_loss_out_dev, uint8_t* predicted_out_dev, float* metrics_dev,
+                       void* stream);
 /* clip_grad_value_(clip_value) + AdamW (torch defaults) over the optim_gpt parameters
  * (src/reinforce.py:344-346, src/models/gpt.py:552-557); grad_scale multiplies the gradients first
  * (1/world_size after a SUM all-reduce). */
@@ -495,6 +525,19 @@ int jn_detector_forward(jn_ctx* ctx, const float* patches_dev, int N, const floa
                         int n_pass, float* metrics_dev, float* boxes_dev, int32_t* counts_dev, float* fpn0_dev,
                         float* fpn1_dev, float* fpn2_dev, void* stream);
 int jn_detector_backward(jn_ctx* ctx, int pass, const float* dloss_dev, float scale, void* stream);
+/* NeedleYOLOX.forward(patches, targets) as VALIDATION calls it (src/supervised.py:465, under model.eval() and no_grad):
+ * the PAFPN runs in the module's current mode — eval, running statistics, none of them written (src/models/yolox.py:54-55)
+ * — and only the head goes to train mode for the loss (`self.train()`, yolox.py:62): batch statistics over the N patches,
+ * and the head's running statistics move with momentum 0.03 as in any train pass (the reference's behaviour, kept).
+ * N <= max_batch, fp32 activations only.  metrics_dev f32[8] as for jn_detector_step.  Optional outputs as in
+ * jn_detector_forward: boxes_dev / counts_dev = the eval head on the same maps with the head statistics as just updated,
+ * postprocessed and clamped (yolox.py:74-91); fpn{0,1,2}_dev = the eval-mode maps.  Works in the eval workspace, and the
+ * next eval pass rebuilds its BatchNorm table.  A detector training pass that is resident (jn_detector_forward without its
+ * backward yet) keeps its own workspace slot, which this call does not write: its jn_detector_backward stays valid and
+ * gives the same gradient as without the call.  All on `stream`, no synchronisation. */
+int jn_detector_eval_loss(jn_ctx* ctx, const float* patches_dev, int N, const float* targets_dev, int nb,
+                          float* metrics_dev, float* boxes_dev, int32_t* counts_dev, float* fpn0_dev, float* fpn1_dev,
+                          float* fpn2_dev, void* stream);
 /* AdamW + clip on one parameter group of the arena: group 0 = optim_gpt (everything but yolox.*,
  * src/models/gpt.py:552-557), group 1 = optim_yolox (yolox.*).  jn_optimizer_step == group 0. */
 int jn_optimizer_step_group(jn_ctx* ctx, int group, float lr, float weight_decay, float clip_value,

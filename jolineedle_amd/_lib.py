@@ -156,6 +156,10 @@ SIGNATURES = {
     "jn_set_dropout": (C.c_int, [C.c_void_p, C.c_float, C.c_uint64]),
     "jn_set_freeze": (C.c_int, [C.c_void_p, C.c_int]),
     "jn_optimizer_steps": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int]),
+    "jn_supervised_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "jn_supervised_eval": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_float, C.c_int] + [C.c_void_p] * 5),
+    "jn_detector_eval_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 7),
 }
 
 

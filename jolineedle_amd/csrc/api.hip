@@ -1687,6 +1687,71 @@ int jn_detector_backward(jn_ctx* ctx, int pass, const float* dloss_dev, float sc
   return rc;
 }
 
+// NeedleYOLOX.forward(patches, targets) as validation calls it (src/supervised.py:465 under model.eval() and no_grad):
+// the PAFPN runs in the module's mode, eval, and only the head goes to train mode for the loss (src/models/yolox.py:54-73).
+// Everything happens in the eval workspace (slot 0): backbone ops with the running-statistics table, then the head ops
+// from n_backbone_ops on as a train-mode pass over those maps (batch statistics over the N patches; the head's running
+// statistics move), the SimOTA loss, and on request the eval head with the statistics as just updated.  The resident
+// training passes live in slots of their own and nothing they keep for their backward is written here.
+int jn_detector_eval_loss(jn_ctx* ctx, const float* patches_dev, int N, const float* targets_dev, int nb, float* metrics_dev,
+                          float* boxes_dev, int32_t* counts_dev, float* fpn0_dev, float* fpn1_dev, float* fpn2_dev, void* stream) {
+  JN_CHECK(ctx && patches_dev && targets_dev && metrics_dev, JN_EINVAL, "jn_detector_eval_loss: null argument");
+  JN_CHECK(ctx->has_net[JN_NET_DETECTOR], JN_ESTATE, "context was created without a detector");
+  JN_CHECK(ctx->weights_loaded, JN_ESTATE, "jn_load_weights has not been called");
+  JN_CHECK(N >= 1 && N <= ctx->cfg.max_batch, JN_EINVAL, "N=%d exceeds max_batch=%d", N, ctx->cfg.max_batch);
+  JN_CHECK(nb >= 1, JN_EINVAL, "targets need at least one (padding) row per patch");
+  JN_CHECK(ctx->cfg.act_dtype == JN_F32, JN_ESTATE, "the detector loss needs act_dtype = fp32 (bf16 is the inference mode)");
+  Net& net = ctx->nets[JN_NET_DETECTOR];
+  JN_CHECK(net.n_backbone_ops >= 0, JN_ESTATE, "detector without a head");
+  JN_HIP(hipSetDevice(ctx->cfg.device));
+  hipStream_t s = (hipStream_t)stream;
+  const int MB = ctx->cfg.max_batch, A = net.n_anchors, P = ctx->cfg.patch_size;
+  int rc;
+  if (!ctx->det_logits) {
+    if ((rc = dev_alloc(ctx, &ctx->det_logits, (size_t)MB * A * 6))) return rc;
+    if ((rc = dev_alloc(ctx, &ctx->det_bwd_scale, (size_t)4))) return rc;
+  }
+  if (!ctx->det_eval_dlogits) {
+    if ((rc = dev_alloc(ctx, &ctx->det_eval_dlogits, (size_t)MB * A * 6))) return rc;
+    if ((rc = dev_alloc(ctx, &ctx->det_eval_acc, (size_t)8 + (size_t)8 * MB))) return rc;
+  }
+  if (!ctx->det_labels || ctx->det_labels_rows < (size_t)N * nb) {
+    if ((rc = dev_alloc(ctx, &ctx->det_labels, (size_t)MB * nb * 5))) return rc;
+    ctx->det_labels_rows = (size_t)MB * nb;
+  }
+  if (boxes_dev && counts_dev && !ctx->det_raw)
+    if ((rc = dev_alloc(ctx, &ctx->det_raw, (size_t)MB * A * 6))) return rc;
+  hipLaunchKernelGGL(labels_to_cxcywh_kernel, dim3((N * nb + 255) / 256), dim3(256), 0, s, targets_dev, ctx->det_labels, N * nb);
+  StemSrc ss{patches_dev, nullptr, 3LL * P * P, (long long)P * P, P};
+  if ((rc = run_net(ctx, JN_NET_DETECTOR, N, ss, 0, 0, nullptr, 0, s))) return rc;             // PAFPN, eval
+  float* outs[3] = {fpn0_dev, fpn1_dev, fpn2_dev};
+  for (int i = 0; i < 3; ++i) {
+    if (!outs[i]) continue;
+    const View& f = net.fpn[i];
+    launch_nhwc_to_nchw(view_ptr(net, 0, MB, f), net.act_dtype, net.bufs[f.buf].C, view_tab(net, 0, f), outs[i], f.C, f.H * f.W, N, s);
+  }
+  StemSrc none{nullptr, nullptr, 0, 0, 0};
+  // head, train: writes batch-statistics entries into slot 0's table for the head layers and sets eval_tab_dirty
+  if ((rc = run_net(ctx, JN_NET_DETECTOR, N, none, 0, 1, nullptr, 0, s, true, net.n_backbone_ops))) return rc;
+  DetGeom geo{};
+  geo.A = A;
+  for (const Op& op : net.ops) {
+    if (op.kind != OP_PRED) continue;
+    geo.a0[op.level] = op.anchor0; geo.H[op.level] = op.in.H; geo.W[op.level] = op.in.W; geo.stride[op.level] = op.stride;
+  }
+  launch_yolox_loss(ctx->det_logits, ctx->det_labels, N, nb, geo, ctx->det_eval_dlogits, ctx->det_eval_acc + 8, 1, 1.0f, metrics_dev,
+                    ctx->det_eval_acc, s);
+  if (boxes_dev && counts_dev) {
+    // head, eval, on the same maps: run_net rebuilds the whole table from the running statistics first (the backbone's
+    // entries come out as they were, the head's from the statistics the pass above has just moved)
+    if ((rc = run_net(ctx, JN_NET_DETECTOR, N, none, 0, 0, nullptr, 0, s, true, net.n_backbone_ops))) return rc;
+    launch_postprocess(ctx->det_raw, A, N, ctx->cfg.det_conf_threshold, ctx->cfg.det_nms_threshold, (float)(P - 1), boxes_dev,
+                       counts_dev, ctx->cfg.max_det_per_patch, nullptr, s);
+  }
+  JN_HIP(hipGetLastError());
+  return JN_OK;
+}
+
 // ---- environment ---------------------------------------------------------------------
 static EnvPtrs env_ptrs(jn_ctx* ctx) {
   const EnvState& e = ctx->env;
@@ -2032,6 +2097,19 @@ int jn_postprocess(const float* raw_dev, int N, int A, float conf_threshold, flo
   JN_CHECK(max_out >= 1, JN_EINVAL, "jn_postprocess: max_out=%d", max_out);
   launch_postprocess(raw_dev, A, N, conf_threshold, nms_threshold, clamp_max, boxes_dev, counts_dev, max_out, stats_dev,
                      (hipStream_t)stream);
+  JN_HIP(hipGetLastError());
+  return JN_OK;
+}
+
+int jn_supervised_metrics(const float* logits_dev, const int64_t* current_actions_dev, const int64_t* next_actions_dev,
+                          const uint8_t* masks_dev, int B, int T, int nA, float stop_weight, int on_self_trajectory,
+                          float* token_loss_out_dev, uint8_t* predicted_out_dev, float* metrics_dev, void* stream) {
+  JN_CHECK(logits_dev && next_actions_dev && masks_dev && metrics_dev, JN_EINVAL, "jn_supervised_metrics: null argument");
+  JN_CHECK(!on_self_trajectory || current_actions_dev, JN_EINVAL, "jn_supervised_metrics: on-self-trajectory labels need current_actions");
+  JN_CHECK(B >= 1 && T >= 1 && nA >= 1 && nA <= 256 && (long long)B * T <= (1LL << 24), JN_EINVAL,
+           "jn_supervised_metrics: B=%d T=%d nA=%d", B, T, nA);
+  launch_supervised_metrics(logits_dev, current_actions_dev, next_actions_dev, masks_dev, B, T, nA, stop_weight,
+                            on_self_trajectory ? 1 : 0, token_loss_out_dev, predicted_out_dev, metrics_dev, (hipStream_t)stream);
   JN_HIP(hipGetLastError());
   return JN_OK;
 }
@@ -2718,6 +2796,64 @@ int jn_supervised_backward(jn_ctx* ctx, const float* dlogits_dev, void* stream) 
   JN_HIP(hipMemcpyAsync(ctx->dlogits, dlogits_dev, (size_t)ctx->sup.B * ctx->sup.T * ctx->cfg.n_actions * sizeof(float),
                         hipMemcpyDeviceToDevice, s));
   return supervised_backward_impl(ctx, s);
+}
+
+// The validation twin of jn_supervised_step (eval_supervised, src/supervised.py:442-472): GPT.forward in eval mode on the
+// teacher's sequences, then the loss / accuracy of compute_metrics.  In eval mode a patch's embedding does not depend
+// on its batch, so the encoder walks the B*T patches in flattened (b t) order in chunks of max_batch and every chunk's
+// embeddings land at their place in the [B][T][C] token buffer the decode reads.
+int jn_supervised_eval(jn_ctx* ctx, const float* patches_dev, const int64_t* current_actions_dev, const int64_t* next_actions_dev,
+                       const int64_t* classes_dev, const int64_t* positions_dev, const uint8_t* masks_dev, int B, int T,
+                       float stop_weight, int on_self_trajectory, float* logits_out_dev, float* token_loss_out_dev,
+                       uint8_t* predicted_out_dev, float* metrics_dev, void* stream) {
+  JN_CHECK(ctx && current_actions_dev && next_actions_dev && masks_dev && metrics_dev, JN_EINVAL, "jn_supervised_eval: null argument");
+  JN_CHECK(ctx->weights_loaded, JN_ESTATE, "jn_load_weights has not been called");
+  const jn_config& c = ctx->cfg;
+  JN_CHECK(B >= 1 && B <= c.max_batch, JN_EINVAL, "B=%d exceeds max_batch=%d", B, c.max_batch);
+  JN_CHECK(T >= 1 && T <= c.block_size, JN_EINVAL, "Cannot forward sequence of length %d, block size is only %d", T, c.block_size);
+  JN_CHECK(!c.use_pos_emb || positions_dev, JN_EINVAL, "positions are required when use_pos_emb is set");
+  JN_CHECK(c.no_patch_emb || patches_dev, JN_EINVAL, "patches are required unless no_patch_emb is set");
+  JN_HIP(hipSetDevice(c.device));
+  hipStream_t s = (hipStream_t)stream;
+  const int C = c.n_embd, P = c.patch_size, nA = c.n_actions, N = B * T, L = T + 1;
+  int rc;
+  if (!ctx->eval_logits && !logits_out_dev)
+    if ((rc = dev_alloc(ctx, &ctx->eval_logits, (size_t)c.max_batch * c.block_size * nA))) return rc;
+  float* logits = logits_out_dev ? logits_out_dev : ctx->eval_logits;
+  if (!c.no_patch_emb) {
+    if (!ctx->tok_emb)
+      if ((rc = dev_alloc(ctx, &ctx->tok_emb, (size_t)c.max_batch * (c.block_size + 1) * C))) return rc;
+    for (int n0 = 0; n0 < N; n0 += c.max_batch) {
+      const int n = std::min(c.max_batch, N - n0);
+      StemSrc ss{patches_dev + (size_t)n0 * 3 * P * P, nullptr, 3LL * P * P, (long long)P * P, P};
+      if ((rc = run_net(ctx, ctx->enc_net, n, ss, 0, 0, nullptr, 0, s))) return rc;
+      if ((rc = run_embed_fpn(ctx, n, 0, nullptr, nullptr, 0, s))) return rc;
+      hipLaunchKernelGGL(emb_finish_kernel, dim3((n * C + 255) / 256), dim3(256), 0, s, ctx->emb_part, ctx->gpt.efpn_lin_b,
+                         ctx->tok_emb + (size_t)n0 * C, (long long)C, n, ctx->KS, C);
+    }
+  }
+  JN_HIP(hipMemsetAsync(ctx->cache_len, 0, (size_t)B * sizeof(int32_t), s));
+  GptStepArgs a{};
+  fill_gpt_weights(ctx, a);
+  a.classes = classes_dev;
+  a.B = B; a.T = L; a.emb_stride = L; a.logits_stride = T * nA;
+  for (int tok = 0; tok < L; ++tok) {
+    a.step = tok;
+    a.logits_rows = tok >= 1 ? logits + (size_t)(tok - 1) * nA : nullptr;
+    if (tok == 0) {
+      a.src_mode = GPT_SRC_CLASS;
+    } else {
+      a.src_mode = GPT_SRC_TEACH;
+      a.t_actions = current_actions_dev; a.t_positions = positions_dev; a.t_stride = T; a.t_index = tok - 1;
+      a.pos_index = tok - 1;
+      a.tok_emb = ctx->tok_emb; a.tok_emb_stride = T; a.tok_emb_index = tok - 1;
+    }
+    launch_gpt_step(a, s);
+  }
+  launch_supervised_metrics(logits, current_actions_dev, next_actions_dev, masks_dev, B, T, nA, stop_weight,
+                            on_self_trajectory ? 1 : 0, token_loss_out_dev, predicted_out_dev, metrics_dev, s);
+  JN_HIP(hipGetLastError());
+  return JN_OK;
 }
 
 int jn_optimizer_step(jn_ctx* ctx, float lr, float weight_decay, float clip_value, float grad_scale, void* stream) {

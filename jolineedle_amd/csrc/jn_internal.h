@@ -282,7 +282,9 @@ struct jn_ctx {
   float* det_labels = nullptr;    // [B][nb][5] cxcywh labels of the training pass
   size_t det_labels_rows = 0;
   float* det_tmp_boxes = nullptr; int32_t* det_tmp_counts = nullptr;   // one step's detections before the scatter
-  float* tok_emb = nullptr;       // [B][T][C] patch embeddings of jn_gpt_forward
+  float* tok_emb = nullptr;       // [B][T][C] patch embeddings of jn_gpt_forward / jn_supervised_eval
+  float* eval_logits = nullptr;   // [B][T][nA] logits of jn_supervised_eval when the caller wants none
+  float* det_eval_dlogits = nullptr; float* det_eval_acc = nullptr;   // jn_detector_eval_loss: the loss kernel's d_raw / sums (unused)
   jnr::EnvState env;
   // rollout workspaces
   float* patch_emb = nullptr;     // [B, C]

@@ -413,6 +413,11 @@ size_t gpt_backward_batched_scratch(int C, int n_head, int n_layer, int nA, int 
 int launch_gpt_backward_batched(const GptBwdArgs& a, const GptLayerPtrs* W, const GptLayerPtrs* G, hipStream_t s);
 int launch_ce_loss(const float* logits, const int64_t* target, const uint8_t* masks, float stop_weight, float* dlogits,
                    float* metrics, int n, int nA, int T, hipStream_t s);
+// validation: loss / accuracy / episode length / valid tokens of logits [B][T][nA] against labels formed in the kernel
+// (next, or with on_self the on-self-trajectory labels from current / next / masks); token_loss, predicted optional
+int launch_supervised_metrics(const float* logits, const int64_t* current, const int64_t* next, const uint8_t* masks, int B, int T,
+                              int nA, float stop_weight, int on_self, float* token_loss, uint8_t* predicted, float* metrics,
+                              hipStream_t s);
 // de[m][k] = 0 where e[m][k] <= 0 (ReLU mask of embed_fpn.0);  gb[o] += sum_m dpe[m][o]
 int launch_relu_mask(float* de, const float* e, long long n, hipStream_t s);
 int launch_colsum_add(const float* dpe, long long M, int Co, float* gb, hipStream_t s);

@@ -223,6 +223,78 @@ int launch_ce_loss(const float* logits, const int64_t* target, const uint8_t* ma
   return 0;
 }
 
+// ---- validation metrics of the teacher-forced pass (src/supervised.py:162-197 on the labels of :449-458) ---------
+// One workgroup of MB threads; token i = b * T + t belongs to thread i % MB.  Every thread adds its tokens in index
+// order, then one fixed LDS tree per sum: no atomics, so two calls give equal bits.  Nothing but the loss is
+// written for the optimiser's sake (ce_loss_kernel also writes dlogits, which validation has no use for).
+constexpr int MB = 1024;
+
+__device__ __forceinline__ float metrics_tree(float* red, float v) {
+  const int tid = threadIdx.x;
+  __syncthreads();                              // (the previous tree's red[0] has been read by everyone)
+  red[tid] = v;
+  __syncthreads();
+  for (int o = MB / 2; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
+  return red[0];
+}
+
+__global__ __launch_bounds__(MB) void supervised_metrics_kernel(const float* __restrict__ logits, const long long* __restrict__ current,
+                                                                const long long* __restrict__ next,
+                                                                const unsigned char* __restrict__ masks, int B, int T, int nA,
+                                                                float stop_weight, int on_self, float* __restrict__ token_loss,
+                                                                unsigned char* __restrict__ predicted, float* __restrict__ metrics) {
+  __shared__ float red[MB];
+  const int n = B * T;
+  float ls = 0.0f, acc = 0.0f, cnt = 0.0f, len = 0.0f;
+  for (int i = threadIdx.x; i < n; i += MB) {
+    const int b = i / T, t = i - b * T;
+    const unsigned char m = masks[i];
+    len += (float)m;                            // masks.sum(dim=1) adds the values, `masks == 1` selects the tokens
+    if (m != 1) {
+      if (token_loss) token_loss[i] = 0.0f;
+      if (predicted) predicted[i] = 0;
+      continue;
+    }
+    long long y = next[i];
+    if (on_self) {
+      // reference_actions[:, :-1] = current[:, 1:]; then column n_b - 1 takes next (n_b = 0: Python's index -1)
+      int nb = 0;
+      for (int k = 0; k < T; ++k) nb += masks[(long long)b * T + k];
+      const int last = nb > 0 ? min(nb, T) - 1 : T - 1;
+      if (t != last) y = t < T - 1 ? current[i + 1] : 0;
+    }
+    const int yi = (int)min(max(y, 0LL), (long long)(nA - 1));
+    const float* lg = logits + (long long)i * nA;
+    float mx = -INFINITY; int best = 0;
+    for (int j = 0; j < nA; ++j) if (lg[j] > mx) { mx = lg[j]; best = j; }      // first maximum wins (argmax)
+    float se = 0.0f;
+    for (int j = 0; j < nA; ++j) se += expf(lg[j] - mx);
+    const float wy = (yi == 8) ? stop_weight : 1.0f;
+    const float l = -wy * ((lg[yi] - mx) - logf(se));
+    if (token_loss) token_loss[i] = l;
+    if (predicted) predicted[i] = (unsigned char)best;
+    ls += l; acc += (best == yi) ? 1.0f : 0.0f; cnt += 1.0f;
+  }
+  const float nvalid = metrics_tree(red, cnt);
+  const float loss = metrics_tree(red, ls);
+  const float hits = metrics_tree(red, acc);
+  const float total = metrics_tree(red, len);
+  if (threadIdx.x == 0) {
+    metrics[0] = loss / nvalid;                             // mean of an empty selection: 0 / 0 = NaN, as torch's
+    metrics[1] = nvalid > 0.0f ? hits / nvalid : 0.0f;      // the reference replaces that NaN by 0 (:188-195)
+    metrics[2] = total / (float)B;
+    metrics[3] = nvalid;
+  }
+}
+
+int launch_supervised_metrics(const float* logits, const int64_t* current, const int64_t* next, const uint8_t* masks, int B, int T,
+                              int nA, float stop_weight, int on_self, float* token_loss, uint8_t* predicted, float* metrics,
+                              hipStream_t s) {
+  hipLaunchKernelGGL(supervised_metrics_kernel, dim3(1), dim3(MB), 0, s, logits, (const long long*)current, (const long long*)next,
+                     masks, B, T, nA, stop_weight, on_self, token_loss, predicted, metrics);
+  return 0;
+}
+
 // ---- helpers on per-agent global scratch (all threads of the block, barrier at the end) --------
 __device__ __forceinline__ void lin_fwd(float* out, const float* in, const float* __restrict__ wt,
                                         const float* __restrict__ b, int L, int K, int N) {

@@ -3,15 +3,34 @@
 (``generate_trajectories``, src/supervised.py:95-136, over trajectory.NeedleSimpleEnv) whose patches are gathered on
 the device, and followed by the detector step on the trajectories' detector patches (src/supervised.py:881-902).
 ``eval_on_images`` is the free-running half of ``test()`` (src/supervised.py:279-405) on the engine's rollout and
-``eval_envs_on_images`` the multistart evaluation that selects the best checkpoint (``eval_envs``, :638-752); the
-teacher-forced ``eval_supervised`` is out of scope; augmentation is opt-in (``init_detection``)."""
+``eval_envs_on_images`` the multistart evaluation that selects the best checkpoint (``eval_envs``, :638-752);
+``eval_supervised_on_images`` is the teacher-forced validation (``eval_supervised``, :407-483) over ``jn_supervised_eval``
+and the detector's validation loss, and ``test_on_images`` the metric assembly of ``test()`` (:754-810); augmentation is
+opt-in (``init_detection``)."""
 import ctypes as C
+import random
 from typing import Dict, Optional, Tuple
 
 import torch
 
 from . import _lib
 from ._lib import check, ptr
+
+
+def reference_actions(current_actions: torch.Tensor, next_actions: torch.Tensor, masks: torch.Tensor,
+                      loss_mode: str = "best-action") -> torch.Tensor:
+    """The labels of a teacher-forced batch (src/supervised.py:449-458, 870-877): ``next_actions``, or with
+    ``loss_mode == "on-self-trajectory"`` the action the trajectory itself takes next — ``current_actions`` shifted left by
+    one, with column n_b - 1 of row b (n_b = the row's mask sum) taken from ``next_actions``; a row without tokens
+    addresses column -1, the last one, as the reference's index does."""
+    if loss_mode != "on-self-trajectory":
+        return next_actions
+    ref = torch.zeros_like(current_actions)
+    ref[:, :-1] = current_actions[:, 1:]
+    last = masks.sum(dim=1).long() - 1
+    rows = torch.arange(current_actions.shape[0], device=current_actions.device)
+    ref[rows, last] = next_actions[rows, last]
+    return ref
 
 
 class SupervisedTrainer:
@@ -21,6 +40,8 @@ class SupervisedTrainer:
         self.device = model.device
         self.stop_weight = float(getattr(config, "stop_weight", 1.0)) if getattr(config, "stop_enabled", False) else 1.0
         self.best_metric_name = "map"
+        self.best_metric_history = []
+        self.last_test_metrics = None
         self.iter_num = 0
         self._flat_grads = None
 
@@ -38,14 +59,18 @@ class SupervisedTrainer:
         self.detection_augment = DetectionAugment(**kw)
         return self.detection_augment
 
-    def generate_trajectories(self, batch: Dict, position: Optional[Tuple[int, int]] = None, seed: Optional[int] = None) -> Dict:
+    def generate_trajectories(self, batch: Dict, position: Optional[Tuple[int, int]] = None, seed: Optional[int] = None,
+                              use_views: bool = True, seed_ties: bool = False) -> Dict:
         """One teacher walk per image of `batch` (``image`` [B, C, H, W] on the device or a list of [C, H, W] of one
         size, ``bboxes`` [B, nb, 4] xyxy with zero-row padding or a list, ``class_id``) -> the collated dict of
         src/supervised.py:95-136: patches [B, T, C, P, P], current_actions / next_actions / labels [B, T],
         positions [B, T, 2], masks [B, T], local_bboxes [B, T, nb, 6], patches_yolox [M, C, P, P], bboxes_yolox
         [M, nb, 6], class_id [B].  The walks are integer work on the host; both patch tensors come from the
         device-resident images in two gather launches.  `seed` makes the walks reproducible (the reference seeds
-        nothing here)."""
+        nothing here).  use_views=False leaves the rotations / translations of the config off (``test()`` disables
+        both, src/supervised.py:773-774).  seed_ties: with a `seed`, the teacher's choice among equally near targets
+        (Python's global ``random`` in the reference and by default here) is drawn from ``random.Random(seed + i)`` too, so
+        that equal seeds give equal walks whatever else drew from the global stream."""
         from .trajectory import NeedleSimpleEnv, assemble_samples
         cfg = self.config
         images = batch["image"]
@@ -59,7 +84,7 @@ class SupervisedTrainer:
         # --augment-rotate / --augment-translate (src/dataset.py:274-278): the teacher walks the transformed boxes on the
         # views' canvas and both patch tensors are cut through the views; the augmented images are never written
         views, boxes = None, batch["bboxes"]
-        if getattr(cfg, "rotations", False) or getattr(cfg, "translations", False):
+        if use_views and (getattr(cfg, "rotations", False) or getattr(cfg, "translations", False)):
             from .views import stack_bboxes, trainer_views
             views = trainer_views(self, images, boxes, P)
             boxes = views.transform_bboxes(stack_bboxes(boxes, images.shape[0]))
@@ -70,7 +95,8 @@ class SupervisedTrainer:
             bb = boxes[i]
             if isinstance(bb, torch.Tensor):
                 bb = bb[(bb != 0).any(dim=-1)] if bb.numel() else bb.reshape(0, 4)      # drop the collate's zero rows
-            env = NeedleSimpleEnv(None, P, bb, seed=None if seed is None else seed + i, height=height, width=width)
+            ties = random.Random(seed + i) if seed_ties and seed is not None else None
+            env = NeedleSimpleEnv(None, P, bb, seed=None if seed is None else seed + i, height=height, width=width, py_random=ties)
             idx.append(env.generate_sample_indices(int(cfg.max_seq_len), int(getattr(cfg, "min_keypoints", 0)),
                                                    int(getattr(cfg, "max_keypoints", 0)),
                                                    bool(getattr(cfg, "binomial_keypoints", False)), position))
@@ -85,14 +111,7 @@ class SupervisedTrainer:
         cfg = self.config
         tr = self.generate_trajectories(batch, seed=seed)
         cur, nxt, masks = tr["current_actions"], tr["next_actions"], tr["masks"]
-        if getattr(cfg, "loss_mode", "best-action") == "on-self-trajectory":          # src/supervised.py:870-877
-            ref_actions = torch.zeros_like(cur)
-            ref_actions[:, :-1] = cur[:, 1:]
-            last = masks.sum(dim=1).long() - 1
-            rows = torch.arange(cur.shape[0], device=cur.device)
-            ref_actions[rows, last] = nxt[rows, last]
-        else:
-            ref_actions = nxt
+        ref_actions = reference_actions(cur, nxt, masks, getattr(cfg, "loss_mode", "best-action"))   # src/supervised.py:870-877
         detection = self.yolox_model() is not None and bool(getattr(cfg, "detection_enabled", True))
         aug = getattr(self, "detection_augment", None)
         if aug is not None:
@@ -177,14 +196,7 @@ class SupervisedTrainer:
                 B_, T_ = current_actions.shape
                 patches = aug(patches.flatten(0, 1)).view(B_, T_, *patches.shape[2:])
         action_logits, _ = model(patches, current_actions, classes=classes, positions=positions)
-        if getattr(cfg, "loss_mode", "best-action") == "on-self-trajectory":
-            reference_actions = torch.zeros_like(current_actions)
-            reference_actions[:, :-1] = current_actions[:, 1:]
-            last = masks.sum(dim=1).long() - 1
-            rows = torch.arange(current_actions.shape[0], device=current_actions.device)
-            reference_actions[rows, last] = next_actions[rows, last]
-        else:
-            reference_actions = next_actions
+        ref_actions = reference_actions(current_actions, next_actions, masks, getattr(cfg, "loss_mode", "best-action"))
         yolo_loss = None
         if self.yolox_model() is not None and bool(getattr(cfg, "detection_enabled", True)):
             patches_yolox = batch["patches_yolox"]
@@ -192,7 +204,7 @@ class SupervisedTrainer:
                 with torch.no_grad():
                     patches_yolox = aug(patches_yolox)
             _, _, yolo_loss = self.yolox_model()(patches_yolox, batch["bboxes_yolox"], predict=False)   # :881-888; total_loss has a graph
-        metrics = self.compute_metrics(action_logits, reference_actions, masks, yolo_loss)
+        metrics = self.compute_metrics(action_logits, ref_actions, masks, yolo_loss)
         metrics["loss"].backward()
         if self.iter_num % int(getattr(cfg, "gradient_accumulation", 1)) == 0:
             optim_gpt.step()
@@ -422,6 +434,160 @@ class SupervisedTrainer:
             for k, v in per_image[i].items():
                 out.setdefault(k, []).append(v)
         return out
+
+    # ---- validation: the teacher-forced half of test() (src/supervised.py:407-483, 754-810) -----------------------------
+    def _yolo_map_device(self, outputs, targets) -> torch.Tensor:
+        """``compute_yolo_metrics`` as a device tensor f64 [1], nothing read back.  `outputs`: the predictions of every
+        patch, packed (boxes [M, K, >= 5], counts int32 [M]) or in the reference's list form (one list of None / [n, >= 5]
+        per image); `targets` [..., nb, 5 | 6] = (class, x1, y1, x2, y2[, 1]), real rows marked by the last column
+        (6 columns) or by a non-zero row (5)."""
+        from . import detection
+        dev = self.device
+        t = targets.to(dev, torch.float32)
+        t = t.reshape(-1, *t.shape[-2:])
+        real = (t[..., -1] == 1) if t.shape[-1] >= 6 else (t != 0).any(dim=-1)
+        # the real rows first, in their order (the reference's `patch_targets[patch_targets[:, -1] == 1]`)
+        order = torch.argsort((~real).to(torch.int8), dim=1, stable=True)
+        rows = torch.take_along_dim(t[..., :5], order[..., None], dim=1).contiguous()
+        tcounts = real.sum(dim=1).to(torch.int32)
+        if not isinstance(outputs, tuple):
+            flat = [o for image in outputs for o in image] if len(outputs) and isinstance(outputs[0], (list, tuple)) else list(outputs)
+            width = next((o.shape[1] for o in flat if o is not None), 7)
+            outputs = detection.pack_boxes(flat, width, dev)
+        M = outputs[0].shape[0]
+        assert rows.shape[0] == M, (rows.shape, M)
+        if M == 0:
+            return torch.zeros(1, device=dev, dtype=torch.float64)
+        if rows.shape[1] == 0:
+            rows = torch.zeros((M, 1, 5), device=dev)
+        if M * 100 > detection.MAX_EVAL_ENTRIES or outputs[0].shape[1] > detection.MAX_EVAL_BOXES:
+            # beyond the kernels' limits: the host function (with readbacks of its own)
+            return torch.tensor([detection.map_50_device(outputs, (rows, tcounts))], device=dev, dtype=torch.float64)
+        return detection.average_precision_device(detection.match_detections_device(outputs, (rows, tcounts)), pooled=True)
+
+    def compute_yolo_metrics(self, outputs, targets, device_metrics: Optional[bool] = None) -> Dict[str, torch.Tensor]:
+        """``compute_yolo_metrics`` (src/supervised.py:203-277): {"map": mAP-50 with every PATCH as one unit}; 0 when the
+        batch holds no real box (:225-230).  Scores come from column 4.  Arguments as
+        ``_yolo_map_device``; the reference passes ``[bbox_outs]`` and ``bboxes_yolox.unsqueeze(0)``.  device_metrics
+        (default: the trainer's device is a GPU): the device matching of ``detection.map_50_device``; False: the same
+        value from ``detection.map_50`` on the host (list-form `outputs` only)."""
+        if device_metrics is None:
+            device_metrics = self.device.type == "cuda"
+        if device_metrics:
+            return {"map": self._yolo_map_device(outputs, targets).to(torch.float32)}
+        from . import detection
+        flat = [o for image in outputs for o in image] if len(outputs) and isinstance(outputs[0], (list, tuple)) else list(outputs)
+        t = targets.reshape(-1, *targets.shape[-2:]).to(torch.float32)
+        assert len(flat) == t.shape[0], (len(flat), t.shape)
+        tgts = [p[(p[:, -1] == 1) if p.shape[-1] >= 6 else (p != 0).any(dim=-1)][:, :5] for p in t]
+        return {"map": torch.tensor([detection.map_50(flat, tgts)], dtype=torch.float32, device=targets.device)}
+
+    def eval_step(self, patches, current_actions, next_actions, positions, masks, classes=None, loss_mode: Optional[str] = None,
+                  want_logits: bool = True) -> Dict[str, torch.Tensor]:
+        """The validation twin of ``train_step`` (``jn_supervised_eval``): eval-mode ``model(patches, current_actions,
+        classes, positions)`` — running statistics, no dropout, nothing written to the model — then the loss and accuracy
+        of ``compute_metrics`` against the labels of `loss_mode` (default ``config.loss_mode``; see
+        ``reference_actions``).  B <= max_batch and T <= block_size; B * T is free (the encoder takes the patches in
+        chunks of max_batch).  Everything stays on the device, nothing is read back: ``metrics`` f32 [4] = action_loss,
+        action_accuracy, episode_length, valid tokens; ``token_loss`` f32 [B, T] and ``predicted`` u8 [B, T] (0 on
+        padding); ``logits`` [B, T, n_actions] unless want_logits is False."""
+        model, dev = self.model, self.device
+        model.sync_weights()
+        eng = model.engine()
+        if loss_mode is None:
+            loss_mode = getattr(self.config, "loss_mode", "best-action")
+        B, T = current_actions.shape
+        f = lambda t, dt: t.to(dev, dt).contiguous()
+        patches = None if patches is None else f(patches, torch.float32)
+        cur, nxt = f(current_actions, torch.int64), f(next_actions, torch.int64)
+        pos = None if positions is None else f(positions, torch.int64)
+        msk = f(masks, torch.uint8)
+        cls = None if classes is None else f(torch.as_tensor(classes), torch.int64)
+        assert cls is None or cls.shape == (B,), "classes must be [B]"
+        out = {"metrics": torch.zeros(4, device=dev, dtype=torch.float32),
+               "token_loss": torch.empty((B, T), device=dev, dtype=torch.float32),
+               "predicted": torch.empty((B, T), device=dev, dtype=torch.uint8),
+               "logits": torch.empty((B, T, eng.cfg.n_actions), device=dev, dtype=torch.float32) if want_logits else None}
+        check(eng.lib.jn_supervised_eval(eng.handle, ptr(patches), ptr(cur), ptr(nxt), ptr(cls), ptr(pos), ptr(msk), B, T,
+                                         self.stop_weight, int(loss_mode == "on-self-trajectory"), ptr(out["logits"]),
+                                         ptr(out["token_loss"]), ptr(out["predicted"]), ptr(out["metrics"]),
+                                         _lib.current_stream(dev)), "jn_supervised_eval")
+        return out
+
+    @torch.no_grad()
+    def eval_supervised_on_images(self, images, bboxes, batch_size: int, class_ids=None, seed: Optional[int] = None) -> Dict[str, list]:
+        """``eval_supervised`` (src/supervised.py:407-483), the validation loss and accuracy on teacher trajectories plus
+        the detector's validation loss, `batch_size` images at a time (the images of one batch share one size).  The model
+        is put in eval mode and restored.  Per batch: ``generate_trajectories`` without views or augmentation ->
+        ``jn_supervised_eval`` with ``config.loss_mode`` -> with a detector configured and enabled, its validation call on
+        ``patches_yolox`` / ``bboxes_yolox`` (eval-mode PAFPN, train-mode head: the head's running statistics move, as the
+        reference's do) -> ``compute_yolo_metrics``; ONE readback per batch.  Returns name -> one entry per batch:
+        ``loss``, ``action_loss``, ``action_accuracy``, ``episode_length`` and, with the detector, ``yolo_total_loss``,
+        ``yolo_iou_loss``, ``yolo_conf_loss``, ``yolo_cls_loss``, ``yolo_l1_loss``, ``yolo_num_fg``, ``yolo_loss``, ``map``.
+        A batch without a valid token gives action_loss NaN and action_accuracy 0.  ``self.last_eval_supervised`` keeps,
+        per batch, ``token_loss`` f32, ``predicted`` and ``labels`` int64 [B, T] on the host and the batch's
+        ``trajectories`` (device tensors).  `seed` makes the walks reproducible (batch i uses seed + its first image)."""
+        from .yolox import LOSS_NAMES
+        cfg, model, dev = self.config, self.model, self.device
+        n_images = len(images)
+        detection = self.yolox_model() is not None and bool(getattr(cfg, "detection_enabled", True))
+        loss_mode = getattr(cfg, "loss_mode", "best-action")
+        out: Dict[str, list] = {}
+        self.last_eval_supervised = []
+        was_training = model.training
+        model.eval()
+        try:
+            for first in range(0, n_images, int(batch_size)):
+                sel = range(first, min(n_images, first + int(batch_size)))
+                batch = {"image": [images[i] for i in sel] if not isinstance(images, torch.Tensor) else images[first:sel.stop],
+                         "bboxes": [bboxes[i] for i in sel] if not isinstance(bboxes, torch.Tensor) else bboxes[first:sel.stop],
+                         "class_id": None if class_ids is None else torch.as_tensor(class_ids)[first:sel.stop]}
+                tr = self.generate_trajectories(batch, seed=None if seed is None else seed + first, use_views=False, seed_ties=True)
+                cur, nxt, msk = tr["current_actions"], tr["next_actions"], tr["masks"]
+                B, T = cur.shape
+                res = self.eval_step(tr["patches"], cur, nxt, tr["positions"], msk, classes=tr["class_id"], loss_mode=loss_mode,
+                                     want_logits=False)
+                metrics, token_loss, predicted = res["metrics"], res["token_loss"], res["predicted"]
+                labels = reference_actions(cur, nxt, msk, loss_mode)
+                parts = [metrics.double(), token_loss.flatten().double(), predicted.flatten().double(), labels.flatten().double()]
+                if detection:
+                    if tr["patches_yolox"].shape[0] > 0:
+                        outputs, _, yolo = self.yolox_model().validation_loss(tr["patches_yolox"], tr["bboxes_yolox"], packed=True)
+                        parts.append(torch.stack([yolo[k] for k in LOSS_NAMES]).double())
+                        parts.append(self._yolo_map_device(outputs, tr["bboxes_yolox"]))
+                    else:                                            # no detector patch in the batch: nothing to score
+                        parts.append(torch.zeros(len(LOSS_NAMES) + 1, device=dev, dtype=torch.float64))
+                host = torch.cat(parts).cpu()                        # the batch's one readback
+                m = host[:4].to(torch.float32)
+                n = B * T
+                self.last_eval_supervised.append({
+                    "token_loss": host[4:4 + n].to(torch.float32).view(B, T), "predicted": host[4 + n:4 + 2 * n].long().view(B, T),
+                    "labels": host[4 + 2 * n:4 + 3 * n].long().view(B, T), "trajectories": tr})
+                row = {"action_loss": m[0], "action_accuracy": m[1], "episode_length": m[2], "loss": m[0]}
+                if detection:
+                    y = host[4 + 3 * n:].to(torch.float32)
+                    for j, k in enumerate(LOSS_NAMES):
+                        row["yolo_" + k] = y[j]
+                    row["yolo_loss"] = row["yolo_total_loss"]
+                    row["loss"] = m[0] + row["yolo_loss"]             # fp32, as compute_metrics adds them (:177-185)
+                    row["map"] = y[len(LOSS_NAMES)]
+                for k, v in row.items():
+                    out.setdefault(k, []).append(float(v))
+        finally:
+            model.train(was_training)
+        return out
+
+    def test_on_images(self, images, bboxes, batch_size: int, class_ids=None, sample_actions: bool = False,
+                       seed: Optional[int] = None) -> Dict[str, list]:
+        """The metric assembly of ``test()`` (src/supervised.py:754-810) without logger, plots or checkpoint: the
+        multistart evaluation's lists (``eval_envs_on_images``), the validation lists under ``supervised_<name>``
+        (:796-799); sets ``last_test_metrics`` and extends ``best_metric_history`` by the mean of ``best_metric_name``."""
+        metrics = self.eval_envs_on_images(images, bboxes, batch_size, sample_actions=sample_actions)
+        for name, values in self.eval_supervised_on_images(images, bboxes, batch_size, class_ids=class_ids, seed=seed).items():
+            metrics["supervised_" + name] = values
+        self.last_test_metrics = metrics
+        self.best_metric_history.append(float(torch.tensor(metrics[self.best_metric_name], dtype=torch.float64).mean()))
+        return metrics
 
     def train_step(self, patches, current_actions, next_actions, positions, masks, optimizer_step: bool = True,
                    process_group=None, classes=None) -> Dict[str, torch.Tensor]:

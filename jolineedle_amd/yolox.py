@@ -116,6 +116,12 @@ class NeedleYOLOX:
     A detection batch larger than ``max_batch`` is fed in chunks of ``max_batch``, each weighted by its share of the
     patches (deviation: BatchNorm statistics and the 1 / num_fg normalisation are per chunk); every chunk keeps its own
     workspace until the backward.
+
+    Validation — the owning model in eval mode AND grad disabled, the context of the reference's ``eval_supervised``
+    (src/supervised.py:407, 465 under ``model.eval()``): the PAFPN then runs in the module's mode, eval (running
+    statistics, none written), and only the head goes to train mode for the loss, so the head's running statistics do
+    move (src/models/yolox.py:54-62; ``jn_detector_eval_loss``); ``fpn_outs`` are the eval-mode maps.  Every other
+    combination takes the path above: in particular eval mode WITH grad enabled still runs the train-mode backbone.
     """
 
     def __init__(self, gpt, conf_threshold: float):
@@ -150,6 +156,8 @@ class NeedleYOLOX:
         t = targets[..., :5].to(g.device, torch.float32).contiguous()
         check_box_cap(t)
         graph = torch.is_grad_enabled()
+        if not g.training and not graph:
+            return self._validation_forward(x, t, predict)
         if graph:
             g.bind_flat()
         g._detector_gen = getattr(g, "_detector_gen", 0) + 1
@@ -182,6 +190,51 @@ class NeedleYOLOX:
             tot["total_loss"] = _DetectorGraph.apply(anchor, g, g._detector_gen, tot["total_loss"], passes, (x, t, keep))
         outputs = self._boxes_to_list(boxes, counts) if predict else [None] * N
         return outputs, (tuple(fpn) if predict else None), tot
+
+    def _fpn_buffers(self, N: int):
+        cfg, P, dev = self._gpt.engine().cfg, self._gpt.patch_size, self._gpt.device
+        chans = [int(256 * cfg.det_width), int(512 * cfg.det_width), int(1024 * cfg.det_width)]
+        return [torch.empty((N, c, P // s, P // s), device=dev) for c, s in zip(chans, (8, 16, 32))]
+
+    def _validation_forward(self, x: torch.Tensor, t: torch.Tensor, predict: bool, packed: bool = False):
+        """The loss branch as validation reaches it (src/supervised.py:465: ``model.eval()`` and ``no_grad``), through
+        ``jn_detector_eval_loss``: eval-mode PAFPN, train-mode head.  No graph, no resident pass.  packed: the
+        predictions stay on the device as (boxes [N, K, 7], counts int32 [N]) and nothing is read back."""
+        g = self._gpt
+        eng, dev = g.engine(), g.device
+        N, K = x.shape[0], eng.cfg.max_det_per_patch
+        boxes = counts = None
+        fpn = [None, None, None]
+        if predict:
+            boxes = torch.zeros((N, K, 7), device=dev)
+            counts = torch.zeros((N,), device=dev, dtype=torch.int32)
+            fpn = self._fpn_buffers(N)
+        tot = {k: torch.zeros((), device=dev) for k in LOSS_NAMES}
+        for i in range(0, N, g.max_batch):
+            n = min(g.max_batch, N - i)
+            metrics = torch.zeros(8, device=dev)
+            check(eng.lib.jn_detector_eval_loss(eng.handle, ptr(x[i:i + n]), n, ptr(t[i:i + n]), t.shape[1], ptr(metrics),
+                                                ptr(boxes[i:i + n]) if predict else None, ptr(counts[i:i + n]) if predict else None,
+                                                *(ptr(f[i:i + n]) if predict else None for f in fpn),
+                                                _lib.current_stream(dev)), "jn_detector_eval_loss")
+            for j, k in enumerate(LOSS_NAMES):
+                tot[k] = tot[k] + metrics[j] * (n / N)
+        if packed and predict:
+            outputs = (boxes, counts)
+        else:
+            outputs = self._boxes_to_list(boxes, counts) if predict else [None] * N
+        return outputs, (tuple(fpn) if predict else None), tot
+
+    def validation_loss(self, patches: torch.Tensor, targets: torch.Tensor, predict: bool = True, packed: bool = False):
+        """``forward(patches, targets)`` on the validation route whatever the modes are (``eval_supervised_on_images``
+        puts the model in eval mode itself): (outputs, fpn_outs, losses), see the class docstring."""
+        g = self._gpt
+        g.sync_weights()
+        assert targets.shape[0] == patches.shape[0] and targets.shape[-1] >= 5
+        x = patches.to(g.device, torch.float32).contiguous()
+        t = targets[..., :5].to(g.device, torch.float32).contiguous()
+        check_box_cap(t)
+        return self._validation_forward(x, t, predict, packed)
 
     def loss_and_backward(self, patches: torch.Tensor, targets: torch.Tensor, loss_scale: float = 1.0) -> dict:
         """Loss branch of src/models/yolox.py:58-73 AND ``(loss_scale * total_loss).backward()`` in one engine call
