@@ -182,7 +182,7 @@ void add_param(std::vector<ParamEntry>& params, const std::string& name, std::in
 // One trainable tensor inside the flat parameter arena.
 struct ParamSeg {
   std::string name;          // the reference's state-dict name
-  int kind = 0, d0 = 0, d1 = 0, d2 = 0;   // packing (api.hip: PackKind) and its dimensions
+  int kind = 0, d0 = 0, d1 = 0, d2 = 0;   // packing (api_ctx.hip: PackKind) and its dimensions
   size_t off = 0, numel = 0;
 };
 
@@ -270,7 +270,7 @@ struct jn_ctx {
   int64_t* det_pos = nullptr; size_t det_pos_cap = 0;   // [T+1][B][2] per-step position snapshots for the detector stream
   float* det_raw = nullptr;       // [B][A][6] decoded head output
   float* det_logits = nullptr;    // [B][A][6] raw predictor outputs of the training pass (consumed by the loss kernel)
-  // one entry per resident detector training pass (jn_detector_forward ... jn_detector_backward, api.hip)
+  // one entry per resident detector training pass (jn_detector_forward ... jn_detector_backward, api_det.hip)
   struct DetPass {
     float* dlogits = nullptr;     // [B][A][6] d loss / d raw (before the 1 / num_fg factor)
     float* acc = nullptr;         // [8] scale (scale[0] = loss_scale / max(num_fg, 1)), then [max_batch][8] per-patch loss sums
@@ -314,3 +314,78 @@ struct jn_ctx {
   std::vector<hipEvent_t> conv_ev;   // pairs per step when profiling
   int conv_ev_used = 0;
 };
+
+// ---- host helpers that cross the api_*.hip units (each defined in the unit its heading names) ----------------------
+namespace jnr {
+
+// where a stem reads its patches: plain patches (positions = null) or windows of whole images at `positions`
+struct StemSrc {
+  const void* src; const int64_t* positions; long long sample_stride, chan_stride; int row_stride;
+  int pos_stride = 2;
+  int src_u8 = 0;     // src holds uint8 (the env's byte images): StemArgs::src_u8
+};
+
+template <typename T>
+int dev_alloc(jn_ctx* ctx, T** out, size_t count) {
+  void* p = nullptr;
+  if (count == 0) count = 1;
+  hipError_t e = hipMalloc(&p, count * sizeof(T));
+  if (e != hipSuccess) {
+    set_error("hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e));
+    return JN_ENOMEM;
+  }
+  ctx->owned.push_back(p);
+  *out = (T*)p;
+  return JN_OK;
+}
+
+// workspace slots.  Activation buffers are stored as net.act_dtype (JN_F32: 4-byte, JN_BF16: 2-byte elements).
+inline size_t act_esz(const Net& net) { return net.act_dtype == JN_BF16 ? 2 : 4; }
+inline void* view_ptr(const Net& net, int slot, int max_batch, const View& v) {
+  const size_t elem = (size_t)slot * net.per_image_floats * max_batch + net.buf_off[v.buf] * (size_t)max_batch + v.coff;
+  return reinterpret_cast<char*>(net.act) + elem * act_esz(net);
+}
+inline ChanTab view_tab(const Net& net, int slot, const View& v) {
+  float* t = net.tab + (size_t)slot * 3 * net.tab_channels + net.tab_off[v.buf] + v.coff;
+  return ChanTab{t, t + net.tab_channels, t + 2 * net.tab_channels};
+}
+inline double* slot_stats(const Net& net, int slot) { return net.stats + (size_t)slot * JN_NREP * 2 * net.stat_channels; }
+inline float* grad_of(const jn_ctx* ctx, const float* param) { return ctx->grads + (param - ctx->params); }
+
+// api_ctx.hip
+int dev_upload(jn_ctx* ctx, float** out, const std::vector<float>& host);
+int n_parts(const jn_config& c);
+// api_net.hip
+StemSrc patch_src(const void* ptr, int P, long long sample_stride = 0);
+int ensure_slots(jn_ctx* ctx, Net& net, int n_slots);
+int refresh_eval_table(jn_ctx* ctx, Net& net, hipStream_t s);
+void mark_params_written(jn_ctx* ctx);
+int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int train, const int* skip_flag, int skip_when,
+            hipStream_t s, bool with_head = false, int first_op = 0);
+int ensure_train_state(jn_ctx* ctx, int g_slots = 1);
+int ensure_aux_stream(jn_ctx* ctx);
+int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, hipStream_t s, int nsl = 1,
+                     long long pos_slot_stride = 0, bool with_head = false, int fpn_zero = 0);
+int run_embed_fpn(jn_ctx* ctx, int N, int slot, float* e_buf, const int* skip_flag, int skip_when, hipStream_t s);
+int embed_tokens(jn_ctx* ctx, const StemSrc& ss, int N, int train, float* e_buf, float* out, long long out_stride,
+                 hipStream_t s);
+// api_det.hip
+int det_slot_base(const jn_ctx* ctx);
+int detect_impl(jn_ctx* ctx, const StemSrc& ss, int N, float* boxes_dev, int32_t* counts_dev, float* raw_dev,
+                const int* skip_flag, int skip_when, hipStream_t s);
+// api_env.hip
+EnvPtrs env_ptrs(jn_ctx* ctx);
+void env_gather(const EnvState& e, float* out, long long out_sample_stride, int P, const int* skip_flag, int skip_when,
+                hipStream_t s);
+StemSrc env_stem_src(const EnvState& e, const int64_t* positions);
+int ensure_stage(jn_ctx* ctx, int cols);
+void stage_fill(const EnvState& e, int P, int t, const int* skip_flag, int skip_when, hipStream_t s);
+StemSrc stage_stem_src(const EnvState& e, int P, int t);
+// api_rollout.hip
+int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const int64_t* start_positions_dev, uint64_t seed,
+                 int do_detection, int stop_early, const jn_rollout_out* out, int train, void* stream);
+// api_train.hip
+void fill_gpt_weights(const jn_ctx* ctx, GptStepArgs& a);
+int ensure_token_train_buffers(jn_ctx* ctx);
+
+}  // namespace jnr

@@ -378,7 +378,7 @@ int launch_reinforce_loss(const LossArgs& a, hipStream_t s);
 // autograd bridge: d loss / d logits [B][T][nA] from d loss / d logprobs and d loss / d entropies [B][T] (either may be null)
 int launch_logits_grad(const float* logits, const int64_t* actions, const float* dlogprobs, const float* dentropies,
                        const int32_t* n_done, float* dlogits, int B, int T, int nA, int stop_early, hipStream_t s);
-// one trainable tensor of the flat arena: packing kind (api.hip PackKind) and dimensions; `off` is its offset both in the
+// one trainable tensor of the flat arena: packing kind (api_ctx.hip PackKind) and dimensions; `off` is its offset both in the
 // packed arena and in a reference-layout buffer of the same size
 struct ArenaSeg { long long off, numel; int kind, d0, d1, d2; };
 int launch_arena_copy(const ArenaSeg* segs, int n_segs, float* arena, float* ref, long long total, int to_ref, int accumulate,

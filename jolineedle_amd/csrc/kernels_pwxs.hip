@@ -597,7 +597,7 @@ bool pw_x3_bwd_data_supported(int cout, int cin) {
   return (cout == 256 && (cin == 128 || cin == 256 || cin == 512)) || (cout == 128 && cin == 256);
 }
 
-// a: the ConvArgs of the gradient conv as api.hip builds them for launch_pw (in = g_z, out = g_x, cin = layer's cout,
+// a: the ConvArgs of the gradient conv as api_net.hip builds them for launch_pw (in = g_z, out = g_x, cin = layer's cout,
 // cout = layer's cin, slots); w = the layer's [cout][cin] weight, w3t = 3 * cout * cin bf16 of scratch owned by the layer
 int launch_pw_x3_bwd_data(const ConvArgs& a, const float* w, void* w3t, hipStream_t s) {
   const int K = a.cin, N = a.cout;                      // of the gradient conv

@@ -131,7 +131,7 @@ int launch_logits_grad(const float* logits, const int64_t* actions, const float*
 
 // ---- packed arena <-> reference (PyTorch) layout, on the device --------------------------------------------------
 // One thread per element of the reference-layout buffer (same segment offsets as the arena): finds its segment by
-// bisection and maps the index by the segment's packing (api.hip: PackKind / unpack_param).
+// bisection and maps the index by the segment's packing (api_ctx.hip: PackKind / unpack_param).
 __device__ __forceinline__ long long packed_index(const ArenaSeg& g, long long r) {
   switch (g.kind) {
     case 1: { const long long o = r / g.d1, i = r - o * g.d1; return i * g.d0 + o; }                       // PK_T [out][in] -> [in][out]

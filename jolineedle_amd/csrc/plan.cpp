@@ -392,7 +392,7 @@ int shortcut_sum_conv(const Net& net, const View& seg, int reader, int also, int
 
 // The backward of `net` as a pure function of its topology, activation dtype, the head (with_head) and the FPN outputs
 // that get no outside gradient (fpn_zero bit i: none arrives in fpn[i], the training backward's case): one record per
-// op of the backward range, filled walking it in reverse like the launcher (run_net_backward, api.hip).
+// op of the backward range, filled walking it in reverse like the launcher (run_net_backward, api_net.hip).
 int plan_backward(const Net& net, bool with_head, int fpn_zero, std::vector<BwdStep>& plan) {
   const int n = (with_head || net.n_backbone_ops < 0) ? (int)net.ops.size() : net.n_backbone_ops;
   const bool f32 = net.act_dtype == JN_F32;
@@ -517,7 +517,7 @@ bool defer_eligible(const Net& net) {
 
 // One forward pass of `net` over N patches as a pure function of its topology, activation dtype and the pass (train,
 // with_head, the first op, whether it defers): one record per op of [first_op, n_ops), in launch order.  What depends
-// on launch-time state (pw_fused_upsample_supported, JN_NO_PW_X3, the stream) stays with the launcher (run_net, api.hip).
+// on launch-time state (pw_fused_upsample_supported, JN_NO_PW_X3, the stream) stays with the launcher (run_net, api_net.hip).
 int plan_forward(const Net& net, int N, bool train, bool with_head, int first_op, bool defer, std::vector<FwdStep>& plan) {
   const int n = (with_head || net.n_backbone_ops < 0) ? (int)net.ops.size() : net.n_backbone_ops;
   const bool f32 = net.act_dtype == JN_F32;

@@ -161,6 +161,24 @@ def test_supervised_eval_against_the_eval_mode_oracle(B, T, tok_seed):
     assert (lg_old - got["logits"]).abs().max() < TOL_LOGIT
 
 
+def test_supervised_eval_and_gpt_forward_decode_alike():
+    """B = 3, T = 3 at max_batch 4, eval mode, no dropout: jn_supervised_eval (encoder chunks of 4 + 4 + 1 patches) and
+    jn_gpt_forward (three passes of 3) embed and decode through the same two functions of the library, so their logits on
+    the same inputs are equal bit for bit."""
+    product, _ = make_pair(3, patch_size=64, block_size=8, with_detector=False, image_processor=None, max_batch=4)
+    product.eval()
+    patches, cur, positions = synth_tokens(3, 3, 64, 9, 4, 100)
+    classes, masks = torch.tensor([3, 99, 0]), prefix_masks([3, 2, 1], 3)
+    nxt = torch.randint(0, 9, (3, 3), generator=torch.Generator().manual_seed(7))
+    got = ja.SupervisedTrainer(_sup_cfg(), product).eval_step(patches, cur, nxt, positions, masks, classes=classes)
+    with torch.no_grad():
+        logits, _ = product(patches, cur, classes, positions)
+    torch.cuda.synchronize()
+    print(f"largest difference of the two paths' logits: {float((logits - got['logits']).abs().max()):.3e}")
+    assert logits.shape == got["logits"].shape == (3, 3, 9)
+    assert torch.equal(logits, got["logits"])
+
+
 def test_supervised_eval_limits_and_a_pending_backward():
     product, _ = make_pair(3, patch_size=64, block_size=8, with_detector=False, image_processor=None, max_batch=4)
     tr = ja.SupervisedTrainer(_sup_cfg(), product)
