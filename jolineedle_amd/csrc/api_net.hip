@@ -141,22 +141,40 @@ int refresh_eval_table(jn_ctx* ctx, Net& net, hipStream_t s) {
 // fp32 passes: the 1x1 weights of `net` as three bf16 planes for pw_x3_kernel (bf16 inference mode uses the h plane
 // alone: pw_x1).  Split again only after something wrote the arena (mark_params_written): a rollout's T passes and
 // every eval pass in between reuse the planes (for yolox-s / -m detectors the split is tens of MB per pass).
-static void refresh_x3_planes(jn_ctx* ctx, Net& net, hipStream_t s) {
+// Two launches per split: the whole range in flat order, then the convs of pw_x3_fragment_order rewritten in fragment
+// order from one device table (built once per net, with the range, when the weights have their arena places).
+static int refresh_x3_planes(jn_ctx* ctx, Net& net, hipStream_t s) {
   if (net.x3_hi == 0) {
     size_t lo = ctx->arena_size, hi = 0;
+    std::vector<X3FragConv> frag;
     for (const Op& op : net.ops) {
       if (op.kind != OP_PW || op.wslot < 0) continue;
       const ConvW& cw = net.convs[op.wslot];
       if (!cw.w_dev) continue;
       const size_t o = (size_t)(cw.w_dev - ctx->params);
       lo = std::min(lo, o); hi = std::max(hi, o + (size_t)cw.cout * cw.cin);
+      // (the shape and the alignment run_net hands the kernels: a.cin, a.cout, a.w_x3)
+      if (o % 8 == 0 && op.in.C * op.out.C == cw.cin * cw.cout && pw_x3_fragment_order(op.in.C, op.out.C)) {
+        bool seen = false;                                // (a conv two ops share is rewritten once)
+        for (const X3FragConv& f : frag) seen = seen || f.off == (long long)o;
+        if (!seen) frag.push_back(X3FragConv{(long long)o, op.out.C, op.in.C});
+      }
+    }
+    if (!frag.empty() && !net.x3_frag) {
+      int rc;
+      if ((rc = dev_alloc(ctx, &net.x3_frag, frag.size()))) return rc;
+      JN_HIP(hipMemcpy(net.x3_frag, frag.data(), frag.size() * sizeof(X3FragConv), hipMemcpyHostToDevice));
+      net.x3_frag_n = (int)frag.size();
+      for (const X3FragConv& f : frag) net.x3_frag_max = std::max(net.x3_frag_max, f.cout * f.cin);
     }
     net.x3_lo = lo / 8 * 8; net.x3_hi = hi > lo ? (hi + 7) / 8 * 8 : 0;
   }
   if (net.x3_hi > net.x3_lo && net.x3_dirty) {
     launch_w_split3(ctx->params + net.x3_lo, ctx->params_x3 + 3 * net.x3_lo, (long long)(net.x3_hi - net.x3_lo), s);
+    launch_w_split3_frag(ctx->params, ctx->params_x3, net.x3_frag, net.x3_frag_n, net.x3_frag_max, s);
     net.x3_dirty = false;
   }
+  return JN_OK;
 }
 
 // Something wrote the parameter arena (jn_load_weights, an optimiser step, jn_import_arena): BN affine and 1x1 weights
@@ -272,7 +290,7 @@ int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int train, 
   invalidate_slot_state(ctx, ni, slot);
   if (!train && (rc = refresh_eval_table(ctx, net, s))) return rc;
   const bool x3 = ctx->params_x3 && !std::getenv("JN_NO_PW_X3");   // read per pass: tests flip it
-  if (x3) refresh_x3_planes(ctx, net, s);
+  if (x3 && (rc = refresh_x3_planes(ctx, net, s))) return rc;
   double* stats = train ? slot_stats(net, slot) : nullptr;
   float* save = train ? slot_save(net, slot) : nullptr;
   // (a train-mode rollout zeroes the statistics of all its slots with ONE memset up front)

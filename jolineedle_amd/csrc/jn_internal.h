@@ -101,6 +101,8 @@ struct Net {
   int n_backbone_ops = -1;  // ops before the detection head (-1: no head, all ops)
   size_t x3_lo = 0, x3_hi = 0;   // arena range of the 1x1 weights (multiples of 8 floats; hi == 0: not computed yet)
   bool x3_dirty = true;           // the bf16 planes of that range are older than the parameters (see mark_params_written)
+  X3FragConv* x3_frag = nullptr;  // device table of the 1x1 convs whose planes are kept in fragment order (pw_x3_fragment_order)
+  int x3_frag_n = 0, x3_frag_max = 0;   // its rows, the largest cout * cin among them
   int n_anchors = 0, head_hid = 0;
   float* pred_w[3] = {nullptr, nullptr, nullptr};   // [6][hid] reg(4), obj, cls predictor rows
   float* pred_b[3] = {nullptr, nullptr, nullptr};   // [6]

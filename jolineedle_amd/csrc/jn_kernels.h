@@ -114,7 +114,20 @@ int launch_pw_dir(const ConvArgs& a, int ctw, hipStream_t s);
 int launch_pw_wide(const ConvArgs& a, hipStream_t s);   // production route: 0 when taken
 bool pw_xs_supported(const ConvArgs& a);               // kernels_pwxs.hip: pixel-stationary kernel for the small maps of a forward pass
 int launch_pw_xs(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu = 0);   // pt: pixel tiles per workgroup (0 = default)
-int launch_pw_x3(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu = 0);   // the same on the bf16 pipe (three-way split operands); needs a.w_x3
+// the same on the bf16 pipe (three-way split operands); needs a.w_x3.  frag: the order a.w_x3 is in (-1: the rule below; the
+// other order of a shape is built for tools/pwxsbench.hip only)
+int launch_pw_x3(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu = 0, int frag = -1);
+// THE layout rule of the split planes of a 1x1 conv (ConvArgs::w_x3): true = MFMA fragment order (kernels_pwxs.hip,
+// w_split3_frag_kernel), false = the flat [row][k / 8][h | m | l] order of w_split3_kernel.  Asked by the splitter's table
+// (api_net.hip) and by every reader: launch_pw_x3, its fused-upsample form and launch_pw_x1.  Shapes: what
+// profiles/pwfrag_bench.txt decided, shape by shape — every shape pw_x3_kernel is built for gains more than the spread of
+// the tool's repeats (K = 64, whose two k steps are fetched once per workgroup: 4 - 9 %; K >= 128: 9 - 41 %).
+constexpr bool pw_x3_fragment_order(int cin, int cout) {
+  return (cin == 64 && (cout == 64 || cout == 128)) || (cin == 128 && (cout == 64 || cout == 128 || cout == 256)) ||
+         (cin == 256 && (cout == 128 || cout == 256)) || (cin == 512 && cout == 256);
+}
+struct X3FragConv { long long off; int cout, cin; };   // a conv of the splitter's table: arena offset of its weight (floats, % 8 == 0)
+void launch_w_split3_frag(const float* params, void* params_x3, const X3FragConv* tab, int n_convs, int max_weights, hipStream_t s);
 bool pw_x3_preferred(const ConvArgs& a);
 // the data gradient of a wide 1x1 layer on pw_x3_kernel (transposed split weight made on the way); -1: shape not taken
 bool pw_x3_bwd_data_supported(int cout, int cin);

@@ -1078,7 +1078,7 @@ static int launch_pw_small_maps(const ConvArgs& a, hipStream_t s) {
 bool pw_fused_upsample_supported(const ConvArgs& a) {
   if ((long long)a.N * a.H * a.W > JN_XS_MAX_M || !pw_xs_supported(a)) return false;
   if (a.cin == 128 && a.cout == 64) return pw_x3_preferred(a);          // pw_x3_kernel<128, 1, 2, 4>
-  return a.cin == 256 && a.cout == 128;                                  // pw_xs_kernel<256, 2, 2, 4>
+  return a.cin == 256 && a.cout == 128;                                  // pw_x3_kernel<256, 2, 2, 2>; fp32 pipe: pw_xs_kernel<256, 2, 2, 4>
 }
 
 int launch_pw(const ConvArgs& a, hipStream_t s) {

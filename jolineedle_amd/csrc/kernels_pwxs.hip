@@ -274,8 +274,10 @@ int launch_pw_xs(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu) {
 // l*l) are dropped and the other six run on v_mfma_f32_16x16x32_bf16 into the same fp32 accumulator: 6 x 16 cycles per
 // 32 k instead of 8 x 32.  The error against an fp64 sum is that of the fp32 fmaf chain (measured, pwxsbench).
 //   * the operand tile is split where it is transformed (once per element) and staged as three bf16 planes;
-//   * the weights are split once per pass for the whole parameter arena (w_split3_kernel): groups of 8 consecutive
-//     elements as [h x 8 | m x 8 | l x 8], i.e. the 48 bytes lane (row, g) needs for one 32-wide k step.
+//   * the weights are split for the whole range of 1x1 weights of the parameter arena whenever it was written
+//     (w_split3_kernel): groups of 8 consecutive elements as [h x 8 | m x 8 | l x 8], i.e. the 48 bytes lane (row, g) needs
+//     for one 32-wide k step — the FLAT order; the layers this kernel takes (pw_x3_fragment_order) have their regions
+//     rewritten in MFMA fragment order by one more launch (w_split3_frag_kernel, below).
 __global__ __launch_bounds__(256) void w_split3_kernel(const float* __restrict__ w, bf16_t* __restrict__ w3, long long n8) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n8) return;
@@ -300,17 +302,54 @@ void launch_w_split3(const float* w, void* w3, long long n_floats, hipStream_t s
   hipLaunchKernelGGL(w_split3_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, w, (bf16_t*)w3, n8);
 }
 
+// Fragment order (pw_x3_fragment_order, jn_kernels.h): the same three planes of a [cout][cin] weight as blocks of 64 lanes x 8
+// bf16 — block ((c16 * cin / 32 + j) * 3 + plane), lane (g, lm) holding w[16 c16 + lm][32 j + 8 g .. + 7] — so that a wave's
+// load of one MFMA fragment is 1 KB contiguous.  One launch after w_split3_kernel rewrites the regions of every conv of the
+// table (blockIdx.y = table row) straight from the fp32 weights: the same three roundings, another address.  A conv's region
+// keeps its place and size in the plane arena (3 * cout * cin bf16 at 3 * off).
+__global__ __launch_bounds__(256) void w_split3_frag_kernel(const float* __restrict__ params, bf16_t* __restrict__ params_x3,
+                                                            const X3FragConv* __restrict__ tab) {
+  const X3FragConv c = tab[blockIdx.y];
+  const int i = blockIdx.x * 256 + threadIdx.x, groups = c.cin / 8;   // (row n, group of 8 input channels)
+  if (i >= c.cout * groups) return;
+  const int n = i / groups, kq = i - n * groups, j = kq >> 2, g = kq & 3;
+  const float* w = params + c.off + 8LL * i;
+  const f32x4 a = *reinterpret_cast<const f32x4*>(w), b = *reinterpret_cast<const f32x4*>(w + 4);
+  bf16x8 h, m, l;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float v = e < 4 ? a[e] : b[e - 4];
+    const bf16_t vh = (bf16_t)v;
+    const float r1 = v - (float)vh;
+    const bf16_t vm = (bf16_t)r1;
+    const float r2 = r1 - (float)vm;
+    h[e] = vh; m[e] = vm; l[e] = (bf16_t)r2;
+  }
+  bf16_t* o = params_x3 + 3 * c.off + ((long long)((n >> 4) * (c.cin / 32) + j) * 3 * 64 + g * 16 + (n & 15)) * 8;
+  *reinterpret_cast<bf16x8*>(o) = h;
+  *reinterpret_cast<bf16x8*>(o + 512) = m;
+  *reinterpret_cast<bf16x8*>(o + 1024) = l;
+}
+
+void launch_w_split3_frag(const float* params, void* params_x3, const X3FragConv* tab, int n_convs, int max_weights, hipStream_t s) {
+  if (n_convs <= 0 || max_weights <= 0) return;
+  hipLaunchKernelGGL(w_split3_frag_kernel, dim3((unsigned)((max_weights / 8 + 255) / 256), (unsigned)n_convs), dim3(256), 0, s,
+                     params, (bf16_t*)params_x3, tab);
+}
+
 // NP = 3, XT = float: the fp32 route.  NP = 1, XT = bf16: the bf16 inference mode on the same kernel — bf16 activations in
 // and out, ONE plane (the operand rounded to bf16, as that mode defines its products), the weights' h plane.
 // SLOTS (round 4, the data gradient of the wide layers in the step-batched backward): the operand is n_slots maps of M pixels
 // each, `sl.in` / `sl.out` elements apart (the workspace slots of the glimpse steps); a tile never straddles two slots.
 struct SlotSpan { int n_slots; long long in, out; };
-// With SLOTS the split weights come in FRAGMENT ORDER: block ((c16 * K / 32 + j) * 3 + plane) of 64 lanes x 8 bf16, lane
+// FRAG: the split weights come in FRAGMENT ORDER: block ((c16 * K / 32 + j) * 3 + plane) of 64 lanes x 8 bf16, lane
 // (g, lm) holding w[16 c16 + lm][32 j + 8 g .. + 7] — a wave's load of one fragment is 1 KB contiguous (8 cache lines).  The
-// [row][k / 8][h | m | l] order of the forward planes makes the same load 64 pieces of 16 bytes in 32 lines, three times over
-// for the three planes: with K = 256 the weights are streamed per tile and the L1 tag rate, not the matrix pipe, set the pace
-// (383 us per 250 880-pixel launch against 79 us of matrix time).
-template <int K, int CTW, int PT, int D, int NP, typename XT, bool UPS = false, bool SLOTS = false>
+// flat [row][k / 8][h | m | l] order makes the same load 64 pieces of 16 bytes in 32 lines, three times over for the three
+// planes: with K = 256 the weights are streamed per tile and the L1 tag rate, not the matrix pipe, set the pace (data
+// gradient: 383 us per 250 880-pixel launch against 79 us of matrix time; 265 us in fragment order).  Always with SLOTS
+// (w_split3_t_kernel writes that order); in the forward for the shapes of pw_x3_fragment_order (w_split3_frag_kernel), NP = 1
+// and UPS included.  Only the addresses differ: the fragments, the product order and the accumulation order are the same.
+template <int K, int CTW, int PT, int D, int NP, typename XT, bool UPS = false, bool SLOTS = false, bool FRAG = SLOTS>
 __global__ __launch_bounds__(256, (K <= 64 ? 3 : CTW <= 2 ? 2 : 1)) void pw_x3_kernel(
     const XT* __restrict__ x, int x_ld, ChanTab it, const bf16_t* __restrict__ w3, XT* __restrict__ out, int out_ld,
     long long M, double* __restrict__ stats, long long rep_stride, int nrep, const int* __restrict__ skip_flag,
@@ -334,11 +373,11 @@ __global__ __launch_bounds__(256, (K <= 64 ? 3 : CTW <= 2 ? 2 : 1)) void pw_x3_k
   const bf16_t* wrow[CTW];
 #pragma unroll
   for (int c = 0; c < CTW; ++c)
-    wrow[c] = SLOTS ? w3 + (long long)(wave * CTW + c) * (K / 32) * 3 * 512 + lane * 8
-                    : w3 + ((long long)((wave * CTW + c) * 16 + lm) * (K / 8) + g) * 24;
+    wrow[c] = FRAG ? w3 + (long long)(wave * CTW + c) * (K / 32) * 3 * 512 + lane * 8
+                   : w3 + ((long long)((wave * CTW + c) * 16 + lm) * (K / 8) + g) * 24;
   // fragment (k step j, plane t) of channel tile c
   auto wfrag = [&](int c, int j, int t) -> bf16x8 {
-    if constexpr (SLOTS) return *reinterpret_cast<const bf16x8*>(wrow[c] + (j * 3 + t) * 512);
+    if constexpr (FRAG) return *reinterpret_cast<const bf16x8*>(wrow[c] + (j * 3 + t) * 512);
     else return *reinterpret_cast<const bf16x8*>(wrow[c] + 96 * j + 8 * t);
   };
   bf16x8 wr[D][CTW][NP];
@@ -484,11 +523,11 @@ __global__ __launch_bounds__(256, (K <= 64 ? 3 : CTW <= 2 ? 2 : 1)) void pw_x3_k
   }
 }
 
-template <int K, int CTW, int PT, int D, int NP, typename XT, bool UPS = false, bool SLOTS = false>
+template <int K, int CTW, int PT, int D, int NP, typename XT, bool UPS = false, bool SLOTS = false, bool FRAG = SLOTS>
 static void launch_pw_x3_t(const ConvArgs& a, long long M, int wg_per_cu, hipStream_t s) {
   constexpr int BM = 16 * PT;
   const size_t smem = (size_t)NP * BM * (K + 16) * sizeof(bf16_t) + 3 * K * sizeof(float);
-  auto kern = pw_x3_kernel<K, CTW, PT, D, NP, XT, UPS, SLOTS>;
+  auto kern = pw_x3_kernel<K, CTW, PT, D, NP, XT, UPS, SLOTS, FRAG>;
   static int places = 0;
   if (!places) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -506,9 +545,11 @@ static void launch_pw_x3_t(const ConvArgs& a, long long M, int wg_per_cu, hipStr
                      SlotSpan{n_slots, a.in_slot_stride, a.out_slot_stride});
 }
 
-// Shapes the x3 kernel is built for — the ones where it beats pw_xs_kernel (tools/pwxsbench.hip, profiles/r03_x3bench.txt:
-// 8 - 21 %); with K >= 256 the weight fragments are streamed per tile and their 1.5x bytes cost more than the matrix
-// cycles saved, except for 256 -> 256 on 64-pixel tiles.
+// Shapes the x3 kernel is built for — the ones where it beats pw_xs_kernel (tools/pwxsbench.hip).  With the planes in flat
+// order that was K <= 128 with N <= 128 (profiles/r03_x3bench.txt: 8 - 21 %) and 256 -> 256 on 64-pixel tiles: wider, the
+// weight fragments are streamed per tile and their scattered 16-byte pieces cost more than the matrix cycles saved.  In
+// fragment order it is every shape of the pixel-stationary kernel (profiles/pwfrag_bench.txt: 14 - 29 % under pw_xs_kernel
+// at K >= 128, 9 - 41 % under the flat order; K = 64: 4 - 9 % under the flat order).
 static bool pw_xs_shape(int K, int N) {
   if (!(K == 64 || K == 128 || K == 256 || K == 512) || !(N == 64 || N == 128 || N == 256)) return false;
   return !(K == 64 && N == 256) && !(K == 512 && N != 256) && !(K == 256 && N == 64);
@@ -516,8 +557,7 @@ static bool pw_xs_shape(int K, int N) {
 
 bool pw_x3_preferred(const ConvArgs& a) {
   if (!a.w_x3 || !pw_xs_supported(a)) return false;
-  const int K = a.cin, N = a.cout;
-  return (K == 64 && (N == 64 || N == 128)) || (K == 128 && (N == 64 || N == 128)) || (K == 256 && N == 256);
+  return pw_x3_fragment_order(a.cin, a.cout);
 }
 
 // bf16 inference mode (bf16 activations in and out, bf16 MFMA): the single-plane form of the kernel, every xs shape
@@ -531,33 +571,53 @@ int launch_pw_x1(const ConvArgs& a, hipStream_t s) {
   const long long M = (long long)a.N * a.H * a.W;
   const int K = a.cin, ctw = a.cout / 64;
   const int wg = (K == 512 || ctw == 4) ? 1 : 2;
-#define JN_X1(K_, C_, P_, D_) if (K == K_ && ctw == C_) { launch_pw_x3_t<K_, C_, P_, D_, 1, bf16_t>(a, M, wg, s); return 0; }
+#define JN_X1(K_, C_, P_, D_) \
+  if (K == K_ && ctw == C_) { launch_pw_x3_t<K_, C_, P_, D_, 1, bf16_t, false, false, pw_x3_fragment_order(K_, 64 * C_)>(a, M, wg, s); return 0; }
   JN_X1(64, 1, 2, 2) JN_X1(64, 2, 2, 2) JN_X1(128, 1, 2, 4) JN_X1(128, 2, 2, 4) JN_X1(128, 4, 2, 4)
   JN_X1(256, 2, 4, 2) JN_X1(256, 4, 4, 2) JN_X1(512, 4, 4, 2)
 #undef JN_X1
   return -1;
 }
 
-int launch_pw_x3(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu) {
+int launch_pw_x3(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu, int frag) {
   if (!pw_xs_supported(a) || !a.w_x3) return -1;
   const long long M = (long long)a.N * a.H * a.W;
   const int K = a.cin, ctw = a.cout / 64;
+  const int rule = pw_x3_fragment_order(K, a.cout) ? 1 : 0;
+  if (frag < 0) frag = rule;
   if (pt == 0) {
-    // measured best per shape: 32-pixel tiles, two persistent workgroups per CU (one when there is at most a tile or two
-    // per workgroup anyway, or for 64 -> 128); 256 -> 256: 64-pixel tiles halve the weight stream
-    pt = K == 256 ? 4 : 2;
-    if (wg_per_cu == 0) wg_per_cu = (K == 256 || (K == 64 && ctw == 2) || (K == 128 && ctw == 2 && M <= 16384)) ? 1 : 2;
+    // measured best per shape (profiles/pwfrag_bench.txt): 32-pixel tiles, two persistent workgroups per CU (one when there
+    // is at most a tile or two per workgroup anyway, or for 64 -> 128); 256 -> 256 stays on 64-pixel tiles, one workgroup
+    // per CU (in fragment order the 32-pixel tiles tie with them: 22.8 / 23.0 us)
+    const bool sq256 = K == 256 && ctw == 4;
+    pt = sq256 ? 4 : 2;
+    if (wg_per_cu == 0) wg_per_cu = (sq256 || (K == 64 && ctw == 2) || (K == 128 && ctw == 2 && M <= 16384)) ? 1 : 2;
   }
-  if (a.up_out) {                       // fused x2 upsample of the output: the one shape that needs it on this route
-    if (!(K == 128 && ctw == 1 && pt == 2)) return -1;
-    launch_pw_x3_t<128, 1, 2, 4, 3, float, true>(a, M, wg_per_cu, s);
-    return 0;
+  if (a.up_out) {                       // fused x2 upsample of the output: the two shapes that need it (reduce_conv1, lateral_conv0)
+    if (pt != 2 || frag != rule) return -1;
+    if (K == 128 && ctw == 1) { launch_pw_x3_t<128, 1, 2, 4, 3, float, true, false, pw_x3_fragment_order(128, 64)>(a, M, wg_per_cu, s); return 0; }
+    if (K == 256 && ctw == 2) { launch_pw_x3_t<256, 2, 2, 2, 3, float, true, false, pw_x3_fragment_order(256, 128)>(a, M, wg_per_cu, s); return 0; }
+    return -1;
   }
-#define JN_X3(K_, C_, P_, D_) if (K == K_ && ctw == C_ && pt == P_) { launch_pw_x3_t<K_, C_, P_, D_, 3, float>(a, M, wg_per_cu, s); return 0; }
-  JN_X3(64, 1, 2, 2) JN_X3(64, 2, 2, 2) JN_X3(128, 1, 2, 4) JN_X3(128, 2, 2, 4) JN_X3(256, 4, 4, 2)
-#ifdef JN_X3_ALL_SHAPES        // tools/pwxsbench.hip: every shape and tile size, to show where the kernel loses
-  JN_X3(64, 1, 4, 2) JN_X3(64, 2, 4, 2) JN_X3(128, 1, 4, 4) JN_X3(128, 2, 4, 4) JN_X3(128, 4, 2, 2) JN_X3(128, 4, 4, 2)
-  JN_X3(256, 2, 2, 2) JN_X3(256, 2, 4, 2) JN_X3(256, 4, 2, 2) JN_X3(512, 4, 2, 2)
+#ifdef JN_X3_ALL_SHAPES        // tools/pwxsbench.hip: every shape and tile size in both weight orders, to show where each loses
+#define JN_X3(K_, C_, P_, D_)                                                                   \
+  if (K == K_ && ctw == C_ && pt == P_) {                                                       \
+    if (frag) launch_pw_x3_t<K_, C_, P_, D_, 3, float, false, false, true>(a, M, wg_per_cu, s);  \
+    else launch_pw_x3_t<K_, C_, P_, D_, 3, float, false, false, false>(a, M, wg_per_cu, s);      \
+    return 0;                                                                                   \
+  }
+#else
+#define JN_X3(K_, C_, P_, D_)                                                                                           \
+  if (K == K_ && ctw == C_ && pt == P_ && frag == rule) {                                                               \
+    launch_pw_x3_t<K_, C_, P_, D_, 3, float, false, false, pw_x3_fragment_order(K_, 64 * C_)>(a, M, wg_per_cu, s);       \
+    return 0;                                                                                                           \
+  }
+#endif
+  JN_X3(64, 1, 2, 2) JN_X3(64, 2, 2, 2) JN_X3(128, 1, 2, 4) JN_X3(128, 2, 2, 4) JN_X3(128, 4, 2, 2)
+  JN_X3(256, 2, 2, 2) JN_X3(256, 4, 4, 2) JN_X3(512, 4, 2, 2)
+#ifdef JN_X3_ALL_SHAPES
+  JN_X3(64, 1, 4, 2) JN_X3(64, 2, 4, 2) JN_X3(128, 1, 4, 4) JN_X3(128, 2, 4, 4) JN_X3(128, 4, 4, 2)
+  JN_X3(256, 2, 4, 2) JN_X3(256, 4, 2, 2)
 #endif
 #undef JN_X3
   return -1;

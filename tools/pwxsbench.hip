@@ -2,10 +2,14 @@
 // the generic pw_mfma_kernel on the small-map shapes of the nano PAFPN (B = 64, 448 px), with a plain table and with a
 // deferred (consumer-side BatchNorm) table as the train-mode pass uses it; results are compared bit for bit.
 // Round 3: the same shapes on the bf16 pipe with three-way split operands (pw_x3_kernel), timing and error against fp64.
+// `pwxsbench frag`: only the weight-order table of the pixel-stationary shapes (profiles/pwfrag_bench.txt) — pw_x3_kernel with the split
+// planes in flat and in MFMA fragment order against the fp32 pw_xs_kernel, per tile size and workgroups per CU; the two orders
+// must agree bit for bit on the outputs and on every workgroup's BatchNorm sums.
 //   build: hipcc -O3 -std=c++17 --offload-arch=gfx950 tools/pwxsbench.hip -o tools/pwxsbench
 #define JN_X3_ALL_SHAPES
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -69,6 +73,77 @@ int main(int argc, char** argv) {
     const float t_touch = time_it([&] { hipLaunchKernelGGL(touch_kernel, dim3(wgs), dim3(256), 0, s, (const float*)x, out); });
     printf("launch floor, %d workgroups: empty kernel %.2f us per dependent launch, one load + barrier + store %.2f us\n", wgs, t_null, t_touch);
   }
+  // ---- weight order of the split planes: flat [row][k / 8][h | m | l] against fragment order (w_split3_frag_kernel) ----
+  {
+    const Shape both[] = {{56, 64, 64}, {28, 64, 64}, {28, 64, 128}, {56, 128, 64}, {28, 128, 64}, {28, 128, 128}, {28, 256, 128}, {14, 128, 128}, {14, 128, 256},
+                          {14, 256, 128}, {14, 256, 256}, {14, 512, 256}};
+    void* w3f; X3FragConv* ftab; double* wstats;
+    const int NWG = 1024;                               // one statistics replica per workgroup (grids are at most 512)
+    CK(hipMalloc(&w3f, 512 * 512 * 6)); CK(hipMalloc(&ftab, sizeof(X3FragConv))); CK(hipMalloc(&wstats, (size_t)NWG * 512 * 8));
+    constexpr int REP = 5;
+    auto med_spread = [&](auto&& fn, float* spread) {   // median and max - min of REP timings of `iters` launches each
+      float t[REP];
+      for (int r = 0; r < REP; ++r) t[r] = time_it(fn);
+      std::sort(t, t + REP);
+      *spread = t[REP - 1] - t[0];
+      return t[REP / 2];
+    };
+    printf("# x3 flat / x3 fragment order / fp32 xs: median us of %d x %d launches (max - min), deferred table, B = %d\n", REP, iters, B);
+    for (const Shape& sh : both) {
+      const long long M = (long long)B * sh.hw * sh.hw;
+      std::vector<double> ds(8 * 2 * 4096, 0.0);
+      for (int r = 0; r < 8; ++r)
+        for (int c = 0; c < sh.K; ++c) { ds[(size_t)r * 2 * 4096 + 2 * c] = 0.1 * M / 8.0; ds[(size_t)r * 2 * 4096 + 2 * c + 1] = (1.0 + 0.01 * (c % 9)) * M / 8.0; }
+      CK(hipMemcpy(dstats, ds.data(), ds.size() * 8, hipMemcpyHostToDevice));
+      ChanTab defer{tab, tab + 2048, tab + 4096};
+      defer.dparams = params; defer.dstats = dstats; defer.drep_stride = 2 * 4096; defer.dN = B; defer.nseg = 1;
+      defer.r0 = ChanTab::Run{0, sh.K, 0, 0, 2048, (float)(sh.hw * sh.hw)};
+      const X3FragConv fc{0, sh.N, sh.K};
+      CK(hipMemcpy(ftab, &fc, sizeof(fc), hipMemcpyHostToDevice));
+      launch_w_split3_frag(w, w3f, ftab, 1, sh.N * sh.K, s); CK(hipDeviceSynchronize());
+      ConvArgs a{};
+      a.in = x; a.in_ld = sh.K; a.in_dtype = JN_F32; a.itab = defer; a.w = w; a.out = out; a.out_ld = sh.N;
+      a.out_dtype = JN_F32; a.N = B; a.H = sh.hw; a.W = sh.hw; a.OH = sh.hw; a.OW = sh.hw; a.cin = sh.K; a.cout = sh.N; a.stride = 1;
+      a.act = ACT_NONE; a.stats = stats; a.stats_rep_stride = 2 * 4096; a.stats_nrep = 8;
+      std::vector<float> of((size_t)M * sh.N), og((size_t)M * sh.N);
+      std::vector<double> sf((size_t)NWG * 512), sg((size_t)NWG * 512);
+      for (int pt : {2, 4})
+        for (int wg : {1, 2}) {
+          ConvArgs f = a; f.w_x3 = w3;
+          ConvArgs g = a; g.w_x3 = w3f;
+          const long long tiles = (M + 16 * pt - 1) / (16 * pt);
+          float sp_f, sp_g, sp_x = 0.f, t_x = 0.f;
+          const bool has_xs = launch_pw_xs(a, pt, s, wg) == 0;
+          if (has_xs) t_x = med_spread([&] { launch_pw_xs(a, pt, s, wg); }, &sp_x);
+          if (launch_pw_x3(f, pt, s, wg, 0) != 0) {       // 512 -> 256 on 64-pixel tiles: three planes exceed the LDS
+            if (has_xs) printf("%2dx%2d K=%3d N=%3d  %2d px, %d wg/CU, %5lld tiles:  flat   n/a        frag   n/a        xs %5.1f (%.1f)\n",
+                               sh.hw, sh.hw, sh.K, sh.N, 16 * pt, wg, tiles, t_x, sp_x);
+            continue;
+          }
+          if (hipDeviceSynchronize() != hipSuccess) { printf("x3 flat failed\n"); return 1; }
+          const float t_f = med_spread([&] { launch_pw_x3(f, pt, s, wg, 0); }, &sp_f);
+          const float t_g = med_spread([&] { launch_pw_x3(g, pt, s, wg, 1); }, &sp_g);
+          // the two orders: outputs and per-workgroup BatchNorm sums (replica = workgroup), bit for bit
+          f.stats = g.stats = wstats; f.stats_rep_stride = g.stats_rep_stride = 512; f.stats_nrep = g.stats_nrep = NWG;
+          f.out = out; g.out = out2;
+          CK(hipMemset(wstats, 0, (size_t)NWG * 512 * 8)); CK(hipMemset(out, 0, of.size() * 4));
+          launch_pw_x3(f, pt, s, wg, 0); CK(hipDeviceSynchronize());
+          CK(hipMemcpy(of.data(), out, of.size() * 4, hipMemcpyDeviceToHost)); CK(hipMemcpy(sf.data(), wstats, sf.size() * 8, hipMemcpyDeviceToHost));
+          CK(hipMemset(wstats, 0, (size_t)NWG * 512 * 8)); CK(hipMemset(out2, 0, og.size() * 4));
+          launch_pw_x3(g, pt, s, wg, 1); CK(hipDeviceSynchronize());
+          CK(hipMemcpy(og.data(), out2, og.size() * 4, hipMemcpyDeviceToHost)); CK(hipMemcpy(sg.data(), wstats, sg.size() * 8, hipMemcpyDeviceToHost));
+          double md = 0, sd = 0, nz = 0;
+          for (size_t i = 0; i < of.size(); ++i) { md = std::max(md, (double)std::fabs(of[i] - og[i])); nz += of[i] != 0.f; }
+          for (size_t i = 0; i < sf.size(); ++i) sd = std::max(sd, std::fabs(sf[i] - sg[i]));
+          printf("%2dx%2d K=%3d N=%3d  %2d px, %d wg/CU, %5lld tiles:  flat %5.1f (%.1f)  frag %5.1f (%.1f)  xs ", sh.hw, sh.hw, sh.K, sh.N,
+                 16 * pt, wg, tiles, t_f, sp_f, t_g, sp_g);
+          if (has_xs) printf("%5.1f (%.1f)", t_x, sp_x); else printf("  n/a      ");
+          printf("  max|frag - flat| out %.1e sums %.1e (%.0f%% of outputs nonzero)\n", md, sd, 100.0 * nz / of.size());
+          fflush(stdout);
+        }
+    }
+    if (argc > 1 && !strcmp(argv[1], "frag")) return 0;
+  }
   for (const Shape& sh : shapes) {
     const long long M = (long long)B * sh.hw * sh.hw;
     // deferred table: channel c of the input = BatchNorm channel c of a producer with the same pixel count; sums that
@@ -105,10 +180,10 @@ int main(int argc, char** argv) {
         for (int wg : {1, 2, 3}) {
           if (dt == 0 && wg != 2) continue;
           if (sh.K == 512 && pt == 4) continue;
-          if (launch_pw_x3(a, pt, s, wg) != 0) { printf(" x3 n/a"); continue; }
+          if (launch_pw_x3(a, pt, s, wg, 0) != 0) { printf(" x3 n/a"); continue; }   // (w3: flat order)
           hipError_t e = hipDeviceSynchronize();
           if (e != hipSuccess) { printf(" x3_%d %s\n", pt, hipGetErrorString(e)); return 1; }
-          printf(" x3_%d/%d %5.1f", pt, wg, time_it([&] { launch_pw_x3(a, pt, s, wg); }));
+          printf(" x3_%d/%d %5.1f", pt, wg, time_it([&] { launch_pw_x3(a, pt, s, wg, 0); }));
         }
     }
     // correctness: outputs bit for bit against pw_mfma_kernel (deferred table), statistics to fp64 rounding
@@ -144,7 +219,7 @@ int main(int argc, char** argv) {
       b.out = out; launch_pw_xs(b, 0, s); CK(hipDeviceSynchronize());
       CK(hipMemcpy(o32.data(), out, o32.size() * 4, hipMemcpyDeviceToHost));
       b.out = out2; CK(hipMemset(out2, 0, o3.size() * 4));
-      if (launch_pw_x3(b, 0, s) == 0) {
+      if (launch_pw_x3(b, 0, s, 0, 0) == 0) {
         CK(hipDeviceSynchronize());
         CK(hipMemcpy(o3.data(), out2, o3.size() * 4, hipMemcpyDeviceToHost));
         double e32 = 0, e3 = 0, d = 0, nrm = 0; 
