@@ -258,9 +258,17 @@ int jn_yolox_loss(const float* raw_dev, const float* targets_dev, int N, int nb,
  * as jn_detect writes them; rows at or beyond counts[n] are left alone.  stats_dev (int32 [N,2], may be NULL): column 0
  * = the anchors with score >= conf_threshold before the 2048 cap, column 1 = the NMS survivors before max_out; a caller
  * sees a cap was reached from stats[n][0] > 2048 or stats[n][1] > max_out.  Launches on `stream` and does not wait.
- * Inputs are finite with w, h >= 0.  JN_EINVAL: a null raw / boxes / counts, N < 1, A < 1, max_out < 1. */
+ * Inputs are finite with w, h >= 0.  JN_EINVAL: a null raw / boxes / counts, N < 1, A < 1, max_out < 1.
+ * jn_postprocess_all is the same stage without the first cap. */
 int jn_postprocess(const float* raw_dev, int N, int A, float conf_threshold, float nms_threshold, float clamp_max,
                    int max_out, float* boxes_dev, int32_t* counts_dev, int32_t* stats_dev, void* stream);
+/* jn_postprocess under the candidate policy "all": EVERY anchor with obj * cls >= conf_threshold enters the sort, so
+ * the result is the published postprocess (which has no candidate cap) cut to max_out rows; everything else, the
+ * arguments, the outputs, stats_dev and the launch contract, is as in jn_postprocess, and for A <= 2048 the two give the
+ * same bytes.  One workgroup per patch holds the candidates in LDS, hence A <= 8400 (640 px at strides 8 / 16 / 32).
+ * JN_EINVAL: as jn_postprocess, and A > 8400 (nothing is launched). */
+int jn_postprocess_all(const float* raw_dev, int N, int A, float conf_threshold, float nms_threshold, float clamp_max,
+                       int max_out, float* boxes_dev, int32_t* counts_dev, int32_t* stats_dev, void* stream);
 /* The metrics of one teacher-forced validation batch on given logits, context-free: SupervisedTrainer.compute_metrics
  * (src/supervised.py:162-197) on the labels eval_supervised forms (:449-458).  logits_dev [B,T,nA] f32, current_actions /
  * next_actions [B,T] int64, masks u8 [B,T] (1 = token, 0 = padding).  Labels: next_actions; with on_self_trajectory != 0
@@ -490,6 +498,13 @@ int jn_gpt_forward(jn_ctx* ctx, const float* patches_dev, const int64_t* actions
  * raw_dev optional [N, A, 6] decoded head output before postprocess. */
 int jn_detect(jn_ctx* ctx, const float* patches_dev, int N, float* boxes_dev,
               int32_t* counts_dev, float* raw_dev, void* stream);
+/* Candidate policy of the detector's threshold / sort / NMS stage wherever `ctx` runs it: jn_detect and the rollout's
+ * do_detection, the eval head of jn_detector_forward, jn_detector_eval_loss.  all = 0 (the default): the first 2048
+ * passing anchors in index order enter the sort (jn_postprocess).  all != 0: every passing anchor does
+ * (jn_postprocess_all), which is the published postprocess up to max_det_per_patch.  Sticky until set again.
+ * JN_ESTATE: the context has no detector.  JN_EINVAL: all != 0 and the detector has more than 8400 anchors (a patch
+ * size above 640). */
+int jn_set_det_candidates(jn_ctx* ctx, int all);
 
 /* One training step of the detector minus the optimiser: NeedleYOLOX.forward(patches, targets) loss branch
  * (src/models/yolox.py:58-73) + loss.backward() (src/reinforce.py:336-341).  PAFPN + head forward with

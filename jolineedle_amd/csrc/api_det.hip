@@ -33,6 +33,15 @@ namespace jnr {
 // (src/reinforce.py:326-341).
 int det_slot_base(const jn_ctx* ctx) { return ctx->enc_net == JN_NET_DETECTOR ? ctx->cfg.block_size + 1 : 1; }
 
+// threshold / sort / NMS of the N patches in det_raw under the context's candidate policy (jn_set_det_candidates)
+static void det_postprocess(jn_ctx* ctx, int N, float* boxes_dev, int32_t* counts_dev, hipStream_t s) {
+  const jn_config& c = ctx->cfg;
+  (ctx->det_all ? launch_postprocess_all : launch_postprocess)(ctx->det_raw, ctx->nets[JN_NET_DETECTOR].n_anchors, N,
+                                                               c.det_conf_threshold, c.det_nms_threshold,
+                                                               (float)(c.patch_size - 1), boxes_dev, counts_dev,
+                                                               c.max_det_per_patch, nullptr, s);
+}
+
 int detect_impl(jn_ctx* ctx, const StemSrc& ss, int N, float* boxes_dev, int32_t* counts_dev, float* raw_dev,
                 const int* skip_flag, int skip_when, hipStream_t s) {
   Net& net = ctx->nets[JN_NET_DETECTOR];
@@ -43,8 +52,7 @@ int detect_impl(jn_ctx* ctx, const StemSrc& ss, int N, float* boxes_dev, int32_t
   if (raw_dev)
     JN_HIP(hipMemcpyAsync(raw_dev, ctx->det_raw, (size_t)N * net.n_anchors * 6 * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (boxes_dev && counts_dev)
-    launch_postprocess(ctx->det_raw, net.n_anchors, N, ctx->cfg.det_conf_threshold, ctx->cfg.det_nms_threshold,
-                       (float)(ctx->cfg.patch_size - 1), boxes_dev, counts_dev, ctx->cfg.max_det_per_patch, nullptr, s);
+    det_postprocess(ctx, N, boxes_dev, counts_dev, s);
   JN_HIP(hipGetLastError());
   return JN_OK;
 }
@@ -146,8 +154,7 @@ static int detector_eval_head(jn_ctx* ctx, int pass, float* boxes_dev, int32_t* 
   rc = run_net(ctx, JN_NET_DETECTOR, N, none, 0, 0, nullptr, 0, s, true, net.n_backbone_ops);
   net.eval_tab_dirty = true;               // slot 0's FPN entries hold batch statistics now: rebuilt before the next eval pass
   if (rc) return rc;
-  launch_postprocess(ctx->det_raw, net.n_anchors, N, ctx->cfg.det_conf_threshold, ctx->cfg.det_nms_threshold,
-                     (float)(ctx->cfg.patch_size - 1), boxes_dev, counts_dev, ctx->cfg.max_det_per_patch, nullptr, s);
+  det_postprocess(ctx, N, boxes_dev, counts_dev, s);
   JN_HIP(hipGetLastError());
   return JN_OK;
 }
@@ -164,6 +171,17 @@ int jn_detect(jn_ctx* ctx, const float* patches_dev, int N, float* boxes_dev, in
   JN_CHECK(N >= 1 && N <= ctx->cfg.max_batch, JN_EINVAL, "N=%d exceeds max_batch=%d", N, ctx->cfg.max_batch);
   JN_HIP(hipSetDevice(ctx->cfg.device));
   return detect_impl(ctx, patch_src(patches_dev, ctx->cfg.patch_size), N, boxes_dev, counts_dev, raw_dev, nullptr, 0, (hipStream_t)stream);
+}
+
+int jn_set_det_candidates(jn_ctx* ctx, int all) {
+  JN_CHECK(ctx, JN_EINVAL, "jn_set_det_candidates: null ctx");
+  JN_CHECK(ctx->has_net[JN_NET_DETECTOR], JN_ESTATE, "context was created without a detector");
+  const int A = ctx->nets[JN_NET_DETECTOR].n_anchors;
+  JN_CHECK(!all || A <= POST_ALL_MAX_A, JN_EINVAL,
+           "jn_set_det_candidates: the detector has A=%d anchors at patch size %d, the kernel holds at most %d in LDS", A,
+           ctx->cfg.patch_size, POST_ALL_MAX_A);
+  ctx->det_all = all != 0;
+  return JN_OK;
 }
 
 int jn_detector_step(jn_ctx* ctx, const float* patches_dev, int N, const float* targets_dev, int nb, float loss_scale,
@@ -265,8 +283,7 @@ int jn_detector_eval_loss(jn_ctx* ctx, const float* patches_dev, int N, const fl
     // head, eval, on the same maps: run_net rebuilds the whole table from the running statistics first (the backbone's
     // entries come out as they were, the head's from the statistics the pass above has just moved)
     if ((rc = run_net(ctx, JN_NET_DETECTOR, N, none, 0, 0, nullptr, 0, s, true, net.n_backbone_ops))) return rc;
-    launch_postprocess(ctx->det_raw, A, N, ctx->cfg.det_conf_threshold, ctx->cfg.det_nms_threshold, (float)(P - 1), boxes_dev,
-                       counts_dev, ctx->cfg.max_det_per_patch, nullptr, s);
+    det_postprocess(ctx, N, boxes_dev, counts_dev, s);
   }
   JN_HIP(hipGetLastError());
   return JN_OK;

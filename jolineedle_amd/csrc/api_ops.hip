@@ -111,6 +111,19 @@ int jn_postprocess(const float* raw_dev, int N, int A, float conf_threshold, flo
   return JN_OK;
 }
 
+int jn_postprocess_all(const float* raw_dev, int N, int A, float conf_threshold, float nms_threshold, float clamp_max,
+                       int max_out, float* boxes_dev, int32_t* counts_dev, int32_t* stats_dev, void* stream) {
+  JN_CHECK(raw_dev && boxes_dev && counts_dev, JN_EINVAL, "jn_postprocess_all: null argument");
+  JN_CHECK(N >= 1 && A >= 1, JN_EINVAL, "jn_postprocess_all: N=%d A=%d", N, A);
+  JN_CHECK(A <= POST_ALL_MAX_A, JN_EINVAL, "jn_postprocess_all: A=%d, the kernel holds at most %d candidates in LDS", A,
+           POST_ALL_MAX_A);
+  JN_CHECK(max_out >= 1, JN_EINVAL, "jn_postprocess_all: max_out=%d", max_out);
+  launch_postprocess_all(raw_dev, A, N, conf_threshold, nms_threshold, clamp_max, boxes_dev, counts_dev, max_out, stats_dev,
+                         (hipStream_t)stream);
+  JN_HIP(hipGetLastError());
+  return JN_OK;
+}
+
 int jn_supervised_metrics(const float* logits_dev, const int64_t* current_actions_dev, const int64_t* next_actions_dev,
                           const uint8_t* masks_dev, int B, int T, int nA, float stop_weight, int on_self_trajectory,
                           float* token_loss_out_dev, uint8_t* predicted_out_dev, float* metrics_dev, void* stream) {

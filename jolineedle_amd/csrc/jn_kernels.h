@@ -180,6 +180,11 @@ int launch_det_scatter(const float* boxes, const int* counts, float* out_boxes, 
 // stats: nullable int [N][2] = (anchors with score >= conf before the 2048-candidate cap, NMS survivors before max_out)
 int launch_postprocess(const float* raw, int A, int N, float conf, float nms_thr, float clamp_max, float* boxes,
                        int* counts, int max_out, int* stats, hipStream_t s);
+// The same stage with EVERY passing anchor in the sort (no 2048-candidate cap): A <= POST_ALL_MAX_A, else nothing is
+// launched and the return value is non-zero.  A <= 2048 goes to launch_postprocess (the two coincide there).
+constexpr int POST_ALL_MAX_A = 8400;                    // 640 px at strides 8 / 16 / 32
+int launch_postprocess_all(const float* raw, int A, int N, float conf, float nms_thr, float clamp_max, float* boxes,
+                           int* counts, int max_out, int* stats, hipStream_t s);
 
 // ---- detector training (kernels_detloss.hip) ------------------------------------------------------------
 struct DetGeom { int A; int a0[3]; int H[3]; int W[3]; int stride[3]; };

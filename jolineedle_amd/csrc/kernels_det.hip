@@ -1488,6 +1488,160 @@ int launch_postprocess(const float* raw, int A, int N, float conf, float nms_thr
   return 0;
 }
 
+// ------------------------------------------------------------------------------------
+// The same stage under the candidate policy "all": every anchor with obj * cls >= conf enters the sort, A <=
+// POST_ALL_MAX_A.  One workgroup of 1024 threads per patch, 136,508 B of static LDS (a gfx950 workgroup may declare all
+// 160 KiB).
+// Sort: key[cnt] = 64-bit (descending-order image of the score, anchor index), sorted ASCENDING, which is (score
+// descending, index ascending).  Only the cnt real keys are stored: the bitonic network runs over np2 = the power of two
+// at or above cnt with every comparator pointing the same way (the first step of a merge pairs i with i ^ (2j - 1), the
+// later ones i with i ^ j, the smaller key to the lower index), so a pad that ranks last never leaves the indices >= cnt
+// and a comparator that touches one is skipped.  No pad is stored, so none can outrank a negative score.
+// Greedy loop: thread t owns the sorted candidates t, t + 1024, ...: it takes their anchor indices out of the keys into
+// registers, then the key buffer becomes box[] (xyxy of every sorted candidate, for the pivot of a round) and the owner
+// keeps its boxes in registers as well, so a round is one LDS broadcast read, the owned IoUs (postprocess_kernel's
+// expressions: the same fp32 values) and one barrier.  dead[] = one bit per sorted candidate.  Nothing is written
+// inside the loop: the survivors are the live candidates below the loop's end, ranked afterwards by a prefix count over
+// dead[] and written by their owners.  Without stats the loop ends once max_out boxes are kept.
+// ------------------------------------------------------------------------------------
+constexpr int POST_ALL_NT = 1024;
+constexpr int POST_ALL_PER = (POST_ALL_MAX_A + POST_ALL_NT - 1) / POST_ALL_NT;    // sorted candidates a thread owns
+constexpr int POST_ALL_WORDS = (POST_ALL_MAX_A + 31) / 32;
+
+__global__ __launch_bounds__(POST_ALL_NT) void postprocess_all_kernel(const float* __restrict__ raw, int A, float conf,
+                                                                      float nms_thr, float clamp_max,
+                                                                      float* __restrict__ boxes, int* __restrict__ counts,
+                                                                      int max_out, int* __restrict__ stats) {
+  __shared__ float4 box[POST_ALL_MAX_A];            // the sort's keys use its first half
+  __shared__ unsigned int dead[POST_ALL_WORDS];
+  __shared__ int wbase[POST_ALL_WORDS];             // survivors in the words before this one
+  __shared__ int s_n;
+  static_assert(sizeof(box) >= POST_ALL_MAX_A * sizeof(unsigned long long), "the keys must fit into box[]");
+  unsigned long long* key = reinterpret_cast<unsigned long long*>(box);
+  if (A > POST_ALL_MAX_A) return;                   // the launcher refuses it; never index past the arrays
+  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const float* r = raw + (long long)n * A * 6;
+  if (tid == 0) s_n = 0;
+  for (int i = tid; i < POST_ALL_WORDS; i += POST_ALL_NT) dead[i] = 0u;
+  __syncthreads();
+  // compaction in any order (the sort's order is total): one LDS atomic per wave and chunk
+  for (int base = 0; base < A; base += POST_ALL_NT) {
+    const int a = base + tid;
+    float score = -1.0f;
+    if (a < A) score = r[a * 6 + 4] * r[a * 6 + 5];
+    const bool ok = a < A && score >= conf;
+    const unsigned long long m = __ballot(ok);
+    int off = 0;
+    if (lane == 0 && m) off = atomicAdd(&s_n, __popcll(m));
+    off = __shfl(off, 0) + __popcll(m & ((1ull << lane) - 1ull));
+    if (ok) {
+      const unsigned int u = __float_as_uint(score + 0.0f);        // -0 -> +0: the two compare equal
+      const unsigned int asc = u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+      key[off] = ((unsigned long long)(~asc) << 32) | (unsigned int)a;
+    }
+  }
+  __syncthreads();
+  const int cnt = s_n;                              // <= A <= POST_ALL_MAX_A
+  if (cnt == 0) {                                   // uniform; the usual patch at the config's threshold
+    if (tid == 0) {
+      counts[n] = 0;
+      if (stats) { stats[n * 2] = 0; stats[n * 2 + 1] = 0; }
+    }
+    return;
+  }
+  int np2 = 1;
+  while (np2 < cnt) np2 <<= 1;
+  for (int k = 2; k <= np2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      const int flip = (j == (k >> 1)) ? k - 1 : j;
+      for (int c = tid; c < (np2 >> 1); c += POST_ALL_NT) {
+        const int i = ((c & ~(j - 1)) << 1) | (c & (j - 1));       // bit j of i clear
+        const int l = i ^ flip;                                    // > i
+        if (l < cnt) {
+          const unsigned long long ki = key[i], kl = key[l];
+          if (kl < ki) { key[i] = kl; key[l] = ki; }
+        }
+      }
+      __syncthreads();
+    }
+  int id[POST_ALL_PER];
+  float x1[POST_ALL_PER], y1[POST_ALL_PER], x2[POST_ALL_PER], y2[POST_ALL_PER];
+#pragma unroll
+  for (int q = 0; q < POST_ALL_PER; ++q) {
+    const int j = q * POST_ALL_NT + tid;
+    id[q] = j < cnt ? (int)(unsigned int)key[j] : 0;
+  }
+  __syncthreads();                                  // every key is in a register: the buffer is box[] from here on
+#pragma unroll
+  for (int q = 0; q < POST_ALL_PER; ++q) {
+    const int j = q * POST_ALL_NT + tid;
+    x1[q] = y1[q] = x2[q] = y2[q] = 0.0f;
+    if (j < cnt) {
+      const float* bj = r + id[q] * 6;
+      x1[q] = bj[0] - bj[2] * 0.5f; y1[q] = bj[1] - bj[3] * 0.5f; x2[q] = bj[0] + bj[2] * 0.5f; y2[q] = bj[1] + bj[3] * 0.5f;
+      box[j] = make_float4(x1[q], y1[q], x2[q], y2[q]);
+    }
+  }
+  __syncthreads();
+  unsigned int mine = 0u;                           // bit q: my candidate q is suppressed (the copy of its dead[] bit)
+  int kept = 0, end = cnt;                          // uniform: every thread takes the same path
+  for (int i = 0; i < cnt; ++i) {
+    if ((dead[i >> 5] >> (i & 31)) & 1u) continue;  // uniform: dead[] is shared and synced
+    if (!stats && kept >= max_out) { end = i; break; }
+    ++kept;
+    const float4 a = box[i];
+    const float ax1 = a.x, ay1 = a.y, ax2 = a.z, ay2 = a.w;
+    const float aa = (ax2 - ax1) * (ay2 - ay1);
+#pragma unroll
+    for (int q = 0; q < POST_ALL_PER; ++q) {
+      const int j = q * POST_ALL_NT + tid;
+      if (j <= i || j >= cnt || ((mine >> q) & 1u)) continue;
+      const float bx1 = x1[q], by1 = y1[q], bx2 = x2[q], by2 = y2[q];
+      const float iw = fmaxf(fminf(ax2, bx2) - fmaxf(ax1, bx1), 0.0f), ih = fmaxf(fminf(ay2, by2) - fmaxf(ay1, by1), 0.0f);
+      const float inter = iw * ih;
+      const float iou = inter / (aa + (bx2 - bx1) * (by2 - by1) - inter);
+      if (iou > nms_thr) { mine |= 1u << q; atomicOr(&dead[j >> 5], 1u << (j & 31)); }
+    }
+    __syncthreads();
+  }
+  // the survivors are the live candidates below `end` (all of them pivots of a round), in sorted order
+  for (int w = tid; w < (end + 31) / 32; w += POST_ALL_NT) {
+    int before = 0;
+    for (int v = 0; v < w; ++v) {
+      const int left = end - 32 * v;                // candidates of word v below `end`
+      const unsigned int valid = left >= 32 ? 0xFFFFFFFFu : left <= 0 ? 0u : (1u << left) - 1u;
+      before += __popc(~dead[v] & valid);
+    }
+    wbase[w] = before;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < POST_ALL_PER; ++q) {
+    const int j = q * POST_ALL_NT + tid;
+    if (j >= end || ((mine >> q) & 1u)) continue;
+    const int rank = wbase[j >> 5] + __popc(~dead[j >> 5] & ((1u << (j & 31)) - 1u));
+    if (rank >= max_out) continue;
+    const float* bj = r + id[q] * 6;
+    float* o = boxes + ((long long)n * max_out + rank) * 7;
+    o[0] = fminf(fmaxf(x1[q], 0.0f), clamp_max); o[1] = fminf(fmaxf(y1[q], 0.0f), clamp_max);
+    o[2] = fminf(fmaxf(x2[q], 0.0f), clamp_max); o[3] = fminf(fmaxf(y2[q], 0.0f), clamp_max);
+    o[4] = bj[4]; o[5] = bj[5]; o[6] = 0.0f;
+  }
+  if (tid == 0) {
+    counts[n] = min(kept, max_out);
+    if (stats) { stats[n * 2] = cnt; stats[n * 2 + 1] = kept; }
+  }
+}
+
+int launch_postprocess_all(const float* raw, int A, int N, float conf, float nms_thr, float clamp_max, float* boxes,
+                           int* counts, int max_out, int* stats, hipStream_t s) {
+  if (A > POST_ALL_MAX_A) return 1;
+  if (A <= DET_CAP) return launch_postprocess(raw, A, N, conf, nms_thr, clamp_max, boxes, counts, max_out, stats, s);
+  hipLaunchKernelGGL(postprocess_all_kernel, dim3(N), dim3(POST_ALL_NT), 0, s, raw, A, conf, nms_thr, clamp_max, boxes,
+                     counts, max_out, stats);
+  return 0;
+}
+
 // boxes [B][K][7] / counts [B] of one glimpse step -> column `col` of [B][cols][K][7] / [B][cols]
 __global__ void det_scatter_kernel(const float* __restrict__ boxes, const int* __restrict__ counts,
                                    float* __restrict__ out_boxes, int* __restrict__ out_counts, int B, int cols, int col,

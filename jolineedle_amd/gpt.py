@@ -16,7 +16,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import check, ptr
 from .engine import Engine, make_jn_config, GPT_ZOO
-from .yolox import NeedleYOLOX
+from .yolox import NeedleYOLOX, DET_CANDIDATES
 
 
 class _Slot(nn.Module):
@@ -122,6 +122,9 @@ class GPT(nn.Module):
         # --dropout (main.py:123-128; embd / attn / resid of the decision transformer): train-mode passes only
         self.dropout = float(getattr(config, "dropout", 0.0) or 0.0)
         self.set_dropout_seed(int(getattr(config, "seed", 0)))
+        self.det_candidates = "first2048"
+        if getattr(config, "det_candidates", "first2048") != "first2048":
+            self.set_det_candidates(config.det_candidates)
         self._build_parameters()
         # --freeze-image-processor (gpt.py:264-268): yolox.backbone.* out of the optimiser
         self.freeze_image_processor = bool(getattr(config, "freeze_image_processor", False))
@@ -177,6 +180,16 @@ class GPT(nn.Module):
     def set_dropout_seed(self, seed: int):
         """(Re)start the dropout mask stream: the n-th train-mode forward after this call uses `seed + n`."""
         check(self._engine.lib.jn_set_dropout(self._engine.handle, self.dropout, int(seed) & 0xFFFFFFFFFFFFFFFF), "jn_set_dropout")
+
+    def set_det_candidates(self, policy: str):
+        """Candidate policy of the detector's threshold / sort / NMS stage from now on (``jn_set_det_candidates``; config
+        field ``det_candidates``): "first2048" = the first 2048 passing anchors in index order enter the sort, "all" =
+        every passing anchor does, which is the published postprocess up to ``max_det_per_patch`` and what an evaluation
+        at a low ``detector_conf_threshold`` wants.  Needs a detector, and for "all" a patch size of at most 640."""
+        if policy not in DET_CANDIDATES:
+            raise ValueError(f"det_candidates={policy!r}: one of {DET_CANDIDATES}")
+        check(self._engine.lib.jn_set_det_candidates(self._engine.handle, int(policy == "all")), "jn_set_det_candidates")
+        self.det_candidates = policy
 
     @property
     def yolox(self):

@@ -51,11 +51,18 @@ def yolox_loss(raw: torch.Tensor, targets: torch.Tensor, patch_size: int, stride
     return d_raw, metrics, scale
 
 
-def postprocess(raw: torch.Tensor, conf: float, nms_thr: float, patch_size: int, max_out: int):
+DET_CANDIDATES = ("first2048", "all")      # candidate policies of the stage: jn_postprocess / jn_postprocess_all
+
+
+def postprocess(raw: torch.Tensor, conf: float, nms_thr: float, patch_size: int, max_out: int, candidates: str = "first2048"):
     """The detector's threshold / sort / NMS / clamp stage on given decoded predictions (``jn_postprocess``, no engine):
     raw [N, A, 6] = (cx, cy, w, h, obj, cls) on the device, finite, w and h >= 0.  Returns (boxes [N, max_out, 7] zero
     beyond the count, counts int32 [N], stats int32 [N, 2] = anchors with obj * cls >= conf before the 2048-candidate cap,
-    NMS survivors before ``max_out``): ``stats[:, 0] > 2048`` or ``stats[:, 1] > max_out`` says a cap cut the patch."""
+    NMS survivors before ``max_out``): ``stats[:, 0] > 2048`` or ``stats[:, 1] > max_out`` says a cap cut the patch.
+    ``candidates="all"`` (``jn_postprocess_all``, A <= 8400) has no candidate cap: every passing anchor reaches the NMS."""
+    if candidates not in DET_CANDIDATES:
+        raise ValueError(f"candidates={candidates!r}: one of {DET_CANDIDATES}")
+    entry = "jn_postprocess_all" if candidates == "all" else "jn_postprocess"
     assert raw.is_cuda and raw.dim() == 3 and raw.shape[2] == 6
     dev = raw.device
     raw = raw.to(torch.float32).contiguous()
@@ -63,8 +70,8 @@ def postprocess(raw: torch.Tensor, conf: float, nms_thr: float, patch_size: int,
     boxes = torch.zeros((N, max(int(max_out), 0), 7), device=dev)
     counts = torch.zeros((N,), device=dev, dtype=torch.int32)
     stats = torch.zeros((N, 2), device=dev, dtype=torch.int32)
-    check(_lib.load_library().jn_postprocess(ptr(raw), N, A, float(conf), float(nms_thr), float(patch_size - 1), int(max_out),
-                                             ptr(boxes), ptr(counts), ptr(stats), _lib.current_stream(dev)), "jn_postprocess")
+    check(getattr(_lib.load_library(), entry)(ptr(raw), N, A, float(conf), float(nms_thr), float(patch_size - 1), int(max_out),
+                                              ptr(boxes), ptr(counts), ptr(stats), _lib.current_stream(dev)), entry)
     return boxes, counts, stats
 
 
