@@ -216,6 +216,33 @@ int jn_env_init_views(jn_ctx* ctx, const jn_image_view* views_host, const int64_
 int jn_env_init_ragged(jn_ctx* ctx, const jn_image_view* views_host, const int32_t* extents_host,
                        const int64_t* bboxes_dev, int B, int Hc, int Wc, int nb, int max_ep_len, int stop_enabled,
                        void* stream);
+/* NeedleGeneralEnv.get_detection_batch (src/env/general_env.py:506-546, over parse_bboxes :381-504) without its patches,
+ * context-free: which cells of the patch grid the detector trains on, and every such patch's targets.  bboxes [B,nb,4]
+ * int64 xyxy in image pixels, zero rows = padding; the grid is Gh x Gw cells of P px, or per image the top-left
+ * gh x gw of it with extents_dev (int32 [B,2] = (gh, gw); cells outside an extent do not exist).
+ *  - Cell (py, px) holds a piece of box k iff y1 // P <= py <= y2 // P and x1 // P <= px <= x2 // P (floor division,
+ *    for negative coordinates too; a box with y2 // P < y1 // P touches nothing); pieces in cells outside the grid or
+ *    the extent are dropped.  The piece is (max(x1, px*P) - px*P, max(y1, py*P) - py*P, min(x2, px*P + P - 1) - px*P,
+ *    min(y2, py*P + P - 1) - py*P).  An all-zero row thus marks cell (0, 0) with a zero box: the reference's padding
+ *    quirk (:492-502), kept.  A cell is positive when any box touches it, else empty.
+ *  - Per image, in index order: its positive cells in row-major (y, x) order, then k = min(sample_neg, n_empty)
+ *    negatives by a partial Fisher-Yates shuffle of the row-major list E of its empty cells: for j = 0..k-1,
+ *    r = Philox4x32-10(key = seed, counter = (image, j, 0x4e454753, 0)).x, swap E[j] with E[j + r mod (n_empty - j)],
+ *    emit E[j].  The draws depend on (seed, image index) only (the reference draws with torch.randperm, which no
+ *    device path reproduces).
+ *  - Row offsets[i] is the first row of image i, offsets[B] = n the number of rows (int32 [B+1]); n_pos int32 [B] the
+ *    positive cells per image.  cells int64 [capacity,3] = (image, y, x); targets int64 [capacity,nb,5] = (0, x1, y1,
+ *    x2, y2) of box k's piece in the cell, zeros where box k does not touch it (F.pad(boxes[i, y, x], (1, 0)), :544).
+ *    Rows >= capacity are not written (offsets still count them); rows >= n are left alone.  capacity = B * Gh * Gw
+ *    always suffices.
+ * Three launches on `stream` (count, scan over B, select), no atomics: equal inputs give equal bytes.  One workgroup
+ * per image keeps the image's cell lists in LDS, hence Gh * Gw <= 4096.  Does not wait for the device, except with
+ * extents_dev: they are read back and checked first (one stream synchronisation).
+ * JN_EINVAL, before any launch: nb < 1, P < 1, sample_neg < 0, Gh or Gw < 1, Gh * Gw > 4096, B < 0, capacity < 0, an
+ * extent outside 1..Gh x 1..Gw, a null pointer (cells / targets may be NULL with capacity 0). */
+int jn_detection_cells(const int64_t* bboxes_dev, const int32_t* extents_dev, int B, int nb, int Gh, int Gw, int P,
+                       int sample_neg, uint64_t seed, int capacity, int64_t* cells_dev, int64_t* targets_dev,
+                       int32_t* offsets_dev, int32_t* n_pos_dev, void* stream);
 /* Trainer.patch_bboxes2full_image (src/trainer.py:250-280) for a whole batch, context-free: the detections of a
  * rollout (jn_rollout_out: det_boxes [B,T+1,K,7], det_counts [B,T+1], positions [B,T+1,2] (y,x), masks u8 [B,T+1])
  * become one list per image in full-image pixels.  Image b walks t = 0..S (S <= T steps were executed), skips the

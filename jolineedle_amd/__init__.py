@@ -22,7 +22,8 @@ from .infer import infer_images, plan_chunks, pad_to_patch_multiple, load_bboxes
 from .trajectory import NeedleSimpleEnv, teacher_action_sets, teacher_action_sets_device  # noqa: F401
 from .views import ImageViews  # noqa: F401
 from .detection import (patch_bboxes2full_image, rollout_boxes_to_image, merge_boxes, merge_boxes_batched,  # noqa: F401
-                        compute_detection_metrics, detection_targets, rollout_boxes_packed, pack_boxes, unpack_boxes,
+                        compute_detection_metrics, detection_targets, detection_cells, detection_cells_device,
+                        rollout_boxes_packed, pack_boxes, unpack_boxes,
                         merge_boxes_device, merge_boxes_batched_device, match_detections_device, average_precision_device,
                         map_50_device, compute_detection_metrics_device, pool_walk_detections,
                         pool_walk_detections_device, cell_targets, average_precision_segments_device, map_50_segments,

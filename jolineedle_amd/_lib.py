@@ -112,6 +112,7 @@ SIGNATURES = {
     "jn_average_precision_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                                 C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "jn_pool_walk_detections": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 9 + [C.c_void_p] * 5),
+    "jn_detection_cells": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_uint64, C.c_int] + [C.c_void_p] * 5),
     "jn_gather_patches_views": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                           C.c_int, C.c_int, C.c_void_p]),
     "jn_backbone_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

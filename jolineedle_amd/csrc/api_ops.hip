@@ -215,6 +215,33 @@ int jn_pool_walk_detections(const float* det_boxes_dev, const int32_t* det_count
   return JN_OK;
 }
 
+// (the extents live on the device and an extent beyond the grid would index past the kernel's LDS lists, so they are
+// read back and checked here: one small copy and a stream sync, in ragged mode only)
+int jn_detection_cells(const int64_t* bboxes_dev, const int32_t* extents_dev, int B, int nb, int Gh, int Gw, int P,
+                       int sample_neg, uint64_t seed, int capacity, int64_t* cells_dev, int64_t* targets_dev,
+                       int32_t* offsets_dev, int32_t* n_pos_dev, void* stream) {
+  JN_CHECK(offsets_dev && ((bboxes_dev && n_pos_dev) || B == 0) && ((cells_dev && targets_dev) || capacity == 0), JN_EINVAL,
+           "jn_detection_cells: null argument");
+  JN_CHECK(B >= 0 && capacity >= 0, JN_EINVAL, "jn_detection_cells: B=%d capacity=%d", B, capacity);
+  JN_CHECK(nb >= 1 && P >= 1 && sample_neg >= 0, JN_EINVAL, "jn_detection_cells: nb=%d P=%d sample_neg=%d", nb, P, sample_neg);
+  JN_CHECK(Gh >= 1 && Gw >= 1 && (long long)Gh * Gw <= JN_DETCELLS_MAX_CELLS, JN_EINVAL,
+           "jn_detection_cells: a grid of %d x %d cells, the kernel holds at most %d per image in LDS", Gh, Gw,
+           JN_DETCELLS_MAX_CELLS);
+  JN_CHECK((long long)B * Gh * Gw <= INT32_MAX, JN_EINVAL, "jn_detection_cells: B * Gh * Gw beyond the int32 offsets");
+  if (extents_dev && B > 0) {
+    std::vector<int32_t> ext(2 * (size_t)B);
+    JN_HIP(hipMemcpyAsync(ext.data(), extents_dev, ext.size() * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    JN_HIP(hipStreamSynchronize((hipStream_t)stream));
+    for (int b = 0; b < B; ++b)
+      JN_CHECK(ext[2 * b] >= 1 && ext[2 * b] <= Gh && ext[2 * b + 1] >= 1 && ext[2 * b + 1] <= Gw, JN_EINVAL,
+               "jn_detection_cells: extent %d x %d of image %d outside 1..%d x 1..%d", ext[2 * b], ext[2 * b + 1], b, Gh, Gw);
+  }
+  launch_detection_cells(bboxes_dev, extents_dev, B, nb, Gh, Gw, P, sample_neg, seed, capacity, cells_dev, targets_dev,
+                         offsets_dev, n_pos_dev, (hipStream_t)stream);
+  JN_HIP(hipGetLastError());
+  return JN_OK;
+}
+
 int jn_teacher_actions(const int64_t* positions_dev, const uint8_t* visited_dev, const uint8_t* targets_dev, int B, int Gh,
                        int Gw, uint8_t* sets_dev, void* stream) {
   JN_CHECK(positions_dev && visited_dev && targets_dev && sets_dev, JN_EINVAL, "jn_teacher_actions: null argument");

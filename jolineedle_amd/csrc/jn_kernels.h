@@ -287,6 +287,13 @@ int launch_gather(const uint8_t* images, const int64_t* positions, float* out, l
                   const int64_t* image_index = nullptr);
 int launch_bbox_masks(const int64_t* bboxes, uint8_t* masks, int32_t* n_tiles, int B, int nb, int H, int W, int P,
                       hipStream_t s, const int32_t* extent = nullptr);
+// the detector's training batch (jnroll.h: jn_detection_cells): count, scan over B, select.  The select kernel keeps two
+// uint16 lists of the image's cells in LDS, so Gh * Gw <= JN_DETCELLS_MAX_CELLS (16 KB); the caller checks it, and that
+// every extent lies in 1..Gh x 1..Gw.
+constexpr int JN_DETCELLS_MAX_CELLS = 4096;
+int launch_detection_cells(const int64_t* bboxes, const int32_t* extents, int B, int nb, int Gh, int Gw, int P, int sample_neg,
+                           uint64_t seed, int capacity, int64_t* cells, int64_t* targets, int32_t* offsets, int32_t* n_pos,
+                           hipStream_t s);
 // kernels_view.hip: the indexed gather through image views (jnroll.h: jn_image_view); all views of one element type.
 // out is float, or uint8 when out_u8 (byte sources only); image_index = null: patch n reads view n
 int launch_view_gather(const jn_image_view* views, int src_u8, const int64_t* image_index, const int64_t* positions,

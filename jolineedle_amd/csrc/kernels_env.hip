@@ -109,6 +109,158 @@ int launch_bbox_masks(const int64_t* bboxes, uint8_t* masks, int32_t* n_tiles, i
   return 0;
 }
 
+// The detector's training batch (NeedleGeneralEnv.get_detection_batch, src/env/general_env.py:381-546; the rule is
+// stated at jnroll.h: jn_detection_cells): which cells of every image hold a piece of a box, `sample_neg` empty cells
+// per image, and every row's patch-local targets.  Integer-exact.  Three launches: count (a workgroup per image), an
+// exclusive scan over the images (one workgroup), select (a workgroup per image).  A row's place follows from the
+// scans alone, so two calls write the same bytes.
+constexpr int kDetThreads = 256;
+
+__device__ inline long long floor_div(long long a, long long p) { return a / p - ((a % p != 0) && (a < 0)); }
+
+// does cell (py, px) hold a piece of any of the image's nb boxes?  (a box with y2 // P < y1 // P touches nothing)
+__device__ inline bool det_cell_positive(const long long* __restrict__ bb, int nb, int P, int py, int px) {
+  for (int k = 0; k < nb; ++k) {
+    const long long* q = bb + 4 * k;
+    if (floor_div(q[1], P) <= py && py <= floor_div(q[3], P) && floor_div(q[0], P) <= px && px <= floor_div(q[2], P)) return true;
+  }
+  return false;
+}
+
+// Inclusive sum of v over the workgroup's kDetThreads threads (Hillis-Steele in LDS, double-buffered).  Returns the
+// thread's own sum, `total` = the workgroup's.  Ends on a barrier; the caller needs one more before the next call
+// rewrites the buffers that other threads may still read.
+__device__ inline int32_t det_block_scan(int32_t (*scan)[kDetThreads], int tid, int32_t v, int32_t& total) {
+  int cur = 0;
+  scan[0][tid] = v;
+  __syncthreads();
+  for (int d = 1; d < kDetThreads; d <<= 1) {
+    scan[cur ^ 1][tid] = scan[cur][tid] + (tid >= d ? scan[cur][tid - d] : 0);
+    cur ^= 1;
+    __syncthreads();
+  }
+  total = scan[cur][kDetThreads - 1];
+  return scan[cur][tid];
+}
+
+// offsets[b + 1] = the rows of image b (its positive cells + min(sample_neg, empty cells)), n_pos[b] = the positive ones
+__global__ __launch_bounds__(kDetThreads) void det_cells_count_kernel(const long long* __restrict__ bboxes,
+                                                                      const int32_t* __restrict__ extents, int nb, int Gh,
+                                                                      int Gw, int P, int sample_neg,
+                                                                      int32_t* __restrict__ offsets,
+                                                                      int32_t* __restrict__ n_pos) {
+  const int b = blockIdx.x;
+  const int gh = extents ? extents[2 * b] : Gh, gw = extents ? extents[2 * b + 1] : Gw;
+  const int cells = gh * gw;
+  const long long* bb = bboxes + (long long)b * nb * 4;
+  int pos = 0;
+  for (int c0 = 0; c0 < cells; c0 += kDetThreads) {        // (uniform trip count: every thread reaches the barrier)
+    const int c = c0 + threadIdx.x;
+    pos += __syncthreads_count(c < cells && det_cell_positive(bb, nb, P, c / gw, c % gw));
+  }
+  if (threadIdx.x == 0) {
+    n_pos[b] = pos;
+    offsets[b + 1] = pos + min(sample_neg, cells - pos);
+  }
+}
+
+// in place: offsets[b + 1] (the rows of image b) -> the inclusive sum, offsets[0] = 0.  One workgroup.
+__global__ __launch_bounds__(kDetThreads) void det_cells_scan_kernel(int32_t* __restrict__ offsets, int B) {
+  __shared__ int32_t scan[2][kDetThreads];
+  __shared__ int32_t carry;
+  const int tid = threadIdx.x;
+  if (tid == 0) { carry = 0; offsets[0] = 0; }
+  __syncthreads();
+  for (int b0 = 0; b0 < B; b0 += kDetThreads) {
+    const int b = b0 + tid;
+    int32_t total;
+    const int32_t sum = det_block_scan(scan, tid, b < B ? offsets[b + 1] : 0, total);
+    const int32_t base = carry;
+    if (b < B) offsets[b + 1] = base + sum;
+    __syncthreads();
+    if (tid == 0) carry = base + total;
+    __syncthreads();
+  }
+}
+
+// Dynamic LDS: uint16 [2][cells] = the image's positive cells and its empty cells, each in row-major order.
+__global__ __launch_bounds__(kDetThreads) void det_cells_select_kernel(
+    const long long* __restrict__ bboxes, const int32_t* __restrict__ extents, int nb, int Gh, int Gw, int P, int sample_neg,
+    uint64_t seed, int capacity, const int32_t* __restrict__ offsets, long long* __restrict__ out_cells,
+    long long* __restrict__ out_targets) {
+  extern __shared__ uint16_t det_lists[];
+  __shared__ int32_t scan[2][kDetThreads];
+  __shared__ int32_t n_positive;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int gh = extents ? extents[2 * b] : Gh, gw = extents ? extents[2 * b + 1] : Gw;
+  const int cells = gh * gw;
+  uint16_t* positive = det_lists;
+  uint16_t* empty = det_lists + cells;
+  const long long* bb = bboxes + (long long)b * nb * 4;
+  int base = 0;                                              // positive cells before this pass (uniform)
+  for (int c0 = 0; c0 < cells; c0 += kDetThreads) {
+    const int c = c0 + tid;
+    const int f = (c < cells && det_cell_positive(bb, nb, P, c / gw, c % gw)) ? 1 : 0;
+    int32_t total;
+    const int before = base + det_block_scan(scan, tid, f, total) - f;   // positive cells in front of c; the others there are empty
+    if (c < cells) {
+      if (f) positive[before] = (uint16_t)c;
+      else empty[c - before] = (uint16_t)c;
+    }
+    base += total;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    // partial Fisher-Yates over the empty list: draw j swaps E[j] with E[j + r mod (n_empty - j)]
+    const int n_empty = cells - base;
+    const int k = min(sample_neg, n_empty);
+    for (int j = 0; j < k; ++j) {
+      const uint32_t r = philox4x32(seed, (uint32_t)b, (uint32_t)j, 0x4e454753u, 0u).x;
+      const int o = j + (int)(r % (uint32_t)(n_empty - j));
+      const uint16_t t = empty[j]; empty[j] = empty[o]; empty[o] = t;
+    }
+    n_positive = base;
+  }
+  __syncthreads();
+  const int npos = n_positive;
+  const int first = offsets[b];
+  const int rows = min(offsets[b + 1], capacity) - first;    // this image's rows below the capacity (may be <= 0)
+  for (int i = tid; i < rows * nb; i += kDetThreads) {
+    const int r = i / nb, k = i % nb;
+    const int c = r < npos ? positive[r] : empty[r - npos];
+    const int py = c / gw, px = c % gw;
+    const long long row = (long long)first + r;
+    if (k == 0) {
+      long long* oc = out_cells + row * 3;
+      oc[0] = b; oc[1] = py; oc[2] = px;
+    }
+    const long long* q = bb + 4 * k;
+    const long long x1 = q[0], y1 = q[1], x2 = q[2], y2 = q[3];
+    const long long ox = (long long)px * P, oy = (long long)py * P;
+    const bool touch = floor_div(y1, P) <= py && py <= floor_div(y2, P) && floor_div(x1, P) <= px && px <= floor_div(x2, P);
+    long long* ot = out_targets + (row * nb + k) * 5;
+    ot[0] = 0;
+    ot[1] = touch ? (x1 > ox ? x1 : ox) - ox : 0;
+    ot[2] = touch ? (y1 > oy ? y1 : oy) - oy : 0;
+    ot[3] = touch ? (x2 < ox + P - 1 ? x2 : ox + P - 1) - ox : 0;
+    ot[4] = touch ? (y2 < oy + P - 1 ? y2 : oy + P - 1) - oy : 0;
+  }
+}
+
+int launch_detection_cells(const int64_t* bboxes, const int32_t* extents, int B, int nb, int Gh, int Gw, int P, int sample_neg,
+                           uint64_t seed, int capacity, int64_t* cells, int64_t* targets, int32_t* offsets, int32_t* n_pos,
+                           hipStream_t s) {
+  if (B > 0)
+    hipLaunchKernelGGL(det_cells_count_kernel, dim3(B), dim3(kDetThreads), 0, s, (const long long*)bboxes, extents, nb, Gh, Gw, P,
+                       sample_neg, offsets, n_pos);
+  hipLaunchKernelGGL(det_cells_scan_kernel, dim3(1), dim3(kDetThreads), 0, s, offsets, B);
+  if (B > 0)
+    hipLaunchKernelGGL(det_cells_select_kernel, dim3(B), dim3(kDetThreads), 2 * sizeof(uint16_t) * (size_t)Gh * Gw, s,
+                       (const long long*)bboxes, extents, nb, Gh, Gw, P, sample_neg, seed, capacity, offsets, (long long*)cells,
+                       (long long*)targets);
+  return 0;
+}
+
 // reset (src/env/general_env.py:144-170): zero state, place agents, mark the start tile.
 __global__ void env_reset_kernel(EnvPtrs e, const long long* __restrict__ start, uint64_t seed) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;

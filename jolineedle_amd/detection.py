@@ -60,6 +60,99 @@ def detection_targets(bboxes: Tensor, n_vertical: int, n_horizontal: int, patch_
     return res
 
 
+MAX_DETECTION_CELLS = 4096       # JN_DETCELLS_MAX_CELLS: cells per image the select kernel lists in LDS
+_NEG_TAG = 0x4E454753            # third Philox counter word of the negative draws
+
+
+def detection_cells(bboxes: Tensor, gh: int, gw: int, P: int, sample_neg: int, seed: int,
+                    extents=None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """The cells and targets of ``NeedleGeneralEnv.get_detection_batch`` (src/env/general_env.py:506-546) for a whole
+    batch, on the host in numpy — the statement of the rule ``jn_detection_cells`` computes (include/jnroll.h) and the
+    comparand of ``detection_cells_device``.  bboxes [B, nb, 4] xyxy (zero rows = padding) on a grid of gh x gw cells
+    of P px; extents [B, 2] = (gh_i, gw_i): image i owns the top-left gh_i x gw_i cells only.
+
+    Per image, in index order: the cells that hold a piece of a box (``split_bboxes_over_patches``' masks) in
+    row-major order, then min(sample_neg, n_empty) of its empty cells by a partial Fisher-Yates shuffle of their
+    row-major list E: draw j swaps E[j] with E[j + r mod (n_empty - j)], r = Philox4x32-10(seed; image, j, 0x4e454753,
+    0).x, and emits E[j] — a function of (seed, image index) alone.  (The reference draws with ``torch.randperm``.)
+
+    Returns on the CPU: cells int64 [n, 3] = (image, y, x), targets int64 [n, nb, 5] = (0, x1, y1, x2, y2) patch-local
+    (zero rows for the boxes that do not touch the cell), offsets int32 [B + 1] (row offsets[i] is image i's first,
+    offsets[B] = n) and n_pos int32 [B]."""
+    import numpy as np
+    from .ragged import _philox4x32
+    gh, gw, P, sample_neg = int(gh), int(gw), int(P), int(sample_neg)
+    bb = np.asarray(bboxes.detach().cpu() if isinstance(bboxes, Tensor) else bboxes, dtype=np.int64)
+    assert bb.ndim == 3 and bb.shape[2] == 4 and bb.shape[1] >= 1 and P >= 1 and sample_neg >= 0 and gh >= 1 and gw >= 1
+    B, nb = bb.shape[0], bb.shape[1]
+    if extents is None:
+        ext = np.tile(np.array([[gh, gw]], np.int64), (B, 1))
+    else:
+        ext = np.asarray(extents.cpu() if isinstance(extents, Tensor) else extents, dtype=np.int64).reshape(B, 2)
+        assert ((ext >= 1) & (ext <= np.array([gh, gw]))).all(), "an extent outside the grid"
+    x1, y1, x2, y2 = (bb[:, :, k, None] for k in range(4))                               # [B, nb, 1]
+    ys, xs = np.arange(gh, dtype=np.int64)[None, None, :], np.arange(gw, dtype=np.int64)[None, None, :]
+    in_y = (y1 // P <= ys) & (ys <= y2 // P) & (ys < ext[:, None, 0:1])                  # [B, nb, gh] (numpy's // floors)
+    in_x = (x1 // P <= xs) & (xs <= x2 // P) & (xs < ext[:, None, 1:2])                  # [B, nb, gw]
+    touch = (in_y[:, :, :, None] & in_x[:, :, None, :]).transpose(0, 2, 3, 1)            # [B, gh, gw, nb]
+    ly1, ly2 = np.maximum(y1, ys * P) - ys * P, np.minimum(y2, ys * P + P - 1) - ys * P  # [B, nb, gh]
+    lx1, lx2 = np.maximum(x1, xs * P) - xs * P, np.minimum(x2, xs * P + P - 1) - xs * P  # [B, nb, gw]
+    local = np.zeros((B, gh, gw, nb, 5), np.int64)
+    local[..., 1] = lx1.transpose(0, 2, 1)[:, None, :, :]
+    local[..., 2] = ly1.transpose(0, 2, 1)[:, :, None, :]
+    local[..., 3] = lx2.transpose(0, 2, 1)[:, None, :, :]
+    local[..., 4] = ly2.transpose(0, 2, 1)[:, :, None, :]
+    local *= touch[..., None]
+    positive = touch.any(-1)                                                             # [B, gh, gw]
+    exists = (np.arange(gh)[None, :, None] < ext[:, 0, None, None]) & (np.arange(gw)[None, None, :] < ext[:, 1, None, None])
+    cells, offsets, n_pos = [], [0], []
+    for i in range(B):
+        pos = np.argwhere(positive[i])                                                   # row-major
+        E = [tuple(c) for c in np.argwhere(exists[i] & ~positive[i])]
+        k = min(sample_neg, len(E))
+        for j in range(k):
+            o = j + _philox4x32(int(seed), i, j, _NEG_TAG, 0)[0] % (len(E) - j)
+            E[j], E[o] = E[o], E[j]
+        rows = np.concatenate((pos, np.array(E[:k], np.int64).reshape(-1, 2)))
+        cells.append(np.concatenate((np.full((len(rows), 1), i, np.int64), rows), 1))
+        n_pos.append(len(pos))
+        offsets.append(offsets[-1] + len(rows))
+    cells = np.concatenate(cells) if cells else np.zeros((0, 3), np.int64)
+    targets = local[cells[:, 0], cells[:, 1], cells[:, 2]]
+    return (torch.from_numpy(cells), torch.from_numpy(targets), torch.tensor(offsets, dtype=torch.int32),
+            torch.tensor(n_pos, dtype=torch.int32))
+
+
+def detection_cells_device(bboxes: Tensor, gh: int, gw: int, P: int, sample_neg: int, seed: int,
+                           extents=None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``detection_cells`` on the device (``jn_detection_cells``: three launches, no Python loop): bboxes [B, nb, 4] on
+    the GPU; returns (cells, targets, offsets, n_pos) as the host function does, with cells, targets and n_pos on the
+    device.  The buffers hold B * gh * gw rows, which always suffices; the B + 1 offsets are read back once — the one
+    synchronisation, for n (with `extents` the entry point checks them on the host first, a second one).  A grid beyond
+    ``MAX_DETECTION_CELLS`` cells is refused by the entry point."""
+    from . import _lib
+    from ._lib import check, ptr
+    if not bboxes.is_cuda:
+        raise RuntimeError("detection_cells_device needs the boxes on the GPU (detection_cells is the host function)")
+    dev = bboxes.device
+    bb = bboxes.to(torch.int64).contiguous()
+    assert bb.dim() == 3 and bb.shape[2] == 4, "bboxes are [B, nb, 4]"
+    B, nb = int(bb.shape[0]), int(bb.shape[1])
+    gh, gw = int(gh), int(gw)
+    ext = None if extents is None else torch.as_tensor(extents).to(dev, torch.int32).reshape(B, 2).contiguous()
+    cap = B * gh * gw
+    cells = torch.empty((cap, 3), device=dev, dtype=torch.int64)
+    targets = torch.empty((cap, max(nb, 1), 5), device=dev, dtype=torch.int64)
+    offsets = torch.empty((B + 1,), device=dev, dtype=torch.int32)
+    n_pos = torch.empty((B,), device=dev, dtype=torch.int32)
+    check(_lib.load_library().jn_detection_cells(ptr(bb), ptr(ext), B, nb, gh, gw, int(P), int(sample_neg),
+                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, cap, ptr(cells), ptr(targets), ptr(offsets),
+                                                 ptr(n_pos), _lib.current_stream(dev)), "jn_detection_cells")
+    offsets = offsets.cpu()
+    n = int(offsets[B])
+    return cells[:n], targets[:n], offsets, n_pos
+
+
 def patch_bboxes2full_image(outputs: List[List[Optional[Tensor]]], offsets: Tensor,
                             masks: Optional[Tensor] = None) -> List[Optional[Tensor]]:
     """Per-patch predictions (list over images of lists over glimpse steps) -> one tensor of boxes per image in

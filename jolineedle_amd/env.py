@@ -27,6 +27,7 @@ class NeedleGeneralEnv:
         — the inference semantics; the default lets every agent walk the canvas, the reference's padded collate."""
         self.views = views
         self.grid_extents = None
+        self._grid_extents_dev = None                      # device copy, made on first use (get_detection_batch(device=True))
         if clamp_to_image:
             assert views is not None, "clamp_to_image needs views"
             self.grid_extents = views.grid_extents(patch_size)
@@ -205,9 +206,18 @@ class NeedleGeneralEnv:
         return detection_targets(self.bboxes, self.n_vertical_patches, self.n_horizontal_patches, self.patch_size)
 
     @torch.no_grad()
-    def get_detection_batch(self, sample_neg: int = 1, generator: torch.Generator = None):
+    def get_detection_batch(self, sample_neg: int = 1, generator: torch.Generator = None, device: bool = False,
+                            seed: int = 0):
         """Patches to train the detector on: every patch holding (a piece of) a box plus `sample_neg` random empty
-        patches per image; returns (patches [n, 3, P, P], bboxes [n, nb, 1 + 4]) like general_env.py:503-544."""
+        patches per image; returns (patches [n, 3, P, P], bboxes [n, nb, 1 + 4]) like general_env.py:503-544.
+        device: the cells and targets come from ``detection.detection_cells_device`` on the env's boxes (the
+        transformed ones under views; with the grid extents in ragged mode) and the patches from one indexed gather —
+        no Python loop over the images, one readback (the row count).  The positive rows are those of the host route,
+        in its order; the negatives are drawn from `seed` by the rule of ``detection.detection_cells`` instead of
+        ``torch.randperm`` (`generator` is not used).  A batch without boxes (nb = 0) gives negatives only, with
+        targets [n, 0, 5], on either route."""
+        if device:
+            return self._detection_batch_device(int(sample_neg), int(seed))
         boxes, masks = self.parse_bboxes()
         any_box = masks.any(-1).cpu()
         P = self.patch_size
@@ -229,6 +239,28 @@ class NeedleGeneralEnv:
             return (gather_indexed(self._images, cells[:, 0], cells[:, 1:], P, views=self.views),
                     torch.stack(all_boxes).to(self.device))
         return torch.stack(patches), torch.stack(all_boxes).to(self.device)
+
+    def _detection_batch_device(self, sample_neg: int, seed: int):
+        from .detection import detection_cells_device
+        from .trajectory import gather_indexed
+        ext = None
+        if self.grid_extents is not None:
+            if self._grid_extents_dev is None:
+                self._grid_extents_dev = self.grid_extents.to(self.device, torch.int32).contiguous()
+            ext = self._grid_extents_dev
+        bb = self._bboxes_dev
+        nb = int(bb.shape[1]) if bb.dim() == 3 else 0
+        if nb == 0:
+            # a batch without any box (the host route then returns negatives only, targets [n, 0, 5]): the kernel takes at
+            # least one box per image, so it gets one that touches no cell (x2 // P < x1 // P) and its column is dropped
+            bb = torch.tensor([0, 0, -1, -1], dtype=torch.int64, device=self.device).repeat(self.batch_size, 1, 1)
+        cells, targets, _, _ = detection_cells_device(bb, self.n_vertical_patches, self.n_horizontal_patches,
+                                                      self.patch_size, sample_neg, seed, extents=ext)
+        targets = targets[:, :nb]
+        # (the cells lie on the grid by construction: the gather's host-side asserts, a readback each, are skipped)
+        patches = gather_indexed(self._images, cells[:, 0], cells[:, 1:], self.patch_size, views=self.views,
+                                 _check_positions=False)
+        return patches, targets
 
     @property
     def prop_bboxes_found(self) -> Tensor:

@@ -238,7 +238,7 @@ class ReinforceTrainer:
         loss = metrics["loss"]
         ga = int(getattr(config, "gradient_accumulation", 1))
         if getattr(config, "detection_enabled", False) and self.yolox_model() is not None:      # src/reinforce.py:330-339
-            patches_yolox, bboxes_yolox = env.get_detection_batch(int(getattr(config, "detection_sample_neg", 1)))
+            patches_yolox, bboxes_yolox = self._detection_batch(env, int(getattr(config, "detection_sample_neg", 1)))
             if getattr(self, "detection_augment", None) is not None:
                 with torch.no_grad():
                     patches_yolox = self.detection_augment(patches_yolox)
@@ -310,6 +310,20 @@ class ReinforceTrainer:
             self._owns_process_group = False
         return metrics
 
+    def _detection_batch(self, env: NeedleGeneralEnv, sample_neg: int):
+        """``env.get_detection_batch``; with ``config.device_detection_batch`` (default off) assembled on the device, the
+        negatives drawn from ``detection_batch_seed()``."""
+        if getattr(self.config, "device_detection_batch", False):
+            return env.get_detection_batch(sample_neg, device=True, seed=self.detection_batch_seed())
+        return env.get_detection_batch(sample_neg)
+
+    def detection_batch_seed(self) -> int:
+        """Key of the device route's negative draws in the current iteration: the trainer's seed, its rank (the draws are
+        keyed by the image's index within the rank's batch, so data-parallel ranks need keys of their own; 17 * rank as in
+        ``init_detection``) and the iteration counter."""
+        rank = int(getattr(self, "rank", 0) or 0)
+        return ((self.seed + 17 * rank) * 1000003 + int(getattr(self, "iter_num", 0))) & 0xFFFFFFFFFFFFFFFF
+
     def init_detection(self, **kw):
         """``Trainer.init_detection`` (src/trainer.py:176-186): installs the on-device augmentation of the detector
         patches.  Off until called (the parity tests compare un-augmented steps); keyword arguments go to
@@ -380,7 +394,7 @@ class ReinforceTrainer:
         detection = bool(getattr(self.config, "detection_enabled", False)) and self.yolox_model() is not None
         yolo_losses = {}
         if detection:
-            patches_y, boxes_y = env.get_detection_batch(int(getattr(self.config, "detection_sample_neg", 1)))
+            patches_y, boxes_y = self._detection_batch(env, int(getattr(self.config, "detection_sample_neg", 1)))
             if getattr(self, "detection_augment", None) is not None:               # src/reinforce.py:332-333
                 patches_y = self.detection_augment(patches_y)
             yolo_losses = self.yolox_model().loss_and_backward(patches_y, boxes_y, loss_scale=1.0 / ga)
@@ -458,7 +472,7 @@ class ReinforceTrainer:
             targets = env.get_detection_targets()
             offsets = ro["positions"][:, :, [1, 0]] * self.patch_size        # (y, x) grid -> (x, y) pixels
             preds = patch_bboxes2full_image(ro["bboxes"], offsets, ro["masks"])
-            patches, patch_targets = env.get_detection_batch(sample_neg=0)
+            patches, patch_targets = self._detection_batch(env, 0)
             metrics.update(self._detection_eval_metrics(preds, targets, patches, patch_targets, merge_bboxes))
         return metrics
 

@@ -319,12 +319,14 @@ def simple_env_targets(bboxes, height: int, width: int, patch_size: int) -> torc
 
 
 def gather_indexed(images: torch.Tensor, image_index: torch.Tensor, positions: torch.Tensor, patch_size: int,
-                   views=None) -> torch.Tensor:
+                   views=None, _check_positions: bool = True) -> torch.Tensor:
     """out[n] = images[image_index[n], :, y*P:(y+1)*P, x*P:(x+1)*P]; a negative image index gives a zero patch.
     uint8 images are read in place and give byte / 255 (fp32, as ToTensor computes it).
-    views: an ``ImageViews`` — the patches are cut from its augmented canvas instead (`images` is not used)."""
+    views: an ``ImageViews`` — the patches are cut from its augmented canvas instead (`images` is not used).
+    _check_positions (internal): False skips the host-side asserts, and the readback they cost, for indices and
+    positions that are valid by construction (the cells ``jn_detection_cells`` names)."""
     if views is not None:
-        return views.gather(image_index, positions, patch_size)
+        return views.gather(image_index, positions, patch_size, _check_positions=_check_positions)
     from . import _lib
     from ._lib import check, ptr
     assert images.is_cuda and images.dtype in (torch.float32, torch.uint8) and images.is_contiguous(), \
@@ -335,7 +337,7 @@ def gather_indexed(images: torch.Tensor, image_index: torch.Tensor, positions: t
     ii = image_index.to(images.device, torch.int64).contiguous()
     pos = positions.to(images.device, torch.int64).contiguous()
     N = int(ii.numel())
-    if N:
+    if N and _check_positions:
         ph, pw = H // P, W // P
         pc, ic = pos.cpu(), ii.cpu()
         assert bool(((pc[:, 0] >= 0) & (pc[:, 0] < ph) & (pc[:, 1] >= 0) & (pc[:, 1] < pw)).all()), "position outside the grid"

@@ -195,9 +195,11 @@ class ImageViews:
             self._table_dev = torch.from_numpy(raw).to(self.device)
         return self._table_dev
 
-    def gather(self, image_index: Tensor, positions: Tensor, patch_size: int, out_uint8: bool = False) -> Tensor:
+    def gather(self, image_index: Tensor, positions: Tensor, patch_size: int, out_uint8: bool = False,
+               _check_positions: bool = True) -> Tensor:
         """out[n] = canvas[image_index[n], :, y*P:(y+1)*P, x*P:(x+1)*P] (negative index: zero patch) without the canvas.
-        fp32 out (bytes as byte / 255), or with `out_uint8` the transformed bytes of uint8 sources."""
+        fp32 out (bytes as byte / 255), or with `out_uint8` the transformed bytes of uint8 sources.
+        _check_positions (internal): as in ``trajectory.gather_indexed``."""
         from . import _lib
         from ._lib import check, ptr
         P = int(patch_size)
@@ -207,7 +209,7 @@ class ImageViews:
         ii = image_index.to(self.device, torch.int64).contiguous()
         pos = positions.to(self.device, torch.int64).contiguous()
         N = int(ii.numel())
-        if N:
+        if N and _check_positions:
             pc, ic = pos.cpu(), ii.cpu()
             assert bool(((pc[:, 0] >= 0) & (pc[:, 0] < Hc // P) & (pc[:, 1] >= 0) & (pc[:, 1] < Wc // P)).all()), "position outside the grid"
             assert bool((ic < len(self)).all()), "image index out of range"
