@@ -615,6 +615,41 @@ int jn_set_rollout_positions(jn_ctx* ctx, int by_token);
  * JN_EINVAL: a null pointer, B, Gh or Gw < 1. */
 int jn_teacher_actions(const int64_t* positions_dev, const uint8_t* visited_dev, const uint8_t* targets_dev, int B, int Gh,
                        int Gw, uint8_t* sets_dev, void* stream);
+/* The teacher's whole walk for a batch of images, context-free: NeedleSimpleEnv.generate_sample_indices
+ * (src/env/simple_env.py:481-588) without its patches, with the env's two random sources replaced by counter-based
+ * draws (no device path can consume numpy's or Python's streams).  Draw k of a stream of image b is
+ * Philox4x32-10(key = seed, counter = (b, k, TAG, 0)).x, k counting from 0 in the order the host code makes its calls:
+ *  - stream R (TAG 0x54574B52) for `rng`: integers(lo, hi) = lo + r mod (hi - lo), one draw (n draws with size = n);
+ *    choice(n) = r mod n; binomial(n, 1/2) = the set bits among n random bits, ceil(n / 32) draws, draw j supplying bits
+ *    32j .. 32j + 31 and the last one only its low n - 32j bits.  In order: the negative detector cell (if the image has
+ *    an empty cell), the start (y, x) unless given, the one random keypoint (y, x) when no target is left to visit, the
+ *    number of detours in min_keypoints .. max_keypoints, their places, then the detours (y, x; binomial: x before y) and
+ *    the STOP replacements as the walk meets them.
+ *  - stream Y (TAG 0x54574B59) for the tie choice of build_keypoints_trajectory: keypoint k is element r_k mod len of the
+ *    remaining target cells nearest (L1) to the previous keypoint, listed in row-major order; one draw per keypoint.
+ * bboxes_dev int64 [B,nb,4] xyxy in pixels, nb >= 0; an all-zero row is padding and is skipped, and column j of both box
+ * outputs is the j-th non-zero row (the other columns are zero).  A box's target cells (bbox_positions, :270-321): the
+ * cells of its own range (floor division) with 20 * h * w > P * P, which is h * w / P**2 > 0.05, plus its centre's cell;
+ * cells outside the Gh x Gw grid are dropped.  start_positions_dev int64 [B,2] (y, x) or NULL; a start outside the grid
+ * is the caller's error (the kernel clamps it into the grid).
+ * Outputs: positions int64 [B,T,2], current_actions / next_actions / labels int64 [B,T], masks f32 [B,T], local_bboxes
+ * f32 [B,T,nb,6] (rows (0, x1, y1, x2, y2, 1) of NeedleSimpleEnv.local_bboxes, :231-268) — the walk's last T steps, zero
+ * rows behind a shorter walk; n_steps int32 [B] the walk's length before that cut; targets uint8 [B,Gh,Gw]; offsets int32
+ * [B+1], cells int64 [capacity,3] = (image, y, x) and bboxes_yolox f32 [capacity,nb,6]: per image its target cells in
+ * row-major order, then the one negative cell, the (first R draw mod n_empty)-th empty cell in row-major order.  Rows
+ * >= capacity are not written (offsets still count them), rows >= offsets[B] are left alone; B * Gh * Gw always suffices.
+ * Three launches on `stream` (walk: one wave per image; scan; detector rows), no atomics: equal inputs give equal
+ * bytes.  Does not wait for the device.  Limits: Gh * Gw <= 4096 (the walk state of an image lives in LDS), T <= 4096
+ * (the LDS ring of the last T steps, 8 bytes each), max_keypoints <= 64 (the detour table, one lane per detour).
+ * JN_EINVAL, before any launch: B < 0, nb < 0, P < 1, Gh or Gw < 1, Gh * Gw > 4096, T < 1, T > 4096, min_keypoints < 0,
+ * max_keypoints < min_keypoints, max_keypoints > 64, capacity < 0, B * Gh * Gw > INT32_MAX, a null pointer (bboxes /
+ * local_bboxes / bboxes_yolox may be NULL with nb = 0, cells / bboxes_yolox with capacity 0).  B = 0 writes offsets[0] = 0
+ * and launches nothing. */
+int jn_teacher_walks(const int64_t* bboxes_dev, const int64_t* start_positions_dev, int B, int nb, int Gh, int Gw, int P,
+                     int T, int min_keypoints, int max_keypoints, int binomial_keypoints, uint64_t seed, int capacity,
+                     int64_t* positions_dev, int64_t* current_actions_dev, int64_t* next_actions_dev, int64_t* labels_dev,
+                     float* masks_dev, float* local_bboxes_dev, int32_t* n_steps_dev, uint8_t* targets_dev,
+                     int64_t* cells_dev, float* bboxes_yolox_dev, int32_t* offsets_dev, void* stream);
 /* Arms the following rollouts of `ctx` with that teacher (the per-step `best_action` that test_model_on_env compares
  * each chosen action with, src/supervised.py:279-405): before the decision of step t, the set of the state that
  * decision sees (position and visited patches before the step) goes to sets_dev[b * T + t] (uint8 [B,T], T =

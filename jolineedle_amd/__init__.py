@@ -20,6 +20,7 @@ from .checkpoint import (save_config, config_from_file, save_checkpoint, load_ch
                          load_detection_checkpoint)
 from .infer import infer_images, plan_chunks, pad_to_patch_multiple, load_bboxes  # noqa: F401
 from .trajectory import NeedleSimpleEnv, teacher_action_sets, teacher_action_sets_device  # noqa: F401
+from .trajectory import PhiloxDraws, teacher_walks, teacher_walks_device  # noqa: F401
 from .views import ImageViews  # noqa: F401
 from .detection import (patch_bboxes2full_image, rollout_boxes_to_image, merge_boxes, merge_boxes_batched,  # noqa: F401
                         compute_detection_metrics, detection_targets, detection_cells, detection_cells_device,

@@ -252,4 +252,36 @@ int jn_teacher_actions(const int64_t* positions_dev, const uint8_t* visited_dev,
   return JN_OK;
 }
 
+int jn_teacher_walks(const int64_t* bboxes_dev, const int64_t* start_positions_dev, int B, int nb, int Gh, int Gw, int P,
+                     int T, int min_keypoints, int max_keypoints, int binomial_keypoints, uint64_t seed, int capacity,
+                     int64_t* positions_dev, int64_t* current_actions_dev, int64_t* next_actions_dev, int64_t* labels_dev,
+                     float* masks_dev, float* local_bboxes_dev, int32_t* n_steps_dev, uint8_t* targets_dev,
+                     int64_t* cells_dev, float* bboxes_yolox_dev, int32_t* offsets_dev, void* stream) {
+  JN_CHECK(B >= 0 && nb >= 0 && P >= 1 && capacity >= 0, JN_EINVAL, "jn_teacher_walks: B=%d nb=%d P=%d capacity=%d", B, nb, P,
+           capacity);
+  JN_CHECK(Gh >= 1 && Gw >= 1 && (long long)Gh * Gw <= JN_TWALK_MAX_CELLS, JN_EINVAL,
+           "jn_teacher_walks: a grid of %d x %d cells, the kernel holds at most %d per image in LDS", Gh, Gw, JN_TWALK_MAX_CELLS);
+  JN_CHECK(T >= 1 && T <= JN_TWALK_MAX_T, JN_EINVAL, "jn_teacher_walks: T=%d, the LDS ring holds 1..%d steps", T, JN_TWALK_MAX_T);
+  JN_CHECK(min_keypoints >= 0 && max_keypoints >= min_keypoints && max_keypoints <= JN_TWALK_MAX_KEYPOINTS, JN_EINVAL,
+           "jn_teacher_walks: min_keypoints=%d max_keypoints=%d, need 0 <= min <= max <= %d (the detour table)", min_keypoints,
+           max_keypoints, JN_TWALK_MAX_KEYPOINTS);
+  JN_CHECK((long long)B * Gh * Gw <= INT32_MAX, JN_EINVAL, "jn_teacher_walks: B * Gh * Gw beyond the int32 offsets");
+  JN_CHECK(offsets_dev, JN_EINVAL, "jn_teacher_walks: null offsets");
+  if (B == 0) {
+    JN_HIP(hipMemsetAsync(offsets_dev, 0, sizeof(int32_t), (hipStream_t)stream));
+    return JN_OK;
+  }
+  JN_CHECK(positions_dev && current_actions_dev && next_actions_dev && labels_dev && masks_dev && n_steps_dev && targets_dev,
+           JN_EINVAL, "jn_teacher_walks: null output");
+  JN_CHECK((bboxes_dev && local_bboxes_dev) || nb == 0, JN_EINVAL, "jn_teacher_walks: null boxes with nb=%d", nb);
+  JN_CHECK((cells_dev && (bboxes_yolox_dev || nb == 0)) || capacity == 0, JN_EINVAL,
+           "jn_teacher_walks: null detector rows with capacity=%d", capacity);
+  TeacherWalkArgs a{bboxes_dev, start_positions_dev, B, nb, Gh, Gw, P, T, min_keypoints, max_keypoints,
+                    binomial_keypoints != 0, seed, capacity, positions_dev, current_actions_dev, next_actions_dev, labels_dev,
+                    masks_dev, local_bboxes_dev, n_steps_dev, targets_dev, cells_dev, bboxes_yolox_dev, offsets_dev};
+  launch_teacher_walks(a, (hipStream_t)stream);
+  JN_HIP(hipGetLastError());
+  return JN_OK;
+}
+
 }  // extern "C"

@@ -328,6 +328,21 @@ int launch_rollout_epilogue(const RolloutBuffers& r, const int32_t* n_done, int 
 // the teacher's action set of every agent's state (jnroll.h: jn_teacher_actions); sets[b * set_stride], one wave per agent
 int launch_teacher_sets(const int64_t* positions, const uint8_t* visited, const uint8_t* targets, uint8_t* sets,
                         long long set_stride, int B, int Gh, int Gw, const int* skip_flag, int skip_when, hipStream_t s);
+// the teacher's whole walks of a batch (jnroll.h: jn_teacher_walks): walk (one wave per image; target / todo bytes of the
+// grid and a ring of T steps in LDS), the scan of launch_detection_cells, detector rows.  The caller checks every limit.
+constexpr int JN_TWALK_MAX_CELLS = JN_DETCELLS_MAX_CELLS;   // 2 x 4 KB of cell bytes
+constexpr int JN_TWALK_MAX_T = 4096;                        // a ring of 8-byte steps: 32 KB
+constexpr int JN_TWALK_MAX_KEYPOINTS = 64;                  // the detour table: one lane per detour
+struct TeacherWalkArgs {
+  const int64_t* bboxes; const int64_t* starts;             // [B,nb,4]; [B,2] or null
+  int B, nb, Gh, Gw, P, T, min_keypoints, max_keypoints, binomial;
+  uint64_t seed;
+  int capacity;
+  int64_t* positions; int64_t* current_actions; int64_t* next_actions; int64_t* labels;
+  float* masks; float* local_bboxes; int32_t* n_steps; uint8_t* targets;
+  int64_t* cells; float* bboxes_yolox; int32_t* offsets;
+};
+int launch_teacher_walks(const TeacherWalkArgs& a, hipStream_t s);
 // kernels_ragged.hip: patch_bboxes2full_image for a whole batch (jnroll.h: jn_rollout_boxes_to_image)
 int launch_boxes_to_image(const float* det_boxes, const int32_t* det_counts, const int64_t* positions, const uint8_t* masks,
                           int B, int T, int S, int K, int P, float* out_boxes, int32_t* out_totals, hipStream_t s);

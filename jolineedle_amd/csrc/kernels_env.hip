@@ -402,4 +402,311 @@ int launch_teacher_sets(const int64_t* positions, const uint8_t* visited, const 
   return 0;
 }
 
+// The teacher's whole walk (NeedleSimpleEnv.generate_sample_indices, src/env/simple_env.py:481-588; the rule and its two
+// Philox streams are stated at jnroll.h: jn_teacher_walks and, on plain integers, by trajectory.teacher_walks).  One wave
+// per image.  The draws and the walk are sequential: every lane computes the same draw and the same position, the values
+// are made scalar (readfirstlane) and the control flow is wave-uniform; lane 0 writes the ring.  The nearest-target search
+// and the tie rank use all 64 lanes.  Three launches: walk (also counts the image's detector rows), the exclusive scan of
+// jn_detection_cells, detector rows.
+constexpr uint32_t kWalkTagR = 0x54574B52u, kWalkTagY = 0x54574B59u;
+
+struct WalkStep { uint8_t action, teacher, label, pad; uint16_t y, x; };      // one step of the LDS ring, 8 bytes
+
+__device__ inline bool walk_box_real(const long long* q) { return (q[0] | q[1] | q[2] | q[3]) != 0; }
+
+// bbox_positions (src/env/simple_env.py:270-321): is cell (cy, cx) one of box q's?  Its centre cell, or a cell of its own
+// range holding more than 1 / 20 of a patch area: h * w / P**2 > 0.05 <=> 20 * h * w > P * P on integers.
+__device__ inline bool walk_cell_target(const long long* q, long long P, int cy, int cx) {
+  const long long x1 = q[0], y1 = q[1], x2 = q[2], y2 = q[3];
+  if (floor_div(floor_div(y1 + y2, 2), P) == cy && floor_div(floor_div(x1 + x2, 2), P) == cx) return true;
+  if (cy < floor_div(y1, P) || cy > floor_div(y2, P) || cx < floor_div(x1, P) || cx > floor_div(x2, P)) return false;
+  const long long h = min((cy + 1) * P, y2) - max(cy * P, y1);
+  const long long w = min((cx + 1) * P, x2) - max(cx * P, x1);
+  return 20 * h * w > P * P;
+}
+
+// NeedleSimpleEnv.local_bboxes (:231-268): the part of box q inside the patch at (py, px) as (0, x1, y1, x2, y2, 1), or zeros
+__device__ inline void walk_local_box(const long long* q, long long P, int py, int px, bool live, float* __restrict__ o) {
+  const long long ox = px * P, oy = py * P;
+  const long long cx1 = max(ox, q[0]), cy1 = max(oy, q[1]), cx2 = min(ox + P, q[2]), cy2 = min(oy + P, q[3]);
+  const bool in = live && cx1 < cx2 && cy1 < cy2;
+  o[0] = 0.f;
+  o[1] = in ? (float)(cx1 - ox) : 0.f;
+  o[2] = in ? (float)(cy1 - oy) : 0.f;
+  o[3] = in ? (float)(cx2 - ox) : 0.f;
+  o[4] = in ? (float)(cy2 - oy) : 0.f;
+  o[5] = in ? 1.f : 0.f;
+}
+
+__device__ inline int walk_towards(int y, int x, int ty, int tx) {
+  return kTowards[((ty > y) - (ty < y) + 1) * 3 + (tx > x) - (tx < x) + 1];
+}
+
+__device__ inline unsigned long long walk_lanes_below(int lane) { return (1ull << lane) - 1ull; }
+
+// Dynamic LDS: WalkStep [T], the ring of the walk's last T steps.
+__global__ __launch_bounds__(64) void teacher_walk_kernel(TeacherWalkArgs a) {
+  __shared__ uint8_t s_target[JN_TWALK_MAX_CELLS];
+  __shared__ uint8_t s_todo[JN_TWALK_MAX_CELLS];
+  extern __shared__ WalkStep walk_ring[];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int Gh = a.Gh, Gw = a.Gw, cells = Gh * Gw, T = a.T, nb = a.nb;
+  const long long P = a.P;
+  const long long* bb = (const long long*)a.bboxes + (long long)b * nb * 4;
+
+  // the target cells of the image, its detector rows counted on the way
+  int n_target = 0;
+  for (int c0 = 0; c0 < cells; c0 += 64) {
+    const int c = c0 + lane;
+    bool t = false;
+    if (c < cells) {
+      const int cy = c / Gw, cx = c % Gw;
+      for (int k = 0; k < nb && !t; ++k) t = walk_box_real(bb + 4 * k) && walk_cell_target(bb + 4 * k, P, cy, cx);
+      s_target[c] = t;
+      s_todo[c] = t;
+      a.targets[(long long)b * cells + c] = t;
+    }
+    n_target += __popcll(__ballot(t));
+  }
+  __syncthreads();
+
+  uint32_t kr = 0;                                           // draws of stream R made so far (uniform)
+  auto draw = [&]() -> uint32_t {
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)philox4x32(a.seed, (uint32_t)b, kr++, kWalkTagR, 0u).x);
+  };
+  if (n_target < cells) draw();                              // the negative detector cell: teacher_walk_rows_kernel redraws it
+  int y, x;
+  if (a.starts) {
+    y = min(max((int)a.starts[2 * b], 0), Gh - 1);
+    x = min(max((int)a.starts[2 * b + 1], 0), Gw - 1);
+  } else {
+    y = (int)(draw() % (uint32_t)Gh);
+    x = (int)(draw() % (uint32_t)Gw);
+  }
+  y = __builtin_amdgcn_readfirstlane(y);
+  x = __builtin_amdgcn_readfirstlane(x);
+  int n_keypoints = __builtin_amdgcn_readfirstlane(n_target - (s_target[y * Gw + x] ? 1 : 0));
+  __syncthreads();                                           // (every lane has read the start's cell)
+  if (lane == 0) s_todo[y * Gw + x] = 0;
+  __syncthreads();
+  const bool random_keypoint = n_keypoints == 0;             // nothing to visit: one random cell
+  int ry = 0, rx = 0;
+  if (random_keypoint) {
+    ry = (int)(draw() % (uint32_t)Gh);
+    rx = (int)(draw() % (uint32_t)Gw);
+    n_keypoints = 1;
+  }
+  const int n_extra = a.min_keypoints + (int)(draw() % (uint32_t)(a.max_keypoints + 1 - a.min_keypoints));
+  // the detour table: lane j holds the keypoint in front of which detour j is walked (n_extra <= 64)
+  int insert_at = -1;
+  if (lane < n_extra)
+    insert_at = (int)(philox4x32(a.seed, (uint32_t)b, kr + (uint32_t)lane, kWalkTagR, 0u).x % (uint32_t)n_keypoints);
+  kr += (uint32_t)n_extra;
+
+  int n = 0;                                                 // steps recorded so far
+  if (lane == 0) walk_ring[0] = WalkStep{0, 0, s_target[y * Gw + x], 0, (uint16_t)y, (uint16_t)x};
+  n = 1;
+  const int longest = max(Gh, Gw);                           // a visit takes fewer king's moves than that
+
+  // walk to (ty, tx) while the teacher points at (ky, kx); STOP is replaced by a random move
+  auto visit = [&](int ty, int tx, int ky, int kx) {
+    for (int i = 0; i < longest && (y != ty || x != tx); ++i) {
+      const int act = walk_towards(y, x, ty, tx);
+      y += kActionDy[act];
+      x += kActionDx[act];
+      int best = walk_towards(y, x, ky, kx);
+      if (best == 8) best = (int)(draw() % 8u);
+      if (lane == 0)
+        walk_ring[n % T] = WalkStep{(uint8_t)act, (uint8_t)best, s_target[y * Gw + x], 0, (uint16_t)y, (uint16_t)x};
+      ++n;
+    }
+  };
+  auto binomial = [&](int bits) -> int {                     // set bits among `bits` random bits, 32 per draw
+    int total = 0;
+    for (int j = 0; 32 * j < bits; ++j) {
+      uint32_t r = draw();
+      if (bits - 32 * j < 32) r &= (1u << (bits - 32 * j)) - 1u;
+      total += __popc(r);
+    }
+    return total;
+  };
+
+  for (int kid = 0; kid < n_keypoints; ++kid) {
+    int ky = ry, kx = rx;
+    if (!random_keypoint) {
+      // the nearest cells still to visit (L1), then the (draw mod their number)-th of them in row-major order
+      int best = INT_MAX, cnt = 0;
+      for (int i = lane; i < cells; i += 64) {
+        if (!s_todo[i]) continue;
+        const int d = abs(i / Gw - y) + abs(i % Gw - x);
+        if (d < best) { best = d; cnt = 1; }
+        else if (d == best) ++cnt;
+      }
+      int wmin = best;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) wmin = min(wmin, __shfl_xor(wmin, o, 64));
+      int len = best == wmin ? cnt : 0;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) len += __shfl_xor(len, o, 64);
+      wmin = __builtin_amdgcn_readfirstlane(wmin);
+      len = __builtin_amdgcn_readfirstlane(len);
+      if (len <= 0) break;                                   // (cannot happen: n_keypoints counts the cells to visit)
+      const uint32_t r = philox4x32(a.seed, (uint32_t)b, (uint32_t)kid, kWalkTagY, 0u).x;
+      const int rank = __builtin_amdgcn_readfirstlane((int)(r % (uint32_t)len));
+      int seen = 0, chosen = -1;
+      for (int c0 = 0; c0 < cells; c0 += 64) {
+        const int c = c0 + lane;
+        const bool tie = c < cells && s_todo[c] && abs(c / Gw - y) + abs(c % Gw - x) == wmin;
+        const unsigned long long m = __ballot(tie);
+        const int pc = __popcll(m);
+        if (rank < seen + pc) {
+          const unsigned long long sel = __ballot(tie && __popcll(m & walk_lanes_below(lane)) == rank - seen);
+          chosen = c0 + __ffsll((long long)sel) - 1;
+          break;
+        }
+        seen += pc;
+      }
+      if (chosen < 0) break;                                 // (cannot happen: rank < len)
+      __syncthreads();                                       // (every lane has read the todo bytes)
+      if (lane == 0) s_todo[chosen] = 0;
+      __syncthreads();
+      ky = chosen / Gw;
+      kx = chosen % Gw;
+    }
+    // the teacher action of the last recorded step now points at this keypoint
+    int best = walk_towards(y, x, ky, kx);
+    if (best == 8) best = (int)(draw() % 8u);
+    if (lane == 0) walk_ring[(n - 1) % T].teacher = (uint8_t)best;
+    const int n_detours = __popcll(__ballot(insert_at == kid));
+    for (int d = 0; d < n_detours; ++d) {
+      int ty, tx;
+      if (a.binomial) {
+        const int dx = binomial(Gw) - Gw / 2;
+        const int dy = binomial(Gh) - Gh / 2;
+        ty = ((ky + dy) % Gh + Gh) % Gh;
+        tx = ((kx + dx) % Gw + Gw) % Gw;
+      } else {
+        ty = (int)(draw() % (uint32_t)Gh);
+        tx = (int)(draw() % (uint32_t)Gw);
+      }
+      visit(ty, tx, ky, kx);
+    }
+    visit(ky, kx, ky, kx);
+  }
+  __syncthreads();
+
+  // the last min(n, T) steps, zero rows behind them
+  const int kept = min(n, T), first = n - kept;
+  if (lane == 0) {
+    a.n_steps[b] = n;
+    a.offsets[b + 1] = n_target + (n_target < cells ? 1 : 0);
+  }
+  for (int i = lane; i < T; i += 64) {
+    const bool live = i < kept;
+    const WalkStep s = live ? walk_ring[(first + i) % T] : WalkStep{0, 0, 0, 0, 0, 0};
+    const long long row = (long long)b * T + i;
+    a.positions[2 * row] = s.y;
+    a.positions[2 * row + 1] = s.x;
+    a.current_actions[row] = s.action;
+    a.next_actions[row] = s.teacher;
+    a.labels[row] = s.label;
+    a.masks[row] = live ? 1.f : 0.f;
+  }
+  // local boxes: column j is the j-th real (non-zero) row; a lane keeps its box and walks the T rows
+  int n_real = 0;
+  for (int k0 = 0; k0 < nb; k0 += 64) {
+    const int k = k0 + lane;
+    const bool real = k < nb && walk_box_real(bb + 4 * k);
+    const unsigned long long m = __ballot(real);
+    if (real) {
+      const int col = n_real + __popcll(m & walk_lanes_below(lane));
+      const long long q[4] = {bb[4 * k], bb[4 * k + 1], bb[4 * k + 2], bb[4 * k + 3]};
+      for (int i = 0; i < T; ++i) {
+        const bool live = i < kept;
+        const WalkStep s = live ? walk_ring[(first + i) % T] : WalkStep{0, 0, 0, 0, 0, 0};
+        walk_local_box(q, P, s.y, s.x, live, a.local_bboxes + (((long long)b * T + i) * nb + col) * 6);
+      }
+    }
+    n_real += __popcll(m);
+  }
+  const int n_pad = nb - n_real;
+  for (long long idx = lane; idx < (long long)T * n_pad; idx += 64) {
+    float* o = a.local_bboxes + (((long long)b * T + idx / n_pad) * nb + n_real + idx % n_pad) * 6;
+    for (int j = 0; j < 6; ++j) o[j] = 0.f;
+  }
+}
+
+// The detector rows of image b at offsets[b]: its target cells in row-major order, then the one negative cell — the
+// (draw 0 of stream R mod n_empty)-th empty cell in row-major order — each with its local boxes.
+__global__ __launch_bounds__(64) void teacher_walk_rows_kernel(TeacherWalkArgs a) {
+  __shared__ uint16_t s_cells[JN_TWALK_MAX_CELLS];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int Gw = a.Gw, cells = a.Gh * Gw, nb = a.nb;
+  const long long P = a.P;
+  const long long* bb = (const long long*)a.bboxes + (long long)b * nb * 4;
+  const uint8_t* tg = a.targets + (long long)b * cells;
+  int n_pos = 0;
+  for (int c0 = 0; c0 < cells; c0 += 64) {
+    const int c = c0 + lane;
+    const bool t = c < cells && tg[c];
+    const unsigned long long m = __ballot(t);
+    if (t) s_cells[n_pos + __popcll(m & walk_lanes_below(lane))] = (uint16_t)c;
+    n_pos += __popcll(m);
+  }
+  int n_rows = n_pos;
+  if (n_pos < cells) {
+    const uint32_t r = philox4x32(a.seed, (uint32_t)b, 0u, kWalkTagR, 0u).x;
+    const int rank = __builtin_amdgcn_readfirstlane((int)(r % (uint32_t)(cells - n_pos)));
+    int seen = 0;
+    for (int c0 = 0; c0 < cells; c0 += 64) {
+      const int c = c0 + lane;
+      const bool e = c < cells && !tg[c];
+      const unsigned long long m = __ballot(e);
+      const int pc = __popcll(m);
+      if (rank < seen + pc) {
+        const unsigned long long sel = __ballot(e && __popcll(m & walk_lanes_below(lane)) == rank - seen);
+        if (lane == 0) s_cells[n_pos] = (uint16_t)(c0 + __ffsll((long long)sel) - 1);
+        break;
+      }
+      seen += pc;
+    }
+    n_rows = n_pos + 1;
+  }
+  __syncthreads();
+  const int first = a.offsets[b];
+  const int rows = min(first + n_rows, a.capacity) - first;   // this image's rows below the capacity (may be <= 0)
+  for (int r = lane; r < rows; r += 64) {
+    long long* oc = (long long*)a.cells + ((long long)first + r) * 3;
+    const int c = s_cells[r];
+    oc[0] = b; oc[1] = c / Gw; oc[2] = c % Gw;
+  }
+  int n_real = 0;
+  for (int k0 = 0; k0 < nb; k0 += 64) {
+    const int k = k0 + lane;
+    const bool real = k < nb && walk_box_real(bb + 4 * k);
+    const unsigned long long m = __ballot(real);
+    if (real) {
+      const int col = n_real + __popcll(m & walk_lanes_below(lane));
+      const long long q[4] = {bb[4 * k], bb[4 * k + 1], bb[4 * k + 2], bb[4 * k + 3]};
+      for (int r = 0; r < rows; ++r) {
+        const int c = s_cells[r];
+        walk_local_box(q, P, c / Gw, c % Gw, true, a.bboxes_yolox + (((long long)first + r) * nb + col) * 6);
+      }
+    }
+    n_real += __popcll(m);
+  }
+  const int n_pad = nb - n_real;
+  for (long long idx = lane; idx < (long long)max(rows, 0) * n_pad; idx += 64) {
+    float* o = a.bboxes_yolox + (((long long)first + idx / n_pad) * nb + n_real + idx % n_pad) * 6;
+    for (int j = 0; j < 6; ++j) o[j] = 0.f;
+  }
+}
+
+int launch_teacher_walks(const TeacherWalkArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(teacher_walk_kernel, dim3(a.B), dim3(64), sizeof(WalkStep) * (size_t)a.T, s, a);
+  hipLaunchKernelGGL(det_cells_scan_kernel, dim3(1), dim3(kDetThreads), 0, s, a.offsets, a.B);
+  hipLaunchKernelGGL(teacher_walk_rows_kernel, dim3(a.B), dim3(64), 0, s, a);
+  return 0;
+}
+
 }  // namespace jnr

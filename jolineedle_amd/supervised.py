@@ -44,6 +44,7 @@ class SupervisedTrainer:
         self.last_test_metrics = None
         self.iter_num = 0
         self._flat_grads = None
+        self._device_walks = 0          # calls of the device route of generate_trajectories: its default seeds move on
 
     def _grad_arena(self):
         """The engine's flat fp32 gradient arena: owned by the MODEL (one per engine, shared by all trainers)."""
@@ -60,7 +61,7 @@ class SupervisedTrainer:
         return self.detection_augment
 
     def generate_trajectories(self, batch: Dict, position: Optional[Tuple[int, int]] = None, seed: Optional[int] = None,
-                              use_views: bool = True, seed_ties: bool = False) -> Dict:
+                              use_views: bool = True, seed_ties: bool = False, device: Optional[bool] = None) -> Dict:
         """One teacher walk per image of `batch` (``image`` [B, C, H, W] on the device or a list of [C, H, W] of one
         size, ``bboxes`` [B, nb, 4] xyxy with zero-row padding or a list, ``class_id``) -> the collated dict of
         src/supervised.py:95-136: patches [B, T, C, P, P], current_actions / next_actions / labels [B, T],
@@ -70,9 +71,19 @@ class SupervisedTrainer:
         nothing here).  use_views=False leaves the rotations / translations of the config off (``test()`` disables
         both, src/supervised.py:773-774).  seed_ties: with a `seed`, the teacher's choice among equally near targets
         (Python's global ``random`` in the reference and by default here) is drawn from ``random.Random(seed + i)`` too, so
-        that equal seeds give equal walks whatever else drew from the global stream."""
+        that equal seeds give equal walks whatever else drew from the global stream.
+
+        device (None: ``config.device_trajectories``, default False): the walks of the whole batch come from ONE
+        ``trajectory.teacher_walks_device`` call (``jn_teacher_walks``) on the boxes uploaded once, and its positions, masks
+        and detector cells feed the two gathers without a host check.  The rule is ``trajectory.teacher_walks``: the
+        env's walk on two Philox streams of (`seed`, image index) instead of numpy's and Python's, so
+        the walks differ from the host route's; seed=None uses ``config.seed * 1000003 +`` the number of such calls this
+        trainer has made; `seed_ties` has no meaning here (ties always come from the seed).  The box outputs keep the
+        batch's nb columns, the real rows first."""
         from .trajectory import NeedleSimpleEnv, assemble_samples
         cfg = self.config
+        if device is None:
+            device = bool(getattr(cfg, "device_trajectories", False))
         images = batch["image"]
         if not isinstance(images, torch.Tensor):
             images = torch.stack(list(images))
@@ -90,6 +101,8 @@ class SupervisedTrainer:
             boxes = views.transform_bboxes(stack_bboxes(boxes, images.shape[0]))
         self.last_views = views
         height, width = views.canvas if views is not None else images.shape[2:]
+        if device:
+            return self._device_trajectories(batch, images, views, boxes, int(height) // P, int(width) // P, position, seed)
         idx = []
         for i in range(images.shape[0]):
             bb = boxes[i]
@@ -103,6 +116,38 @@ class SupervisedTrainer:
         out = assemble_samples(images, list(range(images.shape[0])), idx, P, views=views)
         cid = batch.get("class_id")
         out["class_id"] = (torch.as_tensor(cid) if cid is not None else torch.zeros(images.shape[0], dtype=torch.long)).to(self.device, torch.long)
+        return out
+
+    def _device_trajectories(self, batch: Dict, images, views, boxes, gh: int, gw: int, position, seed) -> Dict:
+        """The device route of ``generate_trajectories``: `boxes` are the batch's (a tensor or a list) or, with views, the
+        transformed ones on the canvas of gh x gw cells."""
+        from .trajectory import gather_indexed, teacher_walks_device
+        from .views import stack_bboxes
+        cfg, dev = self.config, self.device
+        B, P, T = int(images.shape[0]), int(cfg.patch_size), int(cfg.max_seq_len)
+        self._device_walks += 1
+        if seed is None:
+            seed = int(getattr(cfg, "seed", 0)) * 1000003 + self._device_walks
+        starts = None
+        if position is not None:
+            starts = torch.tensor([[int(position[0]), int(position[1])]] * B, dtype=torch.int64).reshape(B, 2)
+        empty = isinstance(boxes, torch.Tensor) and boxes.numel() == 0
+        bb = (torch.zeros((B, 0, 4), dtype=torch.int64) if empty else stack_bboxes(boxes, B)).to(dev)     # the one upload
+        w = teacher_walks_device(bb, gh, gw, P, T, int(getattr(cfg, "min_keypoints", 0)), int(getattr(cfg, "max_keypoints", 0)),
+                                 bool(getattr(cfg, "binomial_keypoints", False)), seed, start_positions=starts)
+        # masked steps read image -1: zero patches, like the host route's (valid by construction: no host check)
+        image = torch.arange(B, device=dev, dtype=torch.int64)[:, None].expand(B, T)
+        ii = torch.where(w["masks"] > 0, image, torch.full_like(image, -1)).reshape(-1)
+        patches = gather_indexed(images, ii, w["positions"].reshape(-1, 2), P, views=views, _check_positions=False)
+        cells = w["cells_yolox"]
+        out = {"patches": patches.view(B, T, *patches.shape[1:]),
+               "patches_yolox": gather_indexed(images, cells[:, 0].contiguous(), cells[:, 1:].contiguous(), P, views=views,
+                                               _check_positions=False),
+               "bboxes_yolox": w["bboxes_yolox"]}
+        for k in ("current_actions", "next_actions", "positions", "masks", "labels", "local_bboxes"):
+            out[k] = w[k]
+        cid = batch.get("class_id")
+        out["class_id"] = (torch.as_tensor(cid) if cid is not None else torch.zeros(B, dtype=torch.long)).to(dev, torch.long)
         return out
 
     def train_iteration(self, batch: Dict, optimizer_step: bool = True, process_group=None, seed: Optional[int] = None) -> Dict[str, torch.Tensor]:

@@ -379,3 +379,235 @@ def assemble_samples(images: torch.Tensor, image_ids: Sequence[int], indices: Se
         assert B == 1
         out = {k: (v if k in ("patches_yolox", "bboxes_yolox") else v[0]) for k, v in out.items()}
     return out
+
+
+# ---- teacher walks of a whole batch: the host statement of ``jn_teacher_walks`` and its device twin ------------------------
+WALK_TAG_R = 0x54574B52          # third Philox counter word of stream R (the role of NeedleSimpleEnv.rng)
+WALK_TAG_Y = 0x54574B59          # ... of stream Y (the role of py_random: the tie choice among equally near targets)
+MAX_WALK_CELLS = 4096            # JN_TWALK_MAX_CELLS: cells per image the walk kernel keeps in LDS
+MAX_WALK_STEPS = 4096            # JN_TWALK_MAX_T: steps of the kernel's LDS ring
+MAX_WALK_KEYPOINTS = 64          # JN_TWALK_MAX_KEYPOINTS: the kernel's detour table, one lane per detour
+
+
+class PhiloxDraws:
+    """A counter-based stand-in for ``numpy.random.Generator`` / Python's ``random`` in ``NeedleSimpleEnv``: draw k is
+    ``philox4x32(seed; image, k, tag, 0).x`` (csrc/jn_device.h, ``ragged._philox4x32``), k counting the draws made."""
+
+    def __init__(self, seed: int, image: int, tag: int):
+        self.seed, self.image, self.tag, self.k = int(seed) & 0xFFFFFFFFFFFFFFFF, int(image), int(tag), 0
+
+    def draw(self) -> int:
+        from .ragged import _philox4x32
+        r = _philox4x32(self.seed, self.image, self.k, self.tag, 0)[0]
+        self.k += 1
+        return r
+
+    def integers(self, low, high=None, size=None):
+        """lo + r % (hi - lo), one draw; with `size` n draws in order (none for n = 0)."""
+        if high is None:
+            low, high = 0, low
+        low, high = int(low), int(high)
+        if size is None:
+            return low + self.draw() % (high - low)
+        return np.array([low + self.draw() % (high - low) for _ in range(int(size))], dtype=np.int64)
+
+    def choice(self, options):
+        """An int n: r % n.  A list: element r % len of the list sorted (cells: row-major).  One draw either way."""
+        if isinstance(options, (int, np.integer)):
+            return self.draw() % int(options)
+        options = sorted(options)
+        return options[self.draw() % len(options)]
+
+    def binomial(self, n, p=0.5) -> int:
+        """Binomial(n, 1/2) as the set bits among n random bits: ceil(n / 32) draws, draw j supplies bits 32j .. 32j + 31,
+        the last one its low n - 32j bits."""
+        assert p == 0.5, "only the fair coin is a bit count"
+        n, total = int(n), 0
+        for j in range((n + 31) // 32):
+            bits = min(32, n - 32 * j)
+            total += bin(self.draw() & ((1 << bits) - 1)).count("1")
+        return total
+
+
+def _walk_targets(boxes, gh: int, gw: int, P: int) -> np.ndarray:
+    """uint8 [gh, gw]: ``bbox_positions`` of every box on integers — cell (y, x) of the box's own cell range with
+    20 * h * w > P * P (h * w / P**2 > 0.05), plus the cell of its centre; cells outside the grid are dropped."""
+    grid = np.zeros((gh, gw), np.uint8)
+    for x1, y1, x2, y2 in boxes:
+        for y in range(max(y1 // P, 0), min(y2 // P, gh - 1) + 1):
+            for x in range(max(x1 // P, 0), min(x2 // P, gw - 1) + 1):
+                h = min((y + 1) * P, y2) - max(y * P, y1)
+                w = min((x + 1) * P, x2) - max(x * P, x1)
+                if 20 * h * w > P * P:
+                    grid[y, x] = 1
+        cy, cx = ((y1 + y2) // 2) // P, ((x1 + x2) // 2) // P
+        if 0 <= cy < gh and 0 <= cx < gw:
+            grid[cy, cx] = 1
+    return grid
+
+
+def _walk_local_bboxes(boxes, nb: int, P: int, y: int, x: int) -> np.ndarray:
+    """f32 [nb, 6]: ``NeedleSimpleEnv.local_bboxes`` at cell (y, x); the rows past len(boxes) are zero."""
+    out = np.zeros((nb, 6), np.float32)
+    px, py = x * P, y * P
+    for j, (x1, y1, x2, y2) in enumerate(boxes):
+        cx1, cy1, cx2, cy2 = max(px, x1), max(py, y1), min(px + P, x2), min(py + P, y2)
+        if cx1 < cx2 and cy1 < cy2:
+            out[j] = (0, cx1 - px, cy1 - py, cx2 - px, cy2 - py, 1)
+    return out
+
+
+_TOWARDS = (4, 2, 5, 0, 8, 1, 6, 3, 7)      # action id at [(sign dy + 1) * 3 + sign dx + 1] (csrc/jn_device.h: kTowards)
+_DELTA_Y = (0, 0, -1, 1, -1, -1, 1, 1, 0)
+_DELTA_X = (-1, 1, 0, 0, -1, 1, -1, 1, 0)
+
+
+def teacher_walks(bboxes, gh: int, gw: int, P: int, T: int, min_keypoints: int, max_keypoints: int,
+                  binomial_keypoints: bool, seed: int, start_positions=None) -> Dict[str, torch.Tensor]:
+    """The teacher walks of a whole batch on plain integers: the host statement of the rule ``jn_teacher_walks``
+    computes (include/jnroll.h) — ``NeedleSimpleEnv.generate_sample_indices`` with its two random sources replaced by the
+    Philox streams of ``PhiloxDraws`` (R, tag ``WALK_TAG_R``, for ``rng``; Y, tag ``WALK_TAG_Y``, for the tie choice, which
+    picks among the nearest cells in row-major order), per image b of `seed`.  bboxes [B, nb, 4] xyxy int64, nb >= 0; an
+    all-zero row is padding and is skipped, column j of every box output is the j-th non-zero row.  start_positions
+    [B, 2] (y, x) replaces the random start.  Draw order of R: the negative detector cell (if the image has an empty
+    cell), the start (y, x), the one random keypoint (y, x) when nothing is left to visit, the number of detours, their
+    places, then the detours (binomial: x before y) and STOP replacements as the walk meets them.
+
+    Returns on the CPU: positions int64 [B, T, 2], current_actions / next_actions / labels int64 [B, T], masks f32 [B, T],
+    local_bboxes f32 [B, T, nb, 6], n_steps int32 [B] (the walk's length before the cut to its last T steps), targets
+    uint8 [B, gh, gw], cells_yolox int64 [M, 3] = (image, y, x) — per image its target cells in row-major order, then the
+    one negative cell — bboxes_yolox f32 [M, nb, 6] and offsets int32 [B + 1]."""
+    gh, gw, P, T = int(gh), int(gw), int(P), int(T)
+    bb = np.asarray(bboxes.detach().cpu() if isinstance(bboxes, torch.Tensor) else bboxes, dtype=np.int64)
+    assert bb.ndim == 3 and bb.shape[2] == 4, "bboxes are [B, nb, 4]"
+    B, nb = bb.shape[0], bb.shape[1]
+    assert gh >= 1 and gw >= 1 and P >= 1 and T >= 1 and 0 <= int(min_keypoints) <= int(max_keypoints)
+    starts = None
+    if start_positions is not None:
+        starts = np.asarray(torch.as_tensor(start_positions).cpu(), dtype=np.int64).reshape(B, 2)
+        assert ((starts >= 0) & (starts < np.array([gh, gw]))).all(), "start position outside the grid"
+    out = {"positions": np.zeros((B, T, 2), np.int64), "current_actions": np.zeros((B, T), np.int64),
+           "next_actions": np.zeros((B, T), np.int64), "labels": np.zeros((B, T), np.int64),
+           "masks": np.zeros((B, T), np.float32), "local_bboxes": np.zeros((B, T, nb, 6), np.float32),
+           "n_steps": np.zeros((B,), np.int32), "targets": np.zeros((B, gh, gw), np.uint8)}
+    cells_yolox, bboxes_yolox, offsets = [], [], [0]
+    for b in range(B):
+        boxes = [tuple(int(v) for v in row) for row in bb[b] if any(int(v) != 0 for v in row)]
+        R, Y = PhiloxDraws(seed, b, WALK_TAG_R), PhiloxDraws(seed, b, WALK_TAG_Y)
+        target = _walk_targets(boxes, gh, gw, P)
+        out["targets"][b] = target
+        flat = target.reshape(-1)
+        rows = [int(c) for c in np.flatnonzero(flat)]
+        empty = [int(c) for c in np.flatnonzero(flat == 0)]
+        if empty:
+            rows.append(empty[R.draw() % len(empty)])
+        for c in rows:
+            cells_yolox.append((b, c // gw, c % gw))
+            bboxes_yolox.append(_walk_local_bboxes(boxes, nb, P, c // gw, c % gw))
+        offsets.append(offsets[-1] + len(rows))
+
+        if starts is None:
+            y = R.draw() % gh
+            x = R.draw() % gw
+        else:
+            y, x = int(starts[b, 0]), int(starts[b, 1])
+        todo = flat.copy()
+        todo[y * gw + x] = 0
+        n_keypoints = int(todo.sum())
+        random_keypoint = None
+        if n_keypoints == 0:
+            ky = R.draw() % gh
+            random_keypoint = (ky, R.draw() % gw)
+            n_keypoints = 1
+        n_extra = int(min_keypoints) + R.draw() % (int(max_keypoints) + 1 - int(min_keypoints))
+        insert_at = [R.draw() % n_keypoints for _ in range(n_extra)]
+        steps = [[0, 0, y, x, int(flat[y * gw + x])]]            # action taken, teacher action, y, x, label
+
+        def towards(ty, tx):
+            a = _TOWARDS[((ty > y) - (ty < y) + 1) * 3 + (tx > x) - (tx < x) + 1]
+            return R.draw() % 8 if a == 8 else a, a
+
+        for kid in range(n_keypoints):
+            if random_keypoint is not None:
+                ky, kx = random_keypoint
+            else:
+                left = np.flatnonzero(todo)
+                dist = np.abs(left // gw - y) + np.abs(left % gw - x)
+                nearest = left[dist == dist.min()]               # row-major
+                c = int(nearest[Y.draw() % len(nearest)])
+                todo[c] = 0
+                ky, kx = c // gw, c % gw
+            steps[-1][1] = towards(ky, kx)[0]
+            for _ in range(insert_at.count(kid)):                # each detour is walked before the next one is drawn
+                if binomial_keypoints:
+                    dx = R.binomial(gw) - gw // 2
+                    dy = R.binomial(gh) - gh // 2
+                    ty, tx = (ky + dy) % gh, (kx + dx) % gw
+                else:
+                    ty = R.draw() % gh
+                    tx = R.draw() % gw
+                while (y, x) != (ty, tx):
+                    _, a = towards(ty, tx)
+                    y, x = y + _DELTA_Y[a], x + _DELTA_X[a]
+                    steps.append([a, towards(ky, kx)[0], y, x, int(flat[y * gw + x])])
+            while (y, x) != (ky, kx):
+                _, a = towards(ky, kx)
+                y, x = y + _DELTA_Y[a], x + _DELTA_X[a]
+                steps.append([a, towards(ky, kx)[0], y, x, int(flat[y * gw + x])])
+
+        out["n_steps"][b] = len(steps)
+        for i, (a, best, sy, sx, lab) in enumerate(steps[-T:]):
+            out["current_actions"][b, i], out["next_actions"][b, i], out["labels"][b, i] = a, best, lab
+            out["positions"][b, i] = (sy, sx)
+            out["masks"][b, i] = 1.0
+            out["local_bboxes"][b, i] = _walk_local_bboxes(boxes, nb, P, sy, sx)
+    out = {k: torch.from_numpy(v) for k, v in out.items()}
+    out["cells_yolox"] = torch.tensor(cells_yolox, dtype=torch.int64).reshape(-1, 3)
+    out["bboxes_yolox"] = torch.from_numpy(np.stack(bboxes_yolox) if bboxes_yolox else np.zeros((0, nb, 6), np.float32))
+    out["offsets"] = torch.tensor(offsets, dtype=torch.int32)
+    return out
+
+
+def teacher_walks_device(bboxes: torch.Tensor, gh: int, gw: int, P: int, T: int, min_keypoints: int, max_keypoints: int,
+                         binomial_keypoints: bool, seed: int, start_positions=None) -> Dict[str, torch.Tensor]:
+    """``teacher_walks`` on the device (``jn_teacher_walks``: three launches, no Python loop): bboxes [B, nb, 4] on the
+    GPU; the same dict with every tensor on the device except ``offsets``, which is read back once — the one
+    synchronisation, for the number of detector rows.  The detector buffers hold B * gh * gw rows, which always suffices.
+    start_positions given on the host are checked on the host; given on the device they are read back for the check (a
+    second synchronisation).  Beyond ``MAX_WALK_CELLS`` cells, ``MAX_WALK_STEPS`` steps or ``MAX_WALK_KEYPOINTS`` detours
+    the entry point refuses."""
+    from . import _lib
+    from ._lib import check, ptr
+    if not bboxes.is_cuda:
+        raise RuntimeError("teacher_walks_device needs the boxes on the GPU (teacher_walks is the host function)")
+    dev = bboxes.device
+    bb = bboxes.to(torch.int64).contiguous()
+    assert bb.dim() == 3 and bb.shape[2] == 4, "bboxes are [B, nb, 4]"
+    B, nb = int(bb.shape[0]), int(bb.shape[1])
+    gh, gw, T = int(gh), int(gw), int(T)
+    starts = None
+    if start_positions is not None:
+        sp = torch.as_tensor(start_positions).to(torch.int64).reshape(B, 2)
+        host = sp.cpu()
+        assert bool(((host >= 0) & (host < torch.tensor([gh, gw]))).all()), "start position outside the grid"
+        starts = sp.to(dev).contiguous()
+    cap = B * max(gh, 0) * max(gw, 0)
+    Tn = max(T, 0)
+    i64 = lambda *shape: torch.empty(shape, device=dev, dtype=torch.int64)
+    out = {"positions": i64(B, Tn, 2), "current_actions": i64(B, Tn), "next_actions": i64(B, Tn), "labels": i64(B, Tn),
+           "masks": torch.empty((B, Tn), device=dev, dtype=torch.float32),
+           "local_bboxes": torch.empty((B, Tn, nb, 6), device=dev, dtype=torch.float32),
+           "n_steps": torch.empty((B,), device=dev, dtype=torch.int32),
+           "targets": torch.empty((B, max(gh, 0), max(gw, 0)), device=dev, dtype=torch.uint8),
+           "cells_yolox": i64(cap, 3), "bboxes_yolox": torch.empty((cap, nb, 6), device=dev, dtype=torch.float32),
+           "offsets": torch.empty((B + 1,), device=dev, dtype=torch.int32)}
+    names = ("positions", "current_actions", "next_actions", "labels", "masks", "local_bboxes", "n_steps", "targets",
+             "cells_yolox", "bboxes_yolox", "offsets")
+    check(_lib.load_library().jn_teacher_walks(ptr(bb), ptr(starts), B, nb, gh, gw, int(P), T, int(min_keypoints),
+                                               int(max_keypoints), int(bool(binomial_keypoints)),
+                                               int(seed) & 0xFFFFFFFFFFFFFFFF, cap, *(ptr(out[k]) for k in names),
+                                               _lib.current_stream(dev)), "jn_teacher_walks")
+    out["offsets"] = out["offsets"].cpu()
+    n = int(out["offsets"][B])
+    out["cells_yolox"], out["bboxes_yolox"] = out["cells_yolox"][:n], out["bboxes_yolox"][:n]
+    return out
