@@ -274,6 +274,12 @@ int jn_merge_boxes(const float* boxes_dev, const int32_t* counts_dev, int B, int
 int jn_yolox_loss(const float* raw_dev, const float* targets_dev, int N, int nb, int P, int stride0, int stride1,
                   int stride2, int use_l1, float loss_scale, float* d_raw_dev, float* metrics_dev, float* scale_dev,
                   void* stream);
+/* jn_yolox_loss over EVERY box of a patch: same arguments, same outputs, always the wide kernel (for any nb >= 1), so
+ * a patch may hold up to nb boxes and none is cut.  JN_EINVAL in addition, before anything is launched: nb >
+ * JN_DETLOSS_MAX_BOXES, A > 8400 (P above 640 at strides 8 / 16 / 32).  Two calls on the same input give the same bits. */
+int jn_yolox_loss_wide(const float* raw_dev, const float* targets_dev, int N, int nb, int P, int stride0, int stride1,
+                       int stride2, int use_l1, float loss_scale, float* d_raw_dev, float* metrics_dev, float* scale_dev,
+                       void* stream);
 /* The detector's threshold / sort / NMS stage on given decoded predictions, context-free: what jn_detect runs behind
  * the head (the published postprocess with class_agnostic = True and one class, then clamp_(0, P - 1);
  * src/models/yolox.py:80-113, restated in oracle/yolox_ref.py::postprocess).  raw_dev [N,A,6] f32 = decoded rows
@@ -541,13 +547,25 @@ int jn_set_det_candidates(jn_ctx* ctx, int all);
  * (NeedleGeneralEnv.get_detection_batch layout).  loss_scale multiplies the loss before backward
  * (1 / gradient_accumulation).  metrics_dev: float32[8] = total_loss, iou_loss (x5), conf_loss, cls_loss, l1_loss,
  * num_fg (foreground anchors per ground-truth box).
- * Box cap: a patch's boxes are its first ng rows, ng = the number of rows with a positive sum (as published); the loss
- * kernel holds 8 of them in LDS, and a patch with ng > 8 is cut to its first 8 rows WITHOUT an error (the reference uses
- * them all; num_fg then counts 8).  nb > 8 is accepted and exact as long as no patch has more than 8 such rows.  The
- * Python wrappers refuse such a batch (ValueError); a C caller checks its own targets.  Holds for jn_detector_forward
- * and jn_yolox_loss too. */
+ * Box cap: a patch's boxes are its first ng rows, ng = the number of rows with a positive sum (as published).  Two
+ * policies, chosen by jn_set_det_loss_boxes:
+ * - the default (all = 0): the loss kernel holds 8 boxes in LDS, and a patch with ng > 8 is cut to its first 8 rows
+ *   WITHOUT an error (the reference uses them all; num_fg then counts 8).  nb > 8 is accepted and exact as long as no
+ *   patch has more than 8 such rows.  The Python wrappers refuse such a batch (ValueError); a C caller checks its own
+ *   targets.  jn_yolox_loss is this policy.
+ * - all != 0: every box is used, as the reference does.  A call with nb > 8 runs the wide kernel (jn_yolox_loss_wide),
+ *   which has no cap: nothing is ever cut.  Its capacity is checked before anything is launched: nb >
+ *   JN_DETLOSS_MAX_BOXES is JN_EINVAL.  A call with nb <= 8 runs the default kernel, which cannot cut it.
+ * Holds for jn_detector_forward and jn_detector_eval_loss too. */
 int jn_detector_step(jn_ctx* ctx, const float* patches_dev, int N, const float* targets_dev, int nb,
                      float loss_scale, float* metrics_dev, void* stream);
+/* Rows of `targets` the wide detector loss accepts per patch (its boxes and candidate lists share 160 KB of LDS). */
+#define JN_DETLOSS_MAX_BOXES 1024
+/* Box policy of the detector loss wherever `ctx` computes it: jn_detector_step, jn_detector_forward,
+ * jn_detector_eval_loss.  all = 0 (the default): at most 8 boxes per patch, see jn_detector_step.  all != 0: every box
+ * of a patch takes part in the SimOTA assignment, which is the published loss.  Sticky until set again.  JN_ESTATE: the
+ * context has no detector.  JN_EINVAL: all != 0 and the detector has more than 8400 anchors (a patch size above 640). */
+int jn_set_det_loss_boxes(jn_ctx* ctx, int all);
 /* Detector autograd bridge — NeedleYOLOX.forward(patches, targets) (src/models/yolox.py:24-91) as the two halves of
  * jn_detector_step around the CALLER's autograd, so that the reference's loop runs as written (src/reinforce.py:330-341:
  * `_, _, yolo_loss = yolox(patches_yolox, bboxes_yolox); loss += yolo_loss["total_loss"]; (loss / ga).backward()`; the

@@ -101,6 +101,8 @@ SIGNATURES = {
                                  C.c_void_p, C.c_void_p]),
     "jn_yolox_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "jn_yolox_loss_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "jn_postprocess": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
     "jn_postprocess_all": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
@@ -138,6 +140,7 @@ SIGNATURES = {
                                  C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "jn_detect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "jn_set_det_candidates": (C.c_int, [C.c_void_p, C.c_int]),
+    "jn_set_det_loss_boxes": (C.c_int, [C.c_void_p, C.c_int]),
     "jn_rollout": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int,
                              C.POINTER(JnRolloutOut), C.c_void_p]),
     "jn_set_rollout_positions": (C.c_int, [C.c_void_p, C.c_int]),

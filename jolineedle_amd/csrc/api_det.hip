@@ -42,6 +42,18 @@ static void det_postprocess(jn_ctx* ctx, int N, float* boxes_dev, int32_t* count
                                                                c.max_det_per_patch, nullptr, s);
 }
 
+// rows of `targets` the default loss kernel can never cut (its DL_MAXG)
+constexpr int DET_LOSS_CAP = 8;
+
+// the SimOTA loss of N patches under the context's box policy (jn_set_det_loss_boxes): the wide kernel only where a
+// patch could hold more boxes than the default kernel keeps, so every nb <= 8 result is the default kernel's
+static int det_loss(jn_ctx* ctx, int N, int nb, const DetGeom& geo, float* d_raw, float* acc, float loss_scale,
+                    float* metrics_dev, float* scale_dev, hipStream_t s) {
+  const bool wide = ctx->det_loss_all && nb > DET_LOSS_CAP;
+  return (wide ? launch_yolox_loss_wide : launch_yolox_loss)(ctx->det_logits, ctx->det_labels, N, nb, geo, d_raw, acc, 1,
+                                                             loss_scale, metrics_dev, scale_dev, s);
+}
+
 int detect_impl(jn_ctx* ctx, const StemSrc& ss, int N, float* boxes_dev, int32_t* counts_dev, float* raw_dev,
                 const int* skip_flag, int skip_when, hipStream_t s) {
   Net& net = ctx->nets[JN_NET_DETECTOR];
@@ -64,6 +76,8 @@ static int detector_forward_impl(jn_ctx* ctx, const float* patches_dev, int N, c
   JN_CHECK(ctx->weights_loaded, JN_ESTATE, "jn_load_weights has not been called");
   JN_CHECK(N >= 1 && N <= ctx->cfg.max_batch, JN_EINVAL, "N=%d exceeds max_batch=%d", N, ctx->cfg.max_batch);
   JN_CHECK(nb >= 1, JN_EINVAL, "targets need at least one (padding) row per patch");
+  JN_CHECK(!ctx->det_loss_all || nb <= JN_DETLOSS_MAX_BOXES, JN_EINVAL,
+           "targets have nb=%d rows per patch, the detector loss takes at most JN_DETLOSS_MAX_BOXES=%d", nb, JN_DETLOSS_MAX_BOXES);
   JN_CHECK(n_pass >= 1 && n_pass <= 64 && pass >= 0 && pass < n_pass, JN_EINVAL, "detector pass %d of %d", pass, n_pass);
   JN_CHECK(ctx->cfg.act_dtype == JN_F32, JN_ESTATE, "training needs act_dtype = fp32 (bf16 is the inference mode)");
   JN_HIP(hipSetDevice(ctx->cfg.device));
@@ -96,7 +110,8 @@ static int detector_forward_impl(jn_ctx* ctx, const float* patches_dev, int N, c
     if (op.kind != OP_PRED) continue;
     geo.a0[op.level] = op.anchor0; geo.H[op.level] = op.in.H; geo.W[op.level] = op.in.W; geo.stride[op.level] = op.stride;
   }
-  launch_yolox_loss(ctx->det_logits, ctx->det_labels, N, nb, geo, dp.dlogits, dp.acc + 8, 1, loss_scale, metrics_dev, dp.acc, s);
+  rc = det_loss(ctx, N, nb, geo, dp.dlogits, dp.acc + 8, loss_scale, metrics_dev, dp.acc, s);
+  JN_CHECK(rc == 0, JN_EINVAL, "detector loss: nb=%d or A=%d is beyond the wide kernel's capacity", nb, A);
   JN_HIP(hipGetLastError());
   dp.patches = patches_dev; dp.N = N; dp.valid = true;
   return JN_OK;
@@ -184,6 +199,17 @@ int jn_set_det_candidates(jn_ctx* ctx, int all) {
   return JN_OK;
 }
 
+int jn_set_det_loss_boxes(jn_ctx* ctx, int all) {
+  JN_CHECK(ctx, JN_EINVAL, "jn_set_det_loss_boxes: null ctx");
+  JN_CHECK(ctx->has_net[JN_NET_DETECTOR], JN_ESTATE, "context was created without a detector");
+  const int A = ctx->nets[JN_NET_DETECTOR].n_anchors;
+  JN_CHECK(!all || A <= DETLOSS_WIDE_MAX_A, JN_EINVAL,
+           "jn_set_det_loss_boxes: the detector has A=%d anchors at patch size %d, the kernel holds at most %d in LDS", A,
+           ctx->cfg.patch_size, DETLOSS_WIDE_MAX_A);
+  ctx->det_loss_all = all != 0;
+  return JN_OK;
+}
+
 int jn_detector_step(jn_ctx* ctx, const float* patches_dev, int N, const float* targets_dev, int nb, float loss_scale,
                      float* metrics_dev, void* stream) {
   hipStream_t s = (hipStream_t)stream;
@@ -239,6 +265,8 @@ int jn_detector_eval_loss(jn_ctx* ctx, const float* patches_dev, int N, const fl
   JN_CHECK(ctx->weights_loaded, JN_ESTATE, "jn_load_weights has not been called");
   JN_CHECK(N >= 1 && N <= ctx->cfg.max_batch, JN_EINVAL, "N=%d exceeds max_batch=%d", N, ctx->cfg.max_batch);
   JN_CHECK(nb >= 1, JN_EINVAL, "targets need at least one (padding) row per patch");
+  JN_CHECK(!ctx->det_loss_all || nb <= JN_DETLOSS_MAX_BOXES, JN_EINVAL,
+           "targets have nb=%d rows per patch, the detector loss takes at most JN_DETLOSS_MAX_BOXES=%d", nb, JN_DETLOSS_MAX_BOXES);
   JN_CHECK(ctx->cfg.act_dtype == JN_F32, JN_ESTATE, "the detector loss needs act_dtype = fp32 (bf16 is the inference mode)");
   Net& net = ctx->nets[JN_NET_DETECTOR];
   JN_CHECK(net.n_backbone_ops >= 0, JN_ESTATE, "detector without a head");
@@ -277,8 +305,8 @@ int jn_detector_eval_loss(jn_ctx* ctx, const float* patches_dev, int N, const fl
     if (op.kind != OP_PRED) continue;
     geo.a0[op.level] = op.anchor0; geo.H[op.level] = op.in.H; geo.W[op.level] = op.in.W; geo.stride[op.level] = op.stride;
   }
-  launch_yolox_loss(ctx->det_logits, ctx->det_labels, N, nb, geo, ctx->det_eval_dlogits, ctx->det_eval_acc + 8, 1, 1.0f, metrics_dev,
-                    ctx->det_eval_acc, s);
+  rc = det_loss(ctx, N, nb, geo, ctx->det_eval_dlogits, ctx->det_eval_acc + 8, 1.0f, metrics_dev, ctx->det_eval_acc, s);
+  JN_CHECK(rc == 0, JN_EINVAL, "detector loss: nb=%d or A=%d is beyond the wide kernel's capacity", nb, A);
   if (boxes_dev && counts_dev) {
     // head, eval, on the same maps: run_net rebuilds the whole table from the running statistics first (the backbone's
     // entries come out as they were, the head's from the statistics the pass above has just moved)
@@ -289,33 +317,55 @@ int jn_detector_eval_loss(jn_ctx* ctx, const float* patches_dev, int N, const fl
   return JN_OK;
 }
 
-int jn_yolox_loss(const float* raw_dev, const float* targets_dev, int N, int nb, int P, int stride0, int stride1,
-                  int stride2, int use_l1, float loss_scale, float* d_raw_dev, float* metrics_dev, float* scale_dev,
-                  void* stream) {
-  JN_CHECK(raw_dev && targets_dev && d_raw_dev && metrics_dev && scale_dev, JN_EINVAL, "jn_yolox_loss: null argument");
-  JN_CHECK(N >= 1, JN_EINVAL, "jn_yolox_loss: N=%d", N);
-  JN_CHECK(nb >= 1, JN_EINVAL, "jn_yolox_loss: targets need at least one (padding) row per patch");
-  JN_CHECK(P >= 32 && P % 32 == 0, JN_EINVAL, "jn_yolox_loss: patch size %d is not a multiple of 32", P);
+// jn_yolox_loss / jn_yolox_loss_wide: the loss of given predictor outputs with the default or the wide kernel
+static int yolox_loss_entry(const char* who, bool wide, const float* raw_dev, const float* targets_dev, int N, int nb, int P,
+                            int stride0, int stride1, int stride2, int use_l1, float loss_scale, float* d_raw_dev,
+                            float* metrics_dev, float* scale_dev, void* stream) {
+  JN_CHECK(raw_dev && targets_dev && d_raw_dev && metrics_dev && scale_dev, JN_EINVAL, "%s: null argument", who);
+  JN_CHECK(N >= 1, JN_EINVAL, "%s: N=%d", who, N);
+  JN_CHECK(nb >= 1, JN_EINVAL, "%s: targets need at least one (padding) row per patch", who);
+  JN_CHECK(P >= 32 && P % 32 == 0, JN_EINVAL, "%s: patch size %d is not a multiple of 32", who, P);
   const int strides[3] = {stride0, stride1, stride2};
   // the geometry detector_forward_impl reads off the three predictor ops: level l is (P / stride)^2 anchors behind level l - 1
   DetGeom geo{};
   for (int l = 0; l < 3; ++l) {
     JN_CHECK(strides[l] >= 1 && P % strides[l] == 0 && (l == 0 || strides[l] > strides[l - 1]), JN_EINVAL,
-             "jn_yolox_loss: strides %d, %d, %d do not ascend or do not divide patch size %d", stride0, stride1, stride2, P);
+             "%s: strides %d, %d, %d do not ascend or do not divide patch size %d", who, stride0, stride1, stride2, P);
     geo.a0[l] = geo.A; geo.H[l] = geo.W[l] = P / strides[l]; geo.stride[l] = strides[l];
     geo.A += geo.H[l] * geo.W[l];
+  }
+  if (wide) {
+    JN_CHECK(nb <= JN_DETLOSS_MAX_BOXES, JN_EINVAL, "%s: targets have nb=%d rows per patch, at most JN_DETLOSS_MAX_BOXES=%d", who,
+             nb, JN_DETLOSS_MAX_BOXES);
+    JN_CHECK(geo.A <= DETLOSS_WIDE_MAX_A, JN_EINVAL, "%s: A=%d anchors at patch size %d, the kernel holds at most %d in LDS", who,
+             geo.A, P, DETLOSS_WIDE_MAX_A);
   }
   hipStream_t s = (hipStream_t)stream;
   float* work = nullptr;                                         // cxcywh labels, then the per-patch sums
   const size_t n_lab = (size_t)N * nb * 5;
   JN_HIP(hipMalloc((void**)&work, (n_lab + (size_t)8 * N) * sizeof(float)));
   hipLaunchKernelGGL(labels_to_cxcywh_kernel, dim3((N * nb + 255) / 256), dim3(256), 0, s, targets_dev, work, N * nb);
-  launch_yolox_loss(raw_dev, work, N, nb, geo, d_raw_dev, work + n_lab, use_l1, loss_scale, metrics_dev, scale_dev, s);
+  (wide ? launch_yolox_loss_wide : launch_yolox_loss)(raw_dev, work, N, nb, geo, d_raw_dev, work + n_lab, use_l1, loss_scale,
+                                                      metrics_dev, scale_dev, s);
   const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(s);
   (void)hipFree(work);
   JN_HIP(e1);
   JN_HIP(e2);
   return JN_OK;
+}
+
+int jn_yolox_loss(const float* raw_dev, const float* targets_dev, int N, int nb, int P, int stride0, int stride1,
+                  int stride2, int use_l1, float loss_scale, float* d_raw_dev, float* metrics_dev, float* scale_dev,
+                  void* stream) {
+  return yolox_loss_entry("jn_yolox_loss", false, raw_dev, targets_dev, N, nb, P, stride0, stride1, stride2, use_l1, loss_scale,
+                          d_raw_dev, metrics_dev, scale_dev, stream);
+}
+
+int jn_yolox_loss_wide(const float* raw_dev, const float* targets_dev, int N, int nb, int P, int stride0, int stride1,
+                       int stride2, int use_l1, float loss_scale, float* d_raw_dev, float* metrics_dev, float* scale_dev,
+                       void* stream) {
+  return yolox_loss_entry("jn_yolox_loss_wide", true, raw_dev, targets_dev, N, nb, P, stride0, stride1, stride2, use_l1,
+                          loss_scale, d_raw_dev, metrics_dev, scale_dev, stream);
 }
 
 }  // extern "C"

@@ -301,6 +301,7 @@ struct jn_ctx {
   bool last_stop_early = true;
   bool pos_by_token = false;      // jn_set_rollout_positions: the token of step t gets 1-D position t (eval rollouts only)
   bool det_all = false;           // jn_set_det_candidates: every passing anchor reaches the NMS (launch_postprocess_all)
+  bool det_loss_all = false;      // jn_set_det_loss_boxes: targets wider than 8 rows go to launch_yolox_loss_wide
   // jn_set_rollout_teacher: armed while teacher_sets is set; caller-owned [B,T] bytes and [B,Gh,Gw] grid (null = bbox_masks)
   uint8_t* teacher_sets = nullptr; const uint8_t* teacher_targets = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};

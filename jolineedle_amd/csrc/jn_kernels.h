@@ -193,6 +193,11 @@ struct DetGeom { int A; int a0[3]; int H[3]; int W[3]; int stride[3]; };
 // acc: [N][8] floats of scratch, one row of sums per patch (written, not accumulated: nothing to clear)
 int launch_yolox_loss(const float* raw, const float* labels, int N, int nb, const DetGeom& geo, float* d_raw, float* acc,
                       int use_l1, float loss_scale, float* metrics, float* scale, hipStream_t s);
+// The same loss over every box of a patch (yolox_loss_wide_kernel: no 8-box cap, no ng x nc matrix).  geo.A <=
+// DETLOSS_WIDE_MAX_A and nb <= JN_DETLOSS_MAX_BOXES, else nothing is launched and the return value is non-zero.
+constexpr int DETLOSS_WIDE_MAX_A = 8400;                // 640 px at strides 8 / 16 / 32
+int launch_yolox_loss_wide(const float* raw, const float* labels, int N, int nb, const DetGeom& geo, float* d_raw, float* acc,
+                           int use_l1, float loss_scale, float* metrics, float* scale, hipStream_t s);
 int launch_head_pred_bwd(const float* d_raw, const float* scale, const void* reg, int reg_ld, ChanTab rt, const void* cls,
                          int cls_ld, ChanTab ct, int dtype, const float* wp, float* g_reg, float* g_cls, float* g_wp,
                          float* g_bp, int hid, int HW, int A, int a0, int N, hipStream_t s);

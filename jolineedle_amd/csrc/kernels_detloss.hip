@@ -6,6 +6,8 @@
 // One workgroup per patch: a patch has <= 27 candidate anchors per ground-truth box (3 x 3 cells x 3 levels).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "jn_kernels.h"
 #include "jn_types.h"
 
@@ -22,7 +24,8 @@ __device__ __forceinline__ f32x4 tf4_d(f32x4 z, f32x4 sc, f32x4 sh, f32x4 fl) {
 }
 
 // A patch with more boxes than DL_MAXG is cut to its first DL_MAXG rows (the reference uses them all): documented at
-// jn_detector_step in include/jnroll.h, refused by the Python wrappers (yolox.py::check_box_cap).
+// jn_detector_step in include/jnroll.h, refused by the Python wrappers (yolox.py::check_box_cap).  That is the default
+// box policy; yolox_loss_wide_kernel below, the opt-in one, takes every box.
 constexpr int DL_MAXG = 8;          // ground-truth boxes per patch
 // A box has at most 3 x 3 cells x 3 levels = 27 candidates, so DL_MAXG boxes give at most 216: the cap is never reached
 // and the `pos < DL_MAXC` / min(DL_MAXC, ...) guards below never drop a candidate.  Raise it with DL_MAXG (27 per box).
@@ -41,6 +44,11 @@ __device__ __forceinline__ float iou_cxcywh(const DlBox& a, const DlBox& b) {
   const float inter = (brx - tlx) * (bry - tly) * en;
   return inter / (a.w * a.h + b.w * b.h - inter);
 }
+
+template <typename IouFn>
+__device__ __forceinline__ void dl_loss_terms(const float* __restrict__ r, float* __restrict__ dr, const DetGeom& geo,
+                                              const DlBox* gt, const int* cand, const int* c_gt, int nc, int ng, int use_l1,
+                                              float (*part)[5], float* __restrict__ out, IouFn matched_iou);
 
 // acc [N][8]: the sums of patch n in row n, [0] iou loss, [1] obj loss, [2] cls loss, [3] l1 loss, [4] num_fg, [5] num_gt
 // (floats).  No atomics: lanes, waves and (in the finalize kernel) patches are summed in a fixed order, so the metrics
@@ -165,6 +173,23 @@ __global__ __launch_bounds__(256) void yolox_loss_kernel(const float* __restrict
     c_gt[c] = cnt == 0 ? -1 : (cnt == 1 ? first : amin);
   }
   __syncthreads();
+  dl_loss_terms(r, dr, geo, gt, cand, c_gt, nc, ng, use_l1, part, acc + (long long)n * 8,
+                [&](int g, int c, const DlBox&, const DlBox&) { return ious[g][c]; });
+}
+
+// The loss terms of one patch once every candidate has its box (c_gt[c], -1 = background): shared by the two kernels.
+// matched_iou(g, c, gt box, predicted box) is the class target of a foreground candidate, its IoU with its match.
+template <typename IouFn>
+__device__ __forceinline__ void dl_loss_terms(const float* __restrict__ r, float* __restrict__ dr, const DetGeom& geo,
+                                              const DlBox* gt, const int* cand, const int* c_gt, int nc, int ng, int use_l1,
+                                              float (*part)[5], float* __restrict__ out, IouFn matched_iou) {
+  const int tid = threadIdx.x, A = geo.A;
+  auto level_of = [&](int a, int& gx, int& gy, float& st) {
+    int l = 0;
+    while (l < 2 && a >= geo.a0[l + 1]) ++l;
+    const int p = a - geo.a0[l];
+    gx = p % geo.W[l]; gy = p / geo.W[l]; st = (float)geo.stride[l];
+  };
   // ---- objectness over all anchors (target 1 on foreground anchors), zero the other gradients ----
   float l_obj = 0.0f;
   for (int a = tid; a < A; a += 256) {
@@ -215,7 +240,7 @@ __global__ __launch_bounds__(256) void yolox_loss_kernel(const float* __restrict
     const float g_w = k_l * d_iou(di_w, ph), g_h = k_l * d_iou(di_h, pw);
     d[0] += g_cx * st; d[1] += g_cy * st; d[2] += g_w * pw; d[3] += g_h * ph;
     // class BCE-with-logits against the (detached) IoU of the match
-    const float tc = ious[g][c];
+    const float tc = matched_iou(g, c, t, DlBox{pcx, pcy, pw, ph});
     l_cls += softplus(o[5]) - tc * o[5];
     d[5] += sigm(o[5]) - tc;
     if (use_l1) {
@@ -235,9 +260,176 @@ __global__ __launch_bounds__(256) void yolox_loss_kernel(const float* __restrict
     if ((tid & 63) == 0) part[tid >> 6][j] = v[j];
   }
   __syncthreads();
-  float* out = acc + (long long)n * 8;
   if (tid < 5) out[tid] = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
   if (tid == 5) out[5] = (float)ng;
+}
+
+// ---- the same loss over EVERY box of a patch (opt-in: jn_set_det_loss_boxes, jn_yolox_loss_wide) ---------------------
+// No ng x nc matrix: a wave owns a box, streams the candidates forming IoU and cost on the fly, and keeps what SimOTA
+// needs of them — the ten largest IoUs and the ten cheapest (cost, candidate) pairs, first per lane, then merged over
+// the wave by repeated extraction.  Dynamic k <= 10, so a box's matches go straight into two integer LDS counters per
+// candidate (claims, lowest claiming box): integer atomics, the result does not depend on their order.  A candidate
+// claimed more than once recomputes its cost against all ng boxes.  Dynamic LDS, sized by the host:
+//   DlBox gt[nb] | int cand[cmax] | int c_cnt[cmax] | int c_gt[cmax],  cmax = min(A, 27 * nb) >= nc
+// (a box has at most 3 x 3 cells x 3 levels of candidates), at most 16 * 1024 + 12 * 8400 = 117,184 B.
+constexpr int DLW_TOP = 10;                     // top-k of the IoU sum and the bound of dynamic k
+
+struct DlPair { float iou, cost; };
+
+// IoU and SimOTA cost of box g against anchor a: the expressions of yolox_loss_kernel's pairwise loop
+__device__ __forceinline__ DlPair dlw_pair(const float* __restrict__ r, const DetGeom& geo, const DlBox& g, int a) {
+  int l = 0;
+  while (l < 2 && a >= geo.a0[l + 1]) ++l;
+  const int p = a - geo.a0[l], gx = p % geo.W[l], gy = p / geo.W[l];
+  const float st = (float)geo.stride[l];
+  const float* o = r + a * 6;
+  const DlBox pb{(o[0] + gx) * st, (o[1] + gy) * st, expf(o[2]) * st, expf(o[3]) * st};
+  const float xc = (gx + 0.5f) * st, yc = (gy + 0.5f) * st, rad = 1.5f * st;
+  const float m = fminf(fminf(xc - (g.cx - rad), yc - (g.cy - rad)), fminf(g.cx + rad - xc, g.cy + rad - yc));
+  const float iou = iou_cxcywh(g, pb);
+  const float pr = sqrtf(sigm(o[5]) * sigm(o[4]));
+  const float cls_cost = fminf(-logf(pr), 100.0f);
+  return DlPair{iou, cls_cost + 3.0f * (-logf(iou + 1e-8f)) + (m > 0.0f ? 0.0f : 1e6f)};
+}
+
+__device__ __forceinline__ float dlw_wave_max(float v) {
+  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+  return v;
+}
+__device__ __forceinline__ float dlw_wave_min(float v) {
+  for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off));
+  return v;
+}
+__device__ __forceinline__ int dlw_wave_min(int v) {
+  for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off));
+  return v;
+}
+
+__global__ __launch_bounds__(256) void yolox_loss_wide_kernel(const float* __restrict__ raw, const float* __restrict__ labels,
+                                                              int nb, int cmax, DetGeom geo, float* __restrict__ d_raw,
+                                                              float* __restrict__ acc, int use_l1) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char dlw_lds[];
+  DlBox* gt = reinterpret_cast<DlBox*>(dlw_lds);               // [nb]
+  int* cand = reinterpret_cast<int*>(gt + nb);                 // [cmax] anchor index of each candidate, ascending
+  int* c_cnt = cand + cmax;                                    // [cmax] boxes that chose the candidate
+  int* c_gt = c_cnt + cmax;                                    // [cmax] lowest such box, then the matched box (-1: none)
+  __shared__ int s_nc, wave_cnt[4];
+  __shared__ float part[4][5];
+  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, A = geo.A;
+  const float* r = raw + (long long)n * A * 6;
+  float* dr = d_raw + (long long)n * A * 6;
+  const float* lab = labels + (long long)n * nb * 5;
+  // number of objects = rows with a positive sum; the FIRST ng rows are taken as the boxes (as published)
+  int mine = 0;
+  for (int k = tid; k < nb; k += 256) {
+    const float* l = lab + k * 5;
+    mine += l[0] + l[1] + l[2] + l[3] + l[4] > 0.0f;
+  }
+  for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
+  if (lane == 0) wave_cnt[wv] = mine;
+  if (tid == 0) s_nc = 0;
+  __syncthreads();
+  const int ng = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];      // <= nb
+  for (int k = tid; k < ng; k += 256) {
+    const float* l = lab + k * 5;
+    gt[k] = DlBox{l[1], l[2], l[3], l[4]};
+  }
+  __syncthreads();
+  // ---- candidates: anchors whose centre lies within 1.5 strides of some gt centre (ordered compaction) ----
+  for (int base = 0; base < A && ng > 0; base += 256) {
+    const int a = base + tid;
+    bool ok = false;
+    if (a < A) {
+      int l = 0;
+      while (l < 2 && a >= geo.a0[l + 1]) ++l;
+      const int p = a - geo.a0[l], gx = p % geo.W[l], gy = p / geo.W[l];
+      const float st = (float)geo.stride[l];
+      const float xc = (gx + 0.5f) * st, yc = (gy + 0.5f) * st, rad = 1.5f * st;
+      for (int g = 0; g < ng && !ok; ++g) {
+        const float m = fminf(fminf(xc - (gt[g].cx - rad), yc - (gt[g].cy - rad)), fminf(gt[g].cx + rad - xc, gt[g].cy + rad - yc));
+        ok = m > 0.0f;
+      }
+    }
+    const unsigned long long bal = __ballot(ok);
+    if (lane == 0) wave_cnt[wv] = __popcll(bal);
+    __syncthreads();
+    int off = s_nc;
+    for (int w = 0; w < wv; ++w) off += wave_cnt[w];
+    const int pos = off + __popcll(bal & ((1ull << lane) - 1ull));
+    if (ok && pos < cmax) { cand[pos] = a; c_cnt[pos] = 0; c_gt[pos] = 0x7fffffff; }      // (27 * ng <= cmax: never cut)
+    __syncthreads();
+    if (tid == 0) s_nc = min(cmax, s_nc + wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3]);
+    __syncthreads();
+  }
+  const int nc = s_nc;
+  // ---- dynamic k and the k cheapest candidates of every gt: one wave per box ----
+  for (int g = wv; g < ng && nc > 0; g += 4) {
+    const DlBox box = gt[g];
+    float ti[DLW_TOP], tv[DLW_TOP];               // this lane's largest IoUs (descending), cheapest costs (ascending)
+    int tx[DLW_TOP];                              // ... and their candidates; equal costs keep the lower index in front
+#pragma unroll
+    for (int j = 0; j < DLW_TOP; ++j) { ti[j] = -INFINITY; tv[j] = INFINITY; tx[j] = 0x7fffffff; }
+    for (int c = lane; c < nc; c += 64) {
+      const DlPair pc = dlw_pair(r, geo, box, cand[c]);
+      if (pc.iou > ti[DLW_TOP - 1]) {
+        ti[DLW_TOP - 1] = pc.iou;
+#pragma unroll
+        for (int j = DLW_TOP - 1; j > 0; --j)
+          if (ti[j] > ti[j - 1]) { const float x = ti[j]; ti[j] = ti[j - 1]; ti[j - 1] = x; }
+      }
+      if (pc.cost < tv[DLW_TOP - 1]) {
+        tv[DLW_TOP - 1] = pc.cost; tx[DLW_TOP - 1] = c;
+#pragma unroll
+        for (int j = DLW_TOP - 1; j > 0; --j)
+          if (tv[j] < tv[j - 1]) {
+            const float x = tv[j]; tv[j] = tv[j - 1]; tv[j - 1] = x;
+            const int y = tx[j]; tx[j] = tx[j - 1]; tx[j - 1] = y;
+          }
+      }
+    }
+    float sum = 0.0f;                             // the ten largest IoUs of the box, added largest first
+    for (int it = 0; it < min(DLW_TOP, nc); ++it) {
+      const float m = dlw_wave_max(ti[0]);
+      const int win = __ffsll((unsigned long long)__ballot(ti[0] == m)) - 1;
+      sum += m;
+      if (lane == win) {
+#pragma unroll
+        for (int j = 0; j < DLW_TOP - 1; ++j) ti[j] = ti[j + 1];
+        ti[DLW_TOP - 1] = -INFINITY;
+      }
+    }
+    int k = (int)sum;
+    if (k < 1) k = 1;
+    if (k > nc) k = nc;
+    if (k > DLW_TOP) k = DLW_TOP;                 // (ten IoUs <= 1 each: not reached)
+    for (int it = 0; it < k; ++it) {              // cheapest first, lowest candidate index on equal cost
+      const float m = dlw_wave_min(tv[0]);
+      const int cm = dlw_wave_min(tv[0] == m ? tx[0] : 0x7fffffff);
+      if (tx[0] == cm && tv[0] == m) {            // candidate cm lives in one lane only
+#pragma unroll
+        for (int j = 0; j < DLW_TOP - 1; ++j) { tv[j] = tv[j + 1]; tx[j] = tx[j + 1]; }
+        tv[DLW_TOP - 1] = INFINITY; tx[DLW_TOP - 1] = 0x7fffffff;
+      }
+      if (lane == 0 && (unsigned)cm < (unsigned)nc) { atomicAdd(&c_cnt[cm], 1); atomicMin(&c_gt[cm], g); }
+    }
+  }
+  __syncthreads();
+  // ---- one gt per anchor: an anchor claimed by several gts goes to the cheapest of ALL boxes, lowest box on ties ----
+  for (int c = tid; c < nc; c += 256) {
+    const int cnt = c_cnt[c];
+    if (cnt == 0) { c_gt[c] = -1; continue; }
+    if (cnt == 1) continue;
+    int amin = 0;
+    float bv = INFINITY;
+    for (int g = 0; g < ng; ++g) {
+      const float cv = dlw_pair(r, geo, gt[g], cand[c]).cost;
+      if (cv < bv) { bv = cv; amin = g; }
+    }
+    c_gt[c] = amin;
+  }
+  __syncthreads();
+  dl_loss_terms(r, dr, geo, gt, cand, c_gt, nc, ng, use_l1, part, acc + (long long)n * 8,
+                [](int, int, const DlBox& t, const DlBox& pb) { return iou_cxcywh(t, pb); });
 }
 
 // metrics[0..5] = total, 5 * iou, obj, cls, l1, num_fg / max(num_gts, 1); scale[0] = loss_scale / max(num_fg, 1)
@@ -261,6 +453,23 @@ __global__ void yolox_loss_finalize_kernel(const float* __restrict__ rows, int N
 int launch_yolox_loss(const float* raw, const float* labels, int N, int nb, const DetGeom& geo, float* d_raw, float* acc,
                       int use_l1, float loss_scale, float* metrics, float* scale, hipStream_t s) {
   hipLaunchKernelGGL(yolox_loss_kernel, dim3(N), dim3(256), 0, s, raw, labels, nb, geo, d_raw, acc, use_l1);
+  hipLaunchKernelGGL(yolox_loss_finalize_kernel, dim3(1), dim3(64), 0, s, acc, N, loss_scale, metrics, scale);
+  return 0;
+}
+
+int launch_yolox_loss_wide(const float* raw, const float* labels, int N, int nb, const DetGeom& geo, float* d_raw, float* acc,
+                           int use_l1, float loss_scale, float* metrics, float* scale, hipStream_t s) {
+  if (geo.A < 1 || geo.A > DETLOSS_WIDE_MAX_A || nb < 1 || nb > JN_DETLOSS_MAX_BOXES) return 1;
+  const int cmax = (int)std::min<long long>(geo.A, 27LL * nb);
+  const size_t smem = (size_t)nb * sizeof(DlBox) + (size_t)3 * cmax * sizeof(int);
+  static bool raised = false;
+  if (!raised) {
+    constexpr size_t most = (size_t)JN_DETLOSS_MAX_BOXES * sizeof(DlBox) + (size_t)3 * DETLOSS_WIDE_MAX_A * sizeof(int);
+    static_assert(most + 256 <= 160 * 1024, "the wide loss kernel's LDS must fit a gfx950 workgroup");
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&yolox_loss_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)most);
+    raised = true;
+  }
+  hipLaunchKernelGGL(yolox_loss_wide_kernel, dim3(N), dim3(256), smem, s, raw, labels, nb, cmax, geo, d_raw, acc, use_l1);
   hipLaunchKernelGGL(yolox_loss_finalize_kernel, dim3(1), dim3(64), 0, s, acc, N, loss_scale, metrics, scale);
   return 0;
 }

@@ -16,7 +16,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import check, ptr
 from .engine import Engine, make_jn_config, GPT_ZOO
-from .yolox import NeedleYOLOX, DET_CANDIDATES
+from .yolox import NeedleYOLOX, DET_CANDIDATES, DET_LOSS_BOXES
 
 
 class _Slot(nn.Module):
@@ -125,6 +125,9 @@ class GPT(nn.Module):
         self.det_candidates = "first2048"
         if getattr(config, "det_candidates", "first2048") != "first2048":
             self.set_det_candidates(config.det_candidates)
+        self.det_loss_boxes = "cap8"
+        if getattr(config, "det_loss_boxes", "cap8") != "cap8":
+            self.set_det_loss_boxes(config.det_loss_boxes)
         self._build_parameters()
         # --freeze-image-processor (gpt.py:264-268): yolox.backbone.* out of the optimiser
         self.freeze_image_processor = bool(getattr(config, "freeze_image_processor", False))
@@ -190,6 +193,17 @@ class GPT(nn.Module):
             raise ValueError(f"det_candidates={policy!r}: one of {DET_CANDIDATES}")
         check(self._engine.lib.jn_set_det_candidates(self._engine.handle, int(policy == "all")), "jn_set_det_candidates")
         self.det_candidates = policy
+
+    def set_det_loss_boxes(self, policy: str):
+        """Box policy of the detector's training / validation loss from now on (``jn_set_det_loss_boxes``; config field
+        ``det_loss_boxes``): "cap8" = at most 8 ground-truth boxes per patch, a patch with more raises ``ValueError``;
+        "all" = every box of a patch takes part in the SimOTA assignment, as in the reference (targets up to
+        ``yolox.MAX_BOXES_WIDE`` rows wide).  Targets of at most 8 rows run the same kernel under either policy.  Needs
+        a detector, and for "all" a patch size of at most 640."""
+        if policy not in DET_LOSS_BOXES:
+            raise ValueError(f"det_loss_boxes={policy!r}: one of {DET_LOSS_BOXES}")
+        check(self._engine.lib.jn_set_det_loss_boxes(self._engine.handle, int(policy == "all")), "jn_set_det_loss_boxes")
+        self.det_loss_boxes = policy
 
     @property
     def yolox(self):

@@ -10,6 +10,8 @@ from ._lib import check, ptr
 
 LOSS_NAMES = ("total_loss", "iou_loss", "conf_loss", "cls_loss", "l1_loss", "num_fg")
 MAX_BOXES_PER_PATCH = 8          # DL_MAXG of csrc/kernels_detloss.hip: boxes of one patch the loss kernel holds in LDS
+MAX_BOXES_WIDE = 1024            # JN_DETLOSS_MAX_BOXES of include/jnroll.h: rows of `targets` the wide loss kernel accepts
+DET_LOSS_BOXES = ("cap8", "all")  # box policies of the loss: jn_yolox_loss (MAX_BOXES_PER_PATCH) / jn_yolox_loss_wide (every box)
 
 
 def check_box_cap(targets: torch.Tensor) -> None:
@@ -29,10 +31,15 @@ def check_box_cap(targets: torch.Tensor) -> None:
 
 
 def yolox_loss(raw: torch.Tensor, targets: torch.Tensor, patch_size: int, strides=(8, 16, 32), use_l1: bool = True,
-               loss_scale: float = 1.0):
+               loss_scale: float = 1.0, boxes: str = "cap8"):
     """The detector's SimOTA loss on given predictor outputs (``jn_yolox_loss``, no engine): raw [N, A, 6] and targets
     [N, nb, 5] = (class, x1, y1, x2, y2) on the device.  Returns (d_raw [N, A, 6] = d loss / d raw before the
-    1 / max(num_fg, 1) factor, metrics f32[8] in the order of ``LOSS_NAMES``, scale f32[1] = loss_scale / max(num_fg, 1))."""
+    1 / max(num_fg, 1) factor, metrics f32[8] in the order of ``LOSS_NAMES``, scale f32[1] = loss_scale / max(num_fg, 1)).
+    ``boxes="all"`` (``jn_yolox_loss_wide``, A <= 8400, nb <= ``MAX_BOXES_WIDE``) uses every box of a patch, as the
+    reference does; the default ``"cap8"`` raises ``ValueError`` on a patch with more than ``MAX_BOXES_PER_PATCH``."""
+    if boxes not in DET_LOSS_BOXES:
+        raise ValueError(f"boxes={boxes!r}: one of {DET_LOSS_BOXES}")
+    entry = "jn_yolox_loss_wide" if boxes == "all" else "jn_yolox_loss"
     assert raw.is_cuda and raw.dim() == 3 and raw.shape[2] == 6 and targets.dim() == 3 and targets.shape[2] == 5
     assert targets.shape[0] == raw.shape[0]
     dev = raw.device
@@ -41,13 +48,14 @@ def yolox_loss(raw: torch.Tensor, targets: torch.Tensor, patch_size: int, stride
     N, A, nb = raw.shape[0], raw.shape[1], t.shape[1]
     if all(int(s) > 0 and patch_size % int(s) == 0 for s in strides):
         assert A == sum((patch_size // int(s)) ** 2 for s in strides), (A, patch_size, strides)
-    check_box_cap(t)
+    if boxes != "all":
+        check_box_cap(t)
     d_raw = torch.empty_like(raw)
     metrics = torch.zeros(8, device=dev)
     scale = torch.zeros(1, device=dev)
-    check(_lib.load_library().jn_yolox_loss(ptr(raw), ptr(t), N, nb, int(patch_size), *(int(s) for s in strides), int(bool(use_l1)),
-                                            float(loss_scale), ptr(d_raw), ptr(metrics), ptr(scale), _lib.current_stream(dev)),
-          "jn_yolox_loss")
+    check(getattr(_lib.load_library(), entry)(ptr(raw), ptr(t), N, nb, int(patch_size), *(int(s) for s in strides),
+                                              int(bool(use_l1)), float(loss_scale), ptr(d_raw), ptr(metrics), ptr(scale),
+                                              _lib.current_stream(dev)), entry)
     return d_raw, metrics, scale
 
 
@@ -119,6 +127,8 @@ class NeedleYOLOX:
 
     At most ``MAX_BOXES_PER_PATCH`` = 8 boxes per patch: ``targets`` may be wider (padding rows), but a patch with more
     real rows raises ``ValueError`` (the loss kernel would drop the rest, the reference uses them all).
+    Under the owning model's box policy "all" (``GPT.set_det_loss_boxes``, config field ``det_loss_boxes``) every box of
+    a patch is used instead, as in the reference, and nothing raises up to ``MAX_BOXES_WIDE`` rows.
 
     A detection batch larger than ``max_batch`` is fed in chunks of ``max_batch``, each weighted by its share of the
     patches (deviation: BatchNorm statistics and the 1 / num_fg normalisation are per chunk); every chunk keeps its own
@@ -137,6 +147,10 @@ class NeedleYOLOX:
 
     def __call__(self, patches, targets=None, predict: bool = True):
         return self.forward(patches, targets, predict)
+
+    def _check_boxes(self, t: torch.Tensor) -> None:
+        if self._gpt.det_loss_boxes != "all":                      # under "all" the engine uses every box: nothing to refuse
+            check_box_cap(t)
 
     def _boxes_to_list(self, boxes, counts) -> List[Optional[torch.Tensor]]:
         cnt = counts.tolist()
@@ -161,7 +175,7 @@ class NeedleYOLOX:
         # ---- loss branch + eval head (src/models/yolox.py:58-91) ----
         assert targets.shape[0] == N and targets.shape[-1] >= 5
         t = targets[..., :5].to(g.device, torch.float32).contiguous()
-        check_box_cap(t)
+        self._check_boxes(t)
         graph = torch.is_grad_enabled()
         if not g.training and not graph:
             return self._validation_forward(x, t, predict)
@@ -240,7 +254,7 @@ class NeedleYOLOX:
         assert targets.shape[0] == patches.shape[0] and targets.shape[-1] >= 5
         x = patches.to(g.device, torch.float32).contiguous()
         t = targets[..., :5].to(g.device, torch.float32).contiguous()
-        check_box_cap(t)
+        self._check_boxes(t)
         return self._validation_forward(x, t, predict, packed)
 
     def loss_and_backward(self, patches: torch.Tensor, targets: torch.Tensor, loss_scale: float = 1.0) -> dict:
@@ -254,7 +268,7 @@ class NeedleYOLOX:
         assert targets.shape[0] == N and targets.shape[-1] >= 5
         x = patches.to(g.device, torch.float32).contiguous()
         t = targets[..., :5].to(g.device, torch.float32).contiguous()
-        check_box_cap(t)
+        self._check_boxes(t)
         tot = {k: torch.zeros((), device=g.device) for k in LOSS_NAMES}
         for i in range(0, N, g.max_batch):
             n = min(g.max_batch, N - i)
