@@ -668,6 +668,21 @@ int jn_teacher_walks(const int64_t* bboxes_dev, const int64_t* start_positions_d
                      int64_t* positions_dev, int64_t* current_actions_dev, int64_t* next_actions_dev, int64_t* labels_dev,
                      float* masks_dev, float* local_bboxes_dev, int32_t* n_steps_dev, uint8_t* targets_dev,
                      int64_t* cells_dev, float* bboxes_yolox_dev, int32_t* offsets_dev, void* stream);
+/* Debug entry, context-free: the fused backward of ONE pointwise (1x1) BatchNorm + SiLU layer over S workspace slots of M
+ * pixels each, as the conv-stack backward launches it for the layers with at most 128 channels on either side (cout and
+ * cin each 16, 32, 64 or 128).  Per slot s, pixel m, with y = sc * z + sh of the layer's raw output z:
+ *   g_z = k * (g * silu'(y) - c1 - (z - mean) * invstd * c2),   gx (=|+=) g_z . w (+ gadd),   gw += g_z^T . a_in,
+ * a_in = fl ? silu(sc_in * x + sh_in) : x.  All fp32: g, z [S,M,cout]; x, gx and the optional gadd (NULL: none) [S,M,cin];
+ * tab [S,3,cout+cin]: rows sc, sh, fl, the output channels' entries first, then the input channels' (fl of the output
+ * is not read); save [S,cout,2] = (mean, invstd); consts [S,cout,3] = (c1, c2, k); w, gw [cout,cin] — gw is added to,
+ * over all slots.  accumulate != 0 adds to what gx holds.  route: 0 = the launcher's choice (32-pixel tiles, two
+ * workgroups per CU, for 128 input channels and 64 or 128 output channels), 1 = the 64-pixel kernel.  max_wg: 0 = the
+ * launcher's rule, else a cap on the workgroups (1: one workgroup walks every tile of every slot).  Allocates its
+ * workspace, waits for `stream` and frees it.  JN_EINVAL: a null pointer, S < 1, M < 1, a shape without a fused kernel,
+ * route outside 0..1, max_wg < 0. */
+int jn_pw_bwd_fused(const float* g_dev, const float* z_dev, const float* x_dev, const float* tab_dev, const float* save_dev,
+                    const float* consts_dev, const float* w_dev, const float* gadd_dev, int accumulate, float* gx_dev,
+                    float* gw_dev, int S, long long M, int cout, int cin, int route, int max_wg, void* stream);
 /* Arms the following rollouts of `ctx` with that teacher (the per-step `best_action` that test_model_on_env compares
  * each chosen action with, src/supervised.py:279-405): before the decision of step t, the set of the state that
  * decision sees (position and visited patches before the step) goes to sets_dev[b * T + t] (uint8 [B,T], T =

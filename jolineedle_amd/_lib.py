@@ -146,6 +146,7 @@ SIGNATURES = {
     "jn_set_rollout_positions": (C.c_int, [C.c_void_p, C.c_int]),
     "jn_teacher_actions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "jn_teacher_walks": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_uint64, C.c_int] + [C.c_void_p] * 12),
+    "jn_pw_bwd_fused": (C.c_int, [C.c_void_p] * 8 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_longlong] + [C.c_int] * 4 + [C.c_void_p]),
     "jn_set_rollout_teacher":(C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "jn_rollout_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "jn_last_timing": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),

@@ -583,6 +583,10 @@ int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, hi
             const ChanTab zt = tab(co.out);
             fa.red2_z = (const float*)ptr(co.out); fa.red2_ld = ld(co.out); fa.red2_sc = zt.sc; fa.red2_sh = zt.sh;
           }
+          // 128 input channels, fp32: the transposed weight in fragment order goes into the layer's own stretch of the
+          // wide route's scratch (6 bytes per weight, unused by a fused layer; 16-byte aligned under the same condition)
+          if (net.act_dtype == JN_F32 && ctx->params_x3t && cw.cin == 128 && (pc == 128 || pc == 64) && (fa.w - ctx->params) % 8 == 0)
+            fa.w_frag = reinterpret_cast<float*>(ctx->params_x3t + 3 * (fa.w - ctx->params));
           launch_pw_bwd_fused(fa, s);
         }
       } else if (st.route == BR_DW_FUSED) {

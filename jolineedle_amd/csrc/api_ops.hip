@@ -284,4 +284,56 @@ int jn_teacher_walks(const int64_t* bboxes_dev, const int64_t* start_positions_d
   return JN_OK;
 }
 
+// (the fragment-order scratch of the 128-input-channel kernel is allocated and freed here, so the call waits for the stream)
+int jn_pw_bwd_fused(const float* g_dev, const float* z_dev, const float* x_dev, const float* tab_dev, const float* save_dev,
+                    const float* consts_dev, const float* w_dev, const float* gadd_dev, int accumulate, float* gx_dev,
+                    float* gw_dev, int S, long long M, int cout, int cin, int route, int max_wg, void* stream) {
+  JN_CHECK(g_dev && z_dev && x_dev && tab_dev && save_dev && consts_dev && w_dev && gx_dev && gw_dev, JN_EINVAL,
+           "jn_pw_bwd_fused: null argument");
+  JN_CHECK(S >= 1 && M >= 1 && M <= (1LL << 40), JN_EINVAL, "jn_pw_bwd_fused: S=%d M=%lld", S, M);
+  JN_CHECK(cout >= 16 && cin >= 16 && pw_bwd_fused_supported(cout, cin), JN_EINVAL, "jn_pw_bwd_fused: %d -> %d channels: no fused kernel",
+           cin, cout);
+  JN_CHECK((route == 0 || route == 1) && max_wg >= 0, JN_EINVAL, "jn_pw_bwd_fused: route=%d max_wg=%d", route, max_wg);
+  // The kernels step all activation buffers by ONE slot stride and all gradient buffers by another (the engine's
+  // workspace slots), so the caller's dense tensors are laid into such slots: [z | x] and [g | gx | gadd] per slot.
+  hipStream_t s = (hipStream_t)stream;
+  const long long C = cout + cin;
+  const size_t zn = (size_t)M * cout, xn = (size_t)M * cin, act = zn + xn, grad = zn + 2 * xn;
+  float* ws = nullptr;
+  JN_HIP(hipMalloc((void**)&ws, ((size_t)S * (act + grad) + (size_t)2 * cout * cin) * sizeof(float)));      // (w_frag: 6 bytes per weight)
+  float *za = ws, *xa = za + zn, *ga = ws + (size_t)S * act, *gxa = ga + zn, *gadda = gxa + xn, *w_frag = ws + (size_t)S * (act + grad);
+  auto lay = [&](float* dst, size_t dst_slot, const float* src, size_t n, bool back) {
+    return back ? hipMemcpy2DAsync(const_cast<float*>(src), n * sizeof(float), dst, dst_slot * sizeof(float), n * sizeof(float), S, hipMemcpyDeviceToDevice, s)
+                : hipMemcpy2DAsync(dst, dst_slot * sizeof(float), src, n * sizeof(float), n * sizeof(float), S, hipMemcpyDeviceToDevice, s);
+  };
+  hipError_t e = lay(za, act, z_dev, zn, false);
+  if (e == hipSuccess) e = lay(xa, act, x_dev, xn, false);
+  if (e == hipSuccess) e = lay(ga, grad, g_dev, zn, false);
+  if (e == hipSuccess && accumulate) e = lay(gxa, grad, gx_dev, xn, false);
+  if (e == hipSuccess && gadd_dev) e = lay(gadda, grad, gadd_dev, xn, false);
+  int rc = -1;
+  if (e == hipSuccess) {
+    float* tab = const_cast<float*>(tab_dev);
+    PwBwdFusedArgs a{};
+    a.g = ga; a.g_ld = cout; a.z = za; a.z_ld = cout;
+    a.ot.sc = tab; a.ot.sh = tab + C; a.ot.fl = tab + 2 * C;
+    a.save = save_dev; a.consts = consts_dev;
+    a.x = xa; a.x_ld = cin;
+    a.it.sc = tab + cout; a.it.sh = tab + C + cout; a.it.fl = tab + 2 * C + cout;
+    a.w = w_dev; a.gx = gxa; a.gx_ld = cin; a.accumulate = accumulate ? 1 : 0; a.gw = gw_dev;
+    a.M = M; a.cout = cout; a.cin = cin;
+    a.sb.n = S; a.sb.act = (long long)act; a.sb.grad = (long long)grad; a.sb.tab = 3 * C; a.sb.save = 2LL * cout; a.sb.consts = 3LL * cout;
+    if (gadd_dev) { a.gadd = gadda; a.gadd_ld = cin; }
+    a.w_frag = w_frag; a.route = route; a.max_wg = max_wg;
+    rc = launch_pw_bwd_fused(a, s);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = lay(gxa, grad, gx_dev, xn, true);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(ws);
+  JN_HIP(e);
+  JN_CHECK(rc == 0, JN_EINVAL, "jn_pw_bwd_fused: %d -> %d channels: no fused kernel", cin, cout);
+  return JN_OK;
+}
+
 }  // extern "C"

@@ -241,6 +241,12 @@ struct PwBwdFusedArgs {
   // sums formed for it belong to the BatchNorm of z2's conv (the bottleneck's last pointwise conv): z2 / its table replace
   // the raw input tile and the input table in that run's silu' and second moment
   const float* red2_z; int red2_ld; const float* red2_sc; const float* red2_sh;
+  // optional: 6 bytes per weight of scratch (three bf16 planes; the fp32 form uses 4), 16-byte aligned, free during this
+  // launch.  With it the (128, 128) and (64, 128) layers take pw_bwd_fused128_kernel, which streams the transposed weight
+  // from there in fragment order
+  float* w_frag;
+  int route;                             // debug entry: 1 keeps the 64-pixel kernel
+  int max_wg;                            // debug entry: > 0 caps the workgroups
 };
 struct DwBwdFusedArgs {                  // the depthwise counterpart (3x3, pad 1, stride 1 / 2)
   const float* g; int g_ld; const float* z; int z_ld; ChanTab ot; const float* save; const float* consts;
@@ -252,6 +258,8 @@ struct DwBwdFusedArgs {                  // the depthwise counterpart (3x3, pad 
 };
 bool dw_bwd_fused_supported(int C, int H, int W, int OH, int OW, int stride);
 int launch_dw_bwd_fused(const DwBwdFusedArgs& a, hipStream_t s);
+// the [cout][cin] weight transposed and split into three bf16 planes, in the fragment order pw_x3_kernel<.., SLOTS> streams
+int launch_w_split3_t(const float* w, void* w3t, int cout, int cin, hipStream_t s);
 bool pw_bwd_fused_supported(int cout, int cin);
 bool pw_bwd_fused_reduces_input(int cout, int cin);
 int launch_pw_bwd_fused(const PwBwdFusedArgs& a, hipStream_t s);

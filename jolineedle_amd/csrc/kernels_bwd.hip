@@ -824,6 +824,7 @@ static void launch_pw_bwd_fused_r(const PwBwdFusedArgs& a, hipStream_t s) {
   }
   const int rounds = std::max(1, (1024 + places / 2) / places);
   long long bx = (long long)rounds * places / a.sb.n;
+  if (a.max_wg > 0 && bx > a.max_wg / a.sb.n) bx = a.max_wg / a.sb.n;
   if (bx < 1) bx = 1;
   if (bx > n_tiles) bx = n_tiles;
   const int rep = (a.wpart && N * K <= JN_WPART_MAX) ? 1 : 0;
@@ -843,6 +844,350 @@ static void launch_pw_bwd_fused_t(const PwBwdFusedArgs& a, hipStream_t s) {
   launch_pw_bwd_fused_r<CTN, CTK, false>(a, s);
 }
 
+// ---- the same pass for 128 input channels, resident twice per CU -----------------------------------
+// pw_bwd_fused_kernel<8 | 4, 8> keeps W^T in LDS (68 / 35 KB of its 140 / 89 KB) and 368+ registers: one workgroup per CU,
+// one wave per SIMD, nothing to overlap a tile's load / stage / matrix / store phases with.  This form has 32-pixel tiles,
+// no W^T in LDS (67 / 55 KB) and at most 256 registers, so two workgroups share a CU:
+//  - W^T comes from `wf`, the weight in FRAGMENT ORDER (a pre-pass per launch), one 1 KB contiguous load per wave and
+//    fragment, requested D steps ahead.  fp32 form (w_frag_t_kernel): block (b * N / 16 + s) of 64 lanes x 4 floats, lane
+//    (gq, lm) holding w[16 s + 4 gq + j][16 b + lm], j = 0..3 — the A operands of the four v_mfma_f32_16x16x4_f32 of
+//    k-step s.  X3: the three bf16 planes of w_split3_t_kernel, as pw_x3_kernel<.., SLOTS> streams them.
+//  - phase 2: wave = all 32 pixels x a QUARTER of the input channels (2 cin tiles x 2 pixel groups = 16 accumulator
+//    registers), so a workgroup requests every fragment once per tile.  fp32 form (64 output channels): the fp32 products
+//    in the k order of the 64-pixel kernel, the data gradient is bit-equal to it.  X3 (128 output channels, where the fp32
+//    matrix loop was the longest part of a tile): the six-product bf16 form of pw_x3_kernel on three planes of g_z.
+//  - phase 3: the tile's 32 pixels are ONE k-step of v_mfma_f32_16x16x32_bf16 (three products as there); wave (cout half,
+//    cin half) owns a disjoint quarter of dW across the whole loop — no cross-wave sum, each wave adds its own tiles.
+//  - ONE resident round of workgroups, each a contiguous run of the tiles of all slots (a slot crossing reloads the
+//    per-channel constants); the store's gadd / accumulate operands and then the next tile's (g, z, x) are requested after
+//    the tile's LAST fragment: loads return in order, so a fragment requested behind them would wait for HBM, and the
+//    store waits for its operands only, not for the next tile.
+
+// a uniform global pointer pinned to scalar registers (the empty asm hides its origin from the optimiser; the address
+// space is given back by the cast), and a 16-byte load at scalar base + 32-bit offset
+using gfloat_p = const __attribute__((address_space(1))) float*;
+__device__ __forceinline__ gfloat_p pin_uniform(const float* p) {
+  asm volatile("" : "+s"(p));
+  return (gfloat_p)p;
+}
+__device__ __forceinline__ f32x4 ldg4(gfloat_p base, unsigned off) {
+  return *(const __attribute__((address_space(1))) f32x4*)(base + off);
+}
+
+__global__ __launch_bounds__(256) void w_frag_t_kernel(const float* __restrict__ w, float* __restrict__ wf, int N, int K) {
+  const int i = blockIdx.x * 256 + threadIdx.x;        // (cin tile b, k-step s, lane)
+  if (i >= N * K / 4) return;
+  const int lane = i & 63, lm = lane & 15, gq = lane >> 4, NS = N / 16, s = (i >> 6) % NS, b = (i >> 6) / NS;
+  f32x4 v;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = w[(long long)(16 * s + 4 * gq + j) * K + 16 * b + lm];
+  *reinterpret_cast<f32x4*>(wf + 4LL * i) = v;
+}
+
+template <int CTN, int D, bool X3>
+__global__ __launch_bounds__(256, 2) void pw_bwd_fused128_kernel(
+    const float* __restrict__ g, int g_ld, const float* __restrict__ z, int z_ld, ChanTab ot,
+    const float* __restrict__ save, const float* __restrict__ consts, const float* __restrict__ x, int x_ld,
+    ChanTab it, const float* __restrict__ wf, float* __restrict__ gx, int gx_ld, int accumulate,
+    float* __restrict__ gw, int rep, long long M, SlotBatch sb, const float* __restrict__ gadd, int gadd_ld) {
+  constexpr int N = 16 * CTN, K = 128, NS = N / 16;  // output / input channels, k-steps of phase 2
+  constexpr int LDG = N + 4, LDA = K + 4;
+  constexpr int NG = 32 * (N / 4) / 256, NA = 32 * (K / 4) / 256;     // f32x4 per thread per tile
+  constexpr int NJ = N / 32, LDK = N + 16;           // X3: k-steps of phase 2, row stride of the bf16 planes (pw_x3_kernel)
+  static_assert(NG >= 1 && D >= 1 && D < (X3 ? 2 * NJ : NS), "pw_bwd_fused128 tile mapping");
+  // fp32 form: two tile buffers — a tile is staged while slower waves still read the previous one, ONE barrier per tile.
+  // X3: one buffer and the three bf16 planes of g_z beside it.
+  constexpr int TILE = 32 * LDG + 32 * LDA, NBUF = X3 ? 1 : 2;
+  __shared__ __attribute__((aligned(16))) float sm[NBUF * TILE + 7 * N + 3 * K + (X3 ? 3 * 32 * LDK / 2 : 0)];
+  float* Gs = sm;                       // [32][LDG]  g_z tile
+  float* As = Gs + 32 * LDG;            // [32][LDA]  activated input tile
+  float* const Cs = sm + NBUF * TILE;   // [7][N] output-side constants, [3][K] input table (of the slot being staged)
+  bf16_t* const Gp = reinterpret_cast<bf16_t*>(Cs + 7 * N + 3 * K);     // X3: [3][32][LDK] h, m, l planes of the g_z tile
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lm = lane & 15, gq = lane >> 4;
+  const int nq = tid % (N / 4), kq = tid % (K / 4);
+  const long long tiles_per_slot = (M + 31) / 32, n_tiles = tiles_per_slot * sb.n;
+  const long long t_begin = n_tiles * blockIdx.x / gridDim.x, t_end = n_tiles * (blockIdx.x + 1) / gridDim.x;
+  if (t_begin >= t_end) return;
+
+  // weight-gradient tiles of this wave: cout tiles dw_a0 .. + CTN / 2, cin tiles dw_b0 .. + 4
+  constexpr int DW_AN = CTN / 2, DW_BN = 4;
+  const int dw_a0 = (wave & 1) * DW_AN, dw_b0 = (wave >> 1) * DW_BN;
+  f32x4 dw[DW_AN][DW_BN];
+#pragma unroll
+  for (int a = 0; a < DW_AN; ++a)
+#pragma unroll
+    for (int b = 0; b < DW_BN; ++b) dw[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  f32x4 rg[NG], rz[NG], rx[NA];
+  long long f_slot = 0, f_m0 = 0;                   // slot and first pixel of the fetched tile
+  auto fetch = [&](bool next) {                     // the tile behind the fetched one, or that one again
+    if (next) {
+      f_m0 += 32;
+      if (f_m0 >= M) { f_m0 = 0; ++f_slot; }
+    }
+    // tile bases are uniform and the offsets inside a tile fit 32 bits: scalar base + one offset register per load.
+    // Rows past the map re-read its last row; stage() writes zeros there.
+    const gfloat_p gs = pin_uniform(g + f_slot * sb.grad + f_m0 * g_ld), zs = pin_uniform(z + f_slot * sb.act + f_m0 * z_ld),
+                   xs = pin_uniform(x + f_slot * sb.act + f_m0 * x_ld);
+    const int last = (int)(M - f_m0 < 32 ? M - f_m0 : 32) - 1;
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {
+      const int r = std::min((tid + 256 * j) / (N / 4), last);
+      rg[j] = ldg4(gs, r * g_ld + 4 * nq);
+      rz[j] = ldg4(zs, r * z_ld + 4 * nq);
+    }
+#pragma unroll
+    for (int j = 0; j < NA; ++j) {
+      const int r = std::min((tid + 256 * j) / (K / 4), last);
+      rx[j] = ldg4(xs, r * x_ld + 4 * kq);
+    }
+  };
+  // the store's operand of tile (slot, m0) in accumulator layout (pixel 16 p + lm, channels 16 (2 wave + c) + 4 gq): gadd,
+  // or the gradient already in gx; with BOTH (no layer of the plan has them) the second one is read at the store
+  f32x4 eo[2][2];
+  auto fetch_store_operand = [&](long long slot, long long m0) {
+    const gfloat_p src = pin_uniform(gadd ? gadd + slot * sb.grad + m0 * gadd_ld : gx + slot * sb.grad + m0 * gx_ld);
+    const int src_ld = gadd ? gadd_ld : gx_ld;
+    const int last = (int)(M - m0 < 32 ? M - m0 : 32) - 1;
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int p = 0; p < 2; ++p)
+        eo[c][p] = ldg4(src, std::min(16 * p + lm, last) * src_ld + 16 * (2 * wave + c) + 4 * gq);
+  };
+  auto load_consts = [&](long long sl) {
+    // (pinned bases: hoisted out of the tile loop, the seven per-lane addresses cost 14 registers for a rare path)
+    const gfloat_p o_sc = pin_uniform(ot.sc + sl * sb.tab), o_sh = pin_uniform(ot.sh + sl * sb.tab), sv = pin_uniform(save + sl * sb.save),
+                   cn = pin_uniform(consts + sl * sb.consts);
+    for (int c = tid; c < N; c += 256) {
+      Cs[c] = o_sc[c]; Cs[N + c] = o_sh[c]; Cs[2 * N + c] = sv[2 * c]; Cs[3 * N + c] = sv[2 * c + 1];
+      Cs[4 * N + c] = cn[3 * c]; Cs[5 * N + c] = cn[3 * c + 1]; Cs[6 * N + c] = cn[3 * c + 2];
+    }
+    const gfloat_p i_sc = pin_uniform(it.sc + sl * sb.tab), i_sh = pin_uniform(it.sh + sl * sb.tab), i_fl = pin_uniform(it.fl + sl * sb.tab);
+    for (int c = tid; c < K; c += 256) { Cs[7 * N + c] = i_sc[c]; Cs[7 * N + K + c] = i_sh[c]; Cs[7 * N + 2 * K + c] = i_fl[c]; }
+  };
+  auto stage = [&](long long m0) {
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {
+      const int r = (tid + 256 * j) / (N / 4);
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (m0 + r < M) {
+        const f32x4 o_sc = *reinterpret_cast<const f32x4*>(Cs + 4 * nq), o_sh = *reinterpret_cast<const f32x4*>(Cs + N + 4 * nq),
+                    o_mean = *reinterpret_cast<const f32x4*>(Cs + 2 * N + 4 * nq), o_istd = *reinterpret_cast<const f32x4*>(Cs + 3 * N + 4 * nq),
+                    o_c1 = *reinterpret_cast<const f32x4*>(Cs + 4 * N + 4 * nq), o_c2 = *reinterpret_cast<const f32x4*>(Cs + 5 * N + 4 * nq),
+                    o_k = *reinterpret_cast<const f32x4*>(Cs + 6 * N + 4 * nq);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float zh = (rz[j][q] - o_mean[q]) * o_istd[q];
+          const float gy = rg[j][q] * dsilu_(fmaf(rz[j][q], o_sc[q], o_sh[q]));
+          v[q] = o_k[q] * (gy - o_c1[q] - zh * o_c2[q]);
+        }
+      }
+      *reinterpret_cast<f32x4*>(Gs + r * LDG + 4 * nq) = v;
+      if constexpr (X3) {
+        const bf16x4 vh = __builtin_convertvector(v, bf16x4);
+        const f32x4 r1 = v - __builtin_convertvector(vh, f32x4);
+        const bf16x4 vm = __builtin_convertvector(r1, bf16x4);
+        const f32x4 r2 = r1 - __builtin_convertvector(vm, f32x4);
+        bf16_t* dst = Gp + r * LDK + 4 * nq;
+        *reinterpret_cast<bf16x4*>(dst) = vh;
+        *reinterpret_cast<bf16x4*>(dst + 32 * LDK) = vm;
+        *reinterpret_cast<bf16x4*>(dst + 2 * 32 * LDK) = __builtin_convertvector(r2, bf16x4);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NA; ++j) {
+      const int r = (tid + 256 * j) / (K / 4);
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (m0 + r < M)
+        v = tf4_(rx[j], *reinterpret_cast<const f32x4*>(Cs + 7 * N + 4 * kq), *reinterpret_cast<const f32x4*>(Cs + 7 * N + K + 4 * kq),
+                 *reinterpret_cast<const f32x4*>(Cs + 7 * N + 2 * K + 4 * kq));
+      *reinterpret_cast<f32x4*>(As + r * LDA + 4 * kq) = v;
+    }
+  };
+
+  // fragment (cin tile 2 wave + c, k-step s)
+  gfloat_p wbase = pin_uniform(wf);                  // re-pinned per tile: the loads must stay inside the tile loop (hoisted,
+  const unsigned woff = (2 * wave * NS * 64 + lane) * 4;      // the wave's 2 NS fragments would sit in registers for good)
+  auto wfrag = [&](int c, int s) -> f32x4 { return ldg4(wbase, woff + (c * NS + s) * 256); };
+  // X3: plane t of fragment (cin tile 2 wave + c, k-step j) in the order of w_split3_t_kernel (offsets in floats)
+  auto wfrag3 = [&](int c, int j, int t) -> bf16x8 {
+    return __builtin_bit_cast(bf16x8, ldg4(wbase, (((2 * wave + c) * NJ + j) * 3 + t) * 256 + lane * 4));
+  };
+
+  long long cur_slot = -1;
+  f_slot = t_begin / tiles_per_slot;
+  f_m0 = (t_begin - f_slot * tiles_per_slot) * 32;
+  fetch(false);
+#pragma unroll 1
+  for (long long tile = t_begin; tile < t_end; ++tile) {
+    const long long slot = f_slot, m0 = f_m0;
+    // the first fragments, requested before the staging that hides their way from L2 (behind the fetched tile in the
+    // queue, so the staging's wait for that tile leaves them in flight)
+    f32x4 wa[X3 ? 1 : NS][2];
+    bf16x8 wx[X3 ? 2 * NJ : 1][3];                    // X3: unit u = (k-step u / 2, cin tile u % 2), requested D units ahead
+    wbase = pin_uniform(wf);
+#pragma unroll
+    for (int s = 0; s < D; ++s) {
+      if constexpr (X3) {
+#pragma unroll
+        for (int t = 0; t < 3; ++t) wx[s][t] = wfrag3(s & 1, s >> 1, t);
+      } else {
+#pragma unroll
+        for (int c = 0; c < 2; ++c) wa[s][c] = wfrag(c, s);
+      }
+    }
+    if constexpr (NBUF == 1) __syncthreads();         // previous tile's readers are done
+    if (slot != cur_slot) {                           // (uniform; every wave is past the staging of the previous tile)
+      load_consts(slot);
+      cur_slot = slot;
+      __syncthreads();
+    }
+    if constexpr (NBUF == 2) {
+      Gs = sm + ((tile - t_begin) & 1) * TILE;
+      As = Gs + 32 * LDG;
+    }
+    stage(m0);
+    __syncthreads();                                  // (the readers of THIS buffer, two tiles back, passed the barrier between)
+    // ---- phase 2: g_in[pixel][cin] = sum_cout g_z[pixel][cout] * W[cout][cin]; D = W^T . G^T
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int p = 0; p < 2; ++p) acc[c][p] = f32x4{0.f, 0.f, 0.f, 0.f};
+    auto late_loads = [&]() {                         // behind the tile's last fragment: the store's operand, the next tile
+      if (gadd || accumulate) fetch_store_operand(slot, m0);
+      fetch(tile + 1 < t_end);                        // (unconditional: behind a branch the loaded registers are copied at the join, which waits for them)
+    };
+    if constexpr (X3) {
+      // the six-product bf16 form of pw_x3_kernel, small products first: (w, g) = (l, h) (h, l) (m, m) (m, h) (h, m) (h, h)
+      const bf16_t* xrow = Gp + lm * LDK + 8 * gq;
+#pragma unroll
+      for (int u = 0; u < 2 * NJ; ++u) {
+        const int j = u >> 1, c = u & 1;
+        if (u + D < 2 * NJ) {
+#pragma unroll
+          for (int t = 0; t < 3; ++t) wx[u + D][t] = wfrag3((u + D) & 1, (u + D) >> 1, t);
+        }
+        if (u + D == 2 * NJ - 1) late_loads();
+        __builtin_amdgcn_sched_barrier(0);
+        constexpr int TW[6] = {2, 0, 1, 1, 0, 0}, TX[6] = {0, 2, 1, 0, 1, 0};
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {                 // (the planes are read again for the second cin tile: 12 registers less)
+          bf16x8 xa[3];
+#pragma unroll
+          for (int t = 0; t < 3; ++t) xa[t] = *reinterpret_cast<const bf16x8*>(xrow + t * 32 * LDK + p * 16 * LDK + 32 * j);
+#pragma unroll
+          for (int e = 0; e < 6; ++e) acc[c][p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wx[u][TW[e]], xa[TX[e]], acc[c][p], 0, 0, 0);
+        }
+      }
+    } else {
+      const float* grow = Gs + lm * LDG + 4 * gq;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        if (s + D < NS) {
+#pragma unroll
+          for (int c = 0; c < 2; ++c) wa[s + D][c] = wfrag(c, s + D);
+        }
+        if (s + D == NS - 1) late_loads();
+        __builtin_amdgcn_sched_barrier(0);
+        f32x4 gb[2];
+#pragma unroll
+        for (int p = 0; p < 2; ++p) gb[p] = *reinterpret_cast<const f32x4*>(grow + p * 16 * LDG + 16 * s);
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+          for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[c][p] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[s][c][j], gb[p][j], acc[c][p], 0, 0, 0);
+      }
+    }
+    {
+      float* gxs = gx + slot * sb.grad + m0 * gx_ld;
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+          if (m0 + 16 * p + lm < M) {
+            float* op = gxs + (unsigned)((16 * p + lm) * gx_ld + 16 * (2 * wave + c) + 4 * gq);
+            // shortcut of a bottleneck: the gradient of the sum joins here, then the gradient already there
+            f32x4 v = acc[c][p];
+            if (gadd || accumulate) v += eo[c][p];
+            if (gadd && accumulate) v += *reinterpret_cast<const f32x4*>(op);
+            *reinterpret_cast<f32x4*>(op) = v;
+          }
+    }
+    // ---- phase 3: dW[cout][cin] += sum_pixel g_z[pixel][cout] * a[pixel][cin], split-bf16 products (a weight gradient
+    // is a leaf, see pw_bwd_weight_wide_kernel).  Lane group gq, element e -> pixel 4 gq + (e & 3) + 16 (e >> 2).
+    {
+      const int prow = 4 * gq;
+      bf16x8 bh[DW_BN], bl[DW_BN];
+#pragma unroll
+      for (int b = 0; b < DW_BN; ++b)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float v = As[(prow + (e & 3) + 16 * (e >> 2)) * LDA + 16 * (dw_b0 + b) + lm];
+          const bf16_t h = (bf16_t)v;
+          bh[b][e] = h; bl[b][e] = (bf16_t)(v - (float)h);
+        }
+#pragma unroll
+      for (int a = 0; a < DW_AN; ++a) {
+        bf16x8 ah, al;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float v = Gs[(prow + (e & 3) + 16 * (e >> 2)) * LDG + 16 * (dw_a0 + a) + lm];
+          const bf16_t h = (bf16_t)v;
+          ah[e] = h; al[e] = (bf16_t)(v - (float)h);
+        }
+#pragma unroll
+        for (int b = 0; b < DW_BN; ++b) {
+          f32x4 d = dw[a][b];
+          d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[b], d, 0, 0, 0);
+          d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[b], d, 0, 0, 0);
+          d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[b], d, 0, 0, 0);
+          dw[a][b] = d;
+        }
+      }
+    }
+  }
+  float* dst = rep ? gw + (blockIdx.x % JN_NREP) * JN_WPART_MAX : gw;
+#pragma unroll
+  for (int a = 0; a < DW_AN; ++a)
+#pragma unroll
+    for (int b = 0; b < DW_BN; ++b)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) atomicAdd(&dst[(16 * (dw_a0 + a) + 4 * gq + r) * K + 16 * (dw_b0 + b) + lm], dw[a][b][r]);
+}
+
+template <int CTN, int D, bool X3>
+static void launch_pw_bwd_fused128(const PwBwdFusedArgs& a, hipStream_t s) {
+  constexpr int N = 16 * CTN, K = 128;
+  if (X3) launch_w_split3_t(a.w, a.w_frag, N, K, s);
+  else hipLaunchKernelGGL(w_frag_t_kernel, dim3(N * K / 4 / 256), dim3(256), 0, s, a.w, a.w_frag, N, K);
+  static int places = 0;                // ONE resident round
+  if (!places) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&pw_bwd_fused128_kernel<CTN, D, X3>), 256, 0) != hipSuccess || per_cu < 1) per_cu = 2;
+    places = per_cu * 256;
+  }
+  const long long n_tiles = (a.M + 31) / 32 * a.sb.n;
+  long long bx = std::min<long long>(places, n_tiles);
+  if (a.max_wg > 0) bx = std::min<long long>(bx, a.max_wg);
+  const int rep = (a.wpart && N * K <= JN_WPART_MAX) ? 1 : 0;
+  hipLaunchKernelGGL((pw_bwd_fused128_kernel<CTN, D, X3>), dim3((unsigned)bx), dim3(256), 0, s, a.g, a.g_ld, a.z, a.z_ld, a.ot, a.save,
+                     a.consts, a.x, a.x_ld, a.it, a.w_frag, a.gx, a.gx_ld, a.accumulate, rep ? a.wpart : a.gw, rep, a.M, a.sb,
+                     a.gadd, a.gadd_ld);
+  if (rep) launch_wpart_reduce(a.gw, a.wpart, N * K, s);
+}
+
+// shapes and operands pw_bwd_fused128_kernel takes (cin = 128 never reduces its input: pw_bwd_fused_reduces_input)
+static bool pw_bwd_fused128_takes(const PwBwdFusedArgs& a) {
+  return a.w_frag && a.route != 1 && a.cin == 128 && (a.cout == 128 || a.cout == 64) && !a.red_in && !a.red_in2 && !a.red2_z &&
+         a.g_ld % 4 == 0 && a.z_ld % 4 == 0 && a.x_ld % 4 == 0 && a.gx_ld % 4 == 0 && (!a.gadd || a.gadd_ld % 4 == 0) &&
+         reinterpret_cast<uintptr_t>(a.w_frag) % 16 == 0;
+}
+
 bool pw_bwd_fused_reduces_input(int cout, int cin) { return pw_bwd_fused_supported(cout, cin) && cin <= 64; }   // (cin = 128 measured: the epilogue of the one-workgroup-per-CU kernels costs more than the 28x28 passes it saves, profiles/r04_ab_red128.txt)
 
 bool pw_bwd_fused_supported(int cout, int cin) {
@@ -854,6 +1199,10 @@ bool pw_bwd_fused_supported(int cout, int cin) {
 
 int launch_pw_bwd_fused(const PwBwdFusedArgs& a, hipStream_t s) {
   const int tn = a.cout / 16, tk = a.cin / 16;
+  if (pw_bwd_fused128_takes(a)) {
+    if (tn == 8) launch_pw_bwd_fused128<8, 2, true>(a, s); else launch_pw_bwd_fused128<4, 2, false>(a, s);
+    return 0;
+  }
 #define JN_PF(A, B) if (tn == A && tk == B) { launch_pw_bwd_fused_t<A, B>(a, s); return 0; }
   JN_PF(1, 1) JN_PF(1, 2) JN_PF(1, 4) JN_PF(1, 8) JN_PF(2, 1) JN_PF(2, 2) JN_PF(2, 4) JN_PF(2, 8)
   JN_PF(4, 1) JN_PF(4, 2) JN_PF(4, 4) JN_PF(4, 8) JN_PF(8, 1) JN_PF(8, 2) JN_PF(8, 4) JN_PF(8, 8)

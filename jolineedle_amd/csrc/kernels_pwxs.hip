@@ -652,6 +652,11 @@ __global__ __launch_bounds__(256) void w_split3_t_kernel(const float* __restrict
   *reinterpret_cast<bf16x8*>(o + 1024) = l;
 }
 
+int launch_w_split3_t(const float* w, void* w3t, int cout, int cin, hipStream_t s) {
+  hipLaunchKernelGGL(w_split3_t_kernel, dim3((unsigned)((cin * (cout / 8) + 255) / 256)), dim3(256), 0, s, w, (bf16_t*)w3t, cout, cin);
+  return 0;
+}
+
 // shapes (cout = the gradient's K, cin = its N) this route takes
 bool pw_x3_bwd_data_supported(int cout, int cin) {
   return (cout == 256 && (cin == 128 || cin == 256 || cin == 512)) || (cout == 128 && cin == 256);
@@ -664,7 +669,7 @@ int launch_pw_x3_bwd_data(const ConvArgs& a, const float* w, void* w3t, hipStrea
   if (!pw_x3_bwd_data_supported(K, N) || a.accumulate || a.in_dtype != JN_F32 || a.out_dtype != JN_F32 || a.bias ||
       a.act != ACT_NONE || a.in_ld % 4 != 0 || a.out_ld % 4 != 0 || a.stats)
     return -1;
-  hipLaunchKernelGGL(w_split3_t_kernel, dim3((unsigned)((N * (K / 8) + 255) / 256)), dim3(256), 0, s, w, (bf16_t*)w3t, K, N);
+  launch_w_split3_t(w, w3t, K, N, s);
   const long long M = (long long)a.N * a.H * a.W;
   ConvArgs b = a;
   b.w_x3 = w3t; b.up_out = nullptr;
