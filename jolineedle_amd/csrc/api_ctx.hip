@@ -403,6 +403,8 @@ int jn_destroy(jn_ctx* ctx) {
   for (auto& e : ctx->conv_ev) (void)hipEventDestroy(e);
   if (ctx->aux_fork) (void)hipEventDestroy(ctx->aux_fork);
   if (ctx->aux_join) (void)hipEventDestroy(ctx->aux_join);
+  if (ctx->steps_ev) (void)hipEventDestroy(ctx->steps_ev);
+  if (ctx->n_done_host) (void)hipHostFree(ctx->n_done_host);
   if (ctx->aux_stream) (void)hipStreamDestroy(ctx->aux_stream);
   delete ctx;
   return JN_OK;

@@ -177,7 +177,7 @@ int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const
     a.skip_flag = flag; a.skip_when = B;
     a.tok_emb_out = train ? ctx->tok_emb_train : nullptr;
     a.pdrop = train ? ctx->pdrop : 0.0f; a.drop_seed = ctx->drop_seed_used;
-    launch_gpt_step(a, s);
+    JN_CHECK(launch_gpt_step(a, s) == 0, JN_ESTATE, "gpt_step_kernel could not be launched (n_embd %d, block_size %d)", a.C, a.Tmax - 1);
     if (out->patches_dev)
       env_gather(e, out->patches_dev + (long long)(t + 1) * 3 * P * P, patch_stride, P, flag, B, s);
     if (vm && (t + 1 < T || do_detection)) stage_fill(e, P, t + 1, flag, B, s);    // read by the next step and the detector
@@ -192,6 +192,36 @@ int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const
   if (ctx->ev[1]) JN_HIP(hipEventRecord(ctx->ev[1], s));
   JN_HIP(hipGetLastError());
   ctx->last_T = T;
+  return JN_OK;
+}
+
+int rollout_steps_begin(jn_ctx* ctx, hipStream_t s) {
+  JN_CHECK(ctx && ctx->last_T > 0, JN_ESTATE, "no rollout has run");
+  JN_HIP(hipSetDevice(ctx->cfg.device));
+  const int n = ctx->last_T + 1;
+  if (ctx->n_done_host_n < n) {
+    // (a copy of an earlier _begin that no _end waited for — an error between the two — may still be on its way there)
+    if (ctx->steps_ev) JN_HIP(hipEventSynchronize(ctx->steps_ev));
+    if (ctx->n_done_host) JN_HIP(hipHostFree(ctx->n_done_host));
+    ctx->n_done_host = nullptr; ctx->n_done_host_n = 0;
+    JN_HIP(hipHostMalloc(reinterpret_cast<void**>(&ctx->n_done_host), (size_t)n * sizeof(int32_t), hipHostMallocDefault));
+    ctx->n_done_host_n = n;
+  }
+  if (!ctx->steps_ev) JN_HIP(hipEventCreateWithFlags(&ctx->steps_ev, hipEventDisableTiming));
+  JN_HIP(hipMemcpyAsync(ctx->n_done_host, ctx->n_done, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  JN_HIP(hipEventRecord(ctx->steps_ev, s));
+  return JN_OK;
+}
+
+int rollout_steps_end(jn_ctx* ctx, int* n_steps) {
+  JN_CHECK(ctx && n_steps && ctx->steps_ev && ctx->n_done_host, JN_ESTATE, "rollout_steps_end without rollout_steps_begin");
+  JN_HIP(hipEventSynchronize(ctx->steps_ev));
+  const int T = ctx->last_T, B = ctx->env.B;
+  int S = T;
+  if (ctx->last_stop_early)
+    for (int t = 1; t <= T; ++t)
+      if (ctx->n_done_host[t] >= B) { S = t; break; }
+  *n_steps = S;
   return JN_OK;
 }
 
@@ -221,17 +251,9 @@ int jn_set_rollout_teacher(jn_ctx* ctx, const uint8_t* targets_dev, uint8_t* set
 
 int jn_rollout_steps(jn_ctx* ctx, int* n_steps, void* stream) {
   JN_CHECK(ctx && n_steps && ctx->last_T > 0, JN_ESTATE, "no rollout has run");
-  JN_HIP(hipSetDevice(ctx->cfg.device));
-  const int T = ctx->last_T, B = ctx->env.B;
-  std::vector<int32_t> h(T + 1);
-  JN_HIP(hipMemcpyAsync(h.data(), ctx->n_done, (T + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
-  JN_HIP(hipStreamSynchronize((hipStream_t)stream));
-  int S = T;
-  if (ctx->last_stop_early)
-    for (int t = 1; t <= T; ++t)
-      if (h[t] >= B) { S = t; break; }
-  *n_steps = S;
-  return JN_OK;
+  int rc = rollout_steps_begin(ctx, (hipStream_t)stream);
+  if (rc) return rc;
+  return rollout_steps_end(ctx, n_steps);
 }
 
 int jn_set_profiling(jn_ctx* ctx, int enabled) {

@@ -19,6 +19,17 @@ void fill_gpt_weights(const jn_ctx* ctx, GptStepArgs& a) {
   a.layers = ctx->layers_dev; a.emb_part = ctx->emb_part; a.KS = ctx->KS; a.efpn_lin_b = g.efpn_lin_b;
   a.kcache = ctx->kcache; a.vcache = ctx->vcache; a.prev_action = ctx->prev_action; a.cache_len = ctx->cache_len;
   a.n_done = ctx->n_done;
+  // head_wt, ln_f and the layers are packed one after the other (load_weights' order): the step kernel warms L2 with that
+  // run.  Should the order ever change, the run is no longer one piece and the kernel is told nothing.
+  a.pf_base = nullptr; a.pf_floats = 0;
+  if (!g.layers.empty()) {
+    const GptW::Layer& last = g.layers.back();
+    const size_t C = c.n_embd, per_layer = 12 * C * C + 13 * C;
+    const long long run = (last.fc2_b + C) - g.head_wt;
+    if (run > 0 && (size_t)run <= (size_t)c.n_actions * C + 2 * C + g.layers.size() * (per_layer + 12 * 16) + 64) {
+      a.pf_base = g.head_wt; a.pf_floats = run;
+    }
+  }
 }
 
 // the per-token buffers of a training forward (a train-mode rollout or the supervised forward) and its backward
@@ -64,7 +75,7 @@ static int teacher_forced_decode(jn_ctx* ctx, const int64_t* actions_dev, const 
       a.pos_index = prev_emb_dev ? 0 : i;                 // recurrent tokens always get position 0 (gpt.py:431-449)
       a.tok_emb = tok_emb; a.tok_emb_stride = tok_emb_stride; a.tok_emb_index = i;
     }
-    launch_gpt_step(a, s);
+    JN_CHECK(launch_gpt_step(a, s) == 0, JN_ESTATE, "gpt_step_kernel could not be launched (n_embd %d, block_size %d)", a.C, a.Tmax - 1);
   }
   return JN_OK;
 }
@@ -197,22 +208,30 @@ static int check_can_train(const jn_ctx* ctx) {
   return JN_OK;
 }
 
-// loss.backward() of a train-mode rollout given d loss / d logits in ctx->dlogits: causal GPT over the trajectory
-// (teacher-forced recompute), embed_fpn, then the patch encoder of all S executed glimpse steps, step-batched.
-static int reinforce_backward_impl(jn_ctx* ctx, const jn_rollout_out* out, int S, int stop_early, hipStream_t s) {
+// loss.backward() of a train-mode rollout given d loss / d logits in ctx->dlogits, in two halves.  The first, the causal
+// GPT over the trajectory (teacher-forced recompute), finds the number of executed steps on the device (n_done), so the
+// callers enqueue it BEFORE the host asks for that number: the host's one sync of the iteration then overlaps with the
+// queued launches instead of being followed by 77 short launches against an idle GPU.
+static int reinforce_backward_gpt(jn_ctx* ctx, const jn_rollout_out* out, int stop_early, hipStream_t s) {
   int rc;
   if ((rc = build_grad_layer_table(ctx))) return rc;
-  const jn_config& c = ctx->cfg;
   const EnvState& e = ctx->env;
-  const int B = e.B, T = e.T, C = c.n_embd, K = ctx->efpn_h * ctx->efpn_w * C;
+  const int B = e.B, T = e.T;
   GptBwdArgs ba{};
   fill_gpt_bwd_common(ctx, ba);
   ba.B = B; ba.T = T; ba.stop_early = stop_early ? 1 : 0;
   ba.final_emb = out->final_emb_dev; ba.actions = out->actions_dev;
   ba.positions = out->positions_dev; ba.pos_tokens = T + 1; ba.pos1d_by_token = 0; ba.tok_actions = nullptr;
   ba.dte_stride_b = 1; ba.dte_stride_t = B;          // [T][B][C]: the rows of one glimpse step are contiguous
-  if ((rc = launch_gpt_bwd(ctx, ba, s))) return rc;
+  return launch_gpt_bwd(ctx, ba, s);
+}
 
+// The second half needs S on the host: embed_fpn, then the patch encoder of all S executed glimpse steps, step-batched.
+static int reinforce_backward_encoder(jn_ctx* ctx, const jn_rollout_out* out, int S, hipStream_t s) {
+  int rc;
+  const jn_config& c = ctx->cfg;
+  const EnvState& e = ctx->env;
+  const int B = e.B, T = e.T, C = c.n_embd, K = ctx->efpn_h * ctx->efpn_w * C;
   // patch-encoder side: all executed glimpse steps in ONE set of launches (chunks of net.g_slots steps
   // when the gradient buffers of a whole trajectory do not fit): embed_fpn backward, then the PAFPN.
   if (ctx->profiling && ctx->ev[2]) JN_HIP(hipEventRecord(ctx->ev[2], s));     // conv-stack backward section (bench.py)
@@ -421,10 +440,12 @@ int jn_reinforce_backward(jn_ctx* ctx, const float* dlogprobs_dev, const float* 
   const jn_rollout_out* out = &ctx->train_out;
   const EnvState& e = ctx->env;
   int S = 0, rc;
-  if ((rc = jn_rollout_steps(ctx, &S, stream))) return rc;
   launch_logits_grad(out->logits_dev, out->actions_dev, dlogprobs_dev, dentropies_dev, ctx->n_done, ctx->dlogits, e.B, e.T,
                      ctx->cfg.n_actions, ctx->last_stop_early ? 1 : 0, s);
-  return reinforce_backward_impl(ctx, out, S, ctx->last_stop_early ? 1 : 0, s);
+  if ((rc = rollout_steps_begin(ctx, s))) return rc;
+  if ((rc = reinforce_backward_gpt(ctx, out, ctx->last_stop_early ? 1 : 0, s))) return rc;
+  if ((rc = rollout_steps_end(ctx, &S))) return rc;
+  return reinforce_backward_encoder(ctx, out, S, s);
 }
 
 int jn_reinforce_step(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const int64_t* start_positions_dev,
@@ -440,17 +461,18 @@ int jn_reinforce_step(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, 
   ctx->train_out = *out; ctx->train_out_valid = true;
   const EnvState& e = ctx->env;
   const int B = e.B, T = e.T, nA = ctx->cfg.n_actions;
-  int S = 0;
-  if ((rc = jn_rollout_steps(ctx, &S, stream))) return rc;      // the one host sync of the iteration
-
   LossArgs la{};
   la.logits = out->logits_dev; la.actions = out->actions_dev; la.returns = out->returns_dev; la.rewards = out->rewards_dev;
   la.logit_masks = out->logit_masks_dev; la.n_done = ctx->n_done; la.dlogits = ctx->dlogits; la.metrics = metrics_dev;
   la.B = B; la.T = T; la.nA = nA; la.stop_early = stop_early ? 1 : 0; la.reward_norm = opts->reward_norm;
   la.ret_mean = opts->ret_mean; la.ret_std = opts->ret_std; la.entropy_weight = opts->entropy_weight;
   la.scale = opts->loss_scale;
+  if ((rc = rollout_steps_begin(ctx, s))) return rc;           // n_done on its way to the host ...
   launch_reinforce_loss(la, s);
-  return reinforce_backward_impl(ctx, out, S, stop_early, s);
+  if ((rc = reinforce_backward_gpt(ctx, out, stop_early, s))) return rc;
+  int S = 0;
+  if ((rc = rollout_steps_end(ctx, &S))) return rc;             // ... the one host wait of the iteration: the GPU runs the queued GPT backward meanwhile
+  return reinforce_backward_encoder(ctx, out, S, s);
 }
 
 // One supervised (teacher-forced) training step minus the optimiser: forward, CrossEntropy(weight[STOP] = stop_weight)

@@ -295,6 +295,9 @@ struct jn_ctx {
   float* vcache = nullptr;
   float* logits_ws = nullptr;     // [B, nA]
   int32_t* n_done = nullptr;      // [T+1] number of finished envs after step t (index t+1)
+  int32_t* n_done_host = nullptr; // pinned copy of n_done (rollout_steps_begin / _end); n_done_host_n ints
+  int n_done_host_n = 0;
+  hipEvent_t steps_ev = nullptr;  // behind that copy
   int64_t* prev_action = nullptr; // [B]
   int32_t* cache_len = nullptr;   // [B]
   int last_T = 0;
@@ -390,6 +393,10 @@ int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const
                  int do_detection, int stop_early, const jn_rollout_out* out, int train, void* stream);
 // api_train.hip
 void fill_gpt_weights(const jn_ctx* ctx, GptStepArgs& a);
+// jn_rollout_steps in two halves: _begin enqueues the copy of n_done to pinned memory and an event behind it, _end waits
+// for that event alone — whatever the caller enqueues between the two runs while the host waits and reads
+int rollout_steps_begin(jn_ctx* ctx, hipStream_t s);
+int rollout_steps_end(jn_ctx* ctx, int* n_steps);
 int ensure_token_train_buffers(jn_ctx* ctx);
 
 }  // namespace jnr

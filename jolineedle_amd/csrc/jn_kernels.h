@@ -395,6 +395,8 @@ struct GptStepArgs {
   const float *wte, *wpe, *embed_class, *proj_wt, *proj_b, *pos1d, *pe2, *head_wt, *lnf_w, *lnf_b;
   const int64_t* classes;           // [B] class id of every agent's class token (gpt.py:476-478), or null = class 0
   const GptLayerPtrs* layers;       // device array [n_layer]
+  int kv_lds;                       // set by launch_gpt_step: the K / V rows of a layer are staged in LDS
+  const float* pf_base; long long pf_floats;   // the run of the arena that holds head, ln_f and every layer (0: unknown)
   const float* emb_part; int KS; const float* efpn_lin_b;   // patch-embedding split-K partials [B][KS][C]
   float *kcache, *vcache;           // [L][B][Tmax][C]
   int64_t* prev_action; int32_t* cache_len;

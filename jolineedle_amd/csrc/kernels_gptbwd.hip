@@ -3,7 +3,8 @@
 // kernels_train.hip, which gives one workgroup to each agent and therefore occupies B compute units).
 //
 // Here every phase is one launch over ALL tokens of ALL agents: rows m = agent * Lm + token (Lm = T + 1), the forward is
-// recomputed into a row-major scratch, and each Linear is one small fp32 GEMM (64 x 64 tiles through LDS, FMA):
+// recomputed into a row-major scratch, and each Linear is one small fp32 GEMM (tiles through LDS, FMA; the token-row
+// products by gptb_tok_gemm_kernel, or gptb_gemm_kernel for K > 192, the weight gradients by gptb_wgrad_kernel):
 //   forward     out[M x N]  = in[M x K] . Wt[K x N]                     (Wt: the arena's transposed Linear weight)
 //   data grad   din[M x K]  = dout[M x N] . Wt^T
 //   weight grad gWt[K x N] += in^T[K x M] . dout[M x N]
@@ -44,12 +45,12 @@ struct GemmArgs {
   const float* mulp;                         // * gelu'(mulp[m][n])
   int a_gelu;                                // A elements pass through gelu on load
   int accumulate;                            // C += result
-  int tok_dim;                               // 0: m runs over token rows, 1: k does (weight gradients)
-  int k_per_block;                           // tok_dim 1: the reduction is split over gridDim.z workgroups (atomic C +=)
+  int tok_dim;                               // 0: m runs over token rows (gptb_tok_gemm_kernel / gptb_gemm_kernel), 1: k does (gptb_wgrad_kernel)
   const int* L; int Lm;                      // a token row r is live iff r % Lm < *L
   float pdrop; uint64_t seed; int site, layer;   // site >= 0: dropout (jn_device.h drop_scale) of product + bias
 };
 
+// The token-row GEMM for the shapes gptb_tok_gemm_kernel does not take (K > TG_KMAX: wide models): 64 x 64 tiles, K in steps of 16.
 template <bool A_KFAST, bool B_NFAST>
 __global__ __launch_bounds__(GT) void gptb_gemm_kernel(GemmArgs g) {
   constexpr int BM = 64, BN = 64, BK = 16;
@@ -62,9 +63,8 @@ __global__ __launch_bounds__(GT) void gptb_gemm_kernel(GemmArgs g) {
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = 0.0f;
-  const int kbeg = g.k_per_block > 0 ? blockIdx.z * g.k_per_block : 0;
-  const int kend = g.k_per_block > 0 ? min(g.K, kbeg + g.k_per_block) : g.K;
-  for (int k0 = kbeg; k0 < kend; k0 += BK) {
+  const int kend = g.K;
+  for (int k0 = 0; k0 < kend; k0 += BK) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int idx = tid + q * GT;
@@ -73,8 +73,7 @@ __global__ __launch_bounds__(GT) void gptb_gemm_kernel(GemmArgs g) {
       const int gm = m0 + m, gk = k0 + k;
       float v = 0.0f;
       if (gm < g.M && gk < kend) {
-        const bool live = g.tok_dim == 0 ? (gm % g.Lm) < L : (gk % g.Lm) < L;
-        if (live) {
+        if ((gm % g.Lm) < L) {
           v = g.A[(long long)gm * g.a_rs + (long long)gk * g.a_cs];
           if (g.a_gelu) v = gelu_fb(v);
         }
@@ -88,7 +87,7 @@ __global__ __launch_bounds__(GT) void gptb_gemm_kernel(GemmArgs g) {
       if (B_NFAST) { n = idx & 63; k = idx >> 6; } else { k = idx & 15; n = idx >> 4; }
       const int gn = n0 + n, gk = k0 + k;
       float v = 0.0f;
-      if (gn < g.N && gk < kend && (g.tok_dim == 0 || (gk % g.Lm) < L)) v = g.B[(long long)gk * g.b_rs + (long long)gn * g.b_cs];
+      if (gn < g.N && gk < kend) v = g.B[(long long)gk * g.b_rs + (long long)gn * g.b_cs];
       Bs[k][n] = v;
     }
     __syncthreads();
@@ -108,7 +107,7 @@ __global__ __launch_bounds__(GT) void gptb_gemm_kernel(GemmArgs g) {
   for (int i = 0; i < 4; ++i) {
     const int gm = m0 + ty * 4 + i;
     if (gm >= g.M) continue;
-    const bool live = g.tok_dim != 0 || (gm % g.Lm) < L;
+    const bool live = (gm % g.Lm) < L;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int gn = n0 + tx * 4 + j;
@@ -123,18 +122,278 @@ __global__ __launch_bounds__(GT) void gptb_gemm_kernel(GemmArgs g) {
       } else {
         v = 0.0f;
       }
-      if (g.k_per_block > 0) atomicAdd(&g.C[o], v);
-      else g.C[o] = g.accumulate ? g.C[o] + v : v;
+      g.C[o] = g.accumulate ? g.C[o] + v : v;
     }
   }
 }
 
-void gemm(GemmArgs g, hipStream_t s) {
-  dim3 grid((g.N + 63) / 64, (g.M + 63) / 64);
-  if (g.tok_dim == 1 && g.accumulate) {      // few output tiles, long reduction: slices of 128 tokens, combined with atomics
-    g.k_per_block = 128;
-    grid.z = (g.K + 127) / 128;
+// Token-row GEMMs (tok_dim 0: m runs over token rows, A's rows contiguous) with K <= TG_KMAX, 28 of the 40 GEMMs of a
+// backward.  gptb_gemm_kernel walks K in steps of 16 with an exposed global round trip and two barriers per step, on 21 -
+// 63 workgroups.  Here a workgroup takes 32 rows x 64 columns (42 x ceil(N / 64) workgroups at the headline's 1344 rows),
+// stages the WHOLE K of both operands in one round with every load in flight — 16-byte loads where the operand's fast
+// axis and alignment allow (vec_a / vec_b, decided by the launcher), guarded 4-byte loads otherwise (the head: N or K =
+// n_actions) — and passes ONE barrier.  A row's liveness is computed once by each of the eight threads that load it.
+// Each output element is one ascending-k fmaf chain from zero, followed by gptb_gemm_kernel's epilogue in its order
+// (bias, dropout, residual, gelu'), so the results equal that kernel's bit for bit.  fp32 VALU on purpose.
+constexpr int TG_BM = 32, TG_BN = 64, TG_KMAX = 192;
+inline int tg_lda(int K) { return ((K + 3) & ~3) + 4; }      // keeps rows 16-byte aligned, spreads the row groups over the banks
+inline size_t tg_lds_bytes(int K) { return ((size_t)TG_BM * tg_lda(K) + (size_t)((K + 3) & ~3) * TG_BN) * sizeof(float); }
+
+template <bool B_NFAST>
+__global__ __launch_bounds__(GT) void gptb_tok_gemm_kernel(GemmArgs g, int vec_a, int vec_b) {
+  using f4 = __attribute__((ext_vector_type(4))) float;
+  extern __shared__ __attribute__((aligned(16))) float tg_sm[];
+  const int K = g.K, K4 = (K + 3) & ~3, lda = K4 + 4;
+  float* As = tg_sm;                       // [TG_BM][lda]   A(m, k)
+  float* Bs = As + TG_BM * lda;            // [K4][TG_BN]    B(k, n)
+  const int tid = threadIdx.x, m0 = blockIdx.y * TG_BM, n0 = blockIdx.x * TG_BN;
+  const int L = *g.L;
+  // ---- A: thread = (row, one of eight lanes of the row); a dead or absent row is zeros
+  {
+    const int m = tid >> 3, r = tid & 7, gm = m0 + m;
+    const bool live = gm < g.M && (gm % g.Lm) < L;
+    const float* ap = g.A + (long long)gm * g.a_rs;
+    float* as = As + m * lda;
+    if (vec_a) {
+      // every load of the thread first (a dead row reads row 0 and is zeroed by a select: no branch around a load)
+      constexpr int NA = TG_KMAX / 4 / 8;
+      const float* src = live ? ap : g.A;
+      const int KQ = K4 >> 2;
+      f4 v[NA];
+#pragma unroll
+      for (int j = 0; j < NA; ++j) v[j] = *reinterpret_cast<const f4*>(src + 4 * min(r + 8 * j, KQ - 1));
+#pragma unroll
+      for (int j = 0; j < NA; ++j) {
+        const int kq = r + 8 * j;
+        f4 w = v[j];
+        if (g.a_gelu) { w.x = gelu_fb(w.x); w.y = gelu_fb(w.y); w.z = gelu_fb(w.z); w.w = gelu_fb(w.w); }
+        if (!live) w = f4{0.f, 0.f, 0.f, 0.f};
+        if (kq < KQ) *reinterpret_cast<f4*>(as + 4 * kq) = w;
+      }
+    } else {
+      for (int k = r; k < K4; k += 8) {
+        float v = 0.0f;
+        if (live && k < K) { v = ap[k]; if (g.a_gelu) v = gelu_fb(v); }
+        as[k] = v;
+      }
+    }
   }
+  // ---- B: columns past N and rows past K are zeros
+  if (B_NFAST) {                           // B(k, n) = B[k * b_rs + n]
+    if (vec_b) {                           // K % 4 == 0 is not needed here, N % 4 == 0 is
+      constexpr int NB = TG_KMAX * (TG_BN / 4) / GT;
+      f4 v[NB];
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        const int e = tid + j * GT, k = min(e >> 4, K - 1), gn = n0 + 4 * (e & 15);
+        v[j] = *reinterpret_cast<const f4*>(g.B + (long long)k * g.b_rs + (gn < g.N ? gn : 0));
+      }
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        const int e = tid + j * GT, k = e >> 4, nq = e & 15;
+        const bool in = k < K && n0 + 4 * nq < g.N;
+        if (k < K4) *reinterpret_cast<f4*>(Bs + k * TG_BN + 4 * nq) = in ? v[j] : f4{0.f, 0.f, 0.f, 0.f};
+      }
+    } else {
+      for (int e = tid; e < K4 * TG_BN; e += GT) {
+        const int k = e >> 6, n = e & 63, gn = n0 + n;
+        Bs[e] = (k < K && gn < g.N) ? g.B[(long long)k * g.b_rs + gn] : 0.0f;
+      }
+    }
+  } else {                                 // B(k, n) = B[n * b_cs + k]: lanes run over n, so the LDS writes do not collide
+    if (vec_b) {                           // K % 4 == 0
+      constexpr int NB = (TG_KMAX / 4) * TG_BN / GT;
+      const int KQ = K >> 2;
+      f4 v[NB];
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        const int e = tid + j * GT, kq = min(e >> 6, KQ - 1), gn = n0 + (e & 63);
+        v[j] = *reinterpret_cast<const f4*>(g.B + (long long)(gn < g.N ? gn : 0) * g.b_cs + 4 * kq);
+      }
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        const int e = tid + j * GT, kq = e >> 6, n = e & 63;
+        const f4 w = n0 + n < g.N ? v[j] : f4{0.f, 0.f, 0.f, 0.f};
+        if (kq < KQ) {
+          float* bs = Bs + (4 * kq) * TG_BN + n;
+          bs[0] = w.x; bs[TG_BN] = w.y; bs[2 * TG_BN] = w.z; bs[3 * TG_BN] = w.w;
+        }
+      }
+    } else {
+      for (int e = tid; e < K4 * TG_BN; e += GT) {
+        const int k = e >> 6, n = e & 63, gn = n0 + n;
+        Bs[e] = (k < K && gn < g.N) ? g.B[(long long)gn * g.b_cs + k] : 0.0f;
+      }
+    }
+  }
+  __syncthreads();
+  // ---- 2 rows x 4 columns per thread, one ascending-k chain per element (the zero padding past K is never added)
+  const int ty = tid >> 4, tx = tid & 15;
+  const float* a0 = As + (2 * ty) * lda;
+  const float* a1 = a0 + lda;
+  const float* bp = Bs + 4 * tx;
+  float acc[2][4];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0.0f;
+  int k = 0;
+  for (; k + 4 <= K; k += 4) {
+    const f4 x0 = *reinterpret_cast<const f4*>(a0 + k), x1 = *reinterpret_cast<const f4*>(a1 + k);
+    const float xa[2][4] = {{x0.x, x0.y, x0.z, x0.w}, {x1.x, x1.y, x1.z, x1.w}};
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      const f4 b = *reinterpret_cast<const f4*>(bp + (k + kk) * TG_BN);
+      const float bb[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(xa[i][kk], bb[j], acc[i][j]);
+    }
+  }
+  for (; k < K; ++k) {
+    const f4 b = *reinterpret_cast<const f4*>(bp + k * TG_BN);
+    const float bb[4] = {b.x, b.y, b.z, b.w};
+    const float xa[2] = {a0[k], a1[k]};
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(xa[i], bb[j], acc[i][j]);
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int gm = m0 + 2 * ty + i;
+    if (gm >= g.M) continue;
+    const bool live = (gm % g.Lm) < L;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int gn = n0 + tx * 4 + j;
+      if (gn >= g.N) continue;
+      const long long o = (long long)gm * g.c_rs + gn;
+      float v = acc[i][j];
+      if (live) {
+        if (g.bias) v += g.bias[gn];
+        if (g.site >= 0 && g.pdrop > 0.0f) v *= drop_scale(g.seed, gm / g.Lm, gm % g.Lm, g.layer, g.site, gn, g.pdrop);
+        if (g.resid) v += g.resid[o];
+        if (g.mulp) v *= gelu_db(g.mulp[o]);
+      } else {
+        v = 0.0f;
+      }
+      g.C[o] = g.accumulate ? g.C[o] + v : v;
+    }
+  }
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// Launches the token-row kernel when it takes the shape; false: the caller's kernel does.
+bool tok_gemm(const GemmArgs& g, hipStream_t s) {
+  const bool bn = g.b_cs == 1, bk = g.b_rs == 1;
+  if (g.tok_dim != 0 || g.a_cs != 1 || g.K > TG_KMAX || g.K < 1 || !(bn || bk)) return false;
+  const size_t lds = tg_lds_bytes(g.K);
+  static bool raised = false;
+  if (!raised) {
+    const int most = (int)tg_lds_bytes(TG_KMAX);
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gptb_tok_gemm_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gptb_tok_gemm_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess)
+      return false;
+    raised = true;
+  }
+  const int vec_a = (g.K & 3) == 0 && (g.a_rs & 3) == 0 && aligned16(g.A);
+  const int vec_b = bn ? ((g.N & 3) == 0 && (g.b_rs & 3) == 0 && aligned16(g.B)) : ((g.K & 3) == 0 && (g.b_cs & 3) == 0 && aligned16(g.B));
+  const dim3 grid((g.N + TG_BN - 1) / TG_BN, (g.M + TG_BM - 1) / TG_BM);
+  if (bn) hipLaunchKernelGGL((gptb_tok_gemm_kernel<true>), grid, dim3(GT), lds, s, g, vec_a, vec_b);
+  else hipLaunchKernelGGL((gptb_tok_gemm_kernel<false>), grid, dim3(GT), lds, s, g, vec_a, vec_b);
+  return true;
+}
+
+// Weight gradients: gWt[Kf x N] += in^T . dout over the token rows, and the bias gradient gb[N] += column sums of dout.
+// A workgroup takes 64 features x 64 columns and a slice of WG_ROWS token rows: both operand tiles (in[rows][64 features],
+// dout[rows][64 columns], both contiguous along the tile's fast axis) are staged whole with every load in flight, one
+// barrier, one ascending chain over the slice's rows per element, then fp32 atomics into gWt (the slices of a tile meet
+// there, in no fixed order — as the 128-row slices of gptb_gemm_kernel did; these sums are held to the oracle, not to
+// bits).  The workgroups of the first feature tile also add their dout tile's column sums — it is in LDS, dead rows are
+// zeros in it — into gb: the separate column-sum launches that re-read dout are gone.
+constexpr int WG_ROWS = 64;
+__global__ __launch_bounds__(GT) void gptb_wgrad_kernel(GemmArgs g, float* __restrict__ gb, int vec_a, int vec_b) {
+  using f4 = __attribute__((ext_vector_type(4))) float;
+  __shared__ __attribute__((aligned(16))) float As[WG_ROWS][64], Bs[WG_ROWS][64];
+  const int tid = threadIdx.x, f0 = blockIdx.y * 64, n0 = blockIdx.x * 64, r0 = blockIdx.z * WG_ROWS;
+  const int L = *g.L, Kf = g.M, N = g.N, R = g.K;           // features, columns, token rows
+  if (vec_a && vec_b) {
+    f4 va[4], vb[4];
+    bool la[4], lb[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {                            // (row, quad): all eight loads first, dead / absent parts zeroed by selects
+      const int e = tid + j * GT, r = e >> 4, q4 = 4 * (e & 15), gr = r0 + r;
+      const bool live = gr < R && (gr % g.Lm) < L;
+      la[j] = live && f0 + q4 < Kf; lb[j] = live && n0 + q4 < N;
+      const long long row = live ? gr : 0;
+      va[j] = *reinterpret_cast<const f4*>(g.A + row * g.a_cs + (la[j] ? f0 + q4 : 0));
+      vb[j] = *reinterpret_cast<const f4*>(g.B + row * g.b_rs + (lb[j] ? n0 + q4 : 0));
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int e = tid + j * GT, r = e >> 4, q4 = 4 * (e & 15);
+      f4 a = va[j];
+      if (g.a_gelu) { a.x = gelu_fb(a.x); a.y = gelu_fb(a.y); a.z = gelu_fb(a.z); a.w = gelu_fb(a.w); }
+      *reinterpret_cast<f4*>(&As[r][q4]) = la[j] ? a : f4{0.f, 0.f, 0.f, 0.f};
+      *reinterpret_cast<f4*>(&Bs[r][q4]) = lb[j] ? vb[j] : f4{0.f, 0.f, 0.f, 0.f};
+    }
+  } else {
+    for (int e = tid; e < WG_ROWS * 64; e += GT) {
+      const int r = e >> 6, c = e & 63, gr = r0 + r;
+      const bool live = gr < R && (gr % g.Lm) < L;
+      float a = 0.0f, b = 0.0f;
+      if (live && f0 + c < Kf) { a = g.A[(long long)gr * g.a_cs + f0 + c]; if (g.a_gelu) a = gelu_fb(a); }
+      if (live && n0 + c < N) b = g.B[(long long)gr * g.b_rs + n0 + c];
+      As[r][c] = a; Bs[r][c] = b;
+    }
+  }
+  __syncthreads();
+  const int ty = tid >> 4, tx = tid & 15;
+  float acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0.0f;
+#pragma unroll 8
+  for (int r = 0; r < WG_ROWS; ++r) {
+    const f4 a = *reinterpret_cast<const f4*>(&As[r][4 * ty]), b = *reinterpret_cast<const f4*>(&Bs[r][4 * tx]);
+    const float aa[4] = {a.x, a.y, a.z, a.w}, bb[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(aa[i], bb[j], acc[i][j]);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int gf = f0 + 4 * ty + i;
+    if (gf >= Kf) continue;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int gn = n0 + 4 * tx + j;
+      if (gn < N && acc[i][j] != 0.0f) atomicAdd(&g.C[(long long)gf * g.c_rs + gn], acc[i][j]);
+    }
+  }
+  if (gb && blockIdx.y == 0 && tid < 64 && n0 + tid < N) {
+    float sum = 0.0f;
+    for (int r = 0; r < WG_ROWS; ++r) sum += Bs[r][tid];
+    if (sum != 0.0f) atomicAdd(&gb[n0 + tid], sum);
+  }
+}
+
+// in: [rows][Kf] (a_cs = Kf), dout: [rows][N]; takes every shape
+void wgrad(const GemmArgs& g, float* gb, hipStream_t s) {
+  const int vec_a = (g.M & 3) == 0 && (g.a_cs & 3) == 0 && aligned16(g.A);
+  const int vec_b = (g.N & 3) == 0 && (g.b_rs & 3) == 0 && aligned16(g.B);
+  const dim3 grid((g.N + 63) / 64, (g.M + 63) / 64, (g.K + WG_ROWS - 1) / WG_ROWS);
+  hipLaunchKernelGGL(gptb_wgrad_kernel, grid, dim3(GT), 0, s, g, gb, vec_a, vec_b);
+}
+
+void gemm(GemmArgs g, hipStream_t s) {
+  if (tok_gemm(g, s)) return;
+  dim3 grid((g.N + 63) / 64, (g.M + 63) / 64);      // shapes the token-row kernel does not take (K > TG_KMAX: wide models)
   const bool ak = g.a_cs == 1, bn = g.b_cs == 1;
   if (ak && bn) hipLaunchKernelGGL((gptb_gemm_kernel<true, true>), grid, dim3(GT), 0, s, g);
   else if (ak) hipLaunchKernelGGL((gptb_gemm_kernel<true, false>), grid, dim3(GT), 0, s, g);
@@ -245,27 +504,6 @@ __global__ __launch_bounds__(GT) void gptb_ln_bwd_kernel(float* __restrict__ din
   for (int q = 0; q < LN_CQ; ++q) {
     const int c = lane + 64 * q;
     if (c < C && (aw[q] != 0.0f || ab[q] != 0.0f)) { atomicAdd(&gw[c], aw[q]); atomicAdd(&gb[c], ab[q]); }
-  }
-}
-
-// gb[n] += sum over the live rows of x[m][n]
-constexpr int COLSUM_ROWS = 128;
-__global__ __launch_bounds__(GT) void gptb_colsum_kernel(const float* __restrict__ x, int M, int N, float* __restrict__ gb,
-                                                         const int* __restrict__ Lp, int Lm) {
-  __shared__ float part[GT / 64][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = blockIdx.x * 64 + lane, L = *Lp;
-  float acc = 0.0f;
-  const int m0 = blockIdx.y * COLSUM_ROWS, m1 = min(M, m0 + COLSUM_ROWS);
-  if (n < N)
-    for (int m = m0 + wave; m < m1; m += GT / 64)
-      if ((m % Lm) < L) acc += x[(long long)m * N + n];
-  part[wave][lane] = acc;
-  __syncthreads();
-  if (wave == 0 && n < N) {
-    float sum = 0.0f;
-#pragma unroll
-    for (int q = 0; q < GT / 64; ++q) sum += part[q][lane];
-    atomicAdd(&gb[n], sum);
   }
 }
 
@@ -540,8 +778,7 @@ int launch_gpt_backward_batched(const GptBwdArgs& a, const GptLayerPtrs* W, cons
     GemmArgs g = G0();
     g.A = in; g.a_rs = 1; g.a_cs = K; g.B = dout; g.b_rs = N; g.b_cs = 1; g.C = gwt; g.c_rs = N; g.M = K; g.N = N; g.K = M;
     g.a_gelu = a_gelu; g.accumulate = 1; g.tok_dim = 1;
-    gemm(g, s);
-    if (gb) hipLaunchKernelGGL(gptb_colsum_kernel, dim3((N + 63) / 64, (M + COLSUM_ROWS - 1) / COLSUM_ROWS), dim3(GT), 0, s, dout, M, N, gb, Lp, Lm);
+    wgrad(g, gb, s);
   };
   auto ln_fwd = [&](float* out, const float* x, const float* w, const float* b, float* mu, float* rs) {
     hipLaunchKernelGGL(gptb_ln_fwd_kernel, dim3(row_blocks), dim3(GT), 0, s, x, w, b, out, mu, rs, M, C, Lp, Lm);
