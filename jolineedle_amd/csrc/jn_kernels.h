@@ -62,6 +62,18 @@ struct SlotBatch {
   long long pos = 0;      // int64 elements between slots of the stem's patch positions
 };
 
+// Dynamic LDS above the 64 KB every kernel may use has to be granted per kernel (hipFuncAttributeMaxDynamicSharedMemorySize).
+// Keeps, per kernel, the bytes granted so far and asks the runtime only when a launch needs more; false: refused.
+template <auto Kernel>
+bool allow_lds(size_t bytes) {
+  static size_t granted = 64 * 1024;
+  if (bytes <= granted) return true;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+    return false;
+  granted = bytes;
+  return true;
+}
+
 struct StemArgs {
   const void* src; const int64_t* positions; int pos_stride;    // positions[pos_stride * n + {0,1}] = (y, x)
   long long sample_stride, chan_stride; int row_stride;
@@ -164,7 +176,7 @@ int launch_nhwc_to_nchw(const void* in, int dtype, int in_ld, ChanTab it, float*
 int launch_efpn_linear(const float* e, const float* wt, float* part, int N, int K, int Co, int KS,
                        const int* skip_flag, int skip_when, hipStream_t s);
 
-// ---- detector (kernels_det.hip) --------------------------------------------------------------
+// ---- dense 3x3 conv (kernels_conv3.hip) ---------------------------------------------------------
 int launch_conv3(const ConvArgs& a, hipStream_t s);     // w_transposed: data gradient of a stride-1 layer
 int launch_conv3_bwd_data_s2(const float* gz, int g_ld, const float* w, float* gin, int gin_ld, int H, int W, int OH,
                              int OW, int Co, int Ci, int N, int accumulate, hipStream_t s,
@@ -172,6 +184,7 @@ int launch_conv3_bwd_data_s2(const float* gz, int g_ld, const float* w, float* g
 int launch_conv3_bwd_weight(const float* gz, int g_ld, const void* x, int x_dtype, int x_ld, ChanTab it, float* gw, int H,
                             int W, int OH, int OW, int Co, int Ci, int N, int stride, hipStream_t s,
                             const SlotBatch& sb = SlotBatch{});
+// ---- detector (kernels_det.hip) --------------------------------------------------------------
 int launch_head_pred(const void* reg, int reg_ld, ChanTab rt, const void* cls, int cls_ld, ChanTab ct, int dtype,
                      const float* wp, const float* bp, float* raw, int hid, int Hl, int Wl, int stride, int A, int a0,
                      int N, hipStream_t s, int logits_only = 0);

@@ -9,14 +9,14 @@
 
 namespace jnr {
 
-__device__ __forceinline__ float silu_tab(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
+__device__ __forceinline__ float silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 
-__device__ __forceinline__ f32x4 tf4_tab(f32x4 z, f32x4 sc, f32x4 sh, f32x4 fl) {
+__device__ __forceinline__ f32x4 tf4(f32x4 z, f32x4 sc, f32x4 sh, f32x4 fl) {
   f32x4 r;
-  r.x = fl.x != 0.0f ? silu_tab(fmaf(z.x, sc.x, sh.x)) : z.x;
-  r.y = fl.y != 0.0f ? silu_tab(fmaf(z.y, sc.y, sh.y)) : z.y;
-  r.z = fl.z != 0.0f ? silu_tab(fmaf(z.z, sc.z, sh.z)) : z.z;
-  r.w = fl.w != 0.0f ? silu_tab(fmaf(z.w, sc.w, sh.w)) : z.w;
+  r.x = fl.x != 0.0f ? silu(fmaf(z.x, sc.x, sh.x)) : z.x;
+  r.y = fl.y != 0.0f ? silu(fmaf(z.y, sc.y, sh.y)) : z.y;
+  r.z = fl.z != 0.0f ? silu(fmaf(z.z, sc.z, sh.z)) : z.z;
+  r.w = fl.w != 0.0f ? silu(fmaf(z.w, sc.w, sh.w)) : z.w;
   return r;
 }
 

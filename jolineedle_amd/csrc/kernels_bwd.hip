@@ -15,23 +15,16 @@
 
 #include "jn_kernels.h"
 #include "jn_reduce.h"
+#include "jn_split.h"
+#include "jn_tab.h"
 #include "jn_types.h"
 
 namespace jnr {
 
 __device__ __forceinline__ float sigmoidf_(float v) { return __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-__device__ __forceinline__ float silu_(float v) { return v * sigmoidf_(v); }
 __device__ __forceinline__ float dsilu_(float y) {
   const float s = sigmoidf_(y);
   return s * (1.0f + y * (1.0f - s));
-}
-__device__ __forceinline__ f32x4 tf4_(f32x4 z, f32x4 sc, f32x4 sh, f32x4 fl) {
-  f32x4 r;
-  r.x = fl.x != 0.0f ? silu_(fmaf(z.x, sc.x, sh.x)) : z.x;
-  r.y = fl.y != 0.0f ? silu_(fmaf(z.y, sc.y, sh.y)) : z.y;
-  r.z = fl.z != 0.0f ? silu_(fmaf(z.z, sc.z, sh.z)) : z.z;
-  r.w = fl.w != 0.0f ? silu_(fmaf(z.w, sc.w, sh.w)) : z.w;
-  return r;
 }
 
 // ---- 1. per-channel reductions ------------------------------------------------------------
@@ -245,8 +238,8 @@ __global__ __launch_bounds__(256) void pw_bwd_weight_kernel(const float* __restr
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
       const int kk = k0 + 4 * q;
       if (rb + r < r1 && kk < K)
-        v = tf4_(*reinterpret_cast<const f32x4*>(x + (rb + r) * x_ld + kk), *reinterpret_cast<const f32x4*>(it.sc + kk),
-                 *reinterpret_cast<const f32x4*>(it.sh + kk), *reinterpret_cast<const f32x4*>(it.fl + kk));
+        v = tf4(*reinterpret_cast<const f32x4*>(x + (rb + r) * x_ld + kk), *reinterpret_cast<const f32x4*>(it.sc + kk),
+                *reinterpret_cast<const f32x4*>(it.sh + kk), *reinterpret_cast<const f32x4*>(it.fl + kk));
       *reinterpret_cast<f32x4*>(As + r * LDK + 4 * q) = v;
     }
     __syncthreads();
@@ -371,7 +364,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
     for (int j = 0; j < 8; ++j) {
       const int r = (tid >> 5) + 8 * j;
       f32x4 u = {0.f, 0.f, 0.f, 0.f};
-      if (rb + r < r1 && k0 + 4 * q < K) u = tf4_(px[j], i_sc, i_sh, i_fl);
+      if (rb + r < r1 && k0 + 4 * q < K) u = tf4(px[j], i_sc, i_sh, i_fl);
       *reinterpret_cast<f32x4*>(Gs + r * LD + 4 * q) = pg[j];
       *reinterpret_cast<f32x4*>(As + r * LD + 4 * q) = u;
     }
@@ -388,6 +381,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             const float v = as[((e & 3) + 16 * (e >> 2)) * LD + 16 * b];
+            // split2 of jn_split.h written out, here and below: through the helper this kernel's registers are allocated
+            // differently (profiles/conv3_unit_ab.txt)
             const bf16_t h = (bf16_t)v;
             bh[b][e] = h; bl[b][e] = (bf16_t)(v - (float)h);
           }
@@ -605,8 +600,8 @@ __global__ __launch_bounds__(256) void pw_bwd_fused_kernel(
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (m0 + r < M) {
           if constexpr (RED) v = rx[j];     // raw z: activated where phase 3 reads it (each element once), z itself feeds the RED sums
-          else v = tf4_(rx[j], *reinterpret_cast<const f32x4*>(Cs + 7 * N + 4 * kq), *reinterpret_cast<const f32x4*>(Cs + 7 * N + K + 4 * kq),
-                        *reinterpret_cast<const f32x4*>(Cs + 7 * N + 2 * K + 4 * kq));
+          else v = tf4(rx[j], *reinterpret_cast<const f32x4*>(Cs + 7 * N + 4 * kq), *reinterpret_cast<const f32x4*>(Cs + 7 * N + K + 4 * kq),
+                       *reinterpret_cast<const f32x4*>(Cs + 7 * N + 2 * K + 4 * kq));
         }
         *reinterpret_cast<f32x4*>(As + r * LDA + 4 * kq) = v;
       }
@@ -706,9 +701,8 @@ __global__ __launch_bounds__(256) void pw_bwd_fused_kernel(
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           float v = As[(prow + (e & 3) + 16 * (e >> 2)) * LDA + 16 * (dw_b0 + b) + lm];
-          if constexpr (RED) v = p_fl[dw_b0 + b] != 0.0f ? silu_(fmaf(v, p_sc[dw_b0 + b], p_sh[dw_b0 + b])) : v;
-          const bf16_t h = (bf16_t)v;
-          bh[b][e] = h; bl[b][e] = (bf16_t)(v - (float)h);
+          if constexpr (RED) v = p_fl[dw_b0 + b] != 0.0f ? silu(fmaf(v, p_sc[dw_b0 + b], p_sh[dw_b0 + b])) : v;
+          split2(v, bh[b], bl[b], e);
         }
 #pragma unroll
       for (int a = 0; a < DW_AN; ++a) {
@@ -716,8 +710,7 @@ __global__ __launch_bounds__(256) void pw_bwd_fused_kernel(
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float v = Gs[(prow + (e & 3) + 16 * (e >> 2)) * LDG + 16 * (dw_a0 + a) + lm];
-          const bf16_t h = (bf16_t)v;
-          ah[e] = h; al[e] = (bf16_t)(v - (float)h);
+          split2(v, ah, al, e);
         }
 #pragma unroll
         for (int b = 0; b < DW_BN; ++b) {
@@ -739,7 +732,7 @@ __global__ __launch_bounds__(256) void pw_bwd_fused_kernel(
 #pragma unroll
         for (int b = 0; b < CTK; ++b) {
           bv[b] = As[row * LDA + 16 * b + lm];
-          if constexpr (RED) bv[b] = p_fl[b] != 0.0f ? silu_(fmaf(bv[b], p_sc[b], p_sh[b])) : bv[b];
+          if constexpr (RED) bv[b] = p_fl[b] != 0.0f ? silu(fmaf(bv[b], p_sc[b], p_sh[b])) : bv[b];
         }
 #pragma unroll
         for (int a = 0; a < CTN; ++a)
@@ -986,6 +979,8 @@ __global__ __launch_bounds__(256, 2) void pw_bwd_fused128_kernel(
       }
       *reinterpret_cast<f32x4*>(Gs + r * LDG + 4 * nq) = v;
       if constexpr (X3) {
+        // split3_store of jn_split.h written out, l converted where it is stored: with the helper the compiler schedules this
+        // kernel differently and it measured 0.7 - 1.3 % slower (profiles/conv3_unit_ab.txt)
         const bf16x4 vh = __builtin_convertvector(v, bf16x4);
         const f32x4 r1 = v - __builtin_convertvector(vh, f32x4);
         const bf16x4 vm = __builtin_convertvector(r1, bf16x4);
@@ -1001,8 +996,8 @@ __global__ __launch_bounds__(256, 2) void pw_bwd_fused128_kernel(
       const int r = (tid + 256 * j) / (K / 4);
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
       if (m0 + r < M)
-        v = tf4_(rx[j], *reinterpret_cast<const f32x4*>(Cs + 7 * N + 4 * kq), *reinterpret_cast<const f32x4*>(Cs + 7 * N + K + 4 * kq),
-                 *reinterpret_cast<const f32x4*>(Cs + 7 * N + 2 * K + 4 * kq));
+        v = tf4(rx[j], *reinterpret_cast<const f32x4*>(Cs + 7 * N + 4 * kq), *reinterpret_cast<const f32x4*>(Cs + 7 * N + K + 4 * kq),
+                *reinterpret_cast<const f32x4*>(Cs + 7 * N + 2 * K + 4 * kq));
       *reinterpret_cast<f32x4*>(As + r * LDA + 4 * kq) = v;
     }
   };
@@ -1061,7 +1056,7 @@ __global__ __launch_bounds__(256, 2) void pw_bwd_fused128_kernel(
       fetch(tile + 1 < t_end);                        // (unconditional: behind a branch the loaded registers are copied at the join, which waits for them)
     };
     if constexpr (X3) {
-      // the six-product bf16 form of pw_x3_kernel, small products first: (w, g) = (l, h) (h, l) (m, m) (m, h) (h, m) (h, h)
+      // the six-product bf16 form of pw_x3_kernel, (w, g) planes in the order of jn_split.h
       const bf16_t* xrow = Gp + lm * LDK + 8 * gq;
 #pragma unroll
       for (int u = 0; u < 2 * NJ; ++u) {
@@ -1072,14 +1067,13 @@ __global__ __launch_bounds__(256, 2) void pw_bwd_fused128_kernel(
         }
         if (u + D == 2 * NJ - 1) late_loads();
         __builtin_amdgcn_sched_barrier(0);
-        constexpr int TW[6] = {2, 0, 1, 1, 0, 0}, TX[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
         for (int p = 0; p < 2; ++p) {                 // (the planes are read again for the second cin tile: 12 registers less)
           bf16x8 xa[3];
 #pragma unroll
           for (int t = 0; t < 3; ++t) xa[t] = *reinterpret_cast<const bf16x8*>(xrow + t * 32 * LDK + p * 16 * LDK + 32 * j);
 #pragma unroll
-          for (int e = 0; e < 6; ++e) acc[c][p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wx[u][TW[e]], xa[TX[e]], acc[c][p], 0, 0, 0);
+          for (int e = 0; e < X3_PRODUCTS; ++e) acc[c][p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wx[u][X3_W[e]], xa[X3_X[e]], acc[c][p], 0, 0, 0);
         }
       }
     } else {
@@ -1128,8 +1122,7 @@ __global__ __launch_bounds__(256, 2) void pw_bwd_fused128_kernel(
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float v = As[(prow + (e & 3) + 16 * (e >> 2)) * LDA + 16 * (dw_b0 + b) + lm];
-          const bf16_t h = (bf16_t)v;
-          bh[b][e] = h; bl[b][e] = (bf16_t)(v - (float)h);
+          split2(v, bh[b], bl[b], e);
         }
 #pragma unroll
       for (int a = 0; a < DW_AN; ++a) {
@@ -1137,8 +1130,7 @@ __global__ __launch_bounds__(256, 2) void pw_bwd_fused128_kernel(
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float v = Gs[(prow + (e & 3) + 16 * (e >> 2)) * LDG + 16 * (dw_a0 + a) + lm];
-          const bf16_t h = (bf16_t)v;
-          ah[e] = h; al[e] = (bf16_t)(v - (float)h);
+          split2(v, ah, al, e);
         }
 #pragma unroll
         for (int b = 0; b < DW_BN; ++b) {
@@ -1307,7 +1299,7 @@ __global__ __launch_bounds__(256) void dw_bwd_weight_kernel(const float* __restr
       for (int kx = 0; kx < 3; ++kx) {
         const int ix = ox * S - 1 + kx;
         if (ix < 0 || ix >= W) continue;
-        const f32x4 v = tf4_(ld4(xb + ((long long)iy * W + ix) * x_ld), sc, sh, fl);
+        const f32x4 v = tf4(ld4(xb + ((long long)iy * W + ix) * x_ld), sc, sh, fl);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int ky = r - j * S;
@@ -1461,7 +1453,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void d
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (iy < H && ix < W) {
           zraw[d] = *reinterpret_cast<const f32x4*>(x + (((long long)n * H + iy) * W + ix) * x_ld + c);
-          v = tf4_(zraw[d], JN_C4(7), JN_C4(8), JN_C4(9));
+          v = tf4(zraw[d], JN_C4(7), JN_C4(8), JN_C4(9));
         }
         *reinterpret_cast<f32x4*>(As + (r * AW + cx) * PS + 4 * q) = v;
       }
@@ -1470,7 +1462,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void d
         const int iy = ay0 + r, ix = ax0 + cx;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (iy >= 0 && iy < H && ix >= 0 && ix < W)
-          v = tf4_(*reinterpret_cast<const f32x4*>(x + (((long long)n * H + iy) * W + ix) * x_ld + c), JN_C4(7), JN_C4(8), JN_C4(9));
+          v = tf4(*reinterpret_cast<const f32x4*>(x + (((long long)n * H + iy) * W + ix) * x_ld + c), JN_C4(7), JN_C4(8), JN_C4(9));
         *reinterpret_cast<f32x4*>(As + (r * AW + cx) * PS + 4 * q) = v;
       }
     } else {
@@ -1479,7 +1471,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void d
         const int iy = ay0 + r, ix = ax0 + cx;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (iy >= 0 && iy < H && ix >= 0 && ix < W)
-          v = tf4_(*reinterpret_cast<const f32x4*>(x + (((long long)n * H + iy) * W + ix) * x_ld + c), JN_C4(7), JN_C4(8), JN_C4(9));
+          v = tf4(*reinterpret_cast<const f32x4*>(x + (((long long)n * H + iy) * W + ix) * x_ld + c), JN_C4(7), JN_C4(8), JN_C4(9));
         *reinterpret_cast<f32x4*>(As + p * PS + 4 * q) = v;
       }
     }
@@ -1828,7 +1820,7 @@ __global__ __launch_bounds__(256) void spp_bwd_kernel(const AT* __restrict__ cat
   for (int e = tid; e < HW * cb; e += 256) {
     const int c = e % cb;
     const float z = ld1(base + (long long)(e / cb) * ld + c);
-    A[e] = it.fl[c0 + c] != 0.0f ? silu_(fmaf(z, it.sc[c0 + c], it.sh[c0 + c])) : z;
+    A[e] = it.fl[c0 + c] != 0.0f ? silu(fmaf(z, it.sc[c0 + c], it.sh[c0 + c])) : z;
     G[e] = 0.0f;
   }
   __syncthreads();
@@ -1914,7 +1906,7 @@ __global__ __launch_bounds__(256) void spp4_bwd_kernel(const float* __restrict__
       const f32x4 z = *reinterpret_cast<const f32x4*>(base + (long long)p * ld + 4 * q);
       f32x4 a;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) a[k] = fl[k] != 0.0f ? silu_(fmaf(z[k], sc[k], sh[k])) : z[k];
+      for (int k = 0; k < 4; ++k) a[k] = fl[k] != 0.0f ? silu(fmaf(z[k], sc[k], sh[k])) : z[k];
       A[e] = a;
       *reinterpret_cast<f32x4*>(G + 4 * e) = f32x4{0.f, 0.f, 0.f, 0.f};
     }

@@ -33,23 +33,11 @@
 
 namespace jnr {
 
-__device__ __forceinline__ float silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-
 __device__ __forceinline__ float act_apply(float v, int act) {
   if (act == ACT_SILU) return silu(v);
   if (act == ACT_RELU) return fmaxf(v, 0.0f);
   if (act == ACT_SIGMOID) return 1.0f / (1.0f + __expf(-v));
   return v;
-}
-
-// a = flag ? silu(z * sc + sh) : z, 4 channels at once
-__device__ __forceinline__ f32x4 tf4(f32x4 z, f32x4 sc, f32x4 sh, f32x4 fl) {
-  f32x4 r;
-  r.x = fl.x != 0.0f ? silu(fmaf(z.x, sc.x, sh.x)) : z.x;
-  r.y = fl.y != 0.0f ? silu(fmaf(z.y, sc.y, sh.y)) : z.y;
-  r.z = fl.z != 0.0f ? silu(fmaf(z.z, sc.z, sh.z)) : z.z;
-  r.w = fl.w != 0.0f ? silu(fmaf(z.w, sc.w, sh.w)) : z.w;
-  return r;
 }
 
 // ------------------------------------------------------------------------------------
@@ -1184,7 +1172,7 @@ __global__ __launch_bounds__(256) void spp4_kernel(float* __restrict__ cat, int 
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
     const int e = tid + 256 * i;
-    if (e < NEL) A[e] = tf4_tab(*reinterpret_cast<const f32x4*>(base + (long long)(e / CBQ) * ld + 4 * q), sc, sh, fl);
+    if (e < NEL) A[e] = tf4(*reinterpret_cast<const f32x4*>(base + (long long)(e / CBQ) * ld + 4 * q), sc, sh, fl);
   }
   __syncthreads();
   const f32x4 ninf = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};

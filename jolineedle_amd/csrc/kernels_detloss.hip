@@ -9,19 +9,10 @@
 #include <algorithm>
 
 #include "jn_kernels.h"
+#include "jn_tab.h"
 #include "jn_types.h"
 
 namespace jnr {
-
-__device__ __forceinline__ float silu_l(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-__device__ __forceinline__ f32x4 tf4_d(f32x4 z, f32x4 sc, f32x4 sh, f32x4 fl) {
-  f32x4 r;
-  r.x = fl.x != 0.0f ? silu_l(fmaf(z.x, sc.x, sh.x)) : z.x;
-  r.y = fl.y != 0.0f ? silu_l(fmaf(z.y, sc.y, sh.y)) : z.y;
-  r.z = fl.z != 0.0f ? silu_l(fmaf(z.z, sc.z, sh.z)) : z.z;
-  r.w = fl.w != 0.0f ? silu_l(fmaf(z.w, sc.w, sh.w)) : z.w;
-  return r;
-}
 
 // A patch with more boxes than DL_MAXG is cut to its first DL_MAXG rows (the reference uses them all): documented at
 // jn_detector_step in include/jnroll.h, refused by the Python wrappers (yolox.py::check_box_cap).  That is the default
@@ -512,10 +503,10 @@ __global__ __launch_bounds__(256) void head_pred_bwd_kernel(const float* __restr
   for (int k = 0; k < hid; k += 4) {
     f32x4 rv = {0.f, 0.f, 0.f, 0.f}, cv = {0.f, 0.f, 0.f, 0.f};
     if (active) {
-      rv = tf4_d(ld4(reg + idx * reg_ld + k), *reinterpret_cast<const f32x4*>(rt.sc + k), *reinterpret_cast<const f32x4*>(rt.sh + k),
-                 *reinterpret_cast<const f32x4*>(rt.fl + k));
-      cv = tf4_d(ld4(cls + idx * cls_ld + k), *reinterpret_cast<const f32x4*>(ct.sc + k), *reinterpret_cast<const f32x4*>(ct.sh + k),
-                 *reinterpret_cast<const f32x4*>(ct.fl + k));
+      rv = tf4(ld4(reg + idx * reg_ld + k), *reinterpret_cast<const f32x4*>(rt.sc + k), *reinterpret_cast<const f32x4*>(rt.sh + k),
+               *reinterpret_cast<const f32x4*>(rt.fl + k));
+      cv = tf4(ld4(cls + idx * cls_ld + k), *reinterpret_cast<const f32x4*>(ct.sc + k), *reinterpret_cast<const f32x4*>(ct.sh + k),
+               *reinterpret_cast<const f32x4*>(ct.fl + k));
       f32x4 gr, gc;
 #pragma unroll
       for (int q = 0; q < 4; ++q) {

@@ -555,17 +555,10 @@ __global__ __launch_bounds__(EV_NT) void pool_walk_detections_kernel(
   }
 }
 
-// LDS beyond the 64 KB a kernel gets by default has to be asked for once per kernel.
-template <typename K>
-static int allow_lds(K kernel, size_t bytes) {
-  if (bytes <= (size_t)64 * 1024) return 0;
-  return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? 0 : 1;
-}
-
 int launch_merge_boxes(const float* boxes, const int32_t* counts, int B, int Nmax, int W, int target, float threshold,
                        float* out_boxes, int32_t* out_counts, int32_t* out_rounds, hipStream_t s) {
   const size_t smem = (size_t)6 * Nmax * sizeof(uint32_t);
-  if (allow_lds(merge_boxes_kernel, smem)) return 1;
+  if (!allow_lds<&merge_boxes_kernel>(smem)) return 1;
   hipLaunchKernelGGL(merge_boxes_kernel, dim3(B), dim3(EV_NT), smem, s, boxes, counts, Nmax, W, target ? 1 : 0, threshold,
                      out_boxes, out_counts, out_rounds);
   return 0;
@@ -588,7 +581,7 @@ int launch_average_precision(const double* scores, const int32_t* hits, const in
   int np2 = 2;
   while (np2 < slots) np2 <<= 1;
   const size_t smem = (size_t)np2 * (sizeof(double) + sizeof(int32_t));
-  if (allow_lds(average_precision_kernel, smem)) return 1;
+  if (!allow_lds<&average_precision_kernel>(smem)) return 1;
   hipLaunchKernelGGL(average_precision_kernel, dim3(pooled ? 1 : B), dim3(EV_NT), smem, s, scores, hits, n_pred, n_gt, B, max_det,
                      pooled, np2, thresholds, n_thresholds, out);
   return 0;
@@ -602,7 +595,7 @@ int launch_pool_walk_detections(const float* det_boxes, const int32_t* det_count
   int cap2 = 1;
   while (cap2 < cap) cap2 <<= 1;
   const size_t smem = (size_t)cap2 * sizeof(unsigned long long) + (size_t)4 * cap * sizeof(float);
-  if (allow_lds(pool_walk_detections_kernel, smem)) return 1;
+  if (!allow_lds<&pool_walk_detections_kernel>(smem)) return 1;
   hipLaunchKernelGGL(pool_walk_detections_kernel, dim3(Gh * Gw, NI), dim3(EV_NT), smem, s, det_boxes, det_counts, positions,
                      walk_tokens, walk_first, walk_count, A, T, S, K, max_walks, Gw, M, cap, cap2, cell_boxes, cell_counts,
                      cell_stats, visited);
@@ -616,7 +609,7 @@ int launch_average_precision_segments(const double* scores, const int32_t* hits,
   int np2 = 2;
   while (np2 < slots) np2 <<= 1;
   const size_t smem = (size_t)np2 * (sizeof(double) + sizeof(int32_t));
-  if (allow_lds(average_precision_segments_kernel, smem)) return 1;
+  if (!allow_lds<&average_precision_segments_kernel>(smem)) return 1;
   hipLaunchKernelGGL(average_precision_segments_kernel, dim3(NS), dim3(EV_NT), smem, s, scores, hits, n_pred, n_gt, U, max_det,
                      seg_offsets, max_units, np2, thresholds, n_thresholds, out);
   return 0;

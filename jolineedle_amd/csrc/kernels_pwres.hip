@@ -140,8 +140,8 @@ __global__ __launch_bounds__(256, 2) void pw_dir_kernel(
       for (int j = 0; j < NF; ++j) {
         const int k = k0 + 16 * j + 4 * g;
         if constexpr (TF)
-          xa[j] = tf4_tab(xr[u][j], *reinterpret_cast<const f32x4*>(Tb + k), *reinterpret_cast<const f32x4*>(Tb + K + k),
-                          *reinterpret_cast<const f32x4*>(Tb + 2 * K + k));
+          xa[j] = tf4(xr[u][j], *reinterpret_cast<const f32x4*>(Tb + k), *reinterpret_cast<const f32x4*>(Tb + K + k),
+                      *reinterpret_cast<const f32x4*>(Tb + 2 * K + k));
         else
           xa[j] = xr[u][j];
       }

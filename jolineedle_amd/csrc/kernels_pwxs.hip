@@ -28,6 +28,7 @@
 
 #include "jn_kernels.h"
 #include "jn_reduce.h"
+#include "jn_split.h"
 #include "jn_tab.h"
 #include "jn_types.h"
 
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256, (K <= 64 ? 3 : (K <= 128 || (K == 256 && CTW <
 #pragma unroll
       for (int u = 0; u < NXB; ++u) {
         const int r = r0 + (b * NXB + u) * RS;
-        f32x4 v = tf4_tab(xr[u], sc, sh, fl);
+        f32x4 v = tf4(xr[u], sc, sh, fl);
         if (m0 + r >= M) v = f32x4{0.f, 0.f, 0.f, 0.f};  // rows past the end contribute nothing (T(0) is not 0)
         *reinterpret_cast<f32x4*>(Xs + r * LDX + 4 * q) = v;
       }
@@ -283,15 +284,7 @@ __global__ __launch_bounds__(256) void w_split3_kernel(const float* __restrict__
   if (i >= n8) return;
   const f32x4 a = *reinterpret_cast<const f32x4*>(w + 8 * i), b = *reinterpret_cast<const f32x4*>(w + 8 * i + 4);
   bf16x8 h, m, l;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float v = e < 4 ? a[e] : b[e - 4];
-    const bf16_t vh = (bf16_t)v;
-    const float r1 = v - (float)vh;
-    const bf16_t vm = (bf16_t)r1;
-    const float r2 = r1 - (float)vm;
-    h[e] = vh; m[e] = vm; l[e] = (bf16_t)r2;
-  }
+  split3(a, b, h, m, l);
   bf16x8* o = reinterpret_cast<bf16x8*>(w3 + 24 * i);
   o[0] = h; o[1] = m; o[2] = l;
 }
@@ -316,15 +309,7 @@ __global__ __launch_bounds__(256) void w_split3_frag_kernel(const float* __restr
   const float* w = params + c.off + 8LL * i;
   const f32x4 a = *reinterpret_cast<const f32x4*>(w), b = *reinterpret_cast<const f32x4*>(w + 4);
   bf16x8 h, m, l;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float v = e < 4 ? a[e] : b[e - 4];
-    const bf16_t vh = (bf16_t)v;
-    const float r1 = v - (float)vh;
-    const bf16_t vm = (bf16_t)r1;
-    const float r2 = r1 - (float)vm;
-    h[e] = vh; m[e] = vm; l[e] = (bf16_t)r2;
-  }
+  split3(a, b, h, m, l);
   bf16_t* o = params_x3 + 3 * c.off + ((long long)((n >> 4) * (c.cin / 32) + j) * 3 * 64 + g * 16 + (n & 15)) * 8;
   *reinterpret_cast<bf16x8*>(o) = h;
   *reinterpret_cast<bf16x8*>(o + 512) = m;
@@ -431,16 +416,14 @@ __global__ __launch_bounds__(256, (K <= 64 ? 3 : CTW <= 2 ? 2 : 1)) void pw_x3_k
 #pragma unroll
       for (int u = 0; u < NXB; ++u) {
         const int r = r0 + (b * NXB + u) * RS;
-        f32x4 v = tf4_tab(xr[u], sc, sh, fl);
+        f32x4 v = tf4(xr[u], sc, sh, fl);
         if (m0 + r >= M) v = f32x4{0.f, 0.f, 0.f, 0.f};
         const bf16x4 vh = __builtin_convertvector(v, bf16x4);
         bf16_t* dst = Xp + r * LDK + 4 * q;
         *reinterpret_cast<bf16x4*>(dst) = vh;
         if constexpr (NP == 3) {
-          const f32x4 r1 = v - __builtin_convertvector(vh, f32x4);
-          const bf16x4 vm = __builtin_convertvector(r1, bf16x4);
-          const f32x4 r2 = r1 - __builtin_convertvector(vm, f32x4);
-          const bf16x4 vl = __builtin_convertvector(r2, bf16x4);
+          bf16x4 vm, vl;
+          split3_low(v, vh, vm, vl);
           *reinterpret_cast<bf16x4*>(dst + BM * LDK) = vm;
           *reinterpret_cast<bf16x4*>(dst + 2 * BM * LDK) = vl;
         }
@@ -478,15 +461,14 @@ __global__ __launch_bounds__(256, (K <= 64 ? 3 : CTW <= 2 ? 2 : 1)) void pw_x3_k
             for (int t = 0; t < NP; ++t) wr[u][c][t] = wfrag(c, jn, t);
           __builtin_amdgcn_sched_barrier(0);
         }
-        // six products, the small ones first: (w, x) = (l, h) (h, l) (m, m) (m, h) (h, m) (h, h)
-        constexpr int TW[6] = {2, 0, 1, 1, 0, 0}, TX[6] = {0, 2, 1, 0, 1, 0};
+        // six products, the small ones first (jn_split.h); one plane: h h alone
 #pragma unroll
-        for (int e = (NP == 3 ? 0 : 5); e < 6; ++e)
+        for (int e = (NP == 3 ? 0 : X3_PRODUCTS - 1); e < X3_PRODUCTS; ++e)
 #pragma unroll
           for (int c = 0; c < CTW; ++c)
 #pragma unroll
             for (int p = 0; p < PT; ++p)
-              acc[c][p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[c][TW[e]], xa[p][TX[e]], acc[c][p], 0, 0, 0);
+              acc[c][p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[c][X3_W[e]], xa[p][X3_X[e]], acc[c][p], 0, 0, 0);
       }
     }
 
@@ -638,14 +620,7 @@ __global__ __launch_bounds__(256) void w_split3_t_kernel(const float* __restrict
   const int NJ = cout / 32, j = gq >> 2, g = gq & 3;   // fragment order (pw_x3_kernel, SLOTS): k step j, lane group g
   bf16x8 h, m, l;
 #pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float v = w[(long long)(8 * gq + e) * cin + n];
-    const bf16_t vh = (bf16_t)v;
-    const float r1 = v - (float)vh;
-    const bf16_t vm = (bf16_t)r1;
-    const float r2 = r1 - (float)vm;
-    h[e] = vh; m[e] = vm; l[e] = (bf16_t)r2;
-  }
+  for (int e = 0; e < 8; ++e) split3(w[(long long)(8 * gq + e) * cin + n], h, m, l, e);
   bf16_t* o = w3t + ((long long)((n >> 4) * NJ + j) * 3 * 64 + g * 16 + (n & 15)) * 8;
   *reinterpret_cast<bf16x8*>(o) = h;
   *reinterpret_cast<bf16x8*>(o + 512) = m;

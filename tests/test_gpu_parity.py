@@ -114,10 +114,13 @@ def test_nano_backbone_fpn_maps(P, N):
         assert err < TOL_MAP, (i, err)
 
 
-def test_dense_backbone_train_mode_batchnorm():
-    """yolox-s encoder (dense 3x3 convs) in train mode: batch-statistics maps and running-stat updates."""
-    product, oracle = make_pair(3, patch_size=96, block_size=6, with_detector=False, image_processor=None, gpt_backbone="yolox-s")
-    x = torch.rand((3, 3, 96, 96), generator=torch.Generator().manual_seed(5))
+@pytest.mark.parametrize("P,N", [(96, 3), (320, 6)])
+def test_dense_backbone_train_mode_batchnorm(P, N):
+    """yolox-s encoder (dense 3x3 convs) in train mode: batch-statistics maps and running-stat updates.
+    (320, 6): dark2.0.conv (32 -> 64, 80 x 80 output) is 600 fp32 against 150 three-way-split workgroups, the one
+    stride-2 layer of the test shapes that the launch rule sends to conv3_x3s2_kernel and its statistics epilogue."""
+    product, oracle = make_pair(3, patch_size=P, block_size=6, with_detector=False, image_processor=None, gpt_backbone="yolox-s")
+    x = torch.rand((N, 3, P, P), generator=torch.Generator().manual_seed(5))
     oracle.gpt_backbone.train()
     with torch.no_grad():
         ref = oracle.gpt_backbone(x)
