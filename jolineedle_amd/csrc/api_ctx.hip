@@ -340,10 +340,12 @@ int jn_create(const jn_config* cfg, jn_ctx** out) {
     ctx->enc_net = JN_NET_DETECTOR;
   }
   // the plans of the training backwards, checked here so that a broken one fails now (each backward plans again): the
-  // patch encoder fed through fpn[2] alone, unless it is the detached detector, and the detector with its head
+  // patch encoder fed through fpn[2] alone, unless it is the detached detector, and the detector with its head.  A bf16
+  // context never trains (plan_backward refuses it): nothing to check
   std::vector<BwdStep> plan;
-  if (ctx->enc_net != JN_NET_DETECTOR && (rc = plan_backward(ctx->nets[ctx->enc_net], false, 0x3, plan))) return rc;
-  if (cfg->with_detector && (rc = plan_backward(ctx->nets[JN_NET_DETECTOR], true, 0, plan))) return rc;
+  const bool trains = cfg->act_dtype == JN_F32;
+  if (trains && ctx->enc_net != JN_NET_DETECTOR && (rc = plan_backward(ctx->nets[ctx->enc_net], false, 0x3, plan))) return rc;
+  if (trains && cfg->with_detector && (rc = plan_backward(ctx->nets[JN_NET_DETECTOR], true, 0, plan))) return rc;
   // ... and the forward passes each net will run (run_net plans again per call), at both ends of the batch range: the
   // PAFPN in eval and train mode, with a head also the whole detector and the head-only range of its training step
   std::vector<FwdStep> fplan;

@@ -279,6 +279,17 @@ static void invalidate_slot_state(jn_ctx* ctx, int ni, int slot) {
     ctx->det_pass[slot - det_slot_base(ctx)].valid = false;
 }
 
+static ChanTab tab_at(ChanTab t, int c0) { t.sc += c0; t.sh += c0; t.fl += c0; return t; }      // channels c0 .. of a table
+
+// The stem conv cw over the N patches of ss: source and weight.  Output, statistics and skip fields are the caller's.
+static StemArgs stem_args(const StemSrc& ss, const Net& net, int N, const ConvW& cw) {
+  StemArgs a{};
+  a.src = ss.src; a.positions = ss.positions; a.pos_stride = ss.pos_stride; a.sample_stride = ss.sample_stride;
+  a.chan_stride = ss.chan_stride; a.row_stride = ss.row_stride; a.P = net.P; a.N = N; a.cout = cw.cout; a.w = cw.w_dev;
+  a.src_u8 = ss.src_u8;
+  return a;
+}
+
 // One pass of a PAFPN over N patches in workspace slot `slot`.  train != 0: batch-statistics
 // BatchNorm (stats accumulated by every conv, finalised per layer, running stats updated).
 // The routes come from plan_forward (plan.cpp); what depends on launch-time state stays here.
@@ -333,9 +344,10 @@ int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int train, 
     switch (st.route) {
       case FR_STEM: {
         const ConvW& cw = net.convs[op.wslot];
-        StemArgs a{ss.src, ss.positions, ss.pos_stride, ss.sample_stride, ss.chan_stride, ss.row_stride, net.P, N, cw.cout,
-                   cw.w_dev, ptr(op.out), ld(op.out), net.act_dtype, train ? stats + 2 * cw.stat_off : nullptr, rep_stride,
-                   skip_flag, skip_when, st.deferred ? JN_NREP_DEFER : JN_NREP, ss.src_u8};
+        StemArgs a = stem_args(ss, net, N, cw);
+        a.out = ptr(op.out); a.out_ld = ld(op.out); a.out_dtype = net.act_dtype; a.skip_flag = skip_flag; a.skip_when = skip_when;
+        a.stats = train ? stats + 2 * cw.stat_off : nullptr; a.stats_rep_stride = rep_stride;
+        a.stats_nrep = st.deferred ? JN_NREP_DEFER : JN_NREP;
         launch_stem(a, s);
         finalize(op, cw, st.deferred);
         break;
@@ -480,6 +492,8 @@ int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, hi
                      bool with_head, int fpn_zero) {
   Net& net = ctx->nets[ni];
   const int MB = ctx->cfg.max_batch;
+  // THE refusal of the backward: every kernel below reads fp32 activations
+  JN_CHECK(net.act_dtype == JN_F32, JN_ESTATE, "training needs act_dtype = fp32 (bf16 is the inference mode)");
   JN_CHECK(nsl >= 1 && nsl <= net.g_slots && slot + nsl <= net.n_slots, JN_ESTATE, "backward over %d slots from %d: not allocated", nsl, slot);
   std::vector<BwdStep> plan;
   int rc = plan_backward(net, with_head, fpn_zero, plan);
@@ -496,7 +510,7 @@ int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, hi
   sb.consts = 3LL * net.stat_channels;
   sb.pos = pos_slot_stride;
   float* save = slot_save(net, slot);
-  auto ptr = [&](const View& v) { return view_ptr(net, slot, MB, v); };
+  auto ptr = [&](const View& v) { return (const float*)view_ptr(net, slot, MB, v); };
   auto gptr = [&](const View& v) { return net.gact + net.buf_off[v.buf] * (size_t)MB + v.coff; };
   auto tab = [&](const View& v) { return view_tab(net, slot, v); };
   auto ld = [&](const View& v) { return net.bufs[v.buf].C; };
@@ -505,12 +519,63 @@ int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, hi
     return net.bred + 2 * (pcw.stat_off + (half > 0 ? pcw.cout / 2 : 0));
   };
   const ChanTab ident{ctx->ident, ctx->ident + 2048, ctx->ident + 4096};
-  // Wide 1x1 layers (unfused path): the weight-gradient GEMM only feeds the optimiser, so it runs on a second stream
-  // beside the data-gradient GEMM of the same layer and whatever follows; joined before this function returns.
   static const bool no_aux = std::getenv("JN_NO_AUX_STREAM") != nullptr;
   static const bool dbg_plan = std::getenv("JN_DBG_BWD_PLAN") != nullptr;
   bool aux_used = false;
   if (!no_aux) { int ra = ensure_aux_stream(ctx); if (ra) return ra; }
+  // A weight-gradient GEMM with plain atomics on gw (no shared scratch) only feeds the optimiser: it runs on the second
+  // stream, behind what `s` holds so far (g_z is complete), beside the data gradient of the same layer and whatever
+  // follows; joined before this function returns.  ws: the stream to launch it on.
+  auto fork_aux = [&](hipStream_t& ws) -> int {
+    ws = s;
+    if (no_aux) return JN_OK;
+    JN_HIP(hipEventRecord(ctx->aux_fork, s));
+    JN_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->aux_fork, 0));
+    ws = ctx->aux_stream;
+    aux_used = true;
+    return JN_OK;
+  };
+  // a conv op: its gradient view (d loss / d activation; g_z once bn_gz ran), pixels, per-channel constants, weight gradient
+  struct ConvB { const Op& op; const BwdStep& st; const ConvW& cw; float* g; int g_ld; long long M; float* consts; float* gw; };
+  // BatchNorm sums and constants of the conv, whole or — a merged pair with a half reduced by its consumer — per half: a
+  // part no consumer reduced gets its own pass, and consumer-made sums carry the moment against y (bn_bwd_consts)
+  auto bn_sums_consts = [&](const ConvB& c) {
+    const ConvW& cw = c.cw;
+    const int parts = c.st.red_by && !cw.prefix2.empty() ? 2 : 1, h = cw.cout / parts;
+    double* red = net.bred + 2 * cw.stat_off;
+    if (dbg_plan) {
+      // elements per patch that a separate bn_bwd_reduce pass re-reads (g and z: 8 bytes each); merged pairs per half
+      const int hm = c.st.red_by;
+      const long long sep = parts == 2 ? (c.M / N) * h * (2 - ((hm & 1) + ((hm >> 1) & 1))) : hm ? 0 : (c.M / N) * cw.cout;
+      std::fprintf(stderr, "[bwd-plan] %-34s kind %d cout %4d cin %4d M/patch %6lld stride %d acc_in %d separate-reduce elements/patch %8lld%s\n",
+                   c.op.name.c_str(), (int)c.op.kind, cw.cout, cw.cin, c.M / N, c.op.stride, (int)c.op.acc_in, sep,
+                   parts == 2 ? (hm == 3 ? " (both halves by their consumers)" : " (one half by its consumer)") : "");
+    }
+    for (int part = 0; part < parts; ++part) {
+      const int c0 = part * h, by_consumer = (c.st.red_by >> part) & 1;
+      float* sv = save + 2 * (cw.stat_off + c0);
+      if (!by_consumer)
+        launch_bn_bwd_reduce(c.g + c0, c.g_ld, ptr(c.op.out) + c0, ld(c.op.out), tab_at(tab(c.op.out), c0), sv, h, c.M,
+                             red + 2 * c0, rep_stride, s, sb);
+      launch_bn_bwd_consts(red + 2 * c0, rep_stride, (double)c.M, cw.gamma_dev + c0, cw.beta_dev + c0, sv, c.consts + 3 * c0,
+                           grad_of(ctx, cw.gamma_dev) + c0, grad_of(ctx, cw.beta_dev) + c0, h, s, sb, by_consumer);
+    }
+  };
+  // the data gradient of a stride-1 conv as its forward kernel over g_z with the transposed weight, all slots in one launch
+  auto gz_conv_args = [&](const ConvB& c) {
+    ConvArgs a{};
+    a.in = c.g; a.in_ld = c.g_ld; a.in_dtype = JN_F32; a.itab = ident; a.w = c.cw.w_dev;
+    a.out = gptr(c.op.in); a.out_ld = ld(c.op.in); a.out_dtype = JN_F32;
+    a.N = N; a.H = c.op.out.H; a.W = c.op.out.W; a.OH = c.op.in.H; a.OW = c.op.in.W;
+    a.cin = c.cw.cout; a.cout = c.cw.cin; a.stride = 1; a.act = ACT_NONE;
+    a.accumulate = c.op.acc_in ? 1 : 0; a.w_transposed = 1; a.in_identity = 1;
+    a.n_slots = nsl; a.in_slot_stride = sb.grad; a.out_slot_stride = sb.grad;
+    return a;
+  };
+  auto bn_gz = [&](const ConvB& c) {      // g_a -> g_z in place (the unfused routes)
+    launch_bn_bwd_gz(c.g, c.g_ld, ptr(c.op.out), ld(c.op.out), tab(c.op.out), save + 2 * c.cw.stat_off, c.consts, c.cw.cout, c.M,
+                     s, sb);
+  };
   const int n_ops_b = (int)plan.size();
   // JN_BWD_PROFILE=1: HIP events around the launches of every op, table on stderr (a measuring aid; use it together with
   // JN_NO_AUX_STREAM=1 so that the wide weight-gradient GEMMs are inside the brackets)
@@ -520,56 +585,44 @@ int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, hi
   for (int obi = n_ops_b - 1; obi >= 0; --obi) {
     const Op& op = net.ops[obi];
     const BwdStep& st = plan[obi];
-    if (op.wslot >= 0) {
-      const ConvW& cw = net.convs[op.wslot];
-      float* const gp_out = gptr(st.g);
-      const int gld_out = ld(st.g);
-      const long long M = (long long)N * op.out.H * op.out.W;
-      double* red = net.bred + 2 * cw.stat_off;
-      float* consts = net.bconsts + 3 * cw.stat_off;
-      const bool pair_halves = st.red_by && !cw.prefix2.empty();
-      if (dbg_plan) {
-        // elements per patch that a separate bn_bwd_reduce pass re-reads (g and z: 8 bytes each); merged pairs per half
-        const int hm = st.red_by;
-        const long long sep = pair_halves ? (M / N) * (cw.cout / 2) * (2 - ((hm & 1) + ((hm >> 1) & 1))) : hm ? 0 : (M / N) * cw.cout;
-        std::fprintf(stderr, "[bwd-plan] %-34s kind %d cout %4d cin %4d M/patch %6lld stride %d acc_in %d separate-reduce elements/patch %8lld%s\n",
-                     op.name.c_str(), (int)op.kind, cw.cout, cw.cin, M / N, op.stride, (int)op.acc_in, sep,
-                     pair_halves ? (hm == 3 ? " (both halves by their consumers)" : " (one half by its consumer)") : "");
-      }
-      if (pair_halves) {
-        // merged pair with at least one half reduced by its consumer: the other half (if any) gets its own pass, and the
-        // constants are formed per half (consumer-made sums carry the moment against y, see bn_bwd_consts)
-        const int h = cw.cout / 2;
-        for (int half = 0; half < 2; ++half) {
-          const int c0 = half * h;
-          ChanTab ot = tab(op.out);
-          ot.sc += c0; ot.sh += c0; ot.fl += c0;
-          if (!(st.red_by & (1 << half)))
-            launch_bn_bwd_reduce(gp_out + c0, gld_out, (const float*)ptr(op.out) + c0, net.act_dtype, ld(op.out), ot,
-                                 save + 2 * (cw.stat_off + c0), h, M, red + 2 * c0, rep_stride, s, sb);
-          launch_bn_bwd_consts(red + 2 * c0, rep_stride, (double)M, cw.gamma_dev + c0, cw.beta_dev + c0, save + 2 * (cw.stat_off + c0), consts + 3 * c0,
-                               grad_of(ctx, cw.gamma_dev) + c0, grad_of(ctx, cw.beta_dev) + c0, h, s, sb, (st.red_by >> half) & 1);
+    const long long M = (long long)N * op.out.H * op.out.W;
+    if (op.wslot < 0) {
+      switch (st.route) {
+        case BR_ADDACT_COPY: case BR_ADDACT_FOLD:
+          // (without acc_in the conv that feeds the add reads g[sum] in place, BwdStep::g; folded: that conv's kernel adds it)
+          if (op.acc_in) launch_grad_copy(gptr(op.out), ld(op.out), gptr(op.in), ld(op.in), op.out.C, M, 1, s, sb);
+          if (st.route == BR_ADDACT_COPY)
+            launch_grad_copy(gptr(op.out), ld(op.out), gptr(op.res), ld(op.res), op.out.C, M, op.acc_res ? 1 : 0, s, sb);
+          break;
+        case BR_SPP: {
+          const View full = net_full_view(net, op.out.buf);
+          JN_CHECK(launch_spp_bwd(ptr(full), gptr(full), ld(op.out), op.in.C, op.in.H, op.in.W, N, tab(op.in), s, sb) == 0, JN_ESTATE,
+                   "launch_spp_bwd: the LDS of %s was refused", op.name.c_str());
+          break;
         }
-      } else {
-        if (!st.red_by)
-          launch_bn_bwd_reduce(gp_out, gld_out, ptr(op.out), net.act_dtype, ld(op.out), tab(op.out), save + 2 * cw.stat_off, cw.cout,
-                               M, red, rep_stride, s, sb);
-        launch_bn_bwd_consts(red, rep_stride, (double)M, cw.gamma_dev, cw.beta_dev, save + 2 * cw.stat_off, consts,
-                             grad_of(ctx, cw.gamma_dev), grad_of(ctx, cw.beta_dev), cw.cout, s, sb, st.red_by & 1);
+        case BR_UPSAMPLE:
+          launch_upsample_bwd(gptr(op.out), ld(op.out), gptr(op.in), ld(op.in), op.in.C, op.in.H, op.in.W, N, op.acc_in ? 1 : 0, s, sb);
+          break;
+        default: break;      // nothing to differentiate here (the head's predictors: api_det.hip)
       }
-      float* gw = grad_of(ctx, cw.w_dev);
-      if (st.route == BR_PW_FUSED || st.route == BR_PW_FUSED_HALVES) {
+      prof.mark(obi);
+      continue;
+    }
+    const ConvW& cw = net.convs[op.wslot];
+    const ConvB c{op, st, cw, gptr(st.g), ld(st.g), M, net.bconsts + 3 * cw.stat_off, grad_of(ctx, cw.w_dev)};
+    hipStream_t ws = s;      // of a weight-gradient kernel that may run beside the rest (fork_aux)
+    bn_sums_consts(c);
+    switch (st.route) {
+      case BR_PW_FUSED: case BR_PW_FUSED_HALVES: {      // one launch, or one per half of the output channels
         const int parts = st.route == BR_PW_FUSED ? 1 : 2, pc = cw.cout / parts;
         for (int part = 0; part < parts; ++part) {
           const int c0 = part * pc;
-          ChanTab ot = tab(op.out);
-          ot.sc += c0; ot.sh += c0; ot.fl += c0;
           PwBwdFusedArgs fa{};
-          fa.g = gp_out + c0; fa.g_ld = gld_out; fa.z = (const float*)ptr(op.out) + c0; fa.z_ld = ld(op.out); fa.ot = ot;
-          fa.save = save + 2 * (cw.stat_off + c0); fa.consts = consts + 3 * c0;
-          fa.x = (const float*)ptr(op.in); fa.x_ld = ld(op.in); fa.it = tab(op.in); fa.w = cw.w_dev + (size_t)c0 * cw.cin;
+          fa.g = c.g + c0; fa.g_ld = c.g_ld; fa.z = ptr(op.out) + c0; fa.z_ld = ld(op.out); fa.ot = tab_at(tab(op.out), c0);
+          fa.save = save + 2 * (cw.stat_off + c0); fa.consts = c.consts + 3 * c0;
+          fa.x = ptr(op.in); fa.x_ld = ld(op.in); fa.it = tab(op.in); fa.w = cw.w_dev + (size_t)c0 * cw.cin;
           fa.gx = gptr(op.in); fa.gx_ld = ld(op.in); fa.accumulate = (op.acc_in || part > 0) ? 1 : 0;
-          fa.gw = gw + (size_t)c0 * cw.cin; fa.wpart = ctx->wpart; fa.M = M; fa.cout = pc; fa.cin = cw.cin; fa.sb = sb;
+          fa.gw = c.gw + (size_t)c0 * cw.cin; fa.wpart = ctx->wpart; fa.M = M; fa.cout = pc; fa.cin = cw.cin; fa.sb = sb;
           if (st.fold >= 0) {                   // the shortcut add's backward left its copy to this kernel
             const View& sum = net.ops[st.fold].out;
             fa.gadd = gptr(sum); fa.gadd_ld = ld(sum); fa.accumulate = 0;
@@ -581,114 +634,74 @@ int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, hi
           if (st.red2) {                        // the sums of the conv behind the shortcut sum: its raw output and table
             const Op& co = net.ops[st.red_in];
             const ChanTab zt = tab(co.out);
-            fa.red2_z = (const float*)ptr(co.out); fa.red2_ld = ld(co.out); fa.red2_sc = zt.sc; fa.red2_sh = zt.sh;
+            fa.red2_z = ptr(co.out); fa.red2_ld = ld(co.out); fa.red2_sc = zt.sc; fa.red2_sh = zt.sh;
           }
-          // 128 input channels, fp32: the transposed weight in fragment order goes into the layer's own stretch of the
-          // wide route's scratch (6 bytes per weight, unused by a fused layer; 16-byte aligned under the same condition)
-          if (net.act_dtype == JN_F32 && ctx->params_x3t && cw.cin == 128 && (pc == 128 || pc == 64) && (fa.w - ctx->params) % 8 == 0)
+          // 128 input channels: the transposed weight in fragment order goes into the layer's own stretch of the wide
+          // route's scratch (6 bytes per weight, unused by a fused layer; 16-byte aligned under the same condition)
+          if (ctx->params_x3t && cw.cin == 128 && (pc == 128 || pc == 64) && (fa.w - ctx->params) % 8 == 0)
             fa.w_frag = reinterpret_cast<float*>(ctx->params_x3t + 3 * (fa.w - ctx->params));
-          launch_pw_bwd_fused(fa, s);
+          JN_CHECK(launch_pw_bwd_fused(fa, s) == 0, JN_ESTATE, "launch_pw_bwd_fused: %s has no kernel, or its LDS was refused", op.name.c_str());
         }
-      } else if (st.route == BR_DW_FUSED) {
+        break;
+      }
+      case BR_DW_FUSED: {
         // stride 2 (round 4): the owner-staged variant of the kernel (every thread stages the 2 x 2 input block it
         // differentiates and keeps the raw values); round 3's variant re-read the input inside the gradient loop and lost
         // more than the separate pass costs
         DwBwdFusedArgs fa{};
-        fa.g = gp_out; fa.g_ld = gld_out; fa.z = (const float*)ptr(op.out); fa.z_ld = ld(op.out); fa.ot = tab(op.out);
-        fa.save = save + 2 * cw.stat_off; fa.consts = consts;
-        fa.x = (const float*)ptr(op.in); fa.x_ld = ld(op.in); fa.it = tab(op.in); fa.w = cw.w_dev;
-        fa.gin = gptr(op.in); fa.gin_ld = ld(op.in); fa.accumulate = op.acc_in ? 1 : 0; fa.gw = gw; fa.wpart = ctx->wpart;
+        fa.g = c.g; fa.g_ld = c.g_ld; fa.z = ptr(op.out); fa.z_ld = ld(op.out); fa.ot = tab(op.out);
+        fa.save = save + 2 * cw.stat_off; fa.consts = c.consts;
+        fa.x = ptr(op.in); fa.x_ld = ld(op.in); fa.it = tab(op.in); fa.w = cw.w_dev;
+        fa.gin = gptr(op.in); fa.gin_ld = ld(op.in); fa.accumulate = op.acc_in ? 1 : 0; fa.gw = c.gw; fa.wpart = ctx->wpart;
         fa.C = cw.cout; fa.H = op.in.H; fa.W = op.in.W; fa.OH = op.out.H; fa.OW = op.out.W; fa.N = N; fa.stride = op.stride;
         fa.sb = sb;
         if (st.red_in >= 0) {
           fa.red_in = sums(st.red_in, st.red_half); fa.red_rep_stride = rep_stride;
           fa.accumulate = 0;                      // sole reader: nothing but the (zero) outside seed was there before
         }
-        launch_dw_bwd_fused(fa, s);
-      } else if (st.route == BR_STEM_FUSED) {
-        StemArgs a{ss.src, ss.positions, ss.pos_stride, ss.sample_stride, ss.chan_stride, ss.row_stride, net.P, N, cw.cout,
-                   cw.w_dev, nullptr, 0, JN_F32, nullptr, 0, nullptr, 0, 0, ss.src_u8};
-        launch_stem_bwd_weight(a, gp_out, gld_out, gw, ctx->wpart, s, sb, (const float*)ptr(op.out), ld(op.out),
-                               tab(op.out), save + 2 * cw.stat_off, consts);
-      } else {
-        launch_bn_bwd_gz(gp_out, gld_out, ptr(op.out), net.act_dtype, ld(op.out), tab(op.out), save + 2 * cw.stat_off, consts,
-                         cw.cout, M, s, sb);
-        if (st.route == BR_PW) {
-          ConvArgs a{};
-          a.in = gp_out; a.in_ld = gld_out; a.in_dtype = JN_F32; a.itab = ident; a.w = cw.w_dev; a.bias = nullptr;
-          a.out = gptr(op.in); a.out_ld = ld(op.in); a.out_dtype = JN_F32; a.bf16_mfma = net.act_dtype == JN_BF16;
-          a.N = N; a.H = op.out.H; a.W = op.out.W; a.OH = op.out.H; a.OW = op.out.W;
-          a.cin = cw.cout; a.cout = cw.cin; a.stride = 1; a.act = ACT_NONE;
-          a.accumulate = op.acc_in ? 1 : 0; a.w_transposed = 1; a.in_identity = 1;
-          a.n_slots = nsl; a.in_slot_stride = sb.grad; a.out_slot_stride = sb.grad; a.tab_slot_stride = 0;
-          hipStream_t ws = s;
-          if (!no_aux && cw.cout >= 128 && cw.cin >= 128) {      // the wide kernel: plain atomics on gw, no shared scratch
-            JN_HIP(hipEventRecord(ctx->aux_fork, s));           // g_z is complete
-            JN_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->aux_fork, 0));
-            ws = ctx->aux_stream;
-            aux_used = true;
-          }
-          // wide layers, fp32: the data gradient on the bf16 pipe at fp32 accuracy (pw_x3_kernel over the slots, transposed
-          // weight split on the way: kernels_pwxs.hip); JN_NO_PW_X3_BWD=1 keeps pw_dir_kernel<WT> on the fp32 pipe
-          const bool no_x3_bwd = std::getenv("JN_NO_PW_X3_BWD") != nullptr;     // read per launch: a test flips it
-          bool x3_done = false;
-          if (!no_x3_bwd && net.act_dtype == JN_F32 && !op.acc_in && ctx->params_x3t && pw_x3_bwd_data_supported(cw.cout, cw.cin) &&
-              (cw.w_dev - ctx->params) % 8 == 0) {
-            x3_done = launch_pw_x3_bwd_data(a, cw.w_dev, ctx->params_x3t + 3 * (cw.w_dev - ctx->params), s) == 0;
-          }
-          if (!x3_done) launch_pw(a, s);
-          launch_pw_bwd_weight(gp_out, gld_out, ptr(op.in), net.act_dtype, ld(op.in), tab(op.in), gw, ctx->wpart, M, cw.cout,
-                               cw.cin, ws, sb);
-        } else if (st.route == BR_DW) {
-          launch_dw_bwd_data(gp_out, gld_out, cw.w_dev, gptr(op.in), ld(op.in), cw.cout, op.in.H, op.in.W, op.out.H,
-                             op.out.W, N, op.stride, op.acc_in ? 1 : 0, s, sb);
-          launch_dw_bwd_weight(gp_out, gld_out, ptr(op.in), net.act_dtype, ld(op.in), tab(op.in), gw, ctx->wpart, cw.cout, op.in.H,
-                               op.in.W, op.out.H, op.out.W, N, op.stride, s, sb);
-        } else if (st.route == BR_STEM) {
-          StemArgs a{ss.src, ss.positions, ss.pos_stride, ss.sample_stride, ss.chan_stride, ss.row_stride, net.P, N, cw.cout,
-                     cw.w_dev, nullptr, 0, JN_F32, nullptr, 0, nullptr, 0, 0, ss.src_u8};
-          launch_stem_bwd_weight(a, gp_out, gld_out, gw, ctx->wpart, s, sb);
-        } else {
-          // dense 3x3 (non-depthwise patch encoders, e.g. yolox-s): stride 1 = the forward kernel over g_z with
-          // mirrored taps and the transposed weight; stride 2 = one MFMA tile loop per input-pixel parity class
-          int rc3 = 0;
-          hipStream_t ws3 = s;
-          if (!no_aux) {                     // the 9-tap weight gradient (plain atomics on gw) beside the data gradient
-            JN_HIP(hipEventRecord(ctx->aux_fork, s));
-            JN_HIP(hipStreamWaitEvent(ctx->aux_stream, ctx->aux_fork, 0));
-            ws3 = ctx->aux_stream;
-            aux_used = true;
-          }
-          if (st.route == BR_CONV3_S1) {
-            ConvArgs a{};
-            a.in = gp_out; a.in_ld = gld_out; a.in_dtype = JN_F32; a.itab = ident; a.w = cw.w_dev; a.bias = nullptr;
-            a.out = gptr(op.in); a.out_ld = ld(op.in); a.out_dtype = JN_F32;
-            a.N = N; a.H = op.out.H; a.W = op.out.W; a.OH = op.in.H; a.OW = op.in.W;
-            a.cin = cw.cout; a.cout = cw.cin; a.stride = 1; a.act = ACT_NONE;
-            a.accumulate = op.acc_in ? 1 : 0; a.w_transposed = 1; a.in_identity = 1;
-            a.n_slots = nsl; a.in_slot_stride = sb.grad; a.out_slot_stride = sb.grad;
-            rc3 = launch_conv3(a, s);
-          } else {
-            rc3 = launch_conv3_bwd_data_s2(gp_out, gld_out, cw.w_dev, gptr(op.in), ld(op.in), op.in.H, op.in.W, op.out.H,
-                                           op.out.W, cw.cout, cw.cin, N, op.acc_in ? 1 : 0, s, sb);
-          }
-          JN_CHECK(rc3 == 0, JN_ESTATE, "backward of dense 3x3 conv %s: unsupported shape", op.name.c_str());
-          launch_conv3_bwd_weight(gp_out, gld_out, ptr(op.in), net.act_dtype, ld(op.in), tab(op.in), gw, op.in.H, op.in.W,
-                                  op.out.H, op.out.W, cw.cout, cw.cin, N, op.stride, ws3, sb);
-        }
+        JN_CHECK(launch_dw_bwd_fused(fa, s) == 0, JN_ESTATE, "launch_dw_bwd_fused: %s has no kernel", op.name.c_str());
+        break;
       }
-    } else if (st.route == BR_ADDACT_COPY || st.route == BR_ADDACT_FOLD) {
-      const long long M = (long long)N * op.out.H * op.out.W;
-      // (without acc_in the conv that feeds the add reads g[sum] in place, BwdStep::g; folded: that conv's kernel adds it)
-      if (op.acc_in) launch_grad_copy(gptr(op.out), ld(op.out), gptr(op.in), ld(op.in), op.out.C, M, 1, s, sb);
-      if (st.route == BR_ADDACT_COPY)
-        launch_grad_copy(gptr(op.out), ld(op.out), gptr(op.res), ld(op.res), op.out.C, M, op.acc_res ? 1 : 0, s, sb);
-    } else if (st.route == BR_SPP) {
-      const View full = net_full_view(net, op.out.buf);
-      launch_spp_bwd(ptr(full), net.act_dtype, gptr(full), ld(op.out), op.in.C, op.in.H, op.in.W, N, tab(op.in), s, sb);
-    } else if (st.route == BR_UPSAMPLE) {
-      launch_upsample_bwd(gptr(op.out), ld(op.out), gptr(op.in), ld(op.in), op.in.C, op.in.H, op.in.W, N,
-                          op.acc_in ? 1 : 0, s, sb);
+      case BR_STEM_FUSED:      // bn_bwd_gz inside: no pass over the largest map of the network
+        launch_stem_bwd_weight(stem_args(ss, net, N, cw), c.g, c.g_ld, c.gw, ctx->wpart, s, sb, ptr(op.out), ld(op.out), tab(op.out),
+                               save + 2 * cw.stat_off, c.consts);
+        break;
+      case BR_PW: {
+        bn_gz(c);
+        const ConvArgs a = gz_conv_args(c);
+        if (cw.cout >= 128 && cw.cin >= 128 && (rc = fork_aux(ws))) return rc;      // the wide weight-gradient kernel
+        // wide layers: the data gradient on the bf16 pipe at fp32 accuracy (pw_x3_kernel over the slots, transposed weight
+        // split on the way: kernels_pwxs.hip); JN_NO_PW_X3_BWD=1 keeps pw_dir_kernel<WT> on the fp32 pipe
+        const bool x3 = !std::getenv("JN_NO_PW_X3_BWD") && !op.acc_in && ctx->params_x3t &&      // read per launch: a test flips it
+                        pw_x3_bwd_data_supported(cw.cout, cw.cin) && (cw.w_dev - ctx->params) % 8 == 0;
+        if (!x3 || launch_pw_x3_bwd_data(a, cw.w_dev, ctx->params_x3t + 3 * (cw.w_dev - ctx->params), s) != 0) launch_pw(a, s);
+        JN_CHECK(launch_pw_bwd_weight(c.g, c.g_ld, ptr(op.in), ld(op.in), tab(op.in), c.gw, ctx->wpart, M, cw.cout, cw.cin, ws, sb) == 0,
+                 JN_ESTATE, "launch_pw_bwd_weight: %s has no kernel, or its LDS was refused", op.name.c_str());
+        break;
+      }
+      case BR_DW:
+        bn_gz(c);
+        launch_dw_bwd_data(c.g, c.g_ld, cw.w_dev, gptr(op.in), ld(op.in), cw.cout, op.in.H, op.in.W, op.out.H, op.out.W, N, op.stride,
+                           op.acc_in ? 1 : 0, s, sb);
+        launch_dw_bwd_weight(c.g, c.g_ld, ptr(op.in), ld(op.in), tab(op.in), c.gw, ctx->wpart, cw.cout, op.in.H, op.in.W, op.out.H,
+                             op.out.W, N, op.stride, s, sb);
+        break;
+      case BR_CONV3_S1: case BR_CONV3_S2: {
+        // dense 3x3 (non-depthwise patch encoders, e.g. yolox-s): stride 1 = the forward kernel over g_z with mirrored
+        // taps and the transposed weight; stride 2 = one MFMA tile loop per input-pixel parity class
+        bn_gz(c);
+        if ((rc = fork_aux(ws))) return rc;      // the 9-tap weight gradient beside the data gradient
+        const int rc3 = st.route == BR_CONV3_S1
+                            ? launch_conv3(gz_conv_args(c), s)
+                            : launch_conv3_bwd_data_s2(c.g, c.g_ld, cw.w_dev, gptr(op.in), ld(op.in), op.in.H, op.in.W, op.out.H,
+                                                       op.out.W, cw.cout, cw.cin, N, op.acc_in ? 1 : 0, s, sb);
+        JN_CHECK(rc3 == 0, JN_ESTATE, "backward of dense 3x3 conv %s: unsupported shape", op.name.c_str());
+        JN_CHECK(launch_conv3_bwd_weight(c.g, c.g_ld, ptr(op.in), ld(op.in), tab(op.in), c.gw, op.in.H, op.in.W, op.out.H, op.out.W,
+                                         cw.cout, cw.cin, N, op.stride, ws, sb) == 0,
+                 JN_ESTATE, "launch_conv3_bwd_weight: the LDS of %s was refused", op.name.c_str());
+        break;
+      }
+      default: JN_CHECK(false, JN_ESTATE, "backward plan: conv %s has route %d", op.name.c_str(), (int)st.route);
     }
     prof.mark(obi);
   }
@@ -800,10 +813,12 @@ int jn_backbone_backward(jn_ctx* ctx, int net, const float* patches_dev, int N, 
   JN_CHECK(ctx && patches_dev, JN_EINVAL, "jn_backbone_backward: null argument");
   int rc = check_net_batch(ctx, net, N);
   if (rc) return rc;
+  Net& n = ctx->nets[net];
+  // (run_net_backward's refusal, repeated before the gradient seeds below are launched)
+  JN_CHECK(n.act_dtype == JN_F32, JN_ESTATE, "training needs act_dtype = fp32 (bf16 is the inference mode)");
   JN_HIP(hipSetDevice(ctx->cfg.device));
   if ((rc = ensure_train_state(ctx))) return rc;
   hipStream_t s = (hipStream_t)stream;
-  Net& n = ctx->nets[net];
   const int MB = ctx->cfg.max_batch;
   const float* gs[3] = {g0_dev, g1_dev, g2_dev};
   int fpn_zero = 0;                 // bit i: no gradient arrives in fpn[i] from outside (the training backward's routes)

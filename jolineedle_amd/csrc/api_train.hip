@@ -163,7 +163,7 @@ static int encoder_backward(jn_ctx* ctx, int g_n, int rows, int slot, const floa
   la2.N = (int)Mr; la2.H = 1; la2.W = 1; la2.OH = 1; la2.OW = 1; la2.cin = C; la2.cout = K; la2.stride = 1; la2.act = ACT_NONE;
   launch_pw(la2, s);
   launch_relu_mask(ctx->de_ws, e, Mr * K, s);
-  launch_pw_bwd_weight(e, K, dpe, JN_F32, C, ident, grad_of(ctx, g.efpn_lin_wt), nullptr, Mr, K, C, s);
+  launch_pw_bwd_weight(e, K, dpe, C, ident, grad_of(ctx, g.efpn_lin_wt), nullptr, Mr, K, C, s);
   launch_colsum_add(dpe, Mr, C, grad_of(ctx, g.efpn_lin_b), s);
   // embed_fpn.0 (1x1 conv) backward into the f2 gradient view of every slot (fp32 operands: the training entry points
   // refuse bf16 activations)
@@ -179,7 +179,7 @@ static int encoder_backward(jn_ctx* ctx, int g_n, int rows, int slot, const floa
   // yolox"): the policy gradient stops at embed_fpn.0's weight
   const bool detached = ctx->enc_net == JN_NET_DETECTOR;
   if (!detached) launch_pw(a, s);
-  launch_pw_bwd_weight(ctx->de_ws, C, view_ptr(net, slot, MB, f2), net.act_dtype, net.bufs[f2.buf].C, view_tab(net, slot, f2),
+  launch_pw_bwd_weight(ctx->de_ws, C, (const float*)view_ptr(net, slot, MB, f2), net.bufs[f2.buf].C, view_tab(net, slot, f2),
                        grad_of(ctx, g.efpn_w), ctx->wpart, (long long)rows * HW, C, f2.C, s, sb, (long long)rows * K);
   if (detached) return JN_OK;
   for (int i = 0; i < 2; ++i) {

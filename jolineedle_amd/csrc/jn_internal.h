@@ -137,7 +137,7 @@ enum BwdRoute {
   BR_NONE = 0,
   BR_PW_FUSED, BR_PW_FUSED_HALVES,        // pw_bwd_fused_kernel over the whole 1x1 conv / the two halves of a merged pair
   BR_DW_FUSED, BR_STEM_FUSED,             // dw_bwd_fused_kernel, the stem's weight gradient with bn_bwd_gz inside
-  BR_PW, BR_DW, BR_STEM, BR_CONV3_S1, BR_CONV3_S2,   // bn_bwd_gz, then separate data / weight gradients
+  BR_PW, BR_DW, BR_CONV3_S1, BR_CONV3_S2,   // bn_bwd_gz, then separate data / weight gradients
   BR_ADDACT_COPY, BR_ADDACT_FOLD,         // shortcut add: g[res] (+)= g[sum] by a copy / inside the fold conv's kernel
   BR_SPP, BR_UPSAMPLE,
 };

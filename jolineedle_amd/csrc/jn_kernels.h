@@ -181,9 +181,8 @@ int launch_conv3(const ConvArgs& a, hipStream_t s);     // w_transposed: data gr
 int launch_conv3_bwd_data_s2(const float* gz, int g_ld, const float* w, float* gin, int gin_ld, int H, int W, int OH,
                              int OW, int Co, int Ci, int N, int accumulate, hipStream_t s,
                              const SlotBatch& sb = SlotBatch{});
-int launch_conv3_bwd_weight(const float* gz, int g_ld, const void* x, int x_dtype, int x_ld, ChanTab it, float* gw, int H,
-                            int W, int OH, int OW, int Co, int Ci, int N, int stride, hipStream_t s,
-                            const SlotBatch& sb = SlotBatch{});
+int launch_conv3_bwd_weight(const float* gz, int g_ld, const float* x, int x_ld, ChanTab it, float* gw, int H, int W, int OH,
+                            int OW, int Co, int Ci, int N, int stride, hipStream_t s, const SlotBatch& sb = SlotBatch{});
 // ---- detector (kernels_det.hip) --------------------------------------------------------------
 int launch_head_pred(const void* reg, int reg_ld, ChanTab rt, const void* cls, int cls_ld, ChanTab ct, int dtype,
                      const float* wp, const float* bp, float* raw, int hid, int Hl, int Wl, int stride, int A, int a0,
@@ -215,21 +214,22 @@ int launch_head_pred_bwd(const float* d_raw, const float* scale, const void* reg
                          int cls_ld, ChanTab ct, int dtype, const float* wp, float* g_reg, float* g_cls, float* g_wp,
                          float* g_bp, int hid, int HW, int A, int a0, int N, hipStream_t s);
 
-// ---- backward of the conv stack (kernels_bwd.hip) ----------------------------------------
-int launch_bn_bwd_reduce(const float* g, int g_ld, const void* z, int z_dtype, int z_ld, ChanTab t, const float* save,
-                         int C, long long M, double* red_out, long long rep_stride, hipStream_t s,
+// ---- backward of the conv stack (kernels_bwd.hip, the 1x1 family in kernels_bwd_pw.hip) ----------------------------------------
+// Activations (z, x, cat) are fp32: training refuses bf16 storage (run_net_backward).
+int launch_bn_bwd_reduce(const float* g, int g_ld, const float* z, int z_ld, ChanTab t, const float* save, int C,
+                         long long M, double* red_out, long long rep_stride, hipStream_t s,
                          const SlotBatch& sb = SlotBatch{});
 // sums the replicas -> consts[c] = {sum_gy/n, sum_gy_zhat/n, gamma*invstd}; dgamma/dbeta += totals.  raw_moment: the second
 // sum is sum gy * y (y = gamma * zhat + beta, formed by a consumer's fused kernel) and is converted here
 int launch_bn_bwd_consts(const double* red, long long rep_stride, double count, const float* gamma, const float* beta,
                          const float* save, float* consts, float* g_gamma, float* g_beta, int C, hipStream_t s,
                          const SlotBatch& sb = SlotBatch{}, int raw_moment = 0);
-int launch_bn_bwd_gz(float* g, int g_ld, const void* z, int z_dtype, int z_ld, ChanTab t, const float* save,
-                     const float* consts, int C, long long M, hipStream_t s, const SlotBatch& sb = SlotBatch{});
+int launch_bn_bwd_gz(float* g, int g_ld, const float* z, int z_ld, ChanTab t, const float* save, const float* consts, int C,
+                     long long M, hipStream_t s, const SlotBatch& sb = SlotBatch{});
 // weight-gradient kernels add into wpart (replicated scratch, zero on entry and on exit) when the
 // tensor fits, else straight into gw; launch_wpart_reduce folds the replicas into gw.
-int launch_pw_bwd_weight(const float* gz, int g_ld, const void* x, int x_dtype, int x_ld, ChanTab it, float* gw,
-                         float* wpart, long long M, int N, int K, hipStream_t s, const SlotBatch& sb = SlotBatch{},
+int launch_pw_bwd_weight(const float* gz, int g_ld, const float* x, int x_ld, ChanTab it, float* gw, float* wpart,
+                         long long M, int N, int K, hipStream_t s, const SlotBatch& sb = SlotBatch{},
                          long long gz_slot_stride = -1);
 int launch_wpart_reduce(float* gw, float* wpart, int n, hipStream_t s);
 // bn_bwd_gz + data gradient + weight gradient of a pointwise layer in one pass (few-channel layers; fp32 buffers)
@@ -278,16 +278,13 @@ bool pw_bwd_fused_reduces_input(int cout, int cin);
 int launch_pw_bwd_fused(const PwBwdFusedArgs& a, hipStream_t s);
 int launch_dw_bwd_data(const float* gz, int g_ld, const float* w, float* gin, int gin_ld, int C, int H, int W, int OH,
                        int OW, int N, int stride, int accumulate, hipStream_t s, const SlotBatch& sb = SlotBatch{});
-int launch_dw_bwd_weight(const float* gz, int g_ld, const void* x, int x_dtype, int x_ld, ChanTab it, float* gw,
-                         float* wpart, int C, int H, int W, int OH, int OW, int N, int stride, hipStream_t s,
-                         const SlotBatch& sb = SlotBatch{});
-// z != null: gz is d loss / d activation and the BN + SiLU backward (g_z) is applied while staging
+int launch_dw_bwd_weight(const float* gz, int g_ld, const float* x, int x_ld, ChanTab it, float* gw, float* wpart, int C,
+                         int H, int W, int OH, int OW, int N, int stride, hipStream_t s, const SlotBatch& sb = SlotBatch{});
+// gz is d loss / d activation of the stem's output z: the BN + SiLU backward (g_z) is applied while staging
 int launch_stem_bwd_weight(const StemArgs& a, const float* gz, int g_ld, float* gw, float* wpart, hipStream_t s,
-                           const SlotBatch& sb = SlotBatch{}, const float* z = nullptr, int z_ld = 0,
-                           ChanTab ot = ChanTab{nullptr, nullptr, nullptr}, const float* save = nullptr,
-                           const float* consts = nullptr);
-int launch_spp_bwd(const void* cat, int dtype, float* gcat, int ld, int h, int H, int W, int N, ChanTab it,
-                   hipStream_t s, const SlotBatch& sb = SlotBatch{});
+                           const SlotBatch& sb, const float* z, int z_ld, ChanTab ot, const float* save, const float* consts);
+int launch_spp_bwd(const float* cat, float* gcat, int ld, int h, int H, int W, int N, ChanTab it, hipStream_t s,
+                   const SlotBatch& sb = SlotBatch{});
 int launch_upsample_bwd(const float* gdst, int dst_ld, float* gsrc, int src_ld, int C, int H, int W, int N,
                         int accumulate, hipStream_t s, const SlotBatch& sb = SlotBatch{});
 int launch_grad_copy(const float* src, int src_ld, float* dst, int dst_ld, int C, long long M, int accumulate,

@@ -1,4 +1,4 @@
-// "Normalize on read" helpers shared by the forward kernels: a = flag ? silu(z * scale + shift) : z, and the
+// "Normalize on read" helpers shared by the conv-stack kernels: a = flag ? silu(z * scale + shift) : z, and the
 // per-channel (scale, shift, flag) entries — from the table, or (deferred entries, see ChanTab in jn_kernels.h)
 // straight from the batch sums of the producing layer.
 #pragma once
@@ -10,6 +10,12 @@
 namespace jnr {
 
 __device__ __forceinline__ float silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
+// silu'(y), for the backward kernels
+__device__ __forceinline__ float sigmoidf_(float v) { return __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
+__device__ __forceinline__ float dsilu_(float y) {
+  const float s = sigmoidf_(y);
+  return s * (1.0f + y * (1.0f - s));
+}
 
 __device__ __forceinline__ f32x4 tf4(f32x4 z, f32x4 sc, f32x4 sh, f32x4 fl) {
   f32x4 r;

@@ -1212,9 +1212,11 @@ __global__ __launch_bounds__(256) void spp4_kernel(float* __restrict__ cat, int 
 
 int launch_spp(void* cat, int dtype, int ld, int h, int H, int W, int N, ChanTab it, const int* skip_flag,
                int skip_when, hipStream_t s) {
-  if (dtype == JN_F32 && h % 16 == 0 && ld % 4 == 0 && H * W * 4 <= 2048) {
-    hipLaunchKernelGGL(spp4_kernel<4>, dim3(h / 16, N), dim3(256), (size_t)H * W * 4 * 2 * sizeof(f32x4), s, (float*)cat, ld, h, H, W, it,
-                       skip_flag, skip_when);
+  // spp4_kernel<4>: 128 bytes of dynamic LDS per pixel beside its static table tb[]; together within the 64 KB a kernel
+  // may use without a grant (H * W <= 510, inside the 2048 elements its threads cover).  Larger maps: spp_kernel
+  const size_t smem4 = (size_t)H * W * 4 * 2 * sizeof(f32x4), tb4 = 3 * 4 * 4 * sizeof(float);
+  if (dtype == JN_F32 && h % 16 == 0 && ld % 4 == 0 && smem4 + tb4 <= 64 * 1024) {
+    hipLaunchKernelGGL(spp4_kernel<4>, dim3(h / 16, N), dim3(256), smem4, s, (float*)cat, ld, h, H, W, it, skip_flag, skip_when);
     return 0;
   }
   // channels per block: 2 * HW * cb floats of LDS; 8 -> 1024 workgroups at B = 64 (measured 40.9 us with 32 or 16, 31.9 us with 8)

@@ -953,9 +953,9 @@ constexpr int CW_BO = 64, CW_BK = 32, CW_LDG = CW_BO + 4, CW_LDX = CW_BK + 4;
 // when they leave LDS and every 16 x 16 x 32 block takes three v_mfma_f32_16x16x32_bf16 (hi*hi + hi*lo + lo*hi) — a weight
 // gradient is a leaf, its ~1e-5 relative error reaches the optimiser only.  Lane group g of a 32-pixel k-step takes
 // pixels (row e >> 2, column 4 g + (e & 3)) of the step's two tile rows: conflict-free for both LDS tiles at stride 1.
-template <int S, typename XT, int TH, bool SP>
+template <int S, int TH, bool SP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(S == 2 ? 2 : 1))) void conv3_bwd_weight_kernel(const float* __restrict__ gz, int g_ld,
-                                                               const XT* __restrict__ x, int x_ld, ChanTab it,
+                                                               const float* __restrict__ x, int x_ld, ChanTab it,
                                                                float* __restrict__ gw, int H, int W, int OH, int OW,
                                                                int Co, int Ci, int tiles_x, int tiles_y, int n_tiles,
                                                                SlotBatch sb) {
@@ -1212,7 +1212,7 @@ __global__ __launch_bounds__(256, 2) void conv3_bwd_weight_tr_kernel(const float
 
 // what the weight-gradient launchers below share
 struct Conv3WLaunch {
-  dim3 grid; const float* gz; int g_ld; const void* x; int x_ld; ChanTab it; float* gw;
+  dim3 grid; const float* gz; int g_ld; const float* x; int x_ld; ChanTab it; float* gw;
   int H, W, OH, OW, Co, Ci, tiles_x, tiles_y, n_tiles; SlotBatch sb;
 };
 
@@ -1222,28 +1222,28 @@ static int launch_cw_tr(const Conv3WLaunch& a, hipStream_t s) {
   constexpr int IHW = (4 * S + 2) * (C3_TW * S + 2);
   constexpr size_t smem = ((size_t)2 * 4 * C3_TW * 80 + (size_t)2 * IHW * (S == 1 ? 48 : 40)) * sizeof(bf16_t);
   if (!allow_lds<&conv3_bwd_weight_tr_kernel<S>>(smem)) return -1;
-  hipLaunchKernelGGL((conv3_bwd_weight_tr_kernel<S>), a.grid, dim3(256), smem, s, a.gz, a.g_ld, (const float*)a.x, a.x_ld, a.it,
-                     a.gw, a.H, a.W, a.OH, a.OW, a.Co, a.Ci, a.tiles_x, a.tiles_y, a.n_tiles, a.sb);
+  hipLaunchKernelGGL((conv3_bwd_weight_tr_kernel<S>), a.grid, dim3(256), smem, s, a.gz, a.g_ld, a.x, a.x_ld, a.it, a.gw, a.H, a.W,
+                     a.OH, a.OW, a.Co, a.Ci, a.tiles_x, a.tiles_y, a.n_tiles, a.sb);
   return 0;
 }
 
-template <int S, typename T, bool SP>
+template <int S, bool SP>
 static int launch_cw(const Conv3WLaunch& a, hipStream_t s) {
   constexpr int TH = 4;
   constexpr size_t smem = ((size_t)TH * C3_TW * CW_LDG + (size_t)(TH * S + 2) * (C3_TW * S + 2) * CW_LDX) * sizeof(float);
-  if (!allow_lds<&conv3_bwd_weight_kernel<S, T, TH, SP>>(smem)) return -1;
-  hipLaunchKernelGGL((conv3_bwd_weight_kernel<S, T, TH, SP>), a.grid, dim3(256), smem, s, a.gz, a.g_ld, (const T*)a.x, a.x_ld,
-                     a.it, a.gw, a.H, a.W, a.OH, a.OW, a.Co, a.Ci, a.tiles_x, a.tiles_y, a.n_tiles, a.sb);
+  if (!allow_lds<&conv3_bwd_weight_kernel<S, TH, SP>>(smem)) return -1;
+  hipLaunchKernelGGL((conv3_bwd_weight_kernel<S, TH, SP>), a.grid, dim3(256), smem, s, a.gz, a.g_ld, a.x, a.x_ld, a.it, a.gw, a.H,
+                     a.W, a.OH, a.OW, a.Co, a.Ci, a.tiles_x, a.tiles_y, a.n_tiles, a.sb);
   return 0;
 }
 
-template <int S, typename T>
+template <int S>
 static int launch_cw(const Conv3WLaunch& a, bool exact, hipStream_t s) {
-  return exact ? launch_cw<S, T, false>(a, s) : launch_cw<S, T, true>(a, s);
+  return exact ? launch_cw<S, false>(a, s) : launch_cw<S, true>(a, s);
 }
 
-int launch_conv3_bwd_weight(const float* gz, int g_ld, const void* x, int x_dtype, int x_ld, ChanTab it, float* gw, int H,
-                            int W, int OH, int OW, int Co, int Ci, int N, int stride, hipStream_t s, const SlotBatch& sb) {
+int launch_conv3_bwd_weight(const float* gz, int g_ld, const float* x, int x_ld, ChanTab it, float* gw, int H, int W, int OH,
+                            int OW, int Co, int Ci, int N, int stride, hipStream_t s, const SlotBatch& sb) {
   const int TH = 4;
   const int tiles_x = (OW + C3_TW - 1) / C3_TW, tiles_y = (OH + TH - 1) / TH, n_tiles = tiles_x * tiles_y * N;
   const int nbo = (Co + CW_BO - 1) / CW_BO, nbk = (Ci + CW_BK - 1) / CW_BK;
@@ -1253,10 +1253,9 @@ int launch_conv3_bwd_weight(const float* gz, int g_ld, const void* x, int x_dtyp
   const Conv3WLaunch a = {dim3((unsigned)gx, nbo, nbk * sb.n), gz, g_ld, x, x_ld, it, gw, H, W, OH, OW, Co, Ci,
                           tiles_x, tiles_y, n_tiles, sb};
   static const bool exact = std::getenv("JN_WW_EXACT") != nullptr;
-  if (!exact && x_dtype == JN_F32 && Co % 16 == 0 && Ci % 4 == 0 && g_ld % 4 == 0 && x_ld % 4 == 0)
+  if (!exact && Co % 16 == 0 && Ci % 4 == 0 && g_ld % 4 == 0 && x_ld % 4 == 0)
     return stride == 1 ? launch_cw_tr<1>(a, s) : launch_cw_tr<2>(a, s);
-  if (x_dtype == JN_BF16) return stride == 1 ? launch_cw<1, bf16_t>(a, exact, s) : launch_cw<2, bf16_t>(a, exact, s);
-  return stride == 1 ? launch_cw<1, float>(a, exact, s) : launch_cw<2, float>(a, exact, s);
+  return stride == 1 ? launch_cw<1>(a, exact, s) : launch_cw<2>(a, exact, s);
 }
 
 }  // namespace jnr

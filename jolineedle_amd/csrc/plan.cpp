@@ -390,17 +390,18 @@ int shortcut_sum_conv(const Net& net, const View& seg, int reader, int also, int
 
 }  // namespace
 
-// The backward of `net` as a pure function of its topology, activation dtype, the head (with_head) and the FPN outputs
-// that get no outside gradient (fpn_zero bit i: none arrives in fpn[i], the training backward's case): one record per
-// op of the backward range, filled walking it in reverse like the launcher (run_net_backward, api_net.hip).
+// The backward of `net` as a pure function of its topology, the head (with_head) and the FPN outputs that get no
+// outside gradient (fpn_zero bit i: none arrives in fpn[i], the training backward's case): one record per op of the
+// backward range, filled walking it in reverse like the launcher (run_net_backward, api_net.hip).  fp32 activations
+// only: the backward kernels read nothing else.
 int plan_backward(const Net& net, bool with_head, int fpn_zero, std::vector<BwdStep>& plan) {
+  JN_CHECK(net.act_dtype == JN_F32, JN_ESTATE, "training needs act_dtype = fp32 (bf16 is the inference mode)");
   const int n = (with_head || net.n_backbone_ops < 0) ? (int)net.ops.size() : net.n_backbone_ops;
-  const bool f32 = net.act_dtype == JN_F32;
   plan.assign(n, BwdStep{});
   auto fused_whole = [&](int j) {       // a 1x1 conv that takes pw_bwd_fused_kernel in one piece
     const Op& o = net.ops[j];
     const ConvW& cw = net.convs[o.wslot];
-    return o.kind == OP_PW && f32 && cw.prefix2.empty() && pw_bwd_fused_supported(cw.cout, cw.cin);
+    return o.kind == OP_PW && cw.prefix2.empty() && pw_bwd_fused_supported(cw.cout, cw.cin);
   };
   for (int i = n - 1; i >= 0; --i) {
     const Op& op = net.ops[i];
@@ -412,7 +413,7 @@ int plan_backward(const Net& net, bool with_head, int fpn_zero, std::vector<BwdS
       // a merged pair too wide for the fused kernel is differentiated as its two halves (independent output rows)
       const bool whole = pw_bwd_fused_supported(cw.cout, cw.cin);
       const bool halves = !whole && !cw.prefix2.empty() && 2 * cw.cout_first == cw.cout && pw_bwd_fused_supported(cw.cout_first, cw.cin);
-      if (op.kind == OP_PW && f32 && (whole || halves)) {
+      if (op.kind == OP_PW && (whole || halves)) {
         st.route = whole ? BR_PW_FUSED : BR_PW_FUSED_HALVES;
         // BN-backward sums of the input's producer(s) in the kernel's epilogue: it must write the FINAL gradient of the
         // view (sole reader, or the shortcut folded in) — one run, or the two halves of a CSP conv3's input
@@ -431,7 +432,7 @@ int plan_backward(const Net& net, bool with_head, int fpn_zero, std::vector<BwdS
           }
           if (st.red_in >= 0 || st.red_in2 >= 0) st.red_split = hC;   // (a lone second run still needs the split)
         }
-      } else if (op.kind == OP_DW && f32 && dw_bwd_fused_supported(cw.cout, op.in.H, op.in.W, op.out.H, op.out.W, op.stride)) {
+      } else if (op.kind == OP_DW && dw_bwd_fused_supported(cw.cout, op.in.H, op.in.W, op.out.H, op.out.W, op.stride)) {
         st.route = BR_DW_FUSED;
         // A view that only the network's outside could also write (an FPN output) and that gets no outside gradient in
         // this backward (fpn_zero) is an ordinary single-consumer output: the kernel then WRITES its gradient (the
@@ -440,7 +441,7 @@ int plan_backward(const Net& net, bool with_head, int fpn_zero, std::vector<BwdS
         for (int k = 0; k < 3; ++k) ext_zero = ext_zero || (((fpn_zero >> k) & 1) && views_overlap(op.in, net.fpn[k]));
         if (!op.acc_in || ext_zero) st.red_in = bn_producer(net, op.in, i, -1, fpn_zero, &st.red_half);
       } else if (op.kind == OP_STEM) {
-        st.route = f32 ? BR_STEM_FUSED : BR_STEM;
+        st.route = BR_STEM_FUSED;
       } else if (op.kind == OP_PW) {
         st.route = BR_PW;
       } else if (op.kind == OP_DW) {
@@ -471,7 +472,7 @@ int plan_backward(const Net& net, bool with_head, int fpn_zero, std::vector<BwdS
         conv1 = j;
         return true;
       }) >= 0;
-      const bool fold = f32 && !op.acc_res && one_reader && conv1 >= 0 && net.ops[conv1].acc_in && fused_whole(conv1) &&
+      const bool fold = !op.acc_res && one_reader && conv1 >= 0 && net.ops[conv1].acc_in && fused_whole(conv1) &&
                         z >= 0 && fused_whole(z);
       if (fold) plan[conv1].fold = i;
       st.route = fold ? BR_ADDACT_FOLD : BR_ADDACT_COPY;

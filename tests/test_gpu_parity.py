@@ -1946,6 +1946,12 @@ def test_bf16_mode_refuses_training():
     tr = ja.ReinforceTrainer(_cfg(T=3, learning_rate=1e-3, gradient_accumulation=1), product)
     with pytest.raises(_lib.JnError, match="fp32"):
         tr.train_iteration(env, start_positions=start)
+    # the backward itself refuses too (jn_backbone_backward reaches it without a training entry point in front)
+    x = torch.rand((2, 3, 64, 64), generator=torch.Generator().manual_seed(2))
+    R = [torch.ones_like(m) for m in product.backbone_features(x)]
+    assert len(R) == 3
+    with pytest.raises(_lib.JnError, match="fp32"):
+        product.backbone_backward(x, R)
 
 
 # --------------------------------------------------------------------------------------

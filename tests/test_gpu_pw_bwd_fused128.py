@@ -1,4 +1,4 @@
-"""The fused pointwise backward at 128 input channels (csrc/kernels_bwd.hip: ``pw_bwd_fused128_kernel``, 32-pixel tiles, two
+"""The fused pointwise backward at 128 input channels (csrc/kernels_bwd_pw.hip: ``pw_bwd_fused128_kernel``, 32-pixel tiles, two
 workgroups per CU, W^T streamed in fragment order) through the context-free entry ``jn_pw_bwd_fused``: against an fp64
 restatement of the formulas in the kernel's header comment, and against the 64-pixel kernel (route 1) it replaces.
 
