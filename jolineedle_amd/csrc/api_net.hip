@@ -326,11 +326,11 @@ int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int train, 
   };
   auto ld = [&](const View& v) { return net.bufs[v.buf].C; };
   auto finalize = [&](const Op& op, const ConvW& cw, bool deferred) {
-    if (!train || !cw.has_bn || deferred) return;
+    if (!train || !cw.has_bn || deferred) return 0;
     ChanTab t1{nullptr, nullptr, nullptr};
     if (op.alias.buf >= 0) t1 = tab(op.alias);
     // with the end-of-pass finalize (defer): table only here, saved / running statistics there
-    launch_bn_finalize(stats + 2 * cw.stat_off, rep_stride, (double)N * op.out.H * op.out.W, cw.gamma_dev, cw.beta_dev,
+    return launch_bn_finalize(stats + 2 * cw.stat_off, rep_stride, (double)N * op.out.H * op.out.W, cw.gamma_dev, cw.beta_dev,
                        defer ? nullptr : cw.rmean_dev, defer ? nullptr : cw.rvar_dev, defer ? nullptr : save + 2 * cw.stat_off,
                        tab(op.out), t1, cw.cout, kBnEps, kBnMomentum, skip_flag, skip_when, s);
   };
@@ -341,6 +341,7 @@ int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int train, 
   for (int oi = first_op; oi < n_ops; ++oi) {
     const Op& op = net.ops[oi];
     const FwdStep& st = plan[oi - first_op];
+    int lrc = 0;      // of the op's launchers: non-zero ends the pass
     switch (st.route) {
       case FR_STEM: {
         const ConvW& cw = net.convs[op.wslot];
@@ -348,8 +349,7 @@ int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int train, 
         a.out = ptr(op.out); a.out_ld = ld(op.out); a.out_dtype = net.act_dtype; a.skip_flag = skip_flag; a.skip_when = skip_when;
         a.stats = train ? stats + 2 * cw.stat_off : nullptr; a.stats_rep_stride = rep_stride;
         a.stats_nrep = st.deferred ? JN_NREP_DEFER : JN_NREP;
-        launch_stem(a, s);
-        finalize(op, cw, st.deferred);
+        if (!(lrc = launch_stem(a, s))) lrc = finalize(op, cw, st.deferred);
         break;
       }
       case FR_DWPW:
@@ -365,7 +365,7 @@ int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int train, 
           f.res = ptr(ad.res); f.res_ld = ld(ad.res); f.rtab = tab(ad.res); f.ptab = tab(nx.out);
           f.out = ptr(ad.out); f.out_ld = ld(ad.out);
         }
-        launch_dwpw(f, s);
+        lrc = launch_dwpw(f, s);
         break;
       }
       case FR_CONV: {
@@ -382,35 +382,35 @@ int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int train, 
         a.stats_rep_stride = rep_stride;
         a.stats_nrep = st.deferred ? JN_NREP_DEFER : JN_NREP;
         a.skip_flag = skip_flag; a.skip_when = skip_when;
-        if (st.link >= 0 && pw_fused_upsample_supported(a)) {      // the planned candidate, where this launch's route can
+        if (st.link >= 0 && pw_fuses_upsample(pw_route(a), a.cin, a.cout)) {      // the planned candidate, where this launch's route can
           const Op& up = net.ops[st.link];
           a.up_out = ptr(up.out); a.up_ld = ld(up.out); up_done[st.link] = 1;
         }
-        if (op.kind == OP_PW) { JN_CHECK(launch_pw(a, s) == 0, JN_ESTATE, "1x1 conv %s: no kernel for this shape", op.name.c_str()); }
-        else if (op.kind == OP_DW) launch_dw(a, s); else launch_conv3(a, s);
-        finalize(op, cw, st.deferred);
+        lrc = op.kind == OP_PW ? launch_pw(a, s) : op.kind == OP_DW ? launch_dw(a, s) : launch_conv3(a, s);
+        if (!lrc) lrc = finalize(op, cw, st.deferred);
         break;
       }
       case FR_SPP:
-        launch_spp(view_ptr(net, slot, MB, net_full_view(net, op.out.buf)), net.act_dtype, ld(op.out), op.in.C, op.in.H, op.in.W, N,
+        lrc = launch_spp(view_ptr(net, slot, MB, net_full_view(net, op.out.buf)), net.act_dtype, ld(op.out), op.in.C, op.in.H, op.in.W, N,
                    tab(op.in), skip_flag, skip_when, s);
         break;
       case FR_UPSAMPLE:
         if (!up_done[oi])
-          launch_upsample(ptr(op.in), ld(op.in), ptr(op.out), ld(op.out), net.act_dtype, op.in.C, op.in.H, op.in.W, N, skip_flag,
+          lrc = launch_upsample(ptr(op.in), ld(op.in), ptr(op.out), ld(op.out), net.act_dtype, op.in.C, op.in.H, op.in.W, N, skip_flag,
                           skip_when, s);
         break;
       case FR_ADDACT:
-        launch_addact(ptr(op.in), ld(op.in), tab(op.in), ptr(op.res), ld(op.res), tab(op.res), ptr(op.out), ld(op.out),
+        lrc = launch_addact(ptr(op.in), ld(op.in), tab(op.in), ptr(op.res), ld(op.res), tab(op.res), ptr(op.out), ld(op.out),
                       net.act_dtype, op.out.C, (long long)N * op.out.H * op.out.W, skip_flag, skip_when, s);
         break;
       case FR_PRED:
-        launch_head_pred(ptr(op.in), ld(op.in), tab(op.in), ptr(op.res), ld(op.res), tab(op.res), net.act_dtype, net.pred_w[op.level],
+        lrc = launch_head_pred(ptr(op.in), ld(op.in), tab(op.in), ptr(op.res), ld(op.res), tab(op.res), net.act_dtype, net.pred_w[op.level],
                          net.pred_b[op.level], train ? ctx->det_logits : ctx->det_raw, net.head_hid, op.in.H, op.in.W, op.stride,
                          net.n_anchors, op.anchor0, N, s, train ? 1 : 0);
         break;
       case FR_ABSORBED: case FR_NONE: break;   // covered by the kernel of op st.link
     }
+    JN_CHECK(lrc == 0, JN_ESTATE, "forward of %s: no kernel for this shape, or its LDS was refused", op.name.c_str());
     prof.mark(oi + 1);
   }
   if (prof) {
@@ -435,7 +435,7 @@ int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int train, 
     fa.tab = net.tab + (size_t)slot * 3 * net.tab_channels; fa.tab_channels = net.tab_channels; fa.save = save;
     fa.run_mean = net.fd_rm; fa.run_var = net.fd_rv; fa.eps = kBnEps; fa.momentum = kBnMomentum;
     fa.skip_flag = skip_flag; fa.skip_when = skip_when; fa.defer_max_m = JN_DEFER_MAX_M;
-    launch_bn_finalize_all(fa, s);
+    JN_CHECK(launch_bn_finalize_all(fa, s) == 0, JN_ESTATE, "forward: the end-of-pass BatchNorm finalize was not launched");
   }
   JN_HIP(hipGetLastError());
   if (train) net.eval_tab_dirty = true;     // running statistics moved
@@ -674,7 +674,8 @@ int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, hi
         // split on the way: kernels_pwxs.hip); JN_NO_PW_X3_BWD=1 keeps pw_dir_kernel<WT> on the fp32 pipe
         const bool x3 = !std::getenv("JN_NO_PW_X3_BWD") && !op.acc_in && ctx->params_x3t &&      // read per launch: a test flips it
                         pw_x3_bwd_data_supported(cw.cout, cw.cin) && (cw.w_dev - ctx->params) % 8 == 0;
-        if (!x3 || launch_pw_x3_bwd_data(a, cw.w_dev, ctx->params_x3t + 3 * (cw.w_dev - ctx->params), s) != 0) launch_pw(a, s);
+        if (!x3 || launch_pw_x3_bwd_data(a, cw.w_dev, ctx->params_x3t + 3 * (cw.w_dev - ctx->params), s) != 0)
+          JN_CHECK(launch_pw(a, s) == 0, JN_ESTATE, "data gradient of %s: no kernel for this shape, or its LDS was refused", op.name.c_str());
         JN_CHECK(launch_pw_bwd_weight(c.g, c.g_ld, ptr(op.in), ld(op.in), tab(op.in), c.gw, ctx->wpart, M, cw.cout, cw.cin, ws, sb) == 0,
                  JN_ESTATE, "launch_pw_bwd_weight: %s has no kernel, or its LDS was refused", op.name.c_str());
         break;
@@ -742,7 +743,7 @@ int run_embed_fpn(jn_ctx* ctx, int N, int slot, float* e_buf, const int* skip_fl
   a.w = ctx->gpt.efpn_w; a.bias = nullptr; a.out = e_buf; a.out_ld = C;
   a.N = N; a.H = f.H; a.W = f.W; a.OH = f.H; a.OW = f.W; a.cin = f.C; a.cout = C; a.stride = 1; a.act = ACT_RELU;
   a.skip_flag = skip_flag; a.skip_when = skip_when;
-  launch_pw(a, s);
+  JN_CHECK(launch_pw(a, s) == 0, JN_ESTATE, "embed_fpn.0: no kernel for this shape, or its LDS was refused");
   launch_efpn_linear(e_buf, ctx->gpt.efpn_lin_wt, x.emb_part, N, f.H * f.W * C, C, x.KS, skip_flag, skip_when, s);
   JN_HIP(hipGetLastError());
   return JN_OK;

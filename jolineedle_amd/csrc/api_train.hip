@@ -161,7 +161,7 @@ static int encoder_backward(jn_ctx* ctx, int g_n, int rows, int slot, const floa
   la2.in = dpe; la2.in_ld = C; la2.in_dtype = JN_F32; la2.itab = ident; la2.w = g.efpn_lin_wt; la2.bias = nullptr;
   la2.out = ctx->de_ws; la2.out_ld = K; la2.out_dtype = JN_F32; la2.bf16_mfma = 0;
   la2.N = (int)Mr; la2.H = 1; la2.W = 1; la2.OH = 1; la2.OW = 1; la2.cin = C; la2.cout = K; la2.stride = 1; la2.act = ACT_NONE;
-  launch_pw(la2, s);
+  JN_CHECK(launch_pw(la2, s) == 0, JN_ESTATE, "backward of embed_fpn.3: no kernel for this shape, or its LDS was refused");
   launch_relu_mask(ctx->de_ws, e, Mr * K, s);
   launch_pw_bwd_weight(e, K, dpe, C, ident, grad_of(ctx, g.efpn_lin_wt), nullptr, Mr, K, C, s);
   launch_colsum_add(dpe, Mr, C, grad_of(ctx, g.efpn_lin_b), s);
@@ -178,7 +178,7 @@ static int encoder_backward(jn_ctx* ctx, int g_n, int rows, int slot, const floa
   // the detector's PAFPN as patch encoder is detached (src/models/gpt.py:376-380 "Do not backpropagate through
   // yolox"): the policy gradient stops at embed_fpn.0's weight
   const bool detached = ctx->enc_net == JN_NET_DETECTOR;
-  if (!detached) launch_pw(a, s);
+  JN_CHECK(detached || launch_pw(a, s) == 0, JN_ESTATE, "backward of embed_fpn.0: no kernel for this shape, or its LDS was refused");
   launch_pw_bwd_weight(ctx->de_ws, C, (const float*)view_ptr(net, slot, MB, f2), net.bufs[f2.buf].C, view_tab(net, slot, f2),
                        grad_of(ctx, g.efpn_w), ctx->wpart, (long long)rows * HW, C, f2.C, s, sb, (long long)rows * K);
   if (detached) return JN_OK;

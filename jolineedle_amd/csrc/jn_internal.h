@@ -165,7 +165,7 @@ enum FwdRoute {
 struct FwdStep {           // op indices and flags only: the launcher turns them into pointers
   FwdRoute route = FR_NONE;
   // FR_ABSORBED: the op whose kernel covers this one.  FR_DWPW / FR_DWPW_ADD: the pointwise op.  FR_CONV of an fp32 1x1
-  // conv: the upsample whose copy its kernel MAY write (the launcher asks pw_fused_upsample_supported).  -1: none
+  // conv: the upsample whose copy its kernel MAY write (the launcher asks pw_fuses_upsample of its route).  -1: none
   int link = -1;
   int add = -1;            // FR_DWPW_ADD: the shortcut add
   bool deferred = false;   // BatchNorm conv: no finalize launch of its own, its consumers read the batch sums

@@ -74,6 +74,18 @@ bool allow_lds(size_t bytes) {
   return true;
 }
 
+// Persistent grids are sized in resident rounds: workgroups one CU holds x the CUs of the chip.
+constexpr int JN_NUM_CU = 256;
+// Workgroups (256 threads, `smem` bytes of dynamic LDS) of the kernel that fit one CU: asked once per kernel, whose LDS
+// size is a function of its template arguments; `fallback` when the runtime cannot say.  LDS above 64 KB: allow_lds first.
+template <auto Kernel>
+int resident_per_cu(size_t smem, int fallback) {
+  static int per_cu = 0;
+  if (!per_cu && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(Kernel), 256, smem) != hipSuccess || per_cu < 1))
+    per_cu = fallback;
+  return per_cu;
+}
+
 struct StemArgs {
   const void* src; const int64_t* positions; int pos_stride;    // positions[pos_stride * n + {0,1}] = (y, x)
   long long sample_stride, chan_stride; int row_stride;
@@ -102,8 +114,8 @@ struct ConvArgs {
   int n_slots;                           // pw: gridDim.z slots, pointers advance by the strides below (0 -> 1 slot)
   long long in_slot_stride, out_slot_stride, tab_slot_stride;
   const void* w_x3;                      // 1x1, fp32: the weights split into three bf16 planes (launch_w_split3), or null
-  void* up_out; int up_ld;               // 1x1, fp32: also store the output nearest-x2 upsampled here (pixel stride up_ld floats), see
-                                         // pw_fused_upsample_supported; null: no
+  void* up_out; int up_ld;               // 1x1, fp32: also store the output nearest-x2 upsampled here (pixel stride up_ld floats), where
+                                         // pw_fuses_upsample(pw_route(a), cin, cout); null: no
 };
 
 // eval-mode DWConv (depthwise 3x3 -> BN + SiLU -> pointwise 1x1) in one kernel; mtab = table of the depthwise output
@@ -119,11 +131,42 @@ int launch_dwpw(const DwPwArgs& a, hipStream_t s);
 int launch_stem(const StemArgs& a, hipStream_t s);
 bool stem_rows_aligned(const StemArgs& a);        // the stem kernels may fetch the image tile with 4-element loads
 int launch_dw(const ConvArgs& a, hipStream_t s);
+// ---- 1x1 convs: THE route of a launch (kernels_conv.hip) ------------------------------------------------------------
+// Which kernel family runs a 1x1 conv is decided once, by pw_route, a pure function of the arguments (and of the test hook
+// JN_PWN_MIN_M); launch_pw is a switch over it, and a launcher handed its route launches or fails (-1: no instantiation, or
+// the LDS was refused).  The clauses, in order:
+//   X1 / X3 / XS  at most JN_XS_MAX_M pixels, forward: the pixel-stationary kernels of kernels_pwxs.hip — bf16 inference
+//                 mode, fp32 as three bf16 planes (a.w_x3 given and in fragment order), fp32 pipe
+//   WIDE          K, N >= 64, forward and data gradient: pw_dir_kernel (kernels_pwres.hip)
+//   NARROW        K <= 64, forward, at least JN_PW_BIG_M pixels: pw_narrow_kernel
+//   MFMA          everything else: pw_mfma_kernel
+// With a.up_out set only the routes and shapes of pw_fuses_upsample remain, anything else is NONE.
+enum PwRoute { PW_NONE = 0, PW_X1, PW_X3, PW_XS, PW_WIDE, PW_NARROW, PW_MFMA };
+PwRoute pw_route(const ConvArgs& a);
 int launch_pw(const ConvArgs& a, hipStream_t s);
-bool pw_fused_upsample_supported(const ConvArgs& a);   // launch_pw(a) with a.up_out set will take a route that writes the upsampled copy
+// Pixels per launch (N * H * W; times the slots where said) at which the routes and tilings change:
+// the pixel-stationary kernels up to here (the 56x56 / 28x28 / 14x14 maps of the headline batch: 10 - 30 % under the
+// weight-stationary kernel on every one of them, profiles/r03_pwxsbench.txt)
+constexpr long long JN_XS_MAX_M = 262144;
+// from here on a persistent kernel has tiles to walk: pw_narrow_kernel's minimum (JN_PWN_MIN_M: test hook, read per launch so
+// that a test can force the kernel onto small maps), and 64 -> 64 on pw_dir_kernel (below: pw_mfma_kernel, 14.3 against
+// 14.6 us at 28x28)
+constexpr long long JN_PW_BIG_M = 65536;
+// pw_mfma_kernel, data gradients (all slots): 64-pixel workgroups up to here, 128-pixel ones above (JN_PW_WT_SMALL_M: test hook,
+// read per launch - 0 forces the large-map variant onto the small parity shapes)
+constexpr long long JN_PW_WT_SMALL_M = 65536;
+// 14x14 maps at 64 patches: pw_mfma_kernel's 32-pixel workgroups (all slots), one pw_x3 workgroup per CU at 128 -> 128
+constexpr long long JN_PW_TINY_M = 16384;
+// fp32 buffers on the fp32 pipe, no bias / activation epilogue ...
+inline bool pw_f32_bare(const ConvArgs& a) {
+  return !a.bf16_mfma && a.in_dtype == JN_F32 && a.out_dtype == JN_F32 && !a.bias && a.act == ACT_NONE;
+}
+// ... of a plain forward layer: weight [N][K], output written, one slot
+inline bool pw_f32_plain(const ConvArgs& a) { return pw_f32_bare(a) && !a.w_transposed && !a.accumulate && a.n_slots <= 1; }
+bool pw_fuses_upsample(PwRoute r, int cin, int cout);  // kernels_pwxs.hip: the route's kernel for this shape can also write a.up_out
 bool pw_res_supported(const ConvArgs& a);              // kernels_pwres.hip: shapes the resident-weight 1x1 kernels take (K, N >= 64)
+int pw_dir_auto_ctw(int cin, int cout);                // launch_pw_dir's automatic slice (channel tiles), 0: none fits
 int launch_pw_dir(const ConvArgs& a, int ctw, hipStream_t s);
-int launch_pw_wide(const ConvArgs& a, hipStream_t s);   // production route: 0 when taken
 bool pw_xs_supported(const ConvArgs& a);               // kernels_pwxs.hip: pixel-stationary kernel for the small maps of a forward pass
 int launch_pw_xs(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu = 0);   // pt: pixel tiles per workgroup (0 = default)
 // the same on the bf16 pipe (three-way split operands); needs a.w_x3.  frag: the order a.w_x3 is in (-1: the rule below; the
@@ -140,7 +183,6 @@ constexpr bool pw_x3_fragment_order(int cin, int cout) {
 }
 struct X3FragConv { long long off; int cout, cin; };   // a conv of the splitter's table: arena offset of its weight (floats, % 8 == 0)
 void launch_w_split3_frag(const float* params, void* params_x3, const X3FragConv* tab, int n_convs, int max_weights, hipStream_t s);
-bool pw_x3_preferred(const ConvArgs& a);
 // the data gradient of a wide 1x1 layer on pw_x3_kernel (transposed split weight made on the way); -1: shape not taken
 bool pw_x3_bwd_data_supported(int cout, int cin);
 int launch_pw_x3_bwd_data(const ConvArgs& a, const float* w, void* w3t, hipStream_t s);

@@ -600,18 +600,13 @@ __global__ __launch_bounds__(256) void pw_bwd_fused_kernel(
 template <int CTN, int CTK, bool RED, bool RED2 = false>
 static int launch_pw_bwd_fused_r(const PwBwdFusedArgs& a, hipStream_t s) {
   constexpr int N = 16 * CTN, K = 16 * CTK;
-  size_t smem = ((size_t)64 * (N + 4) + 64 * (K + 4) + (size_t)K * (N + 4) + 7 * N + 3 * K + (RED ? (RED2 ? 10 : 8) * K : 0)) * sizeof(float);
-  if (smem < (size_t)N * K * sizeof(float)) smem = (size_t)N * K * sizeof(float);
+  constexpr size_t tiles = ((size_t)64 * (N + 4) + 64 * (K + 4) + (size_t)K * (N + 4) + 7 * N + 3 * K + (RED ? (RED2 ? 10 : 8) * K : 0)) * sizeof(float);
+  constexpr size_t smem = std::max(tiles, (size_t)N * K * sizeof(float));
   if (!allow_lds<&pw_bwd_fused_kernel<CTN, CTK, RED, RED2>>(smem)) return -1;
   const long long n_tiles = (a.M + 63) / 64;
   // ~1024 persistent workgroups over all slots, in WHOLE resident rounds: an instantiation that fits 3 workgroups per CU
   // (768 places) ran 1020 of them, i.e. a second round at a third of the occupancy
-  static int places = 0;
-  if (!places) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&pw_bwd_fused_kernel<CTN, CTK, RED, RED2>), 256, smem) != hipSuccess || per_cu < 1) per_cu = 2;
-    places = per_cu * 256;
-  }
+  const int places = resident_per_cu<&pw_bwd_fused_kernel<CTN, CTK, RED, RED2>>(smem, 2) * JN_NUM_CU;
   const int rounds = std::max(1, (1024 + places / 2) / places);
   long long bx = (long long)rounds * places / a.sb.n;
   if (a.max_wg > 0 && bx > a.max_wg / a.sb.n) bx = a.max_wg / a.sb.n;
@@ -955,12 +950,7 @@ static void launch_pw_bwd_fused128(const PwBwdFusedArgs& a, hipStream_t s) {
   constexpr int N = 16 * CTN, K = 128;
   if (X3) launch_w_split3_t(a.w, a.w_frag, N, K, s);
   else hipLaunchKernelGGL(w_frag_t_kernel, dim3(N * K / 4 / 256), dim3(256), 0, s, a.w, a.w_frag, N, K);
-  static int places = 0;                // ONE resident round
-  if (!places) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&pw_bwd_fused128_kernel<CTN, D, X3>), 256, 0) != hipSuccess || per_cu < 1) per_cu = 2;
-    places = per_cu * 256;
-  }
+  const int places = resident_per_cu<&pw_bwd_fused128_kernel<CTN, D, X3>>(0, 2) * JN_NUM_CU;      // ONE resident round
   const long long n_tiles = (a.M + 31) / 32 * a.sb.n;
   long long bx = std::min<long long>(places, n_tiles);
   if (a.max_wg > 0) bx = std::min<long long>(bx, a.max_wg);

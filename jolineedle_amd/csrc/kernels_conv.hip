@@ -182,25 +182,28 @@ bool stem_rows_aligned(const StemArgs& a) {
          a.chan_stride % 4 == 0 && a.row_stride % 4 == 0 && a.P % 4 == 0;
 }
 
-int launch_stem(const StemArgs& a, hipStream_t s) {
+template <typename OT, bool VEC, typename ST>
+static void launch_stem_t(const StemArgs& a, hipStream_t s) {
   const int OH = a.P / 2;
   const int ocg = a.cout / 16;
   const int tiles_x = (OH + ST_TX - 1) / ST_TX, tiles_y = (OH + ST_TY - 1) / ST_TY, n_tiles = tiles_x * tiles_y * a.N;
-  int nwg = 512 / ocg;                                 // 2 persistent workgroups per CU (222 VGPRs)
+  int nwg = 2 * JN_NUM_CU / ocg;                       // 2 persistent workgroups per CU (222 VGPRs)
   if (nwg < 1) nwg = 1;
   if (nwg > n_tiles) nwg = n_tiles;
-  dim3 grid(nwg, ocg);
-  const int nrep = a.stats_nrep > 0 ? a.stats_nrep : JN_NREP;
-  const bool vec = stem_rows_aligned(a);
-#define JN_STEM(OT_, V_, ST_)                                                                                                \
-  hipLaunchKernelGGL((stem_mfma_kernel<OT_, V_, ST_>), grid, dim3(256), 0, s, (const ST_*)a.src, (const long long*)a.positions, \
-                     a.pos_stride, a.sample_stride, a.chan_stride, a.row_stride, a.P, a.w, (OT_*)a.out, a.out_ld, a.cout,    \
-                     tiles_x, tiles_y, n_tiles, a.stats, a.stats_rep_stride, a.skip_flag, a.skip_when, nrep)
-#define JN_STEM_V(OT_, ST_) do { if (vec) JN_STEM(OT_, true, ST_); else JN_STEM(OT_, false, ST_); } while (0)
-  if (a.src_u8) { if (a.out_dtype == JN_BF16) JN_STEM_V(bf16_t, uint8_t); else JN_STEM_V(float, uint8_t); }
-  else { if (a.out_dtype == JN_BF16) JN_STEM_V(bf16_t, float); else JN_STEM_V(float, float); }
-#undef JN_STEM_V
-#undef JN_STEM
+  hipLaunchKernelGGL((stem_mfma_kernel<OT, VEC, ST>), dim3(nwg, ocg), dim3(256), 0, s, (const ST*)a.src, (const long long*)a.positions,
+                     a.pos_stride, a.sample_stride, a.chan_stride, a.row_stride, a.P, a.w, (OT*)a.out, a.out_ld, a.cout,
+                     tiles_x, tiles_y, n_tiles, a.stats, a.stats_rep_stride, a.skip_flag, a.skip_when,
+                     a.stats_nrep > 0 ? a.stats_nrep : JN_NREP);
+}
+
+template <typename OT, typename ST>
+static void launch_stem_v(const StemArgs& a, hipStream_t s) {
+  if (stem_rows_aligned(a)) launch_stem_t<OT, true, ST>(a, s); else launch_stem_t<OT, false, ST>(a, s);
+}
+
+int launch_stem(const StemArgs& a, hipStream_t s) {
+  if (a.src_u8) { if (a.out_dtype == JN_BF16) launch_stem_v<bf16_t, uint8_t>(a, s); else launch_stem_v<float, uint8_t>(a, s); }
+  else { if (a.out_dtype == JN_BF16) launch_stem_v<bf16_t, float>(a, s); else launch_stem_v<float, float>(a, s); }
   return 0;
 }
 
@@ -617,6 +620,16 @@ int launch_dwpw(const DwPwArgs& a, hipStream_t s) {
   return -1;
 }
 
+template <int S, typename T>
+static void launch_dw_t(const ConvArgs& a, hipStream_t s) {      // any channel count: no LDS tile
+  const int YS = (a.OH + 3) / 4;
+  const long long total = (long long)a.N * YS * a.OW * (a.cin / 4);
+  const size_t smem = a.stats ? (size_t)2 * a.cin * sizeof(float) : 0;
+  hipLaunchKernelGGL((dw3x3_kernel<S, T>), dim3((unsigned)((total + 255) / 256)), dim3(256), smem, s, (const T*)a.in, a.in_ld, a.itab,
+                     a.w, (T*)a.out, a.out_ld, a.cin, a.H, a.W, a.OH, a.OW, a.N, a.stats, a.stats_rep_stride, a.skip_flag,
+                     a.skip_when);
+}
+
 int launch_dw(const ConvArgs& a, hipStream_t s) {
   if (a.cin % 16 == 0 && a.N <= 65535) {
     const bool bf = a.in_dtype == JN_BF16;
@@ -632,17 +645,8 @@ int launch_dw(const ConvArgs& a, hipStream_t s) {
     }
     return 0;
   }
-  const int YS = (a.OH + 3) / 4;
-  const long long total = (long long)a.N * YS * a.OW * (a.cin / 4);
-  const unsigned blocks = (unsigned)((total + 255) / 256);
-  const size_t smem = a.stats ? (size_t)2 * a.cin * sizeof(float) : 0;
-#define JN_DW(S_, T_)                                                                                              \
-  hipLaunchKernelGGL((dw3x3_kernel<S_, T_>), dim3(blocks), dim3(256), smem, s, (const T_*)a.in, a.in_ld, a.itab, a.w, \
-                     (T_*)a.out, a.out_ld, a.cin, a.H, a.W, a.OH, a.OW, a.N, a.stats, a.stats_rep_stride, a.skip_flag, \
-                     a.skip_when)
-  if (a.in_dtype == JN_BF16) { if (a.stride == 1) JN_DW(1, bf16_t); else JN_DW(2, bf16_t); }
-  else { if (a.stride == 1) JN_DW(1, float); else JN_DW(2, float); }
-#undef JN_DW
+  if (a.in_dtype == JN_BF16) { if (a.stride == 1) launch_dw_t<1, bf16_t>(a, s); else launch_dw_t<2, bf16_t>(a, s); }
+  else { if (a.stride == 1) launch_dw_t<1, float>(a, s); else launch_dw_t<2, float>(a, s); }
   return 0;
 }
 
@@ -950,40 +954,33 @@ __global__ __launch_bounds__(256) void pw_narrow_kernel(
 template <int CT, int KC>
 static void launch_pw_narrow_t(const ConvArgs& a, long long M, hipStream_t s) {
   constexpr int BM = (CT % 2 == 0) ? 64 : 128;
+  constexpr size_t smem = (size_t)(BM + 16 * CT) * (KC + PWN_PAD) * sizeof(float) + (BM / 32) * 32 * CT * sizeof(float);
   const long long n_tiles = (M + BM - 1) / BM;
   // persistent workgroups: whole resident rounds (what the occupancy API says fits, x 256 CUs).  Round 1 had swept a fixed
   // 1536; the kernel's registers have changed since (84 VGPRs at <2, 32>: five workgroups per CU, so 1536 was a round of 1280 and a
   // tail of 256) — forward 1.842 -> 1.822 ms per pass (tools/ab_fwd.sh, 1024 / 1280 / 1536 / 2048 / resident swept)
-  static int cap = 0;
-  if (!cap) {
-    int per_cu = 0;
-    const size_t sm = (size_t)(BM + 16 * CT) * (KC + PWN_PAD) * sizeof(float) + (BM / 32) * 32 * CT * sizeof(float);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&pw_narrow_kernel<CT, KC>), 256, sm) != hipSuccess || per_cu < 1) per_cu = 4;
-    cap = per_cu * 256;
-  }
-  const unsigned gx = (unsigned)std::min<long long>(n_tiles, cap);
+  const unsigned gx = (unsigned)std::min<long long>(n_tiles, resident_per_cu<&pw_narrow_kernel<CT, KC>>(smem, 4) * JN_NUM_CU);
   dim3 grid(gx, (unsigned)((a.cout + 16 * CT - 1) / (16 * CT)));
-  const size_t smem = (size_t)(BM + 16 * CT) * (KC + PWN_PAD) * sizeof(float) + (BM / 32) * 32 * CT * sizeof(float);
   hipLaunchKernelGGL((pw_narrow_kernel<CT, KC>), grid, dim3(256), smem, s, (const float*)a.in, a.in_ld, a.itab, a.w,
                      (float*)a.out, a.out_ld, M, a.cout, a.stats, a.stats_rep_stride, a.skip_flag, a.skip_when,
                      a.stats_nrep > 0 ? a.stats_nrep : JN_NREP);
 }
 
-// true when the persistent narrow kernel took the launch
-static bool launch_pw_narrow(const ConvArgs& a, hipStream_t s) {
-  if (a.bf16_mfma || a.in_dtype != JN_F32 || a.out_dtype != JN_F32 || a.w_transposed || a.accumulate || a.bias ||
-      a.act != ACT_NONE || a.n_slots > 1)
-    return false;
-  const long long M = (long long)a.N * a.H * a.W;
-  const int nt = (a.cout + 15) / 16;
-  // small maps have too few tiles to walk (JN_PWN_MIN_M: test hook, read per launch so that a test can force the kernel
-  // onto small maps)
-  const char* mm = std::getenv("JN_PWN_MIN_M");
-  if (M < (mm ? std::atoll(mm) : 65536)) return false;
-#define JN_PWN(CT_, KC_) if (nt == CT_ && a.cin == KC_) { launch_pw_narrow_t<CT_, KC_>(a, M, s); return true; }
-  JN_PWN(1, 16) JN_PWN(2, 16) JN_PWN(2, 32) JN_PWN(4, 32) JN_PWN(4, 64) JN_PWN(8, 64)
+// (channel tiles, K) the persistent narrow kernel is built for
+#define JN_PWN_TABLE JN_PWN(1, 16) JN_PWN(2, 16) JN_PWN(2, 32) JN_PWN(4, 32) JN_PWN(4, 64) JN_PWN(8, 64)
+static bool pw_narrow_shape(int nt, int cin) {
+#define JN_PWN(CT_, KC_) if (nt == CT_ && cin == KC_) return true;
+  JN_PWN_TABLE
 #undef JN_PWN
   return false;
+}
+
+static int launch_pw_narrow(const ConvArgs& a, hipStream_t s) {
+  const int nt = (a.cout + 15) / 16;
+#define JN_PWN(CT_, KC_) if (nt == CT_ && a.cin == KC_) { launch_pw_narrow_t<CT_, KC_>(a, (long long)a.N * a.H * a.W, s); return 0; }
+  JN_PWN_TABLE
+#undef JN_PWN
+  return -1;
 }
 
 template <int CT, int KC, bool WT, int WM, typename IT, typename OT, bool BF>
@@ -1019,11 +1016,10 @@ static void launch_pw_ct(const ConvArgs& a, long long M, hipStream_t s) {
   // (measured: 56x56 layers 50 -> 42 us, 112x112 60 -> 55 us against 128-pixel workgroups)
   constexpr bool can_split = (CT % 2 == 0), can_split4 = (CT % 4 == 0);
   const long long Mtot = M * (a.n_slots > 1 ? a.n_slots : 1);
-  const bool tiny_m = Mtot <= 16384;                  // 14x14 maps at 64 patches
+  const bool tiny_m = Mtot <= JN_PW_TINY_M;
   if (a.w_transposed) {              // data gradients (step-batched, large): 128-pixel workgroups unless the map is small
-    // (JN_PW_WT_SMALL_M: test hook, read per launch — 0 forces the large-map variant onto the small parity shapes)
     const char* sm_env = std::getenv("JN_PW_WT_SMALL_M");
-    if (can_split && Mtot <= (sm_env ? std::atoll(sm_env) : 65536)) launch_pw_cfg<CT, true, can_split ? 2 : 4, IT, OT, BF>(a, M, s);
+    if (can_split && Mtot <= (sm_env ? std::atoll(sm_env) : JN_PW_WT_SMALL_M)) launch_pw_cfg<CT, true, can_split ? 2 : 4, IT, OT, BF>(a, M, s);
     else launch_pw_cfg<CT, true, 4, IT, OT, BF>(a, M, s);
   } else {
     // 14x14 maps with K <= 128: 32-pixel workgroups (the four waves split the channel tiles) quadruple the
@@ -1044,45 +1040,59 @@ static void launch_pw_types(const ConvArgs& a, hipStream_t s) {
   else launch_pw_ct<8, IT, OT, BF>(a, M, s);
 }
 
-// Type combinations in use: fp32 mode (f32, f32, fp32 MFMA); bf16 mode: activations (bf16 -> bf16),
+// Type combinations of pw_mfma_kernel in use: fp32 mode (f32, f32, fp32 MFMA); bf16 mode: activations (bf16 -> bf16),
 // embed_fpn.0 (bf16 -> f32) and gradients (f32 -> f32), all on the bf16 MFMA.
-// Pixel-stationary kernel (kernels_pwxs.hip) for the forward 1x1 layers with K, N >= 64 on at most JN_XS_MAX_M pixels per
-// launch (the 56x56 / 28x28 / 14x14 maps of the headline batch: 10 - 30 % under the weight-stationary kernel on every one
-// of them, profiles/r03_pwxsbench.txt).
-constexpr long long JN_XS_MAX_M = 262144;
-static int launch_pw_small_maps(const ConvArgs& a, hipStream_t s) {
-  if ((long long)a.N * a.H * a.W > JN_XS_MAX_M) return -1;
-  if (pw_x1_supported(a)) return launch_pw_x1(a, s);      // bf16 inference mode
-  if (!pw_xs_supported(a)) return -1;
-  // fp32 operands as three bf16 planes on the bf16 matrix pipe where that is the faster kernel (a.w_x3 is null under
-  // JN_NO_PW_X3=1: fp32 pipe)
-  if (pw_x3_preferred(a) && launch_pw_x3(a, 0, s) == 0) return 0;
-  return launch_pw_xs(a, 0, s);
+static bool pw_mfma_types(const ConvArgs& a) {
+  return (a.in_dtype == JN_F32 && a.out_dtype == JN_F32) ||
+         (a.bf16_mfma && a.in_dtype == JN_BF16 && (a.out_dtype == JN_BF16 || a.out_dtype == JN_F32));
 }
 
-// The two layers whose output feeds a nearest x2 upsample (lateral_conv0 256 -> 128, reduce_conv1 128 -> 64) on the
-// small-map routes of the headline batch: their kernel can store the upsampled copy itself (a.up_out).  Mirrors the
-// route choice of launch_pw_small_maps; any other shape / route keeps the separate upsample launch.
-bool pw_fused_upsample_supported(const ConvArgs& a) {
-  if ((long long)a.N * a.H * a.W > JN_XS_MAX_M || !pw_xs_supported(a)) return false;
-  if (a.cin == 128 && a.cout == 64) return pw_x3_preferred(a);          // pw_x3_kernel<128, 1, 2, 4>
-  return a.cin == 256 && a.cout == 128;                                  // pw_x3_kernel<256, 2, 2, 2>; fp32 pipe: pw_xs_kernel<256, 2, 2, 4>
+static int launch_pw_mfma(const ConvArgs& a, hipStream_t s) {
+  if (!pw_mfma_types(a)) return -1;
+  if (a.in_dtype == JN_F32) { if (a.bf16_mfma) launch_pw_types<float, float, true>(a, s); else launch_pw_types<float, float, false>(a, s); }
+  else if (a.out_dtype == JN_BF16) launch_pw_types<bf16_t, bf16_t, true>(a, s);
+  else launch_pw_types<bf16_t, float, true>(a, s);
+  return 0;
+}
+
+// THE route of a 1x1 conv (jn_kernels.h): the clauses in their order of preference, each once.
+PwRoute pw_route(const ConvArgs& a) {
+  const long long M = (long long)a.N * a.H * a.W;
+  PwRoute r = PW_NONE;
+  if (M <= JN_XS_MAX_M) {
+    // fp32 operands as three bf16 planes on the bf16 matrix pipe wherever the planes are there in fragment order (a.w_x3 is
+    // null under JN_NO_PW_X3=1: fp32 pipe)
+    if (pw_x1_supported(a)) r = PW_X1;
+    else if (pw_xs_supported(a)) r = a.w_x3 && pw_x3_fragment_order(a.cin, a.cout) ? PW_X3 : PW_XS;
+  }
+  if (a.up_out) return pw_fuses_upsample(r, a.cin, a.cout) ? r : PW_NONE;
+  if (r != PW_NONE) return r;
+  // The production route of wide layers (forward and data gradient): barrier-free, weight-stationary, exact-fp32 MFMA.  Its
+  // split-bf16 form (round 2, removed after commit 60f1026) measured 2.07 against 2.15 ms per forward pass and 117.0 against
+  // 118.1 ms per iteration (these kernels are latency-, not matrix-bound), but a rounding noise ~10x that of an fp32 fma
+  // chain per layer, which the 77 train-mode BatchNorms amplify to 1.0 - 1.5e-3 on the first layers' gradients — not worth
+  // 1 %; for the data gradients alone (linear in g: no amplification) 3.30 -> 3.27 ms per step, not taken.
+  if (pw_res_supported(a) && a.cin % 64 == 0 && pw_dir_auto_ctw(a.cin, a.cout) &&
+      !(a.cin == 64 && a.cout == 64 && M * (a.n_slots > 1 ? a.n_slots : 1) < JN_PW_BIG_M))
+    return PW_WIDE;
+  if (pw_f32_plain(a) && pw_narrow_shape((a.cout + 15) / 16, a.cin)) {      // (small maps have too few tiles to walk)
+    const char* mm = std::getenv("JN_PWN_MIN_M");
+    if (M >= (mm ? std::atoll(mm) : JN_PW_BIG_M)) return PW_NARROW;
+  }
+  return pw_mfma_types(a) ? PW_MFMA : PW_NONE;
 }
 
 int launch_pw(const ConvArgs& a, hipStream_t s) {
-  if (launch_pw_small_maps(a, s) == 0) return 0;           // small maps, forward: pixel-stationary kernel (kernels_pwxs.hip)
-  if (a.up_out) return -1;                                 // (the caller asked pw_fused_upsample_supported first)
-  if (launch_pw_wide(a, s) == 0) return 0;                // K, N >= 64: weight-stationary kernel (kernels_pwres.hip)
-  if (launch_pw_narrow(a, s)) return 0;
-  if (!a.bf16_mfma) {
-    if (a.in_dtype == JN_F32 && a.out_dtype == JN_F32) { launch_pw_types<float, float, false>(a, s); return 0; }
-    return -1;
+  switch (pw_route(a)) {
+    case PW_X1: return launch_pw_x1(a, s);
+    case PW_X3: return launch_pw_x3(a, 0, s);
+    case PW_XS: return launch_pw_xs(a, 0, s);
+    case PW_WIDE: return launch_pw_dir(a, 0, s);
+    case PW_NARROW: return launch_pw_narrow(a, s);
+    case PW_MFMA: return launch_pw_mfma(a, s);
+    case PW_NONE: break;
   }
-  if (a.in_dtype == JN_BF16 && a.out_dtype == JN_BF16) launch_pw_types<bf16_t, bf16_t, true>(a, s);
-  else if (a.in_dtype == JN_BF16 && a.out_dtype == JN_F32) launch_pw_types<bf16_t, float, true>(a, s);
-  else if (a.in_dtype == JN_F32 && a.out_dtype == JN_F32) launch_pw_types<float, float, true>(a, s);
-  else return -1;
-  return 0;
+  return -1;
 }
 
 // ------------------------------------------------------------------------------------

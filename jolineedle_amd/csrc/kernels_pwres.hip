@@ -201,21 +201,17 @@ static size_t pw_dir_lds(int ctw, int K) {
 }
 
 template <int CTW, bool WT, int PF = 2, bool ST = true, bool TF = true>
-static void launch_pw_dir_t(const ConvArgs& a, long long M, hipStream_t s) {
+static int launch_pw_dir_t(const ConvArgs& a, long long M, hipStream_t s) {
   const int K = a.cin;
   const size_t smem = pw_dir_lds(CTW, K);
-  auto kern = pw_dir_kernel<CTW, WT, PF, ST, TF>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  constexpr auto kern = &pw_dir_kernel<CTW, WT, PF, ST, TF>;
+  if (!allow_lds<kern>(smem)) return -1;
   const long long n_tiles = (M + 15) / 16;
   const int ny = (a.cout + 16 * CTW - 1) / (16 * CTW), nz = a.n_slots > 1 ? a.n_slots : 1;
   const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / smem));
   // one resident round: as many workgroups as the chip holds at once, never a few more (20 steps x 4 slices with the
   // old round-up-to-8 rule gave 640 workgroups for 512 places: a second round at a quarter of the occupancy)
-  long long gx = std::max<long long>(1, 256LL * per_cu / ((long long)ny * nz));
+  long long gx = std::max<long long>(1, (long long)JN_NUM_CU * per_cu / ((long long)ny * nz));
   if (nz == 1 && ny > 1) gx = std::max<long long>(8, gx / 8 * 8);
   gx = std::min<long long>(gx, (n_tiles + 3) / 4);
   dim3 grid((unsigned)gx, (unsigned)ny, (unsigned)nz);
@@ -223,24 +219,23 @@ static void launch_pw_dir_t(const ConvArgs& a, long long M, hipStream_t s) {
                      (float*)a.out, a.out_ld, M, K, a.cout, a.accumulate, a.stats, a.stats_rep_stride,
                      a.stats_nrep > 0 ? a.stats_nrep : JN_NREP, a.skip_flag, a.skip_when, a.in_slot_stride, a.out_slot_stride,
                      a.tab_slot_stride);
+  return 0;
 }
 
-// ctw = channel tiles per workgroup slice (0: automatic — the widest slice <= 128 channels whose weights leave room for two
-// workgroups per CU); returns -1 when the shape does not fit (K % 64, slice too large).
+// The automatic slice: 64-channel slices measured best on every shape of the nano PAFPN (round 2: 28x28 128 -> 128 28.4 us
+// against 29.3 with 128-channel and 32.1 with 32-channel slices); narrower only where the weights would not leave room for
+// two workgroups per CU (K = 512); 0: no slice does
+int pw_dir_auto_ctw(int K, int N) {
+  for (int c : {4, 2})
+    if ((16 * c <= N || c <= 2) && pw_dir_lds(c, K) <= 78 * 1024) return c;
+  return 0;
+}
+
+// ctw = channel tiles per workgroup slice (0: automatic); returns -1 when the shape does not fit (K % 64, slice too large).
 int launch_pw_dir(const ConvArgs& a, int ctw, hipStream_t s) {
   const long long M = (long long)a.N * a.H * a.W;
-  const int K = a.cin, N = a.cout;
-  if (K % 64 != 0) return -1;
-  if (!ctw) {
-    // 64-channel slices measured best on every shape of the nano PAFPN (round 2: 28x28 128 -> 128 28.4 us
-    // against 29.3 with 128-channel and 32.1 with 32-channel slices); narrower only where the weights would not leave
-    // room for two workgroups per CU (K = 512)
-    for (int c : {4, 2}) {
-      if (16 * c > N && c > 2) continue;
-      if (pw_dir_lds(c, K) <= 78 * 1024) { ctw = c; break; }
-    }
-    if (!ctw) return -1;
-  }
+  const int K = a.cin;
+  if (K % 64 != 0 || (!ctw && !(ctw = pw_dir_auto_ctw(K, a.cout)))) return -1;
   if (pw_dir_lds(ctw, K) > 160 * 1024) return -1;
   const bool wt = a.w_transposed != 0;
   // data gradients (transposed weights) collect no statistics: without the two sum registers per tile a third step of
@@ -248,18 +243,10 @@ int launch_pw_dir(const ConvArgs& a, int ctw, hipStream_t s) {
   if (wt && !a.stats && (ctw == 4 || ctw == 2)) {
     // (gradient views carry the identity table: the transform — two transcendentals and half a dozen VALU ops per value,
     //  as long as the MFMAs of the step, round 2 — is compiled out)
-    if (a.in_identity) {
-      if (ctw == 4) launch_pw_dir_t<4, true, 4, false, false>(a, M, s); else launch_pw_dir_t<2, true, 4, false, false>(a, M, s);
-    } else {
-      if (ctw == 4) launch_pw_dir_t<4, true, 4, false>(a, M, s); else launch_pw_dir_t<2, true, 4, false>(a, M, s);
-    }
-    return 0;
+    if (a.in_identity) return ctw == 4 ? launch_pw_dir_t<4, true, 4, false, false>(a, M, s) : launch_pw_dir_t<2, true, 4, false, false>(a, M, s);
+    return ctw == 4 ? launch_pw_dir_t<4, true, 4, false>(a, M, s) : launch_pw_dir_t<2, true, 4, false>(a, M, s);
   }
-#define JN_PD(C_)                                                                                   \
-  if (ctw == C_) {                                                                                  \
-    if (wt) launch_pw_dir_t<C_, true>(a, M, s); else launch_pw_dir_t<C_, false>(a, M, s);          \
-    return 0;                                                                                       \
-  }
+#define JN_PD(C_) if (ctw == C_) return wt ? launch_pw_dir_t<C_, true>(a, M, s) : launch_pw_dir_t<C_, false>(a, M, s);
   JN_PD(8) JN_PD(4) JN_PD(2)
 #undef JN_PD
   return -1;
@@ -267,27 +254,9 @@ int launch_pw_dir(const ConvArgs& a, int ctw, hipStream_t s) {
 
 // Shapes the resident-weight kernel takes (everything else stays with pw_mfma_kernel / pw_narrow_kernel): fp32, no
 // bias / activation epilogue, K a multiple of 64 (32 for K = 32 * odd), at least 64 input and output channels.
-bool pw_res_supported(const ConvArgs& a) {
-  if (a.bf16_mfma || a.in_dtype != JN_F32 || a.out_dtype != JN_F32 || a.bias || a.act != ACT_NONE) return false;
-  if (a.cin < 64 || a.cout < 64 || a.cin % 32 != 0 || a.cout % 4 != 0 || a.cin > 1024) return false;
-  return true;
-}
-
 // (name kept from round 2: the shape test of the resident-weight kernels)
-// The production route for wide 1x1 layers (forward and data gradient): the barrier-free weight-stationary kernel on
-// exact-fp32 MFMA.  Its split-bf16 form (round 2, removed after commit 60f1026) measured 2.07 against 2.15 ms per forward
-// pass and 117.0 against 118.1 ms per iteration (these kernels are latency-, not matrix-bound), but a rounding noise ~10x
-// that of an fp32 fma chain per layer, which the 77 train-mode BatchNorms amplify to 1.0 - 1.5e-3 on the first layers'
-// gradients — not worth 1 %.  Shapes the kernel measured no better on stay with their old kernels: 64 -> 64 on fewer
-// than 65536 pixels (pw_mfma_kernel, 14.3 against 14.6 us at 28x28).
-int launch_pw_wide(const ConvArgs& a, hipStream_t s) {
-  if (!pw_res_supported(a) || a.cin % 64 != 0) return -1;
-  const long long M = (long long)a.N * a.H * a.W * (a.n_slots > 1 ? a.n_slots : 1);
-  if (a.cin == 64 && a.cout == 64 && M < 65536) return -1;
-  // (split products for the data gradients only — the backward is linear in g, so a GEMM error of ~5e-6 travels up the
-  //  chain without the amplification a forward perturbation gets — were measured in round 2: 3.30 -> 3.27 ms per step,
-  //  not taken)
-  return launch_pw_dir(a, 0, s);
+bool pw_res_supported(const ConvArgs& a) {
+  return pw_f32_bare(a) && a.cin >= 64 && a.cout >= 64 && a.cin % 32 == 0 && a.cout % 4 == 0 && a.cin <= 1024;
 }
 
 }  // namespace jnr

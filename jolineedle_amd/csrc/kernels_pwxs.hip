@@ -197,41 +197,44 @@ __global__ __launch_bounds__(256, (K <= 64 ? 3 : (K <= 128 || (K == 256 && CTW <
   }
 }
 
-template <int K, int CTW, int PT, int D, bool UPS = false>
-static void launch_pw_xs_t(const ConvArgs& a, long long M, int wg_per_cu, hipStream_t s) {
-  constexpr int BM = 16 * PT;
-  const size_t smem = ((size_t)BM * (K + 8) + 3 * K) * sizeof(float);
-  auto kern = pw_xs_kernel<K, CTW, PT, D, UPS>;
-  static int places = 0;
-  if (!places) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 256, smem) != hipSuccess || per_cu < 1) per_cu = 1;
-    places = per_cu;
-  }
-  // persistent grid: at most `wg_per_cu` (<= what fits) workgroups per CU, so that every workgroup is resident from the
-  // start and walks over its tiles with the next operand in flight
-  const long long n_tiles = (M + BM - 1) / BM;
-  const int per_cu = std::max(1, std::min(places, wg_per_cu > 0 ? wg_per_cu : 2));
-  const long long gx = std::min<long long>(n_tiles, 256LL * per_cu);
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(256), smem, s, (const float*)a.in, a.in_ld, a.itab, a.w, (float*)a.out,
-                     a.out_ld, M, a.stats, a.stats_rep_stride, a.stats_nrep > 0 ? a.stats_nrep : JN_NREP, a.skip_flag,
-                     a.skip_when, UpsDst{(float*)a.up_out, a.up_ld, a.W, a.H * a.W});
+// persistent grid of the pixel-stationary kernels: at most `wg_per_cu` (<= what fits, default 2) workgroups per CU, so that
+// every workgroup is resident from the start and walks over its tiles with the next operand in flight
+static unsigned pw_xs_grid(long long n_tiles, int fit_per_cu, int wg_per_cu) {
+  const int per_cu = std::max(1, std::min(fit_per_cu, wg_per_cu > 0 ? wg_per_cu : 2));
+  return (unsigned)std::min<long long>(n_tiles, (long long)JN_NUM_CU * per_cu);
 }
 
-// Shapes the kernel takes: fp32 forward (no bias / activation epilogue, weight [N][K] not transposed, one slot),
-// K in {64, 128, 256, 512}, N in {64, 128, 256}.  pt = pixel tiles per workgroup (2 or 4; 0 = the measured best for the
-// shape, tools/pwxsbench.hip).  Returns -1 when the shape is not covered.
-bool pw_xs_supported(const ConvArgs& a) {
-  if (a.bf16_mfma || a.in_dtype != JN_F32 || a.out_dtype != JN_F32 || a.bias || a.act != ACT_NONE || a.w_transposed ||
-      a.accumulate || a.n_slots > 1)
-    return false;
-  const int K = a.cin, N = a.cout;
+template <int K, int CTW, int PT, int D, bool UPS = false>
+static int launch_pw_xs_t(const ConvArgs& a, long long M, int wg_per_cu, hipStream_t s) {
+  constexpr int BM = 16 * PT;
+  constexpr size_t smem = ((size_t)BM * (K + 8) + 3 * K) * sizeof(float);
+  constexpr auto kern = &pw_xs_kernel<K, CTW, PT, D, UPS>;
+  if (!allow_lds<kern>(smem)) return -1;
+  const unsigned gx = pw_xs_grid((M + BM - 1) / BM, resident_per_cu<kern>(smem, 1), wg_per_cu);
+  hipLaunchKernelGGL(kern, dim3(gx), dim3(256), smem, s, (const float*)a.in, a.in_ld, a.itab, a.w, (float*)a.out,
+                     a.out_ld, M, a.stats, a.stats_rep_stride, a.stats_nrep > 0 ? a.stats_nrep : JN_NREP, a.skip_flag,
+                     a.skip_when, UpsDst{(float*)a.up_out, a.up_ld, a.W, a.H * a.W});
+  return 0;
+}
+
+// THE shape list of the pixel-stationary kernels (pw_xs, pw_x3 and its single-plane bf16 form): K in {64, 128, 256, 512},
+// N in {64, 128, 256}
+static bool pw_xs_shape(int K, int N) {
   if (!(K == 64 || K == 128 || K == 256 || K == 512) || !(N == 64 || N == 128 || N == 256)) return false;
-  if (K == 64 && N == 256) return false;
-  if (K == 512 && N != 256) return false;
-  if (K == 256 && N == 64) return false;
-  return a.in_ld % 4 == 0 && a.out_ld % 4 == 0;
+  return !(K == 64 && N == 256) && !(K == 512 && N != 256) && !(K == 256 && N == 64);
+}
+
+// Layers the kernel takes: plain fp32 forward, a shape of the list.  pt = pixel tiles per workgroup (2 or 4; 0 = the measured
+// best for the shape, tools/pwxsbench.hip).  Returns -1 when the shape is not covered.
+bool pw_xs_supported(const ConvArgs& a) {
+  return pw_f32_plain(a) && pw_xs_shape(a.cin, a.cout) && a.in_ld % 4 == 0 && a.out_ld % 4 == 0;
+}
+
+// The layers whose output feeds a nearest x2 upsample (lateral_conv0 256 -> 128, reduce_conv1 128 -> 64) on the small-map
+// routes of the headline batch: the UPS instantiations below — pw_x3_kernel<128, 1, 2, 4> and <256, 2, 2, 2>, on the fp32
+// pipe pw_xs_kernel<256, 2, 2, 4>.  Any other route / shape keeps the separate upsample launch.
+bool pw_fuses_upsample(PwRoute r, int cin, int cout) {
+  return (r == PW_X3 && cin == 128 && cout == 64) || ((r == PW_X3 || r == PW_XS) && cin == 256 && cout == 128);
 }
 
 int launch_pw_xs(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu) {
@@ -245,16 +248,10 @@ int launch_pw_xs(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu) {
     pt = big ? 4 : 2;
     if (wg_per_cu == 0) wg_per_cu = big ? 1 : 2;
   }
-  if (a.up_out) {                       // fused x2 upsample of the output: the one shape that needs it on this route
-    if (!(K == 256 && ctw == 2 && pt == 2)) return -1;
-    launch_pw_xs_t<256, 2, 2, 4, true>(a, M, wg_per_cu, s);
-    return 0;
-  }
-#define JN_XS(K_, C_, D_)                                                          \
-  if (K == K_ && ctw == C_) {                                                      \
-    if (pt == 4) launch_pw_xs_t<K_, C_, 4, D_>(a, M, wg_per_cu, s); else launch_pw_xs_t<K_, C_, 2, D_>(a, M, wg_per_cu, s); \
-    return 0;                                                                      \
-  }
+  if (a.up_out)                         // fused x2 upsample of the output
+    return pw_fuses_upsample(PW_XS, K, a.cout) && pt == 2 ? launch_pw_xs_t<256, 2, 2, 4, true>(a, M, wg_per_cu, s) : -1;
+#define JN_XS(K_, C_, D_) \
+  if (K == K_ && ctw == C_) return pt == 4 ? launch_pw_xs_t<K_, C_, 4, D_>(a, M, wg_per_cu, s) : launch_pw_xs_t<K_, C_, 2, D_>(a, M, wg_per_cu, s);
   // D: k-steps of weight fragments in flight per wave — a step is 4 * PT * CTW MFMAs (32 cycles each), an L2 round trip
   // about 1500 cycles: the narrower the wave's channel slice, the deeper the ring; D = K / 16 (K <= 128 with at most two
   // channel tiles per wave): every fragment is fetched up front, no loads inside the matrix loop
@@ -265,7 +262,6 @@ int launch_pw_xs(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu) {
 #undef JN_XS
   return -1;
 }
-
 
 // ---- the same kernel on the bf16 matrix pipe at fp32 accuracy: "x3" -------------------------------------------------
 // gfx950 has no reduced-precision fast path for fp32 operands: v_mfma_f32_16x16x4_f32 runs at 1/16 of the bf16 rate, and
@@ -506,43 +502,22 @@ __global__ __launch_bounds__(256, (K <= 64 ? 3 : CTW <= 2 ? 2 : 1)) void pw_x3_k
 }
 
 template <int K, int CTW, int PT, int D, int NP, typename XT, bool UPS = false, bool SLOTS = false, bool FRAG = SLOTS>
-static void launch_pw_x3_t(const ConvArgs& a, long long M, int wg_per_cu, hipStream_t s) {
+static int launch_pw_x3_t(const ConvArgs& a, long long M, int wg_per_cu, hipStream_t s) {
   constexpr int BM = 16 * PT;
-  const size_t smem = (size_t)NP * BM * (K + 16) * sizeof(bf16_t) + 3 * K * sizeof(float);
-  auto kern = pw_x3_kernel<K, CTW, PT, D, NP, XT, UPS, SLOTS, FRAG>;
-  static int places = 0;
-  if (!places) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 256, smem) != hipSuccess || per_cu < 1) per_cu = 1;
-    places = per_cu;
-  }
+  constexpr size_t smem = (size_t)NP * BM * (K + 16) * sizeof(bf16_t) + 3 * K * sizeof(float);
+  constexpr auto kern = &pw_x3_kernel<K, CTW, PT, D, NP, XT, UPS, SLOTS, FRAG>;
+  if (!allow_lds<kern>(smem)) return -1;
   const int n_slots = SLOTS ? std::max(1, a.n_slots) : 1;
-  const long long n_tiles = (M + BM - 1) / BM * n_slots;
-  const int per_cu = std::max(1, std::min(places, wg_per_cu > 0 ? wg_per_cu : 2));
-  const long long gx = std::min<long long>(n_tiles, 256LL * per_cu);
-  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(256), smem, s, (const XT*)a.in, a.in_ld, a.itab, (const bf16_t*)a.w_x3,
+  const unsigned gx = pw_xs_grid((M + BM - 1) / BM * n_slots, resident_per_cu<kern>(smem, 1), wg_per_cu);
+  hipLaunchKernelGGL(kern, dim3(gx), dim3(256), smem, s, (const XT*)a.in, a.in_ld, a.itab, (const bf16_t*)a.w_x3,
                      (XT*)a.out, a.out_ld, M, a.stats, a.stats_rep_stride, a.stats_nrep > 0 ? a.stats_nrep : JN_NREP,
                      a.skip_flag, a.skip_when, UpsDst{(float*)a.up_out, a.up_ld, a.W, a.H * a.W},
                      SlotSpan{n_slots, a.in_slot_stride, a.out_slot_stride});
+  return 0;
 }
 
-// Shapes the x3 kernel is built for — the ones where it beats pw_xs_kernel (tools/pwxsbench.hip).  With the planes in flat
-// order that was K <= 128 with N <= 128 (profiles/r03_x3bench.txt: 8 - 21 %) and 256 -> 256 on 64-pixel tiles: wider, the
-// weight fragments are streamed per tile and their scattered 16-byte pieces cost more than the matrix cycles saved.  In
-// fragment order it is every shape of the pixel-stationary kernel (profiles/pwfrag_bench.txt: 14 - 29 % under pw_xs_kernel
-// at K >= 128, 9 - 41 % under the flat order; K = 64: 4 - 9 % under the flat order).
-static bool pw_xs_shape(int K, int N) {
-  if (!(K == 64 || K == 128 || K == 256 || K == 512) || !(N == 64 || N == 128 || N == 256)) return false;
-  return !(K == 64 && N == 256) && !(K == 512 && N != 256) && !(K == 256 && N == 64);
-}
-
-bool pw_x3_preferred(const ConvArgs& a) {
-  if (!a.w_x3 || !pw_xs_supported(a)) return false;
-  return pw_x3_fragment_order(a.cin, a.cout);
-}
-
-// bf16 inference mode (bf16 activations in and out, bf16 MFMA): the single-plane form of the kernel, every xs shape
+// bf16 inference mode (bf16 activations in and out, bf16 MFMA; the bf16 twin of pw_f32_plain): the single-plane form of
+// the kernel, every xs shape
 bool pw_x1_supported(const ConvArgs& a) {
   return a.w_x3 && a.bf16_mfma && a.in_dtype == JN_BF16 && a.out_dtype == JN_BF16 && !a.bias && a.act == ACT_NONE && !a.w_transposed &&
          !a.accumulate && a.n_slots <= 1 && pw_xs_shape(a.cin, a.cout) && a.in_ld % 4 == 0 && a.out_ld % 4 == 0;
@@ -554,13 +529,19 @@ int launch_pw_x1(const ConvArgs& a, hipStream_t s) {
   const int K = a.cin, ctw = a.cout / 64;
   const int wg = (K == 512 || ctw == 4) ? 1 : 2;
 #define JN_X1(K_, C_, P_, D_) \
-  if (K == K_ && ctw == C_) { launch_pw_x3_t<K_, C_, P_, D_, 1, bf16_t, false, false, pw_x3_fragment_order(K_, 64 * C_)>(a, M, wg, s); return 0; }
+  if (K == K_ && ctw == C_) return launch_pw_x3_t<K_, C_, P_, D_, 1, bf16_t, false, false, pw_x3_fragment_order(K_, 64 * C_)>(a, M, wg, s);
   JN_X1(64, 1, 2, 2) JN_X1(64, 2, 2, 2) JN_X1(128, 1, 2, 4) JN_X1(128, 2, 2, 4) JN_X1(128, 4, 2, 4)
   JN_X1(256, 2, 4, 2) JN_X1(256, 4, 4, 2) JN_X1(512, 4, 4, 2)
 #undef JN_X1
   return -1;
 }
 
+// Shapes the x3 kernel is built for — the ones where it beats pw_xs_kernel (tools/pwxsbench.hip).  With the planes in flat
+// order that was K <= 128 with N <= 128 (profiles/r03_x3bench.txt: 8 - 21 %) and 256 -> 256 on 64-pixel tiles: wider, the
+// weight fragments are streamed per tile and their scattered 16-byte pieces cost more than the matrix cycles saved.  In
+// fragment order it is every shape of the pixel-stationary kernel (profiles/pwfrag_bench.txt: 14 - 29 % under pw_xs_kernel
+// at K >= 128, 9 - 41 % under the flat order; K = 64: 4 - 9 % under the flat order): pw_route takes it wherever the planes
+// of the layer are in fragment order.
 int launch_pw_x3(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu, int frag) {
   if (!pw_xs_supported(a) || !a.w_x3) return -1;
   const long long M = (long long)a.N * a.H * a.W;
@@ -573,27 +554,22 @@ int launch_pw_x3(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu, int fr
     // per CU (in fragment order the 32-pixel tiles tie with them: 22.8 / 23.0 us)
     const bool sq256 = K == 256 && ctw == 4;
     pt = sq256 ? 4 : 2;
-    if (wg_per_cu == 0) wg_per_cu = (sq256 || (K == 64 && ctw == 2) || (K == 128 && ctw == 2 && M <= 16384)) ? 1 : 2;
+    if (wg_per_cu == 0) wg_per_cu = (sq256 || (K == 64 && ctw == 2) || (K == 128 && ctw == 2 && M <= JN_PW_TINY_M)) ? 1 : 2;
   }
-  if (a.up_out) {                       // fused x2 upsample of the output: the two shapes that need it (reduce_conv1, lateral_conv0)
-    if (pt != 2 || frag != rule) return -1;
-    if (K == 128 && ctw == 1) { launch_pw_x3_t<128, 1, 2, 4, 3, float, true, false, pw_x3_fragment_order(128, 64)>(a, M, wg_per_cu, s); return 0; }
-    if (K == 256 && ctw == 2) { launch_pw_x3_t<256, 2, 2, 2, 3, float, true, false, pw_x3_fragment_order(256, 128)>(a, M, wg_per_cu, s); return 0; }
-    return -1;
+  if (a.up_out) {                       // fused x2 upsample of the output (reduce_conv1, lateral_conv0)
+    if (pt != 2 || frag != rule || !pw_fuses_upsample(PW_X3, K, a.cout)) return -1;
+    if (K == 128) return launch_pw_x3_t<128, 1, 2, 4, 3, float, true, false, pw_x3_fragment_order(128, 64)>(a, M, wg_per_cu, s);
+    return launch_pw_x3_t<256, 2, 2, 2, 3, float, true, false, pw_x3_fragment_order(256, 128)>(a, M, wg_per_cu, s);
   }
 #ifdef JN_X3_ALL_SHAPES        // tools/pwxsbench.hip: every shape and tile size in both weight orders, to show where each loses
-#define JN_X3(K_, C_, P_, D_)                                                                   \
-  if (K == K_ && ctw == C_ && pt == P_) {                                                       \
-    if (frag) launch_pw_x3_t<K_, C_, P_, D_, 3, float, false, false, true>(a, M, wg_per_cu, s);  \
-    else launch_pw_x3_t<K_, C_, P_, D_, 3, float, false, false, false>(a, M, wg_per_cu, s);      \
-    return 0;                                                                                   \
-  }
+#define JN_X3(K_, C_, P_, D_)                                                                              \
+  if (K == K_ && ctw == C_ && pt == P_)                                                                    \
+    return frag ? launch_pw_x3_t<K_, C_, P_, D_, 3, float, false, false, true>(a, M, wg_per_cu, s)          \
+                : launch_pw_x3_t<K_, C_, P_, D_, 3, float, false, false, false>(a, M, wg_per_cu, s);
 #else
-#define JN_X3(K_, C_, P_, D_)                                                                                           \
-  if (K == K_ && ctw == C_ && pt == P_ && frag == rule) {                                                               \
-    launch_pw_x3_t<K_, C_, P_, D_, 3, float, false, false, pw_x3_fragment_order(K_, 64 * C_)>(a, M, wg_per_cu, s);       \
-    return 0;                                                                                                           \
-  }
+#define JN_X3(K_, C_, P_, D_)                             \
+  if (K == K_ && ctw == C_ && pt == P_ && frag == rule) \
+    return launch_pw_x3_t<K_, C_, P_, D_, 3, float, false, false, pw_x3_fragment_order(K_, 64 * C_)>(a, M, wg_per_cu, s);
 #endif
   JN_X3(64, 1, 2, 2) JN_X3(64, 2, 2, 2) JN_X3(128, 1, 2, 4) JN_X3(128, 2, 2, 4) JN_X3(128, 4, 2, 2)
   JN_X3(256, 2, 2, 2) JN_X3(256, 4, 4, 2) JN_X3(512, 4, 2, 2)
@@ -641,8 +617,7 @@ bool pw_x3_bwd_data_supported(int cout, int cin) {
 // cout = layer's cin, slots); w = the layer's [cout][cin] weight, w3t = 3 * cout * cin bf16 of scratch owned by the layer
 int launch_pw_x3_bwd_data(const ConvArgs& a, const float* w, void* w3t, hipStream_t s) {
   const int K = a.cin, N = a.cout;                      // of the gradient conv
-  if (!pw_x3_bwd_data_supported(K, N) || a.accumulate || a.in_dtype != JN_F32 || a.out_dtype != JN_F32 || a.bias ||
-      a.act != ACT_NONE || a.in_ld % 4 != 0 || a.out_ld % 4 != 0 || a.stats)
+  if (!pw_x3_bwd_data_supported(K, N) || !pw_f32_bare(a) || a.accumulate || a.in_ld % 4 != 0 || a.out_ld % 4 != 0 || a.stats)
     return -1;
   launch_w_split3_t(w, w3t, K, N, s);
   const long long M = (long long)a.N * a.H * a.W;
@@ -650,12 +625,12 @@ int launch_pw_x3_bwd_data(const ConvArgs& a, const float* w, void* w3t, hipStrea
   b.w_x3 = w3t; b.up_out = nullptr;
   // tilings: the best of tools/x3bwdbench.hip (profiles/r04_x3bwdbench.txt) — 32-pixel tiles everywhere (more tiles to
   // balance over the persistent grid), K = 128: all weight fragments in registers (D = K / 32)
-  if (K == 256 && N == 128) { launch_pw_x3_t<256, 2, 2, 2, 3, float, false, true>(b, M, 2, s); return 0; }
-  if (K == 128 && N == 256) { launch_pw_x3_t<128, 4, 2, 4, 3, float, false, true>(b, M, 2, s); return 0; }
+  if (K == 256 && N == 128) return launch_pw_x3_t<256, 2, 2, 2, 3, float, false, true>(b, M, 2, s);
+  if (K == 128 && N == 256) return launch_pw_x3_t<128, 4, 2, 4, 3, float, false, true>(b, M, 2, s);
   for (int n0 = 0; n0 < N; n0 += 256) {                 // 256 -> 256, and 256 -> 512 as two column halves
     b.w_x3 = (const bf16_t*)w3t + (long long)n0 * K * 3;
     b.out = (float*)a.out + n0;
-    launch_pw_x3_t<256, 4, 2, 2, 3, float, false, true>(b, M, 2, s);
+    if (launch_pw_x3_t<256, 4, 2, 2, 3, float, false, true>(b, M, 2, s)) return -1;
   }
   return 0;
 }

@@ -518,7 +518,7 @@ bool defer_eligible(const Net& net) {
 
 // One forward pass of `net` over N patches as a pure function of its topology, activation dtype and the pass (train,
 // with_head, the first op, whether it defers): one record per op of [first_op, n_ops), in launch order.  What depends
-// on launch-time state (pw_fused_upsample_supported, JN_NO_PW_X3, the stream) stays with the launcher (run_net, api_net.hip).
+// on launch-time state (pw_route for the fused upsample, JN_NO_PW_X3, the stream) stays with the launcher (run_net, api_net.hip).
 int plan_forward(const Net& net, int N, bool train, bool with_head, int first_op, bool defer, std::vector<FwdStep>& plan) {
   const int n = (with_head || net.n_backbone_ops < 0) ? (int)net.ops.size() : net.n_backbone_ops;
   const bool f32 = net.act_dtype == JN_F32;

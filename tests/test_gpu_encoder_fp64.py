@@ -25,7 +25,7 @@ pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 
 JN_DEFER_MAX_M = 65536          # jn_kernels.h
-JN_XS_MAX_M = 262144            # kernels_conv.hip
+JN_XS_MAX_M = 262144            # jn_kernels.h
 TINY_M = 16384                  # kernels_conv.hip: tiny_m
 SMALL_M = 65536                 # kernels_conv.hip: pw_narrow minimum / JN_PW_WT_SMALL_M default
 
