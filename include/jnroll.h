@@ -76,6 +76,9 @@ typedef struct jn_config {
   int32_t max_det_per_patch;    /* cap of kept boxes per patch (ragged output rows)     */
   int32_t act_dtype;            /* activation storage: 0 = fp32 (the reference's dtype, exact-fp32 MFMA),
                                  * 1 = bf16 (bf16 storage + bf16 MFMA, fp32 accumulate / statistics / weights) */
+  int32_t gpt_wide;             /* 1: take the wide decision route for every model it admits (n_embd 64, 128, 192, 256
+                                 * as well; a test and A/B switch, the Python layer sets it from JN_GPT_WIDE=1).  Ignored
+                                 * for the shapes that route refuses; n_embd above 256 takes the route whatever is set */
 } jn_config;
 
 /* One state-dict entry (names of SURVEY.md §5, e.g. "gpt_backbone.backbone.stem.conv.bn.weight"). */
@@ -134,6 +137,10 @@ int jn_param_info_at(const jn_ctx* ctx, int index, jn_param_info* out);
  * the layer's BatchNorm table is left to its consumers in this pass. */
 int jn_debug_forward_plan(const jn_ctx* ctx, int net, int N, int train, int with_head, int first_op, int32_t* out,
                           int cap);
+/* Debugging aid, no device needed: the route the context's decision steps take.  0: one workgroup per agent
+ * (n_embd <= 256); 1: the wide route, every Linear one GEMM over all agents (256 < n_embd <= 1024, a multiple of 64;
+ * with jn_config.gpt_wide also n_embd 64, 128, 192, 256). */
+int jn_debug_decision_route(const jn_ctx* ctx);
 /* Uploads and pre-packs (BN folded for eval, Linear weights transposed).  Entries the
  * path does not use are ignored; a missing used entry -> JN_ENOTFOUND.  Synchronises. */
 int jn_load_weights(jn_ctx* ctx, const jn_tensor* tensors, size_t n);

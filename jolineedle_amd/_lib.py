@@ -32,7 +32,7 @@ class JnConfig(C.Structure):
                 ("with_detector", C.c_int32), ("det_depth", C.c_float), ("det_width", C.c_float),
                 ("det_depthwise", C.c_int32), ("det_conf_threshold", C.c_float),
                 ("det_nms_threshold", C.c_float), ("max_batch", C.c_int32), ("max_det_per_patch", C.c_int32),
-                ("act_dtype", C.c_int32)]
+                ("act_dtype", C.c_int32), ("gpt_wide", C.c_int32)]
 
 
 class JnTensor(C.Structure):
@@ -73,6 +73,7 @@ SIGNATURES = {
     "jn_param_count": (C.c_int, [C.c_void_p]),
     "jn_param_info_at": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(JnParamInfo)]),
     "jn_debug_forward_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int]),
+    "jn_debug_decision_route": (C.c_int, [C.c_void_p]),
     "jn_load_weights": (C.c_int, [C.c_void_p, C.POINTER(JnTensor), C.c_size_t]),
     "jn_env_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                               C.c_int, C.c_void_p]),

@@ -270,6 +270,7 @@ static int alloc_workspaces(jn_ctx* ctx) {
   if (!c.no_patch_emb)
     if ((rc = dev_alloc(ctx, &ctx->efpn_act, (size_t)B * ctx->efpn_h * ctx->efpn_w * C))) return rc;
   if ((rc = dev_alloc(ctx, &ctx->patch_emb, (size_t)B * C))) return rc;
+  if (ctx->decision_route == 1 && (rc = dev_alloc(ctx, &ctx->wide_scratch, gpt_wide_scratch_floats(C, n_parts(c), B)))) return rc;
   JN_HIP(hipMemset(ctx->n_done, 0, ((size_t)Tmax + 1) * sizeof(int32_t)));
   for (auto& e : ctx->ev) JN_HIP(hipEventCreate(&e));
   return JN_OK;
@@ -290,8 +291,10 @@ int jn_create(const jn_config* cfg, jn_ctx** out) {
   JN_CHECK(cfg && out, JN_EINVAL, "jn_create: null argument");
   JN_CHECK(cfg->struct_size == (int)sizeof(jn_config), JN_EINVAL, "jn_config.struct_size %d != %zu", cfg->struct_size,
            sizeof(jn_config));
-  JN_CHECK(cfg->n_embd > 0 && cfg->n_embd % 4 == 0 && cfg->n_embd <= 256, JN_EINVAL,
-           "n_embd %d unsupported (multiple of 4, <= 256)", cfg->n_embd);
+  JN_CHECK(cfg->n_embd > 0 && cfg->n_embd % 4 == 0 &&
+               (cfg->n_embd <= GPT_PER_AGENT_MAX_C || (cfg->n_embd <= GPT_WIDE_MAX_C && cfg->n_embd % 64 == 0)),
+           JN_EINVAL, "n_embd %d unsupported (a multiple of 4 up to %d, or a multiple of 64 up to %d)", cfg->n_embd,
+           GPT_PER_AGENT_MAX_C, GPT_WIDE_MAX_C);
   JN_CHECK(cfg->n_head > 0 && cfg->n_embd % cfg->n_head == 0, JN_EINVAL, "n_embd %% n_head != 0");
   JN_CHECK(cfg->n_actions == 8 || cfg->n_actions == 9, JN_EINVAL, "n_actions must be 8 or 9");
   JN_CHECK(cfg->block_size >= 1 && cfg->block_size <= 255, JN_EINVAL, "block_size out of range");
@@ -300,6 +303,15 @@ int jn_create(const jn_config* cfg, jn_ctx** out) {
            "no patch encoder: set gpt_bb_width or with_detector (or no_patch_emb)");
   std::unique_ptr<jn_ctx> ctx(new jn_ctx());
   ctx->cfg = *cfg;
+  {
+    // the decision route: past gpt_step_kernel's envelope the wide one; cfg->gpt_wide (JN_GPT_WIDE=1 of the Python layer)
+    // takes it for every narrower model it admits as well — a test and A/B switch, ignored for the shapes it refuses
+    const bool want = cfg->n_embd > GPT_PER_AGENT_MAX_C || cfg->gpt_wide == 1;
+    ctx->decision_route = want && gpt_wide_admits(cfg->n_embd, cfg->n_head, cfg->block_size) ? 1 : 0;
+    JN_CHECK(cfg->n_embd <= GPT_PER_AGENT_MAX_C || ctx->decision_route == 1, JN_EINVAL,
+             "n_embd %d (above %d, up to %d) needs the wide decision route, which refuses this shape", cfg->n_embd,
+             GPT_PER_AGENT_MAX_C, GPT_WIDE_MAX_C);
+  }
   JN_CHECK(cfg->act_dtype == JN_F32 || cfg->act_dtype == JN_BF16, JN_EINVAL, "act_dtype must be 0 (fp32) or 1 (bf16)");
   ctx->nets[0].act_dtype = ctx->nets[1].act_dtype = cfg->act_dtype;
   if (ctx->cfg.det_nms_threshold <= 0) ctx->cfg.det_nms_threshold = 0.45f;
@@ -411,6 +423,8 @@ int jn_destroy(jn_ctx* ctx) {
   delete ctx;
   return JN_OK;
 }
+
+int jn_debug_decision_route(const jn_ctx* ctx) { return ctx ? ctx->decision_route : JN_EINVAL; }
 
 int jn_param_count(const jn_ctx* ctx) { return ctx ? (int)ctx->params_tab.size() : JN_EINVAL; }
 
@@ -545,6 +559,7 @@ int jn_load_weights(jn_ctx* ctx, const jn_tensor* tensors, size_t n) {
     if ((rc = dev_alloc(ctx, &d, (size_t)c.n_layer))) return rc;
     JN_HIP(hipMemcpy(d, lp.data(), lp.size() * sizeof(GptLayerPtrs), hipMemcpyHostToDevice));
     ctx->layers_dev = d;
+    ctx->layers_host = lp;
   }
   if (!ctx->gpt_arena_end) ctx->gpt_arena_end = ctx->arena_used;
   if ((rc = pack_net(JN_NET_DETECTOR))) return rc;

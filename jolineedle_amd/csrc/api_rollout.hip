@@ -177,7 +177,7 @@ int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const
     a.skip_flag = flag; a.skip_when = B;
     a.tok_emb_out = train ? ctx->tok_emb_train : nullptr;
     a.pdrop = train ? ctx->pdrop : 0.0f; a.drop_seed = ctx->drop_seed_used;
-    JN_CHECK(launch_gpt_step(a, s) == 0, JN_ESTATE, "gpt_step_kernel could not be launched (n_embd %d, block_size %d)", a.C, a.Tmax - 1);
+    JN_CHECK(launch_gpt_step_routed(a, s) == 0, JN_ESTATE, "the decision step could not be launched (n_embd %d, block_size %d)", a.C, a.Tmax - 1);
     if (out->patches_dev)
       env_gather(e, out->patches_dev + (long long)(t + 1) * 3 * P * P, patch_stride, P, flag, B, s);
     if (vm && (t + 1 < T || do_detection)) stage_fill(e, P, t + 1, flag, B, s);    // read by the next step and the detector

@@ -19,6 +19,7 @@ void fill_gpt_weights(const jn_ctx* ctx, GptStepArgs& a) {
   a.layers = ctx->layers_dev; a.emb_part = ctx->emb_part; a.KS = ctx->KS; a.efpn_lin_b = g.efpn_lin_b;
   a.kcache = ctx->kcache; a.vcache = ctx->vcache; a.prev_action = ctx->prev_action; a.cache_len = ctx->cache_len;
   a.n_done = ctx->n_done;
+  a.wide = ctx->decision_route; a.layers_host = ctx->layers_host.data(); a.wide_scratch = ctx->wide_scratch;
   // head_wt, ln_f and the layers are packed one after the other (load_weights' order): the step kernel warms L2 with that
   // run.  Should the order ever change, the run is no longer one piece and the kernel is told nothing.
   a.pf_base = nullptr; a.pf_floats = 0;
@@ -75,7 +76,7 @@ static int teacher_forced_decode(jn_ctx* ctx, const int64_t* actions_dev, const 
       a.pos_index = prev_emb_dev ? 0 : i;                 // recurrent tokens always get position 0 (gpt.py:431-449)
       a.tok_emb = tok_emb; a.tok_emb_stride = tok_emb_stride; a.tok_emb_index = i;
     }
-    JN_CHECK(launch_gpt_step(a, s) == 0, JN_ESTATE, "gpt_step_kernel could not be launched (n_embd %d, block_size %d)", a.C, a.Tmax - 1);
+    JN_CHECK(launch_gpt_step_routed(a, s) == 0, JN_ESTATE, "the decision step could not be launched (n_embd %d, block_size %d)", a.C, a.Tmax - 1);
   }
   return JN_OK;
 }
@@ -122,6 +123,7 @@ static int launch_gpt_bwd(jn_ctx* ctx, GptBwdArgs& ba, hipStream_t s) {
                         grad_of(ctx, y.fc_wt), grad_of(ctx, y.fc_b), grad_of(ctx, y.fc2_wt), grad_of(ctx, y.fc2_b)};
   }
   if (launch_gpt_backward_batched(ba, W.data(), G.data(), s) == 0) return JN_OK;
+  JN_CHECK(ctx->decision_route == 0, JN_EINVAL, "the batched GPT backward refuses n_embd %d, T %d, and a wide model has no other", C, ba.T);
   launch_gpt_backward(ba, s);
   return JN_OK;
 }
@@ -199,9 +201,15 @@ static int check_train_outputs(const jn_rollout_out* out) {
 }
 
 // what every training entry point needs of the context
-static int check_can_train(const jn_ctx* ctx) {
-  JN_CHECK(!ctx->cfg.no_patch_emb, JN_ESTATE, "training without a patch encoder is not supported");
-  JN_CHECK(ctx->cfg.block_size <= 62, JN_EINVAL, "training supports block_size <= 62");
+// (T: the sequence length about to be trained on, 0 when not known yet)
+static int check_can_train(const jn_ctx* ctx, int T) {
+  const jn_config& c = ctx->cfg;
+  JN_CHECK(!c.no_patch_emb, JN_ESTATE, "training without a patch encoder is not supported");
+  JN_CHECK(c.block_size <= 62, JN_EINVAL, "training supports block_size <= 62");
+  // a wide context has no backward but the batched one (gpt_backward_kernel's envelope ends at n_embd 256)
+  JN_CHECK(ctx->decision_route == 0 || T < 1 || gpt_backward_batched_admits(c.n_embd, c.n_head, T), JN_EINVAL,
+           "training a wide model (n_embd %d, head size %d) at T = %d: the batched backward needs n_embd <= %d and "
+           "4 (T + 1) head_size + 2 (T + 1)^2 <= 16384", c.n_embd, c.n_embd / c.n_head, T, GPT_WIDE_MAX_C);
   // batch-statistics BatchNorm on bf16-rounded pre-activations is ill-conditioned (the measurement behind
   // that statement: profiles/r03_bf16_train_probe.txt)
   JN_CHECK(ctx->cfg.act_dtype == JN_F32, JN_ESTATE, "training needs act_dtype = fp32 (bf16 is the inference mode)");
@@ -267,7 +275,7 @@ static int supervised_forward_impl(jn_ctx* ctx, const float* patches_dev, const 
   JN_CHECK(ctx->weights_loaded, JN_ESTATE, "jn_load_weights has not been called");
   const jn_config& c = ctx->cfg;
   int rc;
-  if ((rc = check_can_train(ctx))) return rc;
+  if ((rc = check_can_train(ctx, T))) return rc;
   JN_CHECK(T >= 1 && T <= c.block_size, JN_EINVAL, "sequence length %d out of range", T);
   JN_CHECK(B >= 1 && B * T <= c.max_batch, JN_EINVAL, "B*T = %d patches exceed max_batch = %d", B * T, c.max_batch);
   JN_CHECK(!c.use_pos_emb || positions_dev, JN_EINVAL, "positions are required when use_pos_emb is set");
@@ -424,7 +432,7 @@ int jn_reinforce_forward(jn_ctx* ctx, int mode, const int64_t* forced_actions_de
                          uint64_t seed, int stop_early, const jn_rollout_out* out, void* stream) {
   JN_CHECK(ctx && out, JN_EINVAL, "jn_reinforce_forward: null argument");
   int rc;
-  if ((rc = check_train_outputs(out)) || (rc = check_can_train(ctx))) return rc;
+  if ((rc = check_train_outputs(out)) || (rc = check_can_train(ctx, ctx->env.ready ? ctx->env.T : 0))) return rc;
   if ((rc = rollout_impl(ctx, mode, forced_actions_dev, start_positions_dev, seed, 0, stop_early, out, 1, stream))) return rc;
   ctx->train_out = *out; ctx->train_out_valid = true;
   return JN_OK;
@@ -454,7 +462,7 @@ int jn_reinforce_step(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, 
   JN_CHECK(ctx && opts && out && metrics_dev, JN_EINVAL, "jn_reinforce_step: null argument");
   JN_CHECK(opts->struct_size == (int)sizeof(jn_train_opts), JN_EINVAL, "jn_train_opts.struct_size mismatch");
   int rc;
-  if ((rc = check_train_outputs(out)) || (rc = check_can_train(ctx))) return rc;
+  if ((rc = check_train_outputs(out)) || (rc = check_can_train(ctx, ctx->env.ready ? ctx->env.T : 0))) return rc;
   hipStream_t s = (hipStream_t)stream;
   rc = rollout_impl(ctx, mode, forced_actions_dev, start_positions_dev, seed, 0, stop_early, out, 1, stream);
   if (rc) return rc;

@@ -261,6 +261,9 @@ struct jn_ctx {
   bool weights_loaded = false;
   std::vector<void*> owned;       // device allocations to free
   jnr::GptLayerPtrs* layers_dev = nullptr;
+  std::vector<jnr::GptLayerPtrs> layers_host;   // the same table on the host (the wide route launches per layer)
+  int decision_route = 0;         // 0: gpt_step_kernel, one workgroup per agent; 1: the wide route (kernels_gptwide.hip)
+  float* wide_scratch = nullptr;  // gpt_wide_scratch_floats(n_embd, n_parts, max_batch) floats of a wide context
   float* emb_part = nullptr;      // [B][KS][C] split-K partials of embed_fpn.3
   int KS = 8;
   int32_t* found = nullptr;       // [B] visited bbox tiles

@@ -469,8 +469,24 @@ struct GptStepArgs {
   float* tok_emb_out;               // [B][T][C] finished patch embedding of this step (training) or null
   float pdrop; uint64_t drop_seed;  // train-mode dropout (0 = off), see drop_scale in jn_device.h
   const int* skip_flag; int skip_when;
+  // the wide route (kernels_gptwide.hip), all null / 0 on the per-agent route
+  int wide;                         // 1: launch_gpt_step_routed goes to launch_gpt_step_wide
+  const GptLayerPtrs* layers_host;  // HOST array [n_layer] of the pointers `layers` holds on the device
+  float* wide_scratch;              // gpt_wide_scratch_floats(...) floats, allocated with the workspaces
 };
 int launch_gpt_step(const GptStepArgs& a, hipStream_t s);
+
+// ---- the wide decision route (kernels_gptwide.hip): one step as a chain of launches over all B agents ----------------
+constexpr int GPT_WIDE_MAX_C = 1024;        // 64 * LN_CQ of the batched backward (kernels_gptbwd.hip)
+constexpr int GPT_PER_AGENT_MAX_C = 256;    // where gpt_step_kernel's envelope ends
+// what the wide route takes: the GEMM's 64-column tiles and 32-row K chunks want n_embd a multiple of 64
+inline bool gpt_wide_admits(int C, int n_head, int block_size) {
+  return C >= 64 && C <= GPT_WIDE_MAX_C && C % 64 == 0 && n_head > 0 && C % n_head == 0 && block_size >= 1 && block_size <= 255;
+}
+size_t gpt_wide_scratch_floats(int C, int n_parts, int max_batch);
+int launch_gpt_step_wide(const GptStepArgs& a, hipStream_t s);
+// the step of a context's route: per-agent (launch_gpt_step) or wide
+int launch_gpt_step_routed(const GptStepArgs& a, hipStream_t s);
 
 // ---- training of the decision side (kernels_train.hip) ------------------------------------
 struct LossArgs {
@@ -517,6 +533,7 @@ int launch_gpt_backward(const GptBwdArgs& a, hipStream_t s);
 // the same backward batched over the agents (kernels_gptbwd.hip): W / G are HOST arrays of the per-layer weight and
 // gradient pointers; returns 1 when the shape is outside what it takes (caller falls back to launch_gpt_backward)
 size_t gpt_backward_batched_scratch(int C, int n_head, int n_layer, int nA, int B, int T);
+bool gpt_backward_batched_admits(int C, int n_head, int T);   // pure: the shapes launch_gpt_backward_batched takes
 int launch_gpt_backward_batched(const GptBwdArgs& a, const GptLayerPtrs* W, const GptLayerPtrs* G, hipStream_t s);
 int launch_ce_loss(const float* logits, const int64_t* target, const uint8_t* masks, float stop_weight, float* dlogits,
                    float* metrics, int n, int nA, int T, hipStream_t s);

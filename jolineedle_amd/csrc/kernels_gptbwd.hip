@@ -735,11 +735,19 @@ size_t gpt_backward_batched_scratch(int C, int n_head, int n_layer, int nA, int 
   return (size_t)(y.tmp + y.M * (13LL * C + nA + 2) + 64);
 }
 
+// The LayerNorm backward holds C / 64 <= LN_CQ columns per lane; the attention kernels keep q, k, v, dO of a head
+// (4 * Lm * hs floats) and two Lm x Lm score tiles in the 64 KB of LDS a kernel gets without asking (Lm = T + 1).
+bool gpt_backward_batched_admits(int C, int n_head, int T) {
+  if (C <= 0 || n_head <= 0 || C % n_head != 0 || T < 1 || C > 64 * LN_CQ) return false;
+  const size_t Lm = (size_t)T + 1, hs = (size_t)(C / n_head);
+  return (4 * Lm * hs + 2 * Lm * Lm) * sizeof(float) <= 64 * 1024;
+}
+
 // Returns 0 when launched, 1 when the shape is outside what these kernels take (the caller falls back).
 int launch_gpt_backward_batched(const GptBwdArgs& a, const GptLayerPtrs* W, const GptLayerPtrs* G, hipStream_t s) {
   const int C = a.C, nh = a.n_head, nL = a.n_layer, B = a.B, T = a.T, Lm = T + 1, hs = C / nh, nA = a.nA;
   const size_t attn_lds = ((size_t)4 * Lm * hs + (size_t)2 * Lm * Lm) * sizeof(float);
-  if (C > 64 * LN_CQ || attn_lds > 64 * 1024) return 1;
+  if (!gpt_backward_batched_admits(C, nh, T)) return 1;
   const Layout y = make_layout(C, nh, nL, B, T);
   const int M = (int)y.M;
   float* sc = a.scratch;

@@ -2,6 +2,7 @@
 objects, state-dict table, weight upload.  Shared by GPT / NeedleYOLOX / the env."""
 import ctypes as C
 import math
+import os
 
 import torch
 
@@ -99,6 +100,9 @@ def make_jn_config(config, device_index, max_batch, n_actions):
     c.det_nms_threshold = 0.45
     c.max_batch = max_batch
     c.max_det_per_patch = int(getattr(config, "max_det_per_patch", 64))
+    # JN_GPT_WIDE=1: the wide decision route for the narrow models it admits too (a test and A/B switch, read here once per
+    # context).  The library ignores it for shapes that route refuses (gpt-nano, gpt-pico)
+    c.gpt_wide = int(os.environ.get("JN_GPT_WIDE", "") == "1")
     c.act_dtype = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}[str(getattr(config, "act_dtype", "f32"))]
     return c
 
