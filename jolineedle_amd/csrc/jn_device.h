@@ -1,4 +1,5 @@
-// Device helpers shared by kernels_env.hip and kernels_gpt.hip.
+// Device helpers shared by the env kernels and the decision transformer: action tables, Philox, dropout keys, the env step.
+// (The decision transformer's own shared pieces are in jn_gpt_device.h, which includes this.)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -9,7 +9,7 @@
 // ([k][n]) so lanes read consecutive n.  Nothing here returns to the host.
 #include <hip/hip_runtime.h>
 
-#include "jn_device.h"
+#include "jn_gpt_device.h"
 
 namespace jnr {
 
@@ -75,22 +75,6 @@ __device__ __forceinline__ void touch_sink(const Touch<U>& t) {
 #pragma unroll
   for (int u = 0; u < U; ++u) v ^= t.r[u];
   asm volatile("" ::"v"(v));      // the loads must happen; nothing reads their values
-}
-
-template <int NT>
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  constexpr int GPT_WAVES = NT / 64;
-  // wave reduce by shuffles, then the waves' partials through LDS
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  const int tid = tid_here(), lane = tid & 63, wave = tid >> 6;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float s = 0.0f;
-#pragma unroll
-  for (int w = 0; w < GPT_WAVES; ++w) s += red[w];
-  return s;
 }
 
 // y[n] = b[n] + sum_k x[k] * wt[k*N + n]   (x in LDS, wt transposed in global/L2).
@@ -198,10 +182,10 @@ __device__ __forceinline__ void layer_norm(float* y, const float* x, const float
   const float w0 = w[min(tid, C - 1)], b0 = b[min(tid, C - 1)];
   float s = 0.0f;
   for (int i = tid; i < C; i += NT) s += x[i];
-  const float mean = block_sum<NT>(s, red) / C;
+  const float mean = block_sum<NT>(s, red, tid_here()) / C;
   float q = 0.0f;
   for (int i = tid; i < C; i += NT) { const float d = x[i] - mean; q += d * d; }
-  const float var = block_sum<NT>(q, red) / C;
+  const float var = block_sum<NT>(q, red, tid_here()) / C;
   const float rstd = 1.0f / sqrtf(var + 1e-5f);
   for (int i = tid; i < C; i += NT) {
     const float wi = i == tid ? w0 : w[i], bi = i == tid ? b0 : b[i];
@@ -210,19 +194,10 @@ __device__ __forceinline__ void layer_norm(float* y, const float* x, const float
   __syncthreads();
 }
 
-__device__ __forceinline__ float gelu_tanh(float x) {
-  // NewGELU, src/models/gpt.py:37-47
-  return 0.5f * x * (1.0f + tanhf(0.7978845608028654f * (x + 0.044715f * x * x * x)));
-}
-
 template <int NT>
 __global__ __launch_bounds__(NT) void gpt_step_kernel(GptStepArgs a) {
   constexpr int GPT_WAVES = NT / 64;
-  if (a.skip_flag && *a.skip_flag >= a.skip_when) {
-    // every env was done before this step: stay skipped for the rest of the trajectory
-    if (blockIdx.x == 0 && threadIdx.x == 0) a.n_done[a.step + 1] = a.skip_when;
-    return;
-  }
+  if (gpt_step_skipped(a)) return;
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int C = a.C, tid = threadIdx.x, b = blockIdx.x;
   float* x = sm;                 // [C]   residual stream
@@ -279,48 +254,22 @@ __global__ __launch_bounds__(NT) void gpt_step_kernel(GptStepArgs a) {
     const int tid = tid_here();       // (shadows the kernel's: per-token arithmetic stays inside the loop)
     const bool warm_now = j == 0 && !a.embed_only;
     // ---------------- token embedding ----------------
-    const bool class_tok = (a.src_mode == GPT_SRC_CLASS) || (a.src_mode == GPT_SRC_ENV && t == 0 && j == 0);
-    if (class_tok) {
-      // embed_class(classes) (gpt.py:476-478); the rollout passes no ids: class 0 (reinforce.py:128-129)
-      const int cls = a.classes ? min(max((int)a.classes[b], 0), JN_N_CLASS_ROWS - 1) : 0;
-      for (int i = tid; i < C; i += NT) x[i] = a.embed_class[(long long)cls * C + i];
-      if (warm_now) warm();
-    } else if (a.src_mode == GPT_SRC_GIVEN) {
-      const float* gp = a.given_emb + ((long long)b * a.given_stride + a.given_index) * C;
-      for (int i = tid; i < C; i += NT) x[i] = gp[i];
+    const GptTokSrc ts = gpt_tok_src(a, b, j);
+    if (ts.direct) {                       // the class token or a given embedding: the row as it is
+      for (int i = tid; i < C; i += NT) x[i] = ts.direct[i];
       if (warm_now) warm();
     } else {
-      int act, row, col;
-      if (a.src_mode == GPT_SRC_ENV) {
-        act = (int)a.prev_action[b];
-        row = (int)a.env.positions[2 * b]; col = (int)a.env.positions[2 * b + 1];
-      } else {
-        const long long bi = (long long)b * a.t_stride + a.t_index;
-        act = (int)a.t_actions[bi];
-        row = a.t_positions ? (int)a.t_positions[2 * bi] : 0;
-        col = a.t_positions ? (int)a.t_positions[2 * bi + 1] : 0;
-      }
-      act = min(max(act, 0), a.nA - 1);
-      row = min(max(row, 0), 255); col = min(max(col, 0), 255);
+      const int act = ts.act, row = ts.row, col = ts.col;
       float* parts = mlp;
       int p = 0;
       for (int i = tid; i < C; i += NT) parts[i] = a.wte[act * C + i];
       ++p;
-      for (int i = tid; i < C; i += NT)
-        parts[p * C + i] = a.dec_pos_enc ? a.pos1d[a.pos_index * C + i] : a.wpe[a.pos_index * C + i];
+      for (int i = tid; i < C; i += NT) parts[p * C + i] = gpt_pos1d(a, a.pos_index, i);
       ++p;
       if (!a.no_patch_emb) {
         if (a.src_mode == GPT_SRC_ENV) {
           for (int i = tid; i < C; i += NT) {
-            float s = a.efpn_lin_b[i];
-            const float* ep = a.emb_part + (long long)b * a.KS * C + i;
-            for (int ks0 = 0; ks0 < a.KS; ks0 += 8) {       // eight partials in flight, added in ascending order
-              float v[8];
-#pragma unroll
-              for (int u = 0; u < 8; ++u) v[u] = ep[(long long)min(ks0 + u, a.KS - 1) * C];
-#pragma unroll
-              for (int u = 0; u < 8; ++u) { const float nx = s + v[u]; s = ks0 + u < a.KS ? nx : s; }
-            }
+            const float s = sum_parts(a.efpn_lin_b[i], a.emb_part + (long long)b * a.KS * C + i, (long long)C, a.KS);   // ascending, behind the bias
             parts[p * C + i] = s;
             if (a.tok_emb_out) a.tok_emb_out[((long long)b * a.T + t) * C + i] = s;
           }
@@ -331,8 +280,7 @@ __global__ __launch_bounds__(NT) void gpt_step_kernel(GptStepArgs a) {
         ++p;
       }
       if (a.use_pos_emb) {
-        for (int i = tid; i < C; i += NT)
-          parts[p * C + i] = (i < a.pe2_ch) ? a.pe2[col * a.pe2_ch + i] : a.pe2[row * a.pe2_ch + (i - a.pe2_ch)];
+        for (int i = tid; i < C; i += NT) parts[p * C + i] = gpt_pos2d(a, row, col, i);
         ++p;
       }
       if (warm_now) warm();      // behind the embedding's own loads: loads return in order
@@ -472,49 +420,7 @@ __global__ __launch_bounds__(NT) void gpt_step_kernel(GptStepArgs a) {
     if (a.logits_rows && tid < a.nA) a.logits_rows[(long long)b * a.logits_stride + tid] = lg[tid];
     return;
   }
-  if (tid == 0) {
-    a.cache_len[b] = len;
-    const int nA = a.nA;
-    float m = -INFINITY;
-    int best = 0;
-    for (int i = 0; i < nA; ++i)
-      if (lg[i] > m) { m = lg[i]; best = i; }           // first maximum, as torch.argmax
-    float sum = 0.0f;
-    for (int i = 0; i < nA; ++i) sum += expf(lg[i] - m);
-    const float lse = m + logf(sum);
-    float ent = 0.0f;
-    for (int i = 0; i < nA; ++i) { const float lp = lg[i] - lse; ent -= lp * expf(lp); }
-    int act = best;
-    if (a.mode == JN_MODE_FORCED) {
-      act = (int)a.forced[(long long)b * a.T + t];
-      act = min(max(act, 0), nA - 1);
-    } else if (a.mode == JN_MODE_SAMPLE) {
-      const uint4 r = philox4x32(a.seed, (uint32_t)b, (uint32_t)t, 0x53414d50u, 0u);
-      const float u = u01(r.x);
-      float cdf = 0.0f;
-      act = nA - 1;
-      for (int i = 0; i < nA; ++i) {
-        cdf += expf(lg[i] - lse);
-        if (u < cdf) { act = i; break; }
-      }
-    }
-    const float logp = lg[act] - lse;
-    const EnvStepResult r = env_step_one(a.env, b, act);
-    a.prev_action[b] = act;
-    const long long bt = (long long)b * a.T + t;
-    if (a.out.rewards) a.out.rewards[bt] = r.reward;
-    if (a.out.logprobs) a.out.logprobs[bt] = logp;
-    if (a.out.entropies) a.out.entropies[bt] = ent;
-    if (a.out.actions) a.out.actions[bt] = act;
-    if (a.out.masks) a.out.masks[(long long)b * (a.T + 1) + t + 1] = r.terminated ? 0 : 1;
-    if (a.out.positions) {
-      a.out.positions[((long long)b * (a.T + 1) + t + 1) * 2] = r.y;
-      a.out.positions[((long long)b * (a.T + 1) + t + 1) * 2 + 1] = r.x;
-    }
-    if (a.out.logits)
-      for (int i = 0; i < nA; ++i) a.out.logits[bt * nA + i] = lg[i];
-    if (r.terminated || r.truncated) atomicAdd(a.n_done + t + 1, 1);
-  }
+  if (tid == 0) gpt_decide_and_step(a, b, lg, len);
 }
 
 // The agent's K / V rows of a layer are staged in LDS when the workgroup then still fits a CU's 160 KB (every model of
@@ -528,20 +434,10 @@ int launch_gpt_step(const GptStepArgs& a0, hipStream_t s) {
   const size_t base = (size_t)(9 * a.C + a.n_head * a.Tmax + nt / 64 + 16 + 4 + 4 * nt) * sizeof(float);
   const size_t with_kv = base + (size_t)2 * a.Tmax * a.C * sizeof(float);
   a.kv_lds = with_kv <= GPT_LDS_MAX;
-  if (a.kv_lds && with_kv > 64 * 1024) {       // past the default limit of dynamic LDS (gpt-mini: 2 x 33 x 192 floats -> 75 KB)
-    static size_t raised[2] = {0, 0}, refused[2] = {GPT_LDS_MAX + 1, GPT_LDS_MAX + 1};
-    const int k = nt == 256 ? 0 : 1;
-    if (with_kv >= refused[k]) {
-      a.kv_lds = 0;
-    } else if (with_kv > raised[k]) {
-      const void* f = nt == 256 ? reinterpret_cast<const void*>(&gpt_step_kernel<256>) : reinterpret_cast<const void*>(&gpt_step_kernel<1024>);
-      if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)with_kv) == hipSuccess) {
-        raised[k] = with_kv;
-      } else {
-        (void)hipGetLastError();
-        refused[k] = with_kv; a.kv_lds = 0;
-      }
-    }
+  // past the default limit of dynamic LDS (gpt-mini: 2 x 33 x 192 floats -> 75 KB) the size has to be granted
+  if (a.kv_lds && !(nt == 256 ? allow_lds<&gpt_step_kernel<256>>(with_kv) : allow_lds<&gpt_step_kernel<1024>>(with_kv))) {
+    (void)hipGetLastError();      // refused: the launch below must not report the refusal as its own error
+    a.kv_lds = 0;
   }
   const size_t smem = a.kv_lds ? with_kv : base;
   if (nt == 256) hipLaunchKernelGGL(gpt_step_kernel<256>, dim3(a.B), dim3(256), smem, s, a);

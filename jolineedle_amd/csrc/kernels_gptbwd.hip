@@ -17,7 +17,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "jn_device.h"
+#include "jn_gpt_device.h"
 #include "jn_kernels.h"
 #include "jn_types.h"
 
@@ -25,15 +25,6 @@ namespace jnr {
 namespace {
 
 constexpr int GT = 256;
-
-__device__ __forceinline__ float gelu_fb(float x) {
-  return 0.5f * x * (1.0f + tanhf(0.7978845608028654f * (x + 0.044715f * x * x * x)));
-}
-__device__ __forceinline__ float gelu_db(float x) {
-  const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
-  const float th = tanhf(u);
-  return 0.5f * (1.0f + th) + 0.5f * x * (1.0f - th * th) * 0.7978845608028654f * (1.0f + 3.0f * 0.044715f * x * x);
-}
 
 struct GemmArgs {
   const float* A; long long a_rs, a_cs;      // A(m, k) = A[m * a_rs + k * a_cs]
@@ -75,7 +66,7 @@ __global__ __launch_bounds__(GT) void gptb_gemm_kernel(GemmArgs g) {
       if (gm < g.M && gk < kend) {
         if ((gm % g.Lm) < L) {
           v = g.A[(long long)gm * g.a_rs + (long long)gk * g.a_cs];
-          if (g.a_gelu) v = gelu_fb(v);
+          if (g.a_gelu) v = gelu_tanh(v);
         }
       }
       As[k][m] = v;
@@ -118,7 +109,7 @@ __global__ __launch_bounds__(GT) void gptb_gemm_kernel(GemmArgs g) {
         if (g.bias) v += g.bias[gn];
         if (g.site >= 0 && g.pdrop > 0.0f) v *= drop_scale(g.seed, gm / g.Lm, gm % g.Lm, g.layer, g.site, gn, g.pdrop);
         if (g.resid) v += g.resid[o];
-        if (g.mulp) v *= gelu_db(g.mulp[o]);
+        if (g.mulp) v *= gelu_tanh_grad(g.mulp[o]);
       } else {
         v = 0.0f;
       }
@@ -166,14 +157,14 @@ __global__ __launch_bounds__(GT) void gptb_tok_gemm_kernel(GemmArgs g, int vec_a
       for (int j = 0; j < NA; ++j) {
         const int kq = r + 8 * j;
         f4 w = v[j];
-        if (g.a_gelu) { w.x = gelu_fb(w.x); w.y = gelu_fb(w.y); w.z = gelu_fb(w.z); w.w = gelu_fb(w.w); }
+        if (g.a_gelu) { w.x = gelu_tanh(w.x); w.y = gelu_tanh(w.y); w.z = gelu_tanh(w.z); w.w = gelu_tanh(w.w); }
         if (!live) w = f4{0.f, 0.f, 0.f, 0.f};
         if (kq < KQ) *reinterpret_cast<f4*>(as + 4 * kq) = w;
       }
     } else {
       for (int k = r; k < K4; k += 8) {
         float v = 0.0f;
-        if (live && k < K) { v = ap[k]; if (g.a_gelu) v = gelu_fb(v); }
+        if (live && k < K) { v = ap[k]; if (g.a_gelu) v = gelu_tanh(v); }
         as[k] = v;
       }
     }
@@ -275,7 +266,7 @@ __global__ __launch_bounds__(GT) void gptb_tok_gemm_kernel(GemmArgs g, int vec_a
         if (g.bias) v += g.bias[gn];
         if (g.site >= 0 && g.pdrop > 0.0f) v *= drop_scale(g.seed, gm / g.Lm, gm % g.Lm, g.layer, g.site, gn, g.pdrop);
         if (g.resid) v += g.resid[o];
-        if (g.mulp) v *= gelu_db(g.mulp[o]);
+        if (g.mulp) v *= gelu_tanh_grad(g.mulp[o]);
       } else {
         v = 0.0f;
       }
@@ -336,7 +327,7 @@ __global__ __launch_bounds__(GT) void gptb_wgrad_kernel(GemmArgs g, float* __res
     for (int j = 0; j < 4; ++j) {
       const int e = tid + j * GT, r = e >> 4, q4 = 4 * (e & 15);
       f4 a = va[j];
-      if (g.a_gelu) { a.x = gelu_fb(a.x); a.y = gelu_fb(a.y); a.z = gelu_fb(a.z); a.w = gelu_fb(a.w); }
+      if (g.a_gelu) { a.x = gelu_tanh(a.x); a.y = gelu_tanh(a.y); a.z = gelu_tanh(a.z); a.w = gelu_tanh(a.w); }
       *reinterpret_cast<f4*>(&As[r][q4]) = la[j] ? a : f4{0.f, 0.f, 0.f, 0.f};
       *reinterpret_cast<f4*>(&Bs[r][q4]) = lb[j] ? vb[j] : f4{0.f, 0.f, 0.f, 0.f};
     }
@@ -345,7 +336,7 @@ __global__ __launch_bounds__(GT) void gptb_wgrad_kernel(GemmArgs g, float* __res
       const int r = e >> 6, c = e & 63, gr = r0 + r;
       const bool live = gr < R && (gr % g.Lm) < L;
       float a = 0.0f, b = 0.0f;
-      if (live && f0 + c < Kf) { a = g.A[(long long)gr * g.a_cs + f0 + c]; if (g.a_gelu) a = gelu_fb(a); }
+      if (live && f0 + c < Kf) { a = g.A[(long long)gr * g.a_cs + f0 + c]; if (g.a_gelu) a = gelu_tanh(a); }
       if (live && n0 + c < N) b = g.B[(long long)gr * g.b_rs + n0 + c];
       As[r][c] = a; Bs[r][c] = b;
     }
@@ -399,12 +390,6 @@ void gemm(GemmArgs g, hipStream_t s) {
   else if (ak) hipLaunchKernelGGL((gptb_gemm_kernel<true, false>), grid, dim3(GT), 0, s, g);
   else if (bn) hipLaunchKernelGGL((gptb_gemm_kernel<false, true>), grid, dim3(GT), 0, s, g);
   else hipLaunchKernelGGL((gptb_gemm_kernel<false, false>), grid, dim3(GT), 0, s, g);
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 // L = S + 1 (S = first step at which every agent is done, gpt_backward_kernel's rule) and the embedded trajectory

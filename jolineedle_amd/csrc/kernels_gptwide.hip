@@ -13,12 +13,13 @@
 // appends the K / V row to the cache [L][B][Tmax][C]), proj GEMM, ln_2 (folds the proj residual), fc GEMM, fc2 GEMM
 // (operand = gelu(partials + bias)): 7 launches; with the embedding and the tail 7 L + 2 per token (+ 2 with concat_emb).
 // Dropout: drop_scale of jn_device.h with gpt_step_kernel's keys, so the batched backward differentiates this forward.
-// The env step is env_step_one of jn_device.h, the code gpt_step_kernel calls.
+// The token source, the skipped-step prologue and the decision with its env step are the functions of jn_gpt_device.h
+// that gpt_step_kernel calls.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "jn_device.h"
+#include "jn_gpt_device.h"
 
 namespace jnr {
 
@@ -33,44 +34,6 @@ constexpr int WG_LDX = WG_KC + 4, WG_LDW = 64 + 4;
 constexpr int WIDE_WGS = 256;               // workgroups a Linear should launch at least: one per CU
 constexpr int WIDE_KS_MAX = 32;
 constexpr int WIDE_CQ = GPT_WIDE_MAX_C / WT;   // residual elements per thread of a row
-
-__device__ __forceinline__ float gelu_tanh_w(float x) {
-  // NewGELU, src/models/gpt.py:37-47 (the expression of kernels_gpt.hip)
-  return 0.5f * x * (1.0f + tanhf(0.7978845608028654f * (x + 0.044715f * x * x * x)));
-}
-
-__device__ __forceinline__ bool step_skipped(const int* flag, int when) { return flag && *flag >= when; }
-
-// init + p[0] + p[stride] + ... (n terms, ascending: the order every consumer of split-K partials keeps), eight loads in
-// flight at a time.  A plain loop waits for each load before it asks for the next, and a consumer with one workgroup per
-// agent has nothing else to run meanwhile: 24 partials were 24 round trips to L2.  Terms past n are asked for at a clamped
-// address and left out by a select, not by a branch around the load.
-template <typename V>
-__device__ __forceinline__ V sum_parts(V init, const float* __restrict__ p, long long stride, int n) {
-  V s = init;
-  for (int k0 = 0; k0 < n; k0 += 8) {
-    V v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const V*>(p + (long long)min(k0 + u, n - 1) * stride);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) { const V nx = s + v[u]; s = k0 + u < n ? nx : s; }
-  }
-  return s;
-}
-
-// sum over the workgroup's WT threads; red: WT / 64 floats of LDS
-__device__ __forceinline__ float block_sum_w(float v, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  float s = 0.0f;
-#pragma unroll
-  for (int w = 0; w < WT / 64; ++w) s += red[w];
-  return s;
-}
 
 // ---- the skinny GEMM -------------------------------------------------------------------------------------------------
 struct WideGemm {
@@ -128,7 +91,7 @@ __global__ __launch_bounds__(WT) void gptw_gemm_kernel(WideGemm g) {
         } else {
           v = sum_parts(*reinterpret_cast<const f32x4*>(g.xbias + k), g.X + (long long)m * g.K + k, (long long)g.M * g.K, g.xparts);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = gelu_tanh_w(v[e]);
+          for (int e = 0; e < 4; ++e) v[e] = gelu_tanh(v[e]);
         }
       }
       *reinterpret_cast<f32x4*>(Xs + r * WG_LDX + 4 * q) = v;
@@ -233,12 +196,12 @@ __device__ __forceinline__ void wide_ln_row(const WideLn& a, int b, float* out, 
       s += x;
     }
   }
-  const float mean = block_sum_w(s, red) / C;
+  const float mean = block_sum<WT>(s, red, tid) / C;
   float q = 0.0f;
 #pragma unroll
   for (int u = 0; u < WIDE_CQ; ++u)
     if (tid + u * WT < C) { const float d = xv[u] - mean; q += d * d; }
-  const float var = block_sum_w(q, red) / C;
+  const float var = block_sum<WT>(q, red, tid) / C;
   const float rstd = 1.0f / sqrtf(var + 1e-5f);
 #pragma unroll
   for (int u = 0; u < WIDE_CQ; ++u) {
@@ -261,38 +224,19 @@ __global__ __launch_bounds__(WT) void gptw_embed_kernel(GptStepArgs a, int j, in
   if (step_skipped(a.skip_flag, a.skip_when)) return;
   const int C = a.C, tid = threadIdx.x, b = blockIdx.x, t = a.step;
   const int len = a.cache_len[b] + j;
-  const bool class_tok = (a.src_mode == GPT_SRC_CLASS) || (a.src_mode == GPT_SRC_ENV && t == 0 && j == 0);
-  const bool given = !class_tok && a.src_mode == GPT_SRC_GIVEN;
-  const bool to_gemm = !class_tok && !given && a.concat_emb;
-  int act = 0, row = 0, col = 0;
-  const float* direct = nullptr;
-  if (class_tok) {
-    const int cls = a.classes ? min(max((int)a.classes[b], 0), JN_N_CLASS_ROWS - 1) : 0;
-    direct = a.embed_class + (long long)cls * C;
-  } else if (given) {
-    direct = a.given_emb + ((long long)b * a.given_stride + a.given_index) * C;
-  } else {
-    if (a.src_mode == GPT_SRC_ENV) {
-      act = (int)a.prev_action[b];
-      row = (int)a.env.positions[2 * b]; col = (int)a.env.positions[2 * b + 1];
-    } else {
-      const long long bi = (long long)b * a.t_stride + a.t_index;
-      act = (int)a.t_actions[bi];
-      row = a.t_positions ? (int)a.t_positions[2 * bi] : 0;
-      col = a.t_positions ? (int)a.t_positions[2 * bi + 1] : 0;
-    }
-    act = min(max(act, 0), a.nA - 1);
-    row = min(max(row, 0), 255); col = min(max(col, 0), 255);
-  }
+  const GptTokSrc ts = gpt_tok_src(a, b, j);
+  const bool to_gemm = ts.kind.to_gemm;
+  const int act = ts.act, row = ts.row, col = ts.col;
+  const float* direct = ts.direct;
   for (int i = tid; i < C; i += WT) {
     float x;
     if (direct) {
       x = direct[i];
     } else {
-      float v[4];
+      f32x4 v;       // (a vector, not an array: indexed by p, an array went to 4 KB of LDS here and the step cost 3 % more)
       int p = 0;
       v[p++] = a.wte[act * C + i];
-      v[p++] = a.dec_pos_enc ? a.pos1d[a.pos_index * C + i] : a.wpe[a.pos_index * C + i];
+      v[p++] = gpt_pos1d(a, a.pos_index, i);
       if (!a.no_patch_emb) {
         if (a.src_mode == GPT_SRC_ENV) {
           const float s = sum_parts(a.efpn_lin_b[i], a.emb_part + (long long)b * a.KS * C + i, (long long)C, a.KS);   // ascending, behind the bias
@@ -302,7 +246,7 @@ __global__ __launch_bounds__(WT) void gptw_embed_kernel(GptStepArgs a, int j, in
           v[p++] = a.tok_emb[((long long)b * a.tok_emb_stride + a.tok_emb_index) * C + i];
         }
       }
-      if (a.use_pos_emb) v[p++] = (i < a.pe2_ch) ? a.pe2[col * a.pe2_ch + i] : a.pe2[row * a.pe2_ch + (i - a.pe2_ch)];
+      if (a.use_pos_emb) v[p++] = gpt_pos2d(a, row, col, i);
       if (to_gemm) {
         for (int q = 0; q < p; ++q) E[((long long)b * p + q) * C + i] = v[q];
         continue;
@@ -410,16 +354,12 @@ __global__ __launch_bounds__(64) void gptw_attn_kernel(WideAttn a) {
 
 // ---- tail: last residual, ln_f, head, decision, env step, bookkeeping; one workgroup per agent -------------------------
 __global__ __launch_bounds__(WT) void gptw_tail_kernel(GptStepArgs a, WideLn ln) {
-  if (step_skipped(a.skip_flag, a.skip_when)) {
-    // every env was done before this step: stay skipped for the rest of the trajectory
-    if (blockIdx.x == 0 && threadIdx.x == 0) a.n_done[a.step + 1] = a.skip_when;
-    return;
-  }
+  if (gpt_step_skipped(a)) return;
   __shared__ float h[GPT_WIDE_MAX_C];
   __shared__ float red[WT / 64];
   __shared__ float hp[WT / 64][16];
   __shared__ float lg[16];
-  const int tid = threadIdx.x, b = blockIdx.x, C = a.C, nA = a.nA, t = a.step;
+  const int tid = threadIdx.x, b = blockIdx.x, C = a.C, nA = a.nA;
   const int len = a.cache_len[b] + ln.tok_j + 1;      // tokens cached once this step is done
   wide_ln_row(ln, b, h, red);
   __syncthreads();
@@ -434,9 +374,7 @@ __global__ __launch_bounds__(WT) void gptw_tail_kernel(GptStepArgs a, WideLn ln)
   }
 #pragma unroll
   for (int n = 0; n < 9; ++n) {
-    float v = acc[n];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    const float v = wave_sum(acc[n]);
     if ((tid & 63) == 0) hp[tid >> 6][n] = v;
   }
   __syncthreads();
@@ -453,54 +391,7 @@ __global__ __launch_bounds__(WT) void gptw_tail_kernel(GptStepArgs a, WideLn ln)
     if (a.logits_rows && tid < nA) a.logits_rows[(long long)b * a.logits_stride + tid] = lg[tid];
     return;
   }
-  if (tid == 0) {
-    // KEEP IN STEP with the block behind "head on the newest token" of gpt_step_kernel (kernels_gpt.hip): this is that
-    // block statement for statement — first-maximum argmax, the Philox draw keyed (seed, agent, step, "SAMP"), forced
-    // action, log-prob, entropy, env_step_one, the output writes and the n_done count (reinforce.py:73-90, 169-179).  That
-    // unit is frozen (tests/test_gpu_gpt_step_bits.py pins its bits), so the block is restated here, not shared;
-    // tests/test_gpu_wide_gpt.py holds the two against each other (same integers, same sampled walk).  A change to either
-    // copy goes into both; the place for a shared one is jn_device.h, beside env_step_one.
-    a.cache_len[b] = len;
-    float m = -INFINITY;
-    int best = 0;
-    for (int i = 0; i < nA; ++i)
-      if (lg[i] > m) { m = lg[i]; best = i; }           // first maximum, as torch.argmax
-    float sum = 0.0f;
-    for (int i = 0; i < nA; ++i) sum += expf(lg[i] - m);
-    const float lse = m + logf(sum);
-    float ent = 0.0f;
-    for (int i = 0; i < nA; ++i) { const float lp = lg[i] - lse; ent -= lp * expf(lp); }
-    int act = best;
-    if (a.mode == JN_MODE_FORCED) {
-      act = (int)a.forced[(long long)b * a.T + t];
-      act = min(max(act, 0), nA - 1);
-    } else if (a.mode == JN_MODE_SAMPLE) {
-      const uint4 r = philox4x32(a.seed, (uint32_t)b, (uint32_t)t, 0x53414d50u, 0u);
-      const float u = u01(r.x);
-      float cdf = 0.0f;
-      act = nA - 1;
-      for (int i = 0; i < nA; ++i) {
-        cdf += expf(lg[i] - lse);
-        if (u < cdf) { act = i; break; }
-      }
-    }
-    const float logp = lg[act] - lse;
-    const EnvStepResult r = env_step_one(a.env, b, act);
-    a.prev_action[b] = act;
-    const long long bt = (long long)b * a.T + t;
-    if (a.out.rewards) a.out.rewards[bt] = r.reward;
-    if (a.out.logprobs) a.out.logprobs[bt] = logp;
-    if (a.out.entropies) a.out.entropies[bt] = ent;
-    if (a.out.actions) a.out.actions[bt] = act;
-    if (a.out.masks) a.out.masks[(long long)b * (a.T + 1) + t + 1] = r.terminated ? 0 : 1;
-    if (a.out.positions) {
-      a.out.positions[((long long)b * (a.T + 1) + t + 1) * 2] = r.y;
-      a.out.positions[((long long)b * (a.T + 1) + t + 1) * 2 + 1] = r.x;
-    }
-    if (a.out.logits)
-      for (int i = 0; i < nA; ++i) a.out.logits[bt * nA + i] = lg[i];
-    if (r.terminated || r.truncated) atomicAdd(a.n_done + t + 1, 1);      // an integer count: order-free
-  }
+  if (tid == 0) gpt_decide_and_step(a, b, lg, len);
 }
 
 }  // namespace
@@ -535,8 +426,7 @@ int launch_gpt_step_wide(const GptStepArgs& a, hipStream_t s) {
   int pb_parts = 0;
   for (int j = 0; j < n_new; ++j) {
     const int last = j == n_new - 1;
-    const bool class_tok = a.src_mode == GPT_SRC_CLASS || (a.src_mode == GPT_SRC_ENV && a.step == 0 && j == 0);
-    const bool to_gemm = !class_tok && a.src_mode != GPT_SRC_GIVEN && a.concat_emb;
+    const bool to_gemm = gpt_tok_kind(a, j).to_gemm;
     hipLaunchKernelGGL(gptw_embed_kernel, dim3(B), dim3(WT), 0, s, a, j, last, X, E);
     if (to_gemm) {
       const int ks = gemm(PB, E, 0, nullptr, a.proj_wt, a.n_parts * C, C);

@@ -7,7 +7,7 @@
 // each agent, which is what gpt_backward_kernel recomputes and differentiates.
 #include <hip/hip_runtime.h>
 
-#include "jn_device.h"
+#include "jn_gpt_device.h"
 #include "jn_kernels.h"
 #include "jn_types.h"
 
@@ -381,15 +381,6 @@ __device__ __forceinline__ void ln_bwd(float* din, const float* dout, const floa
   __syncthreads();
 }
 
-__device__ __forceinline__ float gelu_f(float x) {
-  return 0.5f * x * (1.0f + tanhf(0.7978845608028654f * (x + 0.044715f * x * x * x)));
-}
-__device__ __forceinline__ float gelu_d(float x) {
-  const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
-  const float th = tanhf(u);
-  return 0.5f * (1.0f + th) + 0.5f * x * (1.0f - th * th) * 0.7978845608028654f * (1.0f + 3.0f * 0.044715f * x * x);
-}
-
 // ---- GPT backward, one workgroup per agent ------------------------------------------------------
 __global__ __launch_bounds__(GB) void gpt_backward_kernel(GptBwdArgs a) {
   __shared__ float mu[64], rs[64];
@@ -481,7 +472,7 @@ __global__ __launch_bounds__(GB) void gpt_backward_kernel(GptBwdArgs a) {
     lin_fwd(Fp, H2, W.fc_wt, W.fc_b, L, C, 4 * C);
     float* xo = X + (l + 1) * L * C;
     // mlp out: needs gelu(F); use dF as a temporary activation buffer
-    for (int e = tid; e < L * 4 * C; e += GB) dF[e] = gelu_f(Fp[e]);
+    for (int e = tid; e < L * 4 * C; e += GB) dF[e] = gelu_tanh(Fp[e]);
     __syncthreads();
     lin_fwd(xo, dF, W.fc2_wt, W.fc2_b, L, 4 * C, C);
     for (int e = tid; e < L * C; e += GB) xo[e] = XM[e] + (drop ? xo[e] * drop_scale(dseed, b, e / C, l, 3, e % C, pd) : xo[e]);
@@ -534,7 +525,7 @@ __global__ __launch_bounds__(GB) void gpt_backward_kernel(GptBwdArgs a) {
     for (int e = tid; e < 4 * C * C; e += GB) {
       const int k = e / C, c = e - k * C;
       float acc = 0.0f;
-      for (int i = 0; i < L; ++i) acc = fmaf(gelu_f(Fp[i * 4 * C + k]), dO[i * C + c], acc);
+      for (int i = 0; i < L; ++i) acc = fmaf(gelu_tanh(Fp[i * 4 * C + k]), dO[i * C + c], acc);
       atomicAdd(&G.fc2_wt[e], acc);
     }
     for (int c = tid; c < C; c += GB) {
@@ -542,7 +533,7 @@ __global__ __launch_bounds__(GB) void gpt_backward_kernel(GptBwdArgs a) {
       for (int i = 0; i < L; ++i) acc += dO[i * C + c];
       atomicAdd(&G.fc2_b[c], acc);
     }
-    for (int e = tid; e < L * 4 * C; e += GB) dF[e] *= gelu_d(Fp[e]);
+    for (int e = tid; e < L * 4 * C; e += GB) dF[e] *= gelu_tanh_grad(Fp[e]);
     __syncthreads();
     lin_bwd_data(dH, dF, W.fc_wt, L, C, 4 * C, false);
     lin_bwd_weight(G.fc_wt, G.fc_b, H2, dF, L, C, 4 * C, 0);
