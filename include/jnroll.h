@@ -690,6 +690,42 @@ int jn_teacher_walks(const int64_t* bboxes_dev, const int64_t* start_positions_d
 int jn_pw_bwd_fused(const float* g_dev, const float* z_dev, const float* x_dev, const float* tab_dev, const float* save_dev,
                     const float* consts_dev, const float* w_dev, const float* gadd_dev, int accumulate, float* gx_dev,
                     float* gw_dev, int S, long long M, int cout, int cin, int route, int max_wg, void* stream);
+/* Debug entries, context-free: ONE launch of a dense 3x3 kernel (pad 1, stride 1 or 2; csrc/kernels_conv3.hip) on caller
+ * tensors, then a wait for `stream`.  All maps are NHWC with a leading dimension (floats, or bf16 elements, between pixels)
+ * that may exceed the channel count: channels past it are neither read nor written.  H x W is always the layer's INPUT
+ * map, the output map is H / stride x W / stride.  A table is f32 [3][cin]: rows scale, shift, flag; the kernels read
+ * a = flag ? silu(scale * x + shift) : x, and the zero padding is applied to a.  `route` picks the kernel: 0 = the
+ * launcher's own rule (what the networks get), else one kernel family, which must admit the launch.
+ * Common JN_EINVAL, before any device call: a null pointer (but the optional ones), N, H, W < 1, a channel count or a
+ * leading dimension that is no multiple of 4, a leading dimension below its channel count, a stride other than 1 or 2,
+ * an odd H or W at stride 2, n_slots < 1, a route out of range or one whose preconditions the launch does not meet, a size
+ * beyond what a debug call is for (N * H * W > 2^24, more than 4096 channels, a leading dimension above 8192, n_slots > 64).
+ *
+ * jn_conv3: out (=|+=) conv(a(in), w).  w f32 [9][cout][cin], tap = 3 ky + kx.  transposed != 0 (stride 1 only): the data
+ * gradient of a stride-1 layer, out[y][x][n] = sum a(in)[y + 1 - ky][x + 1 - kx][k] * w[tap][k][n] with w f32 [9][cin][cout],
+ * the forward layer's weight.  stats_dev: NULL, or f64 [32][2 cout] that the launch ADDS per-channel (sum, sum of squares)
+ * of the output pixels into, spread over the 32 replicas.  skip_flag_dev: NULL, or a device int; the launch does nothing
+ * when *skip_flag_dev >= skip_when.  n_slots > 1: slot j reads in + j * in_slot_stride and writes out + j * out_slot_stride
+ * (elements; all slots share the table).  Routes: 1 = fp32 matrix pipe; 2 = three-way split operands on the bf16 pipe
+ * (cin % 32 == 0; at stride 2 neither accumulate nor slots); 3 = bf16 inference kernel: in and out hold bf16, w is rounded
+ * to bf16 inside the call (cin % 8 == 0; no stats, accumulate, slots or transposed).
+ * jn_conv3_bwd_data_s2: data gradient of a stride-2 layer, gin [S][N,H,W,gin_ld] (=|+=) from gz [S][N,H/2,W/2,g_ld] and the
+ * forward weight w [9][cout][cin].  Routes: 1 = fp32; 2 = split (cout % 32 == 0).  Allocates a workspace and frees it.
+ * jn_conv3_bwd_weight: gw [9][cout][cin] += sum over slots and pixels of gz[p][o] * a(x)[p (+) tap][k]; gz [S][N,OH,OW,g_ld],
+ * x [S][N,H,W,x_ld], tab [S][3][cin].  Routes: 1 = split planes with transposed LDS reads (cout % 16 == 0); 2 = split at
+ * the LDS read; 3 = exact fp32 products (what JN_WW_EXACT=1 makes the rule pick).  max_wg: 0 = the launcher's rule, else
+ * the number of workgroups that walk the pixel tiles of one channel block (1: one workgroup walks them all); < 0: JN_EINVAL.
+ * jn_conv3_route: host only, no device call: the route (1..3, as above) the launcher's rule gives the launch.  kind 0 =
+ * jn_conv3 forward, 1 = jn_conv3 transposed, 2 = jn_conv3_bwd_data_s2, 3 = jn_conv3_bwd_weight; (ld_a, ld_b) are the two
+ * leading dimensions in the order of that entry's arguments.  JN_EINVAL as above. */
+int jn_conv3(const void* in_dev, int in_ld, const float* tab_dev, const float* w_dev, void* out_dev, int out_ld, int N, int H,
+             int W, int cin, int cout, int stride, int transposed, int accumulate, double* stats_dev, const int* skip_flag_dev,
+             int skip_when, int n_slots, long long in_slot_stride, long long out_slot_stride, int route, void* stream);
+int jn_conv3_bwd_data_s2(const float* gz_dev, int g_ld, const float* w_dev, float* gin_dev, int gin_ld, int N, int H, int W, int cout,
+                         int cin, int accumulate, int n_slots, int route, void* stream);
+int jn_conv3_bwd_weight(const float* gz_dev, int g_ld, const float* x_dev, int x_ld, const float* tab_dev, float* gw_dev, int N, int H,
+                        int W, int cout, int cin, int stride, int n_slots, int route, int max_wg, void* stream);
+int jn_conv3_route(int kind, int N, int H, int W, int cin, int cout, int stride, int n_slots, int ld_a, int ld_b);
 /* Arms the following rollouts of `ctx` with that teacher (the per-step `best_action` that test_model_on_env compares
  * each chosen action with, src/supervised.py:279-405): before the decision of step t, the set of the state that
  * decision sees (position and visited patches before the step) goes to sets_dev[b * T + t] (uint8 [B,T], T =

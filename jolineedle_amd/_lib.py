@@ -148,6 +148,11 @@ SIGNATURES = {
     "jn_teacher_actions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "jn_teacher_walks": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_uint64, C.c_int] + [C.c_void_p] * 12),
     "jn_pw_bwd_fused": (C.c_int, [C.c_void_p] * 8 + [C.c_int] + [C.c_void_p] * 2 + [C.c_int, C.c_longlong] + [C.c_int] * 4 + [C.c_void_p]),
+    "jn_conv3": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                           C.c_longlong, C.c_longlong, C.c_int, C.c_void_p]),
+    "jn_conv3_bwd_data_s2": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p]),
+    "jn_conv3_bwd_weight": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p]),
+    "jn_conv3_route": (C.c_int, [C.c_int] * 10),
     "jn_set_rollout_teacher":(C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "jn_rollout_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "jn_last_timing": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),

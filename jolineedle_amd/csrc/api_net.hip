@@ -386,7 +386,7 @@ int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int train, 
           const Op& up = net.ops[st.link];
           a.up_out = ptr(up.out); a.up_ld = ld(up.out); up_done[st.link] = 1;
         }
-        lrc = op.kind == OP_PW ? launch_pw(a, s) : op.kind == OP_DW ? launch_dw(a, s) : launch_conv3(a, s);
+        lrc = op.kind == OP_PW ? launch_pw(a, s) : op.kind == OP_DW ? launch_dw(a, s) : launch_conv3(a, s, 0);
         if (!lrc) lrc = finalize(op, cw, st.deferred);
         break;
       }
@@ -693,12 +693,12 @@ int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, hi
         bn_gz(c);
         if ((rc = fork_aux(ws))) return rc;      // the 9-tap weight gradient beside the data gradient
         const int rc3 = st.route == BR_CONV3_S1
-                            ? launch_conv3(gz_conv_args(c), s)
+                            ? launch_conv3(gz_conv_args(c), s, 0)
                             : launch_conv3_bwd_data_s2(c.g, c.g_ld, cw.w_dev, gptr(op.in), ld(op.in), op.in.H, op.in.W, op.out.H,
-                                                       op.out.W, cw.cout, cw.cin, N, op.acc_in ? 1 : 0, s, sb);
+                                                       op.out.W, cw.cout, cw.cin, N, op.acc_in ? 1 : 0, s, sb, 0);
         JN_CHECK(rc3 == 0, JN_ESTATE, "backward of dense 3x3 conv %s: unsupported shape", op.name.c_str());
         JN_CHECK(launch_conv3_bwd_weight(c.g, c.g_ld, ptr(op.in), ld(op.in), tab(op.in), c.gw, op.in.H, op.in.W, op.out.H, op.out.W,
-                                         cw.cout, cw.cin, N, op.stride, ws, sb) == 0,
+                                         cw.cout, cw.cin, N, op.stride, ws, sb, 0, 0) == 0,
                  JN_ESTATE, "launch_conv3_bwd_weight: the LDS of %s was refused", op.name.c_str());
         break;
       }

@@ -1,5 +1,7 @@
 // C ABI of libjnroll.so, stateless wrappers: argument checks around one launch each, no jn_ctx.
 // Host code only (compiled by hipcc as C++); kernels live in kernels_*.hip.
+#include <cstring>
+
 #include "jn_internal.h"
 
 using namespace jnr;
@@ -333,6 +335,148 @@ int jn_pw_bwd_fused(const float* g_dev, const float* z_dev, const float* x_dev, 
   (void)hipFree(ws);
   JN_HIP(e);
   JN_CHECK(rc == 0, JN_EINVAL, "jn_pw_bwd_fused: %d -> %d channels: no fused kernel", cin, cout);
+  return JN_OK;
+}
+
+// ---- dense 3x3 kernels on caller tensors (kernels_conv3.hip) ---------------------------------------------------------
+// What the three entries and jn_conv3_route check of a shape before anything else: H x W is the layer's INPUT map
+static bool conv3_shape_ok(int N, int H, int W, int cin, int cout, int stride, int n_slots, int ld_a, int c_a, int ld_b, int c_b) {
+  return N >= 1 && H >= 1 && W >= 1 && (long long)N * H * W <= (1 << 24) && cin >= 4 && cout >= 4 && cin % 4 == 0 && cout % 4 == 0 &&
+         cin <= 4096 && cout <= 4096 && (stride == 1 || (stride == 2 && H % 2 == 0 && W % 2 == 0)) && n_slots >= 1 && n_slots <= 64 &&
+         ld_a >= c_a && ld_b >= c_b && ld_a % 4 == 0 && ld_b % 4 == 0 && ld_a <= 8192 && ld_b <= 8192;
+}
+
+// the launch of jn_conv3 / jn_conv3_route(kind 0, 1) without its pointers
+static ConvArgs conv3_entry_args(int N, int H, int W, int cin, int cout, int stride, int transposed, int in_ld, int out_ld,
+                                 int n_slots, int dtype) {
+  ConvArgs a{};
+  a.in_ld = in_ld; a.in_dtype = dtype; a.out_ld = out_ld; a.out_dtype = dtype; a.bf16_mfma = dtype == JN_BF16;
+  a.N = N; a.H = H; a.W = W; a.OH = H / stride; a.OW = W / stride; a.cin = cin; a.cout = cout; a.stride = stride; a.act = ACT_NONE;
+  a.w_transposed = transposed ? 1 : 0; a.n_slots = n_slots;
+  return a;
+}
+
+int jn_conv3_route(int kind, int N, int H, int W, int cin, int cout, int stride, int n_slots, int ld_a, int ld_b) {
+  JN_CHECK(kind >= 0 && kind <= 3, JN_EINVAL, "jn_conv3_route: kind=%d", kind);
+  const bool fwd_like = kind <= 1;      // (ld_a, ld_b) = (in_ld, out_ld) of jn_conv3, else (g_ld, gin_ld | x_ld)
+  JN_CHECK(conv3_shape_ok(N, H, W, cin, cout, stride, n_slots, ld_a, fwd_like ? cin : cout, ld_b, fwd_like ? cout : cin) &&
+               (kind != 1 || stride == 1) && (kind != 2 || stride == 2),
+           JN_EINVAL, "jn_conv3_route: kind %d, %d x %d x %d, %d -> %d channels, stride %d, %d slots, leading dimensions %d and %d", kind, N,
+           H, W, cin, cout, stride, n_slots, ld_a, ld_b);
+  int r;
+  if (fwd_like) {
+    ConvArgs a = conv3_entry_args(N, H, W, cin, cout, stride, kind == 1, ld_a, ld_b, n_slots, JN_F32);
+    r = conv3_route(a, 0);
+  } else if (kind == 2) {
+    r = conv3_bwd_data_s2_route(ld_a, ld_b, H / 2, W / 2, cout, cin, N, n_slots, 0);
+  } else {
+    r = conv3_bwd_weight_route(ld_a, ld_b, cout, cin, 0);
+  }
+  JN_CHECK(r > 0, JN_EINVAL, "jn_conv3_route: no dense 3x3 kernel takes this launch");
+  return r;
+}
+
+int jn_conv3(const void* in_dev, int in_ld, const float* tab_dev, const float* w_dev, void* out_dev, int out_ld, int N, int H,
+             int W, int cin, int cout, int stride, int transposed, int accumulate, double* stats_dev, const int* skip_flag_dev,
+             int skip_when, int n_slots, long long in_slot_stride, long long out_slot_stride, int route, void* stream) {
+  JN_CHECK(in_dev && tab_dev && w_dev && out_dev, JN_EINVAL, "jn_conv3: null argument");
+  JN_CHECK(conv3_shape_ok(N, H, W, cin, cout, stride, n_slots, in_ld, cin, out_ld, cout) && (!transposed || stride == 1), JN_EINVAL,
+           "jn_conv3: %d x %d x %d, %d -> %d channels, stride %d, transposed %d, %d slots, leading dimensions %d and %d", N, H, W, cin, cout,
+           stride, transposed, n_slots, in_ld, out_ld);
+  const int OH = H / stride, OW = W / stride;
+  JN_CHECK(route >= 0 && route <= C3_ROUTE_BF16 && in_slot_stride >= 0 && out_slot_stride >= 0 &&
+               (n_slots == 1 || (in_slot_stride >= (long long)N * H * W * in_ld && out_slot_stride >= (long long)N * OH * OW * out_ld &&
+                                 in_slot_stride % 4 == 0 && out_slot_stride % 4 == 0)),
+           JN_EINVAL, "jn_conv3: route=%d, slot strides %lld and %lld", route, in_slot_stride, out_slot_stride);
+  const bool bf16 = route == C3_ROUTE_BF16;
+  JN_CHECK(!bf16 || n_slots == 1, JN_EINVAL, "jn_conv3: the bf16 kernel takes one slot");
+  float* tab = const_cast<float*>(tab_dev);
+  ConvArgs a = conv3_entry_args(N, H, W, cin, cout, stride, transposed, in_ld, out_ld, n_slots, bf16 ? JN_BF16 : JN_F32);
+  a.in = in_dev; a.itab.sc = tab; a.itab.sh = tab + cin; a.itab.fl = tab + 2 * cin; a.w = w_dev; a.out = out_dev;
+  a.accumulate = accumulate ? 1 : 0; a.stats = stats_dev; a.stats_rep_stride = 2LL * cout; a.skip_flag = skip_flag_dev; a.skip_when = skip_when;
+  a.in_slot_stride = in_slot_stride; a.out_slot_stride = out_slot_stride;
+  if (bf16) a.w_bf16 = w_dev;      // stands for the rounded copy made below while the route is checked
+  JN_CHECK(conv3_route(a, route) > 0, JN_EINVAL, "jn_conv3: route %d does not take this launch", route);
+  hipStream_t s = (hipStream_t)stream;
+  uint16_t* wb = nullptr;
+  if (bf16) {      // round to nearest even, as the context does once per dense 3x3 layer in bf16 mode (api_ctx.hip)
+    const size_t n = (size_t)9 * cout * cin;
+    std::vector<float> hw(n);
+    std::vector<uint16_t> hb(n);
+    JN_HIP(hipMemcpy(hw.data(), w_dev, n * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+      uint32_t u;
+      std::memcpy(&u, &hw[i], 4);
+      u += 0x7FFFu + ((u >> 16) & 1u);
+      hb[i] = (uint16_t)(u >> 16);
+    }
+    JN_HIP(hipMalloc((void**)&wb, n * sizeof(uint16_t)));
+    hipError_t e = hipMemcpy(wb, hb.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(wb); JN_HIP(e); }
+    a.w_bf16 = wb;
+  }
+  const int rc = launch_conv3(a, s, route);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (wb) (void)hipFree(wb);
+  JN_HIP(e);
+  JN_CHECK(rc == 0, JN_EINVAL, "jn_conv3: the kernel's LDS was refused");
+  return JN_OK;
+}
+
+// (the kernels step g_z and the input gradient by ONE slot stride, the engine's gradient workspace: the caller's dense tensors are
+// laid into slots [g_z | g_in] and the input gradient copied back, so the call allocates, waits for the stream and frees)
+int jn_conv3_bwd_data_s2(const float* gz_dev, int g_ld, const float* w_dev, float* gin_dev, int gin_ld, int N, int H, int W, int cout,
+                         int cin, int accumulate, int n_slots, int route, void* stream) {
+  JN_CHECK(gz_dev && w_dev && gin_dev, JN_EINVAL, "jn_conv3_bwd_data_s2: null argument");
+  JN_CHECK(conv3_shape_ok(N, H, W, cin, cout, 2, n_slots, g_ld, cout, gin_ld, cin), JN_EINVAL,
+           "jn_conv3_bwd_data_s2: %d x %d x %d, %d -> %d channels, %d slots, leading dimensions %d and %d", N, H, W, cin, cout, n_slots, g_ld,
+           gin_ld);
+  const int OH = H / 2, OW = W / 2;
+  JN_CHECK(route >= 0 && route <= C3_ROUTE_X3 && conv3_bwd_data_s2_route(g_ld, gin_ld, OH, OW, cout, cin, N, n_slots, route) > 0, JN_EINVAL,
+           "jn_conv3_bwd_data_s2: route %d does not take this launch", route);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t gn = (size_t)N * OH * OW * g_ld, xn = (size_t)N * H * W * gin_ld, slot = gn + xn;
+  float* ws = nullptr;
+  JN_HIP(hipMalloc((void**)&ws, (size_t)n_slots * slot * sizeof(float)));
+  hipError_t e = hipMemcpy2DAsync(ws, slot * sizeof(float), gz_dev, gn * sizeof(float), gn * sizeof(float), n_slots, hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess)      // always: the channels past cin and, with accumulate, the previous gradient come back as they were
+    e = hipMemcpy2DAsync(ws + gn, slot * sizeof(float), gin_dev, xn * sizeof(float), xn * sizeof(float), n_slots, hipMemcpyDeviceToDevice, s);
+  int rc = -1;
+  if (e == hipSuccess) {
+    SlotBatch sb;
+    sb.n = n_slots; sb.grad = (long long)slot;
+    rc = launch_conv3_bwd_data_s2(ws, g_ld, w_dev, ws + gn, gin_ld, H, W, OH, OW, cout, cin, N, accumulate ? 1 : 0, s, sb, route);
+    e = hipGetLastError();
+    if (e == hipSuccess)
+      e = hipMemcpy2DAsync(gin_dev, xn * sizeof(float), ws + gn, slot * sizeof(float), xn * sizeof(float), n_slots, hipMemcpyDeviceToDevice, s);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(ws);
+  JN_HIP(e);
+  JN_CHECK(rc == 0, JN_EINVAL, "jn_conv3_bwd_data_s2: the kernel's LDS was refused");
+  return JN_OK;
+}
+
+int jn_conv3_bwd_weight(const float* gz_dev, int g_ld, const float* x_dev, int x_ld, const float* tab_dev, float* gw_dev, int N, int H,
+                        int W, int cout, int cin, int stride, int n_slots, int route, int max_wg, void* stream) {
+  JN_CHECK(gz_dev && x_dev && tab_dev && gw_dev, JN_EINVAL, "jn_conv3_bwd_weight: null argument");
+  JN_CHECK(conv3_shape_ok(N, H, W, cin, cout, stride, n_slots, g_ld, cout, x_ld, cin), JN_EINVAL,
+           "jn_conv3_bwd_weight: %d x %d x %d, %d -> %d channels, stride %d, %d slots, leading dimensions %d and %d", N, H, W, cin, cout,
+           stride, n_slots, g_ld, x_ld);
+  JN_CHECK(route >= 0 && route <= CW_ROUTE_EXACT && max_wg >= 0 && conv3_bwd_weight_route(g_ld, x_ld, cout, cin, route) > 0, JN_EINVAL,
+           "jn_conv3_bwd_weight: route=%d max_wg=%d does not take this launch", route, max_wg);
+  const int OH = H / stride, OW = W / stride;
+  hipStream_t s = (hipStream_t)stream;
+  float* tab = const_cast<float*>(tab_dev);
+  ChanTab it{};
+  it.sc = tab; it.sh = tab + cin; it.fl = tab + 2 * cin;
+  SlotBatch sb;      // the caller's [S, ...] tensors are slots already: g_z, x and the [3][cin] tables each by their own size
+  sb.n = n_slots; sb.grad = (long long)N * OH * OW * g_ld; sb.act = (long long)N * H * W * x_ld; sb.tab = 3LL * cin;
+  const int rc = launch_conv3_bwd_weight(gz_dev, g_ld, x_dev, x_ld, it, gw_dev, H, W, OH, OW, cout, cin, N, stride, s, sb, route, max_wg);
+  JN_HIP(hipGetLastError());
+  JN_HIP(hipStreamSynchronize(s));
+  JN_CHECK(rc == 0, JN_EINVAL, "jn_conv3_bwd_weight: the kernel's LDS was refused");
   return JN_OK;
 }
 

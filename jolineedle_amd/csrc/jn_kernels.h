@@ -219,12 +219,20 @@ int launch_efpn_linear(const float* e, const float* wt, float* part, int N, int 
                        const int* skip_flag, int skip_when, hipStream_t s);
 
 // ---- dense 3x3 conv (kernels_conv3.hip) ---------------------------------------------------------
-int launch_conv3(const ConvArgs& a, hipStream_t s);     // w_transposed: data gradient of a stride-1 layer
+// Every launcher takes a route: 0 = its own rule (what the networks pass), else that kernel family, for the per-kernel
+// tests (jn_conv3* in api_ops.hip).  The *_route functions are pure host code: the route a launch gets (forced = 0), or
+// `forced` itself where the launch meets that route's preconditions; -1: refused.  The launchers return -1 likewise.
+enum Conv3Route { C3_ROUTE_F32 = 1, C3_ROUTE_X3 = 2, C3_ROUTE_BF16 = 3 };      // conv3_mfma; conv3_x3 / conv3_x3s2 / conv3_x3_bwd_data_s2; conv3_bf16
+enum Conv3WRoute { CW_ROUTE_TR = 1, CW_ROUTE_SPLIT = 2, CW_ROUTE_EXACT = 3 };  // conv3_bwd_weight_tr; conv3_bwd_weight<SP = true / false>
+int conv3_route(const ConvArgs& a, int forced);
+int launch_conv3(const ConvArgs& a, hipStream_t s, int route);     // w_transposed: data gradient of a stride-1 layer
+int conv3_bwd_data_s2_route(int g_ld, int gin_ld, int OH, int OW, int Co, int Ci, int N, int n_slots, int forced);
 int launch_conv3_bwd_data_s2(const float* gz, int g_ld, const float* w, float* gin, int gin_ld, int H, int W, int OH,
-                             int OW, int Co, int Ci, int N, int accumulate, hipStream_t s,
-                             const SlotBatch& sb = SlotBatch{});
+                             int OW, int Co, int Ci, int N, int accumulate, hipStream_t s, const SlotBatch& sb, int route);
+int conv3_bwd_weight_route(int g_ld, int x_ld, int Co, int Ci, int forced);
+// max_wg: 0 = the rule (2048 / (channel blocks x slots)), else the x extent of the persistent grid (1: one workgroup walks every pixel tile)
 int launch_conv3_bwd_weight(const float* gz, int g_ld, const float* x, int x_ld, ChanTab it, float* gw, int H, int W, int OH,
-                            int OW, int Co, int Ci, int N, int stride, hipStream_t s, const SlotBatch& sb = SlotBatch{});
+                            int OW, int Co, int Ci, int N, int stride, hipStream_t s, const SlotBatch& sb, int route, int max_wg);
 // ---- detector (kernels_det.hip) --------------------------------------------------------------
 int launch_head_pred(const void* reg, int reg_ld, ChanTab rt, const void* cls, int cls_ld, ChanTab ct, int dtype,
                      const float* wp, const float* bp, float* raw, int hid, int Hl, int Wl, int stride, int A, int a0,

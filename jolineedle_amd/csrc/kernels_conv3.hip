@@ -654,22 +654,26 @@ static int launch_conv3_x3s2(const ConvArgs& a, hipStream_t s) {
 }
 
 // fp32 activations, K a multiple of 32 (every dense 3x3 layer of yolox-s / -m / -l), stride 1 (forward and, with the weight
-// transposed, data gradient): 8 x 16 fp32 tiles, two workgroups per CU, against 16 x 16 x3 tiles
+// transposed, data gradient): what conv3_x3_kernel itself needs of a launch ...
+static bool conv3_x3_admits(const ConvArgs& a) {
+  return a.stride == 1 && a.in_dtype == JN_F32 && a.out_dtype == JN_F32 && a.cin % 32 == 0 && a.cout % 4 == 0 && a.in_ld % 4 == 0 &&
+         a.out_ld % 4 == 0 && !a.bias && a.act == ACT_NONE;
+}
+// ... and whether the launch rule gives it the launch: 8 x 16 fp32 tiles, two workgroups per CU, against 16 x 16 x3 tiles
 static bool conv3_x3_ok(const ConvArgs& a) {
-  if (conv3_x3_off() || a.stride != 1 || a.in_dtype != JN_F32 || a.out_dtype != JN_F32 || a.cin % 32 || a.cout % 4 ||
-      a.in_ld % 4 || a.out_ld % 4 || a.bias || a.act != ACT_NONE)
-    return false;
+  if (conv3_x3_off() || !conv3_x3_admits(a)) return false;
   const long long slots = a.n_slots > 1 ? a.n_slots : 1, nbo = (a.cout + C3_BN - 1) / C3_BN, tx = (a.OW + C3_TW - 1) / C3_TW;
   return x3_cheaper(tx * ((a.OH + 7) / 8) * a.N * nbo * slots, 512, 1.0, tx * ((a.OH + 15) / 16) * a.N * nbo * slots);
 }
 
-// stride 2 forward on the parity-class kernel: an fp32 workgroup is 4 rows, two per CU: a round of 512 of them covers what
-// 128 x3 workgroups cover
+// stride 2 forward on the parity-class kernel (no accumulate, no slots, no transposed weight) ...
+static bool conv3_x3s2_admits(const ConvArgs& a) {
+  return a.stride == 2 && a.in_dtype == JN_F32 && a.out_dtype == JN_F32 && a.cin % 32 == 0 && a.cout % 4 == 0 && a.in_ld % 4 == 0 &&
+         a.out_ld % 4 == 0 && !a.bias && a.act == ACT_NONE && !a.accumulate && a.n_slots <= 1 && !a.w_transposed;
+}
+// ... an fp32 workgroup is 4 rows, two per CU: a round of 512 of them covers what 128 x3 workgroups cover
 static bool conv3_x3s2_ok(const ConvArgs& a) {
-  if (conv3_x3_off() || a.stride != 2 || a.in_dtype != JN_F32 || a.out_dtype != JN_F32 ||
-      a.cin % 32 || a.cout % 4 || a.in_ld % 4 || a.out_ld % 4 || a.bias || a.act != ACT_NONE || a.accumulate || a.n_slots > 1 ||
-      a.w_transposed)
-    return false;
+  if (conv3_x3_off() || !conv3_x3s2_admits(a)) return false;
   const long long nbo = (a.cout + C3_BN - 1) / C3_BN, tx = (a.OW + C3_TW - 1) / C3_TW;
   return x3_cheaper(tx * ((a.OH + 3) / 4) * a.N * nbo, 512, 0.5, tx * ((a.OH + 15) / 16) * a.N * nbo);
 }
@@ -691,17 +695,39 @@ static int launch_conv3_t(const ConvArgs& a, hipStream_t s) {
   return 0;
 }
 
-int launch_conv3(const ConvArgs& a, hipStream_t s) {
-  if (a.w_transposed) {               // data gradient of a stride-1 layer (fp32 gradient buffers)
-    if (a.stride != 1 || a.in_dtype != JN_F32 || a.cin % 4) return -1;
-    return conv3_x3_ok(a) ? launch_conv3_x3<1, true, 2, 8>(a, s) : launch_conv3_t<1, float, true>(a, s);
+static bool conv3_bf16_admits(const ConvArgs& a) {
+  return !a.w_transposed && a.w_bf16 && a.in_dtype == JN_BF16 && a.out_dtype == JN_BF16 && !a.stats && !a.accumulate && a.cin % 8 == 0;
+}
+
+// THE route of a launch.  forced == 0: the launch rule; else that route, where the launch meets the route's own
+// preconditions (the rule's cost comparison and JN_NO_CONV3_X3 are not among them).  -1: refused.
+int conv3_route(const ConvArgs& a, int forced) {
+  if (a.w_transposed && (a.stride != 1 || a.in_dtype != JN_F32 || a.cin % 4)) return -1;      // data gradient of a stride-1 layer (fp32 gradient buffers)
+  switch (forced) {
+    case 0: break;
+    case C3_ROUTE_F32: return C3_ROUTE_F32;
+    case C3_ROUTE_X3: return (a.stride == 1 ? conv3_x3_admits(a) : conv3_x3s2_admits(a)) ? C3_ROUTE_X3 : -1;
+    case C3_ROUTE_BF16: return conv3_bf16_admits(a) ? C3_ROUTE_BF16 : -1;
+    default: return -1;
   }
-  if (a.w_bf16 && a.in_dtype == JN_BF16 && a.out_dtype == JN_BF16 && !a.stats && !a.accumulate && a.cin % 8 == 0)
-    return a.stride == 1 ? launch_conv3_bf16<1>(a, s) : launch_conv3_bf16<2>(a, s);
-  if (a.in_dtype == JN_BF16) return a.stride == 1 ? launch_conv3_t<1, bf16_t, false>(a, s) : launch_conv3_t<2, bf16_t, false>(a, s);
-  if (conv3_x3_ok(a)) return launch_conv3_x3<1, false, 2, 8>(a, s);
-  if (conv3_x3s2_ok(a)) return launch_conv3_x3s2(a, s);
-  return a.stride == 1 ? launch_conv3_t<1, float, false>(a, s) : launch_conv3_t<2, float, false>(a, s);
+  if (a.w_transposed) return conv3_x3_ok(a) ? C3_ROUTE_X3 : C3_ROUTE_F32;
+  if (conv3_bf16_admits(a)) return C3_ROUTE_BF16;
+  if (a.in_dtype == JN_BF16) return C3_ROUTE_F32;
+  return conv3_x3_ok(a) || conv3_x3s2_ok(a) ? C3_ROUTE_X3 : C3_ROUTE_F32;
+}
+
+int launch_conv3(const ConvArgs& a, hipStream_t s, int route) {
+  switch (conv3_route(a, route)) {
+    case C3_ROUTE_BF16: return a.stride == 1 ? launch_conv3_bf16<1>(a, s) : launch_conv3_bf16<2>(a, s);
+    case C3_ROUTE_X3:
+      if (a.w_transposed) return launch_conv3_x3<1, true, 2, 8>(a, s);
+      return a.stride == 1 ? launch_conv3_x3<1, false, 2, 8>(a, s) : launch_conv3_x3s2(a, s);
+    case C3_ROUTE_F32:
+      if (a.w_transposed) return launch_conv3_t<1, float, true>(a, s);
+      if (a.in_dtype == JN_BF16) return a.stride == 1 ? launch_conv3_t<1, bf16_t, false>(a, s) : launch_conv3_t<2, bf16_t, false>(a, s);
+      return a.stride == 1 ? launch_conv3_t<1, float, false>(a, s) : launch_conv3_t<2, float, false>(a, s);
+    default: return -1;
+  }
 }
 
 // ---- data gradient of a stride-2 dense 3x3 layer -------------------------------------------------------
@@ -914,24 +940,35 @@ __global__ __launch_bounds__(64 * NW) void conv3_x3_bwd_data_s2_kernel(const flo
   }
 }
 
-int launch_conv3_bwd_data_s2(const float* gz, int g_ld, const float* w, float* gin, int gin_ld, int H, int W, int OH,
-                             int OW, int Co, int Ci, int N, int accumulate, hipStream_t s, const SlotBatch& sb) {
+// The route of a stride-2 data gradient, as conv3_route.  bf16 matrix pipe (three-way split operands): whole 16 x 16 class
+// tiles on a CU of their own against the fp32 kernel's 8 x 16 tiles, two per CU — chosen like the forward routes (x3_cheaper)
+int conv3_bwd_data_s2_route(int g_ld, int gin_ld, int OH, int OW, int Co, int Ci, int N, int n_slots, int forced) {
   if (Co % 4 || Ci % 4) return -1;
-  // bf16 matrix pipe (three-way split operands): whole 16 x 16 class tiles on a CU of their own against the fp32 kernel's
-  // 8 x 16 tiles, two per CU — chosen like the forward routes (x3_cheaper)
-  if (!conv3_x3_off() && Co % 32 == 0 && g_ld % 4 == 0 && gin_ld % 4 == 0) {
+  const bool x3_admits = Co % 32 == 0 && g_ld % 4 == 0 && gin_ld % 4 == 0;
+  if (forced) return forced == C3_ROUTE_F32 || (forced == C3_ROUTE_X3 && x3_admits) ? forced : -1;
+  if (!conv3_x3_off() && x3_admits) {
+    const int txs = (OW + C3_TW - 1) / C3_TW, tys = (OH + 15) / 16;
+    const long long nbi = (Ci + C3_BN - 1) / C3_BN;
+    const long long wg_x3 = (long long)txs * tys * N * nbi * 4 * n_slots, wg_f32 = (long long)txs * ((OH + C3_TH - 1) / C3_TH) * N * nbi * 4 * n_slots;
+    if (x3_cheaper(wg_f32, 512, 1.0, wg_x3)) return C3_ROUTE_X3;
+  }
+  return C3_ROUTE_F32;
+}
+
+int launch_conv3_bwd_data_s2(const float* gz, int g_ld, const float* w, float* gin, int gin_ld, int H, int W, int OH,
+                             int OW, int Co, int Ci, int N, int accumulate, hipStream_t s, const SlotBatch& sb, int route) {
+  const int r = conv3_bwd_data_s2_route(g_ld, gin_ld, OH, OW, Co, Ci, N, sb.n, route);
+  if (r < 0) return -1;
+  if (r == C3_ROUTE_X3) {
     constexpr int PR = 2, NW = 8, TH = PR * NW;
     const int txs = (OW + C3_TW - 1) / C3_TW, tys = (OH + TH - 1) / TH;
     const long long nbi = (Ci + C3_BN - 1) / C3_BN;
-    const long long wg_x3 = (long long)txs * tys * N * nbi * 4 * sb.n, wg_f32 = (long long)txs * ((OH + C3_TH - 1) / C3_TH) * N * nbi * 4 * sb.n;
-    if (x3_cheaper(wg_f32, 512, 1.0, wg_x3)) {
-      constexpr size_t smem = x3_lds_bytes((TH + 1) * (C3_TW + 1), 2, 0);
-      if (!allow_lds<&conv3_x3_bwd_data_s2_kernel<PR, NW>>(smem)) return -1;
-      dim3 grid((unsigned)(txs * tys * N), (unsigned)nbi, 4 * sb.n);
-      hipLaunchKernelGGL((conv3_x3_bwd_data_s2_kernel<PR, NW>), grid, dim3(64 * NW), smem, s, gz, g_ld, w, gin, gin_ld, H, W, OH, OW,
-                         Co, Ci, txs, tys, accumulate, sb.grad);
-      return 0;
-    }
+    constexpr size_t smem = x3_lds_bytes((TH + 1) * (C3_TW + 1), 2, 0);
+    if (!allow_lds<&conv3_x3_bwd_data_s2_kernel<PR, NW>>(smem)) return -1;
+    dim3 grid((unsigned)(txs * tys * N), (unsigned)nbi, 4 * sb.n);
+    hipLaunchKernelGGL((conv3_x3_bwd_data_s2_kernel<PR, NW>), grid, dim3(64 * NW), smem, s, gz, g_ld, w, gin, gin_ld, H, W, OH, OW,
+                       Co, Ci, txs, tys, accumulate, sb.grad);
+    return 0;
   }
   const int tiles_x = (OW + C3_TW - 1) / C3_TW, tiles_y = (OH + C3_TH - 1) / C3_TH;
   dim3 grid(tiles_x * tiles_y * N, (Ci + C3_BN - 1) / C3_BN, 4 * sb.n);
@@ -1237,25 +1274,31 @@ static int launch_cw(const Conv3WLaunch& a, hipStream_t s) {
   return 0;
 }
 
-template <int S>
-static int launch_cw(const Conv3WLaunch& a, bool exact, hipStream_t s) {
-  return exact ? launch_cw<S, false>(a, s) : launch_cw<S, true>(a, s);
+// The route of a weight gradient, as conv3_route: the transposed-read kernel wherever its loads fit, else the split form
+// of conv3_bwd_weight_kernel; JN_WW_EXACT=1 (read once) keeps that kernel's exact fp32 products
+int conv3_bwd_weight_route(int g_ld, int x_ld, int Co, int Ci, int forced) {
+  const bool tr_admits = Co % 16 == 0 && Ci % 4 == 0 && g_ld % 4 == 0 && x_ld % 4 == 0;
+  if (forced) return forced == CW_ROUTE_SPLIT || forced == CW_ROUTE_EXACT || (forced == CW_ROUTE_TR && tr_admits) ? forced : -1;
+  static const bool exact = std::getenv("JN_WW_EXACT") != nullptr;
+  return exact ? CW_ROUTE_EXACT : tr_admits ? CW_ROUTE_TR : CW_ROUTE_SPLIT;
 }
 
 int launch_conv3_bwd_weight(const float* gz, int g_ld, const float* x, int x_ld, ChanTab it, float* gw, int H, int W, int OH,
-                            int OW, int Co, int Ci, int N, int stride, hipStream_t s, const SlotBatch& sb) {
+                            int OW, int Co, int Ci, int N, int stride, hipStream_t s, const SlotBatch& sb, int route, int max_wg) {
   const int TH = 4;
   const int tiles_x = (OW + C3_TW - 1) / C3_TW, tiles_y = (OH + TH - 1) / TH, n_tiles = tiles_x * tiles_y * N;
   const int nbo = (Co + CW_BO - 1) / CW_BO, nbk = (Ci + CW_BK - 1) / CW_BK;
-  long long gx = 2048 / ((long long)nbo * nbk * sb.n);      // persistent workgroups over the pixel tiles
+  long long gx = max_wg > 0 ? max_wg : 2048 / ((long long)nbo * nbk * sb.n);      // persistent workgroups over the pixel tiles
   if (gx < 1) gx = 1;
   if (gx > n_tiles) gx = n_tiles;
   const Conv3WLaunch a = {dim3((unsigned)gx, nbo, nbk * sb.n), gz, g_ld, x, x_ld, it, gw, H, W, OH, OW, Co, Ci,
                           tiles_x, tiles_y, n_tiles, sb};
-  static const bool exact = std::getenv("JN_WW_EXACT") != nullptr;
-  if (!exact && Co % 16 == 0 && Ci % 4 == 0 && g_ld % 4 == 0 && x_ld % 4 == 0)
-    return stride == 1 ? launch_cw_tr<1>(a, s) : launch_cw_tr<2>(a, s);
-  return stride == 1 ? launch_cw<1>(a, exact, s) : launch_cw<2>(a, exact, s);
+  switch (conv3_bwd_weight_route(g_ld, x_ld, Co, Ci, route)) {
+    case CW_ROUTE_TR: return stride == 1 ? launch_cw_tr<1>(a, s) : launch_cw_tr<2>(a, s);
+    case CW_ROUTE_SPLIT: return stride == 1 ? launch_cw<1, true>(a, s) : launch_cw<2, true>(a, s);
+    case CW_ROUTE_EXACT: return stride == 1 ? launch_cw<1, false>(a, s) : launch_cw<2, false>(a, s);
+    default: return -1;
+  }
 }
 
 }  // namespace jnr

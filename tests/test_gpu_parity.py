@@ -198,6 +198,15 @@ def test_nano_backbone_backward_vs_autograd(P, N, bb):
             assert torch.allclose(got2[k], 2 * got[k], rtol=1e-3, atol=1e-3 * got[k].abs().max().item())
 
 
+def test_yolox_s_backbone_backward_on_the_fp32_dense_3x3_routes(monkeypatch):
+    """The same backward with JN_NO_CONV3_X3=1 (read per launch): at test sizes the launch rule gives every stride-1 and
+    stride-2 data gradient the split kernels, so the engine's wiring of conv3_mfma_kernel<1, float, true> and
+    conv3_bwd_data_s2_kernel — the routes of real config-5 batches — otherwise never runs in a backward.  Same assertions.
+    (The kernels themselves: tests/test_gpu_conv3_kernels.py.)"""
+    monkeypatch.setenv("JN_NO_CONV3_X3", "1")
+    test_nano_backbone_backward_vs_autograd(64, 3, "yolox-s")
+
+
 def test_wide_data_gradient_on_the_bf16_pipe_matches_the_fp32_pipe(monkeypatch):
     """The data gradient of the wide 1x1 layers (256 / 512 channels: dark5, lateral_conv0, C3_p4 / C3_n4) runs on pw_x3_kernel
     (three bf16 planes per operand, transposed split weight) since round 4: every gradient of the encoder must stay where the
