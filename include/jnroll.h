@@ -734,6 +734,20 @@ int jn_conv3_route(int kind, int N, int H, int W, int cin, int cout, int stride,
  * ragged extent must be 0).  Both buffers are the caller's and must outlive the rollouts.  sets_dev = NULL disarms.
  * Independent of jn_set_rollout_positions. */
 int jn_set_rollout_teacher(jn_ctx* ctx, const uint8_t* targets_dev, uint8_t* sets_dev);
+/* Names the random stream of every agent of the following rollouts of `ctx`.  keys_host: uint64 [n][2] = (stream seed,
+ * stream index) in HOST memory, read before the call returns (the context keeps its own copy and uploads it on the
+ * stream of the next rollout that needs it).  While armed, the two sampled draws of agent b ignore the rollout's `seed`
+ * argument and its index in the batch: the action of step t (JN_MODE_SAMPLE) is drawn from
+ * Philox4x32-10(key = keys[b][0], counter = ((uint32) keys[b][1], t, 0x53414d50, 0)) and, without start_positions, the
+ * reset position from Philox4x32-10(keys[b][0], ((uint32) keys[b][1], 0, 0x52455345, 0)) modulo the agent's own grid
+ * extent — so keys (seed, b) reproduce the unarmed rollout of `seed`, and an agent keeps its walk wherever it sits in
+ * whichever batch.  Greedy and forced actions, and the train-mode dropout masks (keyed by the batch index), are not
+ * affected.  keys_host = NULL disarms (n is ignored); disarmed, every draw is what it was without this call.  Sticky
+ * until set again.  While armed, jn_rollout, jn_reinforce_forward and jn_reinforce_step fail with JN_EINVAL before any
+ * launch when the env's B != n.  Every check comes before any device call (the one such call: a new table waits for
+ * the upload of the previous one).  JN_EINVAL: a null ctx, n < 1 with a table, a stream index >= 2^32
+ * (the armed keys are then left as they were). */
+int jn_set_rollout_keys(jn_ctx* ctx, const uint64_t* keys_host, int n);
 /* Number of steps S the last rollout executed (reference tensor width).  Synchronises
  * on `stream`. */
 int jn_rollout_steps(jn_ctx* ctx, int* n_steps, void* stream);

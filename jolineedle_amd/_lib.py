@@ -154,6 +154,7 @@ SIGNATURES = {
     "jn_conv3_bwd_weight": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p]),
     "jn_conv3_route": (C.c_int, [C.c_int] * 10),
     "jn_set_rollout_teacher":(C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "jn_set_rollout_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "jn_rollout_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "jn_last_timing": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "jn_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),

@@ -115,7 +115,7 @@ static int env_init_impl(jn_ctx* ctx, const void* images_dev, int images_u8, con
   e.B = B; e.H = H; e.W = W; e.nb = nb; e.Gh = Gh; e.Gw = Gw; e.T = max_ep_len;
   e.stop = stop_enabled ? 1 : 0;
   launch_bbox_masks(bboxes_dev, e.bbox_masks, e.n_bbox_tiles, B, nb, H, W, P, s, e.ragged ? e.extent : nullptr);
-  launch_env_reset(env_ptrs(ctx), nullptr, 0, s);   // zeroed state at (0,0)-independent start; reset() follows
+  launch_env_reset(env_ptrs(ctx), nullptr, 0, nullptr, s);   // zeroed state at (0,0)-independent start; reset() follows
   JN_HIP(hipGetLastError());
   e.ready = true;
   return JN_OK;
@@ -184,7 +184,7 @@ int jn_env_init_ragged(jn_ctx* ctx, const jn_image_view* views_host, const int32
 int jn_env_reset(jn_ctx* ctx, const int64_t* positions_dev, uint64_t seed, void* stream) {
   JN_CHECK(ctx && ctx->env.ready, JN_ESTATE, "jn_env_init has not been called");
   JN_HIP(hipSetDevice(ctx->cfg.device));
-  launch_env_reset(env_ptrs(ctx), positions_dev, seed, (hipStream_t)stream);
+  launch_env_reset(env_ptrs(ctx), positions_dev, seed, nullptr, (hipStream_t)stream);
   JN_HIP(hipGetLastError());
   return JN_OK;
 }

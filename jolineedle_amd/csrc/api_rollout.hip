@@ -44,6 +44,9 @@ int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const
   JN_CHECK(out->rewards_dev && out->masks_dev, JN_EINVAL, "rewards_dev and masks_dev are required outputs");
   JN_CHECK(!do_detection || (ctx->has_net[JN_NET_DETECTOR] && out->det_boxes_dev && out->det_counts_dev), JN_EINVAL,
            "do_detection needs a detector and det_boxes_dev / det_counts_dev outputs");
+  const int n_keys = (int)(ctx->keys_host.size() / 2);
+  JN_CHECK(n_keys == 0 || n_keys == ctx->env.B, JN_EINVAL,
+           "jn_set_rollout_keys armed %d agent streams, the env has %d agents", n_keys, ctx->env.B);
   JN_HIP(hipSetDevice(ctx->cfg.device));
   hipStream_t s = (hipStream_t)stream;
   const jn_config& c = ctx->cfg;
@@ -66,9 +69,27 @@ int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const
                    out->logit_masks_dev, out->positions_dev, out->actions_dev, out->logits_dev, out->final_emb_dev};
   { int rz = zero_rollout_outputs(r, tsets, B, T, C, nA, s); if (rz) return rz; }
 
+  // per-agent streams: the context's copy goes up on this rollout's stream, an event behind it for the setter
+  const uint64_t* keys = nullptr;
+  if (n_keys) {
+    if (ctx->keys_dev_cap < (size_t)n_keys) {
+      int rk = dev_alloc(ctx, &ctx->keys_dev, (size_t)std::max(c.max_batch, n_keys) * 2);
+      if (rk) return rk;
+      ctx->keys_dev_cap = (size_t)std::max(c.max_batch, n_keys);
+      ctx->keys_dirty = true;
+    }
+    if (ctx->keys_dirty) {
+      if (!ctx->keys_ev) JN_HIP(hipEventCreateWithFlags(&ctx->keys_ev, hipEventDisableTiming));
+      JN_HIP(hipMemcpyAsync(ctx->keys_dev, ctx->keys_host.data(), (size_t)n_keys * 2 * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+      JN_HIP(hipEventRecord(ctx->keys_ev, s));
+      ctx->keys_dirty = false;
+    }
+    keys = ctx->keys_dev;
+  }
+
   if (ctx->ev[0]) JN_HIP(hipEventRecord(ctx->ev[0], s));
   EnvPtrs ep = env_ptrs(ctx);
-  launch_env_reset(ep, start_positions_dev, seed, s);
+  launch_env_reset(ep, start_positions_dev, seed, keys, s);
   launch_rollout_begin(ep, r, ctx->prev_action, ctx->cache_len, ctx->n_done, s);
   const long long patch_stride = (long long)(T + 1) * 3 * P * P;
   if (out->patches_dev)
@@ -169,7 +190,7 @@ int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const
     GptStepArgs a{};
     fill_gpt_weights(ctx, a);
     a.B = B; a.T = T;
-    a.step = t; a.mode = mode; a.forced = forced_actions_dev; a.seed = seed;
+    a.step = t; a.mode = mode; a.forced = forced_actions_dev; a.seed = seed; a.keys = keys;
     // recurrent: every new token at 1-D position 0 (gpt.py:431-449); by token: position t, the last row of the
     // reference's full-prefix forward (gpt.py:331-354, 427-428)
     a.src_mode = GPT_SRC_ENV; a.pos_index = by_token ? t : 0; a.emb_stride = T + 1;
@@ -246,6 +267,24 @@ int jn_set_rollout_teacher(jn_ctx* ctx, const uint8_t* targets_dev, uint8_t* set
   JN_CHECK(ctx, JN_EINVAL, "null ctx");
   ctx->teacher_sets = sets_dev;
   ctx->teacher_targets = sets_dev ? targets_dev : nullptr;
+  return JN_OK;
+}
+
+int jn_set_rollout_keys(jn_ctx* ctx, const uint64_t* keys_host, int n) {
+  JN_CHECK(ctx, JN_EINVAL, "jn_set_rollout_keys: null ctx");
+  if (!keys_host) {
+    ctx->keys_host.clear();
+    return JN_OK;
+  }
+  JN_CHECK(n >= 1, JN_EINVAL, "jn_set_rollout_keys: n = %d with a table", n);
+  for (int b = 0; b < n; ++b)
+    JN_CHECK(keys_host[2 * b + 1] <= 0xFFFFFFFFull, JN_EINVAL,
+             "jn_set_rollout_keys: the stream index of agent %d, %llu, does not fit 32 bits", b,
+             (unsigned long long)keys_host[2 * b + 1]);
+  // (an upload of the previous table may still be reading the copy; no event exists before the first armed rollout)
+  if (ctx->keys_ev) JN_HIP(hipEventSynchronize(ctx->keys_ev));
+  ctx->keys_host.assign(keys_host, keys_host + (size_t)n * 2);
+  ctx->keys_dirty = true;
   return JN_OK;
 }
 

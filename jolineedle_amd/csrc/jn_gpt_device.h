@@ -142,7 +142,10 @@ __device__ inline void gpt_decide_and_step(const GptStepArgs& a, int b, const fl
     act = (int)a.forced[(long long)b * a.T + t];
     act = min(max(act, 0), nA - 1);
   } else if (a.mode == JN_MODE_SAMPLE) {
-    const uint4 r = philox4x32(a.seed, (uint32_t)b, (uint32_t)t, 0x53414d50u, 0u);      // keyed (seed, agent, step, "SAMP")
+    // keyed (seed, agent, step, "SAMP"); with jn_set_rollout_keys the agent's own (stream seed, stream index) instead
+    const uint64_t key = a.keys ? a.keys[2 * b] : a.seed;
+    const uint32_t idx = a.keys ? (uint32_t)a.keys[2 * b + 1] : (uint32_t)b;
+    const uint4 r = philox4x32(key, idx, (uint32_t)t, 0x53414d50u, 0u);
     const float u = u01(r.x);
     float cdf = 0.0f;
     act = nA - 1;

@@ -310,6 +310,11 @@ struct jn_ctx {
   bool det_loss_all = false;      // jn_set_det_loss_boxes: targets wider than 8 rows go to launch_yolox_loss_wide
   // jn_set_rollout_teacher: armed while teacher_sets is set; caller-owned [B,T] bytes and [B,Gh,Gw] grid (null = bbox_masks)
   uint8_t* teacher_sets = nullptr; const uint8_t* teacher_targets = nullptr;
+  // jn_set_rollout_keys: armed while keys_host is not empty; the context's own copy of the [n][2] table, uploaded to
+  // keys_dev (keys_dev_cap rows) on the stream of the next rollout when keys_dirty; keys_ev sits behind that upload (the
+  // setter waits for it before it rewrites the copy)
+  std::vector<uint64_t> keys_host; uint64_t* keys_dev = nullptr; size_t keys_dev_cap = 0; bool keys_dirty = false;
+  hipEvent_t keys_ev = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   bool profiling = false;
   bool bwd_timed = false;         // ev[2] / ev[3] bracket a conv-stack backward

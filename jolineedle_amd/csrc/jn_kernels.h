@@ -381,7 +381,7 @@ struct EnvPtrs {
   // leave; null = every agent walks the whole canvas.  The state arrays stay canvas-strided either way.
   const int32_t* extent;
 };
-int launch_env_reset(const EnvPtrs& e, const int64_t* start_positions, uint64_t seed, hipStream_t s);
+int launch_env_reset(const EnvPtrs& e, const int64_t* start_positions, uint64_t seed, const uint64_t* keys, hipStream_t s);
 int launch_env_step(const EnvPtrs& e, const int64_t* actions, float* rewards, uint8_t* terminated,
                     uint8_t* truncated, hipStream_t s);
 
@@ -471,6 +471,7 @@ struct GptStepArgs {
   int emb_stride;                   // tokens per agent in out.final_emb
   float* logits_rows; int logits_stride;   // teacher/given modes: logits of this token -> row b
   int mode; const int64_t* forced; uint64_t seed;
+  const uint64_t* keys;             // [B][2] = (stream seed, stream index) of every agent's sampled draws, or null = (seed, b)
   EnvPtrs env;
   RolloutBuffers out;
   int32_t* n_done;                  // [T+1]

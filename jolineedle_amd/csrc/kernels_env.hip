@@ -261,14 +261,17 @@ int launch_detection_cells(const int64_t* bboxes, const int32_t* extents, int B,
   return 0;
 }
 
-// reset (src/env/general_env.py:144-170): zero state, place agents, mark the start tile.
-__global__ void env_reset_kernel(EnvPtrs e, const long long* __restrict__ start, uint64_t seed) {
+// reset (src/env/general_env.py:144-170): zero state, place agents, mark the start tile.  keys ([B][2] = (stream seed,
+// stream index), or null): the random start of agent b is drawn from its own stream instead of (seed, b).
+__global__ void env_reset_kernel(EnvPtrs e, const long long* __restrict__ start, uint64_t seed,
+                                 const uint64_t* __restrict__ keys) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= e.B) return;
   int y, x;
   if (start) { y = (int)start[2 * b]; x = (int)start[2 * b + 1]; }
   else {
-    const uint4 r = philox4x32(seed, (uint32_t)b, 0u, 0x52455345u, 0u);
+    const uint4 r = keys ? philox4x32(keys[2 * b], (uint32_t)keys[2 * b + 1], 0u, 0x52455345u, 0u)
+                         : philox4x32(seed, (uint32_t)b, 0u, 0x52455345u, 0u);
     const int gh = e.extent ? e.extent[2 * b] : e.Gh, gw = e.extent ? e.extent[2 * b + 1] : e.Gw;
     y = (int)(r.x % (uint32_t)gh); x = (int)(r.y % (uint32_t)gw);
   }
@@ -282,8 +285,8 @@ __global__ void env_reset_kernel(EnvPtrs e, const long long* __restrict__ start,
   e.has_stopped[b] = 0;
 }
 
-int launch_env_reset(const EnvPtrs& e, const int64_t* start_positions, uint64_t seed, hipStream_t s) {
-  hipLaunchKernelGGL(env_reset_kernel, dim3((e.B + 63) / 64), dim3(64), 0, s, e, (const long long*)start_positions, seed);
+int launch_env_reset(const EnvPtrs& e, const int64_t* start_positions, uint64_t seed, const uint64_t* keys, hipStream_t s) {
+  hipLaunchKernelGGL(env_reset_kernel, dim3((e.B + 63) / 64), dim3(64), 0, s, e, (const long long*)start_positions, seed, keys);
   return 0;
 }
 

@@ -19,6 +19,18 @@ def shard_range(global_batch: int, rank: int, world: int) -> Tuple[int, int]:
     return begin, begin + base + (1 if rank < rem else 0)
 
 
+def shard_agent_keys(seed: int, rollout_number: int, rank: int, world: int, B: int):
+    """uint64 [B, 2] the ``agent_keys`` of rank `rank`'s B agents in rollout `rollout_number` of a trainer seeded `seed`:
+    (the rollout's seed, the agent's index in the global batch of world * B agents).  Every rank seeds its rollouts alike
+    (``ReinforceTrainer`` has no rank term), so without keys all ranks draw the same uniforms for their agents 0..B-1;
+    with them the streams of the ranks are disjoint and their concatenation over the ranks is the table of one rank
+    running all world * B agents, whatever `world` is.  Opt-in: ``config.agent_streams = "global"``."""
+    import numpy as np
+    assert 0 <= rank < world and B >= 1 and world * B <= 1 << 32
+    rs = (int(seed) * 1000003 + int(rollout_number)) & 0xFFFFFFFFFFFFFFFF
+    return np.array([[rs, rank * B + b] for b in range(B)], dtype=np.uint64).reshape(-1, 2)
+
+
 def allreduce_gradients(flat: torch.Tensor, numel: int, group=None, timing: list = None) -> float:
     """SUM all-reduce of flat[:numel] in place; returns the scale (1 / world_size) the optimiser
     applies so that ranks step with the MEAN gradient.

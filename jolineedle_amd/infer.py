@@ -11,8 +11,8 @@ import torch.nn.functional as F
 from .detection import (compute_detection_metrics, detection_targets, map_50_device, pack_boxes, patch_bboxes2full_image,
                         rollout_boxes_packed, rollout_boxes_to_image, unpack_boxes)  # noqa: F401
 from .env import NeedleGeneralEnv
-from .ragged import (env_metrics, found_ratios, image_env, loop_start_positions, own_steps, plan_chunks,  # noqa: F401
-                     slice_rollout)
+from .ragged import (env_metrics, found_ratios, image_env, loop_agent_keys, loop_start_positions, own_steps,  # noqa: F401
+                     plan_chunks, slice_rollout)
 
 
 def load_bboxes(bbox_fname) -> List[List[int]]:
@@ -37,7 +37,7 @@ def pad_to_patch_multiple(image: torch.Tensor, patch_size: int) -> torch.Tensor:
 @torch.no_grad()
 def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequence] = None, sample_actions: bool = True,
                  do_detection: Optional[bool] = None, batch_size: Optional[int] = None, device_metrics: bool = False,
-                 token_positions: Optional[str] = None) -> Dict:
+                 token_positions: Optional[str] = None, streams: str = "loop") -> Dict:
     """`images`: [C, H, W] tensors (uint8 0..255 or float 0..1) of any sizes; `targets`: per image an [n, 4] xyxy list /
     tensor or None.  Returns per-image boxes ([n, 7] in full-image pixels or None), positions, step counts, durations
     and — where targets are given — the mean of the reference's metrics.
@@ -48,8 +48,11 @@ def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequ
     are assembled per image on the device.  Same keys, per image and in input order; ``steps[i]`` is what image i's own
     rollout reports; ``duration_ms[i]`` is its chunk's time divided by the chunk's size — a share, not a measurement
     of that image.  Every image starts where the loop's own random reset puts it
-    (``ragged.loop_start_positions``), so on floating-point images greedy results equal the loop's up to the engine's
-    rounding across batch sizes; sampled ones differ (an agent's action stream is keyed by its index in the batch).
+    (``ragged.loop_start_positions``) and samples its actions from the stream of its own rollout of the loop
+    (``ragged.loop_agent_keys``), so on floating-point images greedy and sampled results equal the loop's up to the
+    engine's rounding across batch sizes, whatever `batch_size` is and whichever images share a chunk.  streams="batch"
+    keys a sampled action by the chunk's seed and the agent's place in the chunk instead (the draws before per-agent
+    streams existed); it is an error without batch_size.
     On uint8 images the two do not see the same pixels: the loop scales on the device (``x.float() / 255``, which torch
     computes as a multiply by the rounded reciprocal, one ulp off b / 255 for some bytes) while the batched path reads
     the bytes as the correctly rounded b / 255 that ToTensor computes; measured on the test detector that moved a box
@@ -64,9 +67,13 @@ def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequ
     P, T = int(cfg.patch_size), int(cfg.max_seq_len)
     if do_detection is None:
         do_detection = bool(getattr(cfg, "detection_enabled", False)) and trainer.yolox_model() is not None
+    if streams not in ("loop", "batch"):
+        raise ValueError(f"streams must be 'loop' or 'batch', got {streams!r}")
     if batch_size is not None:
         return _infer_batched(trainer, images, targets, sample_actions, do_detection, int(batch_size), device_metrics,
-                              token_positions)
+                              token_positions, streams)
+    if streams != "loop":
+        raise ValueError("streams='batch' needs batch_size: the per-image loop has no batch")
     if device_metrics:
         raise ValueError("device_metrics needs batch_size: the per-image loop evaluates one image at a time")
     res = {"boxes": [], "positions": [], "steps": [], "duration_ms": []}
@@ -98,7 +105,7 @@ def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequ
 
 
 def _infer_batched(trainer, images, targets, sample_actions, do_detection, batch_size, device_metrics=False,
-                   token_positions=None) -> Dict:
+                   token_positions=None, streams="loop") -> Dict:
     dev, P = trainer.device, int(trainer.config.patch_size)
     n = len(images)
     res = {"boxes": [None] * n, "positions": [None] * n, "steps": [0] * n, "duration_ms": [0.0] * n}
@@ -113,9 +120,10 @@ def _infer_batched(trainer, images, targets, sample_actions, do_detection, batch
         env = image_env(trainer, imgs, rows, canvas=chunk["canvas"])
         extents = env.grid_extents.tolist()
         start = loop_start_positions(trainer, first, sel, extents)
+        keys = loop_agent_keys(trainer, first, sel) if sample_actions and streams == "loop" else None    # greedy: no call
         t0 = time.perf_counter()
         ro = trainer.rollout(env, do_detection=do_detection, sample_actions=sample_actions, start_positions=start,
-                             bbox_lists=False, token_positions=token_positions)
+                             bbox_lists=False, token_positions=token_positions, agent_keys=keys)
         torch.cuda.synchronize(dev)
         ms = (time.perf_counter() - t0) * 1e3 / len(sel)
         packed = rollout_boxes_packed(ro, P) if do_detection else None

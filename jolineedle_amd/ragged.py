@@ -71,19 +71,41 @@ def _philox4x32(seed: int, c0: int, c1: int, c2: int, c3: int):
     return c0, c1, c2, c3
 
 
+def rollout_seed(trainer, number: int) -> int:
+    """The seed ``ReinforceTrainer.rollout`` hands to the engine for its rollout number `number`."""
+    return (trainer.seed * 1000003 + number) & 0xFFFFFFFFFFFFFFFF
+
+
 def loop_start_positions(trainer, first_rollout: int, indices: Sequence[int], extents: Sequence[Sequence[int]]) -> Tensor:
     """[n, 2] the start position image indices[j] draws in the per-image loop: there it is agent 0 of rollout number
     `first_rollout` + indices[j] of this trainer, whose reset draws (y, x) = Philox(rollout seed, agent 0) modulo the
     image's own grid (env_reset_kernel).  Handing these to the batched rollout makes it start where the loop starts."""
     out = []
     for i, (gh, gw) in zip(indices, extents):
-        seed = (trainer.seed * 1000003 + first_rollout + i) & 0xFFFFFFFFFFFFFFFF
+        seed = rollout_seed(trainer, first_rollout + i)
         r = _philox4x32(seed, 0, 0, 0x52455345, 0)
         out.append([r[0] % gh, r[1] % gw])
     return torch.tensor(out, dtype=torch.int64)
 
 
+def loop_agent_keys(trainer, first_rollout: int, indices: Sequence[int]):
+    """uint64 [n, 2] = (stream seed, stream index) of the random stream image indices[j] draws from in the per-image
+    loop: there it is agent 0 of rollout number `first_rollout` + indices[j], so its key is (that rollout's seed, 0).
+    Handed to the batched rollout as ``agent_keys`` they make every agent sample the actions the loop samples (and
+    draw 0 of the same stream's reset is ``loop_start_positions``)."""
+    import numpy as np
+    return np.array([[rollout_seed(trainer, first_rollout + i), 0] for i in indices], dtype=np.uint64).reshape(-1, 2)
+
+
 EVAL_MODES = ("multistart", "corners", "rollouts")
+
+
+def walk_agent_keys(trainer, first_rollout: int, indices: Sequence[int], n_walks: int):
+    """uint64 [n * K, 2] the streams of the K walks of every image of ``walk_start_positions``, in image order then
+    walk order: walk (i, k) is rollout number first_rollout + i * K + k of the per-image loop in every mode — under
+    "rollouts" too, where it starts at walk 0's position but samples from its own rollout's stream."""
+    K = int(n_walks)
+    return loop_agent_keys(trainer, first_rollout, [i * K + k for i in indices for k in range(K)])
 
 
 def walk_start_positions(trainer, first_rollout: int, indices: Sequence[int], extents: Sequence[Sequence[int]], n_walks: int,

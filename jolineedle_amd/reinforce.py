@@ -11,6 +11,16 @@ from ._lib import JnRolloutOut, JnTrainOpts, check, ptr
 from .env import NeedleGeneralEnv
 
 
+def _keys_table(agent_keys, B: int):
+    """The host table of ``jn_set_rollout_keys``: uint64 [B, 2] = (stream seed, stream index) from any [B, 2] integers
+    (a seed is taken modulo 2**64, as the rollout seeds are)."""
+    import numpy as np
+    rows = agent_keys.tolist() if hasattr(agent_keys, "tolist") else list(agent_keys)
+    tab = np.array([[int(s) & 0xFFFFFFFFFFFFFFFF, int(i)] for s, i in rows], dtype=np.uint64).reshape(-1, 2)
+    assert tab.shape[0] == B, f"agent_keys must be [{B}, 2], got {list(tab.shape)}"
+    return np.ascontiguousarray(tab)
+
+
 class _RolloutGraph(torch.autograd.Function):
     """Graph node behind ``rollout()["logprobs"]`` / ``["entropies"]`` of a train-mode rollout ("carry
     autograd graph in training").  backward = ``jn_reinforce_backward`` with the upstream gradients torch hands over, then
@@ -76,7 +86,7 @@ class ReinforceTrainer:
                 forced_actions: torch.Tensor = None, start_positions: torch.Tensor = None,
                 keep_patches: bool = True, stop_early: bool = True, bbox_lists: bool = True,
                 token_positions: str = None, teacher: bool = False,
-                teacher_targets: torch.Tensor = None) -> Dict[str, torch.Tensor]:
+                teacher_targets: torch.Tensor = None, agent_keys=None) -> Dict[str, torch.Tensor]:
         """src/reinforce.py:108-215.  Extra keyword arguments (not in the reference):
         `forced_actions` [B,T] replays a trajectory, `start_positions` [B,2] injects reset
         positions (reference: env.reset(positions)), `keep_patches=False` skips the
@@ -91,7 +101,11 @@ class ReinforceTrainer:
         is an eval-mode feature (see the NotImplementedError below).
         `teacher=True` adds "teacher_sets" [B,S] uint8: per step the teacher's action set
         (``trajectory.teacher_action_sets``) of the state the decision saw, computed inside the rollout;
-        `teacher_targets` [B,Gh,Gw] replaces the env's bbox masks as the cells the teacher walks to."""
+        `teacher_targets` [B,Gh,Gw] replaces the env's bbox masks as the cells the teacher walks to.
+        `agent_keys` [B,2] integers (stream seed, stream index): agent b draws its sampled actions, and its random start
+        when `start_positions` is None, from that Philox stream instead of (this rollout's seed, b)
+        (``jn_set_rollout_keys``) — an agent then walks the same way wherever it sits in whichever batch; None = the
+        default streams, or ``dist.shard_agent_keys`` of this rank when ``config.agent_streams == "global"``."""
         model, dev = self.model, self.device
         if token_positions is None:
             token_positions = "sequence" if getattr(model.config, "no_recurrent_embedding", False) else "recurrent"
@@ -138,6 +152,7 @@ class ReinforceTrainer:
             start_positions = start_positions.to(dev, torch.int64).contiguous()
         self._rollouts += 1
         seed = (self.seed * 1000003 + self._rollouts) & 0xFFFFFFFFFFFFFFFF
+        keys = self._agent_keys_table(agent_keys, B)
         stream = _lib.current_stream(dev)
         # model.train() + grad mode (the reference's training loop, src/reinforce.py:304, 326): batch-statistics BatchNorm,
         # activations of every step kept resident, logprobs / entropies leave with a graph (autograd bridge)
@@ -150,8 +165,10 @@ class ReinforceTrainer:
                 grid = (B, env.n_vertical_patches, env.n_horizontal_patches)
                 assert tuple(teacher_targets.shape) == grid, f"teacher_targets must be {grid}, got {tuple(teacher_targets.shape)}"
         try:
-            # both switches are sticky in the engine: set for this rollout only, so that every other caller of the
-            # engine (and the default path, which makes neither call) finds it as it always was
+            # the switches are sticky in the engine: set for this rollout only, so that every other caller of the
+            # engine (and the default path, which makes none of these calls) finds it as it always was
+            if keys is not None:
+                check(eng.lib.jn_set_rollout_keys(eng.handle, keys.ctypes.data_as(C.c_void_p), B), "jn_set_rollout_keys")
             if by_token:
                 check(eng.lib.jn_set_rollout_positions(eng.handle, 1), "jn_set_rollout_positions")
             if teacher:
@@ -169,6 +186,8 @@ class ReinforceTrainer:
                 check(eng.lib.jn_rollout(eng.handle, mode, ptr(forced_actions), ptr(start_positions), seed,
                                          int(do_detection), int(stop_early), C.byref(out), stream), "jn_rollout")
         finally:
+            if keys is not None:
+                eng.lib.jn_set_rollout_keys(eng.handle, None, 0)
             if by_token:
                 eng.lib.jn_set_rollout_positions(eng.handle, 0)
             if teacher:
@@ -194,6 +213,19 @@ class ReinforceTrainer:
             res["bboxes"] = [[det_boxes[b, t, :cnt[b][t]].clone() if cnt[b][t] > 0 else None for t in range(S + 1)]
                              for b in range(B)]
         return res
+
+    def _agent_keys_table(self, agent_keys, B: int):
+        """uint64 [B, 2] host table for the rollout numbered ``self._rollouts``, or None (no ``jn_set_rollout_keys`` call):
+        the caller's `agent_keys`, else with ``config.agent_streams == "global"`` this rank's ``dist.shard_agent_keys``."""
+        mode = getattr(self.config, "agent_streams", "batch")
+        if mode not in ("batch", "global"):
+            raise ValueError(f"config.agent_streams must be 'batch' or 'global', got {mode!r}")
+        if agent_keys is None and mode == "global":
+            import torch.distributed as dist
+            from .dist import shard_agent_keys
+            world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+            agent_keys = shard_agent_keys(self.seed, self._rollouts, int(getattr(self, "rank", 0) or 0), world, B)
+        return None if agent_keys is None else _keys_table(agent_keys, B)
 
     # ---- the reference's training loop on the autograd bridge (src/trainer.py:61-71, src/reinforce.py:267-362) --------
     def ddp_setup(self, rank: int, world_size: int, port: int, backend: str = None):
@@ -342,9 +374,9 @@ class ReinforceTrainer:
 
     def train_iteration(self, env: NeedleGeneralEnv, sample_actions: bool = True, forced_actions=None,
                         start_positions=None, stop_early: bool = True, optimizer_step: bool = True,
-                        process_group=None) -> Dict[str, torch.Tensor]:
+                        process_group=None, agent_keys=None) -> Dict[str, torch.Tensor]:
         """rollout (train-mode BatchNorm) -> compute_metrics -> backward -> [all-reduce] -> clip + AdamW,
-        all inside the engine.  Returns the metrics of src/reinforce.py:243-252."""
+        all inside the engine.  Returns the metrics of src/reinforce.py:243-252.  `agent_keys`: see ``rollout``."""
         model, dev = self.model, self.device
         model.sync_weights()
         eng = model.engine()
@@ -381,10 +413,17 @@ class ReinforceTrainer:
                            entropy_weight=float(self.entropy_weight), loss_scale=1.0 / ga)
         metrics_dev = torch.zeros(8, **f32)
         seed = (self.seed * 1000003 + self._rollouts) & 0xFFFFFFFFFFFFFFFF
+        keys = self._agent_keys_table(agent_keys, B)
         stream = _lib.current_stream(dev)
-        check(eng.lib.jn_reinforce_step(eng.handle, mode, ptr(forced_actions), ptr(start_positions), seed,
-                                        int(stop_early), C.byref(opts), C.byref(out), ptr(metrics_dev), stream),
-              "jn_reinforce_step")
+        try:
+            if keys is not None:           # sticky in the engine: set for this iteration only
+                check(eng.lib.jn_set_rollout_keys(eng.handle, keys.ctypes.data_as(C.c_void_p), B), "jn_set_rollout_keys")
+            check(eng.lib.jn_reinforce_step(eng.handle, mode, ptr(forced_actions), ptr(start_positions), seed,
+                                            int(stop_early), C.byref(opts), C.byref(out), ptr(metrics_dev), stream),
+                  "jn_reinforce_step")
+        finally:
+            if keys is not None:
+                eng.lib.jn_set_rollout_keys(eng.handle, None, 0)
         m = metrics_dev.cpu()
         S = int(m[5])
         if self.config.reward_norm:
@@ -527,7 +566,8 @@ class ReinforceTrainer:
     @torch.no_grad()
     def _eval_image_chunks(self, images, bboxes, batch_size: int, do_detection: bool = None, merge_bboxes: bool = None,
                            device_metrics: bool = False, sample_actions: bool = False, token_positions: str = None,
-                           teacher_targets=None, walks: int = 1, walk_starts=None, chunk_metrics=None) -> list:
+                           teacher_targets=None, walks: int = 1, walk_starts=None, chunk_metrics=None,
+                           streams: str = "loop") -> list:
         """The chunked rollouts behind ``eval_on_images`` (and ``SupervisedTrainer.eval_on_images``): per image, in image
         order, (the metrics that do not come from ``compute_metrics``, the image's own ``B = 1`` rollout).
         teacher_targets: a callable (box rows of the chunk's images, their grid extents, the canvas grid) -> uint8
@@ -540,13 +580,18 @@ class ReinforceTrainer:
         images and n * K stays within the model's max_batch.  Walk (i, j) starts where rollout first + i * K + j of the
         per-image loop would (``ragged.loop_start_positions``), or at walk_starts(first, image indices, their extents)
         -> [n, K, 2]; the rollout counter ends at first - 1 + len(images) * K.
+        streams: "loop" — a sampled walk draws its actions from the stream of its own rollout of the per-image loop
+        (``ragged.walk_agent_keys``), so that it is that rollout's walk; "batch" — from (the chunk's seed, its place in
+        the chunk).  Greedy chunks make no such call.
         chunk_metrics: a callable(chunk) called once per chunk with {"indices", "env", "rollout", "steps", "extents"
         (per agent), "rows", "walks", "targets" (the teacher grid per agent or None)} in place of the per-image detection
         metrics (`map`, `yolo_*`), which are then not computed."""
         from .detection import (detection_targets, map_50_device, merge_boxes_device, pack_boxes, rollout_boxes_packed,
                                 split_bboxes_over_patches, unpack_boxes)
         from .ragged import (env_metrics, found_ratios, image_env, loop_start_positions, own_steps, plan_chunks,
-                             slice_rollout)
+                             slice_rollout, walk_agent_keys)
+        if streams not in ("loop", "batch"):
+            raise ValueError(f"streams must be 'loop' or 'batch', got {streams!r}")
         cfg, P = self.config, int(self.patch_size)
         if do_detection is None:
             do_detection = bool(getattr(cfg, "detection_enabled", False))
@@ -583,6 +628,8 @@ class ReinforceTrainer:
                 starts = torch.as_tensor(walk_starts(first, imgs_of, extents[::K])).reshape(len(sel), 2).to(torch.int64)
             else:
                 starts = loop_start_positions(self, first, sel, extents)
+            if sample_actions and streams == "loop":
+                kw["agent_keys"] = walk_agent_keys(self, first, imgs_of, K)
             ro = self.rollout(env, sample_actions=sample_actions, do_detection=do_detection, bbox_lists=False,
                               start_positions=starts, token_positions=token_positions, **kw)
             steps = own_steps(ro)

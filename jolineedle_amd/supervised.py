@@ -311,7 +311,7 @@ class SupervisedTrainer:
 
     @torch.no_grad()
     def eval_on_images(self, images, bboxes, batch_size: int, sample_actions: bool = False, do_detection: bool = None,
-                       merge_bboxes: bool = None, device_metrics: bool = False) -> Dict[str, list]:
+                       merge_bboxes: bool = None, device_metrics: bool = False, streams: str = "loop") -> Dict[str, list]:
         """The free-running half of the reference's ``test()``: ``test_model_on_env`` (src/supervised.py:279-405) lets the
         policy walk one image, calling the full-sequence forward again at every step, and compares every chosen action
         with the teacher's ``best_action``.  Here the walks are the engine's rollouts with the token of step t at 1-D
@@ -326,12 +326,14 @@ class SupervisedTrainer:
         `teacher_agreement` (share of the own steps with a non-empty teacher set whose action is a member of it; 0 when
         there is none) and `stopped_inside_bbox` (the final cell is a target cell).  No REINFORCE losses;
         ``last_return_values`` of no trainer is touched.  ``self.last_eval_rollouts`` keeps, per image, the small
-        part of its walk on the host (actions, positions, logits, teacher_sets, teacher_targets).  Deviations from the
-        reference: DESIGN.md §6."""
+        part of its walk on the host (actions, positions, logits, teacher_sets, teacher_targets).  With sample_actions
+        every walk samples from the stream of its own rollout of the per-image loop (``ragged.walk_agent_keys``), so
+        the result does not depend on `batch_size`; streams="batch" keeps the draws keyed by the place in the chunk.
+        Deviations from the reference: DESIGN.md §6."""
         if do_detection is None:
             do_detection = bool(getattr(self.config, "detection_enabled", True)) and self.yolox_model() is not None
         return self._walk_metrics(self._eval_walks(images, bboxes, batch_size, do_detection, merge_bboxes, device_metrics,
-                                                   sample_actions=sample_actions))
+                                                   sample_actions=sample_actions, streams=streams))
 
     def _eval_walks(self, images, bboxes, batch_size, do_detection, merge_bboxes, device_metrics, **kw) -> list:
         """The free-running walks of both evaluations: ``ReinforceTrainer._eval_image_chunks`` in sequence-position mode
@@ -373,7 +375,8 @@ class SupervisedTrainer:
 
     @torch.no_grad()
     def eval_envs_on_images(self, images, bboxes, batch_size: int, eval_mode: str = "multistart", n_starts: int = 2,
-                            sample_actions: bool = False, start_positions=None, device_metrics: bool = True) -> Dict[str, list]:
+                            sample_actions: bool = False, start_positions=None, device_metrics: bool = True,
+                            streams: str = "loop") -> Dict[str, list]:
         """``eval_envs`` of the reference (src/supervised.py:638-752) without its plots — the evaluation whose `map` at one
         start selects ``checkpoint_best.pt`` (:81, :804): every image is walked from K starts and, for every prefix
         k = 1..K of those walks, the detections of the walks are pooled per visited patch, de-duplicated by an NMS at
@@ -384,7 +387,10 @@ class SupervisedTrainer:
         read image i's one stored copy), exactly as ``eval_on_images`` runs its walks (sequence positions, teacher armed).
         eval_mode: "multistart" (K = n_starts random starts, each where the per-image loop's reset would put it),
         "corners" (K = 4, the corners of the image's own grid) or "rollouts" (K = n_starts walks from walk 0's start;
-        meaningful with sample_actions); start_positions [n_images, K, 2] overrides the mode's starts (and its K).  The
+        meaningful with sample_actions); start_positions [n_images, K, 2] overrides the mode's starts (and its K).  With
+        sample_actions, walk (i, k) samples from the stream of rollout i * K + k of the per-image loop
+        (``ragged.walk_agent_keys``): the K walks of an image are that loop's K rollouts, whatever `batch_size` is;
+        streams="batch" keeps the draws keyed by the agent's place in the chunk.  The
         tokens of a walk are t = 0 .. its own steps, the last patch reached included (:354-363).
 
         Returns lists.  One entry per WALK, in image order then walk order (:694-695): `prop_patches_found`,
@@ -474,7 +480,7 @@ class SupervisedTrainer:
 
         out = self._walk_metrics(self._eval_walks(images, bboxes, batch_size, True, False, device_metrics,
                                                   sample_actions=sample_actions, walks=K, walk_starts=starts,
-                                                  chunk_metrics=chunk_metrics))
+                                                  chunk_metrics=chunk_metrics, streams=streams))
         for i in range(len(images)):
             for k, v in per_image[i].items():
                 out.setdefault(k, []).append(v)
@@ -623,11 +629,11 @@ class SupervisedTrainer:
         return out
 
     def test_on_images(self, images, bboxes, batch_size: int, class_ids=None, sample_actions: bool = False,
-                       seed: Optional[int] = None) -> Dict[str, list]:
+                       seed: Optional[int] = None, streams: str = "loop") -> Dict[str, list]:
         """The metric assembly of ``test()`` (src/supervised.py:754-810) without logger, plots or checkpoint: the
         multistart evaluation's lists (``eval_envs_on_images``), the validation lists under ``supervised_<name>``
         (:796-799); sets ``last_test_metrics`` and extends ``best_metric_history`` by the mean of ``best_metric_name``."""
-        metrics = self.eval_envs_on_images(images, bboxes, batch_size, sample_actions=sample_actions)
+        metrics = self.eval_envs_on_images(images, bboxes, batch_size, sample_actions=sample_actions, streams=streams)
         for name, values in self.eval_supervised_on_images(images, bboxes, batch_size, class_ids=class_ids, seed=seed).items():
             metrics["supervised_" + name] = values
         self.last_test_metrics = metrics
