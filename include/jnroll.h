@@ -726,6 +726,45 @@ int jn_conv3_bwd_data_s2(const float* gz_dev, int g_ld, const float* w_dev, floa
 int jn_conv3_bwd_weight(const float* gz_dev, int g_ld, const float* x_dev, int x_ld, const float* tab_dev, float* gw_dev, int N, int H,
                         int W, int cout, int cin, int stride, int n_slots, int route, int max_wg, void* stream);
 int jn_conv3_route(int kind, int N, int H, int W, int cin, int cout, int stride, int n_slots, int ld_a, int ld_b);
+/* Debug entries, context-free: ONE launch of a depthwise 3x3 kernel (pad 1, stride 1 or 2; csrc/kernels_conv.hip, the backward in
+ * csrc/kernels_bwd.hip) on caller tensors, then a wait for `stream`.  Maps are NHWC with a leading dimension that may exceed the
+ * channel count C: channels past it are neither read nor written.  H x W is the layer's INPUT map, of any size; the output map
+ * is OH x OW = (H + stride - 1) / stride x (W + stride - 1) / stride.  Tables are f32 [3][channels], rows scale, shift, flag:
+ * a = flag ? silu(scale * x + shift) : x, zero padding applied to a.  w f32 [9][C], tap = 3 ky + kx.  dtype: 0 = f32, 1 = bf16 maps.
+ * Common JN_EINVAL, before any device call: a null pointer (but the optional ones), N, H, W < 1, N * H * W > 2^24, C < 4, C % 4 != 0,
+ * C > 4096, a stride other than 1 or 2, a leading dimension below its channel count, no multiple of 4 or above 8192, a route out
+ * of range or one whose preconditions the launch does not meet.
+ *
+ * jn_dw3x3: out = dwconv(a(in), w).  stats_dev: NULL, or f64 [nrep][2 C] that the launch ADDS per-channel (sum, sum of squares)
+ * of the output into, spread over the nrep (1..32) replicas.  skip_flag_dev: NULL, or a device int; nothing is done when
+ * *skip_flag_dev >= skip_when.  Routes: 0 = the launcher's rule, 1 = the LDS-tiled kernel (C % 16 == 0, N <= 65535), 2 = the
+ * strip kernel (reads the table arrays only).
+ * jn_dw3x3_route: host only: the route (1 or 2) the launcher's rule gives.
+ * jn_dwpw: the eval-mode fusion out = w_pw . silu(msc * dwconv(a(in), w_dw) + msh), w_pw f32 [cout][C], mtab [3][C] (flag row not
+ * read); with res_dev the bottleneck shortcut out = silu(psc * (that) + psh) + T_rtab(res), res [N,OH,OW,res_ld], rtab and ptab
+ * [3][cout] (ptab's flag row not read).  JN_EINVAL also where dwpw_supported(C, cout, stride) is false: C or cout no multiple of
+ * 16, C > 64, cout / 16 not 1, 2, 4 or 8 (stride 2: not 1).
+ * jn_dw_bwd: the backward of one depthwise BatchNorm + SiLU layer over n_slots (1..64) workspace slots.  Per slot, with
+ * y = o_sc * z + o_sh of the layer's raw output z: g_z = k * (g * silu'(y) - c1 - (z - mean) * invstd * c2); gin (=|+=) the
+ * transposed depthwise conv of g_z; gw [9][C] += sum g_z * a(x) over all slots.  g [S][N,OH,OW,g_ld], z likewise, x [S][N,H,W,x_ld],
+ * gin likewise; otab, itab [S][3][C] (otab's flag row not read); save [S][C][2] = (mean, invstd); consts [S][C][3] = (c1, c2, k).
+ * Routes: 0 = the backward plan's choice, 1 = the fused kernel (C % 16 == 0), 2 = bn_bwd_gz, data-gradient and weight-gradient
+ * kernels one after the other.  red_out_dev: NULL, or f64 [S][32][2 C] the fused kernel ADDS, per input channel,
+ * (sum dx * silu'(y_in), sum dx * silu'(y_in) * y_in) into, y_in = i_sc * x + i_sh, dx the data gradient it writes (route 1 without
+ * accumulate only).  use_wpart != 0: the weight gradient goes through a zeroed [32][16384] replica scratch, copied to
+ * wpart_back_dev (required then) after the launch, where it must be zero again.  max_wg: 0 = the launcher's rule, else a cap on
+ * the persistent workgroups per channel block and slot (route 1) or on the weight-gradient kernel's workgroups per slot (route 2).
+ * Allocates its workspace, waits for `stream` and frees it. */
+int jn_dw3x3(const void* in_dev, int in_ld, const float* tab_dev, const float* w_dev, void* out_dev, int out_ld, int N, int H, int W,
+             int C, int stride, int dtype, double* stats_dev, const int* skip_flag_dev, int skip_when, int nrep, int route, void* stream);
+int jn_dw3x3_route(int N, int C, int stride, int dtype);
+int jn_dwpw(const void* in_dev, int in_ld, const float* itab_dev, const float* w_dw_dev, const float* mtab_dev, const float* w_pw_dev,
+            void* out_dev, int out_ld, const void* res_dev, int res_ld, const float* rtab_dev, const float* ptab_dev, int N, int H, int W,
+            int C, int cout, int stride, int dtype, const int* skip_flag_dev, int skip_when, void* stream);
+int jn_dw_bwd(const float* g_dev, int g_ld, const float* z_dev, int z_ld, const float* x_dev, int x_ld, const float* otab_dev,
+              const float* itab_dev, const float* save_dev, const float* consts_dev, const float* w_dev, float* gin_dev, int gin_ld,
+              int accumulate, float* gw_dev, double* red_out_dev, int N, int H, int W, int C, int stride, int n_slots, int route,
+              int use_wpart, float* wpart_back_dev, int max_wg, void* stream);
 /* Arms the following rollouts of `ctx` with that teacher (the per-step `best_action` that test_model_on_env compares
  * each chosen action with, src/supervised.py:279-405): before the decision of step t, the set of the state that
  * decision sees (position and visited patches before the step) goes to sets_dev[b * T + t] (uint8 [B,T], T =

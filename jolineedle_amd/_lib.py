@@ -153,6 +153,13 @@ SIGNATURES = {
     "jn_conv3_bwd_data_s2": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p]),
     "jn_conv3_bwd_weight": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p]),
     "jn_conv3_route": (C.c_int, [C.c_int] * 10),
+    "jn_dw3x3": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p] + [C.c_int] * 3 +
+                          [C.c_void_p]),
+    "jn_dw3x3_route": (C.c_int, [C.c_int] * 4),
+    "jn_dwpw": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 7 +
+                         [C.c_void_p, C.c_int, C.c_void_p]),
+    "jn_dw_bwd": (C.c_int, [C.c_void_p, C.c_int] * 3 + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 8 +
+                           [C.c_void_p, C.c_int, C.c_void_p]),
     "jn_set_rollout_teacher":(C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "jn_set_rollout_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "jn_rollout_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),

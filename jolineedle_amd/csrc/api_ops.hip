@@ -481,3 +481,141 @@ int jn_conv3_bwd_weight(const float* gz_dev, int g_ld, const float* x_dev, int x
 }
 
 }  // extern "C"
+
+// ---- depthwise 3x3 kernels on caller tensors (kernels_conv.hip, kernels_bwd.hip) -------------------------------------------------
+// What the entries check of a shape before anything else: H x W is the layer's INPUT map, odd sizes included at stride 2
+static bool dw_shape_ok(int N, int H, int W, int C, int stride) {
+  return N >= 1 && H >= 1 && W >= 1 && (long long)N * H * W <= (1 << 24) && C >= 4 && C % 4 == 0 && C <= 4096 && (stride == 1 || stride == 2);
+}
+static bool dw_ld_ok(int ld, int C) { return ld >= C && ld % 4 == 0 && ld <= 8192; }
+static ChanTab dw_tab(const float* t, int C) {
+  float* p = const_cast<float*>(t);
+  ChanTab r{};
+  r.sc = p; r.sh = p + C; r.fl = p + 2 * C;
+  return r;
+}
+
+extern "C" {
+
+int jn_dw3x3_route(int N, int C, int stride, int dtype) {
+  JN_CHECK(dw_shape_ok(N, 1, 1, C, stride) && (dtype == JN_F32 || dtype == JN_BF16), JN_EINVAL,
+           "jn_dw3x3_route: N=%d C=%d stride=%d dtype=%d", N, C, stride, dtype);
+  ConvArgs a{};
+  a.N = N; a.cin = a.cout = C; a.stride = stride; a.in_dtype = a.out_dtype = dtype;
+  return dw_route(a, 0);
+}
+
+int jn_dw3x3(const void* in_dev, int in_ld, const float* tab_dev, const float* w_dev, void* out_dev, int out_ld, int N, int H, int W,
+             int C, int stride, int dtype, double* stats_dev, const int* skip_flag_dev, int skip_when, int nrep, int route, void* stream) {
+  JN_CHECK(in_dev && tab_dev && w_dev && out_dev, JN_EINVAL, "jn_dw3x3: null argument");
+  JN_CHECK(dw_shape_ok(N, H, W, C, stride) && dw_ld_ok(in_ld, C) && dw_ld_ok(out_ld, C) && (dtype == JN_F32 || dtype == JN_BF16), JN_EINVAL,
+           "jn_dw3x3: %d x %d x %d, %d channels, stride %d, dtype %d, leading dimensions %d and %d", N, H, W, C, stride, dtype, in_ld, out_ld);
+  JN_CHECK(nrep >= 1 && nrep <= JN_NREP && route >= 0 && route <= DW_ROUTE_STRIP, JN_EINVAL, "jn_dw3x3: nrep=%d route=%d", nrep, route);
+  ConvArgs a{};
+  a.in = in_dev; a.in_ld = in_ld; a.in_dtype = dtype; a.itab = dw_tab(tab_dev, C); a.w = w_dev;
+  a.out = out_dev; a.out_ld = out_ld; a.out_dtype = dtype;
+  a.N = N; a.H = H; a.W = W; a.OH = (H + stride - 1) / stride; a.OW = (W + stride - 1) / stride; a.cin = a.cout = C; a.stride = stride;
+  a.act = ACT_NONE; a.stats = stats_dev; a.stats_rep_stride = 2LL * C; a.stats_nrep = nrep;
+  a.skip_flag = skip_flag_dev; a.skip_when = skip_when;
+  JN_CHECK(dw_route(a, route) > 0, JN_EINVAL, "jn_dw3x3: route %d does not take this launch", route);
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = launch_dw(a, s, route);
+  JN_HIP(hipGetLastError());
+  JN_HIP(hipStreamSynchronize(s));
+  JN_CHECK(rc == 0, JN_EINVAL, "jn_dw3x3: no kernel took the launch");
+  return JN_OK;
+}
+
+int jn_dwpw(const void* in_dev, int in_ld, const float* itab_dev, const float* w_dw_dev, const float* mtab_dev, const float* w_pw_dev,
+            void* out_dev, int out_ld, const void* res_dev, int res_ld, const float* rtab_dev, const float* ptab_dev, int N, int H, int W,
+            int C, int cout, int stride, int dtype, const int* skip_flag_dev, int skip_when, void* stream) {
+  JN_CHECK(in_dev && itab_dev && w_dw_dev && mtab_dev && w_pw_dev && out_dev, JN_EINVAL, "jn_dwpw: null argument");
+  JN_CHECK(dw_shape_ok(N, H, W, C, stride) && dw_ld_ok(in_ld, C) && cout >= 4 && cout % 4 == 0 && dw_ld_ok(out_ld, cout) &&
+               (dtype == JN_F32 || dtype == JN_BF16),
+           JN_EINVAL, "jn_dwpw: %d x %d x %d, %d -> %d channels, stride %d, dtype %d, leading dimensions %d and %d", N, H, W, C, cout, stride,
+           dtype, in_ld, out_ld);
+  JN_CHECK(dwpw_supported(C, cout, stride), JN_EINVAL, "jn_dwpw: %d -> %d channels at stride %d: no fused kernel", C, cout, stride);
+  JN_CHECK(!res_dev || (rtab_dev && ptab_dev && dw_ld_ok(res_ld, cout)), JN_EINVAL, "jn_dwpw: a shortcut needs both tables and res_ld=%d >= %d",
+           res_ld, cout);
+  DwPwArgs f{};
+  f.in = in_dev; f.in_ld = in_ld; f.itab = dw_tab(itab_dev, C); f.w_dw = w_dw_dev; f.mtab = dw_tab(mtab_dev, C); f.w_pw = w_pw_dev;
+  f.out = out_dev; f.out_ld = out_ld; f.dtype = dtype; f.C = C; f.cout = cout; f.N = N; f.H = H; f.W = W;
+  f.OH = (H + stride - 1) / stride; f.OW = (W + stride - 1) / stride; f.stride = stride; f.skip_flag = skip_flag_dev; f.skip_when = skip_when;
+  if (res_dev) { f.res = res_dev; f.res_ld = res_ld; f.rtab = dw_tab(rtab_dev, cout); f.ptab = dw_tab(ptab_dev, cout); }
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = launch_dwpw(f, s);
+  JN_HIP(hipGetLastError());
+  JN_HIP(hipStreamSynchronize(s));
+  JN_CHECK(rc == 0, JN_EINVAL, "jn_dwpw: no kernel took the launch");
+  return JN_OK;
+}
+
+// (the kernels step z and x by ONE slot stride and g and the input gradient by another, the engine's workspaces: the caller's dense
+// tensors are laid into slots [z | x] and [g | g_in] as in jn_pw_bwd_fused, so the call allocates, waits for the stream and frees;
+// the unfused route turns the copy of g into g_z in place, as the engine does with its gradient buffer)
+int jn_dw_bwd(const float* g_dev, int g_ld, const float* z_dev, int z_ld, const float* x_dev, int x_ld, const float* otab_dev,
+              const float* itab_dev, const float* save_dev, const float* consts_dev, const float* w_dev, float* gin_dev, int gin_ld,
+              int accumulate, float* gw_dev, double* red_out_dev, int N, int H, int W, int C, int stride, int n_slots, int route,
+              int use_wpart, float* wpart_back_dev, int max_wg, void* stream) {
+  JN_CHECK(g_dev && z_dev && x_dev && otab_dev && itab_dev && save_dev && consts_dev && w_dev && gin_dev && gw_dev, JN_EINVAL,
+           "jn_dw_bwd: null argument");
+  JN_CHECK(dw_shape_ok(N, H, W, C, stride) && n_slots >= 1 && n_slots <= 64 && dw_ld_ok(g_ld, C) && dw_ld_ok(z_ld, C) && dw_ld_ok(x_ld, C) &&
+               dw_ld_ok(gin_ld, C),
+           JN_EINVAL, "jn_dw_bwd: %d x %d x %d, %d channels, stride %d, %d slots, leading dimensions %d, %d, %d and %d", N, H, W, C, stride,
+           n_slots, g_ld, z_ld, x_ld, gin_ld);
+  JN_CHECK(route >= 0 && route <= 2 && max_wg >= 0 && (!use_wpart || wpart_back_dev), JN_EINVAL, "jn_dw_bwd: route=%d max_wg=%d use_wpart=%d",
+           route, max_wg, use_wpart);
+  const int OH = (H + stride - 1) / stride, OW = (W + stride - 1) / stride;
+  const bool fused_ok = dw_bwd_fused_supported(C, H, W, OH, OW, stride);
+  if (route == 0) route = fused_ok ? 1 : 2;      // the backward plan's choice (plan.cpp)
+  JN_CHECK(route == 2 || fused_ok, JN_EINVAL, "jn_dw_bwd: the fused kernel takes whole blocks of 16 channels, not %d", C);
+  JN_CHECK(!red_out_dev || (route == 1 && !accumulate), JN_EINVAL,
+           "jn_dw_bwd: the input layer's sums are formed by the fused kernel only, from a gradient it writes (route %d, accumulate %d)", route,
+           accumulate);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t zn = (size_t)N * OH * OW * z_ld, xn = (size_t)N * H * W * x_ld, gn = (size_t)N * OH * OW * g_ld, gin_n = (size_t)N * H * W * gin_ld;
+  const size_t act = zn + xn, grad = gn + gin_n, wp = use_wpart ? (size_t)JN_NREP * JN_WPART_MAX : 0;
+  float* ws = nullptr;
+  JN_HIP(hipMalloc((void**)&ws, ((size_t)n_slots * (act + grad) + wp) * sizeof(float)));
+  float *za = ws, *xa = za + zn, *ga = ws + (size_t)n_slots * act, *gina = ga + gn, *wpart = use_wpart ? ws + (size_t)n_slots * (act + grad) : nullptr;
+  auto lay = [&](float* dst, size_t dst_slot, const float* src, size_t n, bool back) {
+    return back ? hipMemcpy2DAsync(const_cast<float*>(src), n * sizeof(float), dst, dst_slot * sizeof(float), n * sizeof(float), n_slots, hipMemcpyDeviceToDevice, s)
+                : hipMemcpy2DAsync(dst, dst_slot * sizeof(float), src, n * sizeof(float), n * sizeof(float), n_slots, hipMemcpyDeviceToDevice, s);
+  };
+  hipError_t e = lay(za, act, z_dev, zn, false);
+  if (e == hipSuccess) e = lay(xa, act, x_dev, xn, false);
+  if (e == hipSuccess) e = lay(ga, grad, g_dev, gn, false);
+  if (e == hipSuccess) e = lay(gina, grad, gin_dev, gin_n, false);      // always: the channels past C and, with accumulate, the previous gradient
+  if (e == hipSuccess && wpart) e = hipMemsetAsync(wpart, 0, wp * sizeof(float), s);
+  int rc = -1;
+  if (e == hipSuccess) {
+    SlotBatch sb;
+    sb.n = n_slots; sb.act = (long long)act; sb.grad = (long long)grad; sb.tab = 3LL * C; sb.save = 2LL * C; sb.consts = 3LL * C;
+    sb.red = (long long)JN_NREP * 2 * C;
+    const ChanTab ot = dw_tab(otab_dev, C), it = dw_tab(itab_dev, C);
+    if (route == 1) {
+      DwBwdFusedArgs fa{};
+      fa.g = ga; fa.g_ld = g_ld; fa.z = za; fa.z_ld = z_ld; fa.ot = ot; fa.save = save_dev; fa.consts = consts_dev;
+      fa.x = xa; fa.x_ld = x_ld; fa.it = it; fa.w = w_dev;
+      fa.gin = gina; fa.gin_ld = gin_ld; fa.accumulate = accumulate ? 1 : 0; fa.gw = gw_dev; fa.wpart = wpart;
+      fa.C = C; fa.H = H; fa.W = W; fa.OH = OH; fa.OW = OW; fa.N = N; fa.stride = stride; fa.sb = sb;
+      fa.red_in = red_out_dev; fa.red_rep_stride = 2LL * C; fa.max_wg = max_wg;
+      rc = launch_dw_bwd_fused(fa, s);
+    } else {      // BR_DW of the conv-stack backward (api_net.hip)
+      const long long M = (long long)N * OH * OW;
+      rc = launch_bn_bwd_gz(ga, g_ld, za, z_ld, ot, save_dev, consts_dev, C, M, s, sb);
+      if (rc == 0) rc = launch_dw_bwd_data(ga, g_ld, w_dev, gina, gin_ld, C, H, W, OH, OW, N, stride, accumulate ? 1 : 0, s, sb);
+      if (rc == 0) rc = launch_dw_bwd_weight(ga, g_ld, xa, x_ld, it, gw_dev, wpart, C, H, W, OH, OW, N, stride, s, sb, max_wg);
+    }
+    e = hipGetLastError();
+    if (e == hipSuccess) e = lay(gina, grad, gin_dev, gin_n, true);
+    if (e == hipSuccess && wpart) e = hipMemcpyAsync(wpart_back_dev, wpart, wp * sizeof(float), hipMemcpyDeviceToDevice, s);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(ws);
+  JN_HIP(e);
+  JN_CHECK(rc == 0, JN_EINVAL, "jn_dw_bwd: no kernel took the launch");
+  return JN_OK;
+}
+
+}  // extern "C"

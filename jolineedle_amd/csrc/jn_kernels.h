@@ -130,7 +130,10 @@ bool dwpw_supported(int C, int cout, int stride);
 int launch_dwpw(const DwPwArgs& a, hipStream_t s);
 int launch_stem(const StemArgs& a, hipStream_t s);
 bool stem_rows_aligned(const StemArgs& a);        // the stem kernels may fetch the image tile with 4-element loads
-int launch_dw(const ConvArgs& a, hipStream_t s);
+// depthwise 3x3: the route of a launch (forced = 0: the launcher's rule; a forced route that does not admit the launch: -1)
+enum { DW_ROUTE_LDS = 1, DW_ROUTE_STRIP = 2 };      // dw3x3_lds_kernel (C % 16 == 0, N <= 65535), dw3x3_kernel
+int dw_route(const ConvArgs& a, int forced);
+int launch_dw(const ConvArgs& a, hipStream_t s, int route = 0);
 // ---- 1x1 convs: THE route of a launch (kernels_conv.hip) ------------------------------------------------------------
 // Which kernel family runs a 1x1 conv is decided once, by pw_route, a pure function of the arguments (and of the test hook
 // JN_PWN_MIN_M); launch_pw is a switch over it, and a launcher handed its route launches or fails (-1: no instantiation, or
@@ -318,6 +321,7 @@ struct DwBwdFusedArgs {                  // the depthwise counterpart (3x3, pad 
   int C, H, W, OH, OW, N, stride;
   SlotBatch sb;
   double* red_in; long long red_rep_stride;      // as in PwBwdFusedArgs
+  int max_wg;                            // debug entry: > 0 caps the persistent workgroups per channel block and slot
 };
 bool dw_bwd_fused_supported(int C, int H, int W, int OH, int OW, int stride);
 int launch_dw_bwd_fused(const DwBwdFusedArgs& a, hipStream_t s);
@@ -329,7 +333,8 @@ int launch_pw_bwd_fused(const PwBwdFusedArgs& a, hipStream_t s);
 int launch_dw_bwd_data(const float* gz, int g_ld, const float* w, float* gin, int gin_ld, int C, int H, int W, int OH,
                        int OW, int N, int stride, int accumulate, hipStream_t s, const SlotBatch& sb = SlotBatch{});
 int launch_dw_bwd_weight(const float* gz, int g_ld, const float* x, int x_ld, ChanTab it, float* gw, float* wpart, int C,
-                         int H, int W, int OH, int OW, int N, int stride, hipStream_t s, const SlotBatch& sb = SlotBatch{});
+                         int H, int W, int OH, int OW, int N, int stride, hipStream_t s, const SlotBatch& sb = SlotBatch{},
+                         int max_wg = 0);      // debug entry: > 0 caps the workgroups per slot
 // gz is d loss / d activation of the stem's output z: the BN + SiLU backward (g_z) is applied while staging
 int launch_stem_bwd_weight(const StemArgs& a, const float* gz, int g_ld, float* gw, float* wpart, hipStream_t s,
                            const SlotBatch& sb, const float* z, int z_ld, ChanTab ot, const float* save, const float* consts);

@@ -248,7 +248,9 @@ __global__ __launch_bounds__(256) void dw_bwd_weight_kernel(const float* __restr
   const int YS = (OH + 3) >> 2;
   const long long total = (long long)N * YS * OW * C4;
   const long long idx0 = (long long)blockIdx.x * 256 + threadIdx.x;
-  const long long gstride = (long long)gridDim.x * 256;          // multiple of C4: the channel group stays fixed
+  // the grid's threads in whole rows of C4: a thread's channel group stays fixed over its strips whatever the grid
+  // (C = 48: 256 gridDim.x is a multiple of C4 = 12 only for some grids; the threads past the last whole row idle)
+  const long long gstride = (long long)gridDim.x * 256 / C4 * C4;
   {
     const int c = (int)(idx0 % C4) * 4;
     const f32x4 sc = *reinterpret_cast<const f32x4*>(it.sc + c), sh = *reinterpret_cast<const f32x4*>(it.sh + c),
@@ -256,7 +258,7 @@ __global__ __launch_bounds__(256) void dw_bwd_weight_kernel(const float* __restr
     f32x4 dw[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t) dw[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (long long idx = idx0; idx < total; idx += gstride) {
+    for (long long idx = idx0 < gstride ? idx0 : total; idx < total; idx += gstride) {
     const int ox = (int)((idx / C4) % OW);
     const int ys = (int)((idx / ((long long)C4 * OW)) % YS);
     const long long n = idx / ((long long)C4 * OW * YS);
@@ -285,25 +287,38 @@ __global__ __launch_bounds__(256) void dw_bwd_weight_kernel(const float* __restr
       }
     }
     }
-    // lanes l, l + C4, l + 2*C4, ... of a wave hold the same channel group: butterfly-sum them first so that
-    // only C4 lanes per wave touch the (slow) LDS float atomics
-    const int lane = threadIdx.x & 63;
+    // one wave after the other: the fp32 sums of a workgroup do not depend on which wave reaches its LDS atomics first
+    for (int turn = 0; turn < 4; ++turn) {
+      if ((int)(threadIdx.x >> 6) == turn) {
+        if ((C4 & (C4 - 1)) == 0) {
+          // lanes l, l + C4, l + 2*C4, ... of a wave hold the same channel group: butterfly-sum them first so that
+          // only C4 lanes per wave touch the (slow) LDS float atomics
+          const int lane = threadIdx.x & 63;
 #pragma unroll
-    for (int t = 0; t < 9; ++t)
+          for (int t = 0; t < 9; ++t)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        float v = dw[t][q];
-        for (int off = C4; off < 64; off <<= 1) v += __shfl_xor(v, off);
-        if (lane < C4) atomicAdd(&red[t * C + c + q], v);
+            for (int q = 0; q < 4; ++q) {
+              float v = dw[t][q];
+              for (int off = C4; off < 64; off <<= 1) v += __shfl_xor(v, off);
+              if (lane < C4) atomicAdd(&red[t * C + c + q], v);
+            }
+        } else if (idx0 < total) {
+          // any other count (C = 48: C4 = 12): idx % C4 is not lane % C4, every thread adds its own sums
+#pragma unroll
+          for (int t = 0; t < 9; ++t)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) atomicAdd(&red[t * C + c + q], dw[t][q]);
+        }
       }
+      __syncthreads();
+    }
   }
-  __syncthreads();
   float* dst = rep ? gw + ((blockIdx.x + 5 * blockIdx.y) % JN_NREP) * JN_WPART_MAX : gw;
   for (int i = threadIdx.x; i < 9 * C; i += 256) atomicAdd(&dst[i], red[i]);
 }
 
 int launch_dw_bwd_weight(const float* gz, int g_ld, const float* x, int x_ld, ChanTab it, float* gw_final, float* wpart,
-                         int C, int H, int W, int OH, int OW, int N, int stride, hipStream_t s, const SlotBatch& sb) {
+                         int C, int H, int W, int OH, int OW, int N, int stride, hipStream_t s, const SlotBatch& sb, int max_wg) {
   const int rep = (wpart && 9 * C <= JN_WPART_MAX) ? 1 : 0;
   float* gw = rep ? wpart : gw_final;
   const int YS = (OH + 3) / 4;
@@ -311,6 +326,8 @@ int launch_dw_bwd_weight(const float* gz, int g_ld, const float* x, int x_ld, Ch
   long long nb = (total + 255) / 256;
   const long long cap = sb.n >= 8 ? 256 : 2048 / sb.n;
   if (nb > cap) nb = cap;                         // grid-stride: each thread folds many strips before its atomics
+  if (max_wg > 0 && nb > max_wg) nb = max_wg;
+  if (nb * 256 < C / 4) nb = (C / 4 + 255) / 256;      // at least one whole row of channel groups
   const dim3 blocks((unsigned)nb, sb.n);
   const size_t smem = (size_t)9 * C * sizeof(float);
 #define JN_DWW(S_) \
@@ -346,8 +363,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void d
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* Gs = sm;                        // [GH*GW][PS] g_z
   float* As = Gs + GH * GW * PS;         // [AH*AW][PS] activated input
-  float* red = As + AH * AW * PS;        // [9][CB]
-  float* Cs = red + 11 * CB;             // [7][CB] output-side constants, [3][CB] input table, [9][CB] weights (registers
+  float* Cs = As + AH * AW * PS;         // [7][CB] output-side constants, [3][CB] input table, [9][CB] weights (registers
                                          // are the occupancy limit of this kernel)
   {
     const long long sl = blockIdx.y;
@@ -360,7 +376,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void d
   const int tid = threadIdx.x;
   const int ncb = C / CB, cb = blockIdx.x % ncb;
   const int q = tid % Q, c = cb * CB + 4 * q;
-  for (int i = tid; i < 11 * CB; i += 256) red[i] = 0.0f;
   for (int i = tid; i < CB; i += 256) {
     const int cc = cb * CB + i;
     Cs[i] = ot.sc[cc]; Cs[CB + i] = ot.sh[cc]; Cs[2 * CB + i] = save[2 * cc]; Cs[3 * CB + i] = save[2 * cc + 1];
@@ -504,29 +519,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void d
       }
     }
   }
-  // lanes l, l + Q, ... hold the same channel quad: butterfly, then Q lanes per wave add into LDS
+  // lanes l, l + Q, ... hold the same channel quad: butterfly, then Q lanes per wave store the wave's sums in the wave's own
+  // 11 x CB floats of the g_z tile (free after the last tile); the four are added in wave order, so the fp32 sums of a
+  // workgroup do not depend on the waves' timing, as sums formed with LDS atomics would
+  static_assert(4 * 11 * CB <= GH * GW * PS, "per-wave sums fit the g_z tile");
   const int lane = tid & 63;
+  __syncthreads();
+  float* part = Gs + (tid >> 6) * 11 * CB;
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       float v = dw[t][k];
       for (int off = Q; off < 64; off <<= 1) v += __shfl_xor(v, off);
-      if (lane < Q) atomicAdd(&red[t * CB + 4 * q + k], v);
+      if (lane < Q) part[t * CB + 4 * q + k] = v;
     }
   if (RED) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       float a = r1[k], b = r2[k];
       for (int off = Q; off < 64; off <<= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); }
-      if (lane < Q) { atomicAdd(&red[9 * CB + 2 * (4 * q + k)], a); atomicAdd(&red[9 * CB + 2 * (4 * q + k) + 1], b); }
+      if (lane < Q) { part[9 * CB + 2 * (4 * q + k)] = a; part[9 * CB + 2 * (4 * q + k) + 1] = b; }
     }
   }
   __syncthreads();
+  auto wsum = [&](int i) { return ((Gs[i] + Gs[11 * CB + i]) + Gs[22 * CB + i]) + Gs[33 * CB + i]; };
   float* dst = (rep ? gw + ((wg + 5 * blockIdx.y) % JN_NREP) * JN_WPART_MAX : gw);
-  for (int i = tid; i < 9 * CB; i += 256) atomicAdd(&dst[(i / CB) * C + cb * CB + (i % CB)], red[i]);
+  for (int i = tid; i < 9 * CB; i += 256) atomicAdd(&dst[(i / CB) * C + cb * CB + (i % CB)], wsum(i));
   if (RED)
-    if (tid < 2 * CB) atomicAdd(&red_in[(wg % JN_NREP) * red_rep_stride + 2 * cb * CB + tid], (double)red[9 * CB + tid]);
+    if (tid < 2 * CB) atomicAdd(&red_in[(wg % JN_NREP) * red_rep_stride + 2 * cb * CB + tid], (double)wsum(9 * CB + tid));
 #undef JN_C4
 }
 
@@ -535,12 +556,13 @@ static void launch_dw_bwd_fused_r(const DwBwdFusedArgs& a, hipStream_t s) {
   constexpr int PS = S == 1 ? CB : CB + JN_DW_S2_PAD;
   constexpr int GH = S == 1 ? DF_TH + 2 : DF_TH + 1, GW = S == 1 ? DF_TW + 2 : DF_TW + 1;
   constexpr int AH = S == 1 ? DF_TH + 2 : 2 * DF_TH + 1, AW = S == 1 ? DF_TW + 2 : 2 * DF_TW + 1;
-  const size_t smem = ((size_t)(GH * GW + AH * AW) * PS + 11 * CB + 19 * CB) * sizeof(float);
+  const size_t smem = ((size_t)(GH * GW + AH * AW) * PS + 19 * CB) * sizeof(float);
   const int tiles_x = (a.OW + DF_TW - 1) / DF_TW, tiles_y = (a.OH + DF_TH - 1) / DF_TH;
   const int n_tiles = tiles_x * tiles_y * a.N, ncb = a.C / CB;
   int n_wg = 1536 / (ncb * a.sb.n);                 // persistent: one set of weight-gradient atomics per workgroup
   if (n_wg < 8) n_wg = 8;
   if (n_wg > n_tiles) n_wg = n_tiles;
+  if (a.max_wg > 0 && n_wg > a.max_wg) n_wg = a.max_wg;
   const int rep = (a.wpart && 9 * a.C <= JN_WPART_MAX) ? 1 : 0;
   hipLaunchKernelGGL((dw_bwd_fused_kernel<S, CB, DF_TH, RED>), dim3((unsigned)(n_wg * ncb), a.sb.n), dim3(256), smem, s, a.g, a.g_ld, a.z,
                      a.z_ld, a.ot, a.save, a.consts, a.x, a.x_ld, a.it, a.w, a.gin, a.gin_ld, a.accumulate,

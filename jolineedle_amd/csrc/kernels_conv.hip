@@ -214,7 +214,7 @@ template <int S, typename AT>
 __global__ __launch_bounds__(256) void dw3x3_kernel(
     const AT* __restrict__ in, int in_ld, ChanTab it, const float* __restrict__ w, AT* __restrict__ out,
     int out_ld, int C, int H, int W, int OH, int OW, int N, double* __restrict__ stats, long long rep_stride,
-    const int* __restrict__ skip_flag, int skip_when) {
+    const int* __restrict__ skip_flag, int skip_when, int nrep) {
   if (skip_flag && *skip_flag >= skip_when) return;
   extern __shared__ float red[];   // [C][2] when stats
   if (stats) {
@@ -273,18 +273,33 @@ __global__ __launch_bounds__(256) void dw3x3_kernel(
     }
   }
   if (stats) {
-    const int lane = threadIdx.x & 63;         // lanes l, l + C4, ... share the channel group: butterfly first
+    // one wave after the other: the fp32 sums of a workgroup do not depend on which wave reaches its LDS atomics first
+    for (int turn = 0; turn < 4; ++turn) {
+      if ((int)(threadIdx.x >> 6) == turn) {
+        if ((C4 & (C4 - 1)) == 0) {
+          // power-of-two channel groups: lanes l, l + C4, ... share the channel group (256 % C4 == 0): butterfly first
+          const int lane = threadIdx.x & 63;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      float a = s1[q], b = s2[q];
-      for (int off = C4; off < 64; off <<= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); }
-      if (lane < C4) {
-        atomicAdd(&red[2 * (cstat + q)], a);
-        atomicAdd(&red[2 * (cstat + q) + 1], b);
+          for (int q = 0; q < 4; ++q) {
+            float a = s1[q], b = s2[q];
+            for (int off = C4; off < 64; off <<= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); }
+            if (lane < C4) {
+              atomicAdd(&red[2 * (cstat + q)], a);
+              atomicAdd(&red[2 * (cstat + q) + 1], b);
+            }
+          }
+        } else if (idx < total) {
+          // any other count (C = 48: C4 = 12): idx % C4 is not lane % C4, every thread adds its own sums
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            atomicAdd(&red[2 * (cstat + q)], s1[q]);
+            atomicAdd(&red[2 * (cstat + q) + 1], s2[q]);
+          }
+        }
       }
+      __syncthreads();
     }
-    __syncthreads();
-    double* st = stats + (blockIdx.x % JN_NREP) * rep_stride;
+    double* st = stats + (blockIdx.x % nrep) * rep_stride;
     for (int i = threadIdx.x; i < 2 * C; i += 256) atomicAdd(&st[i], (double)red[i]);
   }
 }
@@ -627,11 +642,23 @@ static void launch_dw_t(const ConvArgs& a, hipStream_t s) {      // any channel 
   const size_t smem = a.stats ? (size_t)2 * a.cin * sizeof(float) : 0;
   hipLaunchKernelGGL((dw3x3_kernel<S, T>), dim3((unsigned)((total + 255) / 256)), dim3(256), smem, s, (const T*)a.in, a.in_ld, a.itab,
                      a.w, (T*)a.out, a.out_ld, a.cin, a.H, a.W, a.OH, a.OW, a.N, a.stats, a.stats_rep_stride, a.skip_flag,
-                     a.skip_when);
+                     a.skip_when, a.stats_nrep > 0 ? a.stats_nrep : JN_NREP);
 }
 
-int launch_dw(const ConvArgs& a, hipStream_t s) {
-  if (a.cin % 16 == 0 && a.N <= 65535) {
+// The LDS-tiled kernel takes whole blocks of 16 channels and one image per grid row; everything else (and a forced
+// DW_ROUTE_STRIP) goes to the strip kernel, which reads the plain table only: in the networks it is reached at N > 65535,
+// where no entry is deferred.
+int dw_route(const ConvArgs& a, int forced) {
+  const bool lds_ok = a.cin % 16 == 0 && a.N <= 65535;
+  if (forced == DW_ROUTE_LDS) return lds_ok ? DW_ROUTE_LDS : -1;
+  if (forced == DW_ROUTE_STRIP) return a.cin % 4 == 0 ? DW_ROUTE_STRIP : -1;
+  return forced == 0 ? (lds_ok ? DW_ROUTE_LDS : DW_ROUTE_STRIP) : -1;
+}
+
+int launch_dw(const ConvArgs& a, hipStream_t s, int route) {
+  route = dw_route(a, route);
+  if (route < 0) return -1;
+  if (route == DW_ROUTE_LDS) {
     const bool bf = a.in_dtype == JN_BF16;
     if (a.stride == 1) {
       if (a.cin % 32 == 0) { if (bf) launch_dw_lds<1, 32, 8, bf16_t>(a, s); else launch_dw_lds<1, 32, 8, float>(a, s); }
