@@ -765,6 +765,59 @@ int jn_dw_bwd(const float* g_dev, int g_ld, const float* z_dev, int z_ld, const 
               const float* itab_dev, const float* save_dev, const float* consts_dev, const float* w_dev, float* gin_dev, int gin_ld,
               int accumulate, float* gw_dev, double* red_out_dev, int N, int H, int W, int C, int stride, int n_slots, int route,
               int use_wpart, float* wpart_back_dev, int max_wg, void* stream);
+/* Debug entries, context-free: ONE launch of a 1x1 (pointwise) conv kernel (csrc/kernels_conv.hip, kernels_pwres.hip,
+ * kernels_pwxs.hip; the weight gradient in kernels_bwd_pw.hip) on caller tensors, then a wait for `stream`.  Maps are [M][ld] with
+ * M = N * H * W pixels and a leading dimension that may exceed the channel count: channels past it are neither read nor written.
+ * Common JN_EINVAL, before any device call: a null pointer (but the optional ones), N, H, W or M < 1, M > 2^24, a channel count
+ * below 4, above 4096 or no multiple of 4, a leading dimension below its channel count, no multiple of 4 or above 8192, n_slots
+ * outside 1..64, a forced route whose kernels do not admit the launch, max_wg < 0.
+ *
+ * jn_pw: out (=|+=) act(T(in) . w^T + bias), T(x) = flag ? silu(scale * x + shift) : x from tab f32 [3][cin] (rows scale, shift,
+ * flag).  w f32 [cout][cin]; transposed != 0: w is [cin][cout], the forward weight of the layer whose data gradient this is.
+ * dtype_in / dtype_out: 0 = f32, 1 = bf16 maps; bf16_mfma != 0: the products run on the bf16 matrix pipe (required with bf16 input).
+ * in_identity != 0 promises a table of flags 0 (kernels may compile the transform out).  bias_dev f32 [cout] or NULL; act 0 = none,
+ * 1 = silu, 2 = relu, 3 = sigmoid.  stats_dev: NULL, or f64 [nrep][2 cout] (nrep 1..32) that the launch ADDS per-channel (sum, sum of
+ * squares) of the stored fp32 values into; replicas past nrep are not touched.  skip_flag_dev: NULL, or a device int; nothing is done
+ * when *skip_flag_dev >= skip_when.  n_slots > 1: slot j reads in + j * in_slot_stride, writes out + j * out_slot_stride (elements,
+ * multiples of 4, at least M * ld) and reads the table rows at + j * tab_slot_stride floats each (0: one table for all).
+ * up_out_dev: NULL, or f32 [N][2H][2W][up_ld] that also receives the output upsampled nearest x2 (the routes and shapes of
+ * pw_fuses_upsample only: X3 128 -> 64 and 256 -> 128, XS 256 -> 128).  route: 0 = the rule of pw_route with the split planes
+ * present (what the networks get), else 1 = X1 (bf16 maps, single plane), 2 = X3 (three bf16 planes), 3 = XS, 4 = WIDE (pw_dir_kernel),
+ * 5 = NARROW, 6 = MFMA.  For X1 and X3 the call splits w itself with the context's splitters (flat planes, then fragment order where
+ * pw_x3_fragment_order says so).  max_wg: 0 = the launcher's rule, else a cap on the x extent of the persistent grid (1: one
+ * workgroup walks every pixel tile); MFMA has no persistent grid and refuses max_wg > 0.
+ * defer: NULL = a plain table, else the input view's deferred BatchNorm entries (one slot only): f64 batch sums
+ * [8][rep_stride] ((sum, sum of squares) of stat channel i at [2 i] of a replica), a parameter buffer with the BatchNorm weights and
+ * biases, dN patches, the deferral limit dmax and 1..4 ascending channel runs: channels [c0, c1) are stat channels stat0 + (c - c0)
+ * with weight / bias at params[g0 / b0 + (c - c0)] over dN * hw pixels; stat0 < 0, or dN * hw > dmax: the run reads tab.  use_runs != 0
+ * hands the runs to the kernel as they are (ChanTab::r0..r3), 0 expands them into the per-channel arrays (dsrc / dhw / dgoff / dboff).
+ * jn_pw_route: host only, no device call: with route = 0 the route (1..6) the rule gives that launch, else `route` itself where
+ * that family's kernels admit the launch (JN_EINVAL where not); for route 6 variant_out (int32 [3], or NULL) receives pw_mfma_kernel's tile variant (CT channel tiles, KC chunk, WM pixel waves: 32 WM pixels per workgroup), else zeros.
+ * jn_pw_bwd_data_x3: the data gradient of a wide layer on the split pipe (launch_pw_x3_bwd_data): gx [S][M][gx_ld] = gz [S][M][g_ld] . w,
+ * w f32 [cout][cin] the forward weight, (cout, cin) one of (256, 128), (256, 256), (256, 512), (128, 256).  Allocates the transposed
+ * planes and frees them.
+ * jn_pw_bwd_weight: gw [cout][cin] += sum over slots and pixels of gz[m][n] * T(x)[m][k]; gz slot j at + j * gz_slot_stride floats,
+ * x [S][M][x_ld], tab [S][3][cin].  use_wpart != 0 (cout * cin <= 16384, below 128 x 128): through a zeroed [32][16384] replica
+ * scratch, copied to wpart_back_dev (required then) after the launch, where it must be zero again.  exact != 0 (both counts >= 128):
+ * the wide kernel with exact fp32 products (what JN_WW_EXACT=1 makes the rule pick), else its split products. */
+typedef struct jn_pw_run { int32_t c0, c1, stat0, g0, b0; float hw; } jn_pw_run;
+typedef struct jn_pw_defer {
+  const double* sums_dev; long long rep_stride; const float* params_dev;
+  int32_t dN; long long dmax;
+  int32_t n_runs, use_runs;
+  jn_pw_run run[4];
+} jn_pw_defer;
+int jn_pw(const void* in_dev, int in_ld, int dtype_in, const float* tab_dev, const jn_pw_defer* defer, const float* w_dev,
+          const float* bias_dev, void* out_dev, int out_ld, int dtype_out, int N, int H, int W, int cin, int cout, int bf16_mfma,
+          int transposed, int in_identity, int accumulate, int act, double* stats_dev, int nrep, const int* skip_flag_dev, int skip_when,
+          int n_slots, long long in_slot_stride, long long out_slot_stride, long long tab_slot_stride, float* up_out_dev, int up_ld,
+          int route, int max_wg, void* stream);
+int jn_pw_route(int N, int H, int W, int cin, int cout, int in_ld, int out_ld, int dtype_in, int dtype_out, int bf16_mfma, int transposed,
+                int accumulate, int has_bias, int act, int n_slots, int has_up, int route, int32_t* variant_out);
+int jn_pw_bwd_data_x3(const float* gz_dev, int g_ld, const float* w_dev, float* gx_dev, int gx_ld, long long M, int cout, int cin,
+                      int n_slots, int max_wg, void* stream);
+int jn_pw_bwd_weight(const float* gz_dev, int g_ld, const float* x_dev, int x_ld, const float* tab_dev, float* gw_dev, long long M, int cout,
+                     int cin, int n_slots, long long gz_slot_stride, int use_wpart, float* wpart_back_dev, int exact, void* stream);
 /* Arms the following rollouts of `ctx` with that teacher (the per-step `best_action` that test_model_on_env compares
  * each chosen action with, src/supervised.py:279-405): before the decision of step t, the set of the state that
  * decision sees (position and visited patches before the step) goes to sets_dev[b * T + t] (uint8 [B,T], T =

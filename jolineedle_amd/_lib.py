@@ -62,7 +62,16 @@ class JnImageView(C.Structure):
                 ("ty", C.c_int32), ("tx", C.c_int32)]
 
 
-ABI_VERSION = 2      # JN_ABI_VERSION of include/jnroll.h
+class JnPwRun(C.Structure):
+    _fields_ = [("c0", C.c_int32), ("c1", C.c_int32), ("stat0", C.c_int32), ("g0", C.c_int32), ("b0", C.c_int32), ("hw", C.c_float)]
+
+
+class JnPwDefer(C.Structure):      # jn_pw's deferred-table descriptor
+    _fields_ = [("sums_dev", C.c_void_p), ("rep_stride", C.c_longlong), ("params_dev", C.c_void_p), ("dN", C.c_int32),
+                ("dmax", C.c_longlong), ("n_runs", C.c_int32), ("use_runs", C.c_int32), ("run", JnPwRun * 4)]
+
+
+ABI_VERSION = 2     # JN_ABI_VERSION of include/jnroll.h
 
 # name -> (restype, argtypes); every symbol include/jnroll.h declares
 SIGNATURES = {
@@ -160,6 +169,14 @@ SIGNATURES = {
                          [C.c_void_p, C.c_int, C.c_void_p]),
     "jn_dw_bwd": (C.c_int, [C.c_void_p, C.c_int] * 3 + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 8 +
                            [C.c_void_p, C.c_int, C.c_void_p]),
+    "jn_pw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_int] * 10 +
+                       [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, C.c_int,
+                        C.c_int, C.c_void_p]),
+    "jn_pw_route": (C.c_int, [C.c_int] * 17 + [C.c_void_p]),
+    "jn_pw_bwd_data_x3": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_void_p]),
+    "jn_pw_bwd_weight": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int,
+                                   C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "jn_set_rollout_teacher":(C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "jn_set_rollout_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "jn_rollout_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),

@@ -619,3 +619,227 @@ int jn_dw_bwd(const float* g_dev, int g_ld, const float* z_dev, int z_ld, const 
 }
 
 }  // extern "C"
+
+// ---- 1x1 (pointwise) kernels on caller tensors (kernels_conv.hip, kernels_pwres.hip, kernels_pwxs.hip, kernels_bwd_pw.hip) ---------
+// What the entries check of a shape before anything else: M = N * H * W pixels; H and W matter to the fused upsample alone
+static bool pw_ld_ok(int ld, int C) { return ld >= C && ld % 4 == 0 && ld <= 8192; }
+static bool pw_chan_ok(int C) { return C >= 4 && C % 4 == 0 && C <= 4096; }
+static bool pw_shape_ok(int N, int H, int W, int cin, int cout, int in_ld, int out_ld, int n_slots) {
+  return N >= 1 && H >= 1 && W >= 1 && (long long)N * H * W <= (1 << 24) && pw_chan_ok(cin) && pw_chan_ok(cout) && pw_ld_ok(in_ld, cin) &&
+         pw_ld_ok(out_ld, cout) && n_slots >= 1 && n_slots <= 64;
+}
+static bool pw_flags_ok(int dtype_in, int dtype_out, int act) {
+  return (dtype_in == JN_F32 || dtype_in == JN_BF16) && (dtype_out == JN_F32 || dtype_out == JN_BF16) && act >= ACT_NONE && act <= ACT_SIGMOID;
+}
+
+// the launch of jn_pw / jn_pw_route without its pointers; `some` stands for every optional pointer that is given, and for the split
+// planes, which the entry makes whenever the route reads them (what the networks have unless JN_NO_PW_X3 is set)
+static ConvArgs pw_entry_args(int N, int H, int W, int cin, int cout, int in_ld, int out_ld, int dtype_in, int dtype_out, int bf16_mfma,
+                              int transposed, int in_identity, int accumulate, bool has_bias, int act, int n_slots, bool has_up, const void* some) {
+  ConvArgs a{};
+  a.in_ld = in_ld; a.in_dtype = dtype_in; a.out_ld = out_ld; a.out_dtype = dtype_out; a.bf16_mfma = bf16_mfma ? 1 : 0;
+  a.N = N; a.H = a.OH = H; a.W = a.OW = W; a.cin = cin; a.cout = cout; a.stride = 1; a.act = act;
+  a.accumulate = accumulate ? 1 : 0; a.w_transposed = transposed ? 1 : 0; a.in_identity = in_identity ? 1 : 0; a.n_slots = n_slots;
+  a.bias = has_bias ? (const float*)some : nullptr; a.w_x3 = some; a.up_out = has_up ? const_cast<void*>(some) : nullptr;
+  return a;
+}
+
+// the runs of a descriptor: ascending, disjoint, inside [0, cin); a deferred run's sums inside one replica
+static bool pw_defer_ok(const jn_pw_defer* d, int cin) {
+  if (!d->sums_dev || !d->params_dev || d->dN < 1 || d->dmax < 0 || d->n_runs < 1 || d->n_runs > 4 || d->rep_stride < 2) return false;
+  int prev = 0;
+  for (int i = 0; i < d->n_runs; ++i) {
+    const jn_pw_run& r = d->run[i];
+    if (r.c0 < prev || r.c1 <= r.c0 || r.c1 > cin || !(r.hw >= 1.0f)) return false;
+    if (r.stat0 >= 0 && (r.g0 < 0 || r.b0 < 0 || 2LL * (r.stat0 + (r.c1 - r.c0)) > d->rep_stride)) return false;
+    prev = r.c1;
+  }
+  return true;
+}
+
+extern "C" {
+
+int jn_pw_route(int N, int H, int W, int cin, int cout, int in_ld, int out_ld, int dtype_in, int dtype_out, int bf16_mfma, int transposed,
+                int accumulate, int has_bias, int act, int n_slots, int has_up, int route, int32_t* variant_out) {
+  JN_CHECK(pw_shape_ok(N, H, W, cin, cout, in_ld, out_ld, n_slots) && pw_flags_ok(dtype_in, dtype_out, act), JN_EINVAL,
+           "jn_pw_route: %d x %d x %d, %d -> %d channels, leading dimensions %d and %d, dtypes %d -> %d, act %d, %d slots", N, H, W, cin, cout,
+           in_ld, out_ld, dtype_in, dtype_out, act, n_slots);
+  static const float some = 0.0f;
+  const ConvArgs a = pw_entry_args(N, H, W, cin, cout, in_ld, out_ld, dtype_in, dtype_out, bf16_mfma, transposed, 0, accumulate, has_bias != 0,
+                                   act, n_slots, has_up != 0, &some);
+  JN_CHECK(route >= 0 && route <= PW_MFMA, JN_EINVAL, "jn_pw_route: route=%d", route);
+  const PwRoute r = pw_route(a, route);
+  JN_CHECK(r != PW_NONE, JN_EINVAL, route ? "jn_pw_route: route %d does not take this launch" : "jn_pw_route: no 1x1 kernel takes this launch", route);
+  if (variant_out) {
+    variant_out[0] = variant_out[1] = variant_out[2] = 0;
+    if (r == PW_MFMA) {
+      const PwMfmaVariant v = pw_mfma_variant(a);
+      variant_out[0] = v.ct; variant_out[1] = v.kc; variant_out[2] = v.wm;
+    }
+  }
+  return (int)r;
+}
+
+int jn_pw(const void* in_dev, int in_ld, int dtype_in, const float* tab_dev, const jn_pw_defer* defer, const float* w_dev,
+          const float* bias_dev, void* out_dev, int out_ld, int dtype_out, int N, int H, int W, int cin, int cout, int bf16_mfma,
+          int transposed, int in_identity, int accumulate, int act, double* stats_dev, int nrep, const int* skip_flag_dev, int skip_when,
+          int n_slots, long long in_slot_stride, long long out_slot_stride, long long tab_slot_stride, float* up_out_dev, int up_ld,
+          int route, int max_wg, void* stream) {
+  JN_CHECK(in_dev && tab_dev && w_dev && out_dev, JN_EINVAL, "jn_pw: null argument");
+  JN_CHECK(pw_shape_ok(N, H, W, cin, cout, in_ld, out_ld, n_slots) && pw_flags_ok(dtype_in, dtype_out, act), JN_EINVAL,
+           "jn_pw: %d x %d x %d, %d -> %d channels, leading dimensions %d and %d, dtypes %d -> %d, act %d, %d slots", N, H, W, cin, cout, in_ld,
+           out_ld, dtype_in, dtype_out, act, n_slots);
+  const long long M = (long long)N * H * W;
+  JN_CHECK(nrep >= 1 && nrep <= JN_NREP && route >= 0 && route <= PW_MFMA && max_wg >= 0, JN_EINVAL, "jn_pw: nrep=%d route=%d max_wg=%d", nrep,
+           route, max_wg);
+  JN_CHECK(in_slot_stride >= 0 && out_slot_stride >= 0 && tab_slot_stride >= 0 &&
+               (n_slots == 1 || (in_slot_stride >= M * in_ld && out_slot_stride >= M * out_ld && in_slot_stride % 4 == 0 &&
+                                 out_slot_stride % 4 == 0 && tab_slot_stride % 4 == 0)),
+           JN_EINVAL, "jn_pw: slot strides %lld, %lld and %lld", in_slot_stride, out_slot_stride, tab_slot_stride);
+  JN_CHECK(!up_out_dev || (pw_ld_ok(up_ld, cout) && dtype_out == JN_F32), JN_EINVAL, "jn_pw: the upsampled copy is fp32 with up_ld=%d >= %d",
+           up_ld, cout);
+  JN_CHECK(!defer || (n_slots == 1 && pw_defer_ok(defer, cin)), JN_EINVAL,
+           "jn_pw: a deferred table takes one slot, 1..4 ascending runs inside the %d input channels, sums and parameters", cin);
+  float* tab = const_cast<float*>(tab_dev);
+  ConvArgs a = pw_entry_args(N, H, W, cin, cout, in_ld, out_ld, dtype_in, dtype_out, bf16_mfma, transposed, in_identity, accumulate,
+                             bias_dev != nullptr, act, n_slots, up_out_dev != nullptr, w_dev);
+  const PwRoute r = pw_route(a, route);
+  JN_CHECK(r != PW_NONE, JN_EINVAL, "jn_pw: route %d does not take this launch", route);
+  JN_CHECK(max_wg == 0 || r != PW_MFMA, JN_EINVAL, "jn_pw: pw_mfma_kernel has no persistent grid to cap (max_wg=%d)", max_wg);
+  a.in = in_dev; a.itab.sc = tab; a.itab.sh = tab + cin; a.itab.fl = tab + 2 * cin; a.w = w_dev; a.bias = bias_dev; a.out = out_dev;
+  a.stats = stats_dev; a.stats_rep_stride = 2LL * cout; a.stats_nrep = nrep; a.skip_flag = skip_flag_dev; a.skip_when = skip_when;
+  a.in_slot_stride = in_slot_stride; a.out_slot_stride = out_slot_stride; a.tab_slot_stride = tab_slot_stride;
+  a.up_out = up_out_dev; a.up_ld = up_ld; a.w_x3 = nullptr;
+  // scratch: the split planes (6 bytes per weight) and the splitter's one-row table; the per-channel arrays of a deferred table
+  const bool planes = r == PW_X1 || r == PW_X3, arrays = defer && !defer->use_runs;
+  const size_t nw = (size_t)cout * cin, plane_bytes = planes ? (nw * 6 + 63) / 64 * 64 : 0;
+  const size_t bytes = plane_bytes + (planes ? 64 : 0) + (arrays ? (size_t)4 * cin * 4 : 0);
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = nullptr;
+  if (bytes) JN_HIP(hipMalloc((void**)&ws, bytes));
+  hipError_t e = hipSuccess;
+  if (planes) {      // as the context does for the 1x1 weights of its arena: the flat planes, then the regions in fragment order
+    launch_w_split3(w_dev, ws, (long long)nw, s);
+    if (pw_x3_fragment_order(cin, cout)) {
+      const X3FragConv row{0, cout, cin};
+      e = hipMemcpyAsync(ws + plane_bytes, &row, sizeof(row), hipMemcpyHostToDevice, s);
+      if (e == hipSuccess) e = hipStreamSynchronize(s);      // (`row` leaves scope)
+      if (e == hipSuccess) launch_w_split3_frag(w_dev, ws, (const X3FragConv*)(ws + plane_bytes), 1, (int)nw, s);
+    }
+    a.w_x3 = ws;
+  }
+  if (defer) {
+    ChanTab& t = a.itab;
+    t.dparams = defer->params_dev; t.dstats = defer->sums_dev; t.drep_stride = defer->rep_stride; t.dN = defer->dN; t.dmax = defer->dmax;
+    // a run whose layer is above the deferral limit reads the table in either form (defer_tab_runs, api_net.hip)
+    auto deferred = [&](const jn_pw_run& q) { return q.stat0 >= 0 && (double)defer->dN * q.hw <= (double)defer->dmax; };
+    if (arrays) {
+      std::vector<int32_t> h(4 * (size_t)cin, -1);      // [dsrc | dhw | dgoff | dboff]; channels outside every run: never deferred
+      float* hw = reinterpret_cast<float*>(h.data() + cin);
+      for (int c = 0; c < cin; ++c) { hw[c] = 0.0f; h[2 * cin + c] = h[3 * cin + c] = 0; }
+      for (int i = 0; i < defer->n_runs; ++i) {
+        const jn_pw_run& q = defer->run[i];
+        for (int c = q.c0; c < q.c1; ++c) {      // (the limit is applied by the kernel here: dN * dhw <= dmax)
+          h[c] = q.stat0 >= 0 ? q.stat0 + (c - q.c0) : -1; hw[c] = q.hw;
+          h[2 * cin + c] = q.stat0 >= 0 ? q.g0 + (c - q.c0) : 0; h[3 * cin + c] = q.stat0 >= 0 ? q.b0 + (c - q.c0) : 0;
+        }
+      }
+      char* arr = ws + plane_bytes + (planes ? 64 : 0);
+      if (e == hipSuccess) e = hipMemcpyAsync(arr, h.data(), h.size() * 4, hipMemcpyHostToDevice, s);
+      if (e == hipSuccess) e = hipStreamSynchronize(s);
+      t.dsrc = (const int*)arr; t.dhw = (const float*)(arr + 4 * (size_t)cin); t.dgoff = (const int*)(arr + 8 * (size_t)cin);
+      t.dboff = (const int*)(arr + 12 * (size_t)cin);
+      t.nseg = 0;
+    } else {
+      t.dsrc = reinterpret_cast<const int*>(defer->sums_dev);      // (non-null marks the table as deferred; the runs form never reads it)
+      t.nseg = defer->n_runs;
+      ChanTab::Run* dst[4] = {&t.r0, &t.r1, &t.r2, &t.r3};
+      for (int i = 0; i < defer->n_runs; ++i) {
+        const jn_pw_run& q = defer->run[i];
+        *dst[i] = ChanTab::Run{q.c0, q.c1, deferred(q) ? q.stat0 : -1, q.g0, q.b0, q.hw};
+      }
+    }
+  }
+  int rc = -1;
+  if (e == hipSuccess) {
+    rc = launch_pw(a, s, r, max_wg);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (ws) (void)hipFree(ws);
+  JN_HIP(e);
+  JN_CHECK(rc == 0, JN_EINVAL, "jn_pw: no kernel took the launch, or its LDS was refused");
+  return JN_OK;
+}
+
+int jn_pw_bwd_data_x3(const float* gz_dev, int g_ld, const float* w_dev, float* gx_dev, int gx_ld, long long M, int cout, int cin,
+                      int n_slots, int max_wg, void* stream) {
+  JN_CHECK(gz_dev && w_dev && gx_dev, JN_EINVAL, "jn_pw_bwd_data_x3: null argument");
+  JN_CHECK(M >= 1 && M <= (1 << 24) && pw_chan_ok(cin) && pw_chan_ok(cout) && pw_ld_ok(g_ld, cout) && pw_ld_ok(gx_ld, cin) && n_slots >= 1 &&
+               n_slots <= 64 && max_wg >= 0,
+           JN_EINVAL, "jn_pw_bwd_data_x3: M=%lld, %d -> %d channels, leading dimensions %d and %d, %d slots, max_wg=%d", M, cin, cout, g_ld, gx_ld,
+           n_slots, max_wg);
+  JN_CHECK(pw_x3_bwd_data_supported(cout, cin), JN_EINVAL, "jn_pw_bwd_data_x3: %d -> %d channels: the split data gradient has no kernel", cin, cout);
+  hipStream_t s = (hipStream_t)stream;
+  // scratch: the transposed split planes, and the identity table a gradient view carries
+  const size_t plane_bytes = ((size_t)cout * cin * 6 + 63) / 64 * 64;
+  char* ws = nullptr;
+  JN_HIP(hipMalloc((void**)&ws, plane_bytes + (size_t)3 * cout * sizeof(float)));
+  std::vector<float> ident(3 * (size_t)cout, 0.0f);
+  for (int c = 0; c < cout; ++c) ident[c] = 1.0f;
+  float* tab = reinterpret_cast<float*>(ws + plane_bytes);
+  hipError_t e = hipMemcpyAsync(tab, ident.data(), ident.size() * sizeof(float), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  int rc = -1;
+  if (e == hipSuccess) {      // the gradient conv as the conv-stack backward builds it: in = g_z over the layer's cout, out = g_x
+    ConvArgs a{};
+    a.in = gz_dev; a.in_ld = g_ld; a.in_dtype = JN_F32; a.itab.sc = tab; a.itab.sh = tab + cout; a.itab.fl = tab + 2 * cout;
+    a.w = w_dev; a.out = gx_dev; a.out_ld = gx_ld; a.out_dtype = JN_F32;
+    a.N = 1; a.H = a.OH = 1; a.W = a.OW = (int)M; a.cin = cout; a.cout = cin; a.stride = 1; a.act = ACT_NONE; a.w_transposed = 1; a.in_identity = 1;
+    a.n_slots = n_slots; a.in_slot_stride = M * g_ld; a.out_slot_stride = M * gx_ld;
+    rc = launch_pw_x3_bwd_data(a, w_dev, ws, s, max_wg);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(ws);
+  JN_HIP(e);
+  JN_CHECK(rc == 0, JN_EINVAL, "jn_pw_bwd_data_x3: no kernel took the launch, or its LDS was refused");
+  return JN_OK;
+}
+
+int jn_pw_bwd_weight(const float* gz_dev, int g_ld, const float* x_dev, int x_ld, const float* tab_dev, float* gw_dev, long long M, int cout,
+                     int cin, int n_slots, long long gz_slot_stride, int use_wpart, float* wpart_back_dev, int exact, void* stream) {
+  JN_CHECK(gz_dev && x_dev && tab_dev && gw_dev, JN_EINVAL, "jn_pw_bwd_weight: null argument");
+  JN_CHECK(M >= 1 && M <= (1 << 24) && pw_chan_ok(cin) && pw_chan_ok(cout) && pw_ld_ok(g_ld, cout) && pw_ld_ok(x_ld, cin) && n_slots >= 1 &&
+               n_slots <= 64 && gz_slot_stride >= M * g_ld && gz_slot_stride % 4 == 0,
+           JN_EINVAL, "jn_pw_bwd_weight: M=%lld, %d -> %d channels, leading dimensions %d and %d, %d slots, g_z slots %lld apart", M, cin, cout,
+           g_ld, x_ld, n_slots, gz_slot_stride);
+  const bool wide = cout >= 128 && cin >= 128;
+  JN_CHECK((exact == 0 || exact == 1) && (!exact || wide), JN_EINVAL, "jn_pw_bwd_weight: exact=%d; the exact form is the wide kernel's (both channel counts >= 128)", exact);
+  JN_CHECK(!use_wpart || (wpart_back_dev && !wide && (long long)cout * cin <= JN_WPART_MAX), JN_EINVAL,
+           "jn_pw_bwd_weight: the replica scratch takes at most %d weights of a layer below 128 x 128, and a buffer to copy it back to", JN_WPART_MAX);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t wp = (size_t)JN_NREP * JN_WPART_MAX;
+  float* wpart = nullptr;
+  if (use_wpart) JN_HIP(hipMalloc((void**)&wpart, wp * sizeof(float)));
+  hipError_t e = wpart ? hipMemsetAsync(wpart, 0, wp * sizeof(float), s) : hipSuccess;
+  int rc = -1;
+  if (e == hipSuccess) {
+    float* tab = const_cast<float*>(tab_dev);
+    ChanTab it{};
+    it.sc = tab; it.sh = tab + cin; it.fl = tab + 2 * cin;
+    SlotBatch sb;      // the caller's [S, ...] tensors are slots already: x and the [3][cin] tables by their own size, g_z as said
+    sb.n = n_slots; sb.act = M * x_ld; sb.tab = 3LL * cin; sb.grad = gz_slot_stride;
+    rc = launch_pw_bwd_weight(gz_dev, g_ld, x_dev, x_ld, it, gw_dev, wpart, M, cout, cin, s, sb, gz_slot_stride,
+                              wide ? (exact ? CW_ROUTE_EXACT : CW_ROUTE_SPLIT) : 0);
+    e = hipGetLastError();
+    if (e == hipSuccess && wpart) e = hipMemcpyAsync(wpart_back_dev, wpart, wp * sizeof(float), hipMemcpyDeviceToDevice, s);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (wpart) (void)hipFree(wpart);
+  JN_HIP(e);
+  JN_CHECK(rc == 0, JN_EINVAL, "jn_pw_bwd_weight: no kernel took the launch, or its LDS was refused");
+  return JN_OK;
+}
+
+}  // extern "C"

@@ -144,9 +144,15 @@ int launch_dw(const ConvArgs& a, hipStream_t s, int route = 0);
 //   NARROW        K <= 64, forward, at least JN_PW_BIG_M pixels: pw_narrow_kernel
 //   MFMA          everything else: pw_mfma_kernel
 // With a.up_out set only the routes and shapes of pw_fuses_upsample remain, anything else is NONE.
+// Forced routes (the per-kernel tests, jn_pw in api_ops.hip): pw_route(a, r) is r where that family's kernels admit the launch,
+// else NONE; launch_pw(a, s, r) launches it.  max_wg > 0 caps the x extent of a persistent grid (MFMA has none: refused).
 enum PwRoute { PW_NONE = 0, PW_X1, PW_X3, PW_XS, PW_WIDE, PW_NARROW, PW_MFMA };
-PwRoute pw_route(const ConvArgs& a);
-int launch_pw(const ConvArgs& a, hipStream_t s);
+PwRoute pw_route(const ConvArgs& a, int forced = 0);
+int launch_pw(const ConvArgs& a, hipStream_t s, int route = 0, int max_wg = 0);
+// THE tile variant pw_mfma_kernel<CT, KC, WT, WM, ..> gets: channel tiles per workgroup, K chunk, waves along the pixels (32 WM
+// pixels per workgroup).  Pure host code, like pw_route; launch_pw's MFMA case is a switch over it.
+struct PwMfmaVariant { int ct, kc, wm; };
+PwMfmaVariant pw_mfma_variant(const ConvArgs& a);
 // Pixels per launch (N * H * W; times the slots where said) at which the routes and tilings change:
 // the pixel-stationary kernels up to here (the 56x56 / 28x28 / 14x14 maps of the headline batch: 10 - 30 % under the
 // weight-stationary kernel on every one of them, profiles/r03_pwxsbench.txt)
@@ -169,12 +175,13 @@ inline bool pw_f32_plain(const ConvArgs& a) { return pw_f32_bare(a) && !a.w_tran
 bool pw_fuses_upsample(PwRoute r, int cin, int cout);  // kernels_pwxs.hip: the route's kernel for this shape can also write a.up_out
 bool pw_res_supported(const ConvArgs& a);              // kernels_pwres.hip: shapes the resident-weight 1x1 kernels take (K, N >= 64)
 int pw_dir_auto_ctw(int cin, int cout);                // launch_pw_dir's automatic slice (channel tiles), 0: none fits
-int launch_pw_dir(const ConvArgs& a, int ctw, hipStream_t s);
+// (max_wg, here and below: debug entry, > 0 caps the persistent workgroups along x, so that one walks several tiles of a small map)
+int launch_pw_dir(const ConvArgs& a, int ctw, hipStream_t s, int max_wg = 0);
 bool pw_xs_supported(const ConvArgs& a);               // kernels_pwxs.hip: pixel-stationary kernel for the small maps of a forward pass
-int launch_pw_xs(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu = 0);   // pt: pixel tiles per workgroup (0 = default)
+int launch_pw_xs(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu = 0, int max_wg = 0);   // pt: pixel tiles per workgroup (0 = default)
 // the same on the bf16 pipe (three-way split operands); needs a.w_x3.  frag: the order a.w_x3 is in (-1: the rule below; the
 // other order of a shape is built for tools/pwxsbench.hip only)
-int launch_pw_x3(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu = 0, int frag = -1);
+int launch_pw_x3(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu = 0, int frag = -1, int max_wg = 0);
 // THE layout rule of the split planes of a 1x1 conv (ConvArgs::w_x3): true = MFMA fragment order (kernels_pwxs.hip,
 // w_split3_frag_kernel), false = the flat [row][k / 8][h | m | l] order of w_split3_kernel.  Asked by the splitter's table
 // (api_net.hip) and by every reader: launch_pw_x3, its fused-upsample form and launch_pw_x1.  Shapes: what
@@ -188,9 +195,9 @@ struct X3FragConv { long long off; int cout, cin; };   // a conv of the splitter
 void launch_w_split3_frag(const float* params, void* params_x3, const X3FragConv* tab, int n_convs, int max_weights, hipStream_t s);
 // the data gradient of a wide 1x1 layer on pw_x3_kernel (transposed split weight made on the way); -1: shape not taken
 bool pw_x3_bwd_data_supported(int cout, int cin);
-int launch_pw_x3_bwd_data(const ConvArgs& a, const float* w, void* w3t, hipStream_t s);
+int launch_pw_x3_bwd_data(const ConvArgs& a, const float* w, void* w3t, hipStream_t s, int max_wg = 0);
 bool pw_x1_supported(const ConvArgs& a);               // bf16 inference mode: single-plane form of the same kernel
-int launch_pw_x1(const ConvArgs& a, hipStream_t s);               // shapes on which the x3 kernel is the faster one
+int launch_pw_x1(const ConvArgs& a, hipStream_t s, int max_wg = 0);               // shapes on which the x3 kernel is the faster one
 void launch_w_split3(const float* w, void* w3, long long n_floats, hipStream_t s);   // w3: 6 bytes per weight
 int launch_spp(void* cat, int dtype, int ld, int h, int H, int W, int N, ChanTab it, const int* skip_flag,
                int skip_when, hipStream_t s);
@@ -281,9 +288,11 @@ int launch_bn_bwd_gz(float* g, int g_ld, const float* z, int z_ld, ChanTab t, co
                      long long M, hipStream_t s, const SlotBatch& sb = SlotBatch{});
 // weight-gradient kernels add into wpart (replicated scratch, zero on entry and on exit) when the
 // tensor fits, else straight into gw; launch_wpart_reduce folds the replicas into gw.
+// route (the wide kernel, N, K >= 128): 0 = the rule (split products unless JN_WW_EXACT is set), else as Conv3WRoute:
+// CW_ROUTE_SPLIT / CW_ROUTE_EXACT = pw_bwd_weight_wide_kernel<true / false>; ignored by the narrower layers' fp32 kernel
 int launch_pw_bwd_weight(const float* gz, int g_ld, const float* x, int x_ld, ChanTab it, float* gw, float* wpart,
                          long long M, int N, int K, hipStream_t s, const SlotBatch& sb = SlotBatch{},
-                         long long gz_slot_stride = -1);
+                         long long gz_slot_stride = -1, int route = 0);
 int launch_wpart_reduce(float* gw, float* wpart, int n, hipStream_t s);
 // bn_bwd_gz + data gradient + weight gradient of a pointwise layer in one pass (few-channel layers; fp32 buffers)
 struct PwBwdFusedArgs {

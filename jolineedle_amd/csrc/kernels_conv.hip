@@ -979,14 +979,15 @@ __global__ __launch_bounds__(256) void pw_narrow_kernel(
 }
 
 template <int CT, int KC>
-static void launch_pw_narrow_t(const ConvArgs& a, long long M, hipStream_t s) {
+static void launch_pw_narrow_t(const ConvArgs& a, long long M, hipStream_t s, int max_wg) {
   constexpr int BM = (CT % 2 == 0) ? 64 : 128;
   constexpr size_t smem = (size_t)(BM + 16 * CT) * (KC + PWN_PAD) * sizeof(float) + (BM / 32) * 32 * CT * sizeof(float);
   const long long n_tiles = (M + BM - 1) / BM;
   // persistent workgroups: whole resident rounds (what the occupancy API says fits, x 256 CUs).  Round 1 had swept a fixed
   // 1536; the kernel's registers have changed since (84 VGPRs at <2, 32>: five workgroups per CU, so 1536 was a round of 1280 and a
   // tail of 256) — forward 1.842 -> 1.822 ms per pass (tools/ab_fwd.sh, 1024 / 1280 / 1536 / 2048 / resident swept)
-  const unsigned gx = (unsigned)std::min<long long>(n_tiles, resident_per_cu<&pw_narrow_kernel<CT, KC>>(smem, 4) * JN_NUM_CU);
+  unsigned gx = (unsigned)std::min<long long>(n_tiles, resident_per_cu<&pw_narrow_kernel<CT, KC>>(smem, 4) * JN_NUM_CU);
+  if (max_wg > 0) gx = std::min<unsigned>(gx, (unsigned)max_wg);      // debug entry: a workgroup walks several tiles of a small map
   dim3 grid(gx, (unsigned)((a.cout + 16 * CT - 1) / (16 * CT)));
   hipLaunchKernelGGL((pw_narrow_kernel<CT, KC>), grid, dim3(256), smem, s, (const float*)a.in, a.in_ld, a.itab, a.w,
                      (float*)a.out, a.out_ld, M, a.cout, a.stats, a.stats_rep_stride, a.skip_flag, a.skip_when,
@@ -1002,9 +1003,9 @@ static bool pw_narrow_shape(int nt, int cin) {
   return false;
 }
 
-static int launch_pw_narrow(const ConvArgs& a, hipStream_t s) {
+static int launch_pw_narrow(const ConvArgs& a, hipStream_t s, int max_wg = 0) {
   const int nt = (a.cout + 15) / 16;
-#define JN_PWN(CT_, KC_) if (nt == CT_ && a.cin == KC_) { launch_pw_narrow_t<CT_, KC_>(a, (long long)a.N * a.H * a.W, s); return 0; }
+#define JN_PWN(CT_, KC_) if (nt == CT_ && a.cin == KC_) { launch_pw_narrow_t<CT_, KC_>(a, (long long)a.N * a.H * a.W, s, max_wg); return 0; }
   JN_PWN_TABLE
 #undef JN_PWN
   return -1;
@@ -1022,49 +1023,73 @@ static void launch_pw_kc(const ConvArgs& a, long long M, hipStream_t s) {
                      a.stats_nrep > 0 ? a.stats_nrep : JN_NREP);
 }
 
-template <int CT, bool WT, int WM, typename IT, typename OT, bool BF>
-static void launch_pw_cfg(const ConvArgs& a, long long M, hipStream_t s) {
-  // K chunk: 64 wherever the tiles fit in 64 KB of LDS (fewer load -> LDS -> MFMA round trips); layers with
-  // K <= 32 / K <= 16 get narrower LDS rows: half / a quarter of the LDS per workgroup = more workgroups per CU
-  constexpr int KC = BF ? 64 : ((CT > 4) ? 32 : 64);
-  if constexpr (!BF && CT <= 4) {
-    if constexpr (WM >= 2) {
-      if (a.cin <= 16) { launch_pw_kc<CT, 16, WT, WM, IT, OT, BF>(a, M, s); return; }
-    }
-    if (a.cin <= 32) { launch_pw_kc<CT, 32, WT, WM, IT, OT, BF>(a, M, s); return; }
-  }
-  launch_pw_kc<CT, KC, WT, WM, IT, OT, BF>(a, M, s);
-}
-
-template <int CT, typename IT, typename OT, bool BF>
-static void launch_pw_ct(const ConvArgs& a, long long M, hipStream_t s) {
+// THE tile variant of pw_mfma_kernel for a launch (jn_kernels.h): a pure function of the arguments (and of the test hook
+// JN_PW_WT_SMALL_M); the template dispatch below is a switch over its result.
+PwMfmaVariant pw_mfma_variant(const ConvArgs& a) {
+  const long long M = (long long)a.N * a.H * a.W, Mtot = M * (a.n_slots > 1 ? a.n_slots : 1);
+  const int nt = (a.cout + 15) / 16;
+  PwMfmaVariant v;
+  v.ct = nt <= 3 ? nt : (nt == 4 || (nt % 8 != 0 && nt % 4 == 0)) ? 4 : 8;
   // 64-pixel workgroups (two wave pairs split the channel tiles) whenever CT is even: half the LDS per
   // workgroup -> more workgroups per CU, which is what hides the load -> LDS -> MFMA latency of these short kernels
   // (measured: 56x56 layers 50 -> 42 us, 112x112 60 -> 55 us against 128-pixel workgroups)
-  constexpr bool can_split = (CT % 2 == 0), can_split4 = (CT % 4 == 0);
-  const long long Mtot = M * (a.n_slots > 1 ? a.n_slots : 1);
-  const bool tiny_m = Mtot <= JN_PW_TINY_M;
+  const bool can_split = v.ct % 2 == 0, can_split4 = v.ct % 4 == 0;
   if (a.w_transposed) {              // data gradients (step-batched, large): 128-pixel workgroups unless the map is small
     const char* sm_env = std::getenv("JN_PW_WT_SMALL_M");
-    if (can_split && Mtot <= (sm_env ? std::atoll(sm_env) : JN_PW_WT_SMALL_M)) launch_pw_cfg<CT, true, can_split ? 2 : 4, IT, OT, BF>(a, M, s);
-    else launch_pw_cfg<CT, true, 4, IT, OT, BF>(a, M, s);
+    v.wm = can_split && Mtot <= (sm_env ? std::atoll(sm_env) : JN_PW_WT_SMALL_M) ? 2 : 4;
   } else {
     // 14x14 maps with K <= 128: 32-pixel workgroups (the four waves split the channel tiles) quadruple the
     // workgroup count; with a longer K the re-staged weight tile costs more than the parallelism gains
-    if (can_split4 && tiny_m && a.cin <= 128) launch_pw_cfg<CT, false, can_split4 ? 1 : 4, IT, OT, BF>(a, M, s);
-    else launch_pw_cfg<CT, false, can_split ? 2 : 4, IT, OT, BF>(a, M, s);
+    v.wm = can_split4 && Mtot <= JN_PW_TINY_M && a.cin <= 128 ? 1 : can_split ? 2 : 4;
   }
+  // K chunk: 64 wherever the tiles fit in 64 KB of LDS (fewer load -> LDS -> MFMA round trips); layers with
+  // K <= 32 / K <= 16 get narrower LDS rows: half / a quarter of the LDS per workgroup = more workgroups per CU
+  const bool bf = a.in_dtype != JN_F32 || a.bf16_mfma;
+  v.kc = bf ? 64 : (v.ct > 4 ? 32 : 64);
+  if (!bf && v.ct <= 4) {
+    if (v.wm >= 2 && a.cin <= 16) v.kc = 16;
+    else if (a.cin <= 32) v.kc = 32;
+  }
+  return v;
+}
+
+template <int CT, bool WT, int WM, typename IT, typename OT, bool BF>
+static int launch_pw_cfg(const ConvArgs& a, long long M, int kc, hipStream_t s) {
+  constexpr int KC = BF ? 64 : ((CT > 4) ? 32 : 64);
+  if constexpr (!BF && CT <= 4) {
+    if constexpr (WM >= 2) {
+      if (kc == 16) { launch_pw_kc<CT, 16, WT, WM, IT, OT, BF>(a, M, s); return 0; }
+    }
+    if (kc == 32) { launch_pw_kc<CT, 32, WT, WM, IT, OT, BF>(a, M, s); return 0; }
+  }
+  if (kc != KC) return -1;
+  launch_pw_kc<CT, KC, WT, WM, IT, OT, BF>(a, M, s);
+  return 0;
+}
+
+template <int CT, typename IT, typename OT, bool BF>
+static int launch_pw_ct(const ConvArgs& a, long long M, const PwMfmaVariant& v, hipStream_t s) {
+  constexpr bool can_split = (CT % 2 == 0), can_split4 = (CT % 4 == 0);
+  if (a.w_transposed) {
+    if (can_split && v.wm == 2) return launch_pw_cfg<CT, true, can_split ? 2 : 4, IT, OT, BF>(a, M, v.kc, s);
+    return v.wm == 4 ? launch_pw_cfg<CT, true, 4, IT, OT, BF>(a, M, v.kc, s) : -1;
+  }
+  if (can_split4 && v.wm == 1) return launch_pw_cfg<CT, false, can_split4 ? 1 : 4, IT, OT, BF>(a, M, v.kc, s);
+  return v.wm == (can_split ? 2 : 4) ? launch_pw_cfg<CT, false, can_split ? 2 : 4, IT, OT, BF>(a, M, v.kc, s) : -1;
 }
 
 template <typename IT, typename OT, bool BF>
-static void launch_pw_types(const ConvArgs& a, hipStream_t s) {
+static int launch_pw_types(const ConvArgs& a, hipStream_t s) {
   const long long M = (long long)a.N * a.H * a.W;
-  const int nt = (a.cout + 15) / 16;
-  if (nt == 1) launch_pw_ct<1, IT, OT, BF>(a, M, s);
-  else if (nt == 2) launch_pw_ct<2, IT, OT, BF>(a, M, s);
-  else if (nt == 3) launch_pw_ct<3, IT, OT, BF>(a, M, s);
-  else if (nt == 4 || (nt % 8 != 0 && nt % 4 == 0)) launch_pw_ct<4, IT, OT, BF>(a, M, s);
-  else launch_pw_ct<8, IT, OT, BF>(a, M, s);
+  const PwMfmaVariant v = pw_mfma_variant(a);
+  switch (v.ct) {
+    case 1: return launch_pw_ct<1, IT, OT, BF>(a, M, v, s);
+    case 2: return launch_pw_ct<2, IT, OT, BF>(a, M, v, s);
+    case 3: return launch_pw_ct<3, IT, OT, BF>(a, M, v, s);
+    case 4: return launch_pw_ct<4, IT, OT, BF>(a, M, v, s);
+    case 8: return launch_pw_ct<8, IT, OT, BF>(a, M, v, s);
+  }
+  return -1;
 }
 
 // Type combinations of pw_mfma_kernel in use: fp32 mode (f32, f32, fp32 MFMA); bf16 mode: activations (bf16 -> bf16),
@@ -1076,14 +1101,13 @@ static bool pw_mfma_types(const ConvArgs& a) {
 
 static int launch_pw_mfma(const ConvArgs& a, hipStream_t s) {
   if (!pw_mfma_types(a)) return -1;
-  if (a.in_dtype == JN_F32) { if (a.bf16_mfma) launch_pw_types<float, float, true>(a, s); else launch_pw_types<float, float, false>(a, s); }
-  else if (a.out_dtype == JN_BF16) launch_pw_types<bf16_t, bf16_t, true>(a, s);
-  else launch_pw_types<bf16_t, float, true>(a, s);
-  return 0;
+  if (a.in_dtype == JN_F32) return a.bf16_mfma ? launch_pw_types<float, float, true>(a, s) : launch_pw_types<float, float, false>(a, s);
+  if (a.out_dtype == JN_BF16) return launch_pw_types<bf16_t, bf16_t, true>(a, s);
+  return launch_pw_types<bf16_t, float, true>(a, s);
 }
 
 // THE route of a 1x1 conv (jn_kernels.h): the clauses in their order of preference, each once.
-PwRoute pw_route(const ConvArgs& a) {
+static PwRoute pw_route_rule(const ConvArgs& a) {
   const long long M = (long long)a.N * a.H * a.W;
   PwRoute r = PW_NONE;
   if (M <= JN_XS_MAX_M) {
@@ -1109,13 +1133,31 @@ PwRoute pw_route(const ConvArgs& a) {
   return pw_mfma_types(a) ? PW_MFMA : PW_NONE;
 }
 
-int launch_pw(const ConvArgs& a, hipStream_t s) {
-  switch (pw_route(a)) {
-    case PW_X1: return launch_pw_x1(a, s);
-    case PW_X3: return launch_pw_x3(a, 0, s);
-    case PW_XS: return launch_pw_xs(a, 0, s);
-    case PW_WIDE: return launch_pw_dir(a, 0, s);
-    case PW_NARROW: return launch_pw_narrow(a, s);
+// forced: the route itself where its kernel family admits the launch (what its launcher checks, restated without a launch)
+PwRoute pw_route(const ConvArgs& a, int forced) {
+  if (forced == 0) return pw_route_rule(a);
+  bool ok = false;
+  switch (forced) {
+    case PW_X1: ok = pw_x1_supported(a); break;
+    case PW_X3: ok = pw_xs_supported(a) && a.w_x3 && pw_x3_fragment_order(a.cin, a.cout); break;
+    case PW_XS: ok = pw_xs_supported(a); break;
+    case PW_WIDE: ok = pw_res_supported(a) && a.cin % 64 == 0 && pw_dir_auto_ctw(a.cin, a.cout) != 0; break;
+    case PW_NARROW: ok = pw_f32_plain(a) && pw_narrow_shape((a.cout + 15) / 16, a.cin); break;
+    case PW_MFMA: ok = pw_mfma_types(a); break;
+  }
+  if (ok && a.up_out) ok = pw_fuses_upsample((PwRoute)forced, a.cin, a.cout);
+  return ok ? (PwRoute)forced : PW_NONE;
+}
+
+int launch_pw(const ConvArgs& a, hipStream_t s, int route, int max_wg) {
+  const PwRoute r = pw_route(a, route);
+  if (max_wg < 0 || (max_wg > 0 && r == PW_MFMA)) return -1;      // (pw_mfma_kernel walks nothing: one tile per workgroup)
+  switch (r) {
+    case PW_X1: return launch_pw_x1(a, s, max_wg);
+    case PW_X3: return launch_pw_x3(a, 0, s, 0, -1, max_wg);
+    case PW_XS: return launch_pw_xs(a, 0, s, 0, max_wg);
+    case PW_WIDE: return launch_pw_dir(a, 0, s, max_wg);
+    case PW_NARROW: return launch_pw_narrow(a, s, max_wg);
     case PW_MFMA: return launch_pw_mfma(a, s);
     case PW_NONE: break;
   }

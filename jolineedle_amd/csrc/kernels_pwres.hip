@@ -201,7 +201,7 @@ static size_t pw_dir_lds(int ctw, int K) {
 }
 
 template <int CTW, bool WT, int PF = 2, bool ST = true, bool TF = true>
-static int launch_pw_dir_t(const ConvArgs& a, long long M, hipStream_t s) {
+static int launch_pw_dir_t(const ConvArgs& a, long long M, hipStream_t s, int max_wg) {
   const int K = a.cin;
   const size_t smem = pw_dir_lds(CTW, K);
   constexpr auto kern = &pw_dir_kernel<CTW, WT, PF, ST, TF>;
@@ -214,6 +214,7 @@ static int launch_pw_dir_t(const ConvArgs& a, long long M, hipStream_t s) {
   long long gx = std::max<long long>(1, (long long)JN_NUM_CU * per_cu / ((long long)ny * nz));
   if (nz == 1 && ny > 1) gx = std::max<long long>(8, gx / 8 * 8);
   gx = std::min<long long>(gx, (n_tiles + 3) / 4);
+  if (max_wg > 0) gx = std::min<long long>(gx, max_wg);      // debug entry: a wave walks several 16-pixel tiles of a small map
   dim3 grid((unsigned)gx, (unsigned)ny, (unsigned)nz);
   hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, (const float*)a.in, a.in_ld, a.itab, a.w, WT ? a.cout : a.cin,
                      (float*)a.out, a.out_ld, M, K, a.cout, a.accumulate, a.stats, a.stats_rep_stride,
@@ -232,7 +233,7 @@ int pw_dir_auto_ctw(int K, int N) {
 }
 
 // ctw = channel tiles per workgroup slice (0: automatic); returns -1 when the shape does not fit (K % 64, slice too large).
-int launch_pw_dir(const ConvArgs& a, int ctw, hipStream_t s) {
+int launch_pw_dir(const ConvArgs& a, int ctw, hipStream_t s, int max_wg) {
   const long long M = (long long)a.N * a.H * a.W;
   const int K = a.cin;
   if (K % 64 != 0 || (!ctw && !(ctw = pw_dir_auto_ctw(K, a.cout)))) return -1;
@@ -243,10 +244,10 @@ int launch_pw_dir(const ConvArgs& a, int ctw, hipStream_t s) {
   if (wt && !a.stats && (ctw == 4 || ctw == 2)) {
     // (gradient views carry the identity table: the transform — two transcendentals and half a dozen VALU ops per value,
     //  as long as the MFMAs of the step, round 2 — is compiled out)
-    if (a.in_identity) return ctw == 4 ? launch_pw_dir_t<4, true, 4, false, false>(a, M, s) : launch_pw_dir_t<2, true, 4, false, false>(a, M, s);
-    return ctw == 4 ? launch_pw_dir_t<4, true, 4, false>(a, M, s) : launch_pw_dir_t<2, true, 4, false>(a, M, s);
+    if (a.in_identity) return ctw == 4 ? launch_pw_dir_t<4, true, 4, false, false>(a, M, s, max_wg) : launch_pw_dir_t<2, true, 4, false, false>(a, M, s, max_wg);
+    return ctw == 4 ? launch_pw_dir_t<4, true, 4, false>(a, M, s, max_wg) : launch_pw_dir_t<2, true, 4, false>(a, M, s, max_wg);
   }
-#define JN_PD(C_) if (ctw == C_) return wt ? launch_pw_dir_t<C_, true>(a, M, s) : launch_pw_dir_t<C_, false>(a, M, s);
+#define JN_PD(C_) if (ctw == C_) return wt ? launch_pw_dir_t<C_, true>(a, M, s, max_wg) : launch_pw_dir_t<C_, false>(a, M, s, max_wg);
   JN_PD(8) JN_PD(4) JN_PD(2)
 #undef JN_PD
   return -1;

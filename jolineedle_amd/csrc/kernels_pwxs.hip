@@ -199,18 +199,19 @@ __global__ __launch_bounds__(256, (K <= 64 ? 3 : (K <= 128 || (K == 256 && CTW <
 
 // persistent grid of the pixel-stationary kernels: at most `wg_per_cu` (<= what fits, default 2) workgroups per CU, so that
 // every workgroup is resident from the start and walks over its tiles with the next operand in flight
-static unsigned pw_xs_grid(long long n_tiles, int fit_per_cu, int wg_per_cu) {
+static unsigned pw_xs_grid(long long n_tiles, int fit_per_cu, int wg_per_cu, int max_wg) {
   const int per_cu = std::max(1, std::min(fit_per_cu, wg_per_cu > 0 ? wg_per_cu : 2));
-  return (unsigned)std::min<long long>(n_tiles, (long long)JN_NUM_CU * per_cu);
+  const long long gx = std::min<long long>(n_tiles, (long long)JN_NUM_CU * per_cu);
+  return (unsigned)(max_wg > 0 ? std::min<long long>(gx, max_wg) : gx);      // (max_wg: debug entry)
 }
 
 template <int K, int CTW, int PT, int D, bool UPS = false>
-static int launch_pw_xs_t(const ConvArgs& a, long long M, int wg_per_cu, hipStream_t s) {
+static int launch_pw_xs_t(const ConvArgs& a, long long M, int wg_per_cu, hipStream_t s, int max_wg = 0) {
   constexpr int BM = 16 * PT;
   constexpr size_t smem = ((size_t)BM * (K + 8) + 3 * K) * sizeof(float);
   constexpr auto kern = &pw_xs_kernel<K, CTW, PT, D, UPS>;
   if (!allow_lds<kern>(smem)) return -1;
-  const unsigned gx = pw_xs_grid((M + BM - 1) / BM, resident_per_cu<kern>(smem, 1), wg_per_cu);
+  const unsigned gx = pw_xs_grid((M + BM - 1) / BM, resident_per_cu<kern>(smem, 1), wg_per_cu, max_wg);
   hipLaunchKernelGGL(kern, dim3(gx), dim3(256), smem, s, (const float*)a.in, a.in_ld, a.itab, a.w, (float*)a.out,
                      a.out_ld, M, a.stats, a.stats_rep_stride, a.stats_nrep > 0 ? a.stats_nrep : JN_NREP, a.skip_flag,
                      a.skip_when, UpsDst{(float*)a.up_out, a.up_ld, a.W, a.H * a.W});
@@ -237,7 +238,7 @@ bool pw_fuses_upsample(PwRoute r, int cin, int cout) {
   return (r == PW_X3 && cin == 128 && cout == 64) || ((r == PW_X3 || r == PW_XS) && cin == 256 && cout == 128);
 }
 
-int launch_pw_xs(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu) {
+int launch_pw_xs(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu, int max_wg) {
   if (!pw_xs_supported(a)) return -1;
   const long long M = (long long)a.N * a.H * a.W;
   const int K = a.cin, ctw = a.cout / 64;
@@ -249,9 +250,9 @@ int launch_pw_xs(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu) {
     if (wg_per_cu == 0) wg_per_cu = big ? 1 : 2;
   }
   if (a.up_out)                         // fused x2 upsample of the output
-    return pw_fuses_upsample(PW_XS, K, a.cout) && pt == 2 ? launch_pw_xs_t<256, 2, 2, 4, true>(a, M, wg_per_cu, s) : -1;
+    return pw_fuses_upsample(PW_XS, K, a.cout) && pt == 2 ? launch_pw_xs_t<256, 2, 2, 4, true>(a, M, wg_per_cu, s, max_wg) : -1;
 #define JN_XS(K_, C_, D_) \
-  if (K == K_ && ctw == C_) return pt == 4 ? launch_pw_xs_t<K_, C_, 4, D_>(a, M, wg_per_cu, s) : launch_pw_xs_t<K_, C_, 2, D_>(a, M, wg_per_cu, s);
+  if (K == K_ && ctw == C_) return pt == 4 ? launch_pw_xs_t<K_, C_, 4, D_>(a, M, wg_per_cu, s, max_wg) : launch_pw_xs_t<K_, C_, 2, D_>(a, M, wg_per_cu, s, max_wg);
   // D: k-steps of weight fragments in flight per wave — a step is 4 * PT * CTW MFMAs (32 cycles each), an L2 round trip
   // about 1500 cycles: the narrower the wave's channel slice, the deeper the ring; D = K / 16 (K <= 128 with at most two
   // channel tiles per wave): every fragment is fetched up front, no loads inside the matrix loop
@@ -502,13 +503,13 @@ __global__ __launch_bounds__(256, (K <= 64 ? 3 : CTW <= 2 ? 2 : 1)) void pw_x3_k
 }
 
 template <int K, int CTW, int PT, int D, int NP, typename XT, bool UPS = false, bool SLOTS = false, bool FRAG = SLOTS>
-static int launch_pw_x3_t(const ConvArgs& a, long long M, int wg_per_cu, hipStream_t s) {
+static int launch_pw_x3_t(const ConvArgs& a, long long M, int wg_per_cu, hipStream_t s, int max_wg = 0) {
   constexpr int BM = 16 * PT;
   constexpr size_t smem = (size_t)NP * BM * (K + 16) * sizeof(bf16_t) + 3 * K * sizeof(float);
   constexpr auto kern = &pw_x3_kernel<K, CTW, PT, D, NP, XT, UPS, SLOTS, FRAG>;
   if (!allow_lds<kern>(smem)) return -1;
   const int n_slots = SLOTS ? std::max(1, a.n_slots) : 1;
-  const unsigned gx = pw_xs_grid((M + BM - 1) / BM * n_slots, resident_per_cu<kern>(smem, 1), wg_per_cu);
+  const unsigned gx = pw_xs_grid((M + BM - 1) / BM * n_slots, resident_per_cu<kern>(smem, 1), wg_per_cu, max_wg);
   hipLaunchKernelGGL(kern, dim3(gx), dim3(256), smem, s, (const XT*)a.in, a.in_ld, a.itab, (const bf16_t*)a.w_x3,
                      (XT*)a.out, a.out_ld, M, a.stats, a.stats_rep_stride, a.stats_nrep > 0 ? a.stats_nrep : JN_NREP,
                      a.skip_flag, a.skip_when, UpsDst{(float*)a.up_out, a.up_ld, a.W, a.H * a.W},
@@ -523,13 +524,13 @@ bool pw_x1_supported(const ConvArgs& a) {
          !a.accumulate && a.n_slots <= 1 && pw_xs_shape(a.cin, a.cout) && a.in_ld % 4 == 0 && a.out_ld % 4 == 0;
 }
 
-int launch_pw_x1(const ConvArgs& a, hipStream_t s) {
+int launch_pw_x1(const ConvArgs& a, hipStream_t s, int max_wg) {
   if (!pw_x1_supported(a)) return -1;
   const long long M = (long long)a.N * a.H * a.W;
   const int K = a.cin, ctw = a.cout / 64;
   const int wg = (K == 512 || ctw == 4) ? 1 : 2;
 #define JN_X1(K_, C_, P_, D_) \
-  if (K == K_ && ctw == C_) return launch_pw_x3_t<K_, C_, P_, D_, 1, bf16_t, false, false, pw_x3_fragment_order(K_, 64 * C_)>(a, M, wg, s);
+  if (K == K_ && ctw == C_) return launch_pw_x3_t<K_, C_, P_, D_, 1, bf16_t, false, false, pw_x3_fragment_order(K_, 64 * C_)>(a, M, wg, s, max_wg);
   JN_X1(64, 1, 2, 2) JN_X1(64, 2, 2, 2) JN_X1(128, 1, 2, 4) JN_X1(128, 2, 2, 4) JN_X1(128, 4, 2, 4)
   JN_X1(256, 2, 4, 2) JN_X1(256, 4, 4, 2) JN_X1(512, 4, 4, 2)
 #undef JN_X1
@@ -542,7 +543,7 @@ int launch_pw_x1(const ConvArgs& a, hipStream_t s) {
 // fragment order it is every shape of the pixel-stationary kernel (profiles/pwfrag_bench.txt: 14 - 29 % under pw_xs_kernel
 // at K >= 128, 9 - 41 % under the flat order; K = 64: 4 - 9 % under the flat order): pw_route takes it wherever the planes
 // of the layer are in fragment order.
-int launch_pw_x3(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu, int frag) {
+int launch_pw_x3(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu, int frag, int max_wg) {
   if (!pw_xs_supported(a) || !a.w_x3) return -1;
   const long long M = (long long)a.N * a.H * a.W;
   const int K = a.cin, ctw = a.cout / 64;
@@ -558,18 +559,18 @@ int launch_pw_x3(const ConvArgs& a, int pt, hipStream_t s, int wg_per_cu, int fr
   }
   if (a.up_out) {                       // fused x2 upsample of the output (reduce_conv1, lateral_conv0)
     if (pt != 2 || frag != rule || !pw_fuses_upsample(PW_X3, K, a.cout)) return -1;
-    if (K == 128) return launch_pw_x3_t<128, 1, 2, 4, 3, float, true, false, pw_x3_fragment_order(128, 64)>(a, M, wg_per_cu, s);
-    return launch_pw_x3_t<256, 2, 2, 2, 3, float, true, false, pw_x3_fragment_order(256, 128)>(a, M, wg_per_cu, s);
+    if (K == 128) return launch_pw_x3_t<128, 1, 2, 4, 3, float, true, false, pw_x3_fragment_order(128, 64)>(a, M, wg_per_cu, s, max_wg);
+    return launch_pw_x3_t<256, 2, 2, 2, 3, float, true, false, pw_x3_fragment_order(256, 128)>(a, M, wg_per_cu, s, max_wg);
   }
 #ifdef JN_X3_ALL_SHAPES        // tools/pwxsbench.hip: every shape and tile size in both weight orders, to show where each loses
 #define JN_X3(K_, C_, P_, D_)                                                                              \
   if (K == K_ && ctw == C_ && pt == P_)                                                                    \
-    return frag ? launch_pw_x3_t<K_, C_, P_, D_, 3, float, false, false, true>(a, M, wg_per_cu, s)          \
-                : launch_pw_x3_t<K_, C_, P_, D_, 3, float, false, false, false>(a, M, wg_per_cu, s);
+    return frag ? launch_pw_x3_t<K_, C_, P_, D_, 3, float, false, false, true>(a, M, wg_per_cu, s, max_wg)  \
+                : launch_pw_x3_t<K_, C_, P_, D_, 3, float, false, false, false>(a, M, wg_per_cu, s, max_wg);
 #else
 #define JN_X3(K_, C_, P_, D_)                             \
   if (K == K_ && ctw == C_ && pt == P_ && frag == rule) \
-    return launch_pw_x3_t<K_, C_, P_, D_, 3, float, false, false, pw_x3_fragment_order(K_, 64 * C_)>(a, M, wg_per_cu, s);
+    return launch_pw_x3_t<K_, C_, P_, D_, 3, float, false, false, pw_x3_fragment_order(K_, 64 * C_)>(a, M, wg_per_cu, s, max_wg);
 #endif
   JN_X3(64, 1, 2, 2) JN_X3(64, 2, 2, 2) JN_X3(128, 1, 2, 4) JN_X3(128, 2, 2, 4) JN_X3(128, 4, 2, 2)
   JN_X3(256, 2, 2, 2) JN_X3(256, 4, 4, 2) JN_X3(512, 4, 2, 2)
@@ -615,7 +616,7 @@ bool pw_x3_bwd_data_supported(int cout, int cin) {
 
 // a: the ConvArgs of the gradient conv as api_net.hip builds them for launch_pw (in = g_z, out = g_x, cin = layer's cout,
 // cout = layer's cin, slots); w = the layer's [cout][cin] weight, w3t = 3 * cout * cin bf16 of scratch owned by the layer
-int launch_pw_x3_bwd_data(const ConvArgs& a, const float* w, void* w3t, hipStream_t s) {
+int launch_pw_x3_bwd_data(const ConvArgs& a, const float* w, void* w3t, hipStream_t s, int max_wg) {
   const int K = a.cin, N = a.cout;                      // of the gradient conv
   if (!pw_x3_bwd_data_supported(K, N) || !pw_f32_bare(a) || a.accumulate || a.in_ld % 4 != 0 || a.out_ld % 4 != 0 || a.stats)
     return -1;
@@ -625,12 +626,12 @@ int launch_pw_x3_bwd_data(const ConvArgs& a, const float* w, void* w3t, hipStrea
   b.w_x3 = w3t; b.up_out = nullptr;
   // tilings: the best of tools/x3bwdbench.hip (profiles/r04_x3bwdbench.txt) — 32-pixel tiles everywhere (more tiles to
   // balance over the persistent grid), K = 128: all weight fragments in registers (D = K / 32)
-  if (K == 256 && N == 128) return launch_pw_x3_t<256, 2, 2, 2, 3, float, false, true>(b, M, 2, s);
-  if (K == 128 && N == 256) return launch_pw_x3_t<128, 4, 2, 4, 3, float, false, true>(b, M, 2, s);
+  if (K == 256 && N == 128) return launch_pw_x3_t<256, 2, 2, 2, 3, float, false, true>(b, M, 2, s, max_wg);
+  if (K == 128 && N == 256) return launch_pw_x3_t<128, 4, 2, 4, 3, float, false, true>(b, M, 2, s, max_wg);
   for (int n0 = 0; n0 < N; n0 += 256) {                 // 256 -> 256, and 256 -> 512 as two column halves
     b.w_x3 = (const bf16_t*)w3t + (long long)n0 * K * 3;
     b.out = (float*)a.out + n0;
-    if (launch_pw_x3_t<256, 4, 2, 2, 3, float, false, true>(b, M, 2, s)) return -1;
+    if (launch_pw_x3_t<256, 4, 2, 2, 3, float, false, true>(b, M, 2, s, max_wg)) return -1;
   }
   return 0;
 }

@@ -1,6 +1,7 @@
 """The fused pointwise backward at 128 input channels (csrc/kernels_bwd_pw.hip: ``pw_bwd_fused128_kernel``, 32-pixel tiles, two
 workgroups per CU, W^T streamed in fragment order) through the context-free entry ``jn_pw_bwd_fused``: against an fp64
-restatement of the formulas in the kernel's header comment, and against the 64-pixel kernel (route 1) it replaces.
+restatement of the formulas in the kernel's header comment, and against the 64-pixel kernel (route 1) it replaces; and, against the
+same fp64 restatement, every other shape the entry admits (pw_bwd_fused_kernel, cout and cin each 16, 32, 64 or 128).
 
 Bars:
  - data gradient, route 0 against route 1: 64 output channels multiply on the fp32 matrix pipe in the same k order as the
@@ -27,19 +28,19 @@ DEV = "cuda:0"
 CIN = 128
 
 
-def _inputs(cout, M, S, seed):
+def _inputs(cout, M, S, seed, cin=CIN):
     g = torch.Generator().manual_seed(seed)
     r = lambda *s: torch.randn(*s, generator=g)
     u = lambda lo, hi, *s: lo + (hi - lo) * torch.rand(*s, generator=g)
-    C = cout + CIN
+    C = cout + cin
     tab = torch.empty(S, 3, C)
     tab[:, 0] = u(0.5, 1.5, S, C)
     tab[:, 1] = 0.5 * r(S, C)
     tab[:, 2] = (torch.rand(S, C, generator=g) < 0.75).float()          # some input channels are read raw (fl = 0)
     save = torch.stack([0.3 * r(S, cout), u(0.5, 2.0, S, cout)], -1)     # (mean, invstd)
     consts = torch.stack([0.1 * r(S, cout), 0.1 * r(S, cout), u(0.5, 1.5, S, cout)], -1)      # (c1, c2, k)
-    return dict(g=r(S, M, cout), z=r(S, M, cout), x=r(S, M, CIN), tab=tab, save=save, consts=consts,
-                w=r(cout, CIN) / CIN ** 0.5, gadd=r(S, M, CIN), gx0=r(S, M, CIN), gw0=0.1 * r(cout, CIN))
+    return dict(g=r(S, M, cout), z=r(S, M, cout), x=r(S, M, cin), tab=tab, save=save, consts=consts,
+                w=r(cout, cin) / cin ** 0.5, gadd=r(S, M, cin), gx0=r(S, M, cin), gw0=0.1 * r(cout, cin))
 
 
 def _reference(t, cout, accumulate, gadd):
@@ -63,11 +64,11 @@ def _reference(t, cout, accumulate, gadd):
     return gx, gw
 
 
-def _run(dev, cout, M, S, accumulate, gadd, route, max_wg):
+def _run(dev, cout, M, S, accumulate, gadd, route, max_wg, cin=CIN):
     lib = _lib.load_library()
     gx, gw = dev["gx0"].clone(), dev["gw0"].clone()
     rc = lib.jn_pw_bwd_fused(ptr(dev["g"]), ptr(dev["z"]), ptr(dev["x"]), ptr(dev["tab"]), ptr(dev["save"]), ptr(dev["consts"]),
-                             ptr(dev["w"]), ptr(dev["gadd"]) if gadd else None, int(accumulate), ptr(gx), ptr(gw), S, M, cout, CIN,
+                             ptr(dev["w"]), ptr(dev["gadd"]) if gadd else None, int(accumulate), ptr(gx), ptr(gw), S, M, cout, cin,
                              route, max_wg, None)
     _lib.check(rc, "jn_pw_bwd_fused")
     torch.cuda.synchronize()
@@ -106,6 +107,39 @@ def test_fused128_matches_fp64_and_the_64_pixel_kernel(cout, M, S):
             else:
                 again = (gw2 - gw).abs().max().item() / dw_scale
                 assert again < 1e-5, (max_wg, again)
+
+
+@pytest.mark.parametrize("cin", [16, 32, 64, 128])
+@pytest.mark.parametrize("cout", [16, 32, 64, 128])
+def test_fused_backward_matches_fp64_at_every_shape_the_entry_admits(cout, cin):
+    """All sixteen shapes of pw_bwd_fused_supported on the launcher's own choice of kernel (pw_bwd_fused_kernel<cout / 16, cin / 16,
+    false>, 64-pixel tiles; pw_bwd_fused128_kernel at 128 input and 64 or 128 output channels), at M = 1, a tile less one pixel, a
+    tile, a tile and a pixel, two tiles and two pixels; one and three slots; max_wg 0, 1, 2.  The bars of the test above.  Two runs
+    give the same dW bits where every element has one writer (max_wg = 1 and, on the 64-pixel kernel, whose grid has a row per
+    slot, one slot), else dW to the order of its fp32 atomics.  (The RED / RED2 forms are not reachable through this entry.)"""
+    per_slot_grid = not (cin == 128 and cout in (64, 128))
+    worst_gx = worst_dw = 0.0
+    for M, S in itertools.product((1, 63, 64, 65, 130), (1, 3)):
+        t = _inputs(cout, M, S, seed=100000 * cout + 1000 * cin + 10 * M + S, cin=cin)
+        dev = {k: v.to(DEV).contiguous() for k, v in t.items()}
+        for accumulate, gadd in ((False, False), (True, True)):
+            want_gx, want_gw = _reference(t, cout, accumulate, gadd)
+            dw_scale = want_gw.abs().max().item()
+            for max_wg in (0, 1, 2):
+                gx, gw = _run(dev, cout, M, S, accumulate, gadd, 0, max_wg, cin=cin)
+                gx_rel = ((gx.double() - want_gx).norm() / want_gx.norm()).item()
+                dw = (gw.double() - want_gw).abs().max().item() / dw_scale
+                worst_gx, worst_dw = max(worst_gx, gx_rel), max(worst_dw, dw)
+                assert gx_rel < 2e-5, (M, S, accumulate, max_wg, gx_rel)
+                assert dw < 1e-4, (M, S, accumulate, max_wg, dw)
+                gx2, gw2 = _run(dev, cout, M, S, accumulate, gadd, 0, max_wg, cin=cin)
+                assert torch.equal(gx2, gx), (M, S, accumulate, max_wg)
+                if max_wg == 1 and (S == 1 or not per_slot_grid):
+                    assert torch.equal(gw2, gw), (M, S, accumulate)
+                else:
+                    again = (gw2 - gw).abs().max().item() / dw_scale
+                    assert again < 1e-5, (M, S, accumulate, max_wg, again)
+    print(f"{cin} -> {cout}: worst gx rel L2 {worst_gx:.2e}, worst dW {worst_dw:.2e} of max|dW|")
 
 
 def test_entry_refuses_bad_arguments():
