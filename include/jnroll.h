@@ -840,6 +840,20 @@ int jn_set_rollout_teacher(jn_ctx* ctx, const uint8_t* targets_dev, uint8_t* set
  * the upload of the previous one).  JN_EINVAL: a null ctx, n < 1 with a table, a stream index >= 2^32
  * (the armed keys are then left as they were). */
 int jn_set_rollout_keys(jn_ctx* ctx, const uint64_t* keys_host, int n);
+/* Names the class behind the class token of every agent of the following rollouts of `ctx`: the free-running
+ * evaluation of a class-conditioned (supervised) policy, where test_model_on_env feeds `classes=sample["class_id"]` at
+ * every step and eval_envs hands each image's class down (src/supervised.py:284, 317-331, 663-687).  classes_host: int64
+ * [n] in HOST memory, read before the call returns (the context keeps its own copy and uploads it on the stream of the
+ * next rollout that needs it).  While armed, agent b's first token is row classes[b] of embed_class (gpt.py:476-478) on
+ * both decision routes and under both token positions; a train-mode rollout (jn_reinforce_forward, jn_reinforce_step)
+ * keeps the ids it ran with, and its backward — whenever it runs, whatever is armed by then — adds the class token's
+ * gradient to those rows.  classes_host = NULL disarms (n is ignored); disarmed, every agent gets row 0 (the REINFORCE
+ * loop's zeros, src/reinforce.py:128-129) and every result is what it was without this call.  Sticky until set again.
+ * While armed, jn_rollout, jn_reinforce_forward and jn_reinforce_step fail with JN_EINVAL before any launch when the
+ * env's B != n.  Every check comes before any device call (the one such call: a new table waits for the upload of the
+ * previous one).  JN_EINVAL: a null ctx, n < 1 with a table, an id outside 0 .. 99 (nn.Embedding raises on it; the
+ * message names the agent and the id; the armed table is then left as it was). */
+int jn_set_rollout_classes(jn_ctx* ctx, const int64_t* classes_host, int n);
 /* Number of steps S the last rollout executed (reference tensor width).  Synchronises
  * on `stream`. */
 int jn_rollout_steps(jn_ctx* ctx, int* n_steps, void* stream);

@@ -179,6 +179,7 @@ SIGNATURES = {
                                    C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "jn_set_rollout_teacher":(C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "jn_set_rollout_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "jn_set_rollout_classes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "jn_rollout_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "jn_last_timing": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "jn_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),

@@ -129,6 +129,9 @@ def args_to_config(args):
     t.env_name, t.work_dir, t.seed = args.env_name, args.work_dir, args.seed
     t.test_every, t.test_samples = args.test_every, args.test_samples
     t.eval_max_per_cell = args.eval_max_per_cell       # SupervisedTrainer.eval_envs_on_images (ours)
+    # ReinforceTrainer.training_step hands batch["class_id"] to the rollout's class tokens only when set (ours, no flag:
+    # the reference's REINFORCE loop feeds zeros, src/reinforce.py:128-129)
+    t.class_tokens = False
     t.stop_weight, t.entropy_weight, t.reward_norm = args.stop_weight, args.entropy_weight, args.reward_norm
     t.merge_bboxes, t.failure_select_rate = args.merge_bboxes, args.failure_select_rate
     t.port_ddp = args.port_ddp

@@ -47,6 +47,9 @@ int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const
   const int n_keys = (int)(ctx->keys_host.size() / 2);
   JN_CHECK(n_keys == 0 || n_keys == ctx->env.B, JN_EINVAL,
            "jn_set_rollout_keys armed %d agent streams, the env has %d agents", n_keys, ctx->env.B);
+  const int n_classes = (int)ctx->classes_host.size();
+  JN_CHECK(n_classes == 0 || n_classes == ctx->env.B, JN_EINVAL,
+           "jn_set_rollout_classes armed %d class ids, the env has %d agents", n_classes, ctx->env.B);
   JN_HIP(hipSetDevice(ctx->cfg.device));
   hipStream_t s = (hipStream_t)stream;
   const jn_config& c = ctx->cfg;
@@ -86,6 +89,32 @@ int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const
     }
     keys = ctx->keys_dev;
   }
+  // class ids: the same way; a train-mode rollout also keeps the ids it ran with for its backward
+  const int64_t* classes = nullptr;
+  if (n_classes) {
+    if (ctx->classes_dev_cap < (size_t)n_classes) {
+      int rk = dev_alloc(ctx, &ctx->classes_dev, (size_t)std::max(c.max_batch, n_classes));
+      if (rk) return rk;
+      ctx->classes_dev_cap = (size_t)std::max(c.max_batch, n_classes);
+      ctx->classes_dirty = true;
+    }
+    if (ctx->classes_dirty) {
+      if (!ctx->classes_ev) JN_HIP(hipEventCreateWithFlags(&ctx->classes_ev, hipEventDisableTiming));
+      JN_HIP(hipMemcpyAsync(ctx->classes_dev, ctx->classes_host.data(), (size_t)n_classes * sizeof(int64_t), hipMemcpyHostToDevice, s));
+      JN_HIP(hipEventRecord(ctx->classes_ev, s));
+      ctx->classes_dirty = false;
+    }
+    classes = ctx->classes_dev;
+    if (train) {
+      if (ctx->classes_used_cap < (size_t)n_classes) {
+        int rk = dev_alloc(ctx, &ctx->classes_used, (size_t)std::max(c.max_batch, n_classes));
+        if (rk) return rk;
+        ctx->classes_used_cap = (size_t)std::max(c.max_batch, n_classes);
+      }
+      JN_HIP(hipMemcpyAsync(ctx->classes_used, classes, (size_t)n_classes * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+    }
+  }
+  if (train) ctx->classes_used_n = n_classes;
 
   if (ctx->ev[0]) JN_HIP(hipEventRecord(ctx->ev[0], s));
   EnvPtrs ep = env_ptrs(ctx);
@@ -191,6 +220,7 @@ int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const
     fill_gpt_weights(ctx, a);
     a.B = B; a.T = T;
     a.step = t; a.mode = mode; a.forced = forced_actions_dev; a.seed = seed; a.keys = keys;
+    a.classes = classes;
     // recurrent: every new token at 1-D position 0 (gpt.py:431-449); by token: position t, the last row of the
     // reference's full-prefix forward (gpt.py:331-354, 427-428)
     a.src_mode = GPT_SRC_ENV; a.pos_index = by_token ? t : 0; a.emb_stride = T + 1;
@@ -285,6 +315,24 @@ int jn_set_rollout_keys(jn_ctx* ctx, const uint64_t* keys_host, int n) {
   if (ctx->keys_ev) JN_HIP(hipEventSynchronize(ctx->keys_ev));
   ctx->keys_host.assign(keys_host, keys_host + (size_t)n * 2);
   ctx->keys_dirty = true;
+  return JN_OK;
+}
+
+int jn_set_rollout_classes(jn_ctx* ctx, const int64_t* classes_host, int n) {
+  JN_CHECK(ctx, JN_EINVAL, "jn_set_rollout_classes: null ctx");
+  if (!classes_host) {
+    ctx->classes_host.clear();
+    return JN_OK;
+  }
+  JN_CHECK(n >= 1, JN_EINVAL, "jn_set_rollout_classes: n = %d with a table", n);
+  for (int b = 0; b < n; ++b)
+    JN_CHECK(classes_host[b] >= 0 && classes_host[b] < JN_N_CLASS_ROWS, JN_EINVAL,
+             "jn_set_rollout_classes: the class id of agent %d, %lld, is outside embed_class (rows 0 .. %d)", b,
+             (long long)classes_host[b], JN_N_CLASS_ROWS - 1);
+  // (an upload of the previous table may still be reading the copy; no event exists before the first armed rollout)
+  if (ctx->classes_ev) JN_HIP(hipEventSynchronize(ctx->classes_ev));
+  ctx->classes_host.assign(classes_host, classes_host + n);
+  ctx->classes_dirty = true;
   return JN_OK;
 }
 

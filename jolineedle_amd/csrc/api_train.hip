@@ -230,6 +230,7 @@ static int reinforce_backward_gpt(jn_ctx* ctx, const jn_rollout_out* out, int st
   ba.B = B; ba.T = T; ba.stop_early = stop_early ? 1 : 0;
   ba.final_emb = out->final_emb_dev; ba.actions = out->actions_dev;
   ba.positions = out->positions_dev; ba.pos_tokens = T + 1; ba.pos1d_by_token = 0; ba.tok_actions = nullptr;
+  ba.classes = ctx->classes_used_n ? ctx->classes_used : nullptr;    // the ids the rollout ran with, not the setter's
   ba.dte_stride_b = 1; ba.dte_stride_t = B;          // [T][B][C]: the rows of one glimpse step are contiguous
   return launch_gpt_bwd(ctx, ba, s);
 }

@@ -91,7 +91,8 @@ __device__ __forceinline__ GptTokSrc gpt_tok_src(const GptStepArgs& a, int b, in
   r.kind = gpt_tok_kind(a, j);
   r.direct = nullptr; r.act = 0; r.row = 0; r.col = 0;
   if (r.kind.class_tok) {
-    // embed_class(classes) (gpt.py:476-478); the rollout passes no ids: class 0 (reinforce.py:128-129)
+    // embed_class(classes) (gpt.py:476-478); a rollout without jn_set_rollout_classes passes no ids: class 0
+    // (reinforce.py:128-129)
     const int cls = a.classes ? min(max((int)a.classes[b], 0), JN_N_CLASS_ROWS - 1) : 0;
     r.direct = a.embed_class + (long long)cls * a.C;
   } else if (r.kind.given) {

@@ -315,6 +315,13 @@ struct jn_ctx {
   // setter waits for it before it rewrites the copy)
   std::vector<uint64_t> keys_host; uint64_t* keys_dev = nullptr; size_t keys_dev_cap = 0; bool keys_dirty = false;
   hipEvent_t keys_ev = nullptr;
+  // jn_set_rollout_classes: the same scheme for the class id behind every agent's class token — armed while classes_host
+  // is not empty, uploaded to classes_dev (classes_dev_cap ids) when classes_dirty, classes_ev behind that upload.  A
+  // train-mode rollout leaves the ids it ran with in classes_used (its own device copy, like drop_seed_used: the backward
+  // runs after the caller has cleared or rewritten the table); classes_used_n = 0: it ran without a table (class 0)
+  std::vector<int64_t> classes_host; int64_t* classes_dev = nullptr; size_t classes_dev_cap = 0; bool classes_dirty = false;
+  hipEvent_t classes_ev = nullptr;
+  int64_t* classes_used = nullptr; size_t classes_used_cap = 0; int classes_used_n = 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   bool profiling = false;
   bool bwd_timed = false;         // ev[2] / ev[3] bracket a conv-stack backward

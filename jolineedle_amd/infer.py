@@ -11,8 +11,8 @@ import torch.nn.functional as F
 from .detection import (compute_detection_metrics, detection_targets, map_50_device, pack_boxes, patch_bboxes2full_image,
                         rollout_boxes_packed, rollout_boxes_to_image, unpack_boxes)  # noqa: F401
 from .env import NeedleGeneralEnv
-from .ragged import (env_metrics, found_ratios, image_env, loop_agent_keys, loop_start_positions, own_steps,  # noqa: F401
-                     plan_chunks, slice_rollout)
+from .ragged import (env_metrics, found_ratios, image_classes, image_env, loop_agent_keys, loop_start_positions,  # noqa: F401
+                     own_steps, plan_chunks, slice_rollout, walk_classes)
 
 
 def load_bboxes(bbox_fname) -> List[List[int]]:
@@ -37,7 +37,7 @@ def pad_to_patch_multiple(image: torch.Tensor, patch_size: int) -> torch.Tensor:
 @torch.no_grad()
 def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequence] = None, sample_actions: bool = True,
                  do_detection: Optional[bool] = None, batch_size: Optional[int] = None, device_metrics: bool = False,
-                 token_positions: Optional[str] = None, streams: str = "loop") -> Dict:
+                 token_positions: Optional[str] = None, streams: str = "loop", class_ids=None) -> Dict:
     """`images`: [C, H, W] tensors (uint8 0..255 or float 0..1) of any sizes; `targets`: per image an [n, 4] xyxy list /
     tensor or None.  Returns per-image boxes ([n, 7] in full-image pixels or None), positions, step counts, durations
     and — where targets are given — the mean of the reference's metrics.
@@ -62,7 +62,12 @@ def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequ
     chunk's packed boxes, one readback per chunk, instead of one host ``map_50`` per image.
 
     token_positions: "sequence" / "recurrent" / None, handed to every rollout (``ReinforceTrainer.rollout``): a policy
-    trained in supervised mode needs "sequence"."""
+    trained in supervised mode needs "sequence".
+
+    class_ids: one class per image (a tensor or a sequence): the class token of image i's rollout is row class_ids[i] of
+    ``embed_class`` (``ReinforceTrainer.rollout(classes=...)``), in the loop and in every chunk alike — what a
+    class-conditioned policy was trained under (src/supervised.py:317-331); None = class 0."""
+    class_ids = image_classes(class_ids, len(images))
     cfg, dev = trainer.config, trainer.device
     P, T = int(cfg.patch_size), int(cfg.max_seq_len)
     if do_detection is None:
@@ -71,7 +76,7 @@ def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequ
         raise ValueError(f"streams must be 'loop' or 'batch', got {streams!r}")
     if batch_size is not None:
         return _infer_batched(trainer, images, targets, sample_actions, do_detection, int(batch_size), device_metrics,
-                              token_positions, streams)
+                              token_positions, streams, class_ids)
     if streams != "loop":
         raise ValueError("streams='batch' needs batch_size: the per-image loop has no batch")
     if device_metrics:
@@ -86,7 +91,8 @@ def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequ
         bboxes = tg.to(torch.long) if tg is not None else torch.zeros((1, 1, 4), dtype=torch.long)
         env = NeedleGeneralEnv(x, bboxes, P, T, 1, bool(getattr(cfg, "stop_enabled", False)))
         t0 = time.perf_counter()
-        ro = trainer.rollout(env, do_detection=do_detection, sample_actions=sample_actions, token_positions=token_positions)
+        ro = trainer.rollout(env, do_detection=do_detection, sample_actions=sample_actions, token_positions=token_positions,
+                             classes=walk_classes(class_ids, [i]))
         torch.cuda.synchronize(dev)
         res["duration_ms"].append((time.perf_counter() - t0) * 1e3)
         offsets = ro["positions"][:, :, [1, 0]] * P                       # (y, x) grid -> (x, y) pixels
@@ -105,7 +111,7 @@ def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequ
 
 
 def _infer_batched(trainer, images, targets, sample_actions, do_detection, batch_size, device_metrics=False,
-                   token_positions=None, streams="loop") -> Dict:
+                   token_positions=None, streams="loop", class_ids=None) -> Dict:
     dev, P = trainer.device, int(trainer.config.patch_size)
     n = len(images)
     res = {"boxes": [None] * n, "positions": [None] * n, "steps": [0] * n, "duration_ms": [0.0] * n}
@@ -123,7 +129,8 @@ def _infer_batched(trainer, images, targets, sample_actions, do_detection, batch
         keys = loop_agent_keys(trainer, first, sel) if sample_actions and streams == "loop" else None    # greedy: no call
         t0 = time.perf_counter()
         ro = trainer.rollout(env, do_detection=do_detection, sample_actions=sample_actions, start_positions=start,
-                             bbox_lists=False, token_positions=token_positions, agent_keys=keys)
+                             bbox_lists=False, token_positions=token_positions, agent_keys=keys,
+                             classes=walk_classes(class_ids, sel))
         torch.cuda.synchronize(dev)
         ms = (time.perf_counter() - t0) * 1e3 / len(sel)
         packed = rollout_boxes_packed(ro, P) if do_detection else None

@@ -108,6 +108,29 @@ def walk_agent_keys(trainer, first_rollout: int, indices: Sequence[int], n_walks
     return loop_agent_keys(trainer, first_rollout, [i * K + k for i in indices for k in range(K)])
 
 
+N_CLASS_ROWS = 100       # rows of embed_class (src/models/gpt.py:227)
+
+
+def image_classes(class_ids, n_images: int) -> Optional[List[int]]:
+    """`class_ids` of an evaluation or inference entry point — None, or one integer per image as a tensor (any device:
+    one readback) or a sequence — as a list of Python integers; None stays None (every walk under class 0, no call to
+    the engine).  An id outside ``embed_class`` raises what ``GPT.forward`` raises, before anything runs."""
+    if class_ids is None:
+        return None
+    ids = [int(c) for c in (class_ids.detach().reshape(-1).tolist() if torch.is_tensor(class_ids) else class_ids)]
+    assert len(ids) == n_images, f"class_ids must name one class per image ({n_images}), got {len(ids)}"
+    assert all(0 <= c < N_CLASS_ROWS for c in ids), "class id outside embed_class (100 rows)"
+    return ids
+
+
+def walk_classes(class_ids: Optional[Sequence[int]], indices: Sequence[int], n_walks: int = 1) -> Optional[List[int]]:
+    """The ``classes`` of a chunk's rollout: agent j * K + k carries the class of image indices[j], so the K walks of an
+    image share its class (test_model_on_env gets the image's ``class_id`` for every start, src/supervised.py:663-687)."""
+    if class_ids is None:
+        return None
+    return [int(class_ids[i]) for i in indices for _ in range(int(n_walks))]
+
+
 def walk_start_positions(trainer, first_rollout: int, indices: Sequence[int], extents: Sequence[Sequence[int]], n_walks: int,
                          eval_mode: str = "multistart") -> Tensor:
     """[n, K, 2] the starts of the K walks of every image in ``eval_envs`` (src/supervised.py:668-690), image

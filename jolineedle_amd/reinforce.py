@@ -21,6 +21,17 @@ def _keys_table(agent_keys, B: int):
     return np.ascontiguousarray(tab)
 
 
+def _classes_table(classes, B: int):
+    """The host table of ``jn_set_rollout_classes``: int64 [B] class ids from a [B] integer tensor (any device: one
+    readback) or sequence.  An id outside ``embed_class`` raises what ``GPT.forward`` raises."""
+    import numpy as np
+    rows = classes.detach().reshape(-1).tolist() if torch.is_tensor(classes) else list(classes)
+    tab = np.ascontiguousarray(np.array([int(c) for c in rows], dtype=np.int64).reshape(-1))
+    assert tab.shape[0] == B, f"classes must be [{B}], got {list(tab.shape)}"
+    assert int(tab.min()) >= 0 and int(tab.max()) < 100, "class id outside embed_class (100 rows)"
+    return tab
+
+
 class _RolloutGraph(torch.autograd.Function):
     """Graph node behind ``rollout()["logprobs"]`` / ``["entropies"]`` of a train-mode rollout ("carry
     autograd graph in training").  backward = ``jn_reinforce_backward`` with the upstream gradients torch hands over, then
@@ -86,7 +97,7 @@ class ReinforceTrainer:
                 forced_actions: torch.Tensor = None, start_positions: torch.Tensor = None,
                 keep_patches: bool = True, stop_early: bool = True, bbox_lists: bool = True,
                 token_positions: str = None, teacher: bool = False,
-                teacher_targets: torch.Tensor = None, agent_keys=None) -> Dict[str, torch.Tensor]:
+                teacher_targets: torch.Tensor = None, agent_keys=None, classes=None) -> Dict[str, torch.Tensor]:
         """src/reinforce.py:108-215.  Extra keyword arguments (not in the reference):
         `forced_actions` [B,T] replays a trajectory, `start_positions` [B,2] injects reset
         positions (reference: env.reset(positions)), `keep_patches=False` skips the
@@ -105,8 +116,13 @@ class ReinforceTrainer:
         `agent_keys` [B,2] integers (stream seed, stream index): agent b draws its sampled actions, and its random start
         when `start_positions` is None, from that Philox stream instead of (this rollout's seed, b)
         (``jn_set_rollout_keys``) — an agent then walks the same way wherever it sits in whichever batch; None = the
-        default streams, or ``dist.shard_agent_keys`` of this rank when ``config.agent_streams == "global"``."""
+        default streams, or ``dist.shard_agent_keys`` of this rank when ``config.agent_streams == "global"``.
+        `classes` [B] integers (a tensor on any device or a sequence): agent b's class token is row classes[b] of
+        ``embed_class`` (``jn_set_rollout_classes``), what ``test_model_on_env`` feeds a class-conditioned policy
+        (src/supervised.py:317-331); in train mode the class token's gradient goes to those rows, whenever the backward
+        runs.  None = row 0 for every agent, the reference's REINFORCE loop (src/reinforce.py:128-129)."""
         model, dev = self.model, self.device
+        cls = None if classes is None else _classes_table(classes, env.batch_size)       # checked before any engine call
         if token_positions is None:
             token_positions = "sequence" if getattr(model.config, "no_recurrent_embedding", False) else "recurrent"
         if token_positions not in ("sequence", "recurrent"):
@@ -169,6 +185,8 @@ class ReinforceTrainer:
             # engine (and the default path, which makes none of these calls) finds it as it always was
             if keys is not None:
                 check(eng.lib.jn_set_rollout_keys(eng.handle, keys.ctypes.data_as(C.c_void_p), B), "jn_set_rollout_keys")
+            if cls is not None:
+                check(eng.lib.jn_set_rollout_classes(eng.handle, cls.ctypes.data_as(C.c_void_p), B), "jn_set_rollout_classes")
             if by_token:
                 check(eng.lib.jn_set_rollout_positions(eng.handle, 1), "jn_set_rollout_positions")
             if teacher:
@@ -188,6 +206,8 @@ class ReinforceTrainer:
         finally:
             if keys is not None:
                 eng.lib.jn_set_rollout_keys(eng.handle, None, 0)
+            if cls is not None:
+                eng.lib.jn_set_rollout_classes(eng.handle, None, 0)
             if by_token:
                 eng.lib.jn_set_rollout_positions(eng.handle, 0)
             if teacher:
@@ -265,6 +285,8 @@ class ReinforceTrainer:
             env = NeedleGeneralEnv(images, bboxes, self.patch_size, self.max_ep_len, self.n_glimps_levels, self.stop_enabled,
                                    engine=model.engine(), uint8_images=u8)
         self.last_env = env
+        if getattr(config, "class_tokens", False) and "classes" not in rollout_kw and batch.get("class_id") is not None:
+            rollout_kw["classes"] = batch["class_id"]       # opt-in: the reference's loop feeds zeros (src/reinforce.py:128-129)
         rollout = self.rollout(env, keep_patches=False, **rollout_kw)
         metrics = self.compute_metrics(rollout)
         loss = metrics["loss"]
@@ -374,10 +396,12 @@ class ReinforceTrainer:
 
     def train_iteration(self, env: NeedleGeneralEnv, sample_actions: bool = True, forced_actions=None,
                         start_positions=None, stop_early: bool = True, optimizer_step: bool = True,
-                        process_group=None, agent_keys=None) -> Dict[str, torch.Tensor]:
+                        process_group=None, agent_keys=None, classes=None) -> Dict[str, torch.Tensor]:
         """rollout (train-mode BatchNorm) -> compute_metrics -> backward -> [all-reduce] -> clip + AdamW,
-        all inside the engine.  Returns the metrics of src/reinforce.py:243-252.  `agent_keys`: see ``rollout``."""
+        all inside the engine.  Returns the metrics of src/reinforce.py:243-252.  `agent_keys`, `classes`: see
+        ``rollout``."""
         model, dev = self.model, self.device
+        cls = None if classes is None else _classes_table(classes, env.batch_size)       # checked before any engine call
         model.sync_weights()
         eng = model.engine()
         env.bind(eng)
@@ -418,12 +442,16 @@ class ReinforceTrainer:
         try:
             if keys is not None:           # sticky in the engine: set for this iteration only
                 check(eng.lib.jn_set_rollout_keys(eng.handle, keys.ctypes.data_as(C.c_void_p), B), "jn_set_rollout_keys")
+            if cls is not None:
+                check(eng.lib.jn_set_rollout_classes(eng.handle, cls.ctypes.data_as(C.c_void_p), B), "jn_set_rollout_classes")
             check(eng.lib.jn_reinforce_step(eng.handle, mode, ptr(forced_actions), ptr(start_positions), seed,
                                             int(stop_early), C.byref(opts), C.byref(out), ptr(metrics_dev), stream),
                   "jn_reinforce_step")
         finally:
             if keys is not None:
                 eng.lib.jn_set_rollout_keys(eng.handle, None, 0)
+            if cls is not None:
+                eng.lib.jn_set_rollout_classes(eng.handle, None, 0)
         m = metrics_dev.cpu()
         S = int(m[5])
         if self.config.reward_norm:
@@ -540,7 +568,8 @@ class ReinforceTrainer:
 
     @torch.no_grad()
     def eval_on_images(self, images, bboxes, batch_size: int, do_detection: bool = None,
-                       merge_bboxes: bool = None, device_metrics: bool = False, token_positions: str = None) -> Dict[str, list]:
+                       merge_bboxes: bool = None, device_metrics: bool = False, token_positions: str = None,
+                       class_ids=None) -> Dict[str, list]:
         """The per-image ``all_metrics`` of the reference's ``test()`` (src/reinforce.py:383-392) without its loop of
         ``B = 1`` envs: `images` ([3, Hi, Wi] tensors of any sizes, uint8 read in place or float 0..1) are evaluated
         `batch_size` at a time (``ragged.plan_chunks``), every agent inside its own image.  Returns, for every key of
@@ -552,9 +581,10 @@ class ReinforceTrainer:
         device_metrics=True: the `map` entry of a whole chunk comes from the device — the rollout's boxes go
         ``rollout_boxes_packed`` -> (merge_bboxes) ``merge_boxes_device`` -> ``map_50_device(per_image=True)`` without
         leaving it, the targets are merged there too; one readback per chunk.  Same keys; `map` equals the host
-        path's up to fp32 storage; the `yolo_*` entries are computed as without it.  `token_positions`: see ``rollout``."""
+        path's up to fp32 storage; the `yolo_*` entries are computed as without it.  `token_positions`: see ``rollout``.
+        `class_ids`: one class per image (a tensor or a sequence) behind the class token of its walk; None = class 0."""
         per_image = self._eval_image_chunks(images, bboxes, batch_size, do_detection, merge_bboxes, device_metrics,
-                                            token_positions=token_positions)
+                                            token_positions=token_positions, class_ids=class_ids)
         out: Dict[str, list] = {}
         for tail, ro_b in per_image:                      # compute_metrics in image order: the reward-norm window's order
             m = self.compute_metrics(ro_b)
@@ -567,7 +597,7 @@ class ReinforceTrainer:
     def _eval_image_chunks(self, images, bboxes, batch_size: int, do_detection: bool = None, merge_bboxes: bool = None,
                            device_metrics: bool = False, sample_actions: bool = False, token_positions: str = None,
                            teacher_targets=None, walks: int = 1, walk_starts=None, chunk_metrics=None,
-                           streams: str = "loop") -> list:
+                           streams: str = "loop", class_ids=None) -> list:
         """The chunked rollouts behind ``eval_on_images`` (and ``SupervisedTrainer.eval_on_images``): per image, in image
         order, (the metrics that do not come from ``compute_metrics``, the image's own ``B = 1`` rollout).
         teacher_targets: a callable (box rows of the chunk's images, their grid extents, the canvas grid) -> uint8
@@ -583,13 +613,16 @@ class ReinforceTrainer:
         streams: "loop" — a sampled walk draws its actions from the stream of its own rollout of the per-image loop
         (``ragged.walk_agent_keys``), so that it is that rollout's walk; "batch" — from (the chunk's seed, its place in
         the chunk).  Greedy chunks make no such call.
+        class_ids: one class per IMAGE (``ragged.image_classes``); agent i * K + k of a chunk carries the class of its
+        image i, so the K walks of an image share its class (``ragged.walk_classes``).  None: class 0, no call.
         chunk_metrics: a callable(chunk) called once per chunk with {"indices", "env", "rollout", "steps", "extents"
         (per agent), "rows", "walks", "targets" (the teacher grid per agent or None)} in place of the per-image detection
         metrics (`map`, `yolo_*`), which are then not computed."""
         from .detection import (detection_targets, map_50_device, merge_boxes_device, pack_boxes, rollout_boxes_packed,
                                 split_bboxes_over_patches, unpack_boxes)
         from .ragged import (env_metrics, found_ratios, image_env, loop_start_positions, own_steps, plan_chunks,
-                             slice_rollout, walk_agent_keys)
+                             image_classes, slice_rollout, walk_agent_keys, walk_classes)
+        class_ids = image_classes(class_ids, len(images))
         if streams not in ("loop", "batch"):
             raise ValueError(f"streams must be 'loop' or 'batch', got {streams!r}")
         cfg, P = self.config, int(self.patch_size)
@@ -630,6 +663,8 @@ class ReinforceTrainer:
                 starts = loop_start_positions(self, first, sel, extents)
             if sample_actions and streams == "loop":
                 kw["agent_keys"] = walk_agent_keys(self, first, imgs_of, K)
+            if class_ids is not None:
+                kw["classes"] = walk_classes(class_ids, imgs_of, K)
             ro = self.rollout(env, sample_actions=sample_actions, do_detection=do_detection, bbox_lists=False,
                               start_positions=starts, token_positions=token_positions, **kw)
             steps = own_steps(ro)

@@ -311,7 +311,8 @@ class SupervisedTrainer:
 
     @torch.no_grad()
     def eval_on_images(self, images, bboxes, batch_size: int, sample_actions: bool = False, do_detection: bool = None,
-                       merge_bboxes: bool = None, device_metrics: bool = False, streams: str = "loop") -> Dict[str, list]:
+                       merge_bboxes: bool = None, device_metrics: bool = False, streams: str = "loop",
+                       class_ids=None) -> Dict[str, list]:
         """The free-running half of the reference's ``test()``: ``test_model_on_env`` (src/supervised.py:279-405) lets the
         policy walk one image, calling the full-sequence forward again at every step, and compares every chosen action
         with the teacher's ``best_action``.  Here the walks are the engine's rollouts with the token of step t at 1-D
@@ -329,11 +330,14 @@ class SupervisedTrainer:
         part of its walk on the host (actions, positions, logits, teacher_sets, teacher_targets).  With sample_actions
         every walk samples from the stream of its own rollout of the per-image loop (``ragged.walk_agent_keys``), so
         the result does not depend on `batch_size`; streams="batch" keeps the draws keyed by the place in the chunk.
+        `class_ids`: one class per image (a tensor or a sequence): the class token of image i's walk is row class_ids[i]
+        of ``embed_class``, as ``test_model_on_env`` feeds ``classes=sample["class_id"]`` at every step
+        (src/supervised.py:284, 317-331); None = class 0 for every walk.
         Deviations from the reference: DESIGN.md §6."""
         if do_detection is None:
             do_detection = bool(getattr(self.config, "detection_enabled", True)) and self.yolox_model() is not None
         return self._walk_metrics(self._eval_walks(images, bboxes, batch_size, do_detection, merge_bboxes, device_metrics,
-                                                   sample_actions=sample_actions, streams=streams))
+                                                   sample_actions=sample_actions, streams=streams, class_ids=class_ids))
 
     def _eval_walks(self, images, bboxes, batch_size, do_detection, merge_bboxes, device_metrics, **kw) -> list:
         """The free-running walks of both evaluations: ``ReinforceTrainer._eval_image_chunks`` in sequence-position mode
@@ -376,7 +380,7 @@ class SupervisedTrainer:
     @torch.no_grad()
     def eval_envs_on_images(self, images, bboxes, batch_size: int, eval_mode: str = "multistart", n_starts: int = 2,
                             sample_actions: bool = False, start_positions=None, device_metrics: bool = True,
-                            streams: str = "loop") -> Dict[str, list]:
+                            streams: str = "loop", class_ids=None) -> Dict[str, list]:
         """``eval_envs`` of the reference (src/supervised.py:638-752) without its plots — the evaluation whose `map` at one
         start selects ``checkpoint_best.pt`` (:81, :804): every image is walked from K starts and, for every prefix
         k = 1..K of those walks, the detections of the walks are pooled per visited patch, de-duplicated by an NMS at
@@ -392,6 +396,8 @@ class SupervisedTrainer:
         (``ragged.walk_agent_keys``): the K walks of an image are that loop's K rollouts, whatever `batch_size` is;
         streams="batch" keeps the draws keyed by the agent's place in the chunk.  The
         tokens of a walk are t = 0 .. its own steps, the last patch reached included (:354-363).
+        `class_ids`: one class per image; all K walks of image i run under class_ids[i], as ``eval_envs`` hands the image's
+        ``class_id`` to every ``test_model_on_env`` call (:663-687).  None = class 0 for every walk.
 
         Returns lists.  One entry per WALK, in image order then walk order (:694-695): `prop_patches_found`,
         `episode_length`, `teacher_agreement`, `stopped_inside_bbox` as ``eval_on_images`` reports them.  One entry per
@@ -480,7 +486,7 @@ class SupervisedTrainer:
 
         out = self._walk_metrics(self._eval_walks(images, bboxes, batch_size, True, False, device_metrics,
                                                   sample_actions=sample_actions, walks=K, walk_starts=starts,
-                                                  chunk_metrics=chunk_metrics, streams=streams))
+                                                  chunk_metrics=chunk_metrics, streams=streams, class_ids=class_ids))
         for i in range(len(images)):
             for k, v in per_image[i].items():
                 out.setdefault(k, []).append(v)
@@ -632,8 +638,12 @@ class SupervisedTrainer:
                        seed: Optional[int] = None, streams: str = "loop") -> Dict[str, list]:
         """The metric assembly of ``test()`` (src/supervised.py:754-810) without logger, plots or checkpoint: the
         multistart evaluation's lists (``eval_envs_on_images``), the validation lists under ``supervised_<name>``
-        (:796-799); sets ``last_test_metrics`` and extends ``best_metric_history`` by the mean of ``best_metric_name``."""
-        metrics = self.eval_envs_on_images(images, bboxes, batch_size, sample_actions=sample_actions, streams=streams)
+        (:796-799); sets ``last_test_metrics`` and extends ``best_metric_history`` by the mean of ``best_metric_name``.
+        `class_ids` (one per image) condition BOTH halves: the walks of the multistart evaluation run under the image's
+        class, as the teacher-forced validation always did (before, the walks ran under class 0 whatever was given);
+        None = class 0 everywhere, every result as before."""
+        metrics = self.eval_envs_on_images(images, bboxes, batch_size, sample_actions=sample_actions, streams=streams,
+                                           class_ids=class_ids)
         for name, values in self.eval_supervised_on_images(images, bboxes, batch_size, class_ids=class_ids, seed=seed).items():
             metrics["supervised_" + name] = values
         self.last_test_metrics = metrics
