@@ -418,8 +418,6 @@ int jn_destroy(jn_ctx* ctx) {
   if (ctx->aux_fork) (void)hipEventDestroy(ctx->aux_fork);
   if (ctx->aux_join) (void)hipEventDestroy(ctx->aux_join);
   if (ctx->steps_ev) (void)hipEventDestroy(ctx->steps_ev);
-  if (ctx->keys_ev) (void)hipEventDestroy(ctx->keys_ev);
-  if (ctx->classes_ev) (void)hipEventDestroy(ctx->classes_ev);
   if (ctx->n_done_host) (void)hipHostFree(ctx->n_done_host);
   if (ctx->aux_stream) (void)hipStreamDestroy(ctx->aux_stream);
   delete ctx;

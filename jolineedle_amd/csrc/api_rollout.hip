@@ -44,10 +44,10 @@ int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const
   JN_CHECK(out->rewards_dev && out->masks_dev, JN_EINVAL, "rewards_dev and masks_dev are required outputs");
   JN_CHECK(!do_detection || (ctx->has_net[JN_NET_DETECTOR] && out->det_boxes_dev && out->det_counts_dev), JN_EINVAL,
            "do_detection needs a detector and det_boxes_dev / det_counts_dev outputs");
-  const int n_keys = (int)(ctx->keys_host.size() / 2);
+  const int n_keys = ctx->keys.rows();
   JN_CHECK(n_keys == 0 || n_keys == ctx->env.B, JN_EINVAL,
            "jn_set_rollout_keys armed %d agent streams, the env has %d agents", n_keys, ctx->env.B);
-  const int n_classes = (int)ctx->classes_host.size();
+  const int n_classes = ctx->classes.rows();
   JN_CHECK(n_classes == 0 || n_classes == ctx->env.B, JN_EINVAL,
            "jn_set_rollout_classes armed %d class ids, the env has %d agents", n_classes, ctx->env.B);
   JN_HIP(hipSetDevice(ctx->cfg.device));
@@ -72,47 +72,19 @@ int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const
                    out->logit_masks_dev, out->positions_dev, out->actions_dev, out->logits_dev, out->final_emb_dev};
   { int rz = zero_rollout_outputs(r, tsets, B, T, C, nA, s); if (rz) return rz; }
 
-  // per-agent streams: the context's copy goes up on this rollout's stream, an event behind it for the setter
+  // per-agent streams and class ids: the context's copies go up on this rollout's stream (null: not armed)
   const uint64_t* keys = nullptr;
-  if (n_keys) {
-    if (ctx->keys_dev_cap < (size_t)n_keys) {
-      int rk = dev_alloc(ctx, &ctx->keys_dev, (size_t)std::max(c.max_batch, n_keys) * 2);
-      if (rk) return rk;
-      ctx->keys_dev_cap = (size_t)std::max(c.max_batch, n_keys);
-      ctx->keys_dirty = true;
-    }
-    if (ctx->keys_dirty) {
-      if (!ctx->keys_ev) JN_HIP(hipEventCreateWithFlags(&ctx->keys_ev, hipEventDisableTiming));
-      JN_HIP(hipMemcpyAsync(ctx->keys_dev, ctx->keys_host.data(), (size_t)n_keys * 2 * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-      JN_HIP(hipEventRecord(ctx->keys_ev, s));
-      ctx->keys_dirty = false;
-    }
-    keys = ctx->keys_dev;
-  }
-  // class ids: the same way; a train-mode rollout also keeps the ids it ran with for its backward
   const int64_t* classes = nullptr;
-  if (n_classes) {
-    if (ctx->classes_dev_cap < (size_t)n_classes) {
-      int rk = dev_alloc(ctx, &ctx->classes_dev, (size_t)std::max(c.max_batch, n_classes));
+  { int rk = ctx->keys.upload(ctx, c.max_batch, s, &keys); if (rk) return rk; }
+  { int rk = ctx->classes.upload(ctx, c.max_batch, s, &classes); if (rk) return rk; }
+  // a train-mode rollout also keeps the ids it ran with for its backward
+  if (train && classes) {
+    if (ctx->classes_used_cap < (size_t)n_classes) {
+      int rk = dev_alloc(ctx, &ctx->classes_used, (size_t)std::max(c.max_batch, n_classes));
       if (rk) return rk;
-      ctx->classes_dev_cap = (size_t)std::max(c.max_batch, n_classes);
-      ctx->classes_dirty = true;
+      ctx->classes_used_cap = (size_t)std::max(c.max_batch, n_classes);
     }
-    if (ctx->classes_dirty) {
-      if (!ctx->classes_ev) JN_HIP(hipEventCreateWithFlags(&ctx->classes_ev, hipEventDisableTiming));
-      JN_HIP(hipMemcpyAsync(ctx->classes_dev, ctx->classes_host.data(), (size_t)n_classes * sizeof(int64_t), hipMemcpyHostToDevice, s));
-      JN_HIP(hipEventRecord(ctx->classes_ev, s));
-      ctx->classes_dirty = false;
-    }
-    classes = ctx->classes_dev;
-    if (train) {
-      if (ctx->classes_used_cap < (size_t)n_classes) {
-        int rk = dev_alloc(ctx, &ctx->classes_used, (size_t)std::max(c.max_batch, n_classes));
-        if (rk) return rk;
-        ctx->classes_used_cap = (size_t)std::max(c.max_batch, n_classes);
-      }
-      JN_HIP(hipMemcpyAsync(ctx->classes_used, classes, (size_t)n_classes * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-    }
+    JN_HIP(hipMemcpyAsync(ctx->classes_used, classes, (size_t)n_classes * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
   }
   if (train) ctx->classes_used_n = n_classes;
 
@@ -303,7 +275,7 @@ int jn_set_rollout_teacher(jn_ctx* ctx, const uint8_t* targets_dev, uint8_t* set
 int jn_set_rollout_keys(jn_ctx* ctx, const uint64_t* keys_host, int n) {
   JN_CHECK(ctx, JN_EINVAL, "jn_set_rollout_keys: null ctx");
   if (!keys_host) {
-    ctx->keys_host.clear();
+    ctx->keys.clear();
     return JN_OK;
   }
   JN_CHECK(n >= 1, JN_EINVAL, "jn_set_rollout_keys: n = %d with a table", n);
@@ -311,17 +283,13 @@ int jn_set_rollout_keys(jn_ctx* ctx, const uint64_t* keys_host, int n) {
     JN_CHECK(keys_host[2 * b + 1] <= 0xFFFFFFFFull, JN_EINVAL,
              "jn_set_rollout_keys: the stream index of agent %d, %llu, does not fit 32 bits", b,
              (unsigned long long)keys_host[2 * b + 1]);
-  // (an upload of the previous table may still be reading the copy; no event exists before the first armed rollout)
-  if (ctx->keys_ev) JN_HIP(hipEventSynchronize(ctx->keys_ev));
-  ctx->keys_host.assign(keys_host, keys_host + (size_t)n * 2);
-  ctx->keys_dirty = true;
-  return JN_OK;
+  return ctx->keys.set(keys_host, (size_t)n);
 }
 
 int jn_set_rollout_classes(jn_ctx* ctx, const int64_t* classes_host, int n) {
   JN_CHECK(ctx, JN_EINVAL, "jn_set_rollout_classes: null ctx");
   if (!classes_host) {
-    ctx->classes_host.clear();
+    ctx->classes.clear();
     return JN_OK;
   }
   JN_CHECK(n >= 1, JN_EINVAL, "jn_set_rollout_classes: n = %d with a table", n);
@@ -329,11 +297,7 @@ int jn_set_rollout_classes(jn_ctx* ctx, const int64_t* classes_host, int n) {
     JN_CHECK(classes_host[b] >= 0 && classes_host[b] < JN_N_CLASS_ROWS, JN_EINVAL,
              "jn_set_rollout_classes: the class id of agent %d, %lld, is outside embed_class (rows 0 .. %d)", b,
              (long long)classes_host[b], JN_N_CLASS_ROWS - 1);
-  // (an upload of the previous table may still be reading the copy; no event exists before the first armed rollout)
-  if (ctx->classes_ev) JN_HIP(hipEventSynchronize(ctx->classes_ev));
-  ctx->classes_host.assign(classes_host, classes_host + n);
-  ctx->classes_dirty = true;
-  return JN_OK;
+  return ctx->classes.set(classes_host, (size_t)n);
 }
 
 int jn_rollout_steps(jn_ctx* ctx, int* n_steps, void* stream) {

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <map>
@@ -229,6 +230,32 @@ struct EnvState {
   int32_t* extent = nullptr;      // [max_batch][2] = (gh, gw)
 };
 
+// A per-agent host table behind a rollout switch (jn_set_rollout_keys, jn_set_rollout_classes): the context's own copy
+// of the caller's [rows][Width] values, armed while it is not empty, and its device twin, which the next rollout
+// uploads on its own stream when the copy has changed.  The one ordering rule: `ev` sits behind the most recent upload,
+// and set() waits for it before it rewrites the copy, which that asynchronous upload may still be reading (no event
+// exists before the first armed rollout).
+template <typename T, int Width = 1>
+struct AgentTable {
+  std::vector<T> host; T* dev = nullptr; size_t dev_rows = 0; bool dirty = false;
+  hipEvent_t ev = nullptr;
+
+  bool armed() const { return !host.empty(); }
+  int rows() const { return (int)(host.size() / Width); }
+  void clear() { host.clear(); }
+  int set(const T* values, size_t n_rows) {
+    if (ev) JN_HIP(hipEventSynchronize(ev));
+    host.assign(values, values + n_rows * Width);
+    dirty = true;
+    return JN_OK;
+  }
+  // *dev_out = the device table holding the armed rows (at least min_rows of capacity), or null when not armed
+  int upload(jn_ctx* ctx, int min_rows, hipStream_t s, const T** dev_out);
+  AgentTable() = default;
+  AgentTable(const AgentTable&) = delete;      // owns `ev`
+  ~AgentTable() { if (ev) (void)hipEventDestroy(ev); }
+};
+
 }  // namespace jnr
 
 struct jn_ctx {
@@ -310,17 +337,11 @@ struct jn_ctx {
   bool det_loss_all = false;      // jn_set_det_loss_boxes: targets wider than 8 rows go to launch_yolox_loss_wide
   // jn_set_rollout_teacher: armed while teacher_sets is set; caller-owned [B,T] bytes and [B,Gh,Gw] grid (null = bbox_masks)
   uint8_t* teacher_sets = nullptr; const uint8_t* teacher_targets = nullptr;
-  // jn_set_rollout_keys: armed while keys_host is not empty; the context's own copy of the [n][2] table, uploaded to
-  // keys_dev (keys_dev_cap rows) on the stream of the next rollout when keys_dirty; keys_ev sits behind that upload (the
-  // setter waits for it before it rewrites the copy)
-  std::vector<uint64_t> keys_host; uint64_t* keys_dev = nullptr; size_t keys_dev_cap = 0; bool keys_dirty = false;
-  hipEvent_t keys_ev = nullptr;
-  // jn_set_rollout_classes: the same scheme for the class id behind every agent's class token — armed while classes_host
-  // is not empty, uploaded to classes_dev (classes_dev_cap ids) when classes_dirty, classes_ev behind that upload.  A
-  // train-mode rollout leaves the ids it ran with in classes_used (its own device copy, like drop_seed_used: the backward
-  // runs after the caller has cleared or rewritten the table); classes_used_n = 0: it ran without a table (class 0)
-  std::vector<int64_t> classes_host; int64_t* classes_dev = nullptr; size_t classes_dev_cap = 0; bool classes_dirty = false;
-  hipEvent_t classes_ev = nullptr;
+  // jn_set_rollout_keys: the [n][2] = (stream seed, stream index) table; jn_set_rollout_classes: the class id behind
+  // every agent's class token.  A train-mode rollout leaves the ids it ran with in classes_used (its own device copy,
+  // like drop_seed_used: the backward runs after the caller has cleared or rewritten the table); classes_used_n = 0: it
+  // ran without a table (class 0)
+  jnr::AgentTable<uint64_t, 2> keys; jnr::AgentTable<int64_t> classes;
   int64_t* classes_used = nullptr; size_t classes_used_cap = 0; int classes_used_n = 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   bool profiling = false;
@@ -358,6 +379,28 @@ int dev_alloc(jn_ctx* ctx, T** out, size_t count) {
   }
   ctx->owned.push_back(p);
   *out = (T*)p;
+  return JN_OK;
+}
+
+template <typename T, int Width>
+int AgentTable<T, Width>::upload(jn_ctx* ctx, int min_rows, hipStream_t s, const T** dev_out) {
+  *dev_out = nullptr;
+  if (!armed()) return JN_OK;
+  const size_t n = (size_t)rows();
+  if (dev_rows < n) {
+    const size_t want = std::max((size_t)min_rows, n);
+    int rc = dev_alloc(ctx, &dev, want * Width);
+    if (rc) return rc;
+    dev_rows = want;
+    dirty = true;
+  }
+  if (dirty) {
+    if (!ev) JN_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    JN_HIP(hipMemcpyAsync(dev, host.data(), n * Width * sizeof(T), hipMemcpyHostToDevice, s));
+    JN_HIP(hipEventRecord(ev, s));
+    dirty = false;
+  }
+  *dev_out = dev;
   return JN_OK;
 }
 

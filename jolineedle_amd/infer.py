@@ -11,8 +11,7 @@ import torch.nn.functional as F
 from .detection import (compute_detection_metrics, detection_targets, map_50_device, pack_boxes, patch_bboxes2full_image,
                         rollout_boxes_packed, rollout_boxes_to_image, unpack_boxes)  # noqa: F401
 from .env import NeedleGeneralEnv
-from .ragged import (env_metrics, found_ratios, image_classes, image_env, loop_agent_keys, loop_start_positions,  # noqa: F401
-                     own_steps, plan_chunks, slice_rollout, walk_classes)
+from .ragged import env_metrics, image_classes, plan_chunks, rollout_chunks, slice_rollout, walk_classes  # noqa: F401
 
 
 def load_bboxes(bbox_fname) -> List[List[int]]:
@@ -116,48 +115,36 @@ def _infer_batched(trainer, images, targets, sample_actions, do_detection, batch
     n = len(images)
     res = {"boxes": [None] * n, "positions": [None] * n, "steps": [0] * n, "duration_ms": [0.0] * n}
     per_image = [None] * n
-    first = trainer._rollouts + 1                         # the loop's rollout of image i is this trainer's number first + i
-    for chunk in plan_chunks(images, batch_size, P, getattr(trainer.model, "max_batch", None)):
-        sel = chunk["indices"]
-        has_tg = [not (targets is None or i >= len(targets) or targets[i] is None) for i in sel]
-        rows = [torch.as_tensor(targets[i]).reshape(-1, 4).to(torch.long) if h else torch.zeros((1, 4), dtype=torch.long)
-                for i, h in zip(sel, has_tg)]
-        imgs = [images[i] if images[i].dtype == torch.uint8 else images[i].float() for i in sel]
-        env = image_env(trainer, imgs, rows, canvas=chunk["canvas"])
-        extents = env.grid_extents.tolist()
-        start = loop_start_positions(trainer, first, sel, extents)
-        keys = loop_agent_keys(trainer, first, sel) if sample_actions and streams == "loop" else None    # greedy: no call
-        t0 = time.perf_counter()
-        ro = trainer.rollout(env, do_detection=do_detection, sample_actions=sample_actions, start_positions=start,
-                             bbox_lists=False, token_positions=token_positions, agent_keys=keys,
-                             classes=walk_classes(class_ids, sel))
-        torch.cuda.synchronize(dev)
-        ms = (time.perf_counter() - t0) * 1e3 / len(sel)
+    has_tg = [not (targets is None or i >= len(targets) or targets[i] is None) for i in range(n)]
+    # (an image without targets gets the box (0, 0, 0, 0), as in the loop)
+    rows = [torch.as_tensor(targets[i]).reshape(-1, 4).to(torch.long) if h else torch.zeros((1, 4), dtype=torch.long)
+            for i, h in enumerate(has_tg)]
+    for ch in rollout_chunks(trainer, images, rows, batch_size, sample_actions=sample_actions, do_detection=do_detection,
+                             token_positions=token_positions, streams=streams, class_ids=class_ids):
+        sel, ro, steps, extents = ch["indices"], ch["rollout"], ch["steps"], ch["extents"]
+        ms = ch["seconds"] * 1e3 / len(sel)                # (the walker read the step counts back: the rollout has ended)
         packed = rollout_boxes_packed(ro, P) if do_detection else None
         full = unpack_boxes(*packed) if do_detection else [None] * len(sel)
         maps = None
-        if do_detection and device_metrics and any(has_tg):
-            tg = pack_boxes([detection_targets(rows[b].unsqueeze(0), *extents[b], P)[0] if has_tg[b] else None
-                             for b in range(len(sel))], 5, dev)
+        if do_detection and device_metrics and any(has_tg[i] for i in sel):
+            tg = pack_boxes([detection_targets(rows[i].unsqueeze(0), *extents[b], P)[0] if has_tg[i] else None
+                             for b, i in enumerate(sel)], 5, dev)
             maps = map_50_device(packed, tg, per_image=True)
-        steps = own_steps(ro)
-        found = found_ratios(env, ro, steps) if any(has_tg) else None
         pos_cpu, masks_cpu = ro["positions"].cpu(), ro["masks"].cpu()
         for b, i in enumerate(sel):
             res["boxes"][i] = full[b]
             res["positions"][i] = pos_cpu[b, :steps[b] + 1][masks_cpu[b, :steps[b] + 1]]
             res["steps"][i] = steps[b]
             res["duration_ms"][i] = ms
-            if has_tg[b]:
+            if has_tg[i]:
                 ro_b = slice_rollout(ro, b, steps[b])
-                m = dict(env_metrics(trainer, found, ro_b, b))       # what follows compute_metrics' own entries
+                m = dict(env_metrics(trainer, ch["found"], ro_b, b))       # what follows compute_metrics' own entries
                 if maps is not None:
                     m["map"] = torch.tensor([maps[b]], dtype=torch.float32)
                 elif do_detection:
                     gh, gw = extents[b]
-                    m.update(compute_detection_metrics([full[b]], detection_targets(rows[b].unsqueeze(0), gh, gw, P)))
+                    m.update(compute_detection_metrics([full[b]], detection_targets(rows[i].unsqueeze(0), gh, gw, P)))
                 per_image[i] = (ro_b, m)
-    trainer._rollouts = first - 1 + n                     # where the loop leaves the counter
     all_metrics = defaultdict(list)
     for entry in per_image:                               # in input order, as the loop accumulates them (and as it
         if entry is not None:                             # feeds the reward-norm window through compute_metrics)

@@ -9,6 +9,7 @@ step after which its agent is terminated or truncated, and in a batch that step 
 the masked steps after that point add exact zeros.  The env of the batch keeps stepping an agent after its own end (a
 stopped agent still moves), so the found-ratios are rebuilt from the positions up to the image's own last step and not
 read from the env's final state."""
+import time
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -129,6 +130,93 @@ def walk_classes(class_ids: Optional[Sequence[int]], indices: Sequence[int], n_w
     if class_ids is None:
         return None
     return [int(class_ids[i]) for i in indices for _ in range(int(n_walks))]
+
+
+def chunk_walks(trainer, first_rollout: int, indices: Sequence[int], extents: Sequence[Sequence[int]], n_walks: int = 1,
+                sample_actions: bool = False, streams: str = "loop", class_ids: Optional[Sequence[int]] = None,
+                walk_starts=None) -> Dict:
+    """Who walks what in one chunk of ``rollout_chunks``, from numbers alone (no device): the n images `indices`, grid
+    extents[j] = (gh, gw), run as n * K agents, agents j * K .. j * K + K - 1 walking image indices[j].  "sel": per agent
+    its walk number i * K + k; "image_of": its image; "starts" int64 [n * K, 2]: where rollout first_rollout + i * K + k of
+    the per-image loop would start (``loop_start_positions``), or walk_starts(first_rollout, indices, extents) -> [n, K, 2];
+    "keys": the stream of that same rollout (``walk_agent_keys``), so that a sampled walk is that rollout's walk — None,
+    and then no call to the engine, for greedy walks and for streams="batch" (draws keyed by the chunk's seed and the
+    agent's place in the chunk); "classes": ``walk_classes``."""
+    K = int(n_walks)
+    sel = [i * K + k for i in indices for k in range(K)]
+    if walk_starts is not None:
+        starts = torch.as_tensor(walk_starts(first_rollout, indices, extents)).reshape(len(sel), 2).to(torch.int64)
+    else:
+        starts = loop_start_positions(trainer, first_rollout, sel, [e for e in extents for _ in range(K)])
+    keys = walk_agent_keys(trainer, first_rollout, indices, K) if sample_actions and streams == "loop" else None
+    return {"sel": sel, "image_of": [a // K for a in sel], "starts": starts, "keys": keys,
+            "classes": walk_classes(class_ids, indices, K)}
+
+
+def images_per_chunk(max_batch: Optional[int], n_walks: int) -> Optional[int]:
+    """The most images one chunk of K walks each may hold: n * K agents stay within the model's max_batch."""
+    return max_batch if max_batch is None or int(n_walks) == 1 else int(max_batch) // int(n_walks)
+
+
+def rollouts_after(first_rollout: int, n_images: int, n_walks: int = 1) -> int:
+    """The rollout counter after the per-image loop has walked `n_images` images K times from `first_rollout` on."""
+    return first_rollout - 1 + n_images * int(n_walks)
+
+
+@torch.no_grad()
+def rollout_chunks(trainer, images: Sequence[Tensor], rows: Sequence[Tensor], batch_size: int, walks: int = 1,
+                   sample_actions: bool = False, do_detection: bool = False, token_positions: Optional[str] = None,
+                   streams: str = "loop", class_ids=None, teacher_targets=None, walk_starts=None):
+    """The chunked rollouts behind every batched evaluation and inference: `images` ([3, Hi, Wi], rows[i] their [n_i, 4]
+    boxes) `batch_size` images at a time (``plan_chunks``), every image walked K = `walks` times as ``chunk_walks`` lays
+    out — the same stored image, one view-table row per walk with the same source pointer.  Yields one record per chunk:
+    "indices" (its images), "sel", "env", "extents" (per agent), "rollout" (``rollout(bbox_lists=False)``), "steps"
+    (``own_steps``), "found" (``found_ratios``), "targets", "rows", "walks" and "seconds" (from the rollout's call to the
+    readback of its masks); then leaves the trainer's rollout counter where the per-image loop would.
+    teacher_targets: a callable (box rows of the chunk's images, their grid extents, the canvas grid) -> uint8
+    [n, Gh, Gw]; the rollouts then carry "teacher_sets", "targets" is that grid per agent on the device (else None), and
+    the found-ratios count these cells instead of the env's bbox masks.  class_ids: one class per IMAGE, or None."""
+    class_ids = image_classes(class_ids, len(images))
+    if streams not in ("loop", "batch"):
+        raise ValueError(f"streams must be 'loop' or 'batch', got {streams!r}")
+    K, dev = int(walks), trainer.device
+    assert K >= 1 and len(rows) == len(images)
+    first = trainer._rollouts + 1                         # the loop's walk k of image i is this trainer's rollout first + i * K + k
+    bound = images_per_chunk(getattr(trainer.model, "max_batch", None), K)
+    for chunk in plan_chunks(images, batch_size, int(trainer.patch_size), bound):
+        imgs_of = chunk["indices"]
+        # one upload per image; its K walks hand the SAME tensor to the env, so their views share one source
+        once = {i: images[i].to(dev) if images[i].dtype == torch.uint8 else images[i].to(dev, torch.float32) for i in imgs_of}
+        env = image_env(trainer, [once[i] for i in imgs_of for _ in range(K)], [rows[i] for i in imgs_of for _ in range(K)],
+                        canvas=chunk["canvas"])
+        extents = env.grid_extents.tolist()
+        plan = chunk_walks(trainer, first, imgs_of, extents[::K], K, sample_actions, streams, class_ids, walk_starts)
+        tg_grid = None
+        if teacher_targets is not None:
+            tg_grid = teacher_targets([rows[i] for i in imgs_of], extents[::K], (env.n_vertical_patches, env.n_horizontal_patches))
+            tg_grid = tg_grid.to(dev)                     # uploaded once per chunk
+            if K > 1:
+                tg_grid = tg_grid.repeat_interleave(K, 0)
+        t0 = time.perf_counter()
+        ro = trainer.rollout(env, sample_actions=sample_actions, do_detection=do_detection, bbox_lists=False,
+                             start_positions=plan["starts"], token_positions=token_positions, agent_keys=plan["keys"],
+                             classes=plan["classes"], teacher=tg_grid is not None, teacher_targets=tg_grid)
+        steps = own_steps(ro)
+        seconds = time.perf_counter() - t0
+        found = found_ratios(env, ro, steps, masks=None if tg_grid is None else tg_grid.bool())
+        yield {"indices": imgs_of, "sel": plan["sel"], "env": env, "extents": extents, "rollout": ro, "steps": steps,
+               "found": found, "targets": tg_grid, "rows": rows, "walks": K, "seconds": seconds}
+    trainer._rollouts = rollouts_after(first, len(images), K)
+
+
+def walk_entries(trainer, chunk: Dict):
+    """Per agent of a ``rollout_chunks`` record: (its walk number, the entries ``env_metrics`` gives it, its own
+    ``B = 1`` rollout — with "teacher_targets" [1, Gh, Gw] when the teacher walked along)."""
+    for b, a in enumerate(chunk["sel"]):
+        ro_b = slice_rollout(chunk["rollout"], b, chunk["steps"][b])
+        if chunk["targets"] is not None:
+            ro_b["teacher_targets"] = chunk["targets"][b:b + 1]
+        yield a, dict(env_metrics(trainer, chunk["found"], ro_b, b)), ro_b
 
 
 def walk_start_positions(trainer, first_rollout: int, indices: Sequence[int], extents: Sequence[Sequence[int]], n_walks: int,

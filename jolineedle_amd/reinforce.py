@@ -1,6 +1,7 @@
 """``ReinforceTrainer.rollout`` and the REINFORCE metrics of the reference
 (src/reinforce.py:73-265) over ``jn_rollout``: the whole trajectory of the whole batch is
 enqueued on the current stream, with no host synchronisation until the step count is read."""
+import contextlib
 import ctypes as C
 from typing import Dict
 
@@ -56,6 +57,81 @@ class _RolloutGraph(torch.autograd.Function):
         check(eng.lib.jn_reinforce_backward(eng.handle, ptr(dlp), ptr(dent), _lib.current_stream(dev)), "jn_reinforce_backward")
         model.publish_engine_grads()
         return None, None, None, None, None, None
+
+
+class _RolloutCall:
+    """What one engine rollout needs, prepared the same way for ``ReinforceTrainer.rollout`` and ``train_iteration``: the
+    checked per-agent tables, the bound engine, the output buffers behind a ``JnRolloutOut``, the mode with its device
+    inputs, and — the trainer's rollout counter moved on — the seed and the agent keys of that rollout number."""
+
+    def __init__(self, trainer, env, sample_actions, forced_actions, start_positions, agent_keys, classes, token_positions):
+        model, dev = trainer.model, trainer.device
+        B = env.batch_size
+        self.classes = None if classes is None else _classes_table(classes, B)       # checked before any engine call
+        if token_positions is None:
+            token_positions = "sequence" if getattr(model.config, "no_recurrent_embedding", False) else "recurrent"
+        if token_positions not in ("sequence", "recurrent"):
+            raise ValueError(f"token_positions must be 'sequence', 'recurrent' or None, got {token_positions!r}")
+        self.by_token = token_positions == "sequence"
+        if self.by_token and model.training and torch.is_grad_enabled():
+            raise NotImplementedError(
+                "token_positions='sequence' is for eval-mode rollouts: in train mode the reference re-encodes the whole "
+                "prefix at every step with BatchNorm statistics over B*(t+1) patches, which the per-step rollout cannot "
+                "reproduce (call model.eval() or torch.no_grad())")
+        model.sync_weights()
+        self.eng = eng = model.engine()
+        env.bind(eng)
+        T, C_, nA = env.max_ep_len, model.n_embd, eng.cfg.n_actions
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.buf = {
+            "rewards": torch.empty((B, T), **f32), "returns": torch.empty((B, T), **f32),
+            "logprobs": torch.empty((B, T), **f32), "entropies": torch.empty((B, T), **f32),
+            "masks": torch.empty((B, T + 1), device=dev, dtype=torch.uint8),
+            "logit_masks": torch.empty((B, T), device=dev, dtype=torch.uint8),
+            "positions": torch.empty((B, T + 1, 2), device=dev, dtype=torch.int64),
+            "actions": torch.empty((B, T), device=dev, dtype=torch.int64),
+            "logits": torch.empty((B, T, nA), **f32),
+            "final_emb": torch.empty((B, T + 1, C_), **f32),
+        }
+        self.out = JnRolloutOut()
+        for k, t in self.buf.items():
+            setattr(self.out, k + "_dev", t.data_ptr())
+        if forced_actions is not None:
+            self.mode = _lib.JN_MODE_FORCED
+            forced_actions = forced_actions.to(dev, torch.int64).contiguous()
+        else:
+            self.mode = _lib.JN_MODE_SAMPLE if sample_actions else _lib.JN_MODE_GREEDY
+        if start_positions is not None:
+            start_positions = start_positions.to(dev, torch.int64).contiguous()
+        self.forced_actions, self.start_positions = forced_actions, start_positions
+        trainer._rollouts += 1
+        self.seed = (trainer.seed * 1000003 + trainer._rollouts) & 0xFFFFFFFFFFFFFFFF
+        self.keys = trainer._agent_keys_table(agent_keys, B)
+        self.stream = _lib.current_stream(dev)
+        self.teacher = None       # (targets [B,Gh,Gw] or None, sets [B,T]) on the device once the caller wants the teacher
+
+    @contextlib.contextmanager
+    def armed(self):
+        """The engine's switches around the one engine call.  They are sticky in the engine: set for this rollout only,
+        so that every other caller of the engine (and the default path, which makes none of these calls) finds it as it
+        always was — armed with ``check``, disarmed unchecked on the way out, also when the engine call raised."""
+        lib, h, B = self.eng.lib, self.eng.handle, len(self.buf["rewards"])
+        switches = []             # (export, arming arguments, disarming arguments)
+        if self.keys is not None:
+            switches.append(("jn_set_rollout_keys", (self.keys.ctypes.data_as(C.c_void_p), B), (None, 0)))
+        if self.classes is not None:
+            switches.append(("jn_set_rollout_classes", (self.classes.ctypes.data_as(C.c_void_p), B), (None, 0)))
+        if self.by_token:
+            switches.append(("jn_set_rollout_positions", (1,), (0,)))
+        if self.teacher is not None:
+            switches.append(("jn_set_rollout_teacher", tuple(ptr(t) for t in self.teacher), (None, None)))
+        try:
+            for name, on, _ in switches:
+                check(getattr(lib, name)(h, *on), name)
+            yield
+        finally:
+            for name, _, off in switches:
+                getattr(lib, name)(h, *off)
 
 
 class ReinforceTrainer:
@@ -122,54 +198,17 @@ class ReinforceTrainer:
         (src/supervised.py:317-331); in train mode the class token's gradient goes to those rows, whenever the backward
         runs.  None = row 0 for every agent, the reference's REINFORCE loop (src/reinforce.py:128-129)."""
         model, dev = self.model, self.device
-        cls = None if classes is None else _classes_table(classes, env.batch_size)       # checked before any engine call
-        if token_positions is None:
-            token_positions = "sequence" if getattr(model.config, "no_recurrent_embedding", False) else "recurrent"
-        if token_positions not in ("sequence", "recurrent"):
-            raise ValueError(f"token_positions must be 'sequence', 'recurrent' or None, got {token_positions!r}")
-        by_token = token_positions == "sequence"
-        if by_token and model.training and torch.is_grad_enabled():
-            raise NotImplementedError(
-                "token_positions='sequence' is for eval-mode rollouts: in train mode the reference re-encodes the whole "
-                "prefix at every step with BatchNorm statistics over B*(t+1) patches, which the per-step rollout cannot "
-                "reproduce (call model.eval() or torch.no_grad())")
-        model.sync_weights()
-        eng = model.engine()
-        env.bind(eng)
+        call = _RolloutCall(self, env, sample_actions, forced_actions, start_positions, agent_keys, classes, token_positions)
+        eng, buf, out, stream = call.eng, call.buf, call.out, call.stream
         B, T, P = env.batch_size, env.max_ep_len, env.patch_size
-        C_, nA = model.n_embd, eng.cfg.n_actions
         f32 = dict(device=dev, dtype=torch.float32)
-        buf = {
-            "rewards": torch.empty((B, T), **f32), "returns": torch.empty((B, T), **f32),
-            "logprobs": torch.empty((B, T), **f32), "entropies": torch.empty((B, T), **f32),
-            "masks": torch.empty((B, T + 1), device=dev, dtype=torch.uint8),
-            "logit_masks": torch.empty((B, T), device=dev, dtype=torch.uint8),
-            "positions": torch.empty((B, T + 1, 2), device=dev, dtype=torch.int64),
-            "actions": torch.empty((B, T), device=dev, dtype=torch.int64),
-            "logits": torch.empty((B, T, nA), **f32),
-            "final_emb": torch.empty((B, T + 1, C_), **f32),
-        }
         patches = torch.empty((B, T + 1, 3, P, P), **f32) if keep_patches else None
-        out = JnRolloutOut()
-        for k, t in buf.items():
-            setattr(out, k + "_dev", t.data_ptr())
         out.patches_dev = patches.data_ptr() if patches is not None else None
         Kd = eng.cfg.max_det_per_patch
         if do_detection:
             det_boxes = torch.zeros((B, T + 1, Kd, 7), **f32)
             det_counts = torch.zeros((B, T + 1), device=dev, dtype=torch.int32)
             out.det_boxes_dev, out.det_counts_dev = det_boxes.data_ptr(), det_counts.data_ptr()
-        if forced_actions is not None:
-            mode = _lib.JN_MODE_FORCED
-            forced_actions = forced_actions.to(dev, torch.int64).contiguous()
-        else:
-            mode = _lib.JN_MODE_SAMPLE if sample_actions else _lib.JN_MODE_GREEDY
-        if start_positions is not None:
-            start_positions = start_positions.to(dev, torch.int64).contiguous()
-        self._rollouts += 1
-        seed = (self.seed * 1000003 + self._rollouts) & 0xFFFFFFFFFFFFFFFF
-        keys = self._agent_keys_table(agent_keys, B)
-        stream = _lib.current_stream(dev)
         # model.train() + grad mode (the reference's training loop, src/reinforce.py:304, 326): batch-statistics BatchNorm,
         # activations of every step kept resident, logprobs / entropies leave with a graph (autograd bridge)
         graph = bool(model.training) and torch.is_grad_enabled() and not do_detection
@@ -180,38 +219,20 @@ class ReinforceTrainer:
                 teacher_targets = teacher_targets.to(dev, torch.uint8).contiguous()
                 grid = (B, env.n_vertical_patches, env.n_horizontal_patches)
                 assert tuple(teacher_targets.shape) == grid, f"teacher_targets must be {grid}, got {tuple(teacher_targets.shape)}"
-        try:
-            # the switches are sticky in the engine: set for this rollout only, so that every other caller of the
-            # engine (and the default path, which makes none of these calls) finds it as it always was
-            if keys is not None:
-                check(eng.lib.jn_set_rollout_keys(eng.handle, keys.ctypes.data_as(C.c_void_p), B), "jn_set_rollout_keys")
-            if cls is not None:
-                check(eng.lib.jn_set_rollout_classes(eng.handle, cls.ctypes.data_as(C.c_void_p), B), "jn_set_rollout_classes")
-            if by_token:
-                check(eng.lib.jn_set_rollout_positions(eng.handle, 1), "jn_set_rollout_positions")
-            if teacher:
-                check(eng.lib.jn_set_rollout_teacher(eng.handle, ptr(teacher_targets), ptr(sets)), "jn_set_rollout_teacher")
+            call.teacher = (teacher_targets, sets)
+        with call.armed():
             if graph:
                 model.bind_flat()
                 model._rollout_gen += 1
-                check(eng.lib.jn_reinforce_forward(eng.handle, mode, ptr(forced_actions), ptr(start_positions), seed,
-                                                   int(stop_early), C.byref(out), stream), "jn_reinforce_forward")
+                check(eng.lib.jn_reinforce_forward(eng.handle, call.mode, ptr(call.forced_actions), ptr(call.start_positions),
+                                                   call.seed, int(stop_early), C.byref(out), stream), "jn_reinforce_forward")
                 anchor = next(p for p in model.parameters() if p.requires_grad)
-                keep = dict(buf, forced_actions=forced_actions, start_positions=start_positions)
+                keep = dict(buf, forced_actions=call.forced_actions, start_positions=call.start_positions)
                 buf["logprobs"], buf["entropies"] = _RolloutGraph.apply(anchor, model, model._rollout_gen, buf["logprobs"],
                                                                         buf["entropies"], keep)
             else:
-                check(eng.lib.jn_rollout(eng.handle, mode, ptr(forced_actions), ptr(start_positions), seed,
+                check(eng.lib.jn_rollout(eng.handle, call.mode, ptr(call.forced_actions), ptr(call.start_positions), call.seed,
                                          int(do_detection), int(stop_early), C.byref(out), stream), "jn_rollout")
-        finally:
-            if keys is not None:
-                eng.lib.jn_set_rollout_keys(eng.handle, None, 0)
-            if cls is not None:
-                eng.lib.jn_set_rollout_classes(eng.handle, None, 0)
-            if by_token:
-                eng.lib.jn_set_rollout_positions(eng.handle, 0)
-            if teacher:
-                eng.lib.jn_set_rollout_teacher(eng.handle, None, None)
         S = C.c_int()
         check(eng.lib.jn_rollout_steps(eng.handle, C.byref(S), stream), "jn_rollout_steps")
         S = S.value
@@ -400,58 +421,21 @@ class ReinforceTrainer:
         """rollout (train-mode BatchNorm) -> compute_metrics -> backward -> [all-reduce] -> clip + AdamW,
         all inside the engine.  Returns the metrics of src/reinforce.py:243-252.  `agent_keys`, `classes`: see
         ``rollout``."""
-        model, dev = self.model, self.device
-        cls = None if classes is None else _classes_table(classes, env.batch_size)       # checked before any engine call
-        model.sync_weights()
-        eng = model.engine()
-        env.bind(eng)
+        model = self.model
+        # (a train-mode rollout is recurrent whatever the config says: see ``rollout`` on "sequence")
+        call = _RolloutCall(self, env, sample_actions, forced_actions, start_positions, agent_keys, classes, "recurrent")
+        eng, buf, stream = call.eng, call.buf, call.stream
         grads = self._grad_arena()
-        B, T, P = env.batch_size, env.max_ep_len, env.patch_size
-        C_, nA = model.n_embd, eng.cfg.n_actions
-        f32 = dict(device=dev, dtype=torch.float32)
-        buf = {
-            "rewards": torch.empty((B, T), **f32), "returns": torch.empty((B, T), **f32),
-            "logprobs": torch.empty((B, T), **f32), "entropies": torch.empty((B, T), **f32),
-            "masks": torch.empty((B, T + 1), device=dev, dtype=torch.uint8),
-            "logit_masks": torch.empty((B, T), device=dev, dtype=torch.uint8),
-            "positions": torch.empty((B, T + 1, 2), device=dev, dtype=torch.int64),
-            "actions": torch.empty((B, T), device=dev, dtype=torch.int64),
-            "logits": torch.empty((B, T, nA), **f32),
-            "final_emb": torch.empty((B, T + 1, C_), **f32),
-        }
-        out = JnRolloutOut()
-        for k, t in buf.items():
-            setattr(out, k + "_dev", t.data_ptr())
-        if forced_actions is not None:
-            mode = _lib.JN_MODE_FORCED
-            forced_actions = forced_actions.to(dev, torch.int64).contiguous()
-        else:
-            mode = _lib.JN_MODE_SAMPLE if sample_actions else _lib.JN_MODE_GREEDY
-        if start_positions is not None:
-            start_positions = start_positions.to(dev, torch.int64).contiguous()
-        self._rollouts += 1
         self.iter_num = getattr(self, "iter_num", 0) + 1
         ga = int(getattr(self.config, "gradient_accumulation", 1))
         opts = JnTrainOpts(struct_size=C.sizeof(JnTrainOpts), reward_norm=int(bool(self.config.reward_norm)),
                            ret_mean=float(self.last_return_mean), ret_std=float(self.last_return_std),
                            entropy_weight=float(self.entropy_weight), loss_scale=1.0 / ga)
-        metrics_dev = torch.zeros(8, **f32)
-        seed = (self.seed * 1000003 + self._rollouts) & 0xFFFFFFFFFFFFFFFF
-        keys = self._agent_keys_table(agent_keys, B)
-        stream = _lib.current_stream(dev)
-        try:
-            if keys is not None:           # sticky in the engine: set for this iteration only
-                check(eng.lib.jn_set_rollout_keys(eng.handle, keys.ctypes.data_as(C.c_void_p), B), "jn_set_rollout_keys")
-            if cls is not None:
-                check(eng.lib.jn_set_rollout_classes(eng.handle, cls.ctypes.data_as(C.c_void_p), B), "jn_set_rollout_classes")
-            check(eng.lib.jn_reinforce_step(eng.handle, mode, ptr(forced_actions), ptr(start_positions), seed,
-                                            int(stop_early), C.byref(opts), C.byref(out), ptr(metrics_dev), stream),
+        metrics_dev = torch.zeros(8, device=self.device, dtype=torch.float32)
+        with call.armed():
+            check(eng.lib.jn_reinforce_step(eng.handle, call.mode, ptr(call.forced_actions), ptr(call.start_positions), call.seed,
+                                            int(stop_early), C.byref(opts), C.byref(call.out), ptr(metrics_dev), stream),
                   "jn_reinforce_step")
-        finally:
-            if keys is not None:
-                eng.lib.jn_set_rollout_keys(eng.handle, None, 0)
-            if cls is not None:
-                eng.lib.jn_set_rollout_classes(eng.handle, None, 0)
         m = metrics_dev.cpu()
         S = int(m[5])
         if self.config.reward_norm:
@@ -583,8 +567,14 @@ class ReinforceTrainer:
         leaving it, the targets are merged there too; one readback per chunk.  Same keys; `map` equals the host
         path's up to fp32 storage; the `yolo_*` entries are computed as without it.  `token_positions`: see ``rollout``.
         `class_ids`: one class per image (a tensor or a sequence) behind the class token of its walk; None = class 0."""
-        per_image = self._eval_image_chunks(images, bboxes, batch_size, do_detection, merge_bboxes, device_metrics,
-                                            token_positions=token_positions, class_ids=class_ids)
+        from .ragged import image_classes, rollout_chunks
+        class_ids = image_classes(class_ids, len(images))
+        if do_detection is None:
+            do_detection = bool(getattr(self.config, "detection_enabled", False))
+        rows = [torch.as_tensor(b).reshape(-1, 4).to(torch.long) for b in bboxes]
+        chunks = rollout_chunks(self, images, rows, batch_size, do_detection=do_detection, token_positions=token_positions,
+                                class_ids=class_ids)
+        per_image = self._eval_image_chunks(chunks, do_detection, merge_bboxes, device_metrics)
         out: Dict[str, list] = {}
         for tail, ro_b in per_image:                      # compute_metrics in image order: the reward-norm window's order
             m = self.compute_metrics(ro_b)
@@ -594,91 +584,20 @@ class ReinforceTrainer:
         return out
 
     @torch.no_grad()
-    def _eval_image_chunks(self, images, bboxes, batch_size: int, do_detection: bool = None, merge_bboxes: bool = None,
-                           device_metrics: bool = False, sample_actions: bool = False, token_positions: str = None,
-                           teacher_targets=None, walks: int = 1, walk_starts=None, chunk_metrics=None,
-                           streams: str = "loop", class_ids=None) -> list:
-        """The chunked rollouts behind ``eval_on_images`` (and ``SupervisedTrainer.eval_on_images``): per image, in image
-        order, (the metrics that do not come from ``compute_metrics``, the image's own ``B = 1`` rollout).
-        teacher_targets: a callable (box rows of the chunk's images, their grid extents, the canvas grid) -> uint8
-        [n, Gh, Gw]; the rollouts then carry "teacher_sets" and "teacher_targets", and the found-ratios count these
-        cells instead of the env's bbox masks.
-
-        walks = K > 1 (``SupervisedTrainer.eval_envs_on_images``): a chunk of n images runs as n * K agents, agents
-        i * K .. i * K + K - 1 walking image i — the same stored image, one view-table row per walk with the same source
-        pointer — and the result lists one entry per WALK, in image order then walk order; `batch_size` still counts
-        images and n * K stays within the model's max_batch.  Walk (i, j) starts where rollout first + i * K + j of the
-        per-image loop would (``ragged.loop_start_positions``), or at walk_starts(first, image indices, their extents)
-        -> [n, K, 2]; the rollout counter ends at first - 1 + len(images) * K.
-        streams: "loop" — a sampled walk draws its actions from the stream of its own rollout of the per-image loop
-        (``ragged.walk_agent_keys``), so that it is that rollout's walk; "batch" — from (the chunk's seed, its place in
-        the chunk).  Greedy chunks make no such call.
-        class_ids: one class per IMAGE (``ragged.image_classes``); agent i * K + k of a chunk carries the class of its
-        image i, so the K walks of an image share its class (``ragged.walk_classes``).  None: class 0, no call.
-        chunk_metrics: a callable(chunk) called once per chunk with {"indices", "env", "rollout", "steps", "extents"
-        (per agent), "rows", "walks", "targets" (the teacher grid per agent or None)} in place of the per-image detection
-        metrics (`map`, `yolo_*`), which are then not computed."""
+    def _eval_image_chunks(self, chunks, do_detection: bool, merge_bboxes: bool = None, device_metrics: bool = False) -> list:
+        """Behind ``eval_on_images`` (and ``SupervisedTrainer.eval_on_images``, whose rollouts carry the teacher): from the
+        records of ``ragged.rollout_chunks`` with one walk per image, per image in image order (the metrics that do not
+        come from ``compute_metrics`` — the env's entries and, with detection, `map` and `yolo_*` —, the image's own
+        ``B = 1`` rollout)."""
         from .detection import (detection_targets, map_50_device, merge_boxes_device, pack_boxes, rollout_boxes_packed,
                                 split_bboxes_over_patches, unpack_boxes)
-        from .ragged import (env_metrics, found_ratios, image_env, loop_start_positions, own_steps, plan_chunks,
-                             image_classes, slice_rollout, walk_agent_keys, walk_classes)
-        class_ids = image_classes(class_ids, len(images))
-        if streams not in ("loop", "batch"):
-            raise ValueError(f"streams must be 'loop' or 'batch', got {streams!r}")
-        cfg, P = self.config, int(self.patch_size)
-        if do_detection is None:
-            do_detection = bool(getattr(cfg, "detection_enabled", False))
+        from .ragged import walk_entries
+        P = int(self.patch_size)
         if merge_bboxes is None:
-            merge_bboxes = bool(getattr(cfg, "merge_bboxes", False))
-        rows = [torch.as_tensor(b).reshape(-1, 4).to(torch.long) for b in bboxes]
-        assert len(rows) == len(images)
-        K = int(walks)
-        assert K >= 1
-        per_image = [None] * (len(images) * K)
-        first = self._rollouts + 1                        # eval_on_batch on image i alone would be rollout first + i
-        max_batch = getattr(self.model, "max_batch", None)
-        for chunk in plan_chunks(images, batch_size, P, max_batch if max_batch is None or K == 1 else int(max_batch) // K):
-            imgs_of = chunk["indices"]
-            if K == 1:
-                sel = imgs_of
-                imgs = [images[i] if images[i].dtype == torch.uint8 else images[i].float() for i in sel]
-            else:
-                # one upload per image; its K walks hand the SAME tensor to the env, so their views share one source
-                sel = [i * K + j for i in imgs_of for j in range(K)]
-                once = {i: images[i].to(self.device) if images[i].dtype == torch.uint8 else images[i].to(self.device, torch.float32)
-                        for i in imgs_of}
-                imgs = [once[a // K] for a in sel]
-            env = image_env(self, imgs, [rows[a // K] for a in sel], canvas=chunk["canvas"])
-            extents = env.grid_extents.tolist()
-            kw, tg_grid = {}, None
-            if teacher_targets is not None:
-                tg_grid = teacher_targets([rows[i] for i in imgs_of], extents[::K], (env.n_vertical_patches, env.n_horizontal_patches))
-                tg_grid = tg_grid.to(self.device)                 # uploaded once per chunk
-                if K > 1:
-                    tg_grid = tg_grid.repeat_interleave(K, 0)
-                kw = dict(teacher=True, teacher_targets=tg_grid)
-            if walk_starts is not None:
-                starts = torch.as_tensor(walk_starts(first, imgs_of, extents[::K])).reshape(len(sel), 2).to(torch.int64)
-            else:
-                starts = loop_start_positions(self, first, sel, extents)
-            if sample_actions and streams == "loop":
-                kw["agent_keys"] = walk_agent_keys(self, first, imgs_of, K)
-            if class_ids is not None:
-                kw["classes"] = walk_classes(class_ids, imgs_of, K)
-            ro = self.rollout(env, sample_actions=sample_actions, do_detection=do_detection, bbox_lists=False,
-                              start_positions=starts, token_positions=token_positions, **kw)
-            steps = own_steps(ro)
-            found = found_ratios(env, ro, steps, masks=None if tg_grid is None else tg_grid.bool())
-            if chunk_metrics is not None:
-                chunk_metrics({"indices": imgs_of, "env": env, "rollout": ro, "steps": steps, "extents": extents, "rows": rows,
-                               "walks": K, "targets": tg_grid})
-                for b, i in enumerate(sel):
-                    ro_b = slice_rollout(ro, b, steps[b])
-                    if tg_grid is not None:
-                        ro_b["teacher_targets"] = tg_grid[b:b + 1]
-                    per_image[i] = (dict(env_metrics(self, found, ro_b, b)), ro_b)
-                continue
-            assert K == 1, "several walks per image are evaluated by a chunk_metrics callable"
+            merge_bboxes = bool(getattr(self.config, "merge_bboxes", False))
+        per_image = {}
+        for chunk in chunks:
+            sel, env, ro, extents, rows = chunk["sel"], chunk["env"], chunk["rollout"], chunk["extents"], chunk["rows"]
             packed = rollout_boxes_packed(ro, P) if do_detection else None
             if do_detection and device_metrics:
                 tg = pack_boxes([detection_targets(rows[i].unsqueeze(0), *extents[b], P)[0] for b, i in enumerate(sel)], 5,
@@ -689,11 +608,7 @@ class ReinforceTrainer:
                 maps = map_50_device(pr, tg, per_image=True)
             elif do_detection:
                 full = unpack_boxes(*packed)
-            for b, i in enumerate(sel):
-                ro_b = slice_rollout(ro, b, steps[b])
-                if tg_grid is not None:
-                    ro_b["teacher_targets"] = tg_grid[b:b + 1]
-                metrics = dict(env_metrics(self, found, ro_b, b))     # what follows compute_metrics' own entries
+            for b, (i, metrics, ro_b) in enumerate(walk_entries(self, chunk)):     # metrics: what follows compute_metrics' own entries
                 per_image[i] = (metrics, ro_b)
                 if not do_detection:
                     continue
@@ -710,5 +625,4 @@ class ReinforceTrainer:
                 else:
                     metrics.update(self._detection_eval_metrics([full[b]], detection_targets(box, gh, gw, P), patches,
                                                                 patch_targets, merge_bboxes))
-        self._rollouts = first - 1 + len(images) * K      # where that loop leaves the counter
-        return per_image
+        return [per_image[i] for i in range(len(per_image))]

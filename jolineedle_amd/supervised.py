@@ -336,15 +336,18 @@ class SupervisedTrainer:
         Deviations from the reference: DESIGN.md §6."""
         if do_detection is None:
             do_detection = bool(getattr(self.config, "detection_enabled", True)) and self.yolox_model() is not None
-        return self._walk_metrics(self._eval_walks(images, bboxes, batch_size, do_detection, merge_bboxes, device_metrics,
-                                                   sample_actions=sample_actions, streams=streams, class_ids=class_ids))
+        chunks = self._eval_walks(images, bboxes, batch_size, do_detection, sample_actions=sample_actions, streams=streams,
+                                  class_ids=class_ids)
+        return self._walk_metrics(self._eval_runner()._eval_image_chunks(chunks, do_detection, merge_bboxes, device_metrics))
 
-    def _eval_walks(self, images, bboxes, batch_size, do_detection, merge_bboxes, device_metrics, **kw) -> list:
-        """The free-running walks of both evaluations: ``ReinforceTrainer._eval_image_chunks`` in sequence-position mode
-        with the teacher armed on the simple env's target cells, the model in eval mode (src/supervised.py:294)."""
+    def _eval_walks(self, images, bboxes, batch_size, do_detection, **kw):
+        """The free-running walks of both evaluations, as chunk records: ``ragged.rollout_chunks`` of the eval runner in
+        sequence-position mode with the teacher armed on the simple env's target cells; the model is in eval mode
+        (src/supervised.py:294) until the last record has been taken."""
+        from .ragged import rollout_chunks
         from .trajectory import simple_env_targets
-        runner = self._eval_runner()
         P = int(self.config.patch_size)
+        rows = [torch.as_tensor(b).reshape(-1, 4).to(torch.long) for b in bboxes]
 
         def target_grids(rows, extents, canvas):
             grid = torch.zeros((len(rows), *canvas), dtype=torch.uint8)
@@ -355,13 +358,13 @@ class SupervisedTrainer:
         was_training = self.model.training
         self.model.eval()
         try:
-            return runner._eval_image_chunks(images, bboxes, batch_size, do_detection, merge_bboxes, device_metrics,
-                                             token_positions="sequence", teacher_targets=target_grids, **kw)
+            yield from rollout_chunks(self._eval_runner(), images, rows, batch_size, do_detection=do_detection,
+                                      token_positions="sequence", teacher_targets=target_grids, **kw)
         finally:
             self.model.train(was_training)
 
     def _walk_metrics(self, per_walk: list) -> Dict[str, list]:
-        """The per-walk entries of ``eval_on_images`` from ``_eval_walks``' result; fills ``last_eval_rollouts``."""
+        """The per-walk entries of ``eval_on_images`` from the per-walk (tail, rollout) pairs; fills ``last_eval_rollouts``."""
         from .trajectory import teacher_agreement
         out: Dict[str, list] = {}
         self.last_eval_rollouts = []
@@ -442,7 +445,11 @@ class SupervisedTrainer:
                 return given[list(indices)]
             return ragged.walk_start_positions(runner, first, indices, extents, K, eval_mode)
 
-        def chunk_metrics(ch):
+        per_walk = {}
+        for ch in self._eval_walks(images, bboxes, batch_size, True, sample_actions=sample_actions, walks=K, walk_starts=starts,
+                                   streams=streams, class_ids=class_ids):
+            for a, tail, ro_b in ragged.walk_entries(runner, ch):
+                per_walk[a] = (tail, ro_b)
             ro, env, sel = ch["rollout"], ch["env"], ch["indices"]
             n, grid = len(sel), (env.n_vertical_patches, env.n_horizontal_patches)
             dev = self.device
@@ -483,10 +490,7 @@ class SupervisedTrainer:
                     m["prop_patches_found_traj" + name] = f32(int(hit[b]) / int(tot[b])) if int(tot[b]) > 0 else 0.0
                     m["map" + name] = f32(map_all[b])
                 per_image[i] = m
-
-        out = self._walk_metrics(self._eval_walks(images, bboxes, batch_size, True, False, device_metrics,
-                                                  sample_actions=sample_actions, walks=K, walk_starts=starts,
-                                                  chunk_metrics=chunk_metrics, streams=streams, class_ids=class_ids))
+        out = self._walk_metrics([per_walk[a] for a in range(len(per_walk))])
         for i in range(len(images)):
             for k, v in per_image[i].items():
                 out.setdefault(k, []).append(v)

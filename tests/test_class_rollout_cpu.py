@@ -98,7 +98,7 @@ def test_wrappers_raise_for_id_100_before_any_engine_call():
     calls = [lambda: tr.rollout(env, classes=[0, 100, 3]), lambda: tr.rollout(env, classes=torch.tensor([0, 3, -1])),
              lambda: tr.train_iteration(env, classes=[0, 100, 3]),
              lambda: tr.eval_on_images(images, boxes, 2, class_ids=[0, 100, 3]),
-             lambda: tr._eval_image_chunks(images, boxes, 2, class_ids=[0, 100, 3], walks=2),
+             lambda: list(ragged.rollout_chunks(tr, images, boxes, 2, walks=2, class_ids=[0, 100, 3])),
              lambda: ja.infer_images(tr, images, class_ids=[0, 100, 3]),
              lambda: ja.infer_images(tr, images, batch_size=2, class_ids=[0, 100, 3])]
     sup = ja.SupervisedTrainer(ja.CfgNode(patch_size=64, max_seq_len=4, stop_enabled=True, seed=1), _NoEngine())

@@ -411,11 +411,9 @@ def test_corners_mode_walks_from_the_four_corners_of_every_grid(runs):
 
 @pytest.fixture(scope="module")
 def chunk(runs):
-    """The one chunk of a K = 2 multistart run as the chunk hook sees it."""
+    """The one chunk of a K = 2 multistart run as the walker yields it."""
     tr = _trainer(runs["product"], runs["P"], runs["T"])
-    seen = {}
-    tr._eval_walks(runs["imgs"], runs["boxes"], 5, True, False, True, walks=2, chunk_metrics=seen.update)
-    return seen
+    return list(tr._eval_walks(runs["imgs"], runs["boxes"], 5, True, walks=2))[-1]
 
 
 def test_walk_cell_maps_on_the_rollouts_own_boxes(runs, chunk):

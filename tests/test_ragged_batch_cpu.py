@@ -73,6 +73,40 @@ def test_loop_start_positions_follow_the_engines_reset_draw():
         assert row == [int(r[0][0]) % gh, int(r[1][0]) % gw]
 
 
+def test_chunk_walks_lay_out_the_walks_of_two_chunks_as_the_per_image_loop_numbers_them():
+    """Three images in two chunks (batch_size 2), K = 2, seed 1, first rollout 4, classes [5, 9, 7]: per chunk the
+    agent -> image map, the classes, the keys of every (mode, streams) pair and the starts; then the final counter."""
+    class Tr:
+        seed = 1
+    P, K, first, class_ids = 64, 2, 4, [5, 9, 7]
+    images = [torch.zeros((3, h, w)) for h, w in [(100, 200), (64, 64), (130, 70)]]
+    plan = ragged.plan_chunks(images, 2, P, ragged.images_per_chunk(8, K))
+    assert [c["indices"] for c in plan] == [[0, 1], [2]]
+    assert ragged.images_per_chunk(8, K) == 4 and ragged.images_per_chunk(8, 1) == 8 and ragged.images_per_chunk(None, K) is None
+    ext = ImageViews(images, patch_size=P).grid_extents(P).tolist()
+    assert ext == [[2, 4], [1, 1], [3, 2]]
+    want = [([0, 1, 2, 3], [0, 0, 1, 1], [5, 5, 9, 9]), ([4, 5], [2, 2], [7, 7])]
+    for chunk, (sel, image_of, classes) in zip(plan, want):
+        idx = chunk["indices"]
+        e = [ext[i] for i in idx]
+        for sample, streams in ((True, "loop"), (True, "batch"), (False, "loop"), (False, "batch")):
+            got = ragged.chunk_walks(Tr, first, idx, e, K, sample, streams, class_ids)
+            assert got["sel"] == sel and got["image_of"] == image_of
+            assert got["classes"] == classes == ragged.walk_classes(class_ids, idx, K)
+            if sample and streams == "loop":
+                keys = ragged.walk_agent_keys(Tr, first, idx, K)
+                assert got["keys"].dtype == np.uint64 and np.array_equal(got["keys"], keys)
+                assert keys.tolist() == [[1 * 1000003 + first + a, 0] for a in sel]
+            else:
+                assert got["keys"] is None
+            starts = ragged.loop_start_positions(Tr, first, sel, [x for x in e for _ in range(K)])
+            assert got["starts"].dtype == torch.int64 and torch.equal(got["starts"], starts)
+        assert ragged.chunk_walks(Tr, first, idx, e, K)["classes"] is None
+        given = ragged.chunk_walks(Tr, first, idx, e, K, walk_starts=lambda f, i, x: torch.full((len(i), K, 2), 7))
+        assert given["starts"].tolist() == [[7, 7]] * len(sel)
+    assert ragged.rollouts_after(first, len(images), K) == first - 1 + 3 * 2 == 9
+
+
 def test_own_steps_and_slices_of_a_batched_rollout():
     masks = torch.tensor([[1, 1, 1, 1, 1], [1, 1, 0, 0, 0], [1, 0, 0, 0, 0]], dtype=torch.bool)
     ro = {"masks": masks, "rewards": torch.arange(12.).reshape(3, 4), "positions": torch.zeros((3, 5, 2), dtype=torch.long),

@@ -111,9 +111,8 @@ def main():
 
     # one chunk's evaluation launches under device events, as eval_envs_on_images issues them
     with Limit(lim):
-        seen = {}
         trainer._eval_runner()._rollouts = 0
-        trainer._eval_walks(images[:bs], boxes[:bs], bs, True, False, True, walks=K, chunk_metrics=seen.update)
+        seen = list(trainer._eval_walks(images[:bs], boxes[:bs], bs, True, walks=K))[-1]
         ro, env = seen["rollout"], seen["env"]
         grid = (env.n_vertical_patches, env.n_horizontal_patches)
         tokens = torch.tensor([s + 1 for s in seen["steps"]], dtype=torch.int32, device=dev)
