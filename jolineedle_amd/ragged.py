@@ -219,6 +219,73 @@ def walk_entries(trainer, chunk: Dict):
         yield a, dict(env_metrics(trainer, chunk["found"], ro_b, b)), ro_b
 
 
+@torch.no_grad()
+def eval_image_chunks(trainer, yolox, chunks, do_detection: bool, merge_bboxes: bool = False, device_metrics: bool = False) -> list:
+    """Behind ``ReinforceTrainer.eval_on_images`` and ``SupervisedTrainer.eval_on_images`` (whose rollouts carry the
+    teacher): from the records of ``rollout_chunks`` with one walk per image, per image in image order (the metrics that
+    do not come from ``compute_metrics`` — the env's entries and, with detection, `map` and the `yolo_*` of the detector
+    `yolox` —, the image's own ``B = 1`` rollout).  `trainer`: anything with ``stop_enabled``, ``patch_size``, ``device``."""
+    from .detection import (detection_targets, map_50_device, merge_boxes_device, pack_boxes, rollout_boxes_packed,
+                            split_bboxes_over_patches, unpack_boxes)
+    P = int(trainer.patch_size)
+    per_image = {}
+    for chunk in chunks:
+        sel, env, ro, extents, rows = chunk["sel"], chunk["env"], chunk["rollout"], chunk["extents"], chunk["rows"]
+        packed = rollout_boxes_packed(ro, P) if do_detection else None
+        if do_detection and device_metrics:
+            tg = pack_boxes([detection_targets(rows[i].unsqueeze(0), *extents[b], P)[0] for b, i in enumerate(sel)], 5,
+                            trainer.device)
+            pr = packed
+            if merge_bboxes:
+                pr, tg = merge_boxes_device(*pr, target=False), merge_boxes_device(*tg, target=True)
+            maps = map_50_device(pr, tg, per_image=True)
+        elif do_detection:
+            full = unpack_boxes(*packed)
+        for b, (i, metrics, ro_b) in enumerate(walk_entries(trainer, chunk)):     # metrics: what follows compute_metrics' own entries
+            per_image[i] = (metrics, ro_b)
+            if not do_detection:
+                continue
+            gh, gw = extents[b]
+            box = rows[i].unsqueeze(0)
+            # env.get_detection_batch(sample_neg=0) of the image's own env: every patch that holds a piece of a box
+            local, masks = split_bboxes_over_patches(box, gh, gw, P)
+            cells = torch.nonzero(masks.any(-1)[0].cpu())
+            patches = env.views.gather(torch.full((len(cells),), b, dtype=torch.int64), cells, P)
+            patch_targets = torch.stack([torch.nn.functional.pad(local[0, y, x], (1, 0)) for y, x in cells.tolist()]).to(trainer.device)
+            if device_metrics:
+                metrics["map"] = torch.tensor([maps[b]], dtype=torch.float32)
+                metrics.update(detector_eval_metrics(yolox, patches, patch_targets))
+            else:
+                metrics.update(detection_eval_metrics(yolox, [full[b]], detection_targets(box, gh, gw, P), patches,
+                                                      patch_targets, merge_bboxes))
+    return [per_image[i] for i in range(len(per_image))]
+
+
+def detection_eval_metrics(yolox, preds, targets, patches, patch_targets, merge_bboxes: bool) -> Dict[str, Tensor]:
+    """The detection half of ``eval_on_sample`` (src/reinforce.py:455-497), shared by ``eval_on_batch`` and
+    ``eval_image_chunks``: mAP-50 of the full-image predictions (optionally merged) and the detector's own mAP and
+    losses on the patches that hold a box."""
+    from .detection import compute_detection_metrics, merge_boxes_batched
+    if merge_bboxes:
+        preds = merge_boxes_batched(preds, target=False)
+        targets = merge_boxes_batched(targets, target=True)
+    metrics = dict(compute_detection_metrics(preds, targets))
+    metrics.update(detector_eval_metrics(yolox, patches, patch_targets))
+    return metrics
+
+
+def detector_eval_metrics(yolox, patches, patch_targets) -> Dict[str, Tensor]:
+    """The `yolo_*` entries of ``detection_eval_metrics``: the detector `yolox` alone on the patches that hold a box."""
+    from .detection import compute_detection_metrics
+    metrics = {}
+    pred_bboxes, _, yolo_losses = yolox(patches)
+    for k, v in compute_detection_metrics(pred_bboxes, list(patch_targets)).items():
+        metrics["yolo_" + k] = v
+    for k, v in yolo_losses.items():
+        metrics["yolo_" + k] = v
+    return metrics
+
+
 def walk_start_positions(trainer, first_rollout: int, indices: Sequence[int], extents: Sequence[Sequence[int]], n_walks: int,
                          eval_mode: str = "multistart") -> Tensor:
     """[n, K, 2] the starts of the K walks of every image in ``eval_envs`` (src/supervised.py:668-690), image

@@ -15,6 +15,8 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
+from .rollouts import RolloutRunner
+from .trainer import Trainer
 
 
 def reference_actions(current_actions: torch.Tensor, next_actions: torch.Tensor, masks: torch.Tensor,
@@ -33,32 +35,16 @@ def reference_actions(current_actions: torch.Tensor, next_actions: torch.Tensor,
     return ref
 
 
-class SupervisedTrainer:
+class SupervisedTrainer(Trainer):
     def __init__(self, config, model, logger=None, train_dataset=None, test_dataset=None, rank: int = 0):
-        self.config, self.model, self.rank = config, model, rank
-        self.logger, self.train_dataset, self.test_dataset = logger, train_dataset, test_dataset
-        self.device = model.device
+        Trainer.__init__(self, config, model, logger, train_dataset, test_dataset, rank)
         self.stop_weight = float(getattr(config, "stop_weight", 1.0)) if getattr(config, "stop_enabled", False) else 1.0
         self.best_metric_name = "map"
         self.best_metric_history = []
         self.last_test_metrics = None
-        self.iter_num = 0
         self._flat_grads = None
         self._device_walks = 0          # calls of the device route of generate_trajectories: its default seeds move on
-
-    def _grad_arena(self):
-        """The engine's flat fp32 gradient arena: owned by the MODEL (one per engine, shared by all trainers)."""
-        g = self.model.grad_arena()
-        self._optim_numel = self.model._optim_gpt_numel
-        return g
-
-    def init_detection(self, **kw):
-        """``Trainer.init_detection`` (src/trainer.py:176-186): on-device augmentation of the trajectory patches and the
-        detector patches (src/supervised.py:855-861, 884-885).  Off until called."""
-        from .augment import DetectionAugment
-        kw.setdefault("seed", int(getattr(self.config, "seed", 0)) + 17 * int(self.rank))
-        self.detection_augment = DetectionAugment(**kw)
-        return self.detection_augment
+        self._runner = None             # ``_eval_runner``'s, built on first use
 
     def generate_trajectories(self, batch: Dict, position: Optional[Tuple[int, int]] = None, seed: Optional[int] = None,
                               use_views: bool = True, seed_ties: bool = False, device: Optional[bool] = None) -> Dict:
@@ -158,7 +144,7 @@ class SupervisedTrainer:
         cur, nxt, masks = tr["current_actions"], tr["next_actions"], tr["masks"]
         ref_actions = reference_actions(cur, nxt, masks, getattr(cfg, "loss_mode", "best-action"))   # src/supervised.py:870-877
         detection = self.yolox_model() is not None and bool(getattr(cfg, "detection_enabled", True))
-        aug = getattr(self, "detection_augment", None)
+        aug = self.detection_augment
         if aug is not None:
             B_, T_ = cur.shape
             tr["patches"] = aug(tr["patches"].flatten(0, 1)).view(B_, T_, *tr["patches"].shape[2:])
@@ -171,34 +157,11 @@ class SupervisedTrainer:
                 res["yolo_" + k] = v
             res["loss"] = res["loss"] + yolo["total_loss"].cpu()
         if optimizer_step and self.iter_num % ga == 0:
-            from .dist import allreduce_gradients
-            eng, grads = self.model.engine(), self._grad_arena()
-            stream = _lib.current_stream(self.device)
-            scale = allreduce_gradients(grads, grads.numel() if detection else self._optim_numel, process_group)
-            lr = float(getattr(cfg, "learning_rate", 1e-4))
-            check(eng.lib.jn_optimizer_step(eng.handle, lr, 0.01, 0.0, scale, stream), "jn_optimizer_step")
-            if detection:
-                ylr = float(getattr(cfg, "yolo_lr", lr))
-                check(eng.lib.jn_optimizer_step_group(eng.handle, 1, ylr, 0.01, 0.0, scale, stream), "jn_optimizer_step_group")
-            grads.zero_()
-            self.model.refresh_flat_params()
+            self._engine_optimizer_step(0.0, detection, process_group)     # (0.0: no clipping, as in ``train_step``)
         res["trajectories"] = tr
         return res
 
     # ---- the reference's supervised loop on the autograd bridge (src/supervised.py:138-198, 812-911) -------------------
-    def yolox_model(self):
-        return getattr(self.model, "_yolox_view", None)      # None: no detector configured (with_detector = False)
-
-    def ddp_setup(self, rank: int, world_size: int, port: int, backend: str = None):
-        """``Trainer.ddp_setup`` (src/trainer.py:61-71); rendezvous on 127.0.0.1, ``backend="gloo"`` for rehearsals."""
-        import os
-        import torch.distributed as dist
-        os.environ["MASTER_ADDR"] = "127.0.0.1"
-        os.environ["MASTER_PORT"] = str(port)
-        if not dist.is_initialized():
-            dist.init_process_group(backend=backend or "nccl", rank=rank, world_size=world_size)
-            self._owns_process_group = True           # run() only tears down a group it created itself
-
     def compute_metrics(self, action_logits, actions, masks, yolo_loss: Optional[dict] = None) -> Dict[str, torch.Tensor]:
         """src/supervised.py:138-198: CrossEntropy(weight[STOP] = stop_weight, reduction none) over the non-padding tokens,
         accuracy, the detector's loss terms under ``yolo_*`` and their total added to ``loss``, ``episode_length``."""
@@ -235,7 +198,7 @@ class SupervisedTrainer:
         batch = self.generate_trajectories(batch, seed=seed)
         patches, current_actions, next_actions = batch["patches"], batch["current_actions"], batch["next_actions"]
         positions, masks, classes = batch["positions"], batch["masks"], batch["class_id"]
-        aug = getattr(self, "detection_augment", None)
+        aug = self.detection_augment
         if aug is not None:
             with torch.no_grad():
                 B_, T_ = current_actions.shape
@@ -266,48 +229,20 @@ class SupervisedTrainer:
         SURVEY.md §8): `batches` is any iterable of collated batches ({"image", "bboxes"[, "class_id"]}), re-iterated when
         exhausted.  One process per GPU; gradients are averaged by the optimisers' all-reduce (DDP semantics), BatchNorm
         statistics stay per rank.  Returns the metrics of the last iteration."""
-        import torch.distributed as dist
-        if bool(getattr(self.config, "augment_detection", False)):
-            self.init_detection()
-        self.rank = rank
-        if world_size > 1 or backend:
-            self.ddp_setup(rank, world_size, port, backend)
-        optim_gpt, optim_yolox = self.model.configure_optimizers(self.config)
-        for o in (optim_gpt, optim_yolox):
-            if o is not None:
-                o.sync_gradients = world_size > 1
-        self.optim_gpt, self.optim_yolox = optim_gpt, optim_yolox
-        batches = batches if batches is not None else getattr(self, "train_dataset", None)
-        assert batches is not None, "run() needs an iterable of collated batches"
-        n_iters = int(max_iters if max_iters is not None else getattr(self.config, "max_iters", 1))
-        it, metrics = iter(batches), None
-        for i in range(n_iters):
-            try:
-                batch = next(it)
-            except StopIteration:
-                it = iter(batches)
-                batch = next(it)
-            metrics = self.training_step(batch, optim_gpt, optim_yolox, seed=None if seed is None else seed + i)
-        if getattr(self, "_owns_process_group", False) and dist.is_available() and dist.is_initialized():
-            dist.destroy_process_group()                 # src/reinforce.py:362 / src/supervised.py:911
-            self._owns_process_group = False
-        return metrics
+        def step(i, batch, optim_gpt, optim_yolox):
+            return self.training_step(batch, optim_gpt, optim_yolox, seed=None if seed is None else seed + i)
+        return self._run_loop(step, rank, world_size, port, backend, batches, max_iters,
+                              augment=bool(getattr(self.config, "augment_detection", False)), sync_gradients=world_size > 1)
 
     # ---- evaluation: the free-running half of test() (src/supervised.py:279-405, 407-470) ------------------------------
-    def _eval_runner(self):
-        """The rollout machinery of ``ReinforceTrainer`` over this trainer's model, walking ``test_max_seq_len`` steps.
-        Kept between calls so that its rollout counter (start positions, sampling seeds) moves on like a loop's."""
-        if getattr(self, "_eval_trainer", None) is None:
-            from types import SimpleNamespace
-            from .reinforce import ReinforceTrainer
+    def _eval_runner(self) -> RolloutRunner:
+        """A ``RolloutRunner`` over this trainer's model, walking ``test_max_seq_len`` steps.  Kept between calls so that
+        its rollout counter (start positions, sampling seeds) moves on like a loop's."""
+        if self._runner is None:
             cfg = self.config
-            view = SimpleNamespace(
-                max_seq_len=int(getattr(cfg, "test_max_seq_len", None) or cfg.max_seq_len), entropy_weight=0.0,
-                stop_enabled=bool(getattr(cfg, "stop_enabled", False)), reward_norm=False, seed=int(getattr(cfg, "seed", 0)),
-                patch_size=int(cfg.patch_size), detection_enabled=bool(getattr(cfg, "detection_enabled", True)),
-                merge_bboxes=bool(getattr(cfg, "merge_bboxes", False)))
-            self._eval_trainer = ReinforceTrainer(view, self.model, rank=self.rank)
-        return self._eval_trainer
+            self._runner = RolloutRunner(self.model, int(getattr(cfg, "test_max_seq_len", None) or cfg.max_seq_len),
+                                         bool(getattr(cfg, "stop_enabled", False)), int(getattr(cfg, "seed", 0)), self.rank)
+        return self._runner
 
     @torch.no_grad()
     def eval_on_images(self, images, bboxes, batch_size: int, sample_actions: bool = False, do_detection: bool = None,
@@ -334,11 +269,15 @@ class SupervisedTrainer:
         of ``embed_class``, as ``test_model_on_env`` feeds ``classes=sample["class_id"]`` at every step
         (src/supervised.py:284, 317-331); None = class 0 for every walk.
         Deviations from the reference: DESIGN.md §6."""
+        from .ragged import eval_image_chunks
         if do_detection is None:
             do_detection = bool(getattr(self.config, "detection_enabled", True)) and self.yolox_model() is not None
+        if merge_bboxes is None:
+            merge_bboxes = bool(getattr(self.config, "merge_bboxes", False))
         chunks = self._eval_walks(images, bboxes, batch_size, do_detection, sample_actions=sample_actions, streams=streams,
                                   class_ids=class_ids)
-        return self._walk_metrics(self._eval_runner()._eval_image_chunks(chunks, do_detection, merge_bboxes, device_metrics))
+        return self._walk_metrics(eval_image_chunks(self._eval_runner(), self.yolox_model() if do_detection else None, chunks,
+                                                    do_detection, merge_bboxes, device_metrics))
 
     def _eval_walks(self, images, bboxes, batch_size, do_detection, **kw):
         """The free-running walks of both evaluations, as chunk records: ``ragged.rollout_chunks`` of the eval runner in
@@ -355,13 +294,9 @@ class SupervisedTrainer:
                 grid[b, :gh, :gw] = simple_env_targets(r, gh * P, gw * P, P)
             return grid
 
-        was_training = self.model.training
-        self.model.eval()
-        try:
+        with self._eval_mode():
             yield from rollout_chunks(self._eval_runner(), images, rows, batch_size, do_detection=do_detection,
                                       token_positions="sequence", teacher_targets=target_grids, **kw)
-        finally:
-            self.model.train(was_training)
 
     def _walk_metrics(self, per_walk: list) -> Dict[str, list]:
         """The per-walk entries of ``eval_on_images`` from the per-walk (tail, rollout) pairs; fills ``last_eval_rollouts``."""
@@ -543,6 +478,15 @@ class SupervisedTrainer:
         tgts = [p[(p[:, -1] == 1) if p.shape[-1] >= 6 else (p != 0).any(dim=-1)][:, :5] for p in t]
         return {"map": torch.tensor([detection.map_50(flat, tgts)], dtype=torch.float32, device=targets.device)}
 
+    def _device_batch(self, patches, current_actions, next_actions, positions, masks, classes):
+        """The tensors of a teacher-forced batch as ``jn_supervised_step`` / ``jn_supervised_eval`` read them: on the
+        device, contiguous, patches f32, actions / positions / classes int64, masks uint8; None stays None."""
+        f = lambda t, dt: None if t is None else torch.as_tensor(t).to(self.device, dt).contiguous()
+        cls = f(classes, torch.int64)
+        assert cls is None or cls.shape == (current_actions.shape[0],), "classes must be [B]"
+        return (f(patches, torch.float32), f(current_actions, torch.int64), f(next_actions, torch.int64),
+                f(positions, torch.int64), f(masks, torch.uint8), cls)
+
     def eval_step(self, patches, current_actions, next_actions, positions, masks, classes=None, loss_mode: Optional[str] = None,
                   want_logits: bool = True) -> Dict[str, torch.Tensor]:
         """The validation twin of ``train_step`` (``jn_supervised_eval``): eval-mode ``model(patches, current_actions,
@@ -558,13 +502,7 @@ class SupervisedTrainer:
         if loss_mode is None:
             loss_mode = getattr(self.config, "loss_mode", "best-action")
         B, T = current_actions.shape
-        f = lambda t, dt: t.to(dev, dt).contiguous()
-        patches = None if patches is None else f(patches, torch.float32)
-        cur, nxt = f(current_actions, torch.int64), f(next_actions, torch.int64)
-        pos = None if positions is None else f(positions, torch.int64)
-        msk = f(masks, torch.uint8)
-        cls = None if classes is None else f(torch.as_tensor(classes), torch.int64)
-        assert cls is None or cls.shape == (B,), "classes must be [B]"
+        patches, cur, nxt, pos, msk, cls = self._device_batch(patches, current_actions, next_actions, positions, masks, classes)
         out = {"metrics": torch.zeros(4, device=dev, dtype=torch.float32),
                "token_loss": torch.empty((B, T), device=dev, dtype=torch.float32),
                "predicted": torch.empty((B, T), device=dev, dtype=torch.uint8),
@@ -589,15 +527,13 @@ class SupervisedTrainer:
         per batch, ``token_loss`` f32, ``predicted`` and ``labels`` int64 [B, T] on the host and the batch's
         ``trajectories`` (device tensors).  `seed` makes the walks reproducible (batch i uses seed + its first image)."""
         from .yolox import LOSS_NAMES
-        cfg, model, dev = self.config, self.model, self.device
+        cfg, dev = self.config, self.device
         n_images = len(images)
         detection = self.yolox_model() is not None and bool(getattr(cfg, "detection_enabled", True))
         loss_mode = getattr(cfg, "loss_mode", "best-action")
         out: Dict[str, list] = {}
         self.last_eval_supervised = []
-        was_training = model.training
-        model.eval()
-        try:
+        with self._eval_mode():
             for first in range(0, n_images, int(batch_size)):
                 sel = range(first, min(n_images, first + int(batch_size)))
                 batch = {"image": [images[i] for i in sel] if not isinstance(images, torch.Tensor) else images[first:sel.stop],
@@ -634,8 +570,6 @@ class SupervisedTrainer:
                     row["map"] = y[len(LOSS_NAMES)]
                 for k, v in row.items():
                     out.setdefault(k, []).append(float(v))
-        finally:
-            model.train(was_training)
         return out
 
     def test_on_images(self, images, bboxes, batch_size: int, class_ids=None, sample_actions: bool = False,
@@ -661,14 +595,9 @@ class SupervisedTrainer:
         model, dev = self.model, self.device
         model.sync_weights()
         eng = model.engine()
-        grads = self._grad_arena()
+        self._grad_arena()                      # bound to the engine before its backward writes it
         B, T = current_actions.shape
-        f = lambda t, dt: t.to(dev, dt).contiguous()
-        patches, cur, nxt = f(patches, torch.float32), f(current_actions, torch.int64), f(next_actions, torch.int64)
-        pos = None if positions is None else f(positions, torch.int64)
-        msk = f(masks, torch.uint8)
-        cls = None if classes is None else f(torch.as_tensor(classes), torch.int64)
-        assert cls is None or cls.shape == (B,), "classes must be [B]"
+        patches, cur, nxt, pos, msk, cls = self._device_batch(patches, current_actions, next_actions, positions, masks, classes)
         logits = torch.empty((B, T, eng.cfg.n_actions), device=dev, dtype=torch.float32)
         metrics = torch.zeros(4, device=dev, dtype=torch.float32)
         stream = _lib.current_stream(dev)
@@ -677,13 +606,9 @@ class SupervisedTrainer:
         self.iter_num += 1
         ga = int(getattr(self.config, "gradient_accumulation", 1))
         if optimizer_step and self.iter_num % ga == 0:
-            from .dist import allreduce_gradients
-            scale = allreduce_gradients(grads, self._optim_numel, process_group)
-            lr = float(getattr(self.config, "learning_rate", 1e-4))
-            object.__setattr__(model, "_last_lr", (lr, float(getattr(self.config, "yolo_lr", lr))))     # save_checkpoint's default
-            # the supervised loop does not clip gradients (src/supervised.py:897-902)
-            check(eng.lib.jn_optimizer_step(eng.handle, lr, 0.01, 0.0, scale, stream), "jn_optimizer_step")
-            grads.zero_()
-            self.model.refresh_flat_params()
+            object.__setattr__(model, "_last_lr", self._learning_rates())
+            # the supervised loop does not clip gradients (src/supervised.py:897-902); the detector's group steps in
+            # ``train_iteration``, after its own backward
+            self._engine_optimizer_step(0.0, False, process_group)
         m = metrics.cpu()
         return {"loss": m[0], "action_loss": m[0], "action_accuracy": m[1], "episode_length": m[2], "logits": logits}

@@ -102,7 +102,6 @@ def test_wrappers_raise_for_id_100_before_any_engine_call():
              lambda: ja.infer_images(tr, images, class_ids=[0, 100, 3]),
              lambda: ja.infer_images(tr, images, batch_size=2, class_ids=[0, 100, 3])]
     sup = ja.SupervisedTrainer(ja.CfgNode(patch_size=64, max_seq_len=4, stop_enabled=True, seed=1), _NoEngine())
-    sup._eval_trainer = tr
     calls += [lambda: sup.eval_on_images(images, boxes, 2, do_detection=False, class_ids=[0, 100, 3])]
     for f in calls:
         with pytest.raises(AssertionError, match="class id outside embed_class"):
