@@ -493,6 +493,25 @@ int jn_supervised_forward(jn_ctx* ctx, const float* patches_dev, const int64_t* 
                           const int64_t* classes_dev, const int64_t* positions_dev, int B, int T, float* logits_out_dev,
                           float* final_emb_out_dev, void* stream);
 int jn_supervised_backward(jn_ctx* ctx, const float* dlogits_dev, void* stream);
+/* Which backward differentiates the decision transformer over a sequence of T glimpse steps (T + 1 tokens): host only, no
+ * device call.  decision_route: jn_debug_decision_route of the context (0 per agent, 1 wide).  Returns 0 = none (every
+ * training entry point refuses that length with JN_EINVAL), 1 = the batched backward with a head's attention tiles in LDS
+ * (4 (T + 1) head_size + 2 (T + 1)^2 <= 16384 floats), 2 = the one-workgroup-per-agent kernel (per-agent route, T <= 62),
+ * 3 = the batched backward with the tiled attention kernels (per-agent route, head_size <= 256, T <= 255).  The rule takes
+ * the first of 1, (wide: 0), 2, 3 that admits the shape; the test hook JN_GPT_BWD_TILED=1 sends a per-agent-route shape of 1
+ * or 2 to 3.  JN_EINVAL: decision_route not 0 or 1. */
+int jn_gpt_backward_route(int C, int n_head, int T, int decision_route);
+/* Debug entry, context-free: ONE layer's causal attention of the batched GPT backward on caller tensors — the recompute
+ * (probabilities into ATT_dev [B * n_head][Lm][Lm], Y_dev [B][Lm][C] = drop(P) . V), then its backward dQKV_dev [B][Lm][3 C]
+ * from dY_dev [B][Lm][C] — enqueued on `stream` (no wait).  QKV_dev [B][Lm][3 C] holds q, k, v of token (b, i) side by side,
+ * head h in columns h * head_size ...; L <= Lm is the number of live tokens (stop-early): rows >= L of ATT, Y and dQKV are
+ * left as they are.  Attention dropout pdrop with the key (seed, b, i, layer, 1, h * Tmax + j), Tmax >= Lm.  form 0 = the
+ * LDS kernels, 1 = the tiled kernels (Lm <= 256, head_size <= 256).  The call keeps a workspace per device between calls
+ * (the tiled form's dS, of ATT's shape), so calls on one device are for one stream at a time.  JN_EINVAL: a null pointer,
+ * a size out of range, or a form that does not take the shape. */
+int jn_gpt_attention_backward(int form, const float* QKV_dev, const float* dY_dev, int B, int n_head, int C, int Lm, int L,
+                              float pdrop, uint64_t seed, int layer, int Tmax, float* ATT_dev, float* Y_dev, float* dQKV_dev,
+                              void* stream);
 /* The eval-mode twin of jn_supervised_step — one batch of SupervisedTrainer.eval_supervised (src/supervised.py:431-472,
  * under model.eval() and no_grad): GPT.forward on the teacher's sequences with BatchNorm running statistics and no
  * dropout, then jn_supervised_metrics on the logits.  Same tensors as jn_supervised_step; on_self_trajectory selects the

@@ -138,6 +138,9 @@ SIGNATURES = {
     "jn_supervised_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "jn_supervised_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "jn_gpt_backward_route": (C.c_int, [C.c_int] * 4),
+    "jn_gpt_attention_backward": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_uint64, C.c_int, C.c_int] +
+                                           [C.c_void_p] * 4),
     "jn_optimizer_step": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "jn_arena_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "jn_set_grad_arena": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),

@@ -2,6 +2,7 @@
 // Host code only (compiled by hipcc as C++); kernels live in kernels_*.hip.
 #include <algorithm>
 #include <cmath>
+#include <mutex>
 
 #include "jn_internal.h"
 
@@ -99,15 +100,20 @@ static int build_grad_layer_table(jn_ctx* ctx) {
   return JN_OK;
 }
 
-// GPT backward over a trajectory: scratch (sized for either kernel) + launch.  The batched kernels are the default; the
-// one-workgroup-per-agent kernel takes the shapes the batched one refuses.
+// GPT backward over a trajectory: scratch + launch, a switch over gpt_backward_route (jn_kernels.h).  The scratch counts the
+// per-agent kernel's term only where that kernel can run (T <= GPT_PER_AGENT_MAX_T on the per-agent route: the term grows
+// with max_batch * T^2 and would dwarf the rest at long T), and the tiled form's DS buffer where that form runs.
 static int launch_gpt_bwd(jn_ctx* ctx, GptBwdArgs& ba, hipStream_t s) {
   const jn_config& c = ctx->cfg;
   const int L = ba.T + 1, nL = c.n_layer, nh = c.n_head, C = c.n_embd;
+  const GptBwdRoute route = gpt_backward_route(C, nh, ba.T, ctx->decision_route);
+  JN_CHECK(route != GPT_BWD_NONE, JN_EINVAL, "no GPT backward takes n_embd %d, head size %d, T %d%s", C, C / nh, ba.T,
+           ctx->decision_route ? " (a wide model has the LDS form alone)" : "");
   const long long per_agent = (long long)(nL + 1) * L * C + (long long)nL * (11LL * L * C + (long long)nh * L * L) +
                               12LL * L * C + (long long)nh * L * L + 4LL * C + 64;
-  const size_t need = std::max((size_t)per_agent * c.max_batch,
-                               gpt_backward_batched_scratch(C, nh, nL, c.n_actions, c.max_batch, ba.T));
+  const bool per_agent_possible = ctx->decision_route == 0 && ba.T <= GPT_PER_AGENT_MAX_T && C <= GPT_PER_AGENT_MAX_C;
+  const size_t need = std::max(per_agent_possible ? (size_t)per_agent * c.max_batch : (size_t)0,
+                               gpt_backward_batched_scratch(C, nh, nL, c.n_actions, c.max_batch, ba.T, route == GPT_BWD_TILED));
   if (!ctx->gpt_bwd_scratch || ctx->gpt_bwd_scratch_floats < need) {
     int rc = dev_alloc(ctx, &ctx->gpt_bwd_scratch, need);
     if (rc) return rc;
@@ -122,10 +128,18 @@ static int launch_gpt_bwd(jn_ctx* ctx, GptBwdArgs& ba, hipStream_t s) {
                         grad_of(ctx, y.proj_wt), grad_of(ctx, y.proj_b), grad_of(ctx, y.ln2_w), grad_of(ctx, y.ln2_b),
                         grad_of(ctx, y.fc_wt), grad_of(ctx, y.fc_b), grad_of(ctx, y.fc2_wt), grad_of(ctx, y.fc2_b)};
   }
-  if (launch_gpt_backward_batched(ba, W.data(), G.data(), s) == 0) return JN_OK;
-  JN_CHECK(ctx->decision_route == 0, JN_EINVAL, "the batched GPT backward refuses n_embd %d, T %d, and a wide model has no other", C, ba.T);
-  launch_gpt_backward(ba, s);
-  return JN_OK;
+  switch (route) {
+    case GPT_BWD_LDS:
+    case GPT_BWD_TILED:
+      JN_CHECK(launch_gpt_backward_batched(ba, W.data(), G.data(), s, route == GPT_BWD_TILED) == 0, JN_ESTATE,
+               "the batched GPT backward refused the shape its route admitted (n_embd %d, T %d)", C, ba.T);
+      return JN_OK;
+    case GPT_BWD_PER_AGENT:
+      launch_gpt_backward(ba, s);
+      return JN_OK;
+    default:
+      return JN_EINVAL;
+  }
 }
 
 // The GptBwdArgs fields that the REINFORCE and the supervised backward share: shapes, flags, weights and their
@@ -205,11 +219,14 @@ static int check_train_outputs(const jn_rollout_out* out) {
 static int check_can_train(const jn_ctx* ctx, int T) {
   const jn_config& c = ctx->cfg;
   JN_CHECK(!c.no_patch_emb, JN_ESTATE, "training without a patch encoder is not supported");
-  JN_CHECK(c.block_size <= 62, JN_EINVAL, "training supports block_size <= 62");
-  // a wide context has no backward but the batched one (gpt_backward_kernel's envelope ends at n_embd 256)
+  // a wide context has no backward but the batched one in its LDS form (gpt_backward_kernel's envelope ends at n_embd 256,
+  // and the tiled form is not offered to wide models yet)
   JN_CHECK(ctx->decision_route == 0 || T < 1 || gpt_backward_batched_admits(c.n_embd, c.n_head, T), JN_EINVAL,
            "training a wide model (n_embd %d, head size %d) at T = %d: the batched backward needs n_embd <= %d and "
            "4 (T + 1) head_size + 2 (T + 1)^2 <= 16384", c.n_embd, c.n_embd / c.n_head, T, GPT_WIDE_MAX_C);
+  // the length at hand must have a backward (gpt_backward_route: LDS, per agent up to T = 62, tiled up to T = 255)
+  JN_CHECK(T < 1 || gpt_backward_route(c.n_embd, c.n_head, T, ctx->decision_route) != GPT_BWD_NONE, JN_EINVAL,
+           "no GPT backward takes n_embd %d, head size %d, T = %d", c.n_embd, c.n_embd / c.n_head, T);
   // batch-statistics BatchNorm on bf16-rounded pre-activations is ill-conditioned (the measurement behind
   // that statement: profiles/r03_bf16_train_probe.txt)
   JN_CHECK(ctx->cfg.act_dtype == JN_F32, JN_ESTATE, "training needs act_dtype = fp32 (bf16 is the inference mode)");
@@ -558,6 +575,48 @@ int jn_supervised_eval(jn_ctx* ctx, const float* patches_dev, const int64_t* cur
     return rc;
   launch_supervised_metrics(logits, current_actions_dev, next_actions_dev, masks_dev, B, T, nA, stop_weight,
                             on_self_trajectory ? 1 : 0, token_loss_out_dev, predicted_out_dev, metrics_dev, s);
+  JN_HIP(hipGetLastError());
+  return JN_OK;
+}
+
+// ---- the GPT backward's route and its attention kernels alone (context-free) -------------------------------------------
+int jn_gpt_backward_route(int C, int n_head, int T, int decision_route) {
+  JN_CHECK(decision_route == 0 || decision_route == 1, JN_EINVAL, "jn_gpt_backward_route: decision_route=%d", decision_route);
+  return (int)gpt_backward_route(C, n_head, T, decision_route);
+}
+
+int jn_gpt_attention_backward(int form, const float* QKV_dev, const float* dY_dev, int B, int n_head, int C, int Lm, int L, float pdrop,
+                              uint64_t seed, int layer, int Tmax, float* ATT_dev, float* Y_dev, float* dQKV_dev, void* stream) {
+  JN_CHECK(QKV_dev && dY_dev && ATT_dev && Y_dev && dQKV_dev, JN_EINVAL, "jn_gpt_attention_backward: null argument");
+  JN_CHECK((form == 0 || form == 1) && B >= 1 && B <= 65535 && n_head >= 1 && C >= 1 && C % n_head == 0 && Lm >= 1 && Lm <= 4096 &&
+               L >= 1 && L <= Lm && Tmax >= Lm && layer >= 0 && pdrop >= 0.0f && pdrop < 1.0f &&
+               (long long)B * n_head <= 0x7fffffffLL / ((long long)3 * C * Lm),
+           JN_EINVAL, "jn_gpt_attention_backward: form %d, B %d, n_head %d, C %d, Lm %d, L %d, Tmax %d, layer %d, pdrop %g", form, B,
+           n_head, C, Lm, L, Tmax, layer, (double)pdrop);
+  hipStream_t s = (hipStream_t)stream;
+  // Workspace: the device copy of L, then (tiled form) DS, one buffer of ATT's shape.  It is kept from call to call, one per
+  // device, and grows when a call needs more (which waits for the device), so that a timed call is launches alone; calls
+  // on one device are therefore for one stream at a time.
+  static std::mutex mu;
+  static float* ws_of[64];
+  static size_t ws_floats_of[64];
+  int dev = 0;
+  JN_HIP(hipGetDevice(&dev));
+  JN_CHECK(dev >= 0 && dev < 64, JN_EINVAL, "jn_gpt_attention_backward: device %d", dev);
+  const size_t ws_floats = 16 + (form == 1 ? (size_t)B * n_head * Lm * Lm : 0);
+  std::lock_guard<std::mutex> lock(mu);
+  if (ws_floats_of[dev] < ws_floats) {
+    if (ws_of[dev]) JN_HIP(hipFree(ws_of[dev]));
+    ws_of[dev] = nullptr; ws_floats_of[dev] = 0;
+    JN_HIP(hipMalloc((void**)&ws_of[dev], ws_floats * sizeof(float)));
+    ws_floats_of[dev] = ws_floats;
+  }
+  float* ws = ws_of[dev];
+  JN_HIP(hipMemsetD32Async((hipDeviceptr_t)ws, L, 1, s));
+  JN_CHECK(launch_gpt_attention(form, QKV_dev, dY_dev, B, n_head, C, Lm, reinterpret_cast<const int*>(ws), pdrop, seed, layer, Tmax,
+                                ATT_dev, Y_dev, ws + 16, dQKV_dev, s) == 0,
+           JN_EINVAL, "jn_gpt_attention_backward: the %s form does not take head size %d at Lm = %d", form ? "tiled" : "LDS",
+           C / n_head, Lm);
   JN_HIP(hipGetLastError());
   return JN_OK;
 }

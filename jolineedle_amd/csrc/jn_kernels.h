@@ -555,9 +555,25 @@ struct GptBwdArgs {
 int launch_gpt_backward(const GptBwdArgs& a, hipStream_t s);
 // the same backward batched over the agents (kernels_gptbwd.hip): W / G are HOST arrays of the per-layer weight and
 // gradient pointers; returns 1 when the shape is outside what it takes (caller falls back to launch_gpt_backward)
-size_t gpt_backward_batched_scratch(int C, int n_head, int n_layer, int nA, int B, int T);
-bool gpt_backward_batched_admits(int C, int n_head, int T);   // pure: the shapes launch_gpt_backward_batched takes
-int launch_gpt_backward_batched(const GptBwdArgs& a, const GptLayerPtrs* W, const GptLayerPtrs* G, hipStream_t s);
+// (tiled: with the attention in its tiled form, below; the scratch then holds one more buffer of a layer's ATT shape)
+size_t gpt_backward_batched_scratch(int C, int n_head, int n_layer, int nA, int B, int T, bool tiled = false);
+bool gpt_backward_batched_admits(int C, int n_head, int T);   // pure: the shapes the LDS form of the attention kernels takes
+int launch_gpt_backward_batched(const GptBwdArgs& a, const GptLayerPtrs* W, const GptLayerPtrs* G, hipStream_t s, bool tiled = false);
+// Which backward differentiates the decision transformer is decided once, by gpt_backward_route, a pure function of the shape
+// and the context's decision route (and of the test hook JN_GPT_BWD_TILED, read per call); launch_gpt_bwd (api_train.hip) is
+// a switch over it and check_can_train refuses NONE.  In order:
+//   LDS        where gpt_backward_batched_admits says yes: the batched backward, attention tiles of a head in 64 KB of LDS;
+//   NONE       on the wide route (decision_route 1): a wide context has no other backward;
+//   PER_AGENT  T <= GPT_PER_AGENT_MAX_T: gpt_backward_kernel, one workgroup per agent, never launched above that length;
+//   TILED      head size <= 256, T <= 255: the batched backward with the attention kernels whose LDS does not grow with T;
+//   NONE       otherwise.
+// The hook sends a decision_route 0 shape that would take LDS or PER_AGENT to TILED.
+enum GptBwdRoute { GPT_BWD_NONE = 0, GPT_BWD_LDS = 1, GPT_BWD_PER_AGENT = 2, GPT_BWD_TILED = 3 };
+constexpr int GPT_PER_AGENT_MAX_T = 62;     // gpt_backward_kernel keeps the LayerNorm statistics of T + 1 <= 64 rows
+GptBwdRoute gpt_backward_route(int C, int n_head, int T, int decision_route);
+// one layer's attention recompute + backward on caller tensors (form 0: LDS, 1: tiled with DS of ATT's shape); 1: refused
+int launch_gpt_attention(int form, const float* QKV, const float* dY, int B, int nh, int C, int Lm, const int* Lp, float pdrop,
+                         uint64_t seed, int layer, int Tmax, float* ATT, float* Y, float* DS, float* dQKV, hipStream_t s);
 int launch_ce_loss(const float* logits, const int64_t* target, const uint8_t* masks, float stop_weight, float* dlogits,
                    float* metrics, int n, int nA, int T, hipStream_t s);
 // validation: loss / accuracy / episode length / valid tokens of logits [B][T][nA] against labels formed in the kernel

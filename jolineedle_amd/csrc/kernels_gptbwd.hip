@@ -12,10 +12,14 @@
 // every later kernel treats token rows >= L as absent (zero operands, zero results), so launches do not depend on it.
 // The workload is a few GFLOP of GEMMs with M of a few hundred rows — launch- and latency-bound, not a roofline item;
 // FMA tiles keep fp32 exactness and are far from being the limit.
+// The attention of a head comes in two forms: q, k, v, dY and two Lm x Lm score tiles in LDS (gptb_attn_fwd_kernel,
+// gptb_attn_bwd_kernel: 4 Lm hs + 2 Lm^2 <= 16384 floats), or tiled over 16 query / key rows with LDS that does not grow
+// with Lm (the gptb_attn_*_tiled / _rows / _keys kernels: Lm <= 256, head size <= 256).  gpt_backward_route picks.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 
 #include "jn_gpt_device.h"
 #include "jn_kernels.h"
@@ -612,6 +616,233 @@ __global__ __launch_bounds__(GT) void gptb_attn_bwd_kernel(const float* __restri
   }
 }
 
+// ---- the tiled form of the two kernels above: LDS that does not grow with Lm (any Lm <= 256, head size <= 256) -------------
+// A workgroup owns TR query rows of one (agent, head) for the recompute, dP, the softmax backward and dQ, or TR key rows for
+// dK and dV.  The probabilities stay in ATT; dS goes through DS, a global buffer of ATT's shape (row i written for j <= i
+// only).  In LDS: the TR q (or dY) rows, a 64-key x 32-column staging tile of K (or V), and the TR x jmax score tile held
+// key-major, so that the products over keys read it as a broadcast.  Every output element has one writer and a fixed
+// summation order: equal inputs give equal bytes, as in the LDS form.
+// Precision: the score products (q . k, dY . v: sums of head-size terms) accumulate in fp64 and a row's softmax and softmax
+// backward run in fp64 on that tile, so P and dS carry one fp32 rounding each; the products over keys and rows (Y, dQ, dK,
+// dV) are fp32 chains in the LDS form's order.  The fp64 tile Pd is followed by its fp32 image Pf, which takes the place of
+// the q rows and the staging tile once the score product is done.
+constexpr int TR = 16;            // rows per workgroup: GT / 64 waves x 4 rows in the score product, GT / TR lanes per softmax row
+constexpr int TRP = TR + 1;       // leading dimension of the key-major tile (odd: the softmax's column walks spread over banks)
+constexpr int TKJ = 64, TKD = 32; // staging tile of the score product: keys x head columns (leading dimension TKD + 1)
+constexpr int T_MAX_LM = 256, T_MAX_HS = 256;
+static_assert(TR == 4 * (GT / 64) && GT % TR == 0 && GT / TR == 16, "the thread maps below");
+
+// floats in front of the fp64 tile: the q rows + staging tile, later the fp32 tile Pf (an even count: Pd is 8-byte aligned)
+__host__ __device__ inline int tiled_front_floats(int Lm, int hs) {
+  const int a = TR * hs + TKJ * (TKD + 1), b = Lm * TRP;
+  return ((a > b ? a : b) + 1) & ~1;
+}
+size_t tiled_row_lds(int Lm, int hs) { return (size_t)tiled_front_floats(Lm, hs) * sizeof(float) + (size_t)Lm * TRP * sizeof(double); }
+size_t tiled_key_lds(int Lm) { return (size_t)2 * Lm * TRP * sizeof(float); }
+static_assert(((size_t)TR * T_MAX_HS + TKJ * (TKD + 1)) * sizeof(float) + (size_t)T_MAX_LM * TRP * sizeof(double) <= 64 * 1024 &&
+              TR * T_MAX_HS + TKJ * (TKD + 1) >= T_MAX_LM * TRP &&
+              (size_t)2 * T_MAX_LM * TRP * sizeof(float) <= 64 * 1024, "the tiled form stays inside the LDS that needs no grant");
+
+// Pd[j][r] = sum_d Xs[r][d] * Z[j][d] for the keys j < jmax and the TR rows of Xs (LDS, [TR][hs]); Z: global rows ldz apart.
+// Wave w owns rows 4 w .. 4 w + 3, a lane one key of the 64 staged: the Xs reads are broadcasts, the tile reads stride
+// TKD + 1.  The products are exact in fp64 and summed there, first column to last.  Ends unsynchronised.
+__device__ __forceinline__ void tiled_scores(const float* __restrict__ Xs, const float* __restrict__ Z, long long ldz, int hs,
+                                             int jmax, float* __restrict__ Zs, double* __restrict__ Pd) {
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  for (int j0 = 0; j0 < jmax; j0 += TKJ) {
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int d0 = 0; d0 < hs; d0 += TKD) {
+      __syncthreads();
+      for (int e = tid; e < TKJ * TKD; e += GT) {
+        const int jj = e / TKD, dd = e - jj * TKD, j = j0 + jj, d = d0 + dd;
+        Zs[jj * (TKD + 1) + dd] = (j < jmax && d < hs) ? Z[(long long)j * ldz + d] : 0.0f;
+      }
+      __syncthreads();
+      const int dn = min(TKD, hs - d0);
+      const float* x = Xs + (4 * w) * hs + d0;
+      for (int dd = 0; dd < dn; ++dd) {
+        const double z = (double)Zs[lane * (TKD + 1) + dd];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] = fma((double)x[r * hs + dd], z, acc[r]);
+      }
+    }
+    if (j0 + lane < jmax) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Pd[(j0 + lane) * TRP + 4 * w + r] = acc[r];
+    }
+  }
+}
+
+// How the threads share a [TR][hs] output: G = GT / hs groups of hs threads (thread = one head column d), group g owns the rows
+// g, g + G, ... (rpt of them at the most); threads past G * hs idle.
+struct TiledCols { int g, d, G, rpt; bool on; };
+__device__ __forceinline__ TiledCols tiled_cols(int hs) {
+  TiledCols t;
+  t.G = min(GT / hs, TR); t.g = threadIdx.x / hs; t.d = threadIdx.x - t.g * hs; t.on = t.g < t.G;
+  t.rpt = (TR + t.G - 1) / t.G;
+  return t;
+}
+
+// acc[r] += sum_{n < N} Wt[n][g + r G] * Z[n][d]: Wt the key-major LDS tile ([N][TRP]), Z global rows ldz apart (the lanes of
+// a group read one row side by side).  One chain over n, first to last, as the LDS form sums.
+__device__ __forceinline__ void tiled_accumulate(const float* __restrict__ Wt, const float* __restrict__ Z, long long ldz, int N,
+                                                 const TiledCols& t, float (&acc)[TR]) {
+#pragma unroll 4
+  for (int n = 0; n < N; ++n) {
+    const float z = Z[(long long)n * ldz + t.d];
+    const float* wr = Wt + n * TRP + t.g;
+#pragma unroll
+    for (int r = 0; r < TR; ++r) {
+      if (r >= t.rpt) break;
+      acc[r] = fmaf(wr[min(r * t.G, TR - 1 - t.g)], z, acc[r]);       // (rows past TR: clamped read, never stored)
+    }
+  }
+}
+
+// grid (B * nh, ceil(Lm / TR)): probabilities of the query rows [i0, i0 + TR) into ATT, Y = drop(P) . V of those rows
+__global__ __launch_bounds__(GT) void gptb_attn_fwd_tiled_kernel(const float* __restrict__ QKV, float* __restrict__ ATT,
+                                                                 float* __restrict__ Y, int C, int nh, int Lm,
+                                                                 const int* __restrict__ Lp, float pdrop, uint64_t seed,
+                                                                 int layer, int Tmax) {
+  extern __shared__ float sm[];
+  const int b = blockIdx.x / nh, h = blockIdx.x % nh, hs = C / nh, tid = threadIdx.x, L = *Lp, i0 = blockIdx.y * TR;
+  if (i0 >= L) return;
+  const int i1 = min(i0 + TR, L), jmax = i1;
+  float* Xs = sm; float* Zs = Xs + TR * hs; float* Pf = sm;          // Pf: after the score product
+  double* Pd = reinterpret_cast<double*>(sm + tiled_front_floats(Lm, hs));
+  const float* base = QKV + (long long)b * Lm * 3 * C + h * hs;
+  for (int e = tid; e < TR * hs; e += GT) {
+    const int r = e / hs, d = e - r * hs;
+    Xs[e] = (i0 + r < i1) ? base[(long long)(i0 + r) * 3 * C + d] : 0.0f;
+  }
+  tiled_scores(Xs, base + C, 3LL * C, hs, jmax, Zs, Pd);
+  __syncthreads();
+  // softmax of row i0 + r by 16 neighbouring lanes; the undropped row goes to ATT (zeros right of the diagonal up to L)
+  {
+    const int r = tid / (GT / TR), part = tid % (GT / TR), i = i0 + r;
+    const bool live = i < i1;
+    const double scale = 1.0 / sqrt((double)hs);
+    double m = -INFINITY;
+    if (live) for (int j = part; j <= i; j += GT / TR) { const double v = Pd[j * TRP + r] * scale; Pd[j * TRP + r] = v; m = fmax(m, v); }
+    for (int o = GT / TR / 2; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+    double sum = 0.0;
+    if (live) for (int j = part; j <= i; j += GT / TR) { const double v = exp(Pd[j * TRP + r] - m); Pd[j * TRP + r] = v; sum += v; }
+    for (int o = GT / TR / 2; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    float* att = ATT + ((long long)blockIdx.x * Lm + i) * Lm;
+    for (int j = part; j < (live ? L : jmax); j += GT / TR) {
+      float p = 0.0f;
+      if (live && j <= i) p = (float)(Pd[j * TRP + r] / sum);
+      if (live) att[j] = p;
+      if (j < jmax) Pf[j * TRP + r] = (p != 0.0f && pdrop > 0.0f) ? p * drop_scale(seed, b, i, layer, 1, h * Tmax + j, pdrop) : p;
+    }
+  }
+  __syncthreads();
+  const TiledCols t = tiled_cols(hs);
+  if (!t.on) return;
+  float acc[TR];
+#pragma unroll
+  for (int r = 0; r < TR; ++r) acc[r] = 0.0f;
+  tiled_accumulate(Pf, base + 2 * C, 3LL * C, jmax, t, acc);
+#pragma unroll
+  for (int r = 0; r < TR; ++r) {
+    const int i = i0 + t.g + r * t.G;
+    if (r < t.rpt && t.g + r * t.G < TR && i < i1) Y[((long long)b * Lm + i) * C + h * hs + t.d] = acc[r];
+  }
+}
+
+// grid (B * nh, ceil(Lm / TR)): dP, the softmax backward (dS into DS, j <= i) and dQ of the query rows [i0, i0 + TR)
+__global__ __launch_bounds__(GT) void gptb_attn_bwd_rows_kernel(const float* __restrict__ QKV, const float* __restrict__ ATT,
+                                                                const float* __restrict__ dY, float* __restrict__ DS,
+                                                                float* __restrict__ dQKV, int C, int nh, int Lm,
+                                                                const int* __restrict__ Lp, float pdrop, uint64_t seed,
+                                                                int layer, int Tmax) {
+  extern __shared__ float sm[];
+  const int b = blockIdx.x / nh, h = blockIdx.x % nh, hs = C / nh, tid = threadIdx.x, L = *Lp, i0 = blockIdx.y * TR;
+  if (i0 >= L) return;
+  const int i1 = min(i0 + TR, L), jmax = i1;
+  float* Xs = sm; float* Zs = Xs + TR * hs; float* Pf = sm;          // Pf: after the score product
+  double* Pd = reinterpret_cast<double*>(sm + tiled_front_floats(Lm, hs));
+  const float* base = QKV + (long long)b * Lm * 3 * C + h * hs;
+  for (int e = tid; e < TR * hs; e += GT) {
+    const int r = e / hs, d = e - r * hs;
+    Xs[e] = (i0 + r < i1) ? dY[((long long)b * Lm + i0 + r) * C + h * hs + d] : 0.0f;
+  }
+  tiled_scores(Xs, base + 2 * C, 3LL * C, hs, jmax, Zs, Pd);       // dY . V^T
+  __syncthreads();
+  {
+    const int r = tid / (GT / TR), part = tid % (GT / TR), i = i0 + r;
+    const bool live = i < i1;
+    const double scale = 1.0 / sqrt((double)hs);
+    const long long row = ((long long)blockIdx.x * Lm + i) * Lm;
+    double dot = 0.0;
+    if (live)
+      for (int j = part; j <= i; j += GT / TR) {
+        double dp = Pd[j * TRP + r];
+        if (pdrop > 0.0f) dp *= (double)drop_scale(seed, b, i, layer, 1, h * Tmax + j, pdrop);
+        Pd[j * TRP + r] = dp;
+        dot = fma((double)ATT[row + j], dp, dot);
+      }
+    for (int o = GT / TR / 2; o > 0; o >>= 1) dot += __shfl_xor(dot, o, 64);
+    for (int j = part; j < jmax; j += GT / TR) {
+      float ds = 0.0f;
+      if (live && j <= i) { ds = (float)((double)ATT[row + j] * (Pd[j * TRP + r] - dot) * scale); DS[row + j] = ds; }
+      Pf[j * TRP + r] = ds;
+    }
+  }
+  __syncthreads();
+  const TiledCols t = tiled_cols(hs);
+  if (!t.on) return;
+  float acc[TR];
+#pragma unroll
+  for (int r = 0; r < TR; ++r) acc[r] = 0.0f;
+  tiled_accumulate(Pf, base + C, 3LL * C, jmax, t, acc);           // dQ = dS . K
+#pragma unroll
+  for (int r = 0; r < TR; ++r) {
+    const int i = i0 + t.g + r * t.G;
+    if (r < t.rpt && t.g + r * t.G < TR && i < i1) dQKV[((long long)b * Lm + i) * 3 * C + h * hs + t.d] = acc[r];
+  }
+}
+
+// grid (B * nh, ceil(Lm / TR)): dV = drop(P)^T . dY and dK = dS^T . Q of the key rows [j0, j0 + TR), over the query rows j0 .. L - 1
+__global__ __launch_bounds__(GT) void gptb_attn_bwd_keys_kernel(const float* __restrict__ QKV, const float* __restrict__ ATT,
+                                                                const float* __restrict__ dY, const float* __restrict__ DS,
+                                                                float* __restrict__ dQKV, int C, int nh, int Lm,
+                                                                const int* __restrict__ Lp, float pdrop, uint64_t seed,
+                                                                int layer, int Tmax) {
+  extern __shared__ float sm[];
+  const int b = blockIdx.x / nh, h = blockIdx.x % nh, hs = C / nh, tid = threadIdx.x, L = *Lp, j0 = blockIdx.y * TR;
+  if (j0 >= L) return;
+  const int N = L - j0;                                            // query rows i = j0 + n
+  float* Wp = sm; float* Ws = Wp + Lm * TRP;
+  const long long head = (long long)blockIdx.x * Lm * Lm;
+  for (int e = tid; e < N * TR; e += GT) {
+    const int n = e / TR, jj = e - n * TR, i = j0 + n, j = j0 + jj;
+    float p = 0.0f, ds = 0.0f;
+    if (j <= i && j < L) {
+      p = ATT[head + (long long)i * Lm + j];
+      if (pdrop > 0.0f) p *= drop_scale(seed, b, i, layer, 1, h * Tmax + j, pdrop);
+      ds = DS[head + (long long)i * Lm + j];
+    }
+    Wp[n * TRP + jj] = p; Ws[n * TRP + jj] = ds;
+  }
+  __syncthreads();
+  const TiledCols t = tiled_cols(hs);
+  if (!t.on) return;
+  float av[TR], ak[TR];
+#pragma unroll
+  for (int r = 0; r < TR; ++r) { av[r] = 0.0f; ak[r] = 0.0f; }
+  tiled_accumulate(Wp, dY + ((long long)b * Lm + j0) * C + h * hs, (long long)C, N, t, av);
+  tiled_accumulate(Ws, QKV + ((long long)b * Lm + j0) * 3 * C + h * hs, 3LL * C, N, t, ak);
+#pragma unroll
+  for (int r = 0; r < TR; ++r) {
+    const int j = j0 + t.g + r * t.G;
+    if (r < t.rpt && t.g + r * t.G < TR && j < L) {
+      float* dst = dQKV + ((long long)b * Lm + j) * 3 * C + h * hs + t.d;
+      dst[C] = ak[r]; dst[2 * C] = av[r];
+    }
+  }
+}
+
 // DL[m][a] = dlogits[b][i - 1][a] for the live tokens i >= 1 (token i predicts the action of step i - 1), else 0
 __global__ __launch_bounds__(GT) void gptb_dl_kernel(const float* __restrict__ dlogits, float* __restrict__ DL, int B, int T,
                                                      int nA, int Lm, const int* __restrict__ Lp) {
@@ -714,10 +945,12 @@ Layout make_layout(int C, int nh, int nL, int B, int T) {
 
 }  // namespace
 
-size_t gpt_backward_batched_scratch(int C, int n_head, int n_layer, int nA, int B, int T) {
+size_t gpt_backward_batched_scratch(int C, int n_head, int n_layer, int nA, int B, int T, bool tiled) {
   const Layout y = make_layout(C, n_head, n_layer, B, T);
-  // temporaries: dX dXM dH dY dO HF (M*C each), dQKV (3), dF (4), DL (M*nA), ln_f statistics (2M)
-  return (size_t)(y.tmp + y.M * (13LL * C + nA + 2) + 64);
+  // temporaries: dX dXM dH dY dO HF (M*C each), dQKV (3), dF (4), DL (M*nA), ln_f statistics (2M); the tiled attention adds
+  // DS, one buffer of a layer's ATT shape
+  const long long Lm = T + 1, ds = tiled ? (long long)B * n_head * Lm * Lm : 0;
+  return (size_t)(y.tmp + y.M * (13LL * C + nA + 2) + ds + 64);
 }
 
 // The LayerNorm backward holds C / 64 <= LN_CQ columns per lane; the attention kernels keep q, k, v, dO of a head
@@ -728,11 +961,59 @@ bool gpt_backward_batched_admits(int C, int n_head, int T) {
   return (4 * Lm * hs + 2 * Lm * Lm) * sizeof(float) <= 64 * 1024;
 }
 
-// Returns 0 when launched, 1 when the shape is outside what these kernels take (the caller falls back).
-int launch_gpt_backward_batched(const GptBwdArgs& a, const GptLayerPtrs* W, const GptLayerPtrs* G, hipStream_t s) {
+// What the tiled attention kernels take (with the LayerNorm backward's bound on C): any head up to T_MAX_HS columns, any
+// sequence up to T_MAX_LM tokens.
+static bool tiled_admits(int C, int n_head, int T) {
+  if (C <= 0 || n_head <= 0 || C % n_head != 0 || T < 1 || C > 64 * LN_CQ) return false;
+  return T + 1 <= T_MAX_LM && C / n_head <= T_MAX_HS;
+}
+
+// JN_GPT_BWD_TILED=1 (test hook, read per launch so that a test can flip it): a per-agent-route shape that would take the LDS
+// form or the per-agent kernel takes the tiled form.  (The name is held in a constant: the hook is listed in DESIGN.md §4.5.)
+static const char* const kTiledHook = "JN_GPT_BWD_TILED";
+
+GptBwdRoute gpt_backward_route(int C, int n_head, int T, int decision_route) {
+  if (C <= 0 || n_head <= 0 || C % n_head != 0 || T < 1) return GPT_BWD_NONE;
+  if (decision_route == 0 && tiled_admits(C, n_head, T)) {
+    const char* hook = std::getenv(kTiledHook);
+    if (hook && std::atoi(hook) == 1) return GPT_BWD_TILED;
+  }
+  if (gpt_backward_batched_admits(C, n_head, T)) return GPT_BWD_LDS;
+  if (decision_route == 1) return GPT_BWD_NONE;                    // a wide context has no other backward
+  if (T <= GPT_PER_AGENT_MAX_T) return C <= GPT_PER_AGENT_MAX_C ? GPT_BWD_PER_AGENT : GPT_BWD_NONE;
+  return tiled_admits(C, n_head, T) ? GPT_BWD_TILED : GPT_BWD_NONE;
+}
+
+// One layer's attention on caller tensors (jn_gpt_attention_backward): the recompute (ATT, Y), then dQKV.  form 0: the LDS
+// kernels, 1: the tiled ones (DS: a buffer of ATT's shape).  Returns 1 when the form does not take the shape.
+int launch_gpt_attention(int form, const float* QKV, const float* dY, int B, int nh, int C, int Lm, const int* Lp, float pdrop,
+                         uint64_t seed, int layer, int Tmax, float* ATT, float* Y, float* DS, float* dQKV, hipStream_t s) {
+  if (C <= 0 || nh <= 0 || C % nh != 0 || Lm < 1 || B < 1) return 1;
+  const int hs = C / nh;
+  if (form == 0) {
+    const size_t lds = ((size_t)4 * Lm * hs + (size_t)2 * Lm * Lm) * sizeof(float);
+    if (lds > 64 * 1024) return 1;
+    hipLaunchKernelGGL(gptb_attn_fwd_kernel, dim3(B * nh), dim3(GT), lds, s, QKV, ATT, Y, C, nh, Lm, Lp, pdrop, seed, layer, Tmax);
+    hipLaunchKernelGGL(gptb_attn_bwd_kernel, dim3(B * nh), dim3(GT), lds, s, QKV, ATT, dY, dQKV, C, nh, Lm, Lp, pdrop, seed, layer, Tmax);
+    return 0;
+  }
+  if (form != 1 || Lm > T_MAX_LM || hs > T_MAX_HS) return 1;
+  const dim3 grid(B * nh, (Lm + TR - 1) / TR);
+  hipLaunchKernelGGL(gptb_attn_fwd_tiled_kernel, grid, dim3(GT), tiled_row_lds(Lm, hs), s, QKV, ATT, Y, C, nh, Lm, Lp, pdrop, seed,
+                     layer, Tmax);
+  hipLaunchKernelGGL(gptb_attn_bwd_rows_kernel, grid, dim3(GT), tiled_row_lds(Lm, hs), s, QKV, ATT, dY, DS, dQKV, C, nh, Lm, Lp,
+                     pdrop, seed, layer, Tmax);
+  hipLaunchKernelGGL(gptb_attn_bwd_keys_kernel, grid, dim3(GT), tiled_key_lds(Lm), s, QKV, ATT, dY, DS, dQKV, C, nh, Lm, Lp, pdrop,
+                     seed, layer, Tmax);
+  return 0;
+}
+
+// Returns 0 when launched, 1 when the shape is outside what the chosen attention form takes (tiled: the tiled kernels and
+// their DS buffer, which gpt_backward_batched_scratch(..., true) counts; else the LDS kernels).
+int launch_gpt_backward_batched(const GptBwdArgs& a, const GptLayerPtrs* W, const GptLayerPtrs* G, hipStream_t s, bool tiled) {
   const int C = a.C, nh = a.n_head, nL = a.n_layer, B = a.B, T = a.T, Lm = T + 1, hs = C / nh, nA = a.nA;
   const size_t attn_lds = ((size_t)4 * Lm * hs + (size_t)2 * Lm * Lm) * sizeof(float);
-  if (!gpt_backward_batched_admits(C, nh, T)) return 1;
+  if (!(tiled ? tiled_admits(C, nh, T) : gpt_backward_batched_admits(C, nh, T))) return 1;
   const Layout y = make_layout(C, nh, nL, B, T);
   const int M = (int)y.M;
   float* sc = a.scratch;
@@ -743,6 +1024,8 @@ int launch_gpt_backward_batched(const GptBwdArgs& a, const GptLayerPtrs* W, cons
   float* dO = dY + (long long)M * C; float* HF = dO + (long long)M * C; float* dQKV = HF + (long long)M * C;
   float* dF = dQKV + (long long)M * 3 * C; float* DL = dF + (long long)M * 4 * C; float* muF = DL + (long long)M * nA;
   float* rsF = muF + M;
+  float* DS = rsF + M;                                   // tiled attention only
+  const dim3 tiled_grid(B * nh, (Lm + TR - 1) / TR);
   const bool drop = a.pdrop > 0.0f;
   const int row_blocks = (M + GT / 64 - 1) / (GT / 64), lnb_blocks = (M + LN_RPB - 1) / LN_RPB;
   const long long MC = (long long)M * C;
@@ -795,8 +1078,12 @@ int launch_gpt_backward_batched(const GptBwdArgs& a, const GptLayerPtrs* W, cons
           *H2 = lay + y.o_H2, *Fp = lay + y.o_Fp, *st = lay + y.o_st;
     ln_fwd(H1, x, w.ln1_w, w.ln1_b, st, st + M);
     fwd(QKV, H1, w.qkv_wt, w.qkv_b, C, 3 * C, nullptr, -1, l, 0);
-    hipLaunchKernelGGL(gptb_attn_fwd_kernel, dim3(B * nh), dim3(GT), attn_lds, s, QKV, ATT, Yb, C, nh, Lm, Lp, a.pdrop,
-                       a.drop_seed, l, a.Tmax);
+    if (tiled)
+      hipLaunchKernelGGL(gptb_attn_fwd_tiled_kernel, tiled_grid, dim3(GT), tiled_row_lds(Lm, hs), s, QKV, ATT, Yb, C, nh, Lm, Lp,
+                         a.pdrop, a.drop_seed, l, a.Tmax);
+    else
+      hipLaunchKernelGGL(gptb_attn_fwd_kernel, dim3(B * nh), dim3(GT), attn_lds, s, QKV, ATT, Yb, C, nh, Lm, Lp, a.pdrop,
+                         a.drop_seed, l, a.Tmax);
     fwd(XM, Yb, w.proj_wt, w.proj_b, C, C, x, 2, l, 0);                       // XM = x + drop(proj(Y))
     ln_fwd(H2, XM, w.ln2_w, w.ln2_b, st + 2 * M, st + 3 * M);
     fwd(Fp, H2, w.fc_wt, w.fc_b, C, 4 * C, nullptr, -1, l, 0);                // pre-activation
@@ -830,8 +1117,15 @@ int launch_gpt_backward_batched(const GptBwdArgs& a, const GptLayerPtrs* W, cons
     if (drop) { dropmul(dO, dXM, l, 2); dPo = dO; }
     bwd_data(dY, dPo, w.proj_wt, C, C, nullptr);
     bwd_weight(gr.proj_wt, gr.proj_b, Yb, dPo, C, C, 0);
-    hipLaunchKernelGGL(gptb_attn_bwd_kernel, dim3(B * nh), dim3(GT), attn_lds, s, QKV, ATT, dY, dQKV, C, nh, Lm, Lp, a.pdrop,
-                       a.drop_seed, l, a.Tmax);
+    if (tiled) {
+      hipLaunchKernelGGL(gptb_attn_bwd_rows_kernel, tiled_grid, dim3(GT), tiled_row_lds(Lm, hs), s, QKV, ATT, dY, DS, dQKV, C, nh,
+                         Lm, Lp, a.pdrop, a.drop_seed, l, a.Tmax);
+      hipLaunchKernelGGL(gptb_attn_bwd_keys_kernel, tiled_grid, dim3(GT), tiled_key_lds(Lm), s, QKV, ATT, dY, DS, dQKV, C, nh, Lm,
+                         Lp, a.pdrop, a.drop_seed, l, a.Tmax);
+    } else {
+      hipLaunchKernelGGL(gptb_attn_bwd_kernel, dim3(B * nh), dim3(GT), attn_lds, s, QKV, ATT, dY, dQKV, C, nh, Lm, Lp, a.pdrop,
+                         a.drop_seed, l, a.Tmax);
+    }
     bwd_data(dH, dQKV, w.qkv_wt, C, 3 * C, nullptr);
     bwd_weight(gr.qkv_wt, gr.qkv_b, H1, dQKV, C, 3 * C, 0);
     ln_bwd(dX, dXM, dH, x, w.ln1_w, gr.ln1_w, gr.ln1_b, st, st + M);                    // dX = dXM + LN1^T(dH)
