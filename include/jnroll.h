@@ -837,6 +837,77 @@ int jn_pw_bwd_data_x3(const float* gz_dev, int g_ld, const float* w_dev, float* 
                       int n_slots, int max_wg, void* stream);
 int jn_pw_bwd_weight(const float* gz_dev, int g_ld, const float* x_dev, int x_ld, const float* tab_dev, float* gw_dev, long long M, int cout,
                      int cin, int n_slots, long long gz_slot_stride, int use_wpart, float* wpart_back_dev, int exact, void* stream);
+/* Debug entries, context-free: ONE launch of a kernel that runs between the convolutions of a train-mode pass (csrc/kernels_conv.hip:
+ * stem, SPP, upsample, shortcut sum, BatchNorm tables, embed_fpn linear; csrc/kernels_bwd.hip: their backward and the BatchNorm
+ * sums) on caller tensors, then a wait for `stream`.  Maps are NHWC with a leading dimension that may exceed the channel count;
+ * tables are f32 [3][C] (rows scale, shift, flag), per slot [S][3][C]; dtype 0 = f32, 1 = bf16 maps.  skip_flag_dev: NULL, or a device
+ * int; nothing is done when *skip_flag_dev >= skip_when.  JN_EINVAL before any device call: a null pointer (but the optional ones),
+ * a count below 1, n_slots outside 1..64, a leading dimension below its channel count or above 8192, max_wg < 0, and whatever the
+ * launcher refuses: named per entry.
+ *
+ * jn_stem: out [N][P/2][P/2][out_ld] = the 6 x 6 stride-2 conv (Focus + 3 x 3, zero padding at the patch border) of the P x P patch
+ * of image n at src + n * sample_stride (+ positions[pos_stride * n + {0, 1}] = (y, x) patch indices, if positions_dev is given),
+ * channels chan_stride and rows row_stride elements apart; src_u8 != 0: bytes b read as b / 255.  w f32 [108][cout], k = 36 c + 6 dy
+ * + dx.  out_dtype 0 / 1.  stats_dev: NULL, or f64 [nrep][2 cout] the launch ADDS (sum, sum of squares) per channel into, nrep 1..32.
+ * max_wg: 0 = the launcher's rule, else a cap on the persistent workgroups along x.  Refused: odd P, cout % 16 != 0, out_ld % 4 != 0.
+ * jn_stem_bwd_weight: gw [108][cout] += sum over slots and pixels of g_z * patch; g [S][N][P/2][P/2][g_ld] is g_z itself, or with
+ * z_dev (same shape, z_ld) d loss / d activation, turned into g_z = k (g silu'(o_sc z + o_sh) - c1 - (z - mean) invstd c2) on the way:
+ * otab [S][3][cout], save [S][cout][2], consts [S][cout][3].  Slot j reads positions + j * pos_slot_stride.  wpart_dev: the
+ * f32 [32][16384] replica scratch, zero on entry and zero again afterwards.  Refused: as jn_stem, and cout > 144 (the scratch).
+ * jn_spp: slices 1..3 of cat [N][H][W][ld] (h channels each) = max-pools 5 / 9 / 13 of the activation of slice 0 (tab [3][h]).
+ * route: 0 = the launcher's rule, 1 = the quad kernel (f32, h % 16 == 0, ld % 4 == 0, H * W <= 510), 2 = the scalar kernel (h a
+ * multiple of its 8 channels per workgroup, 4 where the map needs more than 48 KB of LDS with 8).  Refused: a route whose
+ * preconditions the launch misses, LDS above what a workgroup can be granted, N > 65535.
+ * jn_spp_bwd: slice 0 of gcat [S][N][H][W][ld] += the three pooled gradients of slices 1..3, each sent to the first maximum of
+ * its window in row-major order; cat as in jn_spp per slot, tab [S][3][h].  Routes as jn_spp (quad: H * W <= 512; scalar: 4 channels
+ * above 60 KB).
+ * jn_spp_route: host only: the route (1 or 2) the rule gives (bwd != 0: the backward launcher's).
+ * jn_upsample: out [N][2H][2W][out_ld] = nearest x2 copy of in [N][H][W][in_ld].  Refused: C or a leading dimension no multiple of 4.
+ * jn_upsample_bwd: gsrc [S][N][H][W][src_ld] (=|+=) the sum of the 2 x 2 children in gdst [S][N][2H][2W][dst_ld]; f32.  Allocates
+ * its workspace and frees it.
+ * jn_addact: out [M][out_ld] = T_ztab(z) + T_rtab(res).  Refused: C or a leading dimension no multiple of 4, C > 2048.
+ * jn_bn_finalize: train-mode BatchNorm of C channels from the f64 sums stats [32][rep_stride] ((sum, sum of squares) of channel c at
+ * [2 c] of a replica) over `count` values: tab0 (and tab1, if given) [3][C] = (gamma invstd, beta - mean gamma invstd, 1); save [C][2]
+ * = (mean, invstd) and the running statistics (unbiased variance) are optional.
+ * jn_bn_finalize_all: the same for n_stat channels of many layers at once: channel i has hw[i] pixels per image (<= 0: skipped),
+ * weight and bias at params[goff[i]] and params[boff[i]], table columns t0[i] and t1[i] (-1: none) of tab [3][tab_channels]; it sums
+ * 8 replicas where N * hw <= defer_max_m, else all 32.  run_mean, run_var f32 [n_stat].  Allocates an address array and frees it.
+ * jn_bn_bwd_sums: reduce != 0: red [S][32][2 C] += per channel (sum g silu'(y), sum g silu'(y) zhat) over the M pixels of g, z
+ * [S][M][ld] with y = sc z + sh (tab [S][3][C], flag row not read), zhat = (z - mean) invstd from save [S][C][2]; refused: C % 4 != 0,
+ * C > 1024.  consts_dev given: consts [S][C][3] = (sum1 / M, sum2 / M, gamma invstd) from the replicas' totals, g_beta += sum1,
+ * g_gamma += sum2 over all slots; raw_moment != 0 (without reduce): the second sum is against y and is converted first.
+ * jn_efpn_linear: part [N][KS][Co] = the K-slice partial sums of e [N][K] . wt [K][Co] (MFMA form where Co % 16 == 0 and K % 4 == 0,
+ * else the scalar form).  Refused: the scalar form with Co > 256. */
+int jn_stem(const void* src_dev, int src_u8, const int64_t* positions_dev, int pos_stride, long long sample_stride, long long chan_stride,
+            int row_stride, int P, int N, int cout, const float* w_dev, void* out_dev, int out_ld, int out_dtype, double* stats_dev, int nrep,
+            const int* skip_flag_dev, int skip_when, int max_wg, void* stream);
+int jn_stem_bwd_weight(const void* src_dev, int src_u8, const int64_t* positions_dev, int pos_stride, long long pos_slot_stride,
+                       long long sample_stride, long long chan_stride, int row_stride, int P, int N, int cout, const float* g_dev, int g_ld,
+                       const float* z_dev, int z_ld, const float* otab_dev, const float* save_dev, const float* consts_dev, float* gw_dev,
+                       float* wpart_dev, int n_slots, int max_wg, void* stream);
+int jn_spp_route(int dtype, int ld, int h, int H, int W, int N, int bwd);
+int jn_spp(void* cat_dev, int dtype, int ld, int h, int H, int W, int N, const float* tab_dev, const int* skip_flag_dev, int skip_when,
+           int route, void* stream);
+int jn_spp_bwd(const float* cat_dev, float* gcat_dev, int ld, int h, int H, int W, int N, const float* tab_dev, int n_slots, int route,
+               void* stream);
+int jn_upsample(const void* in_dev, int in_ld, void* out_dev, int out_ld, int dtype, int C, int H, int W, int N, const int* skip_flag_dev,
+                int skip_when, void* stream);
+int jn_upsample_bwd(const float* gdst_dev, int dst_ld, float* gsrc_dev, int src_ld, int C, int H, int W, int N, int accumulate, int n_slots,
+                    void* stream);
+int jn_addact(const void* z_dev, int z_ld, const float* ztab_dev, const void* res_dev, int res_ld, const float* rtab_dev, void* out_dev,
+              int out_ld, int dtype, int C, long long M, const int* skip_flag_dev, int skip_when, void* stream);
+int jn_bn_finalize(const double* stats_dev, long long rep_stride, double count, const float* gamma_dev, const float* beta_dev, float* run_mean_dev,
+                   float* run_var_dev, float* save_dev, float* tab0_dev, float* tab1_dev, int C, float eps, float momentum,
+                   const int* skip_flag_dev, int skip_when, void* stream);
+int jn_bn_finalize_all(const double* stats_dev, long long rep_stride, int n_stat, int N, const float* hw_dev, const int* goff_dev,
+                       const int* boff_dev, const float* params_dev, const int* t0_dev, const int* t1_dev, float* tab_dev, int tab_channels,
+                       float* save_dev, float* run_mean_dev, float* run_var_dev, float eps, float momentum, const int* skip_flag_dev, int skip_when,
+                       long long defer_max_m, void* stream);
+int jn_bn_bwd_sums(const float* g_dev, int g_ld, const float* z_dev, int z_ld, const float* tab_dev, const float* save_dev, int C, long long M,
+                   int n_slots, double* red_dev, const float* gamma_dev, const float* beta_dev, float* consts_dev, float* g_gamma_dev,
+                   float* g_beta_dev, int reduce, int raw_moment, void* stream);
+int jn_efpn_linear(const float* e_dev, const float* wt_dev, float* part_dev, int N, int K, int Co, int KS, const int* skip_flag_dev, int skip_when,
+                   void* stream);
 /* Arms the following rollouts of `ctx` with that teacher (the per-step `best_action` that test_model_on_env compares
  * each chosen action with, src/supervised.py:279-405): before the decision of step t, the set of the state that
  * decision sees (position and visited patches before the step) goes to sets_dev[b * T + t] (uint8 [B,T], T =

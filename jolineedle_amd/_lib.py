@@ -180,6 +180,24 @@ SIGNATURES = {
                                     C.c_void_p]),
     "jn_pw_bwd_weight": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int,
                                    C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "jn_stem": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int,
+                          C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "jn_stem_bwd_weight": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong] + [C.c_int] * 4 +
+                                     [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_void_p]),
+    "jn_spp_route": (C.c_int, [C.c_int] * 7),
+    "jn_spp": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "jn_spp_bwd": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "jn_upsample": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p]),
+    "jn_upsample_bwd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_int] * 6 + [C.c_void_p]),
+    "jn_addact": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p] * 2 + [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_int,
+                            C.c_void_p]),
+    "jn_bn_finalize": (C.c_int, [C.c_void_p, C.c_longlong, C.c_double] + [C.c_void_p] * 7 + [C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int,
+                                 C.c_void_p]),
+    "jn_bn_finalize_all": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 3 +
+                                     [C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p]),
+    "jn_bn_bwd_sums": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int] +
+                                 [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]),
+    "jn_efpn_linear": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p]),
     "jn_set_rollout_teacher":(C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "jn_set_rollout_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "jn_set_rollout_classes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),

@@ -539,7 +539,7 @@ int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, hi
   struct ConvB { const Op& op; const BwdStep& st; const ConvW& cw; float* g; int g_ld; long long M; float* consts; float* gw; };
   // BatchNorm sums and constants of the conv, whole or — a merged pair with a half reduced by its consumer — per half: a
   // part no consumer reduced gets its own pass, and consumer-made sums carry the moment against y (bn_bwd_consts)
-  auto bn_sums_consts = [&](const ConvB& c) {
+  auto bn_sums_consts = [&](const ConvB& c) -> int {
     const ConvW& cw = c.cw;
     const int parts = c.st.red_by && !cw.prefix2.empty() ? 2 : 1, h = cw.cout / parts;
     double* red = net.bred + 2 * cw.stat_off;
@@ -554,12 +554,14 @@ int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, hi
     for (int part = 0; part < parts; ++part) {
       const int c0 = part * h, by_consumer = (c.st.red_by >> part) & 1;
       float* sv = save + 2 * (cw.stat_off + c0);
-      if (!by_consumer)
-        launch_bn_bwd_reduce(c.g + c0, c.g_ld, ptr(c.op.out) + c0, ld(c.op.out), tab_at(tab(c.op.out), c0), sv, h, c.M,
-                             red + 2 * c0, rep_stride, s, sb);
-      launch_bn_bwd_consts(red + 2 * c0, rep_stride, (double)c.M, cw.gamma_dev + c0, cw.beta_dev + c0, sv, c.consts + 3 * c0,
-                           grad_of(ctx, cw.gamma_dev) + c0, grad_of(ctx, cw.beta_dev) + c0, h, s, sb, by_consumer);
+      JN_CHECK(by_consumer || launch_bn_bwd_reduce(c.g + c0, c.g_ld, ptr(c.op.out) + c0, ld(c.op.out), tab_at(tab(c.op.out), c0), sv, h, c.M,
+                                                   red + 2 * c0, rep_stride, s, sb) == 0,
+               JN_ESTATE, "launch_bn_bwd_reduce: %s has %d channels (whole quads, at most 1024)", c.op.name.c_str(), h);
+      JN_CHECK(launch_bn_bwd_consts(red + 2 * c0, rep_stride, (double)c.M, cw.gamma_dev + c0, cw.beta_dev + c0, sv, c.consts + 3 * c0,
+                                    grad_of(ctx, cw.gamma_dev) + c0, grad_of(ctx, cw.beta_dev) + c0, h, s, sb, by_consumer) == 0,
+               JN_ESTATE, "launch_bn_bwd_consts: %s was refused", c.op.name.c_str());
     }
+    return JN_OK;
   };
   // the data gradient of a stride-1 conv as its forward kernel over g_z with the transposed weight, all slots in one launch
   auto gz_conv_args = [&](const ConvB& c) {
@@ -590,18 +592,21 @@ int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, hi
       switch (st.route) {
         case BR_ADDACT_COPY: case BR_ADDACT_FOLD:
           // (without acc_in the conv that feeds the add reads g[sum] in place, BwdStep::g; folded: that conv's kernel adds it)
-          if (op.acc_in) launch_grad_copy(gptr(op.out), ld(op.out), gptr(op.in), ld(op.in), op.out.C, M, 1, s, sb);
-          if (st.route == BR_ADDACT_COPY)
-            launch_grad_copy(gptr(op.out), ld(op.out), gptr(op.res), ld(op.res), op.out.C, M, op.acc_res ? 1 : 0, s, sb);
+          JN_CHECK(!op.acc_in || launch_grad_copy(gptr(op.out), ld(op.out), gptr(op.in), ld(op.in), op.out.C, M, 1, s, sb) == 0, JN_ESTATE,
+                   "launch_grad_copy: %s was refused", op.name.c_str());
+          JN_CHECK(st.route != BR_ADDACT_COPY ||
+                       launch_grad_copy(gptr(op.out), ld(op.out), gptr(op.res), ld(op.res), op.out.C, M, op.acc_res ? 1 : 0, s, sb) == 0,
+                   JN_ESTATE, "launch_grad_copy: %s was refused", op.name.c_str());
           break;
         case BR_SPP: {
           const View full = net_full_view(net, op.out.buf);
           JN_CHECK(launch_spp_bwd(ptr(full), gptr(full), ld(op.out), op.in.C, op.in.H, op.in.W, N, tab(op.in), s, sb) == 0, JN_ESTATE,
-                   "launch_spp_bwd: the LDS of %s was refused", op.name.c_str());
+                   "launch_spp_bwd: %s was refused (channel block, alignment or LDS)", op.name.c_str());
           break;
         }
         case BR_UPSAMPLE:
-          launch_upsample_bwd(gptr(op.out), ld(op.out), gptr(op.in), ld(op.in), op.in.C, op.in.H, op.in.W, N, op.acc_in ? 1 : 0, s, sb);
+          JN_CHECK(launch_upsample_bwd(gptr(op.out), ld(op.out), gptr(op.in), ld(op.in), op.in.C, op.in.H, op.in.W, N, op.acc_in ? 1 : 0, s, sb) == 0,
+                   JN_ESTATE, "launch_upsample_bwd: %s was refused", op.name.c_str());
           break;
         default: break;      // nothing to differentiate here (the head's predictors: api_det.hip)
       }
@@ -611,7 +616,7 @@ int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, hi
     const ConvW& cw = net.convs[op.wslot];
     const ConvB c{op, st, cw, gptr(st.g), ld(st.g), M, net.bconsts + 3 * cw.stat_off, grad_of(ctx, cw.w_dev)};
     hipStream_t ws = s;      // of a weight-gradient kernel that may run beside the rest (fork_aux)
-    bn_sums_consts(c);
+    if ((rc = bn_sums_consts(c))) return rc;
     switch (st.route) {
       case BR_PW_FUSED: case BR_PW_FUSED_HALVES: {      // one launch, or one per half of the output channels
         const int parts = st.route == BR_PW_FUSED ? 1 : 2, pc = cw.cout / parts;
@@ -663,8 +668,9 @@ int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, hi
         break;
       }
       case BR_STEM_FUSED:      // bn_bwd_gz inside: no pass over the largest map of the network
-        launch_stem_bwd_weight(stem_args(ss, net, N, cw), c.g, c.g_ld, c.gw, ctx->wpart, s, sb, ptr(op.out), ld(op.out), tab(op.out),
-                               save + 2 * cw.stat_off, c.consts);
+        JN_CHECK(launch_stem_bwd_weight(stem_args(ss, net, N, cw), c.g, c.g_ld, c.gw, ctx->wpart, s, sb, ptr(op.out), ld(op.out), tab(op.out),
+                                        save + 2 * cw.stat_off, c.consts) == 0,
+                 JN_ESTATE, "launch_stem_bwd_weight: %s was refused (patch size %d, %d output channels)", op.name.c_str(), net.P, cw.cout);
         break;
       case BR_PW: {
         bn_gz(c);
@@ -744,7 +750,8 @@ int run_embed_fpn(jn_ctx* ctx, int N, int slot, float* e_buf, const int* skip_fl
   a.N = N; a.H = f.H; a.W = f.W; a.OH = f.H; a.OW = f.W; a.cin = f.C; a.cout = C; a.stride = 1; a.act = ACT_RELU;
   a.skip_flag = skip_flag; a.skip_when = skip_when;
   JN_CHECK(launch_pw(a, s) == 0, JN_ESTATE, "embed_fpn.0: no kernel for this shape, or its LDS was refused");
-  launch_efpn_linear(e_buf, ctx->gpt.efpn_lin_wt, x.emb_part, N, f.H * f.W * C, C, x.KS, skip_flag, skip_when, s);
+  JN_CHECK(launch_efpn_linear(e_buf, ctx->gpt.efpn_lin_wt, x.emb_part, N, f.H * f.W * C, C, x.KS, skip_flag, skip_when, s) == 0, JN_ESTATE,
+           "embed_fpn.3: no kernel for %d outputs", C);
   JN_HIP(hipGetLastError());
   return JN_OK;
 }

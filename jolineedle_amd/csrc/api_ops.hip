@@ -843,3 +843,227 @@ int jn_pw_bwd_weight(const float* gz_dev, int g_ld, const float* x_dev, int x_ld
 }
 
 }  // extern "C"
+
+// ---- stem, SPP, upsample, shortcut sum, BatchNorm tables and sums, embed_fpn linear on caller tensors (kernels_conv.hip, kernels_bwd.hip) ----
+// The launchers refuse what their kernels cannot take (-1, before anything is launched); the entries check what only they can know
+// (ranges that keep the index arithmetic in int, table shapes) and pass the launchers' refusals on.
+static bool glue_map_ok(int N, int H, int W) { return N >= 1 && H >= 1 && W >= 1 && (long long)N * H * W <= (1 << 24); }
+static bool glue_ld_ok(int ld, int C) { return ld >= C && ld <= 8192; }
+
+// runs `launch` (a launcher's return code), then waits for the stream
+template <typename F>
+static int glue_run(const char* who, hipStream_t s, F launch) {
+  const int rc = launch();
+  JN_CHECK(rc == 0, JN_EINVAL, "%s: the launcher refused the arguments", who);
+  JN_HIP(hipGetLastError());
+  JN_HIP(hipStreamSynchronize(s));
+  return JN_OK;
+}
+
+static StemArgs stem_entry_args(const void* src_dev, int src_u8, const int64_t* positions_dev, int pos_stride, long long sample_stride,
+                                long long chan_stride, int row_stride, int P, int N, int cout, const float* w_dev) {
+  StemArgs a{};
+  a.src = src_dev; a.src_u8 = src_u8 ? 1 : 0; a.positions = positions_dev; a.pos_stride = pos_stride; a.sample_stride = sample_stride;
+  a.chan_stride = chan_stride; a.row_stride = row_stride; a.P = P; a.N = N; a.cout = cout; a.w = w_dev;
+  return a;
+}
+static bool stem_entry_ok(int P, int N, int cout, long long sample_stride, long long chan_stride, int row_stride) {
+  return P >= 1 && P <= 4096 && N >= 1 && N <= 65536 && cout >= 1 && cout <= 4096 && sample_stride >= 0 && chan_stride >= 1 && row_stride >= 1;
+}
+
+extern "C" {
+
+int jn_stem(const void* src_dev, int src_u8, const int64_t* positions_dev, int pos_stride, long long sample_stride, long long chan_stride,
+            int row_stride, int P, int N, int cout, const float* w_dev, void* out_dev, int out_ld, int out_dtype, double* stats_dev, int nrep,
+            const int* skip_flag_dev, int skip_when, int max_wg, void* stream) {
+  JN_CHECK(src_dev && w_dev && out_dev, JN_EINVAL, "jn_stem: null argument");
+  JN_CHECK(stem_entry_ok(P, N, cout, sample_stride, chan_stride, row_stride) && glue_ld_ok(out_ld, cout) && (out_dtype == JN_F32 || out_dtype == JN_BF16) &&
+               nrep >= 1 && nrep <= JN_NREP && max_wg >= 0,
+           JN_EINVAL, "jn_stem: P=%d N=%d cout=%d out_ld=%d out_dtype=%d nrep=%d max_wg=%d", P, N, cout, out_ld, out_dtype, nrep, max_wg);
+  StemArgs a = stem_entry_args(src_dev, src_u8, positions_dev, pos_stride, sample_stride, chan_stride, row_stride, P, N, cout, w_dev);
+  a.out = out_dev; a.out_ld = out_ld; a.out_dtype = out_dtype; a.stats = stats_dev; a.stats_rep_stride = 2LL * cout; a.stats_nrep = nrep;
+  a.skip_flag = skip_flag_dev; a.skip_when = skip_when;
+  hipStream_t s = (hipStream_t)stream;
+  return glue_run("jn_stem", s, [&] { return launch_stem(a, s, max_wg); });
+}
+
+int jn_stem_bwd_weight(const void* src_dev, int src_u8, const int64_t* positions_dev, int pos_stride, long long pos_slot_stride,
+                       long long sample_stride, long long chan_stride, int row_stride, int P, int N, int cout, const float* g_dev, int g_ld,
+                       const float* z_dev, int z_ld, const float* otab_dev, const float* save_dev, const float* consts_dev, float* gw_dev,
+                       float* wpart_dev, int n_slots, int max_wg, void* stream) {
+  JN_CHECK(src_dev && g_dev && gw_dev && wpart_dev, JN_EINVAL, "jn_stem_bwd_weight: null argument");
+  JN_CHECK(stem_entry_ok(P, N, cout, sample_stride, chan_stride, row_stride) && glue_ld_ok(g_ld, cout) && n_slots >= 1 && n_slots <= 64 &&
+               max_wg >= 0 && pos_slot_stride >= 0,
+           JN_EINVAL, "jn_stem_bwd_weight: P=%d N=%d cout=%d g_ld=%d slots=%d max_wg=%d", P, N, cout, g_ld, n_slots, max_wg);
+  JN_CHECK(!z_dev || (otab_dev && save_dev && consts_dev && glue_ld_ok(z_ld, cout)), JN_EINVAL,
+           "jn_stem_bwd_weight: the fused g_z form needs the output table, save and consts, and z_ld=%d >= %d", z_ld, cout);
+  const StemArgs a = stem_entry_args(src_dev, src_u8, positions_dev, pos_stride, sample_stride, chan_stride, row_stride, P, N, cout, gw_dev);
+  // (StemArgs::w: the weight gradient does not read the weight; the field holds the [108][cout] array of the same shape, as the
+  // check both stem launchers share wants it set)
+  const long long px = (long long)N * (P / 2) * (P / 2);
+  SlotBatch sb;
+  sb.n = n_slots; sb.grad = px * g_ld; sb.act = px * z_ld; sb.tab = 3LL * cout; sb.save = 2LL * cout; sb.consts = 3LL * cout; sb.pos = pos_slot_stride;
+  const ChanTab ot = z_dev ? dw_tab(otab_dev, cout) : ChanTab{};
+  hipStream_t s = (hipStream_t)stream;
+  return glue_run("jn_stem_bwd_weight", s, [&] {
+    return launch_stem_bwd_weight(a, g_dev, g_ld, gw_dev, wpart_dev, s, sb, z_dev, z_ld, ot, save_dev, consts_dev, max_wg);
+  });
+}
+
+int jn_spp_route(int dtype, int ld, int h, int H, int W, int N, int bwd) {
+  JN_CHECK(dtype == JN_F32 || dtype == JN_BF16, JN_EINVAL, "jn_spp_route: dtype=%d", dtype);
+  const int r = spp_route(dtype, ld, h, H, W, N, bwd ? 1 : 0, 0);
+  JN_CHECK(r > 0, JN_EINVAL, "jn_spp_route: no kernel takes %d x %d x %d with %d channels of %d (bwd %d)", N, H, W, h, ld, bwd);
+  return r;
+}
+
+int jn_spp(void* cat_dev, int dtype, int ld, int h, int H, int W, int N, const float* tab_dev, const int* skip_flag_dev, int skip_when,
+           int route, void* stream) {
+  JN_CHECK(cat_dev && tab_dev, JN_EINVAL, "jn_spp: null argument");
+  JN_CHECK(glue_map_ok(N, H, W) && h >= 1 && h <= 2048 && glue_ld_ok(ld, 4 * h) && (dtype == JN_F32 || dtype == JN_BF16) && route >= 0 &&
+               route <= SPP_ROUTE_SCALAR,
+           JN_EINVAL, "jn_spp: %d x %d x %d, %d channels of %d, dtype %d, route %d", N, H, W, h, ld, dtype, route);
+  hipStream_t s = (hipStream_t)stream;
+  return glue_run("jn_spp", s, [&] { return launch_spp(cat_dev, dtype, ld, h, H, W, N, dw_tab(tab_dev, h), skip_flag_dev, skip_when, s, route); });
+}
+
+int jn_spp_bwd(const float* cat_dev, float* gcat_dev, int ld, int h, int H, int W, int N, const float* tab_dev, int n_slots, int route,
+               void* stream) {
+  JN_CHECK(cat_dev && gcat_dev && tab_dev, JN_EINVAL, "jn_spp_bwd: null argument");
+  JN_CHECK(glue_map_ok(N, H, W) && h >= 1 && h <= 2048 && glue_ld_ok(ld, 4 * h) && n_slots >= 1 && n_slots <= 64 && route >= 0 &&
+               route <= SPP_ROUTE_SCALAR,
+           JN_EINVAL, "jn_spp_bwd: %d x %d x %d, %d channels of %d, %d slots, route %d", N, H, W, h, ld, n_slots, route);
+  SlotBatch sb;      // the caller's [S, ...] tensors are slots already
+  sb.n = n_slots; sb.act = sb.grad = (long long)N * H * W * ld; sb.tab = 3LL * h;
+  hipStream_t s = (hipStream_t)stream;
+  return glue_run("jn_spp_bwd", s, [&] { return launch_spp_bwd(cat_dev, gcat_dev, ld, h, H, W, N, dw_tab(tab_dev, h), s, sb, route); });
+}
+
+int jn_upsample(const void* in_dev, int in_ld, void* out_dev, int out_ld, int dtype, int C, int H, int W, int N, const int* skip_flag_dev,
+                int skip_when, void* stream) {
+  JN_CHECK(in_dev && out_dev, JN_EINVAL, "jn_upsample: null argument");
+  JN_CHECK(glue_map_ok(N, 2 * H, 2 * W) && H >= 1 && W >= 1 && C >= 1 && glue_ld_ok(in_ld, C) && glue_ld_ok(out_ld, C), JN_EINVAL,
+           "jn_upsample: %d x %d x %d, %d channels, leading dimensions %d and %d", N, H, W, C, in_ld, out_ld);
+  hipStream_t s = (hipStream_t)stream;
+  return glue_run("jn_upsample", s, [&] { return launch_upsample(in_dev, in_ld, out_dev, out_ld, dtype, C, H, W, N, skip_flag_dev, skip_when, s); });
+}
+
+// (the kernel steps both gradients by ONE slot stride, the engine's gradient workspace: the caller's dense tensors are laid into
+// slots [g_dst | g_src] as in jn_dw_bwd, so the call allocates, waits for the stream and frees)
+int jn_upsample_bwd(const float* gdst_dev, int dst_ld, float* gsrc_dev, int src_ld, int C, int H, int W, int N, int accumulate, int n_slots,
+                    void* stream) {
+  JN_CHECK(gdst_dev && gsrc_dev, JN_EINVAL, "jn_upsample_bwd: null argument");
+  JN_CHECK(glue_map_ok(N, 2 * H, 2 * W) && H >= 1 && W >= 1 && C >= 1 && glue_ld_ok(dst_ld, C) && glue_ld_ok(src_ld, C) && n_slots >= 1 && n_slots <= 64,
+           JN_EINVAL, "jn_upsample_bwd: %d x %d x %d, %d channels, leading dimensions %d and %d, %d slots", N, H, W, C, dst_ld, src_ld, n_slots);
+  JN_CHECK(C >= 4 && C % 4 == 0 && dst_ld % 4 == 0 && src_ld % 4 == 0, JN_EINVAL, "jn_upsample_bwd: %d channels, leading dimensions %d and %d: whole quads",
+           C, dst_ld, src_ld);      // (the launcher's refusal, taken before the workspace is allocated)
+  hipStream_t s = (hipStream_t)stream;
+  const size_t dn = (size_t)N * 4 * H * W * dst_ld, sn = (size_t)N * H * W * src_ld, slot = dn + sn;
+  float* ws = nullptr;
+  JN_HIP(hipMalloc((void**)&ws, (size_t)n_slots * slot * sizeof(float)));
+  hipError_t e = hipMemcpy2DAsync(ws, slot * sizeof(float), gdst_dev, dn * sizeof(float), dn * sizeof(float), n_slots, hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = hipMemcpy2DAsync(ws + dn, slot * sizeof(float), gsrc_dev, sn * sizeof(float), sn * sizeof(float), n_slots, hipMemcpyDeviceToDevice, s);
+  int rc = -1;
+  if (e == hipSuccess) {
+    SlotBatch sb;
+    sb.n = n_slots; sb.grad = (long long)slot;
+    rc = launch_upsample_bwd(ws, dst_ld, ws + dn, src_ld, C, H, W, N, accumulate ? 1 : 0, s, sb);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy2DAsync(gsrc_dev, sn * sizeof(float), ws + dn, slot * sizeof(float), sn * sizeof(float), n_slots, hipMemcpyDeviceToDevice, s);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(ws);
+  JN_HIP(e);
+  JN_CHECK(rc == 0, JN_EINVAL, "jn_upsample_bwd: the launcher refused the arguments");
+  return JN_OK;
+}
+
+int jn_addact(const void* z_dev, int z_ld, const float* ztab_dev, const void* res_dev, int res_ld, const float* rtab_dev, void* out_dev,
+              int out_ld, int dtype, int C, long long M, const int* skip_flag_dev, int skip_when, void* stream) {
+  JN_CHECK(z_dev && ztab_dev && res_dev && rtab_dev && out_dev, JN_EINVAL, "jn_addact: null argument");
+  JN_CHECK(M >= 1 && M <= (1 << 24) && C >= 1 && glue_ld_ok(z_ld, C) && glue_ld_ok(res_ld, C) && glue_ld_ok(out_ld, C), JN_EINVAL,
+           "jn_addact: M=%lld, %d channels, leading dimensions %d, %d and %d", M, C, z_ld, res_ld, out_ld);
+  hipStream_t s = (hipStream_t)stream;
+  return glue_run("jn_addact", s, [&] {
+    return launch_addact(z_dev, z_ld, dw_tab(ztab_dev, C), res_dev, res_ld, dw_tab(rtab_dev, C), out_dev, out_ld, dtype, C, M, skip_flag_dev, skip_when, s);
+  });
+}
+
+int jn_bn_finalize(const double* stats_dev, long long rep_stride, double count, const float* gamma_dev, const float* beta_dev, float* run_mean_dev,
+                   float* run_var_dev, float* save_dev, float* tab0_dev, float* tab1_dev, int C, float eps, float momentum,
+                   const int* skip_flag_dev, int skip_when, void* stream) {
+  JN_CHECK(stats_dev && gamma_dev && beta_dev && tab0_dev, JN_EINVAL, "jn_bn_finalize: null argument");
+  JN_CHECK(C >= 1 && C <= 8192 && eps > 0.0f && momentum >= 0.0f && momentum <= 1.0f, JN_EINVAL, "jn_bn_finalize: C=%d eps=%g momentum=%g", C, eps,
+           momentum);
+  const ChanTab t0 = dw_tab(tab0_dev, C), t1 = tab1_dev ? dw_tab(tab1_dev, C) : ChanTab{};
+  hipStream_t s = (hipStream_t)stream;
+  return glue_run("jn_bn_finalize", s, [&] {
+    return launch_bn_finalize(stats_dev, rep_stride, count, gamma_dev, beta_dev, run_mean_dev, run_var_dev, save_dev, t0, t1, C, eps, momentum,
+                              skip_flag_dev, skip_when, s);
+  });
+}
+
+// (the kernel takes the running statistics as per-channel addresses, as the engine's parameter arena has them: built here from the
+// two dense arrays, so the call allocates, waits for the stream and frees)
+int jn_bn_finalize_all(const double* stats_dev, long long rep_stride, int n_stat, int N, const float* hw_dev, const int* goff_dev,
+                       const int* boff_dev, const float* params_dev, const int* t0_dev, const int* t1_dev, float* tab_dev, int tab_channels,
+                       float* save_dev, float* run_mean_dev, float* run_var_dev, float eps, float momentum, const int* skip_flag_dev, int skip_when,
+                       long long defer_max_m, void* stream) {
+  JN_CHECK(stats_dev && hw_dev && goff_dev && boff_dev && params_dev && t0_dev && t1_dev && tab_dev && save_dev && run_mean_dev && run_var_dev,
+           JN_EINVAL, "jn_bn_finalize_all: null argument");
+  JN_CHECK(n_stat >= 1 && n_stat <= (1 << 20) && N >= 1 && tab_channels >= 1 && rep_stride >= 2LL * n_stat && eps > 0.0f && momentum >= 0.0f &&
+               momentum <= 1.0f && defer_max_m >= 0,
+           JN_EINVAL, "jn_bn_finalize_all: %d channels, N=%d, table of %d, replicas %lld apart", n_stat, N, tab_channels, rep_stride);
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<float*> addr(2 * (size_t)n_stat);
+  for (int i = 0; i < n_stat; ++i) { addr[i] = run_mean_dev + i; addr[n_stat + i] = run_var_dev + i; }
+  float** addr_dev = nullptr;
+  JN_HIP(hipMalloc((void**)&addr_dev, addr.size() * sizeof(float*)));
+  hipError_t e = hipMemcpyAsync(addr_dev, addr.data(), addr.size() * sizeof(float*), hipMemcpyHostToDevice, s);
+  int rc = -1;
+  if (e == hipSuccess) {
+    BnAllArgs a{};
+    a.stats = stats_dev; a.rep_stride = rep_stride; a.n_stat = n_stat; a.N = N; a.hw = hw_dev; a.goff = goff_dev; a.boff = boff_dev;
+    a.params = params_dev; a.t0 = t0_dev; a.t1 = t1_dev; a.tab = tab_dev; a.tab_channels = tab_channels; a.save = save_dev;
+    a.run_mean = addr_dev; a.run_var = addr_dev + n_stat; a.eps = eps; a.momentum = momentum; a.skip_flag = skip_flag_dev;
+    a.skip_when = skip_when; a.defer_max_m = defer_max_m;
+    rc = launch_bn_finalize_all(a, s);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);      // (the address array was read from pageable memory before this returns)
+  (void)hipFree(addr_dev);
+  JN_HIP(e);
+  JN_CHECK(rc == 0, JN_EINVAL, "jn_bn_finalize_all: the launcher refused the arguments");
+  return JN_OK;
+}
+
+int jn_bn_bwd_sums(const float* g_dev, int g_ld, const float* z_dev, int z_ld, const float* tab_dev, const float* save_dev, int C, long long M,
+                   int n_slots, double* red_dev, const float* gamma_dev, const float* beta_dev, float* consts_dev, float* g_gamma_dev,
+                   float* g_beta_dev, int reduce, int raw_moment, void* stream) {
+  JN_CHECK(save_dev && red_dev && (!reduce || (g_dev && z_dev && tab_dev)), JN_EINVAL, "jn_bn_bwd_sums: null argument");
+  JN_CHECK(!consts_dev || (gamma_dev && beta_dev && g_gamma_dev && g_beta_dev), JN_EINVAL, "jn_bn_bwd_sums: consts need gamma, beta and their gradients");
+  JN_CHECK((reduce || consts_dev) && !(reduce && raw_moment), JN_EINVAL,
+           "jn_bn_bwd_sums: nothing to do, or a raw moment asked of the reduce kernel (it forms the moment against zhat)");
+  JN_CHECK(M >= 1 && M <= (1 << 24) && C >= 1 && C <= 8192 && n_slots >= 1 && n_slots <= 64 && (!reduce || (glue_ld_ok(g_ld, C) && glue_ld_ok(z_ld, C))),
+           JN_EINVAL, "jn_bn_bwd_sums: M=%lld, %d channels, leading dimensions %d and %d, %d slots", M, C, g_ld, z_ld, n_slots);
+  SlotBatch sb;      // the caller's [S, ...] tensors are slots already
+  sb.n = n_slots; sb.grad = M * g_ld; sb.act = M * z_ld; sb.tab = 3LL * C; sb.save = 2LL * C; sb.consts = 3LL * C; sb.red = (long long)JN_NREP * 2 * C;
+  hipStream_t s = (hipStream_t)stream;
+  return glue_run("jn_bn_bwd_sums", s, [&] {
+    int rc = reduce ? launch_bn_bwd_reduce(g_dev, g_ld, z_dev, z_ld, dw_tab(tab_dev, C), save_dev, C, M, red_dev, 2LL * C, s, sb) : 0;
+    if (rc == 0 && consts_dev)
+      rc = launch_bn_bwd_consts(red_dev, 2LL * C, (double)M, gamma_dev, beta_dev, save_dev, consts_dev, g_gamma_dev, g_beta_dev, C, s, sb, raw_moment ? 1 : 0);
+    return rc;
+  });
+}
+
+int jn_efpn_linear(const float* e_dev, const float* wt_dev, float* part_dev, int N, int K, int Co, int KS, const int* skip_flag_dev, int skip_when,
+                   void* stream) {
+  JN_CHECK(e_dev && wt_dev && part_dev, JN_EINVAL, "jn_efpn_linear: null argument");
+  JN_CHECK(N >= 1 && N <= 65535 && K >= 1 && K <= (1 << 24) && Co >= 1 && Co <= 4096 && KS >= 1 && KS <= 4096, JN_EINVAL,
+           "jn_efpn_linear: N=%d K=%d Co=%d KS=%d", N, K, Co, KS);
+  hipStream_t s = (hipStream_t)stream;
+  return glue_run("jn_efpn_linear", s, [&] { return launch_efpn_linear(e_dev, wt_dev, part_dev, N, K, Co, KS, skip_flag_dev, skip_when, s); });
+}
+
+}  // extern "C"

@@ -74,6 +74,9 @@ bool allow_lds(size_t bytes) {
   return true;
 }
 
+// The most dynamic LDS a launcher asks to be granted: the 160 KB of a gfx950 CU less room for a kernel's static arrays
+constexpr size_t JN_LDS_GRANT_MAX = 159 * 1024;
+
 // Persistent grids are sized in resident rounds: workgroups one CU holds x the CUs of the chip.
 constexpr int JN_NUM_CU = 256;
 // Workgroups (256 threads, `smem` bytes of dynamic LDS) of the kernel that fit one CU: asked once per kernel, whose LDS
@@ -128,7 +131,10 @@ struct DwPwArgs {
 };
 bool dwpw_supported(int C, int cout, int stride);
 int launch_dwpw(const DwPwArgs& a, hipStream_t s);
-int launch_stem(const StemArgs& a, hipStream_t s);
+// (max_wg, here and in launch_stem_bwd_weight: debug entry, > 0 caps the persistent workgroups along x, so that one walks
+// several tiles of a small batch.)  -1: an odd patch, output channels that are no whole blocks of 16, a null pointer
+int launch_stem(const StemArgs& a, hipStream_t s, int max_wg = 0);
+bool stem_args_ok(const StemArgs& a);
 bool stem_rows_aligned(const StemArgs& a);        // the stem kernels may fetch the image tile with 4-element loads
 // depthwise 3x3: the route of a launch (forced = 0: the launcher's rule; a forced route that does not admit the launch: -1)
 enum { DW_ROUTE_LDS = 1, DW_ROUTE_STRIP = 2 };      // dw3x3_lds_kernel (C % 16 == 0, N <= 65535), dw3x3_kernel
@@ -199,8 +205,13 @@ int launch_pw_x3_bwd_data(const ConvArgs& a, const float* w, void* w3t, hipStrea
 bool pw_x1_supported(const ConvArgs& a);               // bf16 inference mode: single-plane form of the same kernel
 int launch_pw_x1(const ConvArgs& a, hipStream_t s, int max_wg = 0);               // shapes on which the x3 kernel is the faster one
 void launch_w_split3(const float* w, void* w3, long long n_floats, hipStream_t s);   // w3: 6 bytes per weight
+// SPP: the route of a launch (forced = 0: the launchers' rule; a forced route that does not admit the launch: -1), pure host
+// code; bwd = the backward pair of kernels.  The launchers return -1 where spp_route does, and for a null pointer.
+enum { SPP_ROUTE_QUAD = 1, SPP_ROUTE_SCALAR = 2 };      // spp4_kernel / spp4_bwd_kernel; spp_kernel / spp_bwd_kernel
+int spp_route(int dtype, int ld, int h, int H, int W, int N, int bwd, int forced);
+int spp_scalar_channels(int H, int W, int bwd);         // channels per workgroup of the scalar kernels
 int launch_spp(void* cat, int dtype, int ld, int h, int H, int W, int N, ChanTab it, const int* skip_flag,
-               int skip_when, hipStream_t s);
+               int skip_when, hipStream_t s, int route = 0);
 int launch_upsample(const void* in, int in_ld, void* out, int out_ld, int dtype, int C, int H, int W, int N,
                     const int* skip_flag, int skip_when, hipStream_t s);
 int launch_addact(const void* z, int z_ld, ChanTab zt, const void* res, int res_ld, ChanTab rt, void* out, int out_ld,
@@ -346,9 +357,10 @@ int launch_dw_bwd_weight(const float* gz, int g_ld, const float* x, int x_ld, Ch
                          int max_wg = 0);      // debug entry: > 0 caps the workgroups per slot
 // gz is d loss / d activation of the stem's output z: the BN + SiLU backward (g_z) is applied while staging
 int launch_stem_bwd_weight(const StemArgs& a, const float* gz, int g_ld, float* gw, float* wpart, hipStream_t s,
-                           const SlotBatch& sb, const float* z, int z_ld, ChanTab ot, const float* save, const float* consts);
+                           const SlotBatch& sb, const float* z, int z_ld, ChanTab ot, const float* save, const float* consts,
+                           int max_wg = 0);
 int launch_spp_bwd(const float* cat, float* gcat, int ld, int h, int H, int W, int N, ChanTab it, hipStream_t s,
-                   const SlotBatch& sb = SlotBatch{});
+                   const SlotBatch& sb = SlotBatch{}, int route = 0);
 int launch_upsample_bwd(const float* gdst, int dst_ld, float* gsrc, int src_ld, int C, int H, int W, int N,
                         int accumulate, hipStream_t s, const SlotBatch& sb = SlotBatch{});
 int launch_grad_copy(const float* src, int src_ld, float* dst, int dst_ld, int C, long long M, int accumulate,

@@ -82,7 +82,11 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
 
 int launch_bn_bwd_reduce(const float* g, int g_ld, const float* z, int z_ld, ChanTab t, const float* save, int C,
                          long long M, double* red_out, long long rep_stride, hipStream_t s, const SlotBatch& sb) {
-  const int rstep = 256 / (C / 4) > 0 ? 256 / (C / 4) : 1;
+  // (C <= 1024: a thread owns a channel quad, and above 256 quads no thread of the workgroup would be active)
+  if (!g || !z || !t.sc || !t.sh || !save || !red_out || C < 4 || C % 4 || C > 1024 || M < 1 || g_ld < C || z_ld < C || rep_stride < 2LL * C ||
+      sb.n < 1 || sb.n > 65535)
+    return -1;
+  const int rstep = 256 / (C / 4);
   const int rows_per_block = rstep * 32;
   const dim3 grid((unsigned)((M + rows_per_block - 1) / rows_per_block), sb.n);
   hipLaunchKernelGGL(bn_bwd_reduce_kernel, grid, dim3(256), (size_t)2 * C * sizeof(float), s, g, g_ld, z, z_ld, t, save, C, M,
@@ -122,6 +126,9 @@ __global__ void bn_bwd_consts_kernel(const double* __restrict__ red, long long r
 int launch_bn_bwd_consts(const double* red, long long rep_stride, double count, const float* gamma, const float* beta,
                          const float* save, float* consts, float* g_gamma, float* g_beta, int C, hipStream_t s, const SlotBatch& sb,
                          int raw_moment) {
+  if (!red || !gamma || !beta || !save || !consts || !g_gamma || !g_beta || C < 1 || !(count >= 1.0) || rep_stride < 2LL * C || sb.n < 1 ||
+      sb.n > 65535)
+    return -1;
   hipLaunchKernelGGL(bn_bwd_consts_kernel, dim3((C + 63) / 64, sb.n), dim3(64), 0, s, red, rep_stride, count, gamma, beta, save,
                      consts, g_gamma, g_beta, C, sb, raw_moment);
   return 0;
@@ -776,12 +783,16 @@ __global__ __launch_bounds__(256) void stem_bwd_weight_kernel(
 
 int launch_stem_bwd_weight(const StemArgs& a, const float* gz, int g_ld, float* gw, float* wpart, hipStream_t s,
                            const SlotBatch& sb, const float* z, int z_ld, ChanTab ot, const float* save,
-                           const float* consts) {
+                           const float* consts, int max_wg) {
+  if (!stem_args_ok(a) || !gz || !gw || !wpart || g_ld < a.cout || g_ld % 4 || 108 * a.cout > JN_WPART_MAX || sb.n < 1 || sb.n > 65535 || max_wg < 0)
+    return -1;
+  if (z && (!ot.sc || !ot.sh || !save || !consts || z_ld < a.cout || z_ld % 4)) return -1;
   const int OH = a.P / 2, ocg = a.cout / 16;
   const int tiles_x = (OH + SB_TX - 1) / SB_TX, tiles_y = (OH + SB_TY - 1) / SB_TY;
   const int n_tiles = tiles_x * tiles_y * a.N;
   const int cap = sb.n >= 4 ? 256 : 1024 / sb.n;
   dim3 grid(n_tiles < cap ? n_tiles : cap, ocg, sb.n);
+  if (max_wg > 0 && grid.x > (unsigned)max_wg) grid.x = max_wg;      // debug entry: a workgroup walks several tiles of a small batch
 #define JN_STEMB(V_, ST_)                                                                                                 \
   hipLaunchKernelGGL((stem_bwd_weight_kernel<V_, ST_>), grid, dim3(256), 0, s, (const ST_*)a.src, (const long long*)a.positions, \
                      a.pos_stride, a.sample_stride, a.chan_stride, a.row_stride, a.P, gz, g_ld, a.cout, ocg, tiles_x, tiles_y, \
@@ -972,18 +983,20 @@ __global__ __launch_bounds__(256) void spp4_bwd_kernel(const float* __restrict__
 }
 
 int launch_spp_bwd(const float* cat, float* gcat, int ld, int h, int H, int W, int N, ChanTab it, hipStream_t s,
-                   const SlotBatch& sb) {
-  if (h % 16 == 0 && ld % 4 == 0 && H * W * 4 <= 2048) {
+                   const SlotBatch& sb, int route) {
+  if (!cat || !gcat || !it.sc || !it.sh || !it.fl || sb.n < 1 || sb.n > 65535) return -1;
+  route = spp_route(JN_F32, ld, h, H, W, N, 1, route);
+  if (route < 0) return -1;
+  if (route == SPP_ROUTE_QUAD) {
     const size_t smem4 = (size_t)H * W * 4 * 16 * sizeof(float);        // at most 128 KB (H * W <= 512)
     if (!allow_lds<&spp4_bwd_kernel<4>>(smem4)) return -1;
     hipLaunchKernelGGL(spp4_bwd_kernel<4>, dim3(h / 16, N, sb.n), dim3(256), smem4, s, cat, gcat, ld, h, H, W, it, sb);
     return 0;
   }
-  const int cb0 = 8;   // channels per workgroup, measured at B = 64, 20 steps: 16: 1068 us, 8: 847 us, 4: 888 us
-  int cb = cb0;
-  while (cb > 4 && (size_t)H * W * cb * 4 * sizeof(float) > 60 * 1024) cb >>= 1;
+  const int cb = spp_scalar_channels(H, W, 1);
   dim3 grid(h / cb, N, sb.n);
   const size_t smem = (size_t)H * W * cb * 4 * sizeof(float);
+  if (!allow_lds<&spp_bwd_kernel>(smem)) return -1;
   hipLaunchKernelGGL(spp_bwd_kernel, grid, dim3(256), smem, s, cat, gcat, ld, h, H, W, cb, it, sb);
   return 0;
 }
@@ -1014,6 +1027,9 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const float* __restri
 
 int launch_upsample_bwd(const float* gdst, int dst_ld, float* gsrc, int src_ld, int C, int H, int W, int N,
                         int accumulate, hipStream_t s, const SlotBatch& sb) {
+  if (!gdst || !gsrc || C < 4 || C % 4 || H < 1 || W < 1 || N < 1 || dst_ld < C || dst_ld % 4 || src_ld < C || src_ld % 4 || sb.n < 1 ||
+      sb.n > 65535)
+    return -1;
   const long long total = (long long)N * H * W * (C / 4);
   hipLaunchKernelGGL(upsample_bwd_kernel, dim3((unsigned)((total + 255) / 256), sb.n), dim3(256), 0, s, gdst, dst_ld, gsrc,
                      src_ld, C, H, W, total, accumulate, sb.grad);
@@ -1037,6 +1053,7 @@ __global__ __launch_bounds__(256) void grad_copy_kernel(const float* __restrict_
 
 int launch_grad_copy(const float* src, int src_ld, float* dst, int dst_ld, int C, long long M, int accumulate,
                      hipStream_t s, const SlotBatch& sb) {
+  if (!src || !dst || C < 4 || C % 4 || M < 1 || src_ld < C || src_ld % 4 || dst_ld < C || dst_ld % 4 || sb.n < 1 || sb.n > 65535) return -1;
   const long long total = M * (C / 4);
   hipLaunchKernelGGL(grad_copy_kernel, dim3((unsigned)((total + 255) / 256), sb.n), dim3(256), 0, s, src, src_ld, dst, dst_ld,
                      C, M, accumulate, sb.grad);

@@ -183,13 +183,14 @@ bool stem_rows_aligned(const StemArgs& a) {
 }
 
 template <typename OT, bool VEC, typename ST>
-static void launch_stem_t(const StemArgs& a, hipStream_t s) {
+static void launch_stem_t(const StemArgs& a, hipStream_t s, int max_wg) {
   const int OH = a.P / 2;
   const int ocg = a.cout / 16;
   const int tiles_x = (OH + ST_TX - 1) / ST_TX, tiles_y = (OH + ST_TY - 1) / ST_TY, n_tiles = tiles_x * tiles_y * a.N;
   int nwg = 2 * JN_NUM_CU / ocg;                       // 2 persistent workgroups per CU (222 VGPRs)
   if (nwg < 1) nwg = 1;
   if (nwg > n_tiles) nwg = n_tiles;
+  if (max_wg > 0 && nwg > max_wg) nwg = max_wg;        // debug entry: a workgroup walks several tiles of a small batch
   hipLaunchKernelGGL((stem_mfma_kernel<OT, VEC, ST>), dim3(nwg, ocg), dim3(256), 0, s, (const ST*)a.src, (const long long*)a.positions,
                      a.pos_stride, a.sample_stride, a.chan_stride, a.row_stride, a.P, a.w, (OT*)a.out, a.out_ld, a.cout,
                      tiles_x, tiles_y, n_tiles, a.stats, a.stats_rep_stride, a.skip_flag, a.skip_when,
@@ -197,13 +198,21 @@ static void launch_stem_t(const StemArgs& a, hipStream_t s) {
 }
 
 template <typename OT, typename ST>
-static void launch_stem_v(const StemArgs& a, hipStream_t s) {
-  if (stem_rows_aligned(a)) launch_stem_t<OT, true, ST>(a, s); else launch_stem_t<OT, false, ST>(a, s);
+static void launch_stem_v(const StemArgs& a, hipStream_t s, int max_wg) {
+  if (stem_rows_aligned(a)) launch_stem_t<OT, true, ST>(a, s, max_wg); else launch_stem_t<OT, false, ST>(a, s, max_wg);
 }
 
-int launch_stem(const StemArgs& a, hipStream_t s) {
-  if (a.src_u8) { if (a.out_dtype == JN_BF16) launch_stem_v<bf16_t, uint8_t>(a, s); else launch_stem_v<float, uint8_t>(a, s); }
-  else { if (a.out_dtype == JN_BF16) launch_stem_v<bf16_t, float>(a, s); else launch_stem_v<float, float>(a, s); }
+// What both stem launchers ask of a launch: the Focus slicing needs an even patch, a workgroup owns 16 output channels
+bool stem_args_ok(const StemArgs& a) {
+  return a.src && a.w && a.P >= 2 && a.P % 2 == 0 && a.N >= 1 && a.cout >= 16 && a.cout % 16 == 0 && (!a.positions || a.pos_stride >= 2) &&
+         a.row_stride >= 1 && a.chan_stride >= 1 && (long long)a.N * (a.P / 2) * (a.P / 2) <= (1LL << 28);
+}
+
+int launch_stem(const StemArgs& a, hipStream_t s, int max_wg) {
+  if (!stem_args_ok(a) || !a.out || a.out_ld < a.cout || a.out_ld % 4 || max_wg < 0) return -1;
+  if (a.stats && (a.stats_nrep < 0 || a.stats_nrep > JN_NREP || a.stats_rep_stride < 2LL * a.cout)) return -1;
+  if (a.src_u8) { if (a.out_dtype == JN_BF16) launch_stem_v<bf16_t, uint8_t>(a, s, max_wg); else launch_stem_v<float, uint8_t>(a, s, max_wg); }
+  else { if (a.out_dtype == JN_BF16) launch_stem_v<bf16_t, float>(a, s, max_wg); else launch_stem_v<float, float>(a, s, max_wg); }
   return 0;
 }
 
@@ -1289,21 +1298,50 @@ __global__ __launch_bounds__(256) void spp4_kernel(float* __restrict__ cat, int 
   }
 }
 
+// Channels per workgroup of the scalar kernels: 8 (forward: 1024 workgroups at B = 64, measured 40.9 us with 32 or 16, 31.9 us
+// with 8; backward, B = 64, 20 steps: 16: 1068 us, 8: 847 us, 4: 888 us), 4 where the LDS of 8 passes `soft` bytes
+static int spp_scalar_cb(long long HW, int bytes_per_elem, size_t soft) {
+  int cb = 8;
+  while (cb > 4 && (size_t)HW * cb * bytes_per_elem > soft) cb >>= 1;
+  return cb;
+}
+
+// The route of an SPP launch, pure host code (forced = 0: the launchers' rule; else that route where the launch meets its
+// preconditions); -1: refused.  Quad: fp32, whole blocks of 16 channels, 16-byte aligned pixels, a map within the 2048
+// elements its threads cover and, forward, within the 64 KB of LDS it asks for without a grant (H * W <= 510; 128 bytes of
+// dynamic LDS per pixel beside its static table).  Scalar: whole blocks of its 8 (4) channels, its LDS within what a
+// workgroup can be granted.  Either: one image per grid row.
+int spp_route(int dtype, int ld, int h, int H, int W, int N, int bwd, int forced) {
+  if (h < 1 || H < 1 || W < 1 || N < 1 || N > 65535 || ld < 4 * h || forced < 0 || forced > SPP_ROUTE_SCALAR) return -1;
+  if ((long long)H * W > (1 << 20) || (bwd && dtype != JN_F32)) return -1;
+  const long long HW = (long long)H * W;
+  const bool quad = dtype == JN_F32 && h % 16 == 0 && ld % 4 == 0 &&
+                    (bwd ? HW * 4 <= 2048 : (size_t)HW * 4 * 2 * sizeof(f32x4) + 3 * 4 * 4 * sizeof(float) <= 64 * 1024);
+  if (forced == SPP_ROUTE_QUAD || (forced == 0 && quad)) return quad ? SPP_ROUTE_QUAD : -1;
+  const int cb = bwd ? spp_scalar_cb(HW, 4 * sizeof(float), 60 * 1024) : spp_scalar_cb(HW, 2 * sizeof(float), 48 * 1024);
+  const size_t smem = (size_t)HW * cb * (bwd ? 4 : 2) * sizeof(float);
+  if (h % cb != 0 || smem > JN_LDS_GRANT_MAX) return -1;
+  return SPP_ROUTE_SCALAR;
+}
+
+int spp_scalar_channels(int H, int W, int bwd) {
+  return bwd ? spp_scalar_cb((long long)H * W, 4 * sizeof(float), 60 * 1024) : spp_scalar_cb((long long)H * W, 2 * sizeof(float), 48 * 1024);
+}
+
 int launch_spp(void* cat, int dtype, int ld, int h, int H, int W, int N, ChanTab it, const int* skip_flag,
-               int skip_when, hipStream_t s) {
-  // spp4_kernel<4>: 128 bytes of dynamic LDS per pixel beside its static table tb[]; together within the 64 KB a kernel
-  // may use without a grant (H * W <= 510, inside the 2048 elements its threads cover).  Larger maps: spp_kernel
-  const size_t smem4 = (size_t)H * W * 4 * 2 * sizeof(f32x4), tb4 = 3 * 4 * 4 * sizeof(float);
-  if (dtype == JN_F32 && h % 16 == 0 && ld % 4 == 0 && smem4 + tb4 <= 64 * 1024) {
+               int skip_when, hipStream_t s, int route) {
+  if (!cat || !it.sc || !it.sh || !it.fl || (dtype != JN_F32 && dtype != JN_BF16)) return -1;
+  route = spp_route(dtype, ld, h, H, W, N, 0, route);
+  if (route < 0) return -1;
+  if (route == SPP_ROUTE_QUAD) {
+    const size_t smem4 = (size_t)H * W * 4 * 2 * sizeof(f32x4);
     hipLaunchKernelGGL(spp4_kernel<4>, dim3(h / 16, N), dim3(256), smem4, s, (float*)cat, ld, h, H, W, it, skip_flag, skip_when);
     return 0;
   }
-  // channels per block: 2 * HW * cb floats of LDS; 8 -> 1024 workgroups at B = 64 (measured 40.9 us with 32 or 16, 31.9 us with 8)
-  const int cb0 = 8;
-  int cb = cb0 > 64 ? 64 : cb0;
-  while (cb > 4 && (size_t)H * W * cb * 2 * sizeof(float) > 48 * 1024) cb >>= 1;
+  const int cb = spp_scalar_channels(H, W, 0);
   dim3 grid(h / cb, N);
   const size_t smem = (size_t)H * W * cb * 2 * sizeof(float);
+  if (dtype == JN_BF16 ? !allow_lds<&spp_kernel<bf16_t>>(smem) : !allow_lds<&spp_kernel<float>>(smem)) return -1;
   if (dtype == JN_BF16)
     hipLaunchKernelGGL(spp_kernel<bf16_t>, grid, dim3(256), smem, s, (bf16_t*)cat, ld, h, H, W, cb, it, skip_flag, skip_when);
   else
@@ -1331,7 +1369,11 @@ __global__ __launch_bounds__(256) void upsample_kernel(const AT* __restrict__ in
 
 int launch_upsample(const void* in, int in_ld, void* out, int out_ld, int dtype, int C, int H, int W, int N,
                     const int* skip_flag, int skip_when, hipStream_t s) {
+  if (!in || !out || C < 4 || C % 4 || H < 1 || W < 1 || N < 1 || in_ld < C || in_ld % 4 || out_ld < C || out_ld % 4 ||
+      (dtype != JN_F32 && dtype != JN_BF16))
+    return -1;
   const long long total = (long long)N * 4 * H * W * (C / 4);
+  if ((total + 255) / 256 > 0x7fffffffLL) return -1;
   const dim3 grid((unsigned)((total + 255) / 256));
   if (dtype == JN_BF16)
     hipLaunchKernelGGL(upsample_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)in, in_ld, (bf16_t*)out, out_ld, C, H,
@@ -1369,6 +1411,9 @@ __global__ __launch_bounds__(256) void addact_kernel(const AT* __restrict__ z, i
 
 int launch_addact(const void* z, int z_ld, ChanTab zt, const void* res, int res_ld, ChanTab rt, void* out, int out_ld,
                   int dtype, int C, long long M, const int* skip_flag, int skip_when, hipStream_t s) {
+  if (!z || !res || !out || !zt.sc || !zt.sh || !zt.fl || !rt.sc || !rt.sh || !rt.fl || C < 4 || C % 4 || C > 2048 || M < 1 || z_ld < C ||
+      res_ld < C || out_ld < C || z_ld % 4 || res_ld % 4 || out_ld % 4 || (dtype != JN_F32 && dtype != JN_BF16))
+    return -1;      // (C <= 2048: the two tables, 24 bytes per channel, within 48 KB of LDS)
   const long long total = M * (C / 4);
   const dim3 grid((unsigned)std::min<long long>((total + 255) / 256, 4096));      // (512 ... 4096 workgroups: no difference, measured)
   const size_t smem = (size_t)6 * C * sizeof(float);
@@ -1427,6 +1472,9 @@ __global__ void bn_finalize_kernel(const double* __restrict__ stats, long long r
 int launch_bn_finalize(const double* stats, long long rep_stride, double count, const float* gamma, const float* beta, float* run_mean,
                        float* run_var, float* save, ChanTab t0, ChanTab t1, int C, float eps, float momentum,
                        const int* skip_flag, int skip_when, hipStream_t s) {
+  if (!stats || !gamma || !beta || !t0.sc || !t0.sh || !t0.fl || C < 1 || !(count >= 1.0) || rep_stride < 2LL * C || (!run_mean != !run_var) ||
+      (t1.sc && (!t1.sh || !t1.fl)))
+    return -1;
   hipLaunchKernelGGL(bn_finalize_kernel, dim3((8 * C + 255) / 256), dim3(256), 0, s, stats, rep_stride, count, gamma, beta, run_mean,
                      run_var,
                      save, t0, t1, C, eps, momentum, skip_flag, skip_when);
@@ -1460,6 +1508,9 @@ __global__ __launch_bounds__(256) void bn_finalize_all_kernel(BnAllArgs a) {
 }
 
 int launch_bn_finalize_all(const BnAllArgs& a, hipStream_t s) {
+  if (!a.stats || !a.hw || !a.goff || !a.boff || !a.params || !a.t0 || !a.t1 || !a.tab || !a.save || !a.run_mean || !a.run_var ||
+      a.n_stat < 1 || a.N < 1 || a.tab_channels < 1 || a.rep_stride < 2LL * a.n_stat)
+    return -1;
   hipLaunchKernelGGL(bn_finalize_all_kernel, dim3((a.n_stat + 255) / 256), dim3(256), 0, s, a);
   return 0;
 }
@@ -1574,12 +1625,15 @@ __global__ __launch_bounds__(256) void efpn_linear_mfma_kernel(const float* __re
 
 int launch_efpn_linear(const float* e, const float* wt, float* part, int N, int K, int Co, int KS,
                        const int* skip_flag, int skip_when, hipStream_t s) {
+  if (!e || !wt || !part || N < 1 || K < 1 || Co < 1 || KS < 1 || KS > 65535) return -1;
   if (Co % 16 == 0 && K % 4 == 0) {
+    if ((N + 63) / 64 > 65535) return -1;
     const int kper = ((K + KS - 1) / KS + 3) / 4 * 4;
     dim3 grid(KS, (N + 63) / 64, (Co + 47) / 48);
     hipLaunchKernelGGL(efpn_linear_mfma_kernel, grid, dim3(256), 0, s, e, wt, part, N, K, Co, KS, kper, skip_flag, skip_when);
     return 0;
   }
+  if (Co > 256 || N > 65535) return -1;      // the scalar form: a thread per output, 256 / Co k-slices per workgroup
   dim3 grid(KS, N);
   const size_t smem = (size_t)(256 / Co) * Co * sizeof(float);
   hipLaunchKernelGGL(efpn_linear_kernel, grid, dim3(256), smem, s, e, wt, part, K, Co, KS, skip_flag, skip_when);
