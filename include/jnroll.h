@@ -437,12 +437,40 @@ int jn_reinforce_step(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev,
 /* Autograd bridge (SURVEY.md 8b "Ownership": in training, rollout's logprobs / entropies carry a graph).  The reference
  * differentiates a loss built from the rollout dict (src/reinforce.py:326-341: rollout -> compute_metrics ->
  * (loss / ga).backward()).  jn_reinforce_forward is the train-mode rollout alone (batch-statistics BatchNorm, every
- * step's activations kept resident); jn_reinforce_backward is the backward of that rollout for GIVEN d loss / d logprobs
+ * step's activations kept resident, or a ring of them under jn_set_activation_slots); jn_reinforce_backward is the backward of that rollout for GIVEN d loss / d logprobs
  * and d loss / d entropies ([B, T] f32, either may be NULL = zero): what a torch.autograd.Function around the rollout
  * receives.  Parameter gradients ACCUMULATE in the gradient arena.  jn_reinforce_backward synchronises once (step count). */
 int jn_reinforce_forward(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const int64_t* start_positions_dev,
                          uint64_t seed, int stop_early, const jn_rollout_out* out, void* stream);
 int jn_reinforce_backward(jn_ctx* ctx, const float* dlogprobs_dev, const float* dentropies_dev, void* stream);
+/* Walks that do not fit: activation replay (opt-in).  By default a train-mode rollout of the patch encoder keeps one full
+ * workspace slot per glimpse step (activations of every layer at max_batch) until its backward.  With n >= 1 it keeps a
+ * ring of n activation slots besides slot 0 and only the small per-step state of every step (BatchNorm tables, saved
+ * mean / invstd, fp64 batch sums, the staged view columns, embed_fpn's activations); the backward walks the trajectory in
+ * chunks of min(n, gradient slots) steps and re-runs the forward of a chunk from the kept statistics, bit for bit, just
+ * before that chunk's backward (no BatchNorm finalize, no running-statistics update: those happened once, in the
+ * rollout).  n = 0 (default): one activation slot per step, nothing is replayed.  A rollout of T <= n steps takes the
+ * default path unchanged.  n < 0: JN_EINVAL.  The setter makes the state of an earlier train-mode rollout stale:
+ * jn_reinforce_backward after it fails with JN_ESTATE until a new jn_reinforce_forward / jn_reinforce_step has run.  With a
+ * detached encoder (no gpt_backbone: the detector's PAFPN encodes the patches and gets no policy gradient) there is no
+ * encoder backward: the switch is accepted and has no effect.  The supervised step (one slot of B*T patches) is not
+ * covered. */
+int jn_set_activation_slots(jn_ctx* ctx, int n);
+/* What a net's workspace holds now: activation slots and table slots (equal unless a ring is in use), the bytes of one
+ * activation slot at max_batch, and how many glimpse steps the most recent REINFORCE backward replayed (0 for a net
+ * that is not the patch encoder).  Any output may be NULL. */
+int jn_activation_slots_info(const jn_ctx* ctx, int net, int* act_slots, int* table_slots, size_t* slot_bytes, int* replayed_steps);
+/* The chunks in which the encoder's backward walks S executed glimpse steps, in the order it runs them (host rule, no
+ * device; the backward itself calls it): chunk i covers steps t0[i] .. t0[i] + n[i] - 1, every chunk has min(act_slots,
+ * g_slots) steps and the last one the rest.  act_slots = 0: every step is resident, chunks of g_slots steps, no replay.
+ * Writes at most `cap` chunks and returns their number (which may exceed cap); JN_EINVAL: S < 0, act_slots < 0,
+ * g_slots < 1. */
+int jn_replay_chunks(int S, int act_slots, int g_slots, int* t0, int* n, int cap);
+/* Debug entry of the replay: after a train-mode rollout under n = 0 (every step resident) re-runs glimpse step `step`
+ * (< the executed steps) into activation slot 0 and counts the 32-bit words, over the first B patches of every buffer of
+ * the patch encoder, in which the replay differs from the resident slot of that step: *n_diff, 0 = bit for bit.
+ * Overwrites the eval workspace (a pending jn_supervised_backward is refused afterwards).  Synchronises. */
+int jn_debug_replay_diff(jn_ctx* ctx, int step, long long* n_diff, void* stream);
 /* The arena keeps tensors in kernel-friendly layouts (transposed Linear weights, tap-major conv weights, ...).  These
  * convert, ON THE DEVICE, between the arena and a caller-owned buffer of >= arena floats that holds every trainable
  * tensor in the reference's (PyTorch) layout at the SAME offset as in the arena (jn_arena_segment): the Python module's

@@ -212,6 +212,11 @@ SIGNATURES = {
     "jn_reinforce_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int,
                                        C.POINTER(JnRolloutOut), C.c_void_p]),
     "jn_reinforce_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "jn_set_activation_slots": (C.c_int, [C.c_void_p, C.c_int]),
+    "jn_activation_slots_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t),
+                                           C.POINTER(C.c_int)]),
+    "jn_replay_chunks": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
+    "jn_debug_replay_diff": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.c_void_p]),
     "jn_arena_segment": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "jn_export_arena": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "jn_import_arena": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),

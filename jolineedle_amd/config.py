@@ -165,7 +165,8 @@ def model_config(**kw):
     cfg = dict(model_type="gpt-nano", n_layer=None, n_head=None, n_embd=None, block_size=20, patch_size=448,
                image_processor="yolox-s", gpt_backbone="yolox-nano", use_pos_emb=True, no_patch_emb=False,
                concat_emb=True, decoder_pos_encoding=True, pos_emb_size=25, dropout=0.0,
-               detector_conf_threshold=0.5, no_recurrent_embedding=False, with_detector=True, nclasses=9)
+               detector_conf_threshold=0.5, no_recurrent_embedding=False, with_detector=True, nclasses=9,
+               activation_slots=0)
     cfg.update(kw)
     n = cfg.pop("nclasses")
     cfg["actions_info"] = [ActionInfo("categorical", n)]

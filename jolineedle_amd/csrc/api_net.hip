@@ -26,6 +26,21 @@ __global__ void fill_kernel(float* p, float v, long long n) {
   if (i < n) p[i] = v;
 }
 
+// *total += the number of 32-bit words in which a and b differ (grid-stride; a workgroup adds its count once)
+extern "C"
+__global__ __launch_bounds__(256) void word_diff_kernel(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, long long n,
+                                                        unsigned long long* __restrict__ total) {
+  __shared__ unsigned int wg_count;
+  if (threadIdx.x == 0) wg_count = 0;
+  __syncthreads();
+  unsigned int c = 0;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) c += a[i] != b[i] ? 1u : 0u;
+  for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(&wg_count, c);
+  __syncthreads();
+  if (threadIdx.x == 0 && wg_count) atomicAdd(total, (unsigned long long)wg_count);
+}
+
 // finishes the split-K sums: out[n][c] = bias[c] + sum_ks part[n][ks][c]
 extern "C"
 __global__ void emb_finish_kernel(const float* __restrict__ part, const float* __restrict__ bias, float* __restrict__ out,
@@ -77,8 +92,6 @@ static bool defer_tab_runs(const Net& net, const View& v, int N, ChanTab& t) {
   return true;
 }
 
-static inline float* slot_save(const Net& net, int slot) { return net.save + (size_t)slot * 2 * net.stat_channels; }
-
 // N plain patches [n][3][P][P] (no positions), sample_stride elements apart (0: back to back)
 StemSrc patch_src(const void* ptr, int P, long long sample_stride) {
   return StemSrc{ptr, nullptr, sample_stride ? sample_stride : 3LL * P * P, (long long)P * P, P};
@@ -86,29 +99,38 @@ StemSrc patch_src(const void* ptr, int P, long long sample_stride) {
 
 // Allocates (or grows to) n_slots workspace slots of a net; tables start as identity
 // (scale 1, shift 0, flag 0 = "already an activation").
-int ensure_slots(jn_ctx* ctx, Net& net, int n_slots) {
-  if (net.n_slots >= n_slots) return JN_OK;
+// The activations get a_slots slots of their own (default: as many).  Either count only grows, and a call that grows
+// neither allocates nothing.
+int ensure_slots(jn_ctx* ctx, Net& net, int n_slots, int a_slots) {
+  if (a_slots < 0) a_slots = n_slots;
+  const bool grow_tab = net.n_slots < n_slots, grow_act = net.a_slots < a_slots;
+  if (!grow_tab && !grow_act) return JN_OK;
   const int MB = ctx->cfg.max_batch;
-  float *tab = nullptr, *save = nullptr;
-  double* stats = nullptr;
-  char* act = nullptr;
+  float *tab = net.tab, *save = net.save;
+  double* stats = net.stats;
+  char* act = net.act;
   int rc;
-  if ((rc = dev_alloc(ctx, &act, (size_t)n_slots * net.per_image_floats * MB * act_esz(net)))) return rc;
-  if ((rc = dev_alloc(ctx, &tab, (size_t)n_slots * 3 * net.tab_channels))) return rc;
-  if ((rc = dev_alloc(ctx, &save, (size_t)n_slots * 2 * net.stat_channels))) return rc;
-  if ((rc = dev_alloc(ctx, &stats, (size_t)n_slots * JN_NREP * 2 * net.stat_channels))) return rc;
+  if (grow_act && (rc = dev_alloc(ctx, &act, (size_t)a_slots * net.per_image_floats * MB * act_esz(net)))) return rc;
+  if (grow_tab) {
+    if ((rc = dev_alloc(ctx, &tab, (size_t)n_slots * 3 * net.tab_channels))) return rc;
+    if ((rc = dev_alloc(ctx, &save, (size_t)n_slots * 2 * net.stat_channels))) return rc;
+    if ((rc = dev_alloc(ctx, &stats, (size_t)n_slots * JN_NREP * 2 * net.stat_channels))) return rc;
+  }
   // old (smaller) allocations stay owned by the context until jn_destroy; slots are grown once per config.  What the
   // old slots hold moves along (a detector pass may need its slot AFTER a train-mode rollout filled the encoder's, and
   // the rollout's backward still reads them: the reference's statement order, src/reinforce.py:326-341)
-  const int n_old = net.n_slots;
-  if (n_old > 0) {
-    JN_HIP(hipDeviceSynchronize());
-    JN_HIP(hipMemcpy(act, net.act, (size_t)n_old * net.per_image_floats * MB * act_esz(net), hipMemcpyDeviceToDevice));
+  const int n_old = net.n_slots, a_old = net.a_slots;
+  if (n_old > 0 || a_old > 0) JN_HIP(hipDeviceSynchronize());
+  if (grow_act && a_old > 0)
+    JN_HIP(hipMemcpy(act, net.act, (size_t)a_old * net.per_image_floats * MB * act_esz(net), hipMemcpyDeviceToDevice));
+  if (grow_tab && n_old > 0) {
     JN_HIP(hipMemcpy(tab, net.tab, (size_t)n_old * 3 * net.tab_channels * sizeof(float), hipMemcpyDeviceToDevice));
     JN_HIP(hipMemcpy(save, net.save, (size_t)n_old * 2 * net.stat_channels * sizeof(float), hipMemcpyDeviceToDevice));
     JN_HIP(hipMemcpy(stats, net.stats, (size_t)n_old * JN_NREP * 2 * net.stat_channels * sizeof(double), hipMemcpyDeviceToDevice));
   }
-  net.act = act; net.tab = tab; net.save = save; net.stats = stats; net.n_slots = n_slots;
+  net.act = act; net.a_slots = std::max(a_old, a_slots);
+  if (!grow_tab) return JN_OK;
+  net.tab = tab; net.save = save; net.stats = stats; net.n_slots = n_slots;
   for (int sl = n_old; sl < n_slots; ++sl) {
     float* t = tab + (size_t)sl * 3 * net.tab_channels;
     const long long n = net.tab_channels;
@@ -293,19 +315,35 @@ static StemArgs stem_args(const StemSrc& ss, const Net& net, int N, const ConvW&
 // One pass of a PAFPN over N patches in workspace slot `slot`.  train != 0: batch-statistics
 // BatchNorm (stats accumulated by every conv, finalised per layer, running stats updated).
 // The routes come from plan_forward (plan.cpp); what depends on launch-time state stays here.
+// The activations go to slot `slot`, tables / saved statistics / sums to table slot tab_slot (< 0: the same slot).
+// mode RUN_REPLAY: the train-mode pass that filled table slot tab_slot once more, into activation slot `slot`, from what
+// that slot kept: the same plan, kernels and instantiations; consumers of deferred tables read the kept sums, the others
+// the kept table; the producers add their sums to a sink nobody reads (the accumulating instantiations, so that no
+// element rounds differently); no finalize launch, no running-statistics update, no write to `save`.  Every conv has one
+// writer per element, so the slot comes out bit for bit.  Of the validity flags only the eval workspace's (slot 0) moves.
 int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int train, const int* skip_flag, int skip_when,
-            hipStream_t s, bool with_head, int first_op) {
+            hipStream_t s, bool with_head, int first_op, int tab_slot, RunMode mode) {
   Net& net = ctx->nets[ni];
   const int MB = ctx->cfg.max_batch;
+  const bool replay = mode == RUN_REPLAY;
+  const int ts = tab_slot < 0 ? slot : tab_slot;
   int rc;
-  invalidate_slot_state(ctx, ni, slot);
+  JN_CHECK(slot >= 0 && slot < net.a_slots && ts >= 0 && ts < net.n_slots, JN_ESTATE, "pass over activation slot %d, table slot %d: not allocated", slot, ts);
+  JN_CHECK(!replay || (train && !with_head && first_op == 0), JN_ESTATE, "a replay is a whole train-mode pass without the head");
+  if (!replay) invalidate_slot_state(ctx, ni, slot);
+  else if (slot == 0 && ni == ctx->enc_net) ctx->sup_valid = false;
   if (!train && (rc = refresh_eval_table(ctx, net, s))) return rc;
   const bool x3 = ctx->params_x3 && !std::getenv("JN_NO_PW_X3");   // read per pass: tests flip it
   if (x3 && (rc = refresh_x3_planes(ctx, net, s))) return rc;
-  double* stats = train ? slot_stats(net, slot) : nullptr;
-  float* save = train ? slot_save(net, slot) : nullptr;
+  double* stats = train ? slot_stats(net, ts) : nullptr;    // what the consumers of deferred tables read
+  float* save = train ? slot_save(net, ts) : nullptr;
+  if (replay && !net.stats_sink) {
+    if ((rc = dev_alloc(ctx, &net.stats_sink, (size_t)JN_NREP * 2 * net.stat_channels))) return rc;
+    JN_HIP(hipMemsetAsync(net.stats_sink, 0, (size_t)JN_NREP * 2 * net.stat_channels * sizeof(double), s));
+  }
+  double* acc = replay ? net.stats_sink : stats;            // what the producers add to
   // (a train-mode rollout zeroes the statistics of all its slots with ONE memset up front)
-  if (train && !ctx->stats_prezeroed) JN_HIP(hipMemsetAsync(stats, 0, (size_t)JN_NREP * 2 * net.stat_channels * sizeof(double), s));
+  if (train && !replay && !ctx->stats_prezeroed) JN_HIP(hipMemsetAsync(stats, 0, (size_t)JN_NREP * 2 * net.stat_channels * sizeof(double), s));
   const long long rep_stride = 2LL * net.stat_channels;
   // deferred tables: the small-map layers of the depthwise fp32 encoder get no finalize launch of their own; their
   // consumers read the batch sums (ChanTab in jn_kernels.h), one finalize launch closes the pass
@@ -316,7 +354,7 @@ int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int train, 
   const int n_ops = first_op + (int)plan.size();
   auto ptr = [&](const View& v) { return view_ptr(net, slot, MB, v); };
   auto tab = [&](const View& v) {
-    ChanTab t = view_tab(net, slot, v);
+    ChanTab t = view_tab(net, ts, v);
     if (defer && defer_tab_runs(net, v, N, t)) {     // the view holds a channel whose table is deferred in this pass
       const int off = net.tab_off[v.buf] + v.coff;
       t.dsrc = net.td_src + off; t.dhw = net.td_hw + off; t.dgoff = net.td_goff + off; t.dboff = net.td_boff + off;
@@ -326,7 +364,7 @@ int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int train, 
   };
   auto ld = [&](const View& v) { return net.bufs[v.buf].C; };
   auto finalize = [&](const Op& op, const ConvW& cw, bool deferred) {
-    if (!train || !cw.has_bn || deferred) return 0;
+    if (!train || !cw.has_bn || deferred || replay) return 0;      // (a replay reads the table the pass left)
     ChanTab t1{nullptr, nullptr, nullptr};
     if (op.alias.buf >= 0) t1 = tab(op.alias);
     // with the end-of-pass finalize (defer): table only here, saved / running statistics there
@@ -347,7 +385,7 @@ int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int train, 
         const ConvW& cw = net.convs[op.wslot];
         StemArgs a = stem_args(ss, net, N, cw);
         a.out = ptr(op.out); a.out_ld = ld(op.out); a.out_dtype = net.act_dtype; a.skip_flag = skip_flag; a.skip_when = skip_when;
-        a.stats = train ? stats + 2 * cw.stat_off : nullptr; a.stats_rep_stride = rep_stride;
+        a.stats = train ? acc + 2 * cw.stat_off : nullptr; a.stats_rep_stride = rep_stride;
         a.stats_nrep = st.deferred ? JN_NREP_DEFER : JN_NREP;
         if (!(lrc = launch_stem(a, s))) lrc = finalize(op, cw, st.deferred);
         break;
@@ -378,7 +416,7 @@ int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int train, 
         a.bf16_mfma = net.act_dtype == JN_BF16;
         a.N = N; a.H = op.in.H; a.W = op.in.W; a.OH = op.out.H; a.OW = op.out.W;
         a.cin = op.in.C; a.cout = op.out.C; a.stride = op.stride; a.act = op.act;
-        a.stats = (train && cw.has_bn) ? stats + 2 * cw.stat_off : nullptr;
+        a.stats = (train && cw.has_bn) ? acc + 2 * cw.stat_off : nullptr;
         a.stats_rep_stride = rep_stride;
         a.stats_nrep = st.deferred ? JN_NREP_DEFER : JN_NREP;
         a.skip_flag = skip_flag; a.skip_when = skip_when;
@@ -428,17 +466,17 @@ int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int train, 
     }
     prof.total();
   }
-  if (defer) {
+  if (defer && !replay) {
     BnAllArgs fa{};
     fa.stats = stats; fa.rep_stride = rep_stride; fa.n_stat = net.stat_channels; fa.N = N; fa.hw = net.fd_hw;
     fa.goff = net.fd_goff; fa.boff = net.fd_boff; fa.params = ctx->params; fa.t0 = net.fd_t0; fa.t1 = net.fd_t1;
-    fa.tab = net.tab + (size_t)slot * 3 * net.tab_channels; fa.tab_channels = net.tab_channels; fa.save = save;
+    fa.tab = net.tab + (size_t)ts * 3 * net.tab_channels; fa.tab_channels = net.tab_channels; fa.save = save;
     fa.run_mean = net.fd_rm; fa.run_var = net.fd_rv; fa.eps = kBnEps; fa.momentum = kBnMomentum;
     fa.skip_flag = skip_flag; fa.skip_when = skip_when; fa.defer_max_m = JN_DEFER_MAX_M;
     JN_CHECK(launch_bn_finalize_all(fa, s) == 0, JN_ESTATE, "forward: the end-of-pass BatchNorm finalize was not launched");
   }
   JN_HIP(hipGetLastError());
-  if (train) net.eval_tab_dirty = true;     // running statistics moved
+  if (train && !replay) net.eval_tab_dirty = true;     // running statistics moved
   return JN_OK;
 }
 
@@ -489,12 +527,14 @@ int ensure_aux_stream(jn_ctx* ctx) {
 // fpn_zero: bit i set = NO gradient arrives in net.fpn[i] from outside the network (the REINFORCE / supervised backward
 // only feeds fpn[2]).  The routes come from plan_backward (plan.cpp); what depends on launch-time state stays here.
 int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, hipStream_t s, int nsl, long long pos_slot_stride,
-                     bool with_head, int fpn_zero) {
+                     bool with_head, int fpn_zero, int tab_slot) {
   Net& net = ctx->nets[ni];
+  const int ts = tab_slot < 0 ? slot : tab_slot;      // activations from slot `slot` on, tables / saved statistics from table slot ts on
   const int MB = ctx->cfg.max_batch;
   // THE refusal of the backward: every kernel below reads fp32 activations
   JN_CHECK(net.act_dtype == JN_F32, JN_ESTATE, "training needs act_dtype = fp32 (bf16 is the inference mode)");
-  JN_CHECK(nsl >= 1 && nsl <= net.g_slots && slot + nsl <= net.n_slots, JN_ESTATE, "backward over %d slots from %d: not allocated", nsl, slot);
+  JN_CHECK(nsl >= 1 && nsl <= net.g_slots && slot >= 0 && slot + nsl <= net.a_slots && ts >= 0 && ts + nsl <= net.n_slots, JN_ESTATE,
+           "backward over %d slots from %d (tables from %d): not allocated", nsl, slot, ts);
   std::vector<BwdStep> plan;
   int rc = plan_backward(net, with_head, fpn_zero, plan);
   if (rc) return rc;
@@ -509,10 +549,10 @@ int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, hi
   sb.red = (long long)JN_NREP * 2 * net.stat_channels;
   sb.consts = 3LL * net.stat_channels;
   sb.pos = pos_slot_stride;
-  float* save = slot_save(net, slot);
+  float* save = slot_save(net, ts);
   auto ptr = [&](const View& v) { return (const float*)view_ptr(net, slot, MB, v); };
   auto gptr = [&](const View& v) { return net.gact + net.buf_off[v.buf] * (size_t)MB + v.coff; };
-  auto tab = [&](const View& v) { return view_tab(net, slot, v); };
+  auto tab = [&](const View& v) { return view_tab(net, ts, v); };
   auto ld = [&](const View& v) { return net.bufs[v.buf].C; };
   auto sums = [&](int p, int half) {      // BN-backward sums of op p (half -1: the whole conv)
     const ConvW& pcw = net.convs[net.ops[p].wslot];
@@ -737,14 +777,14 @@ int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, hi
 
 // embed_fpn (src/models/gpt.py:294-306, 382) on the last FPN map of the encoder for N patches:
 // 1x1 conv + ReLU, then the split-K partial sums of the Linear (finished by the consumer).
-int run_embed_fpn(jn_ctx* ctx, int N, int slot, float* e_buf, const int* skip_flag, int skip_when, hipStream_t s) {
+int run_embed_fpn(jn_ctx* ctx, int N, int slot, float* e_buf, const int* skip_flag, int skip_when, hipStream_t s, int tab_slot) {
   if (!e_buf) e_buf = ctx->efpn_act;
   const Net& net = ctx->nets[ctx->enc_net];
   jn_ctx& x = *ctx;
   const int C = ctx->cfg.n_embd, MB = ctx->cfg.max_batch;
   const View& f = net.fpn[2];
   ConvArgs a{};
-  a.in = view_ptr(net, slot, MB, f); a.in_ld = net.bufs[f.buf].C; a.in_dtype = net.act_dtype; a.itab = view_tab(net, slot, f);
+  a.in = view_ptr(net, slot, MB, f); a.in_ld = net.bufs[f.buf].C; a.in_dtype = net.act_dtype; a.itab = view_tab(net, tab_slot < 0 ? slot : tab_slot, f);
   a.out_dtype = JN_F32; a.bf16_mfma = net.act_dtype == JN_BF16;
   a.w = ctx->gpt.efpn_w; a.bias = nullptr; a.out = e_buf; a.out_ld = C;
   a.N = N; a.H = f.H; a.W = f.W; a.OH = f.H; a.OW = f.W; a.cin = f.C; a.cout = C; a.stride = 1; a.act = ACT_RELU;
@@ -753,6 +793,34 @@ int run_embed_fpn(jn_ctx* ctx, int N, int slot, float* e_buf, const int* skip_fl
   JN_CHECK(launch_efpn_linear(e_buf, ctx->gpt.efpn_lin_wt, x.emb_part, N, f.H * f.W * C, C, x.KS, skip_flag, skip_when, s) == 0, JN_ESTATE,
            "embed_fpn.3: no kernel for %d outputs", C);
   JN_HIP(hipGetLastError());
+  return JN_OK;
+}
+
+// Words of activation slot slot_a that differ from slot_b, over the first N patches of every buffer of the net (a debug
+// aid of the replay mode: waits for the stream).
+int replay_slot_diff(jn_ctx* ctx, Net& net, int slot_a, int slot_b, int N, long long* n_diff, hipStream_t s) {
+  const int MB = ctx->cfg.max_batch;
+  JN_CHECK(slot_a >= 0 && slot_b >= 0 && slot_a < net.a_slots && slot_b < net.a_slots && N >= 1 && N <= MB, JN_ESTATE,
+           "compare of activation slots %d and %d over %d patches: not allocated", slot_a, slot_b, N);
+  JN_CHECK(net.act_dtype == JN_F32, JN_ESTATE, "the slot compare reads fp32 activations");
+  unsigned long long* total = nullptr;
+  JN_HIP(hipMalloc((void**)&total, sizeof(unsigned long long)));
+  hipError_t e = hipMemsetAsync(total, 0, sizeof(unsigned long long), s);
+  for (size_t b = 0; b < net.bufs.size() && e == hipSuccess; ++b) {
+    View v; v.buf = (int)b; v.coff = 0;
+    const long long n = (long long)N * (long long)net.bufs[b].per_image();
+    if (n == 0) continue;
+    const unsigned grid = (unsigned)std::min<long long>((n + 255) / 256, 2048);
+    hipLaunchKernelGGL(word_diff_kernel, dim3(grid), dim3(256), 0, s, (const uint32_t*)view_ptr(net, slot_a, MB, v),
+                       (const uint32_t*)view_ptr(net, slot_b, MB, v), n, total);
+  }
+  unsigned long long host = 0;
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(&host, total, sizeof(host), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  (void)hipFree(total);
+  JN_HIP(e);
+  *n_diff = (long long)host;
   return JN_OK;
 }
 

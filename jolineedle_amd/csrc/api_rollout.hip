@@ -160,14 +160,19 @@ int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const
   ctx->conv_ev_used = 0;
   const StemSrc ss = env_stem_src(e, e.positions);
   int rc;
+  // jn_set_activation_slots: a walk longer than the ring keeps `ring` activation slots besides slot 0 (step t writes
+  // slot 1 + t % ring) and the backward replays every step; tables, saved statistics and sums stay one slot per step
+  const int ring = train && !c.no_patch_emb && ctx->enc_net != JN_NET_DETECTOR && ctx->act_ring > 0 && ctx->act_ring < T ? ctx->act_ring : 0;
+  if (train) ctx->train_ring = ring;
   if (train) {
     Net& tn = ctx->nets[ctx->enc_net];
     // (a shared detector / encoder net: the detector's training pass gets its slot behind the rollout's right away, so
     // that no growth — and copy — happens between this rollout and its backward)
-    if ((rc = ensure_slots(ctx, tn, ctx->enc_net == JN_NET_DETECTOR ? c.block_size + 2 : T + 1))) return rc;
+    if ((rc = ensure_slots(ctx, tn, ctx->enc_net == JN_NET_DETECTOR ? c.block_size + 2 : T + 1, ring ? ring + 1 : -1))) return rc;
     int g_want = tn.g_slots;
+    const int g_most = ring ? ring : T;      // a gradient mirror for a step whose activations are not there is useless
     if (ctx->enc_net == JN_NET_DETECTOR) g_want = std::max(1, g_want);   // detached encoder: no conv-stack backward
-    else if (g_want < T && (rc = grad_slots_that_fit(ctx, tn, T, &g_want))) return rc;
+    else if (g_want < g_most && (rc = grad_slots_that_fit(ctx, tn, g_most, &g_want))) return rc;
     if ((rc = ensure_train_state(ctx, g_want))) return rc;
     if ((rc = ensure_token_train_buffers(ctx))) return rc;
   }
@@ -184,9 +189,12 @@ int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const
     if (tsets) launch_teacher_sets(e.positions, e.visited, ttargets, tsets + t, T, B, e.Gh, e.Gw, flag, B, s);
     if (!c.no_patch_emb) {
       if (ctx->profiling) JN_HIP(hipEventRecord(ctx->conv_ev[2 * t], s));
-      if ((rc = run_net(ctx, ctx->enc_net, B, vm ? stage_stem_src(e, P, t) : ss, train ? t + 1 : 0, train, flag, B, s))) return rc;
+      const int a_slot = !train ? 0 : ring ? 1 + t % ring : t + 1;
+      if ((rc = run_net(ctx, ctx->enc_net, B, vm ? stage_stem_src(e, P, t) : ss, a_slot, train, flag, B, s, false, 0, train ? t + 1 : 0))) return rc;
       if (ctx->profiling) { JN_HIP(hipEventRecord(ctx->conv_ev[2 * t + 1], s)); ctx->conv_ev_used = 2 * (t + 1); }
-      if ((rc = run_embed_fpn(ctx, B, train ? t + 1 : 0, train ? ctx->efpn_train + (size_t)t * B * ctx->efpn_h * ctx->efpn_w * C : nullptr, flag, B, s))) return rc;
+      if ((rc = run_embed_fpn(ctx, B, a_slot, train ? ctx->efpn_train + (size_t)t * B * ctx->efpn_h * ctx->efpn_w * C : nullptr, flag, B, s,
+                              train ? t + 1 : 0)))
+        return rc;
     }
     GptStepArgs a{};
     fill_gpt_weights(ctx, a);
@@ -262,6 +270,24 @@ int jn_rollout(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const i
 int jn_set_rollout_positions(jn_ctx* ctx, int by_token) {
   JN_CHECK(ctx, JN_EINVAL, "null ctx");
   ctx->pos_by_token = by_token != 0;
+  return JN_OK;
+}
+
+int jn_set_activation_slots(jn_ctx* ctx, int n) {
+  JN_CHECK(ctx, JN_EINVAL, "jn_set_activation_slots: null ctx");
+  JN_CHECK(n >= 0, JN_EINVAL, "jn_set_activation_slots: n = %d (0: one slot per glimpse step, n >= 1: a ring of n)", n);
+  ctx->act_ring = n;
+  ctx->train_out_valid = false;      // a rollout made under another setting is not differentiated under this one
+  return JN_OK;
+}
+
+int jn_activation_slots_info(const jn_ctx* ctx, int net, int* act_slots, int* table_slots, size_t* slot_bytes, int* replayed_steps) {
+  JN_CHECK(ctx && net >= 0 && net < 2 && ctx->has_net[net], JN_EINVAL, "jn_activation_slots_info: network %d is not part of this context", net);
+  const Net& n = ctx->nets[net];
+  if (act_slots) *act_slots = n.a_slots;
+  if (table_slots) *table_slots = n.n_slots;
+  if (slot_bytes) *slot_bytes = n.per_image_floats * (size_t)ctx->cfg.max_batch * act_esz(n);
+  if (replayed_steps) *replayed_steps = net == ctx->enc_net ? ctx->replayed_steps : 0;
   return JN_OK;
 }
 

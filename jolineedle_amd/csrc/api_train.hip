@@ -164,8 +164,10 @@ static void fill_gpt_bwd_common(jn_ctx* ctx, GptBwdArgs& ba) {
 // slots 0 .. g_n - 1), given e (embed_fpn.0 activations) and dpe (d loss / d patch embedding) of those g_n * rows
 // patches: embed_fpn's backward, then the conv stack's.  In training only fpn[2] gets a gradient from outside the
 // encoder (embed_fpn): fpn[0] and fpn[1] are zeroed and the conv stack takes the routes of fpn_zero = 0x3.
+// `slot` counts activation slots; the tables and saved statistics start at table slot tab_slot (< 0: the same slot).
 static int encoder_backward(jn_ctx* ctx, int g_n, int rows, int slot, const float* e, const float* dpe, const StemSrc& ss,
-                            long long pos_slot_stride, hipStream_t s) {
+                            long long pos_slot_stride, hipStream_t s, int tab_slot = -1) {
+  if (tab_slot < 0) tab_slot = slot;
   const int C = ctx->cfg.n_embd, MB = ctx->cfg.max_batch, HW = ctx->efpn_h * ctx->efpn_w, K = HW * C;
   const GptW& g = ctx->gpt;
   Net& net = ctx->nets[ctx->enc_net];
@@ -195,7 +197,7 @@ static int encoder_backward(jn_ctx* ctx, int g_n, int rows, int slot, const floa
   // yolox"): the policy gradient stops at embed_fpn.0's weight
   const bool detached = ctx->enc_net == JN_NET_DETECTOR;
   JN_CHECK(detached || launch_pw(a, s) == 0, JN_ESTATE, "backward of embed_fpn.0: no kernel for this shape, or its LDS was refused");
-  launch_pw_bwd_weight(ctx->de_ws, C, (const float*)view_ptr(net, slot, MB, f2), net.bufs[f2.buf].C, view_tab(net, slot, f2),
+  launch_pw_bwd_weight(ctx->de_ws, C, (const float*)view_ptr(net, slot, MB, f2), net.bufs[f2.buf].C, view_tab(net, tab_slot, f2),
                        grad_of(ctx, g.efpn_w), ctx->wpart, (long long)rows * HW, C, f2.C, s, sb, (long long)rows * K);
   if (detached) return JN_OK;
   for (int i = 0; i < 2; ++i) {
@@ -204,7 +206,7 @@ static int encoder_backward(jn_ctx* ctx, int g_n, int rows, int slot, const floa
       JN_HIP(hipMemsetAsync(net.gact + (size_t)j * g_slot + net.buf_off[f.buf] * (size_t)MB + f.coff, 0,
                             (size_t)rows * f.H * f.W * f.C * sizeof(float), s));
   }
-  return run_net_backward(ctx, ctx->enc_net, rows, ss, slot, s, g_n, pos_slot_stride, false, 0x3);
+  return run_net_backward(ctx, ctx->enc_net, rows, ss, slot, s, g_n, pos_slot_stride, false, 0x3, tab_slot);
 }
 
 static int check_train_outputs(const jn_rollout_out* out) {
@@ -252,6 +254,16 @@ static int reinforce_backward_gpt(jn_ctx* ctx, const jn_rollout_out* out, int st
   return launch_gpt_bwd(ctx, ba, s);
 }
 
+// Where the forward of glimpse step t of the rollout behind `out` read its B patches: the walk's own positions (column t
+// of positions [B][T + 1][2]) over the env's images, or, in view mode, staged column t.
+static StemSrc rollout_step_src(const jn_ctx* ctx, const jn_rollout_out* out, int t) {
+  const EnvState& e = ctx->env;
+  if (e.view_mode) return stage_stem_src(e, ctx->cfg.patch_size, t);
+  StemSrc ss = env_stem_src(e, out->positions_dev + 2 * t);
+  ss.pos_stride = 2 * (e.T + 1);
+  return ss;
+}
+
 // The second half needs S on the host: embed_fpn, then the patch encoder of all S executed glimpse steps, step-batched.
 static int reinforce_backward_encoder(jn_ctx* ctx, const jn_rollout_out* out, int S, hipStream_t s) {
   int rc;
@@ -262,8 +274,20 @@ static int reinforce_backward_encoder(jn_ctx* ctx, const jn_rollout_out* out, in
   // when the gradient buffers of a whole trajectory do not fit): embed_fpn backward, then the PAFPN.
   if (ctx->profiling && ctx->ev[2]) JN_HIP(hipEventRecord(ctx->ev[2], s));     // conv-stack backward section (bench.py)
   // (a detached encoder needs no gradient slots: all steps in one chunk)
-  const int chunk = ctx->enc_net == JN_NET_DETECTOR ? std::max(S, 1) : ctx->nets[ctx->enc_net].g_slots;
-  for (int t0 = 0; t0 < S; t0 += chunk) {
+  const bool detached = ctx->enc_net == JN_NET_DETECTOR;
+  const int ring = detached ? 0 : ctx->train_ring;
+  std::vector<int> c_t0(std::max(S, 1)), c_n(std::max(S, 1));
+  const int n_chunks = jn_replay_chunks(S, ring, detached ? std::max(S, 1) : ctx->nets[ctx->enc_net].g_slots, c_t0.data(), c_n.data(), (int)c_t0.size());
+  if (n_chunks < 0) return n_chunks;
+  ctx->replayed_steps = 0;
+  JN_CHECK(!ring || !e.view_mode || (e.stage && e.stage_cols == T + 1), JN_ESTATE, "the staged patches of the rollout are gone");
+  for (int ci = 0; ci < n_chunks; ++ci) {
+    const int t0 = c_t0[ci], k = c_n[ci];
+    // under a ring the chunk's steps are run again, from what their table slots kept, into activation slots 1 .. k
+    for (int j = 0; ring && j < k; ++j) {
+      if ((rc = run_net(ctx, ctx->enc_net, B, rollout_step_src(ctx, out, t0 + j), 1 + j, 1, nullptr, 0, s, false, 0, t0 + j + 1, RUN_REPLAY))) return rc;
+      ++ctx->replayed_steps;
+    }
     StemSrc ss = env_stem_src(e, out->positions_dev + 2 * t0);
     ss.pos_stride = 2 * (T + 1);
     long long pos_slot = 2;
@@ -275,8 +299,9 @@ static int reinforce_backward_encoder(jn_ctx* ctx, const jn_rollout_out* out, in
       ss.positions = e.stage_pos + (size_t)t0 * B * 2;
       pos_slot = 2LL * B;
     }
-    if ((rc = encoder_backward(ctx, std::min(chunk, S - t0), B, t0 + 1, ctx->efpn_train + (size_t)t0 * B * K,
-                               ctx->d_tok_emb + (size_t)t0 * B * C, ss, pos_slot, s))) return rc;
+    if ((rc = encoder_backward(ctx, k, B, ring ? 1 : t0 + 1, ctx->efpn_train + (size_t)t0 * B * K, ctx->d_tok_emb + (size_t)t0 * B * C, ss,
+                               pos_slot, s, t0 + 1)))
+      return rc;
   }
   if (ctx->profiling && ctx->ev[3]) { JN_HIP(hipEventRecord(ctx->ev[3], s)); ctx->bwd_timed = true; }
   JN_HIP(hipGetLastError());
@@ -577,6 +602,36 @@ int jn_supervised_eval(jn_ctx* ctx, const float* patches_dev, const int64_t* cur
                             on_self_trajectory ? 1 : 0, token_loss_out_dev, predicted_out_dev, metrics_dev, s);
   JN_HIP(hipGetLastError());
   return JN_OK;
+}
+
+// ---- the chunks of the encoder's backward (host rule, no device) and the replay check -------------------------------------
+int jn_replay_chunks(int S, int act_slots, int g_slots, int* t0, int* n, int cap) {
+  JN_CHECK(S >= 0 && act_slots >= 0 && g_slots >= 1 && cap >= 0 && ((t0 && n) || cap == 0), JN_EINVAL,
+           "jn_replay_chunks: S=%d act_slots=%d g_slots=%d cap=%d", S, act_slots, g_slots, cap);
+  const int chunk = act_slots ? std::min(act_slots, g_slots) : g_slots;
+  int count = 0;
+  for (int at = 0; at < S; at += chunk, ++count)
+    if (count < cap) { t0[count] = at; n[count] = std::min(chunk, S - at); }
+  return count;
+}
+
+int jn_debug_replay_diff(jn_ctx* ctx, int step, long long* n_diff, void* stream) {
+  JN_CHECK(ctx && n_diff, JN_EINVAL, "jn_debug_replay_diff: null argument");
+  JN_CHECK(ctx->train_out_valid, JN_ESTATE, "jn_debug_replay_diff needs a preceding train-mode rollout (jn_reinforce_forward / jn_reinforce_step)");
+  JN_CHECK(ctx->enc_net != JN_NET_DETECTOR && ctx->train_ring == 0, JN_ESTATE,
+           "jn_debug_replay_diff compares against resident steps: a patch encoder of its own and jn_set_activation_slots 0");
+  JN_HIP(hipSetDevice(ctx->cfg.device));
+  hipStream_t s = (hipStream_t)stream;
+  int S = 0, rc;
+  if ((rc = rollout_steps_begin(ctx, s)) || (rc = rollout_steps_end(ctx, &S))) return rc;
+  JN_CHECK(step >= 0 && step < S, JN_EINVAL, "jn_debug_replay_diff: step %d of %d executed steps", step, S);
+  const EnvState& e = ctx->env;
+  JN_CHECK(!e.view_mode || (e.stage && e.stage_cols == e.T + 1), JN_ESTATE, "the staged patches of the rollout are gone");
+  Net& net = ctx->nets[ctx->enc_net];
+  // (activation slot 0 is the eval workspace: run_net's replay mode marks what it held as gone)
+  if ((rc = run_net(ctx, ctx->enc_net, e.B, rollout_step_src(ctx, &ctx->train_out, step), 0, 1, nullptr, 0, s, false, 0, step + 1, RUN_REPLAY)))
+    return rc;
+  return replay_slot_diff(ctx, net, 0, step + 1, e.B, n_diff, s);
 }
 
 // ---- the GPT backward's route and its attention kernels alone (context-free) -------------------------------------------

@@ -112,13 +112,18 @@ struct Net {
   std::vector<int> tab_off;       // first table channel of each buffer
   int tab_channels = 0;           // sum of buffer channels (table length)
   int stat_channels = 0;          // sum of BN channels
-  // workspace slots: slot 0 = eval / single-step; slots 1..n = one per glimpse step when training
+  // workspace slots: slot 0 = eval / single-step; slots 1..n = one per glimpse step when training.  The small per-step
+  // state (tab / save / stats) has n_slots slots, the activations a_slots: the two counts are equal, and a step's
+  // activation slot is its table slot, unless a train-mode rollout runs under jn_set_activation_slots, which keeps a
+  // ring of activation slots and replays a step's forward before its backward (run_net's replay mode)
   int n_slots = 0;
+  int a_slots = 0;
   int act_dtype = 0;              // JN_F32 / JN_BF16 storage of the activation buffers
-  char* act = nullptr;            // [n_slots][per_image_floats * max_batch] elements of act_dtype
+  char* act = nullptr;            // [a_slots][per_image_floats * max_batch] elements of act_dtype
   float* tab = nullptr;           // [n_slots][3][tab_channels]
   float* save = nullptr;          // [n_slots][2 * stat_channels]  (mean, invstd)
   double* stats = nullptr;        // [n_slots][2 * stat_channels]  (sum, sumsq)
+  double* stats_sink = nullptr;   // one slot of sums nobody reads: where the producers of a replayed pass add theirs
   int g_slots = 0;                // slots of the three gradient-side buffers below (backward is step-batched)
   float* gact = nullptr;          // [g_slots] gradient buffers: mirror of one `act` slot each
   double* bred = nullptr;         // [g_slots][JN_NREP][2 * stat_channels] backward reductions (sum g_y, sum g_y * zhat)
@@ -350,6 +355,9 @@ struct jn_ctx {
   uint64_t drop_seed = 0, drop_ctr = 0, drop_seed_used = 0;   // seed of the NEXT / the most recent train-mode forward
   jn_rollout_out train_out{};     // output buffers of the most recent train-mode rollout (jn_reinforce_backward reads them)
   bool train_out_valid = false;   // cleared by every entry point that overwrites what jn_reinforce_backward reads
+  // jn_set_activation_slots: act_ring = the setting (0: one activation slot per glimpse step); train_ring = the ring the
+  // most recent train-mode rollout ran under (0: all its steps resident); replayed_steps: of the most recent backward
+  int act_ring = 0, train_ring = 0, replayed_steps = 0;
   // supervised autograd bridge: inputs of the most recent supervised forward (caller-owned, alive until the backward)
   struct SupState { const float* patches; const int64_t* actions; const int64_t* positions; const int64_t* classes; int B, T; } sup{};
   bool sup_valid = false;         // cleared by every pass over workspace slot 0 of the patch encoder
@@ -405,6 +413,7 @@ int AgentTable<T, Width>::upload(jn_ctx* ctx, int min_rows, hipStream_t s, const
 }
 
 // workspace slots.  Activation buffers are stored as net.act_dtype (JN_F32: 4-byte, JN_BF16: 2-byte elements).
+// view_ptr takes an ACTIVATION slot (< net.a_slots); view_tab, slot_save and slot_stats take a TABLE slot (< net.n_slots).
 inline size_t act_esz(const Net& net) { return net.act_dtype == JN_BF16 ? 2 : 4; }
 inline void* view_ptr(const Net& net, int slot, int max_batch, const View& v) {
   const size_t elem = (size_t)slot * net.per_image_floats * max_batch + net.buf_off[v.buf] * (size_t)max_batch + v.coff;
@@ -415,6 +424,7 @@ inline ChanTab view_tab(const Net& net, int slot, const View& v) {
   return ChanTab{t, t + net.tab_channels, t + 2 * net.tab_channels};
 }
 inline double* slot_stats(const Net& net, int slot) { return net.stats + (size_t)slot * JN_NREP * 2 * net.stat_channels; }
+inline float* slot_save(const Net& net, int slot) { return net.save + (size_t)slot * 2 * net.stat_channels; }
 inline float* grad_of(const jn_ctx* ctx, const float* param) { return ctx->grads + (param - ctx->params); }
 
 // api_ctx.hip
@@ -422,16 +432,19 @@ int dev_upload(jn_ctx* ctx, float** out, const std::vector<float>& host);
 int n_parts(const jn_config& c);
 // api_net.hip
 StemSrc patch_src(const void* ptr, int P, long long sample_stride = 0);
-int ensure_slots(jn_ctx* ctx, Net& net, int n_slots);
+int ensure_slots(jn_ctx* ctx, Net& net, int n_slots, int a_slots = -1);   // a_slots < 0: as many as n_slots
 int refresh_eval_table(jn_ctx* ctx, Net& net, hipStream_t s);
 void mark_params_written(jn_ctx* ctx);
+// tab_slot < 0: the pass's table slot is its activation slot `slot`
+enum RunMode { RUN_PASS = 0, RUN_REPLAY = 1 };
 int run_net(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, int train, const int* skip_flag, int skip_when,
-            hipStream_t s, bool with_head = false, int first_op = 0);
+            hipStream_t s, bool with_head = false, int first_op = 0, int tab_slot = -1, RunMode mode = RUN_PASS);
 int ensure_train_state(jn_ctx* ctx, int g_slots = 1);
 int ensure_aux_stream(jn_ctx* ctx);
 int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, hipStream_t s, int nsl = 1,
-                     long long pos_slot_stride = 0, bool with_head = false, int fpn_zero = 0);
-int run_embed_fpn(jn_ctx* ctx, int N, int slot, float* e_buf, const int* skip_flag, int skip_when, hipStream_t s);
+                     long long pos_slot_stride = 0, bool with_head = false, int fpn_zero = 0, int tab_slot = -1);
+int run_embed_fpn(jn_ctx* ctx, int N, int slot, float* e_buf, const int* skip_flag, int skip_when, hipStream_t s, int tab_slot = -1);
+int replay_slot_diff(jn_ctx* ctx, Net& net, int slot_a, int slot_b, int N, long long* n_diff, hipStream_t s);
 int embed_tokens(jn_ctx* ctx, const StemSrc& ss, int N, int train, float* e_buf, float* out, long long out_stride,
                  hipStream_t s);
 // api_det.hip

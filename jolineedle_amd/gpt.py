@@ -128,6 +128,9 @@ class GPT(nn.Module):
         self.det_loss_boxes = "cap8"
         if getattr(config, "det_loss_boxes", "cap8") != "cap8":
             self.set_det_loss_boxes(config.det_loss_boxes)
+        self.activation_slots = 0
+        if int(getattr(config, "activation_slots", 0) or 0) != 0:
+            self.set_activation_slots(config.activation_slots)
         self._build_parameters()
         # --freeze-image-processor (gpt.py:264-268): yolox.backbone.* out of the optimiser
         self.freeze_image_processor = bool(getattr(config, "freeze_image_processor", False))
@@ -204,6 +207,30 @@ class GPT(nn.Module):
             raise ValueError(f"det_loss_boxes={policy!r}: one of {DET_LOSS_BOXES}")
         check(self._engine.lib.jn_set_det_loss_boxes(self._engine.handle, int(policy == "all")), "jn_set_det_loss_boxes")
         self.det_loss_boxes = policy
+
+    def set_activation_slots(self, n: int):
+        """Activation slots a train-mode rollout of the patch encoder keeps from now on (``jn_set_activation_slots``; config
+        field ``activation_slots``): 0 = one per glimpse step (the default), n >= 1 = a ring of n, and the backward
+        re-runs the forward of every chunk of steps from the kept BatchNorm statistics just before it differentiates
+        it — the way to train walks whose activations do not fit (29 MB x max_batch per step at 448 px).  The gradients
+        are those of the default up to the order of the atomics.  A rollout made before the call can no longer be
+        differentiated.  With ``gpt_backbone=None`` (detached encoder) the setting is accepted and has no effect."""
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"activation_slots={n}: 0 (one per glimpse step) or a ring of n >= 1")
+        check(self._engine.lib.jn_set_activation_slots(self._engine.handle, n), "jn_set_activation_slots")
+        self.activation_slots = n
+
+    def activation_slots_info(self):
+        """What the patch encoder's workspace holds (``jn_activation_slots_info``): ``act_slots`` / ``table_slots`` now,
+        ``slot_bytes`` of one activation slot at ``max_batch``, ``replayed_steps`` of the most recent backward."""
+        import ctypes
+        eng = self._engine
+        a, t, r, b = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_size_t(0)
+        net = _lib.JN_NET_GPT_BACKBONE if eng.cfg.gpt_bb_width > 0 else _lib.JN_NET_DETECTOR
+        check(eng.lib.jn_activation_slots_info(eng.handle, net, ctypes.byref(a), ctypes.byref(t), ctypes.byref(b), ctypes.byref(r)),
+              "jn_activation_slots_info")
+        return {"act_slots": a.value, "table_slots": t.value, "slot_bytes": b.value, "replayed_steps": r.value}
 
     @property
     def yolox(self):
