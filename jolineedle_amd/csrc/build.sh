@@ -6,7 +6,7 @@ OUT="${JN_LIB_OUT:-$HERE/../lib}"
 mkdir -p "$OUT" "$HERE/obj"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function -Wno-unused-result ${JN_EXTRA_FLAGS:-}"
-UNITS="kernels_conv kernels_pwres kernels_pwxs kernels_bwd kernels_bwd_pw kernels_train kernels_gptbwd kernels_conv3 kernels_det kernels_detloss kernels_aug kernels_env kernels_view kernels_ragged kernels_eval kernels_gpt kernels_gptwide api_ctx api_net api_det api_env api_ops api_rollout api_train"
+UNITS="kernels_conv kernels_pwres kernels_pwxs kernels_bwd kernels_bwd_pw kernels_train kernels_gptbwd kernels_conv3 kernels_det kernels_detloss kernels_aug kernels_env kernels_view kernels_ragged kernels_eval kernels_gpt kernels_gptwide api_ctx api_net api_det api_env api_ops api_kernels api_rollout api_train"
 pids=()
 for f in $UNITS; do
   if [ ! -f "$HERE/obj/$f.o" ] || [ "$HERE/$f.hip" -nt "$HERE/obj/$f.o" ] || [ -n "$(find "$HERE" -maxdepth 1 -name '*.h' -newer "$HERE/obj/$f.o")" ] || [ "$HERE/../../include/jnroll.h" -nt "$HERE/obj/$f.o" ]; then

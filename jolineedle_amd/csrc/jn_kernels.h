@@ -150,7 +150,7 @@ int launch_dw(const ConvArgs& a, hipStream_t s, int route = 0);
 //   NARROW        K <= 64, forward, at least JN_PW_BIG_M pixels: pw_narrow_kernel
 //   MFMA          everything else: pw_mfma_kernel
 // With a.up_out set only the routes and shapes of pw_fuses_upsample remain, anything else is NONE.
-// Forced routes (the per-kernel tests, jn_pw in api_ops.hip): pw_route(a, r) is r where that family's kernels admit the launch,
+// Forced routes (the per-kernel tests, jn_pw in api_kernels.hip): pw_route(a, r) is r where that family's kernels admit the launch,
 // else NONE; launch_pw(a, s, r) launches it.  max_wg > 0 caps the x extent of a persistent grid (MFMA has none: refused).
 enum PwRoute { PW_NONE = 0, PW_X1, PW_X3, PW_XS, PW_WIDE, PW_NARROW, PW_MFMA };
 PwRoute pw_route(const ConvArgs& a, int forced = 0);
@@ -241,7 +241,7 @@ int launch_efpn_linear(const float* e, const float* wt, float* part, int N, int 
 
 // ---- dense 3x3 conv (kernels_conv3.hip) ---------------------------------------------------------
 // Every launcher takes a route: 0 = its own rule (what the networks pass), else that kernel family, for the per-kernel
-// tests (jn_conv3* in api_ops.hip).  The *_route functions are pure host code: the route a launch gets (forced = 0), or
+// tests (jn_conv3* in api_kernels.hip).  The *_route functions are pure host code: the route a launch gets (forced = 0), or
 // `forced` itself where the launch meets that route's preconditions; -1: refused.  The launchers return -1 likewise.
 enum Conv3Route { C3_ROUTE_F32 = 1, C3_ROUTE_X3 = 2, C3_ROUTE_BF16 = 3 };      // conv3_mfma; conv3_x3 / conv3_x3s2 / conv3_x3_bwd_data_s2; conv3_bf16
 enum Conv3WRoute { CW_ROUTE_TR = 1, CW_ROUTE_SPLIT = 2, CW_ROUTE_EXACT = 3 };  // conv3_bwd_weight_tr; conv3_bwd_weight<SP = true / false>

@@ -28,6 +28,7 @@ import torch
 import torch.nn.functional as F
 
 from tests.fp64_bars import STAT_ATOL, STAT_RTOL      # noqa: F401  (re-exported: the stats bar of the GPU test)
+from tests.kernel_helpers import _bf16, _nchw, _nhwc
 
 Case = collections.namedtuple("Case", "kind route stride H W cin cout slots accumulate stats skip max_wg")
 
@@ -183,14 +184,6 @@ def transform(x, tab):
     return torch.where(tab[2] != 0, y * torch.sigmoid(y), x)
 
 
-def _nchw(t):
-    return t.permute(0, 3, 1, 2)
-
-
-def _nhwc(t):
-    return t.permute(0, 2, 3, 1)
-
-
 def _w4(w):
     """[9][a][b], tap = 3 ky + kx -> [a][b][3][3]."""
     return w.reshape(3, 3, w.shape[1], w.shape[2]).permute(2, 3, 0, 1)
@@ -284,10 +277,6 @@ def reference(c):
 
 
 # ---- emulations of the kernels' number formats (CPU) ---------------------------------------------------------------------
-def _bf16(t):
-    return t.to(torch.bfloat16).to(torch.float32)
-
-
 def split3(t):
     """An fp32 tensor as three bf16 planes (jn_split.h): h = bf16(v), m = bf16(v - h), l = bf16(v - h - m)."""
     h = _bf16(t)

@@ -27,6 +27,7 @@ import torch.nn.functional as F
 
 from tests.conv3_cases import (BF16_ABS, BF16_L2, BF16_MAX, CANARY, CANARY_BF16, DW_MAX, DW_ORDER, NREP, OUT_L2, OUT_MAX,      # noqa: F401
                                SKIP_WHEN, STAT_ATOL, STAT_RTOL, distances, padded, stats_over_bar, transform)
+from tests.kernel_helpers import _bf16, _dsilu, _nchw, _nhwc
 
 Case = collections.namedtuple("Case", "kind route stride H W C cout dtype slots accumulate stats skip nrep use_wpart max_wg red res")
 
@@ -151,14 +152,6 @@ def inputs(c):
 
 
 # ---- the reference: a plain restatement, fp64 by default ---------------------------------------------------------------
-def _nchw(t):
-    return t.permute(0, 3, 1, 2)
-
-
-def _nhwc(t):
-    return t.permute(0, 2, 3, 1)
-
-
 def _w4(w):
     """[9][C], tap = 3 ky + kx -> [C][1][3][3]."""
     return w.t().reshape(w.shape[1], 1, 3, 3)
@@ -199,11 +192,6 @@ def dwconv(c, x, tab, w, mutant=None):
             a2[:, :, :, i_c] = 0
             out[:, :, :, o_c - 1] = F.conv2d(a2, _w4(w), stride=c.stride, padding=pad, groups=c.C)[:, :, :, o_c - 1]
     return out
-
-
-def _dsilu(y):
-    s = torch.sigmoid(y)
-    return s * (1 + y * (1 - s))
 
 
 def _dw_transposed(c, gz, w, mutant=None):
@@ -319,10 +307,6 @@ def _reference(key):
 def reference(c):
     """fp64, computed once per distinct computation; shared by the routes and options.  Do not modify."""
     return _reference(_key(c))
-
-
-def _bf16(t):
-    return t.to(torch.bfloat16).to(torch.float32)
 
 
 def compute_bf16(c):

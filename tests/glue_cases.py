@@ -35,6 +35,7 @@ import torch.nn.functional as F
 from tests.conv3_cases import (BF16_ABS, BF16_L2, BF16_MAX, CANARY, CANARY_BF16, DW_MAX, DW_ORDER, NREP, OUT_L2, OUT_MAX,      # noqa: F401
                                SKIP_WHEN, STAT_ATOL, STAT_RTOL, distances, padded, stats_over_bar, transform)
 from tests.dw_cases import RED_BAR
+from tests.kernel_helpers import _bf16, _dsilu
 
 _FIELDS = "kind route P H W C cout K KS N M src align pos dtype stats nrep skip max_wg slots z accumulate ints t1 save run raw consts"
 Case = collections.namedtuple("Case", _FIELDS)
@@ -185,11 +186,6 @@ def _stem_gz(c, d, s, mutant=None):
     y = d["zz"][s] * otab[0] + otab[1]
     zhat = (d["zz"][s] - save[:, 0]) * save[:, 1]
     return consts[:, 2] * (d["g"][s] * _dsilu(y) - consts[:, 0] - zhat * consts[:, 1])
-
-
-def _dsilu(y):
-    s = torch.sigmoid(y)
-    return s * (1 + y * (1 - s))
 
 
 def _compute_stem(c, dtype, mutant):
@@ -354,10 +350,6 @@ def _up_inputs(kind, H, W, C, dtype, slots, ints, M):
     # bf16 maps: outputs of about 0.03, where the absolute part of the max-norm bar leaves a 2x margin (dw_cases.py)
     small = 1.0 / 64 if dtype else 1.0
     return dict(z=r(M, C) * small, res=r(M, C) * small, ztab=_mixed_table(g, C, small), rtab=_mixed_table(g, C, small))
-
-
-def _bf16(t):
-    return t.to(torch.bfloat16).to(torch.float32)
 
 
 def _compute_up(c, dtype, mutant, tensors=None):

@@ -41,6 +41,7 @@ import torch
 from tests.conv3_cases import (BF16_ABS, BF16_L2, BF16_MAX, CANARY, CANARY_BF16, DW_EXACT_L2, DW_MAX, DW_ORDER, NREP, OUT_L2,      # noqa: F401
                                OUT_MAX, SKIP_WHEN, SPLIT_VS_F32, STAT_ATOL, STAT_RTOL, X3_W, X3_X, distances, padded, split3,
                                stats_over_bar, transform)
+from tests.kernel_helpers import _bf16
 
 Case = collections.namedtuple("Case", "kind route M cin cout dt transposed identity accumulate bias act stats nrep skip slots up defer "
                                       "max_wg wt_big use_wpart exact")
@@ -402,10 +403,6 @@ def inputs(c):
 
 
 # ---- the reference: a plain restatement, fp64 by default ---------------------------------------------------------------
-def _bf16(t):
-    return t.to(torch.bfloat16).to(torch.float32)
-
-
 def activation(v, act):
     return v if act == 0 else v * torch.sigmoid(v) if act == 1 else torch.relu(v) if act == 2 else torch.sigmoid(v)
 

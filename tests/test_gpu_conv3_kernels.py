@@ -28,15 +28,12 @@ import torch
 from jolineedle_amd import _lib
 from jolineedle_amd._lib import ptr
 from tests import conv3_cases as cc
+from tests.kernel_helpers import _bits, _dev
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 Run = collections.namedtuple("Run", "out stats raw raw0 stats_raw stats0 inputs_intact")
-
-
-def _dev(t):
-    return t.to(DEV).contiguous()
 
 
 def _run(c, route):
@@ -89,11 +86,6 @@ def _run(c, route):
         sums = (stats - stats0).sum(0).reshape(c_b, 2).t().cpu()      # [2, C]: the replicas summed, (sum, sum of squares) per channel
     return Run(out.float().cpu(), sums, raw.cpu(), raw0.cpu(), None if stats is None else stats.cpu(),
                None if stats0 is None else stats0.cpu(), all(torch.equal(a, b) for a, b in zip(ins, before)))
-
-
-def _bits(a, b):
-    return torch.equal(a.view(torch.int16) if a.dtype == torch.bfloat16 else a.view(torch.int32),
-                       b.view(torch.int16) if b.dtype == torch.bfloat16 else b.view(torch.int32))
 
 
 def _single_writer(c):

@@ -48,23 +48,12 @@ import torch
 from jolineedle_amd import _lib
 from jolineedle_amd._lib import ptr
 from tests import dw_cases as dc
+from tests.kernel_helpers import _bits, _dev, _pattern
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 Run = collections.namedtuple("Run", "res raw raw0 f64 f64_0 gw wpart inputs_intact")
-
-
-def _dev(t):
-    return t.to(DEV).contiguous()
-
-
-def _pattern(*shape):
-    """What the fp64 accumulators hold before the launch adds to them: not zero."""
-    n = 1
-    for s in shape:
-        n *= s
-    return (torch.arange(n, dtype=torch.float64, device=DEV) % 7).reshape(shape)
 
 
 def _run(c, route):
@@ -126,11 +115,6 @@ def _run(c, route):
             res["red"] = (f64 - f64_0).sum(1).reshape(c.slots, c.C, 2).permute(0, 2, 1).cpu()
     return Run(res, raw.cpu(), raw0.cpu(), None if f64 is None else f64.cpu(), None if f64_0 is None else f64_0.cpu(),
                None if gw is None else gw.cpu(), None if wpart is None else wpart.cpu(), all(torch.equal(a, b) for a, b in zip(ins, before)))
-
-
-def _bits(a, b):
-    return torch.equal(a.view(torch.int16) if a.dtype == torch.bfloat16 else a.view(torch.int32),
-                       b.view(torch.int16) if b.dtype == torch.bfloat16 else b.view(torch.int32))
 
 
 def _single_writer(c):

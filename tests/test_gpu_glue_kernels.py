@@ -50,6 +50,7 @@ import torch
 from jolineedle_amd import _lib
 from jolineedle_amd._lib import ptr
 from tests import glue_cases as gc
+from tests.kernel_helpers import _dev, _pattern
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -57,20 +58,8 @@ DEV = "cuda:0"
 Run = collections.namedtuple("Run", "res outs outs0 f64 f64_0 wpart inputs_intact")      # outs: name -> raw buffer after the launch; outs0: before
 
 
-def _dev(t):
-    return t.to(DEV).contiguous()
-
-
 def _opt(t):
     return None if t is None else ptr(t)
-
-
-def _pattern(*shape):
-    """What the fp64 accumulators hold before the launch adds to them: not zero."""
-    n = 1
-    for s in shape:
-        n *= s
-    return (torch.arange(n, dtype=torch.float64, device=DEV) % 7).reshape(shape)
 
 
 def _bits(a, b):

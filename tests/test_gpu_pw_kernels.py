@@ -26,23 +26,12 @@ import torch
 from jolineedle_amd import _lib
 from jolineedle_amd._lib import ptr
 from tests import pw_cases as pc
+from tests.kernel_helpers import _bits, _dev, _pattern
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 Run = collections.namedtuple("Run", "res raw raw0 f64 f64_0 wpart up up0 inputs_intact")
-
-
-def _dev(t):
-    return t.to(DEV).contiguous()
-
-
-def _pattern(*shape):
-    """What the fp64 accumulators hold before the launch adds to them: not zero."""
-    n = 1
-    for s in shape:
-        n *= s
-    return (torch.arange(n, dtype=torch.float64, device=DEV) % 7).reshape(shape)
 
 
 def _rows(t, ld, canary, row_pad=pc.ROW_PAD, dt=torch.float32):
@@ -126,11 +115,6 @@ def _run(c, route):
     res["stats"] = (f64 - f64_0).sum(0).reshape(c.cout, 2).t().cpu() if f64 is not None else None
     cpu = lambda t: None if t is None else t.cpu()
     return Run(res, raw.cpu(), raw0.cpu(), cpu(f64), cpu(f64_0), cpu(wpart), cpu(up), cpu(up0), all(torch.equal(a, b) for a, b in zip(ins, before)))
-
-
-def _bits(a, b):
-    return torch.equal(a.view(torch.int16) if a.dtype == torch.bfloat16 else a.view(torch.int32),
-                       b.view(torch.int16) if b.dtype == torch.bfloat16 else b.view(torch.int32))
 
 
 def _got(r):
