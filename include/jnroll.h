@@ -865,6 +865,8 @@ int jn_pw_bwd_data_x3(const float* gz_dev, int g_ld, const float* w_dev, float* 
                       int n_slots, int max_wg, void* stream);
 int jn_pw_bwd_weight(const float* gz_dev, int g_ld, const float* x_dev, int x_ld, const float* tab_dev, float* gw_dev, long long M, int cout,
                      int cin, int n_slots, long long gz_slot_stride, int use_wpart, float* wpart_back_dev, int exact, void* stream);
+/* host only: the kernel launch_pw_bwd_weight gives a layer: 1 = pw_bwd_weight_kernel, 2 = pw_bwd_weight_wide_kernel (both counts >= 128) */
+int jn_pw_bwd_weight_route(int cout, int cin);
 /* Debug entries, context-free: ONE launch of a kernel that runs between the convolutions of a train-mode pass (csrc/kernels_conv.hip:
  * stem, SPP, upsample, shortcut sum, BatchNorm tables, embed_fpn linear; csrc/kernels_bwd.hip: their backward and the BatchNorm
  * sums) on caller tensors, then a wait for `stream`.  Maps are NHWC with a leading dimension that may exceed the channel count;
@@ -902,7 +904,8 @@ int jn_pw_bwd_weight(const float* gz_dev, int g_ld, const float* x_dev, int x_ld
  * 8 replicas where N * hw <= defer_max_m, else all 32.  run_mean, run_var f32 [n_stat].  Allocates an address array and frees it.
  * jn_bn_bwd_sums: reduce != 0: red [S][32][2 C] += per channel (sum g silu'(y), sum g silu'(y) zhat) over the M pixels of g, z
  * [S][M][ld] with y = sc z + sh (tab [S][3][C], flag row not read), zhat = (z - mean) invstd from save [S][C][2]; refused: C % 4 != 0,
- * C > 1024.  consts_dev given: consts [S][C][3] = (sum1 / M, sum2 / M, gamma invstd) from the replicas' totals, g_beta += sum1,
+ * C > 1280, and above 1024 a C that is no multiple of 8 (two launches over halves of whole quads).  consts_dev given: consts
+ * [S][C][3] = (sum1 / M, sum2 / M, gamma invstd) from the replicas' totals, g_beta += sum1,
  * g_gamma += sum2 over all slots; raw_moment != 0 (without reduce): the second sum is against y and is converted first.
  * jn_efpn_linear: part [N][KS][Co] = the K-slice partial sums of e [N][K] . wt [K][Co] (MFMA form where Co % 16 == 0 and K % 4 == 0,
  * else the scalar form).  Refused: the scalar form with Co > 256. */

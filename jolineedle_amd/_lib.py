@@ -176,6 +176,7 @@ SIGNATURES = {
                        [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p, C.c_int, C.c_int,
                         C.c_int, C.c_void_p]),
     "jn_pw_route": (C.c_int, [C.c_int] * 17 + [C.c_void_p]),
+    "jn_pw_bwd_weight_route": (C.c_int, [C.c_int] * 2),
     "jn_pw_bwd_data_x3": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_void_p]),
     "jn_pw_bwd_weight": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_int,

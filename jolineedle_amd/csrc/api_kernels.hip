@@ -537,6 +537,11 @@ int jn_pw_bwd_data_x3(const float* gz_dev, int g_ld, const float* w_dev, float* 
                    "no kernel took the launch, or its LDS was refused");
 }
 
+int jn_pw_bwd_weight_route(int cout, int cin) {
+  JN_CHECK(quad_chan_ok(cin) && quad_chan_ok(cout), JN_EINVAL, "jn_pw_bwd_weight_route: %d -> %d channels", cin, cout);
+  return pw_bwd_weight_wide(cout, cin) ? 2 : 1;
+}
+
 int jn_pw_bwd_weight(const float* gz_dev, int g_ld, const float* x_dev, int x_ld, const float* tab_dev, float* gw_dev, long long M, int cout,
                      int cin, int n_slots, long long gz_slot_stride, int use_wpart, float* wpart_back_dev, int exact, void* stream) {
   JN_CHECK(gz_dev && x_dev && tab_dev && gw_dev, JN_EINVAL, "jn_pw_bwd_weight: null argument");
@@ -544,7 +549,7 @@ int jn_pw_bwd_weight(const float* gz_dev, int g_ld, const float* x_dev, int x_ld
                gz_slot_stride >= M * g_ld && gz_slot_stride % 4 == 0,
            JN_EINVAL, "jn_pw_bwd_weight: M=%lld, %d -> %d channels, leading dimensions %d and %d, %d slots, g_z slots %lld apart", M, cin, cout,
            g_ld, x_ld, n_slots, gz_slot_stride);
-  const bool wide = cout >= 128 && cin >= 128;
+  const bool wide = pw_bwd_weight_wide(cout, cin);
   JN_CHECK((exact == 0 || exact == 1) && (!exact || wide), JN_EINVAL, "jn_pw_bwd_weight: exact=%d; the exact form is the wide kernel's (both channel counts >= 128)", exact);
   JN_CHECK(!use_wpart || (wpart_back_dev && !wide && (long long)cout * cin <= JN_WPART_MAX), JN_EINVAL,
            "jn_pw_bwd_weight: the replica scratch takes at most %d weights of a layer below 128 x 128, and a buffer to copy it back to", JN_WPART_MAX);

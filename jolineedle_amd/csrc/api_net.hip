@@ -596,7 +596,7 @@ int run_net_backward(jn_ctx* ctx, int ni, int N, const StemSrc& ss, int slot, hi
       float* sv = save + 2 * (cw.stat_off + c0);
       JN_CHECK(by_consumer || launch_bn_bwd_reduce(c.g + c0, c.g_ld, ptr(c.op.out) + c0, ld(c.op.out), tab_at(tab(c.op.out), c0), sv, h, c.M,
                                                    red + 2 * c0, rep_stride, s, sb) == 0,
-               JN_ESTATE, "launch_bn_bwd_reduce: %s has %d channels (whole quads, at most 1024)", c.op.name.c_str(), h);
+               JN_ESTATE, "launch_bn_bwd_reduce: %s has %d channels (whole quads, at most %d)", c.op.name.c_str(), h, JN_BN_BWD_MAX_C);
       JN_CHECK(launch_bn_bwd_consts(red + 2 * c0, rep_stride, (double)c.M, cw.gamma_dev + c0, cw.beta_dev + c0, sv, c.consts + 3 * c0,
                                     grad_of(ctx, cw.gamma_dev) + c0, grad_of(ctx, cw.beta_dev) + c0, h, s, sb, by_consumer) == 0,
                JN_ESTATE, "launch_bn_bwd_consts: %s was refused", c.op.name.c_str());

@@ -232,6 +232,13 @@ static int check_can_train(const jn_ctx* ctx, int T) {
   // batch-statistics BatchNorm on bf16-rounded pre-activations is ill-conditioned (the measurement behind
   // that statement: profiles/r03_bf16_train_probe.txt)
   JN_CHECK(ctx->cfg.act_dtype == JN_F32, JN_ESTATE, "training needs act_dtype = fp32 (bf16 is the inference mode)");
+  // every BatchNorm layer the conv-stack backward reduces must be one launch_bn_bwd_reduce takes: refused here, by name, not in the
+  // middle of a backward (a detached encoder, enc_net == the detector, has no conv-stack backward)
+  if (ctx->enc_net != JN_NET_DETECTOR)
+    for (const ConvW& cw : ctx->nets[ctx->enc_net].convs)
+      JN_CHECK(!cw.has_bn || (bn_bwd_reduce_admits(cw.cout) && (cw.prefix2.empty() || bn_bwd_reduce_admits(cw.cout / 2))), JN_EINVAL,
+               "training: BatchNorm layer %s has %d channels; the backward takes whole quads, at most %d, and above 1024 a multiple of 8",
+               cw.prefix.c_str(), cw.cout, JN_BN_BWD_MAX_C);
   return JN_OK;
 }
 

@@ -16,6 +16,10 @@ enum { JN_F32 = 0, JN_BF16 = 1 };   // storage type of an activation buffer (jn_
 // (finalize / reduce kernels) sums the replicas.
 constexpr int JN_NREP = 32;
 constexpr int JN_WPART_MAX = 16384;   // floats per replica of the weight-gradient scratch
+constexpr int JN_BN_BWD_MAX_C = 1280; // channels of one launch_bn_bwd_reduce call (above 1024: two halves; yolox-x's widest layer)
+// What launch_bn_bwd_reduce takes: whole channel quads, and above 1024 channels two halves of whole quads (pure host code; the
+// launcher returns -1 where this is false, check_can_train asks it for every BatchNorm layer before a training pass starts)
+inline bool bn_bwd_reduce_admits(int C) { return C >= 4 && C % 4 == 0 && C <= JN_BN_BWD_MAX_C && (C <= 1024 || C % 8 == 0); }
 
 // Every hot-loop kernel takes (skip_flag, skip_when): it returns at once when
 // *skip_flag >= skip_when.  The rollout points skip_flag at n_done[t] with skip_when = B,
@@ -301,6 +305,8 @@ int launch_bn_bwd_gz(float* g, int g_ld, const float* z, int z_ld, ChanTab t, co
 // tensor fits, else straight into gw; launch_wpart_reduce folds the replicas into gw.
 // route (the wide kernel, N, K >= 128): 0 = the rule (split products unless JN_WW_EXACT is set), else as Conv3WRoute:
 // CW_ROUTE_SPLIT / CW_ROUTE_EXACT = pw_bwd_weight_wide_kernel<true / false>; ignored by the narrower layers' fp32 kernel
+// (the rule of launch_pw_bwd_weight, pure host code: the wide kernel takes layers of at least 128 x 128 channels in whole quads)
+inline bool pw_bwd_weight_wide(int N, int K) { return N >= 128 && K >= 128 && N % 4 == 0 && K % 4 == 0; }
 int launch_pw_bwd_weight(const float* gz, int g_ld, const float* x, int x_ld, ChanTab it, float* gw, float* wpart,
                          long long M, int N, int K, hipStream_t s, const SlotBatch& sb = SlotBatch{},
                          long long gz_slot_stride = -1, int route = 0);

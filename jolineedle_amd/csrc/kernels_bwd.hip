@@ -82,15 +82,22 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
 
 int launch_bn_bwd_reduce(const float* g, int g_ld, const float* z, int z_ld, ChanTab t, const float* save, int C,
                          long long M, double* red_out, long long rep_stride, hipStream_t s, const SlotBatch& sb) {
-  // (C <= 1024: a thread owns a channel quad, and above 256 quads no thread of the workgroup would be active)
-  if (!g || !z || !t.sc || !t.sh || !save || !red_out || C < 4 || C % 4 || C > 1024 || M < 1 || g_ld < C || z_ld < C || rep_stride < 2LL * C ||
-      sb.n < 1 || sb.n > 65535)
+  if (!g || !z || !t.sc || !t.sh || !save || !red_out || !bn_bwd_reduce_admits(C) || M < 1 || g_ld < C || z_ld < C ||
+      rep_stride < 2LL * C || sb.n < 1 || sb.n > 65535)
     return -1;
-  const int rstep = 256 / (C / 4);
+  // A thread owns a channel quad, and above 256 quads no thread of the workgroup would be active: a layer above 1024 channels
+  // (yolox-x: 1280, the widest of the YOLOX sizes and the limit here) goes as two halves of whole quads, one launch each; a
+  // half's kernel sees its own C and base pointers.  A count that does not halve into quads is refused (bn_bwd_reduce_admits).
+  const int parts = C > 1024 ? 2 : 1, Cc = C / parts;
+  const int rstep = 256 / (Cc / 4);
   const int rows_per_block = rstep * 32;
   const dim3 grid((unsigned)((M + rows_per_block - 1) / rows_per_block), sb.n);
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel, grid, dim3(256), (size_t)2 * C * sizeof(float), s, g, g_ld, z, z_ld, t, save, C, M,
-                     rows_per_block, red_out, rep_stride, sb);
+  for (int c0 = 0; c0 < C; c0 += Cc) {
+    ChanTab tc = t;
+    tc.sc += c0; tc.sh += c0;
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel, grid, dim3(256), (size_t)2 * Cc * sizeof(float), s, g + c0, g_ld, z + c0, z_ld, tc, save + 2 * c0,
+                       Cc, M, rows_per_block, red_out + 2 * c0, rep_stride, sb);
+  }
   return 0;
 }
 

@@ -263,7 +263,7 @@ static int launch_pw_bwd_weight_wide(const float* gz, int g_ld, const float* x, 
 int launch_pw_bwd_weight(const float* gz, int g_ld, const float* x, int x_ld, ChanTab it, float* gw_final, float* wpart,
                          long long M, int N, int K, hipStream_t s, const SlotBatch& sb, long long gz_slot_stride, int route) {
   const long long gz_slot = gz_slot_stride >= 0 ? gz_slot_stride : sb.grad;
-  if (N >= 128 && K >= 128 && N % 4 == 0 && K % 4 == 0) {
+  if (pw_bwd_weight_wide(N, K)) {
     static const bool exact_env = std::getenv("JN_WW_EXACT") != nullptr;
     const bool exact = route ? route == CW_ROUTE_EXACT : exact_env;
     return exact ? launch_pw_bwd_weight_wide<false>(gz, g_ld, x, x_ld, it, gw_final, M, N, K, s, sb, gz_slot)
