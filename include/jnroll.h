@@ -939,6 +939,34 @@ int jn_bn_bwd_sums(const float* g_dev, int g_ld, const float* z_dev, int z_ld, c
                    float* g_beta_dev, int reduce, int raw_moment, void* stream);
 int jn_efpn_linear(const float* e_dev, const float* wt_dev, float* part_dev, int N, int K, int Co, int KS, const int* skip_flag_dev, int skip_when,
                    void* stream);
+/* Debug entries, context-free: ONE launch of a decision-side training kernel (csrc/kernels_train.hip) on caller tensors, then a wait
+ * for `stream`.  logits f32 [B][T][nA], actions / target int64 [B][T] inside [0, nA), masks uint8 [B][T], dlogits f32 [B][T][nA].
+ * n_done_dev: NULL, or the rollout's int32 [T + 1] count of finished agents after each step; with it the executed steps are
+ * S = the first t in 1..T with n_done[t] >= B (T if none) and the rows t >= S of dlogits are zero.  JN_EINVAL before any device
+ * call: a null pointer (but the optional ones), B or T below 1, nA outside 1..256, B * T above 2^24.
+ *
+ * jn_reinforce_loss: the REINFORCE loss of jn_reinforce_step on given rollout tensors (returns, rewards f32 [B][T]): over the
+ * tokens with t < S and logit_masks != 0, loss = mean(-logp[action] adv) + entropy_weight mean(-H), adv = (returns - ret_mean) /
+ * (ret_std + 1e-8) with reward_norm, else the returns; dlogits = loss_scale d loss / d logits (zero rows elsewhere); metrics f32
+ * [6] = action loss, entropy loss, loss, sum of the selected rewards / B, selected tokens / B, S.  No selected token: 0 / 0.
+ * jn_logits_grad: dlogits = dlogprobs d logp[action] / d logits + dentropies d H / d logits for upstream gradients f32 [B][T]; either
+ * may be NULL (zeros), not both.  A token whose upstream values are both 0 gets a zero row.
+ * jn_ce_loss: the supervised loss of jn_supervised_step: cross-entropy with weight stop_weight on class 8 and 1 elsewhere, summed
+ * over the tokens with masks != 0 and divided by their count n; dlogits its gradient (zero rows elsewhere); metrics f32 [3] = loss,
+ * accuracy (the first maximum is the prediction), n / B.
+ * jn_adamw: one clip_grad_value_ + AdamW update of jn_optimizer_step_group over n elements: g' = clamp(g grad_scale, +-clip_value)
+ * (clip_value 0: no clamp), p -= lr weight_decay p, m = 0.9 m + 0.1 g', v = 0.999 v + 0.001 g'^2, p -= lr / (1 - 0.9^step) m /
+ * (sqrt(v) / sqrt(1 - 0.999^step) + 1e-8); 0.1, 0.001, lr / (1 - 0.9^step) and sqrt(1 - 0.999^step) are formed in double and rounded
+ * once, the per-element arithmetic is fp32.  JN_EINVAL: n or step below 1, a negative lr, weight_decay or clip_value. */
+int jn_reinforce_loss(const float* logits_dev, const int64_t* actions_dev, const float* returns_dev, const float* rewards_dev,
+                      const uint8_t* logit_masks_dev, const int32_t* n_done_dev, int B, int T, int nA, int reward_norm, float ret_mean,
+                      float ret_std, float entropy_weight, float loss_scale, float* dlogits_dev, float* metrics_dev, void* stream);
+int jn_logits_grad(const float* logits_dev, const int64_t* actions_dev, const float* dlogprobs_dev, const float* dentropies_dev,
+                   const int32_t* n_done_dev, int B, int T, int nA, float* dlogits_dev, void* stream);
+int jn_ce_loss(const float* logits_dev, const int64_t* target_dev, const uint8_t* masks_dev, int B, int T, int nA, float stop_weight,
+               float* dlogits_dev, float* metrics_dev, void* stream);
+int jn_adamw(float* p_dev, const float* g_dev, float* m_dev, float* v_dev, long long n, float lr, float weight_decay, int step, float clip_value,
+             float grad_scale, void* stream);
 /* Arms the following rollouts of `ctx` with that teacher (the per-step `best_action` that test_model_on_env compares
  * each chosen action with, src/supervised.py:279-405): before the decision of step t, the set of the state that
  * decision sees (position and visited patches before the step) goes to sets_dev[b * T + t] (uint8 [B,T], T =

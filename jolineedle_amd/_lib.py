@@ -199,6 +199,10 @@ SIGNATURES = {
     "jn_bn_bwd_sums": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int] +
                                  [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]),
     "jn_efpn_linear": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p]),
+    "jn_reinforce_loss": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float] * 4 + [C.c_void_p] * 3),
+    "jn_logits_grad": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p] * 2),
+    "jn_ce_loss": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_float] + [C.c_void_p] * 3),
+    "jn_adamw": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.c_void_p]),
     "jn_set_rollout_teacher":(C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "jn_set_rollout_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "jn_set_rollout_classes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),

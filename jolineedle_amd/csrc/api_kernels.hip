@@ -1,6 +1,6 @@
 // C ABI of libjnroll.so, kernel-level entries: one kernel family each on the caller's tensors, no jn_ctx, for the per-kernel tests.
 // Host code only (compiled by hipcc as C++); kernels live in kernels_*.hip.  Every argument check of an entry runs before its first
-// device call.  Sections: what the entries share, fused 1x1 backward, dense 3x3, depthwise, 1x1, glue.
+// device call.  Sections: what the entries share, fused 1x1 backward, dense 3x3, depthwise, 1x1, glue, decision-side training kernels.
 #include <cstring>
 
 #include "jn_internal.h"
@@ -765,6 +765,59 @@ int jn_efpn_linear(const float* e_dev, const float* wt_dev, float* part_dev, int
            "jn_efpn_linear: N=%d K=%d Co=%d KS=%d", N, K, Co, KS);
   hipStream_t s = (hipStream_t)stream;
   return run_entry<true>("jn_efpn_linear", s, [&] { return launch_efpn_linear(e_dev, wt_dev, part_dev, N, K, Co, KS, skip_flag_dev, skip_when, s); });
+}
+
+}  // extern "C"
+
+// ---- decision-side training kernels on caller tensors (kernels_train.hip) ------------------------------------------------------------
+// The three loss kernels and the optimiser update, one launch each.  The launchers refuse nothing, so every range is the entry's:
+// B * T tokens and n_actions that keep the kernels' index arithmetic in int.  Actions and targets are the caller's to keep inside
+// [0, nA) (the context's rollouts and teachers do); n_done is the rollout's int32 [T + 1] count of finished agents per step.
+static bool tokens_ok(int B, int T, int nA) { return B >= 1 && T >= 1 && nA >= 1 && nA <= 256 && (long long)B * T <= (1LL << 24); }
+
+extern "C" {
+
+int jn_reinforce_loss(const float* logits_dev, const int64_t* actions_dev, const float* returns_dev, const float* rewards_dev,
+                      const uint8_t* logit_masks_dev, const int32_t* n_done_dev, int B, int T, int nA, int reward_norm, float ret_mean,
+                      float ret_std, float entropy_weight, float loss_scale, float* dlogits_dev, float* metrics_dev, void* stream) {
+  JN_CHECK(logits_dev && actions_dev && returns_dev && rewards_dev && logit_masks_dev && dlogits_dev && metrics_dev, JN_EINVAL,
+           "jn_reinforce_loss: null argument");
+  JN_CHECK(tokens_ok(B, T, nA), JN_EINVAL, "jn_reinforce_loss: B=%d T=%d nA=%d", B, T, nA);
+  LossArgs a{};
+  a.logits = logits_dev; a.actions = actions_dev; a.returns = returns_dev; a.rewards = rewards_dev; a.logit_masks = logit_masks_dev;
+  a.n_done = n_done_dev; a.dlogits = dlogits_dev; a.metrics = metrics_dev;
+  a.B = B; a.T = T; a.nA = nA; a.stop_early = n_done_dev ? 1 : 0; a.reward_norm = reward_norm ? 1 : 0;
+  a.ret_mean = ret_mean; a.ret_std = ret_std; a.entropy_weight = entropy_weight; a.scale = loss_scale;
+  hipStream_t s = (hipStream_t)stream;
+  return run_entry<true>("jn_reinforce_loss", s, [&] { return launch_reinforce_loss(a, s); });
+}
+
+int jn_logits_grad(const float* logits_dev, const int64_t* actions_dev, const float* dlogprobs_dev, const float* dentropies_dev,
+                   const int32_t* n_done_dev, int B, int T, int nA, float* dlogits_dev, void* stream) {
+  JN_CHECK(logits_dev && actions_dev && dlogits_dev && (dlogprobs_dev || dentropies_dev), JN_EINVAL, "jn_logits_grad: null argument");
+  JN_CHECK(tokens_ok(B, T, nA), JN_EINVAL, "jn_logits_grad: B=%d T=%d nA=%d", B, T, nA);
+  hipStream_t s = (hipStream_t)stream;
+  return run_entry<true>("jn_logits_grad", s, [&] {
+    return launch_logits_grad(logits_dev, actions_dev, dlogprobs_dev, dentropies_dev, n_done_dev, dlogits_dev, B, T, nA, n_done_dev ? 1 : 0, s);
+  });
+}
+
+int jn_ce_loss(const float* logits_dev, const int64_t* target_dev, const uint8_t* masks_dev, int B, int T, int nA, float stop_weight,
+               float* dlogits_dev, float* metrics_dev, void* stream) {
+  JN_CHECK(logits_dev && target_dev && masks_dev && dlogits_dev && metrics_dev, JN_EINVAL, "jn_ce_loss: null argument");
+  JN_CHECK(tokens_ok(B, T, nA), JN_EINVAL, "jn_ce_loss: B=%d T=%d nA=%d", B, T, nA);
+  hipStream_t s = (hipStream_t)stream;
+  return run_entry<true>("jn_ce_loss", s, [&] { return launch_ce_loss(logits_dev, target_dev, masks_dev, stop_weight, dlogits_dev, metrics_dev, B * T, nA, T, s); });
+}
+
+// (the betas and eps are those of jn_optimizer_step_group: torch's defaults)
+int jn_adamw(float* p_dev, const float* g_dev, float* m_dev, float* v_dev, long long n, float lr, float weight_decay, int step, float clip_value,
+             float grad_scale, void* stream) {
+  JN_CHECK(p_dev && g_dev && m_dev && v_dev, JN_EINVAL, "jn_adamw: null argument");
+  JN_CHECK(n >= 1 && n <= (1LL << 38) && step >= 1 && lr >= 0.0f && weight_decay >= 0.0f && clip_value >= 0.0f, JN_EINVAL,
+           "jn_adamw: n=%lld step=%d lr=%g weight_decay=%g clip_value=%g", n, step, lr, weight_decay, clip_value);
+  hipStream_t s = (hipStream_t)stream;
+  return run_entry<true>("jn_adamw", s, [&] { return launch_adamw(p_dev, g_dev, m_dev, v_dev, n, lr, 0.9, 0.999, 1e-8f, weight_decay, step, clip_value, grad_scale, s); });
 }
 
 }  // extern "C"

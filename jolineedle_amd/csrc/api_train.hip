@@ -699,7 +699,7 @@ int jn_optimizer_step_group(jn_ctx* ctx, int group, float lr, float weight_decay
   JN_CHECK(hi > lo, JN_ESTATE, "parameter group %d is empty", group);
   int& step = group == 0 ? ctx->adam_step : ctx->adam_step_yolox;
   step += 1;
-  launch_adamw(ctx->params + lo, ctx->grads + lo, ctx->adam_m + lo, ctx->adam_v + lo, (long long)(hi - lo), lr, 0.9f, 0.999f, 1e-8f,
+  launch_adamw(ctx->params + lo, ctx->grads + lo, ctx->adam_m + lo, ctx->adam_v + lo, (long long)(hi - lo), lr, 0.9, 0.999, 1e-8f,
                weight_decay, step, clip_value, grad_scale, (hipStream_t)stream);
   mark_params_written(ctx);
   JN_HIP(hipGetLastError());

@@ -602,7 +602,8 @@ int launch_supervised_metrics(const float* logits, const int64_t* current, const
 // de[m][k] = 0 where e[m][k] <= 0 (ReLU mask of embed_fpn.0);  gb[o] += sum_m dpe[m][o]
 int launch_relu_mask(float* de, const float* e, long long n, hipStream_t s);
 int launch_colsum_add(const float* dpe, long long M, int Co, float* gb, hipStream_t s);
-int launch_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
+// (the betas are doubles: the bias corrections are formed in double from them, the per-element arithmetic is fp32)
+int launch_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, double beta1, double beta2,
                  float eps, float wd, int step, float clip, float grad_scale, hipStream_t s);
 
 }  // namespace jnr

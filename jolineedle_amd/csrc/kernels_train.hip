@@ -726,27 +726,32 @@ int launch_colsum_add(const float* dpe, long long M, int Co, float* gb, hipStrea
 // weight_decay .01) over the flat arena; grad_scale folds the 1/world_size of the all-reduce ----
 __global__ __launch_bounds__(TB) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, long long n, float lr,
-                                                   float beta1, float beta2, float eps, float wd, float bc1, float bc2,
-                                                   float clip, float grad_scale) {
+                                                   float beta1, float beta2, float omb1, float omb2, float eps, float wd,
+                                                   float step_size, float bc2_sqrt, float clip, float grad_scale) {
   const long long i = (long long)blockIdx.x * TB + threadIdx.x;
   if (i >= n) return;
   float gr = g[i] * grad_scale;
   if (clip > 0.0f) gr = fminf(fmaxf(gr, -clip), clip);
   float pv = p[i];
   pv *= 1.0f - lr * wd;
-  const float mi = beta1 * m[i] + (1.0f - beta1) * gr;
-  const float vi = beta2 * v[i] + (1.0f - beta2) * gr * gr;
+  const float mi = beta1 * m[i] + omb1 * gr;
+  const float vi = beta2 * v[i] + omb2 * gr * gr;
   m[i] = mi; v[i] = vi;
-  const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
-  pv -= (lr / bc1) * (mi / denom);
+  const float denom = sqrtf(vi) / bc2_sqrt + eps;
+  pv -= step_size * (mi / denom);
   p[i] = pv;
 }
 
-int launch_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
+// Everything that is a function of the betas and the step is formed in double from the double betas, as torch forms it in Python
+// floats, and rounded once: 1 - beta (omb1, omb2), the step size lr / (1 - beta1^step) and sqrt(1 - beta2^step).  Formed in fp32
+// from 0.999f = 0.99900001..., 1 - beta2 is 1.3e-5 below 0.001: v came out 1.3e-5 low at every step, which the fp32 bias correction
+// 1 - powf(0.999f, step) shared at the first steps from zero moments and lost with the step count, leaving updates up to 1e-5 off.
+int launch_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, double beta1, double beta2,
                  float eps, float wd, int step, float clip, float grad_scale, hipStream_t s) {
-  const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
-  hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + TB - 1) / TB)), dim3(TB), 0, s, p, g, m, v, n, lr, beta1, beta2,
-                     eps, wd, bc1, bc2, clip, grad_scale);
+  const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+  const float step_size = (float)((double)lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+  hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + TB - 1) / TB)), dim3(TB), 0, s, p, g, m, v, n, lr, (float)beta1, (float)beta2,
+                     (float)(1.0 - beta1), (float)(1.0 - beta2), eps, wd, step_size, bc2_sqrt, clip, grad_scale);
   return 0;
 }
 
