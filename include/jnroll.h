@@ -1003,6 +1003,44 @@ int jn_set_rollout_keys(jn_ctx* ctx, const uint64_t* keys_host, int n);
  * previous one).  JN_EINVAL: a null ctx, n < 1 with a table, an id outside 0 .. 99 (nn.Embedding raises on it; the
  * message names the agent and the id; the armed table is then left as it was). */
 int jn_set_rollout_classes(jn_ctx* ctx, const int64_t* classes_host, int n);
+/* Invalid-action masking of the following rollouts of `ctx` (opt-in; not in the reference, whose env clamps a move that
+ * leaves the grid).  Before the decision of step t every agent, finished ones included, gets an action set M, a uint16
+ * whose bit a says that action a may be taken.  It is formed from the agent's position, its grid (its own extent in
+ * ragged mode) and `visited` before this step's update (the current cell is marked); a move a < 8 is inside when its
+ * target lies on the grid and fresh when it is inside and its target is unvisited:
+ *   JN_MASK_NONE       no set is formed: every result is what it was without this call
+ *   JN_MASK_GRID       M = the moves that are inside
+ *   JN_MASK_UNVISITED  M = the fresh moves, or when there is none the moves that are inside
+ * A set that is still empty (a 1 x 1 grid) becomes all of 0..7; with n_actions == 9 STOP is always a member, and in
+ * JN_MODE_FORCED so is the forced action.  Under M the log-probability, the entropy, the greedy maximum (the first one)
+ * and the sampled action (inverse CDF over the members in index order at the unmasked rollout's Philox uniform; the last
+ * member when none passes) are those of the softmax over the members' logits; a logit outside M is never read.  The
+ * outputs' logits stay the head's.  The set of step t goes to a buffer of the context and, with sets_out_dev (uint16
+ * [B,T], the caller's, alive during the rollouts; columns past the executed steps are 0), to sets_out_dev[b * T + t].
+ * jn_reinforce_step forms its loss, and jn_reinforce_backward its gradient, under the sets of the forward they
+ * differentiate: d logp / d logits_j = [j == a] - p_j and d H / d logits_j = -p_j (logp_j + H) for j in M, exactly 0
+ * elsewhere.  Arming between a jn_reinforce_forward and its backward makes that forward stale (JN_ESTATE from the
+ * backward), as jn_set_activation_slots does; disarming does not.  Sticky until set again; policy 0 disarms.  Needs no
+ * device.  JN_EINVAL: a null ctx, a policy outside 0..2 (what was armed stays). */
+enum { JN_MASK_NONE = 0, JN_MASK_GRID = 1, JN_MASK_UNVISITED = 2 };
+int jn_set_rollout_action_mask(jn_ctx* ctx, int policy, uint16_t* sets_out_dev);
+/* The action sets of jn_set_rollout_action_mask for N given states, context-free, one launch on `stream`:
+ * positions int64 [N][2] = (y, x), visited uint8 [N][Gh][Gw], extents int32 [N][2] = (gh, gw) or NULL (Gh, Gw), forced
+ * int64 [N] or NULL, policy 1 or 2, nA 8 or 9; sets_dev uint16 [N].  JN_EINVAL before any device call: a null pointer
+ * (but the optional ones), N, Gh or Gw below 1, another policy or nA.  Positions and extents are the caller's to keep on
+ * the grid. */
+int jn_action_sets(const int64_t* positions_dev, const uint8_t* visited_dev, const int32_t* extents_dev, const int64_t* forced_dev,
+                   int N, int Gh, int Gw, int policy, int nA, uint16_t* sets_dev, void* stream);
+/* jn_reinforce_loss and jn_logits_grad under action sets sets_dev uint16 [B][T] (debug entries like them; nA at most 16):
+ * softmax, entropy and gradient over the members of each token's set, gradient exactly 0 elsewhere; the action of a
+ * counted token must be a member and no counted token's set empty.  Sets that hold all nA bits give the bits of the
+ * unmasked entries. */
+int jn_reinforce_loss_masked(const float* logits_dev, const int64_t* actions_dev, const float* returns_dev, const float* rewards_dev,
+                             const uint8_t* logit_masks_dev, const int32_t* n_done_dev, int B, int T, int nA, int reward_norm,
+                             float ret_mean, float ret_std, float entropy_weight, float loss_scale, float* dlogits_dev,
+                             float* metrics_dev, const uint16_t* sets_dev, void* stream);
+int jn_logits_grad_masked(const float* logits_dev, const int64_t* actions_dev, const float* dlogprobs_dev, const float* dentropies_dev,
+                          const int32_t* n_done_dev, int B, int T, int nA, float* dlogits_dev, const uint16_t* sets_dev, void* stream);
 /* Number of steps S the last rollout executed (reference tensor width).  Synchronises
  * on `stream`. */
 int jn_rollout_steps(jn_ctx* ctx, int* n_steps, void* stream);

@@ -206,6 +206,10 @@ SIGNATURES = {
     "jn_set_rollout_teacher":(C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "jn_set_rollout_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "jn_set_rollout_classes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "jn_set_rollout_action_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "jn_action_sets": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 2),
+    "jn_reinforce_loss_masked": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float] * 4 + [C.c_void_p] * 4),
+    "jn_logits_grad_masked": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p] * 3),
     "jn_rollout_steps": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "jn_last_timing": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "jn_set_profiling": (C.c_int, [C.c_void_p, C.c_int]),

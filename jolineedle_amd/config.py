@@ -112,6 +112,8 @@ def get_args(args=None):
     p.add_argument("--no-recurrent-embedding", action="store_true")
     p.add_argument("--eval-max-per-cell", type=int, default=64,
                    help="multistart evaluation: survivors of the per-patch NMS that are scored, per patch (not a reference flag)")
+    p.add_argument("--action-mask", type=str, default=None, choices=["grid", "unvisited"],
+                   help="rollouts decide among the moves that stay on the grid / that reach an unvisited cell (not a reference flag)")
     return p.parse_args(args)
 
 
@@ -132,6 +134,7 @@ def args_to_config(args):
     # ReinforceTrainer.training_step hands batch["class_id"] to the rollout's class tokens only when set (ours, no flag:
     # the reference's REINFORCE loop feeds zeros, src/reinforce.py:128-129)
     t.class_tokens = False
+    t.action_mask = args.action_mask                   # RolloutRunner.rollout (ours, opt-in)
     t.stop_weight, t.entropy_weight, t.reward_norm = args.stop_weight, args.entropy_weight, args.reward_norm
     t.merge_bboxes, t.failure_select_rate = args.merge_bboxes, args.failure_select_rate
     t.port_ddp = args.port_ddp

@@ -802,6 +802,34 @@ int jn_logits_grad(const float* logits_dev, const int64_t* actions_dev, const fl
   });
 }
 
+int jn_reinforce_loss_masked(const float* logits_dev, const int64_t* actions_dev, const float* returns_dev, const float* rewards_dev,
+                             const uint8_t* logit_masks_dev, const int32_t* n_done_dev, int B, int T, int nA, int reward_norm,
+                             float ret_mean, float ret_std, float entropy_weight, float loss_scale, float* dlogits_dev,
+                             float* metrics_dev, const uint16_t* sets_dev, void* stream) {
+  JN_CHECK(logits_dev && actions_dev && returns_dev && rewards_dev && logit_masks_dev && dlogits_dev && metrics_dev && sets_dev, JN_EINVAL,
+           "jn_reinforce_loss_masked: null argument");
+  JN_CHECK(tokens_ok(B, T, nA) && nA <= 16, JN_EINVAL, "jn_reinforce_loss_masked: B=%d T=%d nA=%d", B, T, nA);
+  LossArgs a{};
+  a.logits = logits_dev; a.actions = actions_dev; a.returns = returns_dev; a.rewards = rewards_dev; a.logit_masks = logit_masks_dev;
+  a.n_done = n_done_dev; a.dlogits = dlogits_dev; a.metrics = metrics_dev; a.sets = sets_dev;
+  a.B = B; a.T = T; a.nA = nA; a.stop_early = n_done_dev ? 1 : 0; a.reward_norm = reward_norm ? 1 : 0;
+  a.ret_mean = ret_mean; a.ret_std = ret_std; a.entropy_weight = entropy_weight; a.scale = loss_scale;
+  hipStream_t s = (hipStream_t)stream;
+  return run_entry<true>("jn_reinforce_loss_masked", s, [&] { return launch_reinforce_loss(a, s); });
+}
+
+int jn_logits_grad_masked(const float* logits_dev, const int64_t* actions_dev, const float* dlogprobs_dev, const float* dentropies_dev,
+                          const int32_t* n_done_dev, int B, int T, int nA, float* dlogits_dev, const uint16_t* sets_dev, void* stream) {
+  JN_CHECK(logits_dev && actions_dev && dlogits_dev && sets_dev && (dlogprobs_dev || dentropies_dev), JN_EINVAL,
+           "jn_logits_grad_masked: null argument");
+  JN_CHECK(tokens_ok(B, T, nA) && nA <= 16, JN_EINVAL, "jn_logits_grad_masked: B=%d T=%d nA=%d", B, T, nA);
+  hipStream_t s = (hipStream_t)stream;
+  return run_entry<true>("jn_logits_grad_masked", s, [&] {
+    return launch_logits_grad(logits_dev, actions_dev, dlogprobs_dev, dentropies_dev, n_done_dev, dlogits_dev, B, T, nA, n_done_dev ? 1 : 0, s,
+                              sets_dev);
+  });
+}
+
 int jn_ce_loss(const float* logits_dev, const int64_t* target_dev, const uint8_t* masks_dev, int B, int T, int nA, float stop_weight,
                float* dlogits_dev, float* metrics_dev, void* stream) {
   JN_CHECK(logits_dev && target_dev && masks_dev && dlogits_dev && metrics_dev, JN_EINVAL, "jn_ce_loss: null argument");

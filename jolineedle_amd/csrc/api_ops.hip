@@ -253,6 +253,17 @@ int jn_teacher_actions(const int64_t* positions_dev, const uint8_t* visited_dev,
   return JN_OK;
 }
 
+int jn_action_sets(const int64_t* positions_dev, const uint8_t* visited_dev, const int32_t* extents_dev, const int64_t* forced_dev,
+                   int N, int Gh, int Gw, int policy, int nA, uint16_t* sets_dev, void* stream) {
+  JN_CHECK(positions_dev && visited_dev && sets_dev, JN_EINVAL, "jn_action_sets: null argument");
+  JN_CHECK(N >= 1 && Gh >= 1 && Gw >= 1 && (long long)Gh * Gw <= INT32_MAX, JN_EINVAL, "jn_action_sets: N=%d grid %dx%d", N, Gh, Gw);
+  JN_CHECK((policy == JN_MASK_GRID || policy == JN_MASK_UNVISITED) && (nA == 8 || nA == 9), JN_EINVAL,
+           "jn_action_sets: policy %d (1: grid, 2: unvisited), %d actions (8 or 9)", policy, nA);
+  launch_action_sets(positions_dev, visited_dev, extents_dev, forced_dev, N, Gh, Gw, policy, nA, sets_dev, (hipStream_t)stream);
+  JN_HIP(hipGetLastError());
+  return JN_OK;
+}
+
 int jn_teacher_walks(const int64_t* bboxes_dev, const int64_t* start_positions_dev, int B, int nb, int Gh, int Gw, int P,
                      int T, int min_keypoints, int max_keypoints, int binomial_keypoints, uint64_t seed, int capacity,
                      int64_t* positions_dev, int64_t* current_actions_dev, int64_t* next_actions_dev, int64_t* labels_dev,

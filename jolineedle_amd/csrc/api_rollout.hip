@@ -71,6 +71,15 @@ int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const
   RolloutBuffers r{out->rewards_dev, out->returns_dev, out->logprobs_dev, out->entropies_dev, out->masks_dev,
                    out->logit_masks_dev, out->positions_dev, out->actions_dev, out->logits_dev, out->final_emb_dev};
   { int rz = zero_rollout_outputs(r, tsets, B, T, C, nA, s); if (rz) return rz; }
+  // jn_set_rollout_action_mask: the sets of the executed steps are written by the decision; the rest read 0
+  const int mask_policy = ctx->mask_policy;
+  if (mask_policy) {
+    JN_CHECK(nA <= 16, JN_EINVAL, "action masking: %d actions do not fit a 16-bit set", nA);
+    if (!ctx->mask_sets) { int rm = dev_alloc(ctx, &ctx->mask_sets, (size_t)c.max_batch * c.block_size); if (rm) return rm; }
+    JN_HIP(hipMemsetAsync(ctx->mask_sets, 0, (size_t)B * T * sizeof(uint16_t), s));
+    if (ctx->mask_sets_out) JN_HIP(hipMemsetAsync(ctx->mask_sets_out, 0, (size_t)B * T * sizeof(uint16_t), s));
+  }
+  if (train) ctx->train_mask_policy = mask_policy;
 
   // per-agent streams and class ids: the context's copies go up on this rollout's stream (null: not armed)
   const uint64_t* keys = nullptr;
@@ -208,6 +217,7 @@ int rollout_impl(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, const
     a.skip_flag = flag; a.skip_when = B;
     a.tok_emb_out = train ? ctx->tok_emb_train : nullptr;
     a.pdrop = train ? ctx->pdrop : 0.0f; a.drop_seed = ctx->drop_seed_used;
+    a.mask_policy = mask_policy; a.mask_sets = ctx->mask_sets; a.mask_sets_out = ctx->mask_sets_out;
     JN_CHECK(launch_gpt_step_routed(a, s) == 0, JN_ESTATE, "the decision step could not be launched (n_embd %d, block_size %d)", a.C, a.Tmax - 1);
     if (out->patches_dev)
       env_gather(e, out->patches_dev + (long long)(t + 1) * 3 * P * P, patch_stride, P, flag, B, s);
@@ -295,6 +305,16 @@ int jn_set_rollout_teacher(jn_ctx* ctx, const uint8_t* targets_dev, uint8_t* set
   JN_CHECK(ctx, JN_EINVAL, "null ctx");
   ctx->teacher_sets = sets_dev;
   ctx->teacher_targets = sets_dev ? targets_dev : nullptr;
+  return JN_OK;
+}
+
+int jn_set_rollout_action_mask(jn_ctx* ctx, int policy, uint16_t* sets_out_dev) {
+  JN_CHECK(ctx, JN_EINVAL, "jn_set_rollout_action_mask: null ctx");
+  JN_CHECK(policy >= JN_MASK_NONE && policy <= JN_MASK_UNVISITED, JN_EINVAL,
+           "jn_set_rollout_action_mask: policy %d (0: none, 1: grid, 2: unvisited)", policy);
+  ctx->mask_policy = policy;
+  ctx->mask_sets_out = policy ? sets_out_dev : nullptr;
+  if (policy) ctx->train_out_valid = false;   // a forward made before this arming is not differentiated after it
   return JN_OK;
 }
 

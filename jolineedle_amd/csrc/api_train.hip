@@ -499,7 +499,7 @@ int jn_reinforce_backward(jn_ctx* ctx, const float* dlogprobs_dev, const float* 
   const EnvState& e = ctx->env;
   int S = 0, rc;
   launch_logits_grad(out->logits_dev, out->actions_dev, dlogprobs_dev, dentropies_dev, ctx->n_done, ctx->dlogits, e.B, e.T,
-                     ctx->cfg.n_actions, ctx->last_stop_early ? 1 : 0, s);
+                     ctx->cfg.n_actions, ctx->last_stop_early ? 1 : 0, s, ctx->train_mask_policy ? ctx->mask_sets : nullptr);
   if ((rc = rollout_steps_begin(ctx, s))) return rc;
   if ((rc = reinforce_backward_gpt(ctx, out, ctx->last_stop_early ? 1 : 0, s))) return rc;
   if ((rc = rollout_steps_end(ctx, &S))) return rc;
@@ -525,6 +525,7 @@ int jn_reinforce_step(jn_ctx* ctx, int mode, const int64_t* forced_actions_dev, 
   la.B = B; la.T = T; la.nA = nA; la.stop_early = stop_early ? 1 : 0; la.reward_norm = opts->reward_norm;
   la.ret_mean = opts->ret_mean; la.ret_std = opts->ret_std; la.entropy_weight = opts->entropy_weight;
   la.scale = opts->loss_scale;
+  la.sets = ctx->train_mask_policy ? ctx->mask_sets : nullptr;      // the sets this rollout decided under
   if ((rc = rollout_steps_begin(ctx, s))) return rc;           // n_done on its way to the host ...
   launch_reinforce_loss(la, s);
   if ((rc = reinforce_backward_gpt(ctx, out, stop_early, s))) return rc;

@@ -77,4 +77,23 @@ __device__ inline EnvStepResult env_step_one(const EnvPtrs& e, int b, int action
   return r;
 }
 
+// The action set of one agent under a masking policy (jnroll.h: jn_set_rollout_action_mask): bit a of the result = action a
+// is allowed at (y, x) on a gh x gw grid whose visited bytes `vis` are rows of `row` cells.  JN_MASK_GRID keeps the moves
+// that stay inside, JN_MASK_UNVISITED those that also reach an unvisited cell (none: the moves that stay inside); a grid
+// of one cell leaves no move, then every move is allowed.  STOP (nA == 9) is always a member, and so is `forced` (< 0: none).
+__device__ inline uint32_t action_set_one(int policy, int y, int x, int gh, int gw, const uint8_t* vis, int row, int nA, int forced) {
+  uint32_t inside = 0, fresh = 0;
+  for (int a = 0; a < 8 && a < nA; ++a) {
+    const int ty = y + kActionDy[a], tx = x + kActionDx[a];
+    if (ty < 0 || ty >= gh || tx < 0 || tx >= gw) continue;
+    inside |= 1u << a;
+    if (!vis[ty * row + tx]) fresh |= 1u << a;
+  }
+  uint32_t m = (policy == JN_MASK_UNVISITED && fresh) ? fresh : inside;
+  if (!m) m = (1u << min(nA, 8)) - 1u;
+  if (nA > 8) m |= 1u << 8;
+  if (forced >= 0) m |= 1u << forced;
+  return m;
+}
+
 }  // namespace jnr

@@ -173,4 +173,67 @@ __device__ inline void gpt_decide_and_step(const GptStepArgs& a, int b, const fl
   if (r.terminated || r.truncated) atomicAdd(a.n_done + t + 1, 1);      // an integer count: order-free
 }
 
+// The same under invalid-action masking (a.mask_policy != 0, jn_set_rollout_action_mask; not in the reference): the agent's
+// action set M is formed from the state the decision sees, the Categorical is the softmax over the members' logits, and a
+// logit outside M is never read into the maximum, the sum or the entropy.  The sample walks the members in index order at the
+// uniform the unmasked decision draws; M goes to the context's buffer and the caller's.  The step's tail is the one above.
+__device__ inline void gpt_decide_and_step_masked(const GptStepArgs& a, int b, const float* lg, int len) {
+  a.cache_len[b] = len;
+  const int nA = a.nA, t = a.step;
+  const long long bt = (long long)b * a.T + t;
+  int forced = -1;
+  if (a.mode == JN_MODE_FORCED) forced = min(max((int)a.forced[bt], 0), nA - 1);
+  const EnvPtrs& e = a.env;
+  const int gh = e.extent ? e.extent[2 * b] : e.Gh, gw = e.extent ? e.extent[2 * b + 1] : e.Gw;
+  const uint32_t M = action_set_one(a.mask_policy, (int)e.positions[2 * b], (int)e.positions[2 * b + 1], gh, gw,
+                                    e.visited + (long long)b * e.Gh * e.Gw, e.Gw, nA, forced);
+  a.mask_sets[bt] = (uint16_t)M;
+  if (a.mask_sets_out) a.mask_sets_out[bt] = (uint16_t)M;
+  float m = -INFINITY;
+  int best = 0, last = 0;
+  for (int i = 0; i < nA; ++i) {
+    if (!(M >> i & 1u)) continue;
+    last = i;
+    if (lg[i] > m) { m = lg[i]; best = i; }           // first maximum among the members
+  }
+  float sum = 0.0f;
+  for (int i = 0; i < nA; ++i)
+    if (M >> i & 1u) sum += expf(lg[i] - m);
+  const float lse = m + logf(sum);
+  float ent = 0.0f;
+  for (int i = 0; i < nA; ++i)
+    if (M >> i & 1u) { const float lp = lg[i] - lse; ent -= lp * expf(lp); }
+  int act = best;
+  if (a.mode == JN_MODE_FORCED) {
+    act = forced;
+  } else if (a.mode == JN_MODE_SAMPLE) {
+    const uint64_t key = a.keys ? a.keys[2 * b] : a.seed;
+    const uint32_t idx = a.keys ? (uint32_t)a.keys[2 * b + 1] : (uint32_t)b;
+    const uint4 r = philox4x32(key, idx, (uint32_t)t, 0x53414d50u, 0u);
+    const float u = u01(r.x);
+    float cdf = 0.0f;
+    act = last;
+    for (int i = 0; i < nA; ++i) {
+      if (!(M >> i & 1u)) continue;
+      cdf += expf(lg[i] - lse);
+      if (u < cdf) { act = i; break; }
+    }
+  }
+  const float logp = lg[act] - lse;
+  const EnvStepResult r = env_step_one(a.env, b, act);
+  a.prev_action[b] = act;
+  if (a.out.rewards) a.out.rewards[bt] = r.reward;
+  if (a.out.logprobs) a.out.logprobs[bt] = logp;
+  if (a.out.entropies) a.out.entropies[bt] = ent;
+  if (a.out.actions) a.out.actions[bt] = act;
+  if (a.out.masks) a.out.masks[(long long)b * (a.T + 1) + t + 1] = r.terminated ? 0 : 1;
+  if (a.out.positions) {
+    a.out.positions[((long long)b * (a.T + 1) + t + 1) * 2] = r.y;
+    a.out.positions[((long long)b * (a.T + 1) + t + 1) * 2 + 1] = r.x;
+  }
+  if (a.out.logits)
+    for (int i = 0; i < nA; ++i) a.out.logits[bt * nA + i] = lg[i];
+  if (r.terminated || r.truncated) atomicAdd(a.n_done + t + 1, 1);
+}
+
 }  // namespace jnr

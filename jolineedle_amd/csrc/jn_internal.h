@@ -348,6 +348,10 @@ struct jn_ctx {
   // ran without a table (class 0)
   jnr::AgentTable<uint64_t, 2> keys; jnr::AgentTable<int64_t> classes;
   int64_t* classes_used = nullptr; size_t classes_used_cap = 0; int classes_used_n = 0;
+  // jn_set_rollout_action_mask: the armed policy and the caller's [B,T] buffer (or null); mask_sets: the context's own
+  // uint16 [max_batch][block_size] sets of the most recent masked rollout (allocated by the first one); train_mask_policy:
+  // the policy the most recent train-mode rollout ran under (0: its loss and backward are the unmasked ones)
+  int mask_policy = 0, train_mask_policy = 0; uint16_t* mask_sets_out = nullptr; uint16_t* mask_sets = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   bool profiling = false;
   bool bwd_timed = false;         // ev[2] / ev[3] bracket a conv-stack backward

@@ -433,6 +433,9 @@ int launch_rollout_epilogue(const RolloutBuffers& r, const int32_t* n_done, int 
 // the teacher's action set of every agent's state (jnroll.h: jn_teacher_actions); sets[b * set_stride], one wave per agent
 int launch_teacher_sets(const int64_t* positions, const uint8_t* visited, const uint8_t* targets, uint8_t* sets,
                         long long set_stride, int B, int Gh, int Gw, const int* skip_flag, int skip_when, hipStream_t s);
+// the action sets of N states under a masking policy (jnroll.h: jn_action_sets), one thread per state
+int launch_action_sets(const int64_t* positions, const uint8_t* visited, const int32_t* extents, const int64_t* forced, int N,
+                       int Gh, int Gw, int policy, int nA, uint16_t* sets, hipStream_t s);
 // the teacher's whole walks of a batch (jnroll.h: jn_teacher_walks): walk (one wave per image; target / todo bytes of the
 // grid and a ring of T steps in LDS), the scan of launch_detection_cells, detector rows.  The caller checks every limit.
 constexpr int JN_TWALK_MAX_CELLS = JN_DETCELLS_MAX_CELLS;   // 2 x 4 KB of cell bytes
@@ -514,6 +517,9 @@ struct GptStepArgs {
   int wide;                         // 1: launch_gpt_step_routed goes to launch_gpt_step_wide
   const GptLayerPtrs* layers_host;  // HOST array [n_layer] of the pointers `layers` holds on the device
   float* wide_scratch;              // gpt_wide_scratch_floats(...) floats, allocated with the workspaces
+  // jn_set_rollout_action_mask: 0 = gpt_decide_and_step; else gpt_decide_and_step_masked forms the agent's action set under
+  // this policy, decides inside it and writes it to mask_sets[b * T + t] (the context's) and mask_sets_out (the caller's, or null)
+  int mask_policy; uint16_t* mask_sets; uint16_t* mask_sets_out;
 };
 int launch_gpt_step(const GptStepArgs& a, hipStream_t s);
 
@@ -537,11 +543,13 @@ struct LossArgs {
   float* metrics;                   // [8]: action_loss, entropy_loss, loss, returns, episode_length, S
   int B, T, nA, stop_early, reward_norm;
   float ret_mean, ret_std, entropy_weight, scale;
+  const uint16_t* sets;             // [B][T] action sets of a masked rollout (jn_set_rollout_action_mask), or null = all actions
 };
 int launch_reinforce_loss(const LossArgs& a, hipStream_t s);
 // autograd bridge: d loss / d logits [B][T][nA] from d loss / d logprobs and d loss / d entropies [B][T] (either may be null)
 int launch_logits_grad(const float* logits, const int64_t* actions, const float* dlogprobs, const float* dentropies,
-                       const int32_t* n_done, float* dlogits, int B, int T, int nA, int stop_early, hipStream_t s);
+                       const int32_t* n_done, float* dlogits, int B, int T, int nA, int stop_early, hipStream_t s,
+                       const uint16_t* sets = nullptr);      // sets: as LossArgs::sets
 // one trainable tensor of the flat arena: packing kind (api_ctx.hip PackKind) and dimensions; `off` is its offset both in the
 // packed arena and in a reference-layout buffer of the same size
 struct ArenaSeg { long long off, numel; int kind, d0, d1, d2; };

@@ -405,6 +405,25 @@ int launch_teacher_sets(const int64_t* positions, const uint8_t* visited, const 
   return 0;
 }
 
+// The action sets of N given states under a masking policy: action_set_one (jn_device.h), the function the masked decision
+// of a rollout calls, on caller arrays — one thread per state.
+__global__ __launch_bounds__(256) void action_sets_kernel(const long long* __restrict__ pos, const uint8_t* __restrict__ visited,
+                                                          const int32_t* __restrict__ extents, const long long* __restrict__ forced,
+                                                          int N, int Gh, int Gw, int policy, int nA, uint16_t* __restrict__ sets) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  const int gh = extents ? min(extents[2 * n], Gh) : Gh, gw = extents ? min(extents[2 * n + 1], Gw) : Gw;   // reads stay inside `visited`
+  const int f = forced ? min(max((int)forced[n], 0), nA - 1) : -1;
+  sets[n] = (uint16_t)action_set_one(policy, (int)pos[2 * n], (int)pos[2 * n + 1], gh, gw, visited + (long long)n * Gh * Gw, Gw, nA, f);
+}
+
+int launch_action_sets(const int64_t* positions, const uint8_t* visited, const int32_t* extents, const int64_t* forced, int N,
+                       int Gh, int Gw, int policy, int nA, uint16_t* sets, hipStream_t s) {
+  hipLaunchKernelGGL(action_sets_kernel, dim3((N + 255) / 256), dim3(256), 0, s, (const long long*)positions, visited, extents,
+                     (const long long*)forced, N, Gh, Gw, policy, nA, sets);
+  return 0;
+}
+
 // The teacher's whole walk (NeedleSimpleEnv.generate_sample_indices, src/env/simple_env.py:481-588; the rule and its two
 // Philox streams are stated at jnroll.h: jn_teacher_walks and, on plain integers, by trajectory.teacher_walks).  One wave
 // per image.  The draws and the walk are sequential: every lane computes the same draw and the same position, the values

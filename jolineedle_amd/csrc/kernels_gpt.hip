@@ -420,7 +420,7 @@ __global__ __launch_bounds__(NT) void gpt_step_kernel(GptStepArgs a) {
     if (a.logits_rows && tid < a.nA) a.logits_rows[(long long)b * a.logits_stride + tid] = lg[tid];
     return;
   }
-  if (tid == 0) gpt_decide_and_step(a, b, lg, len);
+  if (tid == 0) { if (a.mask_policy) gpt_decide_and_step_masked(a, b, lg, len); else gpt_decide_and_step(a, b, lg, len); }
 }
 
 // The agent's K / V rows of a layer are staged in LDS when the workgroup then still fits a CU's 160 KB (every model of

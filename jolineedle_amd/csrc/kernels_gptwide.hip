@@ -391,7 +391,7 @@ __global__ __launch_bounds__(WT) void gptw_tail_kernel(GptStepArgs a, WideLn ln)
     if (a.logits_rows && tid < nA) a.logits_rows[(long long)b * a.logits_stride + tid] = lg[tid];
     return;
   }
-  if (tid == 0) gpt_decide_and_step(a, b, lg, len);
+  if (tid == 0) { if (a.mask_policy) gpt_decide_and_step_masked(a, b, lg, len); else gpt_decide_and_step(a, b, lg, len); }
 }
 
 }  // namespace

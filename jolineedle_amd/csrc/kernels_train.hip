@@ -21,6 +21,13 @@ constexpr int GB = 1024;
 // ---- REINFORCE loss (src/reinforce.py:217-265) and d loss / d logits --------------------------
 // loss = -sum(logp*adv*m)/sum(m) + w * (-sum(H*m)/sum(m)),  adv = (returns - mean)/(std + 1e-8)
 // dlogits[b,t,j] = scale * m/sum(m) * ( -adv*(1[j==a] - p_j) + w * p_j*(log p_j + H) )
+// MASKED (jn_set_rollout_action_mask): softmax, entropy and gradient over the members of the token's action set a.sets[i]
+// alone, in index order — a logit outside the set is never read and its gradient is exactly 0.  in_set folds to true in the
+// unmasked instantiation, which is the kernel as it was.
+template <bool MASKED>
+__device__ __forceinline__ bool in_set(unsigned set, int j) { return !MASKED || (set >> j & 1u); }
+
+template <bool MASKED>
 __global__ __launch_bounds__(TB) void reinforce_loss_kernel(LossArgs a) {
   __shared__ float red[TB];
   __shared__ float tot[4];
@@ -46,17 +53,19 @@ __global__ __launch_bounds__(TB) void reinforce_loss_kernel(LossArgs a) {
     const bool m = t < S && a.logit_masks[i];
     if (!m) { for (int j = 0; j < a.nA; ++j) dl[j] = 0.0f; continue; }
     const float* lg = a.logits + (long long)i * a.nA;
+    const unsigned set = MASKED ? a.sets[i] : 0u;
     float mx = -INFINITY;
-    for (int j = 0; j < a.nA; ++j) mx = fmaxf(mx, lg[j]);
+    for (int j = 0; j < a.nA; ++j) if (in_set<MASKED>(set, j)) mx = fmaxf(mx, lg[j]);
     float se = 0.0f;
-    for (int j = 0; j < a.nA; ++j) se += expf(lg[j] - mx);
+    for (int j = 0; j < a.nA; ++j) if (in_set<MASKED>(set, j)) se += expf(lg[j] - mx);
     const float lse = mx + logf(se);
     float H = 0.0f;
-    for (int j = 0; j < a.nA; ++j) { const float lp = lg[j] - lse; H -= lp * expf(lp); }
+    for (int j = 0; j < a.nA; ++j) if (in_set<MASKED>(set, j)) { const float lp = lg[j] - lse; H -= lp * expf(lp); }
     const int act = (int)a.actions[i];
     const float adv = a.reward_norm ? (a.returns[i] - a.ret_mean) / (a.ret_std + 1e-8f) : a.returns[i];
     const float k = a.scale / msum;
     for (int j = 0; j < a.nA; ++j) {
+      if (!in_set<MASKED>(set, j)) { dl[j] = 0.0f; continue; }
       const float lp = lg[j] - lse, p = expf(lp);
       dl[j] = k * (-adv * ((j == act ? 1.0f : 0.0f) - p) + a.entropy_weight * p * (lp + H));
     }
@@ -85,7 +94,8 @@ __global__ __launch_bounds__(TB) void reinforce_loss_kernel(LossArgs a) {
 }
 
 int launch_reinforce_loss(const LossArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(reinforce_loss_kernel, dim3(1), dim3(TB), 0, s, a);
+  if (a.sets) hipLaunchKernelGGL(reinforce_loss_kernel<true>, dim3(1), dim3(TB), 0, s, a);
+  else hipLaunchKernelGGL(reinforce_loss_kernel<false>, dim3(1), dim3(TB), 0, s, a);
   return 0;
 }
 
@@ -93,10 +103,12 @@ int launch_reinforce_loss(const LossArgs& a, hipStream_t s) {
 // logp = log_softmax(logits), lp = logp[action], H = -sum p logp  (src/reinforce.py:73-90):
 //   d lp / d logits_j = [j == action] - p_j          d H / d logits_j = -p_j (logp_j + H)
 // Steps the rollout did not execute (t >= S) get zero rows.
+// MASKED: as in reinforce_loss_kernel, under sets [B][T].
+template <bool MASKED>
 __global__ __launch_bounds__(TB) void logits_grad_kernel(const float* __restrict__ logits, const long long* __restrict__ actions,
                                                          const float* __restrict__ dlogprobs, const float* __restrict__ dentropies,
                                                          const int* __restrict__ n_done, float* __restrict__ dlogits, int B,
-                                                         int T, int nA, int stop_early) {
+                                                         int T, int nA, int stop_early, const uint16_t* __restrict__ sets) {
   int S = T;
   if (stop_early)
     for (int t = 1; t <= T; ++t)
@@ -108,24 +120,40 @@ __global__ __launch_bounds__(TB) void logits_grad_kernel(const float* __restrict
   const float glp = dlogprobs ? dlogprobs[i] : 0.0f, gh = dentropies ? dentropies[i] : 0.0f;
   if (t >= S || (glp == 0.0f && gh == 0.0f)) { for (int j = 0; j < nA; ++j) dl[j] = 0.0f; return; }
   const float* lg = logits + (long long)i * nA;
+  const unsigned set = MASKED ? sets[i] : 0u;
   float mx = -INFINITY;
-  for (int j = 0; j < nA; ++j) mx = fmaxf(mx, lg[j]);
+  for (int j = 0; j < nA; ++j) if (in_set<MASKED>(set, j)) mx = fmaxf(mx, lg[j]);
   float se = 0.0f;
-  for (int j = 0; j < nA; ++j) se += expf(lg[j] - mx);
+  for (int j = 0; j < nA; ++j) if (in_set<MASKED>(set, j)) se += expf(lg[j] - mx);
   const float lse = mx + logf(se);
   float H = 0.0f;
-  for (int j = 0; j < nA; ++j) { const float lp = lg[j] - lse; H -= lp * expf(lp); }
+  for (int j = 0; j < nA; ++j) if (in_set<MASKED>(set, j)) { const float lp = lg[j] - lse; H -= lp * expf(lp); }
   const int act = (int)actions[i];
   for (int j = 0; j < nA; ++j) {
+    if (!in_set<MASKED>(set, j)) { dl[j] = 0.0f; continue; }
     const float lp = lg[j] - lse, pj = expf(lp);
-    dl[j] = glp * ((j == act ? 1.0f : 0.0f) - pj) - gh * pj * (lp + H);
+    if constexpr (!MASKED) {
+      dl[j] = glp * ((j == act ? 1.0f : 0.0f) - pj) - gh * pj * (lp + H);
+    } else {
+      // The same expression with its last step pinned to what the unmasked instantiation compiles to, so that full sets give its
+      // bits: the compiler walks that loop two classes at a time and contracts the last step of a pair into one fma, while the odd
+      // class left over at the end (nA = 9: STOP) gets a rounded product and a difference.  Left to itself, this instantiation's
+      // branchy loop got the product and the difference everywhere.
+      const float x = (j == act ? 1.0f : 0.0f) - pj, y = gh * pj * (lp + H);
+      dl[j] = ((nA & 1) && j == nA - 1) ? __fsub_rn(__fmul_rn(glp, x), y) : fmaf(glp, x, -y);
+    }
   }
 }
 
 int launch_logits_grad(const float* logits, const int64_t* actions, const float* dlogprobs, const float* dentropies,
-                       const int32_t* n_done, float* dlogits, int B, int T, int nA, int stop_early, hipStream_t s) {
-  hipLaunchKernelGGL(logits_grad_kernel, dim3((B * T + TB - 1) / TB), dim3(TB), 0, s, logits, (const long long*)actions, dlogprobs,
-                     dentropies, n_done, dlogits, B, T, nA, stop_early);
+                       const int32_t* n_done, float* dlogits, int B, int T, int nA, int stop_early, hipStream_t s, const uint16_t* sets) {
+  const dim3 grid((B * T + TB - 1) / TB);
+  if (sets)
+    hipLaunchKernelGGL(logits_grad_kernel<true>, grid, dim3(TB), 0, s, logits, (const long long*)actions, dlogprobs, dentropies, n_done,
+                       dlogits, B, T, nA, stop_early, sets);
+  else
+    hipLaunchKernelGGL(logits_grad_kernel<false>, grid, dim3(TB), 0, s, logits, (const long long*)actions, dlogprobs, dentropies, n_done,
+                       dlogits, B, T, nA, stop_early, sets);
   return 0;
 }
 

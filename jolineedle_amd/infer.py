@@ -36,7 +36,8 @@ def pad_to_patch_multiple(image: torch.Tensor, patch_size: int) -> torch.Tensor:
 @torch.no_grad()
 def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequence] = None, sample_actions: bool = True,
                  do_detection: Optional[bool] = None, batch_size: Optional[int] = None, device_metrics: bool = False,
-                 token_positions: Optional[str] = None, streams: str = "loop", class_ids=None) -> Dict:
+                 token_positions: Optional[str] = None, streams: str = "loop", class_ids=None,
+                 action_mask: Optional[str] = None) -> Dict:
     """`images`: [C, H, W] tensors (uint8 0..255 or float 0..1) of any sizes; `targets`: per image an [n, 4] xyxy list /
     tensor or None.  Returns per-image boxes ([n, 7] in full-image pixels or None), positions, step counts, durations
     and — where targets are given — the mean of the reference's metrics.
@@ -65,7 +66,10 @@ def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequ
 
     class_ids: one class per image (a tensor or a sequence): the class token of image i's rollout is row class_ids[i] of
     ``embed_class`` (``ReinforceTrainer.rollout(classes=...)``), in the loop and in every chunk alike — what a
-    class-conditioned policy was trained under (src/supervised.py:317-331); None = class 0."""
+    class-conditioned policy was trained under (src/supervised.py:317-331); None = class 0.
+
+    action_mask: "grid" / "unvisited" / None, handed to every rollout (``RolloutRunner.rollout``): the sampled or greedy
+    decisions are then made among the allowed actions only; None = ``config.action_mask``."""
     class_ids = image_classes(class_ids, len(images))
     cfg, dev = trainer.config, trainer.device
     P, T = int(cfg.patch_size), int(cfg.max_seq_len)
@@ -75,7 +79,7 @@ def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequ
         raise ValueError(f"streams must be 'loop' or 'batch', got {streams!r}")
     if batch_size is not None:
         return _infer_batched(trainer, images, targets, sample_actions, do_detection, int(batch_size), device_metrics,
-                              token_positions, streams, class_ids)
+                              token_positions, streams, class_ids, action_mask)
     if streams != "loop":
         raise ValueError("streams='batch' needs batch_size: the per-image loop has no batch")
     if device_metrics:
@@ -91,7 +95,7 @@ def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequ
         env = NeedleGeneralEnv(x, bboxes, P, T, 1, bool(getattr(cfg, "stop_enabled", False)))
         t0 = time.perf_counter()
         ro = trainer.rollout(env, do_detection=do_detection, sample_actions=sample_actions, token_positions=token_positions,
-                             classes=walk_classes(class_ids, [i]))
+                             classes=walk_classes(class_ids, [i]), action_mask=action_mask)
         torch.cuda.synchronize(dev)
         res["duration_ms"].append((time.perf_counter() - t0) * 1e3)
         offsets = ro["positions"][:, :, [1, 0]] * P                       # (y, x) grid -> (x, y) pixels
@@ -110,7 +114,7 @@ def infer_images(trainer, images: Sequence[torch.Tensor], targets: Optional[Sequ
 
 
 def _infer_batched(trainer, images, targets, sample_actions, do_detection, batch_size, device_metrics=False,
-                   token_positions=None, streams="loop", class_ids=None) -> Dict:
+                   token_positions=None, streams="loop", class_ids=None, action_mask=None) -> Dict:
     dev, P = trainer.device, int(trainer.config.patch_size)
     n = len(images)
     res = {"boxes": [None] * n, "positions": [None] * n, "steps": [0] * n, "duration_ms": [0.0] * n}
@@ -120,7 +124,7 @@ def _infer_batched(trainer, images, targets, sample_actions, do_detection, batch
     rows = [torch.as_tensor(targets[i]).reshape(-1, 4).to(torch.long) if h else torch.zeros((1, 4), dtype=torch.long)
             for i, h in enumerate(has_tg)]
     for ch in rollout_chunks(trainer, images, rows, batch_size, sample_actions=sample_actions, do_detection=do_detection,
-                             token_positions=token_positions, streams=streams, class_ids=class_ids):
+                             token_positions=token_positions, streams=streams, class_ids=class_ids, action_mask=action_mask):
         sel, ro, steps, extents = ch["indices"], ch["rollout"], ch["steps"], ch["extents"]
         ms = ch["seconds"] * 1e3 / len(sel)                # (the walker read the step counts back: the rollout has ended)
         packed = rollout_boxes_packed(ro, P) if do_detection else None

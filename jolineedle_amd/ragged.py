@@ -22,7 +22,7 @@ from .views import ImageViews
 # padding here: the per-image loop gives an image without targets the box (0, 0, 0, 0), which marks patch (0, 0)
 INERT_BOX = (0, 0, -1, -1)
 
-_PER_STEP = ("rewards", "returns", "logprobs", "entropies", "logit_masks", "actions", "logits", "teacher_sets")
+_PER_STEP = ("rewards", "returns", "logprobs", "entropies", "logit_masks", "actions", "logits", "teacher_sets", "action_sets")
 _PER_TOKEN = ("masks", "positions", "final_emb", "det_counts", "det_boxes", "patches")
 
 
@@ -166,7 +166,7 @@ def rollouts_after(first_rollout: int, n_images: int, n_walks: int = 1) -> int:
 @torch.no_grad()
 def rollout_chunks(trainer, images: Sequence[Tensor], rows: Sequence[Tensor], batch_size: int, walks: int = 1,
                    sample_actions: bool = False, do_detection: bool = False, token_positions: Optional[str] = None,
-                   streams: str = "loop", class_ids=None, teacher_targets=None, walk_starts=None):
+                   streams: str = "loop", class_ids=None, teacher_targets=None, walk_starts=None, action_mask: Optional[str] = None):
     """The chunked rollouts behind every batched evaluation and inference: `images` ([3, Hi, Wi], rows[i] their [n_i, 4]
     boxes) `batch_size` images at a time (``plan_chunks``), every image walked K = `walks` times as ``chunk_walks`` lays
     out — the same stored image, one view-table row per walk with the same source pointer.  Yields one record per chunk:
@@ -175,7 +175,8 @@ def rollout_chunks(trainer, images: Sequence[Tensor], rows: Sequence[Tensor], ba
     readback of its masks); then leaves the trainer's rollout counter where the per-image loop would.
     teacher_targets: a callable (box rows of the chunk's images, their grid extents, the canvas grid) -> uint8
     [n, Gh, Gw]; the rollouts then carry "teacher_sets", "targets" is that grid per agent on the device (else None), and
-    the found-ratios count these cells instead of the env's bbox masks.  class_ids: one class per IMAGE, or None."""
+    the found-ratios count these cells instead of the env's bbox masks.  class_ids: one class per IMAGE, or None.
+    action_mask: handed to every rollout (``RolloutRunner.rollout``); every agent's sets are formed on its own extent."""
     class_ids = image_classes(class_ids, len(images))
     if streams not in ("loop", "batch"):
         raise ValueError(f"streams must be 'loop' or 'batch', got {streams!r}")
@@ -200,7 +201,8 @@ def rollout_chunks(trainer, images: Sequence[Tensor], rows: Sequence[Tensor], ba
         t0 = time.perf_counter()
         ro = trainer.rollout(env, sample_actions=sample_actions, do_detection=do_detection, bbox_lists=False,
                              start_positions=plan["starts"], token_positions=token_positions, agent_keys=plan["keys"],
-                             classes=plan["classes"], teacher=tg_grid is not None, teacher_targets=tg_grid)
+                             classes=plan["classes"], teacher=tg_grid is not None, teacher_targets=tg_grid,
+                             action_mask=action_mask)
         steps = own_steps(ro)
         seconds = time.perf_counter() - t0
         found = found_ratios(env, ro, steps, masks=None if tg_grid is None else tg_grid.bool())

@@ -19,7 +19,7 @@ class ReinforceTrainer(Trainer, RolloutRunner):
     def __init__(self, config, model, logger=None, train_dataset=None, test_dataset=None, rank: int = 0):
         Trainer.__init__(self, config, model, logger, train_dataset, test_dataset, rank)
         RolloutRunner.__init__(self, model, config.max_seq_len, config.stop_enabled, getattr(config, "seed", 0), rank,
-                               getattr(config, "agent_streams", "batch"))
+                               getattr(config, "agent_streams", "batch"), getattr(config, "action_mask", None))
         self.entropy_weight = config.entropy_weight
         self.best_metric_name = "prop_patches_found"
         self.last_return_values = []
@@ -139,12 +139,12 @@ class ReinforceTrainer(Trainer, RolloutRunner):
     # ---- training: one REINFORCE iteration (src/reinforce.py:302-353) ------------------------
     def train_iteration(self, env: NeedleGeneralEnv, sample_actions: bool = True, forced_actions=None,
                         start_positions=None, stop_early: bool = True, optimizer_step: bool = True,
-                        process_group=None, agent_keys=None, classes=None) -> Dict[str, torch.Tensor]:
+                        process_group=None, agent_keys=None, classes=None, action_mask: str = None) -> Dict[str, torch.Tensor]:
         """rollout (train-mode BatchNorm) -> compute_metrics -> backward -> [all-reduce] -> clip + AdamW,
-        all inside the engine.  Returns the metrics of src/reinforce.py:243-252.  `agent_keys`, `classes`: see
-        ``rollout``."""
+        all inside the engine.  Returns the metrics of src/reinforce.py:243-252.  `agent_keys`, `classes`, `action_mask`
+        (the loss and its gradient are then those of the masked Categorical): see ``rollout``."""
         # (a train-mode rollout is recurrent whatever the config says: see ``rollout`` on "sequence")
-        call = _RolloutCall(self, env, sample_actions, forced_actions, start_positions, agent_keys, classes, "recurrent")
+        call = _RolloutCall(self, env, sample_actions, forced_actions, start_positions, agent_keys, classes, "recurrent", action_mask)
         eng, buf, stream = call.eng, call.buf, call.stream
         self._grad_arena()                      # bound to the engine before its backward writes it
         self.iter_num += 1
@@ -176,6 +176,7 @@ class ReinforceTrainer(Trainer, RolloutRunner):
             if self.config.reward_norm:
                 self._compute_last_returns_mean_std()
         self._last_train_buffers = buf
+        self._last_action_sets = call.action_sets
         res = {"action_loss": m[0], "entropy_loss": m[1], "loss": m[2], "returns": m[3], "episode_length": m[4], "steps": S}
         for k, v in yolo_losses.items():
             res["yolo_" + k] = v
@@ -216,12 +217,12 @@ class ReinforceTrainer(Trainer, RolloutRunner):
 
     @torch.no_grad()
     def eval_on_batch(self, env: NeedleGeneralEnv, do_detection: bool = None, merge_bboxes: bool = None,
-                      token_positions: str = None) -> Dict[str, torch.Tensor]:
+                      token_positions: str = None, action_mask: str = None) -> Dict[str, torch.Tensor]:
         """``eval_on_sample`` of the reference (src/reinforce.py:424-497) without the plotting: greedy rollout,
         rollout metrics incl. the env's found-ratios, and — with detection — mAP-50 of the boxes found along the
         trajectories (moved to full-image coordinates, optionally merged) plus the detector's mAP on every patch that
         holds a box (`yolo_map`).  The reference evaluates one image at a time; any batch size works here (the
-        per-image metrics it reads from index 0 stay index 0).  `token_positions`: see ``rollout``."""
+        per-image metrics it reads from index 0 stay index 0).  `token_positions`, `action_mask`: see ``rollout``."""
         from .detection import patch_bboxes2full_image
         from .ragged import detection_eval_metrics
         cfg = self.config
@@ -229,7 +230,8 @@ class ReinforceTrainer(Trainer, RolloutRunner):
             do_detection = bool(getattr(cfg, "detection_enabled", False))
         if merge_bboxes is None:
             merge_bboxes = bool(getattr(cfg, "merge_bboxes", False))
-        ro = self.rollout(env, sample_actions=False, do_detection=do_detection, token_positions=token_positions)
+        ro = self.rollout(env, sample_actions=False, do_detection=do_detection, token_positions=token_positions,
+                          action_mask=action_mask)
         metrics = self.compute_metrics(ro, env)
         if do_detection:
             targets = env.get_detection_targets()
@@ -242,7 +244,7 @@ class ReinforceTrainer(Trainer, RolloutRunner):
     @torch.no_grad()
     def eval_on_images(self, images, bboxes, batch_size: int, do_detection: bool = None,
                        merge_bboxes: bool = None, device_metrics: bool = False, token_positions: str = None,
-                       class_ids=None) -> Dict[str, list]:
+                       class_ids=None, action_mask: str = None) -> Dict[str, list]:
         """The per-image ``all_metrics`` of the reference's ``test()`` (src/reinforce.py:383-392) without its loop of
         ``B = 1`` envs: `images` ([3, Hi, Wi] tensors of any sizes, uint8 read in place or float 0..1) are evaluated
         `batch_size` at a time (``ragged.plan_chunks``), every agent inside its own image.  Returns, for every key of
@@ -255,7 +257,8 @@ class ReinforceTrainer(Trainer, RolloutRunner):
         ``rollout_boxes_packed`` -> (merge_bboxes) ``merge_boxes_device`` -> ``map_50_device(per_image=True)`` without
         leaving it, the targets are merged there too; one readback per chunk.  Same keys; `map` equals the host
         path's up to fp32 storage; the `yolo_*` entries are computed as without it.  `token_positions`: see ``rollout``.
-        `class_ids`: one class per image (a tensor or a sequence) behind the class token of its walk; None = class 0."""
+        `class_ids`: one class per image (a tensor or a sequence) behind the class token of its walk; None = class 0.
+        `action_mask`: see ``rollout``."""
         from .ragged import eval_image_chunks, image_classes, rollout_chunks
         class_ids = image_classes(class_ids, len(images))
         if do_detection is None:
@@ -264,7 +267,7 @@ class ReinforceTrainer(Trainer, RolloutRunner):
             merge_bboxes = bool(getattr(self.config, "merge_bboxes", False))
         rows = [torch.as_tensor(b).reshape(-1, 4).to(torch.long) for b in bboxes]
         chunks = rollout_chunks(self, images, rows, batch_size, do_detection=do_detection, token_positions=token_positions,
-                                class_ids=class_ids)
+                                class_ids=class_ids, action_mask=action_mask)
         per_image = eval_image_chunks(self, self.yolox_model(), chunks, do_detection, merge_bboxes, device_metrics)
         out: Dict[str, list] = {}
         for tail, ro_b in per_image:                      # compute_metrics in image order: the reward-norm window's order

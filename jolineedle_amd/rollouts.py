@@ -33,6 +33,15 @@ def _classes_table(classes, B: int):
     return tab
 
 
+ACTION_MASKS = {None: 0, "grid": 1, "unvisited": 2}      # the policies of ``jn_set_rollout_action_mask``
+
+
+def _mask_policy(action_mask) -> int:
+    if action_mask not in ACTION_MASKS:
+        raise ValueError(f"action_mask must be None, 'grid' or 'unvisited', got {action_mask!r}")
+    return ACTION_MASKS[action_mask]
+
+
 class _RolloutGraph(torch.autograd.Function):
     """Graph node behind ``rollout()["logprobs"]`` / ``["entropies"]`` of a train-mode rollout ("carry
     autograd graph in training").  backward = ``jn_reinforce_backward`` with the upstream gradients torch hands over, then
@@ -65,10 +74,12 @@ class _RolloutCall:
     ``JnRolloutOut``, the mode with its device inputs, and — the runner's rollout counter moved on — the seed and the
     agent keys of that rollout number."""
 
-    def __init__(self, runner, env, sample_actions, forced_actions, start_positions, agent_keys, classes, token_positions):
+    def __init__(self, runner, env, sample_actions, forced_actions, start_positions, agent_keys, classes, token_positions,
+                 action_mask=None):
         model, dev = runner.model, runner.device
         B = env.batch_size
         self.classes = None if classes is None else _classes_table(classes, B)       # checked before any engine call
+        self.mask_policy = _mask_policy(action_mask if action_mask is not None else getattr(runner, "action_mask", None))
         if token_positions is None:
             token_positions = "sequence" if getattr(model.config, "no_recurrent_embedding", False) else "recurrent"
         if token_positions not in ("sequence", "recurrent"):
@@ -110,6 +121,8 @@ class _RolloutCall:
         self.keys = runner._agent_keys_table(agent_keys, B)
         self.stream = _lib.current_stream(dev)
         self.teacher = None       # (targets [B,Gh,Gw] or None, sets [B,T]) on the device once the caller wants the teacher
+        # the action sets the decisions were made under, [B,T] uint16 bit patterns (torch has no dependable uint16)
+        self.action_sets = torch.empty((B, T), device=dev, dtype=torch.int16) if self.mask_policy else None
 
     @contextlib.contextmanager
     def armed(self):
@@ -126,6 +139,8 @@ class _RolloutCall:
             switches.append(("jn_set_rollout_positions", (1,), (0,)))
         if self.teacher is not None:
             switches.append(("jn_set_rollout_teacher", tuple(ptr(t) for t in self.teacher), (None, None)))
+        if self.mask_policy:
+            switches.append(("jn_set_rollout_action_mask", (self.mask_policy, ptr(self.action_sets)), (0, None)))
         try:
             for name, on, _ in switches:
                 check(getattr(lib, name)(h, *on), name)
@@ -140,8 +155,10 @@ class RolloutRunner:
     and all ``ragged`` / ``infer`` read of a trainer.  `agent_streams`: "batch", or "global" for
     ``dist.shard_agent_keys`` of this rank (checked at the rollout)."""
 
-    def __init__(self, model, max_ep_len: int, stop_enabled: bool, seed: int = 0, rank: int = 0, agent_streams: str = "batch"):
+    def __init__(self, model, max_ep_len: int, stop_enabled: bool, seed: int = 0, rank: int = 0, agent_streams: str = "batch",
+                 action_mask: str = None):
         self.model, self.device, self.patch_size = model, model.device, model.patch_size
+        self.action_mask = action_mask      # what a rollout without an `action_mask` of its own runs under (config.action_mask)
         self.max_ep_len, self.stop_enabled, self.n_glimps_levels = max_ep_len, stop_enabled, 1
         self.seed, self.rank, self.agent_streams = int(seed), rank, agent_streams
         self._rollouts = 0
@@ -150,7 +167,8 @@ class RolloutRunner:
                 forced_actions: torch.Tensor = None, start_positions: torch.Tensor = None,
                 keep_patches: bool = True, stop_early: bool = True, bbox_lists: bool = True,
                 token_positions: str = None, teacher: bool = False,
-                teacher_targets: torch.Tensor = None, agent_keys=None, classes=None) -> Dict[str, torch.Tensor]:
+                teacher_targets: torch.Tensor = None, agent_keys=None, classes=None,
+                action_mask: str = None) -> Dict[str, torch.Tensor]:
         """src/reinforce.py:108-215.  Extra keyword arguments (not in the reference):
         `forced_actions` [B,T] replays a trajectory, `start_positions` [B,2] injects reset
         positions (reference: env.reset(positions)), `keep_patches=False` skips the
@@ -173,9 +191,15 @@ class RolloutRunner:
         `classes` [B] integers (a tensor on any device or a sequence): agent b's class token is row classes[b] of
         ``embed_class`` (``jn_set_rollout_classes``), what ``test_model_on_env`` feeds a class-conditioned policy
         (src/supervised.py:317-331); in train mode the class token's gradient goes to those rows, whenever the backward
-        runs.  None = row 0 for every agent, the reference's REINFORCE loop (src/reinforce.py:128-129)."""
+        runs.  None = row 0 for every agent, the reference's REINFORCE loop (src/reinforce.py:128-129).
+        `action_mask`: "grid" lets no decision pick a move that leaves the agent's grid, "unvisited" none that re-enters a
+        visited cell while a fresh neighbour exists (``jn_set_rollout_action_mask``; not in the reference, whose env clamps):
+        log-probs, entropies, the greedy choice and the samples are those of the softmax over the allowed actions, and
+        "action_sets" [B,S] (int64, bit a = action a allowed) holds the sets.  In train mode the backward differentiates
+        under the same sets.  None = ``config.action_mask`` (default None: no masking, no "action_sets")."""
         model, dev = self.model, self.device
-        call = _RolloutCall(self, env, sample_actions, forced_actions, start_positions, agent_keys, classes, token_positions)
+        call = _RolloutCall(self, env, sample_actions, forced_actions, start_positions, agent_keys, classes, token_positions,
+                            action_mask)
         eng, buf, out, stream = call.eng, call.buf, call.out, call.stream
         B, T, P = env.batch_size, env.max_ep_len, env.patch_size
         f32 = dict(device=dev, dtype=torch.float32)
@@ -226,6 +250,8 @@ class RolloutRunner:
         }
         if teacher:
             res["teacher_sets"] = sets[:, :S]
+        if call.action_sets is not None:
+            res["action_sets"] = call.action_sets[:, :S].to(torch.int64) & 0xFFFF
         if do_detection and bbox_lists:       # ragged list-of-lists of [n,7] | None (src/reinforce.py:145-146, 166-167)
             cnt = det_counts[:, :S + 1].tolist()
             res["bboxes"] = [[det_boxes[b, t, :cnt[b][t]].clone() if cnt[b][t] > 0 else None for t in range(S + 1)]

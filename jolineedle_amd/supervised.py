@@ -241,13 +241,14 @@ class SupervisedTrainer(Trainer):
         if self._runner is None:
             cfg = self.config
             self._runner = RolloutRunner(self.model, int(getattr(cfg, "test_max_seq_len", None) or cfg.max_seq_len),
-                                         bool(getattr(cfg, "stop_enabled", False)), int(getattr(cfg, "seed", 0)), self.rank)
+                                         bool(getattr(cfg, "stop_enabled", False)), int(getattr(cfg, "seed", 0)), self.rank,
+                                         action_mask=getattr(cfg, "action_mask", None))
         return self._runner
 
     @torch.no_grad()
     def eval_on_images(self, images, bboxes, batch_size: int, sample_actions: bool = False, do_detection: bool = None,
                        merge_bboxes: bool = None, device_metrics: bool = False, streams: str = "loop",
-                       class_ids=None) -> Dict[str, list]:
+                       class_ids=None, action_mask: str = None) -> Dict[str, list]:
         """The free-running half of the reference's ``test()``: ``test_model_on_env`` (src/supervised.py:279-405) lets the
         policy walk one image, calling the full-sequence forward again at every step, and compares every chosen action
         with the teacher's ``best_action``.  Here the walks are the engine's rollouts with the token of step t at 1-D
@@ -268,6 +269,7 @@ class SupervisedTrainer(Trainer):
         `class_ids`: one class per image (a tensor or a sequence): the class token of image i's walk is row class_ids[i]
         of ``embed_class``, as ``test_model_on_env`` feeds ``classes=sample["class_id"]`` at every step
         (src/supervised.py:284, 317-331); None = class 0 for every walk.
+        `action_mask`: "grid" / "unvisited" / None (``config.action_mask``), see ``RolloutRunner.rollout``.
         Deviations from the reference: DESIGN.md §6."""
         from .ragged import eval_image_chunks
         if do_detection is None:
@@ -275,7 +277,7 @@ class SupervisedTrainer(Trainer):
         if merge_bboxes is None:
             merge_bboxes = bool(getattr(self.config, "merge_bboxes", False))
         chunks = self._eval_walks(images, bboxes, batch_size, do_detection, sample_actions=sample_actions, streams=streams,
-                                  class_ids=class_ids)
+                                  class_ids=class_ids, action_mask=action_mask)
         return self._walk_metrics(eval_image_chunks(self._eval_runner(), self.yolox_model() if do_detection else None, chunks,
                                                     do_detection, merge_bboxes, device_metrics))
 
@@ -318,7 +320,7 @@ class SupervisedTrainer(Trainer):
     @torch.no_grad()
     def eval_envs_on_images(self, images, bboxes, batch_size: int, eval_mode: str = "multistart", n_starts: int = 2,
                             sample_actions: bool = False, start_positions=None, device_metrics: bool = True,
-                            streams: str = "loop", class_ids=None) -> Dict[str, list]:
+                            streams: str = "loop", class_ids=None, action_mask: str = None) -> Dict[str, list]:
         """``eval_envs`` of the reference (src/supervised.py:638-752) without its plots — the evaluation whose `map` at one
         start selects ``checkpoint_best.pt`` (:81, :804): every image is walked from K starts and, for every prefix
         k = 1..K of those walks, the detections of the walks are pooled per visited patch, de-duplicated by an NMS at
@@ -336,6 +338,7 @@ class SupervisedTrainer(Trainer):
         tokens of a walk are t = 0 .. its own steps, the last patch reached included (:354-363).
         `class_ids`: one class per image; all K walks of image i run under class_ids[i], as ``eval_envs`` hands the image's
         ``class_id`` to every ``test_model_on_env`` call (:663-687).  None = class 0 for every walk.
+        `action_mask`: "grid" / "unvisited" / None (``config.action_mask``), see ``RolloutRunner.rollout``.
 
         Returns lists.  One entry per WALK, in image order then walk order (:694-695): `prop_patches_found`,
         `episode_length`, `teacher_agreement`, `stopped_inside_bbox` as ``eval_on_images`` reports them.  One entry per
@@ -382,7 +385,7 @@ class SupervisedTrainer(Trainer):
 
         per_walk = {}
         for ch in self._eval_walks(images, bboxes, batch_size, True, sample_actions=sample_actions, walks=K, walk_starts=starts,
-                                   streams=streams, class_ids=class_ids):
+                                   streams=streams, class_ids=class_ids, action_mask=action_mask):
             for a, tail, ro_b in ragged.walk_entries(runner, ch):
                 per_walk[a] = (tail, ro_b)
             ro, env, sel = ch["rollout"], ch["env"], ch["indices"]
